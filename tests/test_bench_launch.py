@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,7 +36,7 @@ def test_gpus_2_without_a_launcher_runs_two_ranks():
     one-GPU box the two ranks share device 0 (CAPGPU_ALLOW_DUPLICATE_DEVICES=1, gloo) - what matters is that the line
     says n_gpus 2 and names what was bound"""
     small = [a for a in SMALL if a != "--no-cpu-baseline"]
-    r = run_bench(["--gpus", "2", "--msm-log-n", "14"] + small, {"CAPGPU_ALLOW_DUPLICATE_DEVICES": "1"})
+    r = run_bench(["--gpus", "2", "--full", "--msm-log-n", "14"] + small, {"CAPGPU_ALLOW_DUPLICATE_DEVICES": "1"})
     assert r.returncode == 0, r.stderr[-1500:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -80,7 +81,7 @@ def test_preflight_stops_a_launch_whose_ranks_share_a_device():
 
 @pytest.mark.gpu
 def test_single_process_model_reports_its_devices():
-    r = run_bench(["--single-process", "--devices", "0,0", "--msm-log-n", "15"] + SMALL,
+    r = run_bench(["--single-process", "--full", "--devices", "0,0", "--msm-log-n", "15"] + SMALL,
                   {"CAPGPU_ALLOW_DUPLICATE_DEVICES": "1", "CAPGPU_SHARD_MIN_POINTS": "4096"})
     assert r.returncode == 0, r.stderr[-1500:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
@@ -89,3 +90,30 @@ def test_single_process_model_reports_its_devices():
     m = out["msm"][0]
     assert m["shards"] == 2 and m["identity_check"] is True
     assert m["bytes_between_devices_per_call"] == {"scalars": 0, "partials": 96}
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_only_and_dumps_its_last_step(tmp_path):
+    """A plain run sets up, warms up, times exactly --steps steps and prints the line; --dump-outputs writes the proofs of
+    the last timed step.  --full adds the secondary legs and proves the same batch: the dumps are identical."""
+    small = SMALL + ["--no-msm", "--steps", "3"]
+    r = run_bench(small + ["--dump-outputs", str(tmp_path / "plain")])
+    assert r.returncode == 0, r.stderr[-1500:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0
+    assert abs(out["value"] * out["ms_per_step"] / 1e3 - 8) < 1e-6      # 8 proofs per step
+    assert "one_context_profiled_pass" not in out and out["top_kernels_ms"] == {}
+    assert out["roofline"] is None and "device_memory_in_use_GB" not in out["config"]
+    r = run_bench(small + ["--full", "--dump-outputs", str(tmp_path / "full")])
+    assert r.returncode == 0, r.stderr[-1500:]
+    full = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
+    assert full["one_context_profiled_pass"]["same_proofs_as_the_headline"] is True
+    assert full["roofline"]["kernel"] and "device_memory_in_use_GB" in full["config"]
+    names = sorted(os.listdir(tmp_path / "plain"))
+    assert "wires_poly_comms.npy" in names and "proof_index.npy" in names and names == sorted(os.listdir(tmp_path / "full"))
+    for name in names:
+        a, b = np.load(tmp_path / "plain" / name), np.load(tmp_path / "full" / name)
+        assert a.dtype == np.float64 and a.shape[0] == 8 and np.array_equal(a, b), name
+    assert np.load(tmp_path / "plain" / "wires_poly_comms.npy").shape == (8, 5, 16)

@@ -63,3 +63,43 @@ def test_algorithmic_bytes_are_the_survey_figures():
     assert ab["msm_pairs"] == 13 * ((1 << 15) + 2) + 1
     assert ab["ntt_elems"] == 7 * (1 << 15) + 26 * 8 * (1 << 15)
     assert abs(ab["total_bytes"] / 1e9 - 0.4918) < 5e-4
+
+
+def test_dump_outputs_writes_every_proof_word_exactly(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one float64 file per proof field, each uint64 word as its two 32-bit halves (low first),
+    rows in batch order; above the size limit a fixed, seeded sample of whole proofs"""
+    import importlib.util
+    import os
+
+    import numpy as np
+
+    from cap_amd import lib as cg
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_dump", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(1)
+    proofs = []
+    for _ in range(5):
+        p = cg.Proof()
+        for name, _t in cg.Proof._fields_:
+            a = np.ctypeslib.as_array(getattr(p, name))
+            a[...] = rng.integers(0, 2 ** 64, size=a.shape, dtype=np.uint64)
+        proofs.append(p)
+    bench.dump_outputs(cg, proofs, str(tmp_path / "all"))
+    assert sorted(os.listdir(tmp_path / "all")) == sorted([f + ".npy" for f, _t in cg.Proof._fields_] + ["proof_index.npy"])
+    for name, _t in cg.Proof._fields_:
+        got = np.load(tmp_path / "all" / (name + ".npy"))
+        assert got.dtype == np.float64
+        w = got.astype(np.uint64)
+        back = w[..., 0::2] | (w[..., 1::2] << np.uint64(32))
+        assert np.array_equal(back, np.stack([np.ctypeslib.as_array(getattr(p, name)) for p in proofs])), name
+    assert np.array_equal(np.load(tmp_path / "all" / "proof_index.npy"), np.arange(5))
+    per_proof = 2 * 8 * (13 * 8 + 10 * 4) + 8
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", (1 << 16) + 2 * per_proof)
+    bench.dump_outputs(cg, proofs, str(tmp_path / "s1"))
+    bench.dump_outputs(cg, proofs, str(tmp_path / "s2"))
+    idx = np.load(tmp_path / "s1" / "proof_index.npy")
+    assert len(idx) == 2 and np.array_equal(idx, np.load(tmp_path / "s2" / "proof_index.npy"))
+    full = np.load(tmp_path / "all" / "opening_proof.npy")
+    assert np.array_equal(np.load(tmp_path / "s1" / "opening_proof.npy"), full[idx.astype(int)])

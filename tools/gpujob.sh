@@ -3,7 +3,7 @@
 # rounds 1-5 are gone - their results live in profiles/, their text in the git history, tools/README.md has the table).
 #   /usr/local/graft/bin/gpurun --timeout 2400 -- 'bash tools/gpujob.sh JOB [ARGS...]'
 # Outputs land under gpurun_out/ (scratch); what is kept is copied to profiles/ by hand or by tools/refresh_profiles.py.
-#   suite TAG                 pytest -m gpu, smoke(), default bench.py
+#   suite TAG                 pytest -m gpu, smoke(), bench.py --full
 #   final TAG                 round-end evidence in one call: suite, 20-step / mixed64 / single-process bench, single-MSM profile,
 #                             rocprofv3 stats + PMC traffic, instruction counters, clocks, world-2 (gloo) lines, phase traces
 #   prof TAG                  rocprofv3 --kernel-trace --stats, then FETCH_SIZE / WRITE_SIZE passes (separate runs) + summary
@@ -14,7 +14,7 @@
 #   ntt TAG LIB...            device time of batches of coset NTTs for several library builds (tools/gpu_ntt_time.py)
 #   phase TAG [VAR=VAL...]    host-side phase traces of the host-witness and coalesced paths (tools/gpu_phase_trace.py)
 #   campaign TAG [SEED]       fuzz / stress campaign: prover, primitives, parameter blobs, threads, leaks, graph capture
-#   w2                        bench.py --gpus 2 on this one GPU (gloo, shared device): the N > 1 line and its wall time
+#   w2                        bench.py --gpus 2 --full on this one GPU (gloo, shared device): the N > 1 line and its wall time
 #   ubench NAME               build and run tools/ubench_NAME.hip (microbenchmarks behind DESIGN.md's numbers)
 job=$1; shift
 case "$job" in
@@ -23,7 +23,7 @@ suite)
   O=gpurun_out/suite_$tag; mkdir -p $O
   timeout 1500 python -m pytest tests -m gpu -q --durations=10 --timeout=300 > $O/pytest_gpu.txt 2>&1; tail -3 $O/pytest_gpu.txt
   python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; tail -1 $O/smoke.txt
-  S0=$SECONDS; timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench.py wall $((SECONDS-S0)) s"; tail -c 2000 $O/bench.json; echo
+  S0=$SECONDS; timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench.py --full wall $((SECONDS-S0)) s"; tail -c 2000 $O/bench.json; echo
   ;;
 final)
   tag=$1
@@ -31,11 +31,11 @@ final)
   mkdir -p $O
   timeout 1500 python -m pytest tests -m gpu -q --durations=10 --timeout=300 > $O/pytest_gpu.txt 2>&1; tail -3 $O/pytest_gpu.txt
   python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; tail -1 $O/smoke.txt
-  S0=$SECONDS; timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "driver command wall $((SECONDS-S0)) s"; tail -c 300 $O/bench.err
+  S0=$SECONDS; timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "driver command wall $((SECONDS-S0)) s"; tail -c 300 $O/bench.err
   bash tools/gpujob.sh phase $tag > $O/phase.log 2>&1; cp gpurun_out/phase_$tag/phase.jsonl $O/phase.jsonl
-  timeout 600 python bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-reference-schedule --no-msm > $O/bench_20steps.json 2>/dev/null
-  timeout 600 python bench.py --workload mixed64 --steps 12 --warmup 3 --no-msm > $O/bench_mixed64.json 2>/dev/null
-  CAPGPU_ALLOW_DUPLICATE_DEVICES=1 timeout 600 python bench.py --single-process --devices 0,0 --batch 128 --steps 4 --warmup 1 --msm-log-n 22 > $O/bench_single_process.json 2>/dev/null
+  timeout 600 python bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-reference-schedule --no-msm > $O/bench_20steps.json 2>/dev/null
+  timeout 600 python bench.py --full --workload mixed64 --steps 12 --warmup 3 --no-msm > $O/bench_mixed64.json 2>/dev/null
+  CAPGPU_ALLOW_DUPLICATE_DEVICES=1 timeout 600 python bench.py --full --single-process --devices 0,0 --batch 128 --steps 4 --warmup 1 --msm-log-n 22 > $O/bench_single_process.json 2>/dev/null
   MINLOG=21 timeout 300 python tools/gpu_msm_deep_ab.py 24 > $O/msm_deep_ab.jsonl 2>/dev/null
   timeout 300 python tools/gpu_two_ctx.py 15 256 2>/dev/null | tail -1 > $O/two_ctx.json
   timeout 600 python tools/gpu_latency_ab.py --quick > $O/latency_ab.jsonl 2>/dev/null
@@ -105,11 +105,12 @@ clock)
   R=$GRAFT_REPO_ROOT
   cd $R
   mkdir -p gpurun_out/clock_$tag
+  D=$_                          # (the directory just made; --full: the issue-rate launches clock.json compares with)
   for ctr in GRBM_GUI_ACTIVE GRBM_COUNT SQ_BUSY_CU_CYCLES SQ_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY; do
-    timeout 240 rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d gpurun_out/clock_$tag/$ctr -- python3 bench.py --one-context --steps 1 --warmup 1 --no-cpu-baseline --no-reference-schedule --no-msm --no-extras > /dev/null 2> gpurun_out/clock_$tag/$ctr.err
+    timeout 240 rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $D/$ctr -- python3 bench.py --full --one-context --steps 1 --warmup 1 --no-cpu-baseline --no-reference-schedule --no-msm --no-extras > /dev/null 2> $D/$ctr.err
   done
   # the two counters of the busy share in ONE pass (the same dispatches, the same clock)
-  timeout 240 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_BUSY_CU_CYCLES --kernel-trace --output-format csv -d gpurun_out/clock_$tag/PAIR -- python3 bench.py --one-context --steps 1 --warmup 1 --no-cpu-baseline --no-reference-schedule --no-msm --no-extras > /dev/null 2> gpurun_out/clock_$tag/PAIR.err
+  timeout 240 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_BUSY_CU_CYCLES --kernel-trace --output-format csv -d $D/PAIR -- python3 bench.py --full --one-context --steps 1 --warmup 1 --no-cpu-baseline --no-reference-schedule --no-msm --no-extras > /dev/null 2> $D/PAIR.err
   python3 - <<PY
 import csv, glob, collections, json
 out = {}
@@ -164,7 +165,7 @@ ab)
   TAG=$1; shift
   OUT=gpurun_out/abn_$TAG
   mkdir -p $OUT
-  ARGS="--steps 4 --warmup 2 --no-cpu-baseline --no-reference-schedule --no-msm --no-extras"
+  ARGS="--full --steps 4 --warmup 2 --no-cpu-baseline --no-reference-schedule --no-msm --no-extras"
   python bench.py $ARGS > $OUT/base.json 2> $OUT/base.err
   i=0
   for L in "$@"; do
@@ -186,8 +187,9 @@ PY
 env)
   tag=$1; shift
   mkdir -p gpurun_out
+  D=$_                          # (the directory just made)
   for kv in "$@"; do export "$kv"; done
-  python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-reference-schedule --no-msm > gpurun_out/bench_$tag.json 2> gpurun_out/bench_$tag.err
+  python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-reference-schedule --no-msm > $D/bench_$tag.json 2> $D/bench_$tag.err
   python - <<PY
 import json
 d=json.load(open("gpurun_out/bench_$tag.json"))
@@ -231,10 +233,11 @@ campaign)
   ;;
 w2)
   mkdir -p gpurun_out
+  D=$_                          # (the directory just made)
   S0=$SECONDS
-  CAPGPU_ALLOW_DUPLICATE_DEVICES=1 timeout 900 python bench.py --gpus 2 > gpurun_out/bench_w2.json 2> gpurun_out/bench_w2.err
+  CAPGPU_ALLOW_DUPLICATE_DEVICES=1 timeout 900 python bench.py --gpus 2 --full > $D/bench_w2.json 2> $D/bench_w2.err
   echo "rc=$? bench.py --gpus 2 (one GPU shared by both ranks, gloo) wall $((SECONDS-S0)) s"; tail -c 1500 gpurun_out/bench_w2.json; echo
-  CAPGPU_ALLOW_DUPLICATE_DEVICES=1 timeout 600 python bench.py --gpus 2 --workload mixed64 --steps 2 --warmup 1 --no-msm > gpurun_out/bench_w2_mixed.json 2> gpurun_out/bench_w2_mixed.err
+  CAPGPU_ALLOW_DUPLICATE_DEVICES=1 timeout 600 python bench.py --gpus 2 --full --workload mixed64 --steps 2 --warmup 1 --no-msm > $D/bench_w2_mixed.json 2> $D/bench_w2_mixed.err
   echo "rc=$?"; tail -c 600 gpurun_out/bench_w2_mixed.json; echo
   ;;
 ubench)
