@@ -207,6 +207,14 @@ extern "C" {
                                          num_inputs: *const usize, proofs: *const *const capgpu_proof,
                                          ext_msgs: *const *const u8, ext_msg_lens: *const usize, count: usize,
                                          ok_out: *mut c_int) -> c_int;
+    // ---- per-proof verification on the device
+    pub fn capgpu_pairing_check_pairs_dev(p: *const u64, r: *const u64, count: usize, q1: *const u64, q2: *const u64,
+                                          ok_out: *mut c_int) -> c_int;
+    pub fn capgpu_plonk_verify_each_dev(vks: *const *const capgpu_verifying_key, g2_h: *const u64,
+                                        g2_beta_h: *const u64, pub_inputs: *const *const u64,
+                                        num_inputs: *const usize, proofs: *const *const capgpu_proof,
+                                        ext_msgs: *const *const u8, ext_msg_lens: *const usize, count: usize,
+                                        ok_out: *mut c_int) -> c_int;
     pub fn capgpu_proof_serialize(proof: *const capgpu_proof, out: *mut u8, cap: usize, len_out: *mut usize) -> c_int;
     pub fn capgpu_proof_deserialize(bytes: *const u8, len: usize, proof_out: *mut capgpu_proof,
                                     consumed_out: *mut usize) -> c_int;

@@ -16,6 +16,7 @@
 #include "../../include/capgpu.h"
 #include "host_util.hpp"
 #include "pairing.hpp"
+#include "verify_terms.hpp"
 
 namespace cap {
 void set_error(const char* fmt, ...);
@@ -315,18 +316,17 @@ static std::vector<fe> batch_weights(const std::vector<ProofTerms>& pt) {
   return rs;
 }
 
-// terms of every proof of a batch, in parallel on host threads; returns a negative code for malformed arguments,
-// *all_valid = 0 when some proof is already known to be invalid
-static int batch_terms(const capgpu_verifying_key* const* vks, const uint64_t* const* pub_inputs,
-                       const size_t* num_inputs, const capgpu_proof* const* proofs, const uint8_t* const* ext_msgs,
-                       const size_t* ext_msg_lens, size_t count, std::vector<ProofTerms>* out, int* all_valid) {
+// verifier_terms of every proof of a batch, in parallel on host threads: rcs[i] its return code, valids[i] its verdict
+static void prepare_terms_parallel(const capgpu_verifying_key* const* vks, const uint64_t* const* pub_inputs,
+                                   const size_t* num_inputs, const capgpu_proof* const* proofs,
+                                   const uint8_t* const* ext_msgs, const size_t* ext_msg_lens, size_t count,
+                                   std::vector<ProofTerms>* out, std::vector<int>* rcs, std::vector<int>* valids) {
   out->assign(count, ProofTerms{});
-  std::vector<int> rcs(count, CAPGPU_OK), valids(count, 0);
-  for (size_t i = 0; i < count; i++)
-    if (!vks[i] || !proofs[i] || (num_inputs[i] && !pub_inputs[i])) return CAPGPU_ERR_INVALID_ARG;
+  rcs->assign(count, CAPGPU_OK);
+  valids->assign(count, 0);
   auto prepare = [&](size_t i) {
-    rcs[i] = verifier_terms(vks[i], pub_inputs[i], num_inputs[i], proofs[i], ext_msgs ? ext_msgs[i] : nullptr,
-                            (ext_msgs && ext_msg_lens) ? ext_msg_lens[i] : 0, &(*out)[i], &valids[i]);
+    (*rcs)[i] = verifier_terms(vks[i], pub_inputs[i], num_inputs[i], proofs[i], ext_msgs ? ext_msgs[i] : nullptr,
+                               (ext_msgs && ext_msg_lens) ? ext_msg_lens[i] : 0, &(*out)[i], &(*valids)[i]);
   };
   const unsigned nt = (unsigned)std::min<size_t>(count, std::max(1u, std::min(std::thread::hardware_concurrency(), 32u)));
   if (nt <= 1) {
@@ -345,14 +345,34 @@ static int batch_terms(const capgpu_verifying_key* const* vks, const uint64_t* c
     work();
     for (auto& t : th) t.join();
   }
+}
+// the message of a failing proof was recorded on a worker thread: redo that one here for this thread's string
+static int redo_for_error(const capgpu_verifying_key* const* vks, const uint64_t* const* pub_inputs,
+                          const size_t* num_inputs, const capgpu_proof* const* proofs, const uint8_t* const* ext_msgs,
+                          const size_t* ext_msg_lens, size_t i) {
+  int v = 0;
+  ProofTerms scratch;
+  return verifier_terms(vks[i], pub_inputs[i], num_inputs[i], proofs[i], ext_msgs ? ext_msgs[i] : nullptr,
+                        (ext_msgs && ext_msg_lens) ? ext_msg_lens[i] : 0, &scratch, &v);
+}
+static bool args_present(const capgpu_verifying_key* const* vks, const uint64_t* const* pub_inputs,
+                         const size_t* num_inputs, const capgpu_proof* const* proofs, size_t count) {
+  for (size_t i = 0; i < count; i++)
+    if (!vks[i] || !proofs[i] || (num_inputs[i] && !pub_inputs[i])) return false;
+  return true;
+}
+
+// terms of every proof of a batch, in parallel on host threads; returns a negative code for malformed arguments,
+// *all_valid = 0 when some proof is already known to be invalid
+static int batch_terms(const capgpu_verifying_key* const* vks, const uint64_t* const* pub_inputs,
+                       const size_t* num_inputs, const capgpu_proof* const* proofs, const uint8_t* const* ext_msgs,
+                       const size_t* ext_msg_lens, size_t count, std::vector<ProofTerms>* out, int* all_valid) {
+  if (!args_present(vks, pub_inputs, num_inputs, proofs, count)) return CAPGPU_ERR_INVALID_ARG;
+  std::vector<int> rcs, valids;
+  prepare_terms_parallel(vks, pub_inputs, num_inputs, proofs, ext_msgs, ext_msg_lens, count, out, &rcs, &valids);
   *all_valid = 1;
   for (size_t i = 0; i < count; i++) {
-    if (rcs[i]) {  // the message was recorded on a worker thread: redo the failing one here for this thread's string
-      int v = 0;
-      ProofTerms scratch;
-      return verifier_terms(vks[i], pub_inputs[i], num_inputs[i], proofs[i], ext_msgs ? ext_msgs[i] : nullptr,
-                            (ext_msgs && ext_msg_lens) ? ext_msg_lens[i] : 0, &scratch, &v);
-    }
+    if (rcs[i]) return redo_for_error(vks, pub_inputs, num_inputs, proofs, ext_msgs, ext_msg_lens, i);
     if (!valids[i]) *all_valid = 0;
   }
   return CAPGPU_OK;
@@ -555,3 +575,33 @@ int capgpu_proof_serialize(const capgpu_proof* proof, uint8_t* out, size_t cap, 
 }
 
 }  // extern "C"
+
+// ---- for the per-proof device verifier (verify_dev.hip) ----------------------------------------------------------
+namespace cap {
+// The per-proof sibling of batch_terms: the same terms on the same host threads, one validity flag per proof
+int batch_terms_each(const capgpu_verifying_key* const* vks, const uint64_t* const* pub_inputs,
+                     const size_t* num_inputs, const capgpu_proof* const* proofs, const uint8_t* const* ext_msgs,
+                     const size_t* ext_msg_lens, size_t count, std::vector<EachTerms>* out) {
+  if (!args_present(vks, pub_inputs, num_inputs, proofs, count)) return CAPGPU_ERR_INVALID_ARG;
+  std::vector<ProofTerms> pt;
+  std::vector<int> rcs, valids;
+  prepare_terms_parallel(vks, pub_inputs, num_inputs, proofs, ext_msgs, ext_msg_lens, count, &pt, &rcs, &valids);
+  for (size_t i = 0; i < count; i++)
+    if (rcs[i]) return redo_for_error(vks, pub_inputs, num_inputs, proofs, ext_msgs, ext_msg_lens, i);
+  out->assign(count, EachTerms{});
+  for (size_t i = 0; i < count; i++) {
+    EachTerms& e = (*out)[i];
+    e.valid = valids[i];
+    if (!e.valid) continue;
+    for (const Term& t : pt[i].a) e.a.push_back(EachTerm{t.p, Fr::from_mont(t.s)});
+    for (const Term& t : pt[i].b) e.b.push_back(EachTerm{t.p, Fr::from_mont(t.s)});
+  }
+  return CAPGPU_OK;
+}
+int open_key_from_abi(const uint64_t g2_h[16], const uint64_t g2_beta_h[16], g2_affine* h, g2_affine* beta_h) {
+  return ::load_open_key(g2_h, g2_beta_h, h, beta_h);
+}
+g2_affine g2_from_abi(const uint64_t w[16]) { return g2_from_words(w); }
+g1_affine g1_from_abi(const uint64_t w[8]) { return g1_from_words(w); }
+bool g1_abi_on_curve(const g1_affine& p) { return g1_on_curve(p); }
+}  // namespace cap

@@ -773,6 +773,47 @@ def plonk_batch_verify(vks, g2_h: np.ndarray, g2_beta_h: np.ndarray, pub_inputs_
     return bool(ok.value)
 
 
+# ---- per-proof verification on the device (needs init()) ------------------------------------------------------
+def pairing_check_pairs_dev(p: np.ndarray, r: np.ndarray, q1: np.ndarray, q2: np.ndarray) -> np.ndarray:
+    """ok[i] = (e(p[i], q1) e(r[i], q2) == 1), one check per GPU lane; p, r: (count, 8) affine G1 words (all-zero =
+    infinity), q1, q2: 16-word twist points."""
+    p = np.ascontiguousarray(p, dtype=np.uint64).reshape(-1, 8)
+    r = np.ascontiguousarray(r, dtype=np.uint64).reshape(-1, 8)
+    if p.shape != r.shape:
+        raise ValueError("pairing_check_pairs_dev: p and r must hold the same number of points")
+    cnt = p.shape[0]
+    ok = np.zeros(max(cnt, 1), dtype=np.int32)
+    check(load().capgpu_pairing_check_pairs_dev(_p(p.reshape(-1)) if cnt else None, _p(r.reshape(-1)) if cnt else None,
+                                                ctypes.c_size_t(cnt), _p(np.ascontiguousarray(q1, dtype=np.uint64)),
+                                                _p(np.ascontiguousarray(q2, dtype=np.uint64)),
+                                                ok.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+    return ok[:cnt] != 0
+
+
+def plonk_verify_each(vks, g2_h: np.ndarray, g2_beta_h: np.ndarray, pub_inputs_list, proofs,
+                      ext_msgs=None) -> np.ndarray:
+    """One verdict per proof (capgpu_plonk_verify_each_dev): ok[i] == plonk_verify(vks[i], ..., proofs[i]).  The group
+    arithmetic and the pairing check of every proof run on the GPU: finds the bad proofs of a batch that
+    plonk_batch_verify rejected."""
+    cnt = len(proofs)
+    n = max(cnt, 1)
+    vk_arr = (ctypes.POINTER(VerifyingKey) * n)(*[ctypes.pointer(v) for v in vks])
+    pubs = [np.ascontiguousarray(p, dtype=np.uint64).reshape(-1) for p in pub_inputs_list]
+    pub_arr = (u64p * n)(*[(_p(p) if p.size else None) for p in pubs])
+    nin = (ctypes.c_size_t * n)(*[p.size // 4 for p in pubs])
+    pr_arr = (ctypes.POINTER(Proof) * n)(*[ctypes.pointer(p) for p in proofs])
+    msgs = [(m if m is not None else b"") for m in (ext_msgs or [None] * cnt)]
+    bufs = [(ctypes.c_uint8 * max(len(m), 1)).from_buffer_copy(m + (b"\0" if not m else b"")) for m in msgs]
+    msg_arr = (ctypes.POINTER(ctypes.c_uint8) * n)(*[ctypes.cast(b, ctypes.POINTER(ctypes.c_uint8)) for b in bufs])
+    len_arr = (ctypes.c_size_t * n)(*[len(m) for m in msgs])
+    ok = np.zeros(n, dtype=np.int32)
+    check(load().capgpu_plonk_verify_each_dev(vk_arr, _p(np.ascontiguousarray(g2_h, dtype=np.uint64)),
+                                              _p(np.ascontiguousarray(g2_beta_h, dtype=np.uint64)), pub_arr, nin,
+                                              pr_arr, msg_arr, len_arr, ctypes.c_size_t(cnt),
+                                              ok.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+    return ok[:cnt] != 0
+
+
 def proof_serialize(proof: Proof) -> bytes:
     buf = (ctypes.c_uint8 * 1024)()
     n = ctypes.c_size_t(0)

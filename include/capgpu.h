@@ -475,6 +475,24 @@ int capgpu_plonk_batch_verify_dev(const capgpu_verifying_key* const* vks, const 
                                   const uint64_t g2_beta_h[16], const uint64_t* const* pub_inputs,
                                   const size_t* num_inputs, const capgpu_proof* const* proofs,
                                   const uint8_t* const* ext_msgs, const size_t* ext_msg_lens, size_t count, int* ok_out);
+/* ---- per-proof verification on the device (needs capgpu_init; CAPGPU_ERR_NOT_INITIALISED otherwise, no host path) --
+ * Runs on the calling thread's bound context.  The pairing check is device code (Fq12 tower, Miller loop over prepared
+ * lines of the two G2 points, final exponentiation: one check per lane). */
+/* ok_out[i] = (e(p_i, q1) * e(r_i, q2) == 1) for i < count; p, r: count affine G1 points (8 words, Montgomery,
+ * all-zero = infinity); q1, q2: twist points (16 words).  Off-curve input: CAPGPU_ERR_INVALID_ARG naming the index.
+ * The two-pair, many-times form of capgpu_pairing_check (same verdict for each i). */
+int capgpu_pairing_check_pairs_dev(const uint64_t* p, const uint64_t* r, size_t count, const uint64_t q1[16],
+                                   const uint64_t q2[16], int* ok_out);
+/* One verdict per proof, arguments as capgpu_plonk_batch_verify_dev; ok_out: count ints.  Replaces the loop of
+ * TransferNote::verify (src/transfer.rs:345-363) that finds the bad notes of a block txn_batch_verify rejected:
+ * ok_out[i] equals what capgpu_plonk_verify gives for proof i.  A proof that is off-curve, non-canonical, has zeta in
+ * the domain or fails its pairing gets 0 and the call still returns CAPGPU_OK; negative codes only for the malformed
+ * arguments capgpu_plonk_batch_verify rejects.  Transcripts and scalars on host threads; each proof's ~35 scalar
+ * multiplications and its pairing check on the device. */
+int capgpu_plonk_verify_each_dev(const capgpu_verifying_key* const* vks, const uint64_t g2_h[16],
+                                 const uint64_t g2_beta_h[16], const uint64_t* const* pub_inputs,
+                                 const size_t* num_inputs, const capgpu_proof* const* proofs,
+                                 const uint8_t* const* ext_msgs, const size_t* ext_msg_lens, size_t count, int* ok_out);
 /* ark-serialize 0.3 CanonicalSerialize bytes of the Proof as it sits inside a TransferNote / MintNote / FreezeNote
  * (src/transfer.rs:60): compressed G1 (32 B), Fr little-endian, Vec = u64 length prefix, plookup_proof = None.
  * 769 bytes; *len_out receives the size. */
