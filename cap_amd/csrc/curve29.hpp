@@ -226,6 +226,35 @@ struct G1LT {
     return o;
   }
 
+  // ---- scalar multiplication of one term (k_verify_terms, verify_dev.hip) ---------------------------------------
+  // index of the highest set bit of a non-zero word
+  static CAP_HD int top_bit(uint32_t w) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return 31 - __clz(w);
+#else
+    return 31 - __builtin_clz(w);
+#endif
+  }
+  // [k] P for an affine P (internal form) and a 256-bit integer k (taken as the integer it is, not reduced): two bits
+  // per step from the top
+  static CAP_HD g1x term_mul(const g1a& b, const fe& k) {
+    int top = -1;
+    for (int i = 7; i >= 0 && top < 0; i--)
+      if (k.v[i]) top = 32 * i + top_bit(k.v[i]);
+    if (top < 0 || is_inf(b)) return inf();
+    const g1x b2 = dbl_affine(b);
+    const g1x b3 = add_mixed(b2, b);
+    g1x acc = inf();
+#pragma unroll 1
+    for (int pos = top | 1; pos >= 1; pos -= 2) {  // digit = bits pos, pos - 1
+      acc = dbl(dbl(acc));
+      const uint32_t d = (k.v[(pos - 1) >> 5] >> ((pos - 1) & 31)) & 3u;
+      if (d == 1) acc = add_mixed(acc, b);
+      else if (d) acc = add(acc, d == 2 ? b2 : b3);
+    }
+    return acc;
+  }
+
   // ---- inversion (a^(p-2)) and normalisation to affine ------------------------------------------------
   static CAP_HD fl inv(const fl& a) {
     // exponent p - 2, 32-bit words of the modulus

@@ -1535,10 +1535,7 @@ __global__ __launch_bounds__(128) void msm_reduce_grid_final_small(const g1_xyzz
 // Same sums, same order of the operands where it matters (none: the group is commutative and the results leave as affine
 // coordinates); taken for launches of up to quad_max_batch() MSMs, the one-lane kernels above stay for everything else.
 using QD = QuadG1<G1S, QuadDev>;
-__device__ __noinline__ g1x quad_slow_add(const g1x& a, const g1x& b) { return G1S::add(a, b); }
-struct QuadSlow {
-  __device__ __forceinline__ g1x operator()(const g1x& a, const g1x& b) const { return quad_slow_add(a, b); }
-};
+using QuadSlow = QuadSlowT<G1S>;  // quad29.hpp: the out-of-line G1S::add
 __device__ __forceinline__ fl quad_zero() { return G1S::F::zero(); }
 __device__ __forceinline__ fl quad_load(const g1_xyzz* p) {
   return G1S::F::load(reinterpret_cast<const fe*>(p)[threadIdx.x & 3]);

@@ -189,4 +189,14 @@ struct QuadG1 {
   }
 };
 
+#if defined(__HIPCC__)
+// The general single-lane addition the device kernels hand to QuadG1::add as `slow`: one out-of-line copy per kernel.
+template <class G>
+__device__ __noinline__ g1x quad_slow_add(const g1x& a, const g1x& b) { return G::add(a, b); }
+template <class G>
+struct QuadSlowT {
+  __device__ __forceinline__ g1x operator()(const g1x& a, const g1x& b) const { return quad_slow_add<G>(a, b); }
+};
+#endif
+
 }  // namespace cap

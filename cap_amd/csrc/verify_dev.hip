@@ -29,24 +29,8 @@ using F = Fq29;
 using T = p29::Tower<CAP_FL_SCHED>;
 constexpr int kTermLanes = 64;
 
-// [k] P for an affine P (internal form) and a canonical 256-bit integer k: two bits per step from the top
-__device__ __noinline__ g1x term_mul(const g1a& b, const fe& k) {
-  int top = -1;
-  for (int i = 7; i >= 0 && top < 0; i--)
-    if (k.v[i]) top = 32 * i + (31 - __clz(k.v[i]));
-  if (top < 0 || G1L::is_inf(b)) return G1L::inf();
-  const g1x b2 = G1L::dbl_affine(b);
-  const g1x b3 = G1L::add_mixed(b2, b);
-  g1x acc = G1L::inf();
-#pragma unroll 1
-  for (int pos = top | 1; pos >= 1; pos -= 2) {  // digit = bits pos, pos - 1
-    acc = G1L::dbl(G1L::dbl(acc));
-    const uint32_t d = (k.v[(pos - 1) >> 5] >> ((pos - 1) & 31)) & 3u;
-    if (d == 1) acc = G1L::add_mixed(acc, b);
-    else if (d) acc = G1L::add(acc, d == 2 ? b2 : b3);
-  }
-  return acc;
-}
+// [k] P, one out-of-line copy per kernel (curve29.hpp: G1LT::term_mul; tests/hip runs the same function)
+__device__ __noinline__ g1x term_mul(const g1a& b, const fe& k) { return G1L::term_mul(b, k); }
 
 __device__ __forceinline__ g1a load_abi(const g1_affine& m) {  // arkworks Montgomery -> internal form; (0, 0) stays
   g1a r;

@@ -81,3 +81,21 @@ def oracle_proof_points(pr):
 
 def cref_proof_points(comms, evals):
     return [cr.affine_to_ints(c) for c in comms], fr_to_ints(evals)
+
+
+def to_tower(f):
+    """Fq12, flat basis (w^0..w^11, u = w^6 - 9) -> for k < 6 the Fq2 coefficient (x, y) of w^k in the tower of
+    cap_amd/csrc/pairing29.hpp: x = f_k + 9 f_(k+6), y = f_(k+6)"""
+    out = []
+    for k in range(6):
+        out += [(f[k] + 9 * f[k + 6]) % bn.P, f[k + 6] % bn.P]
+    return out
+
+
+def from_tower(t):
+    f = [0] * 12
+    for k in range(6):
+        x, y = t[2 * k], t[2 * k + 1]
+        f[k] = (x - 9 * y) % bn.P
+        f[k + 6] = y % bn.P
+    return f

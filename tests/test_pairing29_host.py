@@ -9,6 +9,7 @@ import pytest
 
 from oracle import pairing as op
 from oracle.bn254 import G1_GEN, P, R, g1_mul
+from tests.helpers import from_tower, to_tower
 from tests.test_field29_host import _cxx
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -24,23 +25,6 @@ def exe(tmp_path_factory, request):
     subprocess.check_call([_cxx(), "-O1", "-std=c++17", flag, os.path.join(HERE, "cpp", "pairing29_check.cpp"),
                            "-o", path])
     return path
-
-
-def to_tower(f):
-    """flat basis (w^0..w^11, u = w^6 - 9) -> for k < 6 the Fq2 coefficient (x, y) of w^k: x = f_k + 9 f_(k+6), y = f_(k+6)"""
-    out = []
-    for k in range(6):
-        out += [(f[k] + 9 * f[k + 6]) % P, f[k + 6] % P]
-    return out
-
-
-def from_tower(t):
-    f = [0] * 12
-    for k in range(6):
-        x, y = t[2 * k], t[2 * k + 1]
-        f[k] = (x - 9 * y) % P
-        f[k + 6] = y % P
-    return f
 
 
 def h(v):
