@@ -58,6 +58,21 @@ pub struct capgpu_verifying_key {
     pub sigma_comms: [[u64; 8]; NUM_WIRE_TYPES],
 }
 
+/// `capgpu_witness_fault`: the verdict of the witness check for one proof (48 bytes).
+/// `kind`: 0 satisfied, 1 gate `row`, 2 copy constraint `(wire, row) -> (wire2, row2)`.
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct capgpu_witness_fault {
+    pub kind: u32,
+    pub wire: u32,
+    pub wire2: u32,
+    pub reserved: u32,
+    pub row: u64,
+    pub row2: u64,
+    pub gates_failed: u64,
+    pub copies_failed: u64,
+}
+
 #[link(name = "capgpu")]
 extern "C" {
     // ---- lifecycle, devices
@@ -191,6 +206,19 @@ extern "C" {
                                            pub_inputs: *const u64, num_inputs: usize, ext_msg: *const u8,
                                            ext_msg_len: usize, blinders: *const u64, input_form: c_int,
                                            proofs_out: *mut capgpu_proof) -> c_int;
+    // ---- witness check (Circuit::check_circuit_satisfiability as the reference's prove() calls it)
+    pub fn capgpu_plonk_check_witness(pk_handle: u64, wires: *const u64, pub_inputs: *const u64, num_inputs: usize,
+                                      input_form: c_int, fault_out: *mut capgpu_witness_fault) -> c_int;
+    pub fn capgpu_plonk_check_witness_batch(pk_handle: u64, count: c_int, wires: *const u64, pub_inputs: *const u64,
+                                            num_inputs: usize, input_form: c_int,
+                                            faults_out: *mut capgpu_witness_fault) -> c_int;
+    pub fn capgpu_plonk_check_witness_batch_dev(pk_handle: u64, count: c_int, d_wires: *const c_void,
+                                                pub_inputs: *const u64, num_inputs: usize, input_form: c_int,
+                                                faults_out: *mut capgpu_witness_fault) -> c_int;
+    pub fn capgpu_plonk_check_witness_multi(pk_handles: *const u64, count: c_int, wires: *const u64,
+                                            pub_inputs: *const u64, num_inputs: usize, input_form: c_int,
+                                            faults_out: *mut capgpu_witness_fault) -> c_int;
+    pub fn capgpu_plonk_set_precheck(on: c_int) -> c_int;
     // ---- verification (host only)
     pub fn capgpu_g2_generator(out: *mut u64) -> c_int;
     pub fn capgpu_g2_mul(q: *const u64, scalar: *const u64, out: *mut u64) -> c_int;

@@ -31,6 +31,7 @@
 #include <thread>
 #include <vector>
 
+#include "check_kernels.hpp"
 #include "coalescer.hpp"
 #include "context.hpp"
 #include "host_util.hpp"
@@ -64,11 +65,18 @@ struct ProvingKey {
   }
   // Immutable once published: contexts on the same device share the object, other devices get a peer copy
   // (clone_key_to_current).  The batch workspace lives in the context (Context::prove_ws).
+  // The one exception: the tables of the witness check (key_check_tables), derived on the first check of this key on this
+  // device under chk_mu, read-only afterwards, freed with the key.  A replica on another device derives its own.
+  mutable std::mutex chk_mu;
+  mutable fe* chk_sel = nullptr;         // [13][n] selector VALUES on the domain, internal form (13.6 MB at n = 2^15)
+  mutable uint32_t* chk_perm = nullptr;  // [5 n] index form of the extended permutation: cell i n + j -> i' n + j'
+  mutable int chk_rc = 1;                // 1: not derived yet; CAPGPU_OK: ready; < 0: sigma was refused (chk_err), for good
+  mutable std::string chk_err;
   ProvingKey() = default;
   ProvingKey(const ProvingKey&) = delete;
   ProvingKey& operator=(const ProvingKey&) = delete;
   ~ProvingKey() {
-    for (void* p : {(void*)coef, (void*)sig_eval, (void*)pk_coset, (void*)inv_nx1})
+    for (void* p : {(void*)coef, (void*)sig_eval, (void*)pk_coset, (void*)inv_nx1, (void*)chk_sel, (void*)chk_perm})
       if (p) hipFree(p);
   }
 };
@@ -541,6 +549,178 @@ uint32_t h2d_chunk_start(uint32_t P, uint32_t chunks, uint32_t ck, bool short_fi
   return first + (uint32_t)((uint64_t)(P - first) * (ck - 1) / (chunks - 1));
 }
 
+// ---- witness check ---------------------------------------------------------------------------------------------------
+// The reference refuses a witness that does not satisfy its circuit before it calls the SNARK, and names the constraint
+// (`check_circuit_satisfiability`, src/proof/transfer.rs:167-177; mint.rs and freeze.rs likewise).  Here: two launches over
+// the resident witnesses (check_kernels.hpp) against two tables a key derives on its first check.
+std::atomic<int> g_precheck{0};             // capgpu_plonk_set_precheck
+thread_local bool tl_prechecked = false;    // the batch this thread is about to prove has been checked already (coalescer)
+
+// selector values on the domain and the index form of sigma, on the current context's stream; synchronous
+int key_check_tables(const ProvingKey& K) {
+  std::lock_guard<std::mutex> lk(K.chk_mu);
+  if (K.chk_rc <= 0) {
+    if (K.chk_rc) set_error("%s", K.chk_err.c_str());
+    return K.chk_rc;
+  }
+  Context& c = ctx();
+  hipStream_t s = c.stream;
+  const size_t n = K.n, cells = (size_t)NW * n;
+  DevTmp<fe> sel;
+  DevTmp<uint32_t> perm, bad;
+  CAP_HIP(sel.alloc((size_t)NS * n));
+  CAP_HIP(perm.alloc(cells));
+  CAP_HIP(bad.alloc(1));
+  int rc = run_ntt_from(s, K.log_n, K.coef, K.ps, n, sel, n, NS, 0, 0);
+  if (rc) return rc;
+  ntt_table_to_internal(sel, sel, (size_t)NS * n, s);
+  wc29::PermConsts pc;
+  memset(&pc, 0, sizeof pc);
+  pc.log_n = K.log_n;
+  auto conv = [](const fe& a) { return Fr29::pack(Fr29::canonical(Fr29::from_ext(a))); };
+  for (int i = 0; i < NW; i++) pc.kinv[i] = conv(Fr::inv(K.qc.k[i]));
+  fe w = Fr::inv(ntt_root_of_unity(K.log_n));
+  for (uint32_t b = 0; b < K.log_n && b < 28; b++) {
+    pc.winv[b] = conv(w);
+    w = Fr::sqr(w);
+  }
+  CAP_HIP(hipMemsetAsync(bad, 0, sizeof(uint32_t), s));
+  launch("k_perm_index", k_perm_index, dim3(cdiv(cells, kThreads)), dim3(kThreads), 0, s, (const fe*)K.sig_eval, pc, cells,
+         perm.p, bad.p);
+  uint32_t h_bad = 0;
+  CAP_HIP(hipMemcpyAsync(&h_bad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  CAP_HIP(hipStreamSynchronize(s));
+  if ((rc = take_launch_error())) return rc;
+  if (h_bad) {
+    set_error("capgpu_plonk_check_witness: sigma is not a permutation of the extended domain (a value of sigma lies in "
+              "none of the five cosets k_i H)");
+    K.chk_err = last_error();
+    K.chk_rc = CAPGPU_ERR_INVALID_ARG;
+    return K.chk_rc;
+  }
+  K.chk_sel = sel.p;
+  K.chk_perm = perm.p;
+  sel.p = nullptr;
+  perm.p = nullptr;
+  K.chk_rc = CAPGPU_OK;
+  return CAPGPU_OK;
+}
+
+size_t check_small_bytes(uint32_t P) {
+  return (sizeof(CheckKey) + sizeof(CheckOut) + sizeof(uint32_t)) * (size_t)P + 768;
+}
+
+// Verdicts of P witnesses whose VALUES are resident at d_vals ([P][5][n]); d_pub: [P][pub_stride] on the device; d_small:
+// check_small_bytes(P) of device scratch.  Runs on the current context's stream and waits for it.
+int check_batch(const ProvingKey& K, const std::vector<const ProvingKey*>* keys, uint32_t P, const fe* d_vals,
+                const fe* d_pub, size_t pub_stride, void* d_small, capgpu_witness_fault* faults) {
+  Context& c = ctx();
+  hipStream_t s = c.stream;
+  const size_t n = K.n;
+  std::vector<CheckKey> hk(P);
+  int rc;
+  for (uint32_t p = 0; p < P; p++) {
+    const ProvingKey& Kp = keys ? *(*keys)[p] : K;
+    if (Kp.n != n) {
+      set_error("capgpu_plonk_check_witness_multi: the keys of one batch must share the domain size");
+      return CAPGPU_ERR_INVALID_ARG;
+    }
+    if ((p == 0 || keys) && (rc = key_check_tables(Kp))) return rc;
+    hk[p] = CheckKey{Kp.chk_sel, Kp.chk_perm, (uint32_t)Kp.num_inputs, 0};
+  }
+  CheckKey* dk = (CheckKey*)d_small;
+  CheckOut* dout = (CheckOut*)((char*)d_small + (sizeof(CheckKey) * P + 255) / 256 * 256);
+  uint32_t* dto = (uint32_t*)((char*)dout + (sizeof(CheckOut) * P + 255) / 256 * 256);
+  std::vector<CheckOut> ho(P, CheckOut{kNoFault, 0, 0});
+  std::vector<uint32_t> hto(P);
+  CAP_HIP(hipMemcpyAsync(dk, hk.data(), sizeof(CheckKey) * P, hipMemcpyHostToDevice, s));
+  CAP_HIP(hipMemcpyAsync(dout, ho.data(), sizeof(CheckOut) * P, hipMemcpyHostToDevice, s));
+  launch("k_check_gates", k_check_gates, dim3(cdiv(n, kThreads), P), dim3(kThreads), 0, s, d_vals, d_pub, pub_stride,
+         (const CheckKey*)dk, n, dout);
+  launch("k_check_copies", k_check_copies, dim3(cdiv((size_t)NW * n, kThreads), P), dim3(kThreads), 0, s, d_vals,
+         (const CheckKey*)dk, n, dout);
+  launch("k_check_targets", k_check_targets, dim3(cdiv(P, 64)), dim3(64), 0, s, (const CheckKey*)dk, (const CheckOut*)dout,
+         P, (size_t)NW * n, dto);
+  CAP_HIP(hipMemcpyAsync(ho.data(), dout, sizeof(CheckOut) * P, hipMemcpyDeviceToHost, s));
+  CAP_HIP(hipMemcpyAsync(hto.data(), dto, sizeof(uint32_t) * P, hipMemcpyDeviceToHost, s));
+  CAP_HIP(hipStreamSynchronize(s));
+  if ((rc = take_launch_error())) return rc;
+  for (uint32_t p = 0; p < P; p++) {
+    capgpu_witness_fault& f = faults[p];
+    memset(&f, 0, sizeof f);
+    f.gates_failed = ho[p].gates;
+    f.copies_failed = ho[p].copies;
+    if (ho[p].first == kNoFault) continue;
+    if (ho[p].first < kCopyKeyBase) {
+      f.kind = 1;
+      f.row = ho[p].first;
+      continue;
+    }
+    const uint64_t cell = ho[p].first - kCopyKeyBase;
+    const uint32_t to = hto[p];  // k_check_targets: the cell the constraint points to
+    f.kind = 2;
+    f.wire = (uint32_t)(cell / n);
+    f.row = cell % n;
+    f.wire2 = (uint32_t)(to / n);
+    f.row2 = to % n;
+  }
+  return CAPGPU_OK;
+}
+
+// The same for witnesses resident at d_wires in `form` with their public inputs still on the host (`pubs`: P rows of
+// pub_stride elements).  Scratch: Context::stage_a.  Coefficient-form input is transformed to values out of place, into
+// stage_a; d_wires is never written.
+int check_resident(const ProvingKey& K, const std::vector<const ProvingKey*>* keys, uint32_t P, const fe* d_wires,
+                   const uint64_t* pubs, size_t pub_stride, int form, capgpu_witness_fault* faults) {
+  Context& c = ctx();
+  hipStream_t s = c.stream;
+  const size_t n = K.n;
+  const bool coeffs = form == CAPGPU_INPUT_COEFFS;
+  Carver cv(nullptr);
+  auto carve_all = [&](Carver& k, void** small, fe** pub, fe** v) {
+    *small = k.take<char>(check_small_bytes(P));
+    *pub = k.take<fe>((size_t)P * (pub_stride ? pub_stride : 1));
+    *v = coeffs ? k.take<fe>((size_t)P * NW * n) : nullptr;
+  };
+  void* d_small = nullptr;
+  fe *d_pub = nullptr, *d_vals = nullptr;
+  carve_all(cv, &d_small, &d_pub, &d_vals);
+  int rc = scratch_reserve(c.stage_a, cv.off + 256);
+  if (rc) return rc;
+  Carver cr(c.stage_a.p);
+  carve_all(cr, &d_small, &d_pub, &d_vals);
+  if (pub_stride) CAP_HIP(hipMemcpyAsync(d_pub, pubs, sizeof(fe) * P * pub_stride, hipMemcpyHostToDevice, s));
+  if (coeffs) {
+    if ((rc = run_ntt_from(s, K.log_n, d_wires, n, n, d_vals, n, P * NW, 0, 0))) return rc;
+  } else {
+    d_vals = const_cast<fe*>(d_wires);
+  }
+  return check_batch(K, keys, P, d_vals, d_pub, pub_stride, d_small, faults);
+}
+
+std::string fault_text(uint32_t p, const capgpu_witness_fault& f) {
+  char b[160];
+  if (f.kind == 1)
+    snprintf(b, sizeof b, "proof %u: gate %llu not satisfied", p, (unsigned long long)f.row);
+  else
+    snprintf(b, sizeof b, "proof %u: copy constraint (%u,%llu) -> (%u,%llu) violated", p, f.wire,
+             (unsigned long long)f.row, f.wire2, (unsigned long long)f.row2);
+  return b;
+}
+// CAPGPU_OK when every witness holds; else CAPGPU_ERR_PROOF with the number of bad proofs, the first one and its fault
+int precheck_verdict(const capgpu_witness_fault* faults, uint32_t P) {
+  uint32_t bad = 0, first = P;
+  for (uint32_t p = 0; p < P; p++)
+    if (faults[p].kind) {
+      if (!bad) first = p;
+      bad++;
+    }
+  if (!bad) return CAPGPU_OK;
+  set_error("capgpu_plonk_prove: %u of %u witnesses do not satisfy their circuit; first: %s", bad, P,
+            fault_text(first, faults[first]).c_str());
+  return CAPGPU_ERR_PROOF;
+}
+
 // msgs / msg_lens (optional): one transcript init message per proof; otherwise ext_msg is shared by the batch.
 // keys (optional): the proving key of every proof - keys of ONE domain size under ONE SRS (the reference proves transfer,
 // mint and freeze notes side by side, src/utils/params_builder.rs:194-226; proofs of different circuits on the same
@@ -605,6 +785,27 @@ int prove_batch(const ProvingKey& K, uint32_t P, const fe* d_wires, const uint64
   const MsmBases* B = nullptr;
   int rc = find_srs(K.srs_handle, &B);
   if (rc) return rc;
+  // capgpu_plonk_set_precheck: the witnesses are checked against their circuits before anything is committed to.  The
+  // check reads whole witnesses, so host-resident ones are copied now, in one go, instead of chunk by chunk in round 1.
+  const bool precheck = g_precheck.load(std::memory_order_relaxed) != 0 && !tl_prechecked;
+  if (precheck && h_wires) {
+    for (uint32_t p = 0; p < P;) {
+      uint32_t q = p + 1;
+      while (q < P && h_wires[q] == h_wires[q - 1] + (size_t)4 * NW * n) q++;
+      CAP_HIP(hipMemcpyAsync(const_cast<fe*>(d_wires) + (size_t)p * NW * n, h_wires[p], sizeof(fe) * (size_t)(q - p) * NW * n,
+                             hipMemcpyHostToDevice, s));
+      p = q;
+    }
+    h_wires = nullptr;
+  }
+  if (precheck) {
+    // Ahead of everything the proof itself needs - the Lagrange-form commit key a domain's first proof may have to build,
+    // the workspace, every MSM and NTT: a refused batch has cost the check's launches.  (Coefficient-form input is first
+    // transformed to values, in scratch of the check's own.)
+    std::vector<capgpu_witness_fault> faults(P);
+    if ((rc = check_resident(K, keys, P, d_wires, pub_inputs, num_inputs, form, faults.data()))) return rc;
+    if ((rc = precheck_verdict(faults.data(), P))) return rc;
+  }
   // the Lagrange-form commit key (built on the first proof of this domain size under this SRS if preprocess did not);
   // sharded commitment MSMs (mode A of config 4) cut the monomial key by point range: they keep the coefficient form
   // The Lagrange-form key is an OPTIMISATION (the same commitments come from the coefficients): when it cannot be had -
@@ -2107,13 +2308,19 @@ static void run_coalesced(std::vector<ProveReq*>& reqs) {
     hold.push_back(K);
   }
   if (good.empty()) return;
-  const size_t g = good.size(), n = hold[0]->n;
+  size_t g = good.size();
+  const size_t n = hold[0]->n;
   size_t ni = 0;  // row length of the public inputs: the largest count among the batch's keys
   bool mixed = false;
-  for (size_t i = 0; i < g; i++) {
-    ni = std::max(ni, hold[i]->num_inputs);
-    mixed = mixed || hold[i].get() != hold[0].get();
-  }
+  auto shape = [&] {
+    ni = 0;
+    mixed = false;
+    for (size_t i = 0; i < g; i++) {
+      ni = std::max(ni, hold[i]->num_inputs);
+      mixed = mixed || hold[i].get() != hold[0].get();
+    }
+  };
+  shape();
   bool recompute = false;
   for (size_t i = 0; i < g; i++) recompute = recompute || hold[i]->recompute;
   if (mixed && recompute) {  // the reference-schedule test mode keeps one key per batch: prove these one by one
@@ -2133,6 +2340,61 @@ static void run_coalesced(std::vector<ProveReq*>& reqs) {
   } growth((double)std::max<size_t>(64, (g + 31) / 32 * 32) / (double)g);
   int rc = scratch_reserve(c.stage_b, per * g);
   if (rc) return fail_all(rc);
+  // capgpu_plonk_set_precheck: every witness of the gathered batch is checked where it will be proved from; a request
+  // whose witness does not satisfy its circuit gets its own CAPGPU_ERR_PROOF and fault text, the others close ranks in
+  // the input array and are proved as ONE batch - no request-by-request re-run, whoever shares the batch.
+  // every request's witness into the batch's input array on the batch's stream: from the slot its caller staged it in
+  // (StagePool; behind that copy), else from the caller's host buffer
+  auto gather_all = [&]() -> hipError_t {
+    hipError_t e = hipSuccess;
+    for (size_t i = 0; i < g && e == hipSuccess; i++) {
+      char* dst = (char*)c.stage_b.p + per * i;
+      if (good[i]->d_wires) {
+        e = hipStreamWaitEvent(c.stream, good[i]->staged, 0);
+        if (e == hipSuccess) e = hipMemcpyAsync(dst, good[i]->d_wires, per, hipMemcpyDeviceToDevice, c.stream);
+      } else {
+        e = hipMemcpyAsync(dst, good[i]->wires, per, hipMemcpyHostToDevice, c.stream);
+      }
+    }
+    return e;
+  };
+  bool prechecked = false;
+  if (g_precheck.load(std::memory_order_relaxed) != 0) {
+    hipError_t e = gather_all();
+    if (e != hipSuccess) return fail_all(hip_fail(e, "gathering the witnesses"));
+    std::vector<uint64_t> rows(4 * ni * g + 4, 0);
+    std::vector<const ProvingKey*> ks(g);
+    for (size_t i = 0; i < g; i++) {
+      if (good[i]->num_inputs) memcpy(&rows[4 * ni * i], good[i]->pubs, 32 * good[i]->num_inputs);
+      ks[i] = hold[i].get();
+    }
+    std::vector<capgpu_witness_fault> faults(g);
+    rc = check_resident(*ks[0], mixed ? &ks : nullptr, (uint32_t)g, (const fe*)c.stage_b.p, rows.data(), ni, good[0]->form,
+                        faults.data());
+    if (rc) return fail_all(rc);
+    size_t k = 0;
+    for (size_t i = 0; i < g && e == hipSuccess; i++) {
+      if (faults[i].kind) {
+        (void)precheck_verdict(&faults[i], 1);
+        good[i]->rc = CAPGPU_ERR_PROOF;
+        good[i]->err = capgpu_last_error();
+        continue;
+      }
+      if (k != i) {  // (row k < i has been read or dropped: the copies run in stream order)
+        e = hipMemcpyAsync((char*)c.stage_b.p + per * k, (char*)c.stage_b.p + per * i, per, hipMemcpyDeviceToDevice, c.stream);
+        good[k] = good[i];
+        hold[k] = hold[i];
+      }
+      k++;
+    }
+    good.resize(k);  // (the statistics count what is proved: the refused requests enter neither batches nor proofs)
+    hold.resize(k);
+    if (e != hipSuccess) return fail_all(hip_fail(e, "closing ranks in the gathered witnesses"));
+    if (k == 0) return;
+    g = k;
+    shape();
+    prechecked = true;
+  }
   std::vector<uint64_t> pubs(4 * ni * g + 4, 0), blind(4 * 13 * g);
   std::vector<const uint8_t*> msgs(g);
   std::vector<size_t> lens(g);
@@ -2149,26 +2411,19 @@ static void run_coalesced(std::vector<ProveReq*>& reqs) {
     lens[i] = good[i]->msg_len;
     keys[i] = hold[i].get();
   }
-  bool resident = false;
-  if (staged) {
+  bool resident = prechecked;
+  if (staged && !prechecked) {
     // the callers copied their witnesses when they arrived (StagePool): gather them into the batch's input array behind
     // their copies; a request that got no slot goes host -> device here, on the batch's stream
     trace("co_gather_staged", (int64_t)staged, (int64_t)g);
-    hipError_t e = hipSuccess;
-    for (size_t i = 0; i < g && e == hipSuccess; i++) {
-      char* dst = (char*)c.stage_b.p + per * i;
-      if (good[i]->d_wires) {
-        e = hipStreamWaitEvent(c.stream, good[i]->staged, 0);
-        if (e == hipSuccess) e = hipMemcpyAsync(dst, good[i]->d_wires, per, hipMemcpyDeviceToDevice, c.stream);
-      } else {
-        e = hipMemcpyAsync(dst, good[i]->wires, per, hipMemcpyHostToDevice, c.stream);
-      }
-    }
+    const hipError_t e = gather_all();
     if (e != hipSuccess) return fail_all(hip_fail(e, "gathering the staged witnesses"));
     resident = true;
   }
+  tl_prechecked = prechecked;
   rc = prove_batch(*keys[0], (uint32_t)g, (const fe*)c.stage_b.p, pubs.data(), ni, nullptr, 0, blind.data(), out.data(),
                    msgs.data(), lens.data(), mixed ? &keys : nullptr, resident ? nullptr : rows.data(), good[0]->form);
+  tl_prechecked = false;
   if (rc == CAPGPU_OK) rc = take_launch_error();
   if (rc == CAPGPU_OK) {
     for (size_t i = 0; i < g; i++) *good[i]->out = out[i];
@@ -2323,6 +2578,120 @@ int capgpu_plonk_prove(uint64_t pk_handle, const uint64_t* wires, const uint64_t
                        const uint8_t* ext_msg, size_t ext_msg_len, const uint64_t* blinders, capgpu_proof* proof_out) {
   return capgpu_plonk_prove_ex(pk_handle, wires, pub_inputs, num_inputs, ext_msg, ext_msg_len, blinders,
                                CAPGPU_INPUT_EVALS, proof_out);
+}
+
+// ---- witness check (see check_batch) -------------------------------------------------------------------------------
+// One part of a check call on the calling thread's context: `cnt` witnesses from host memory (h_wires) or resident
+// (d_wires), keys per proof (pk_handles) or one for all.
+static int check_part(const uint64_t* pk_handles, uint64_t pk_handle, uint32_t cnt, const uint64_t* h_wires,
+                      const void* d_wires, const uint64_t* pubs, size_t num_inputs, int form,
+                      capgpu_witness_fault* faults) {
+  Context& c = ctx();
+  Entry lk(c);
+  std::vector<std::shared_ptr<ProvingKey>> hold(pk_handles ? cnt : 1);
+  std::vector<const ProvingKey*> keys(hold.size());
+  int rc;
+  for (size_t i = 0; i < hold.size(); i++) {
+    if ((rc = lookup_key(pk_handles ? pk_handles[i] : pk_handle, &hold[i]))) return rc;
+    keys[i] = hold[i].get();
+    if (keys[i]->n != keys[0]->n || keys[i]->srs_handle != keys[0]->srs_handle) {
+      set_error("capgpu_plonk_check_witness_multi: the keys of one batch must share the domain size and the SRS");
+      return CAPGPU_ERR_INVALID_ARG;
+    }
+  }
+  const size_t n = keys[0]->n;
+  if (h_wires) {
+    if ((rc = scratch_reserve(c.stage_b, sizeof(fe) * (size_t)cnt * NW * n))) return rc;
+    CAP_HIP(hipMemcpyAsync(c.stage_b.p, h_wires, sizeof(fe) * (size_t)cnt * NW * n, hipMemcpyHostToDevice, c.stream));
+    d_wires = c.stage_b.p;
+  }
+  return check_resident(*keys[0], pk_handles ? &keys : nullptr, cnt, (const fe*)d_wires, pubs, num_inputs, form, faults);
+}
+
+int capgpu_plonk_check_witness_batch_dev(uint64_t pk_handle, int count, const void* d_wires, const uint64_t* pub_inputs,
+                                         size_t num_inputs, int input_form, capgpu_witness_fault* faults_out) {
+  CAP_CHECK_INIT();
+  if (bad_form(input_form)) return CAPGPU_ERR_INVALID_ARG;
+  if (count < 0 || (count && (!d_wires || !faults_out || (num_inputs && !pub_inputs)))) {
+    set_error("capgpu_plonk_check_witness: bad argument");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  if (count == 0) return CAPGPU_OK;
+  std::shared_ptr<ProvingKey> K0;
+  int rc = home_key(pk_handle, &K0);
+  if (rc) return rc;
+  if (num_inputs != K0->num_inputs) {
+    set_error("capgpu_plonk_check_witness: %zu public inputs given, key expects %zu", num_inputs, K0->num_inputs);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  return check_part(nullptr, pk_handle, (uint32_t)count, nullptr, d_wires, pub_inputs, num_inputs, input_form, faults_out);
+}
+
+int capgpu_plonk_check_witness_batch(uint64_t pk_handle, int count, const uint64_t* wires, const uint64_t* pub_inputs,
+                                     size_t num_inputs, int input_form, capgpu_witness_fault* faults_out) {
+  CAP_CHECK_INIT();
+  if (bad_form(input_form)) return CAPGPU_ERR_INVALID_ARG;
+  if (count < 0 || (count && (!wires || !faults_out || (num_inputs && !pub_inputs)))) {
+    set_error("capgpu_plonk_check_witness: bad argument");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  if (count == 0) return CAPGPU_OK;
+  std::shared_ptr<ProvingKey> K0;
+  int rc0 = home_key(pk_handle, &K0);
+  if (rc0) return rc0;
+  if (num_inputs != K0->num_inputs) {
+    set_error("capgpu_plonk_check_witness: %zu public inputs given, key expects %zu", num_inputs, K0->num_inputs);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  const size_t n = K0->n;
+  return deal(count, [&](int first, int cnt) -> int {
+    return check_part(nullptr, pk_handle, (uint32_t)cnt, wires + (size_t)4 * first * NW * n, nullptr,
+                      pub_inputs ? pub_inputs + (size_t)4 * first * num_inputs : nullptr, num_inputs, input_form,
+                      faults_out + first);
+  });
+}
+
+int capgpu_plonk_check_witness(uint64_t pk_handle, const uint64_t* wires, const uint64_t* pub_inputs, size_t num_inputs,
+                               int input_form, capgpu_witness_fault* fault_out) {
+  return capgpu_plonk_check_witness_batch(pk_handle, 1, wires, pub_inputs, num_inputs, input_form, fault_out);
+}
+
+int capgpu_plonk_check_witness_multi(const uint64_t* pk_handles, int count, const uint64_t* wires,
+                                     const uint64_t* pub_inputs, size_t num_inputs, int input_form,
+                                     capgpu_witness_fault* faults_out) {
+  CAP_CHECK_INIT();
+  if (bad_form(input_form)) return CAPGPU_ERR_INVALID_ARG;
+  if (count < 0 || (count && (!pk_handles || !wires || !faults_out || (num_inputs && !pub_inputs)))) {
+    set_error("capgpu_plonk_check_witness_multi: bad argument");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  if (count == 0) return CAPGPU_OK;
+  size_t n = 0, max_ni = 0;
+  for (int i = 0; i < count; i++) {
+    std::shared_ptr<ProvingKey> Ki;
+    int rc = home_key(pk_handles[i], &Ki);
+    if (rc) return rc;
+    if (i == 0) n = Ki->n;
+    if (Ki->n != n) {
+      set_error("capgpu_plonk_check_witness_multi: the keys of one batch must share the domain size and the SRS");
+      return CAPGPU_ERR_INVALID_ARG;
+    }
+    max_ni = std::max(max_ni, Ki->num_inputs);
+  }
+  if (num_inputs != max_ni) {
+    set_error("capgpu_plonk_check_witness_multi: rows of %zu public inputs given, the keys need %zu", num_inputs, max_ni);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  return deal(count, [&](int first, int cnt) -> int {
+    return check_part(pk_handles + first, 0, (uint32_t)cnt, wires + (size_t)4 * first * NW * n, nullptr,
+                      pub_inputs ? pub_inputs + (size_t)4 * first * num_inputs : nullptr, num_inputs, input_form,
+                      faults_out + first);
+  });
+}
+
+int capgpu_plonk_set_precheck(int on) {
+  g_precheck.store(on != 0);
+  return CAPGPU_OK;
 }
 
 int capgpu_plonk_set_coalescing(uint32_t window_us, uint32_t max_batch) {

@@ -629,6 +629,72 @@ def plonk_set_wire_commit_from_evals(on):
     check(load().capgpu_plonk_set_wire_commit(ctypes.c_int(-1 if on is None else (1 if on else 0))))
 
 
+class WitnessFault(ctypes.Structure):
+    """capgpu_witness_fault (include/capgpu.h): the verdict of the witness check for one proof."""
+    _fields_ = [
+        ("kind", ctypes.c_uint32),       # 0 satisfied, 1 gate, 2 copy constraint
+        ("wire", ctypes.c_uint32),
+        ("wire2", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("row", ctypes.c_uint64),
+        ("row2", ctypes.c_uint64),
+        ("gates_failed", ctypes.c_uint64),
+        ("copies_failed", ctypes.c_uint64),
+    ]
+
+    def __str__(self):
+        """the wording of the reference's check_circuit_satisfiability errors ('' when the witness is satisfied)"""
+        if self.kind == 1:
+            return f"gate {self.row} not satisfied"
+        if self.kind == 2:
+            return f"copy constraint ({self.wire},{self.row}) -> ({self.wire2},{self.row2}) violated"
+        return ""
+
+
+def plonk_check_witness_batch(pk_handle, wires, pub_inputs: np.ndarray, count: int = 1, input_form=INPUT_EVALS) -> list:
+    """One WitnessFault per witness: gates and copy constraints checked on the device before anything is proved.
+    wires: (count, 5, n, 4) numpy array (host: the batch is dealt over the contexts) or a DevBuf of that content;
+    pk_handle: one key, or a list of `count` keys of one domain (capgpu_plonk_check_witness_multi; pub_inputs then has
+    rows of the largest public-input count)."""
+    pub_inputs = np.ascontiguousarray(pub_inputs, dtype=np.uint64).reshape(-1)
+    multi = isinstance(pk_handle, (list, tuple))
+    shapes = [plonk_key_info(h) for h in (pk_handle if multi else [pk_handle])]
+    n, num_inputs = shapes[0][0], max(sh[1] for sh in shapes)
+    if multi and len(pk_handle) != count:
+        raise CapGpuError(-1, f"{len(pk_handle)} keys for {count} witnesses")
+    if count < 1:
+        raise CapGpuError(-1, f"count must be >= 1, got {count}")
+    elems = wires.nbytes // 32 if isinstance(wires, DevBuf) else np.asarray(wires).size // 4
+    if elems != count * NUM_WIRE_TYPES * n:
+        raise CapGpuError(-1, f"wires hold {elems} field elements, key (n = {n}) needs count * 5 * n = "
+                              f"{count * NUM_WIRE_TYPES * n}")
+    if pub_inputs.size != count * num_inputs * 4:
+        raise CapGpuError(-1, f"pub_inputs hold {pub_inputs.size / 4:g} field elements, need count * {num_inputs}")
+    faults = (WitnessFault * count)()
+    pub_ptr = _p(pub_inputs) if pub_inputs.size else None
+    L, form = load(), ctypes.c_int(_form(input_form))
+    if isinstance(wires, DevBuf):
+        if multi:
+            raise CapGpuError(-1, "the multi-key check takes host-resident witnesses")
+        check(L.capgpu_plonk_check_witness_batch_dev(ctypes.c_uint64(pk_handle), count, wires.ptr, pub_ptr,
+                                                     ctypes.c_size_t(num_inputs), form, faults))
+        return list(faults)
+    wires = np.ascontiguousarray(wires, dtype=np.uint64).reshape(-1)
+    if multi:
+        handles = (ctypes.c_uint64 * count)(*pk_handle)
+        check(L.capgpu_plonk_check_witness_multi(handles, count, _p(wires), pub_ptr, ctypes.c_size_t(num_inputs), form,
+                                                 faults))
+    else:
+        check(L.capgpu_plonk_check_witness_batch(ctypes.c_uint64(pk_handle), count, _p(wires), pub_ptr,
+                                                 ctypes.c_size_t(num_inputs), form, faults))
+    return list(faults)
+
+
+def plonk_set_precheck(on: bool):
+    """capgpu_plonk_set_precheck: every prove entry point checks its witnesses first (off by default)"""
+    check(load().capgpu_plonk_set_precheck(ctypes.c_int(1 if on else 0)))
+
+
 def plonk_set_coalescing(window_us: int, max_batch: int = 0):
     check(load().capgpu_plonk_set_coalescing(ctypes.c_uint32(window_us), ctypes.c_uint32(max_batch)))
 

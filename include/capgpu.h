@@ -445,6 +445,54 @@ int capgpu_plonk_prove_batch_dev_ex(uint64_t pk_handle, int count, const void* d
                                     size_t num_inputs, const uint8_t* ext_msg, size_t ext_msg_len,
                                     const uint64_t* blinders, int input_form, capgpu_proof* proofs_out);
 
+/* ---- witness check: replaces Circuit::check_circuit_satisfiability as the reference's prove() calls it ------------
+ * The reference checks every witness against its circuit BEFORE it calls the SNARK (src/proof/transfer.rs:167-177,
+ * mint.rs and freeze.rs likewise) and names the constraint that failed.  The prove entry points above do not: they notice
+ * an unsatisfied witness only after round 3, as a quotient of the wrong degree, which names no gate and costs a batch
+ * more than half its work.  These calls are that check on the device: every gate (spec eq. (1) with the public input of
+ * the row) and every copy constraint w[i][j] == w[i'][j'], sigma_i(omega^j) = k_i' omega^j', for `count` witnesses at
+ * once.  Verdict per witness: the first failing gate in row order or, when every gate holds, the first violated copy
+ * constraint in (wire, row) order - and how many gates and copy constraints fail in all.  The same on every run.
+ *
+ * Arguments as the prove entry point of the same suffix (wires: count * 5 * n field elements in `input_form`, never
+ * written - coefficient-form input is transformed to values in scratch; pub_inputs: count rows of num_inputs; _multi:
+ * one key per witness, rows of the largest public-input count); the same mistakes get the same codes.  The calls return
+ * CAPGPU_OK whenever the check RAN - the verdicts are in faults_out - and run on the calling context's stream
+ * (capgpu_set_stream); host-resident batches are dealt over the contexts as capgpu_plonk_prove_batch deals them.
+ * The first check of a key derives two tables from it on the device and keeps them with the key until
+ * capgpu_plonk_free_key: the 13 selector columns' VALUES on the domain (13 * 32 B * n: 13.6 MB at n = 2^15) and the index
+ * form of the permutation (4 B * 5 n), one discrete logarithm per cell.  A key whose sigma holds a value in none of the
+ * five cosets k_i H is refused by every check: CAPGPU_ERR_INVALID_ARG, "sigma is not a permutation of the extended
+ * domain". */
+typedef struct capgpu_witness_fault {
+  uint32_t kind;            /* 0 satisfied, 1 gate, 2 copy constraint */
+  uint32_t wire, wire2;     /* copy: cell (wire,row) must equal (wire2,row2); gate: 0 */
+  uint32_t reserved;
+  uint64_t row, row2;
+  uint64_t gates_failed, copies_failed;
+} capgpu_witness_fault;     /* 48 bytes */
+
+int capgpu_plonk_check_witness(uint64_t pk_handle, const uint64_t* wires, const uint64_t* pub_inputs, size_t num_inputs,
+                               int input_form, capgpu_witness_fault* fault_out);
+int capgpu_plonk_check_witness_batch(uint64_t pk_handle, int count, const uint64_t* wires, const uint64_t* pub_inputs,
+                                     size_t num_inputs, int input_form, capgpu_witness_fault* faults_out);
+int capgpu_plonk_check_witness_batch_dev(uint64_t pk_handle, int count, const void* d_wires, const uint64_t* pub_inputs,
+                                         size_t num_inputs, int input_form, capgpu_witness_fault* faults_out);
+int capgpu_plonk_check_witness_multi(const uint64_t* pk_handles, int count, const uint64_t* wires,
+                                     const uint64_t* pub_inputs, size_t num_inputs, int input_form,
+                                     capgpu_witness_fault* faults_out);
+/* on != 0: every prove entry point (direct, _batch, _multi, _dev, _ex, small batches replayed as graphs, coalesced
+ * calls) runs the check on its staged witnesses first - ahead of the Lagrange-form commit key a domain's first proof may
+ * have to build, the workspace and every MSM and NTT of the proof (the check's own work: the first check of a key derives
+ * the key's two tables, coefficient-form witnesses take one forward transform into scratch).  A batch with faults
+ * returns CAPGPU_ERR_PROOF and a message with the number of bad proofs, the first one and its fault in the reference's
+ * wording ("... 2 of 8 witnesses do not satisfy their circuit; first: proof 3: gate 1234 not satisfied", "proof 3: copy
+ * constraint (2,40) -> (0,7) violated").  A coalesced call with a bad witness fails alone, with its own message; the
+ * other calls of its batch are proved as ONE batch (without the check, the whole batch is proved again call by call).
+ * Host-resident witnesses are then copied in one go instead of chunk by chunk under round 1.  Off (the default):
+ * nothing changes.  Process-wide; takes effect with the next prove call. */
+int capgpu_plonk_set_precheck(int on);
+
 /* ---- verification (host only: needs neither a GPU nor capgpu_init) ---------------------------------------- */
 /* G2 elements: x.c0, x.c1, y.c0, y.c1 of the twist point (Fq2 = Fq[u]/(u^2+1)), Montgomery, 16 words;
  * all-zero = infinity.  They are the `h` / `beta_h` of jf-plonk's VerifyingKey.open_key. */

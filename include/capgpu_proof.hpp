@@ -310,6 +310,23 @@ inline std::vector<uint8_t> bound_message(const std::vector<uint8_t>& ver_key_by
 }
 }  // namespace detail_snark
 
+// Opt-in counterpart of the `check_circuit_satisfiability` call the reference makes inside prove() (src/proof/
+// transfer.rs:167-177, mint.rs, freeze.rs): Ok when the assignment satisfies the key's circuit, else Err(FailedSnark)
+// naming the first failing gate or copy constraint ("gate 1234 not satisfied", "copy constraint (2,40) -> (0,7)
+// violated").  Runs on the device (capgpu_plonk_check_witness); prove() itself does not call it - a caller who wants the
+// reference's order calls this first, or switches the check on for every prove call with capgpu_plonk_set_precheck(1).
+inline Result<Unit> check_satisfiability(const ProvingKey& pk, const Assignment& a) {
+  if (!a.wires || (!a.pub_inputs && pk.num_inputs())) return TxnApiError::failed_snark("check_satisfiability: empty assignment");
+  capgpu_witness_fault f;
+  int rc = capgpu_plonk_check_witness(pk.handle(), a.wires, a.pub_inputs, pk.num_inputs(), a.input_form, &f);
+  if (rc != CAPGPU_OK) return detail::map_error(rc, "check_satisfiability");
+  if (f.kind == 1) return TxnApiError::failed_snark("gate " + std::to_string(f.row) + " not satisfied");
+  if (f.kind == 2)
+    return TxnApiError::failed_snark("copy constraint (" + std::to_string(f.wire) + "," + std::to_string(f.row) + ") -> (" +
+                                     std::to_string(f.wire2) + "," + std::to_string(f.row2) + ") violated");
+  return Unit{};
+}
+
 }  // namespace proof
 
 // ---- Transfer (src/proof/transfer.rs) ----------------------------------------------------------------------------
@@ -372,9 +389,10 @@ inline Result<Preprocessed> preprocess(const UniversalSrs& srs, size_t n_inputs,
   TransferVerifyingKey vk(pk);
   return Preprocessed{std::move(pk), vk, circuit.num_gates};
 }
-// transfer.rs:159-188.  The satisfiability check of the reference (check_circuit_satisfiability, :169-176) is the
-// circuit builder's; an unsatisfied assignment is still caught here: the quotient's degree check fails and the call
-// returns Err(FailedSnark) like the reference does.
+// transfer.rs:159-188.  The satisfiability check of the reference (check_circuit_satisfiability, :169-176) is not made
+// here: proof::check_satisfiability (above) is that step on the device, for callers who want it, and
+// capgpu_plonk_set_precheck(1) puts it in front of every prove call.  Without either, an unsatisfied assignment is still
+// caught: the quotient's degree check fails and the call returns Err(FailedSnark) like the reference does - naming no gate.
 template <class Rng>
 Result<Proof> prove(Rng& rng, const TransferProvingKey& pk, const Assignment& witness,
                     const std::vector<uint8_t>& txn_memo_ver_key, const std::vector<uint8_t>& extra_proof_bound_data) {
