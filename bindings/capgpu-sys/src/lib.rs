@@ -175,6 +175,10 @@ extern "C" {
     pub fn capgpu_plonk_set_wire_commit(mode: c_int) -> c_int;
     pub fn capgpu_plonk_graph_stats(segments_captured_out: *mut u64, segments_replayed_out: *mut u64) -> c_int;
     pub fn capgpu_plonk_coalescing_stats(batches_out: *mut u64, proofs_out: *mut u64) -> c_int;
+    pub fn capgpu_plonk_set_transcript(mode: c_int) -> c_int;
+    pub fn capgpu_plonk_get_transcript(mode_out: *mut c_int) -> c_int;
+    pub fn capgpu_plonk_sync_stats(prove_calls_out: *mut u64, stream_waits_out: *mut u64) -> c_int;
+    pub fn capgpu_keccak256_batch_dev(data: *const u8, offsets: *const u64, count: c_int, digests_out: *mut u8) -> c_int;
     pub fn capgpu_plonk_prove_batch(pk_handle: u64, count: c_int, wires: *const u64, pub_inputs: *const u64,
                                     num_inputs: usize, ext_msg: *const u8, ext_msg_len: usize, blinders: *const u64,
                                     proofs_out: *mut capgpu_proof) -> c_int;
@@ -316,6 +320,22 @@ pub fn set_coalescing(window_us: u32, max_batch: u32) -> Result<()> {
 /// the mode for deployments where an adversary can time proofs: include/capgpu.h, "TIMING AND THE SECRET WITNESS").
 pub fn set_wire_commit_from_evals(on: bool) -> Result<()> {
     check(unsafe { capgpu_plonk_set_wire_commit(if on { 1 } else { 0 }) })
+}
+
+pub const CAPGPU_TRANSCRIPT_HOST: c_int = 0;
+pub const CAPGPU_TRANSCRIPT_DEVICE: c_int = 1;
+
+/// Where the Fiat-Shamir transcript of the next prove calls runs: `true` on the device - the five rounds are enqueued
+/// without a host wait and the call synchronises once -, `false` (the default) on the host.  Same proof bytes.
+pub fn set_transcript_on_device(on: bool) -> Result<()> {
+    check(unsafe { capgpu_plonk_set_transcript(if on { CAPGPU_TRANSCRIPT_DEVICE } else { CAPGPU_TRANSCRIPT_HOST }) })
+}
+
+/// (device batches proved, host waits on the proving stream inside them) since process start.
+pub fn sync_stats() -> Result<(u64, u64)> {
+    let (mut calls, mut waits) = (0u64, 0u64);
+    check(unsafe { capgpu_plonk_sync_stats(&mut calls, &mut waits) })?;
+    Ok((calls, waits))
 }
 
 /// Releases the workspace of every idle device context (scratch, pinned result areas, captured launch graphs): tables -

@@ -1,7 +1,8 @@
 // Keccak-256 (original padding 0x01) and jf-plonk's SolidityTranscript, host side.
 // Replaces `jf_plonk::transcript::SolidityTranscript` (imported at
 // src/proof/transfer.rs:39-45; sha3 0.10.1 Keccak256 underneath).  O(1) work per proof;
-// stays on the host exactly as in the reference.
+// stays on the host exactly as in the reference - unless capgpu_plonk_set_transcript moves the prover's transcript to the
+// device (transcript_dev.hpp, which is checked against this file byte for byte).
 #pragma once
 #include <stdint.h>
 #include <string.h>

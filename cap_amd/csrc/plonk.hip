@@ -7,7 +7,8 @@
 // arithmetic and Jacobian -> affine of the 13 commitments.  All O(n) work - 7 iNTT(n),
 // the coset transforms of the quotient step (jf-plonk: 26 of size 8n; here 8 of size 6n per
 // proof, the 18 key columns being cached), 13 MSM, grand product, quotient, evaluations,
-// linearisation, openings - runs on the GPU without leaving HBM between rounds.
+// linearisation, openings - runs on the GPU without leaving HBM between rounds.  With capgpu_plonk_set_transcript(DEVICE)
+// the O(1) steps move there too (transcript_dev.hpp) and a call is enqueued whole: one host wait instead of six or seven.
 //
 // MI355X-first choices: a batch of P proofs is proved in lockstep so that every launch
 // is P times larger (13 MSMs become 5 launches of 5P / P / 5P / 2P MSMs; NTTs are
@@ -38,6 +39,7 @@
 #include "launch.hpp"
 #include "params.hpp"
 #include "plonk_kernels.hpp"
+#include "transcript_dev.hpp"
 
 namespace cap {
 
@@ -104,10 +106,15 @@ struct ProveGraphSig {
   // rounds 1-2 with the side stream (segments 1 and 3 are then empty: their transforms were captured inside segments 0
   // and 7): a set captured one way must never be replayed the other way - round 3 would read stale coset evaluations
   bool overlap = false;
+  // where the transcript runs (capgpu_plonk_set_transcript) and, on the device, the stride of its prefix array: the two
+  // modes cut the schedule differently (eight segments / one), and the stride is baked into the captured launches
+  int transcript = 0;
+  uint32_t tr_stride = 0;
   bool operator==(const ProveGraphSig& o) const {
     return key_uid == o.key_uid && srs == o.srs && P == o.P && num_inputs == o.num_inputs && form == o.form &&
            multi == o.multi && d_wires == o.d_wires && ws == o.ws && msm_ws == o.msm_ws && ntt_scratch == o.ntt_scratch &&
-           bases == o.bases && lagrange == o.lagrange && stream == o.stream && overlap == o.overlap;
+           bases == o.bases && lagrange == o.lagrange && stream == o.stream && overlap == o.overlap && transcript == o.transcript &&
+           tr_stride == o.tr_stride;
   }
 };
 struct ProveGraphSet {
@@ -133,6 +140,18 @@ struct ProveGraphCache {
   uint64_t clock = 0;
 };
 static std::atomic<uint64_t> g_graph_captured{0}, g_graph_replayed{0};
+// capgpu_plonk_sync_stats: prove_batch calls, and the times they made the host wait for the proving stream
+static std::atomic<uint64_t> g_prove_calls{0}, g_stream_waits{0};
+
+static_assert(sizeof(capgpu_proof) == td::kPrBytes && offsetof(capgpu_proof, prod_perm_poly_comm) == td::kPrZ &&
+                  offsetof(capgpu_proof, split_quot_poly_comms) == td::kPrQuot &&
+                  offsetof(capgpu_proof, opening_proof) == td::kPrOpen &&
+                  offsetof(capgpu_proof, shifted_opening_proof) == td::kPrShifted &&
+                  offsetof(capgpu_proof, wires_evals) == td::kPrWireEvals &&
+                  offsetof(capgpu_proof, wire_sigma_evals) == td::kPrSigmaEvals &&
+                  offsetof(capgpu_proof, perm_next_eval) == td::kPrNext,
+              "transcript_dev.hpp writes capgpu_proof by offset");
+
 
 namespace {
 
@@ -177,7 +196,7 @@ ProveGraphSet* graph_set_for(Context& c, const ProveGraphSig& sig) {
   ProveGraphSet* slot = nullptr;
   for (auto& sp : gc.sets)
     if (sp->sig.key_uid == sig.key_uid && sp->sig.P == sig.P && sp->sig.form == sig.form && sp->sig.multi == sig.multi &&
-        sp->sig.d_wires == sig.d_wires)
+        sp->sig.d_wires == sig.d_wires && sp->sig.transcript == sig.transcript)
       slot = sp.get();
   if (!slot && gc.sets.size() >= 8) {
     slot = gc.sets[0].get();
@@ -393,12 +412,17 @@ struct BatchWs {
   EvalDesc* edesc;
   LinTerm* terms;
   const fe** key_ptrs;  // [2][P]: sigma evaluations / coset columns of every proof's key (mixed-key batches)
+  // device transcript only (capgpu_plonk_set_transcript): the proofs in ABI layout, zeta, and the transcript's bytes
+  uint8_t *d_proofs, *tr_state, *tr_pre, *tr_app;
+  uint32_t* tr_pre_len;
+  fe* zeta;
   size_t total;
 };
 constexpr uint32_t kEvalChunks = 16;
 constexpr uint32_t kLinTerms = 29;
+static_assert(kLinTerms == (uint32_t)td::kLinScalars, "transcript_dev.hpp derives the scalars of k_lincomb's terms");
 
-BatchWs carve(void* base, const ProvingKey& K, uint32_t P, size_t num_inputs, bool coeffs) {
+BatchWs carve(void* base, const ProvingKey& K, uint32_t P, size_t num_inputs, bool coeffs, uint32_t tr_stride = 0) {
   Carver c(base);
   BatchWs w{};
   size_t n = K.n, m = K.m, ps = K.ps;
@@ -433,6 +457,14 @@ BatchWs carve(void* base, const ProvingKey& K, uint32_t P, size_t num_inputs, bo
   w.edesc = c.take<EvalDesc>((size_t)P * 10);
   w.terms = c.take<LinTerm>((size_t)P * kLinTerms);
   w.key_ptrs = c.take<const fe*>((size_t)P * 2);
+  if (tr_stride) {  // (last: the host mode's layout is a prefix of this one)
+    w.d_proofs = c.take<uint8_t>((size_t)P * td::kPrBytes);
+    w.zeta = c.take<fe>(P);
+    w.tr_state = c.take<uint8_t>((size_t)P * 64);
+    w.tr_app = c.take<uint8_t>((size_t)P * td::kAppBytes);
+    w.tr_pre_len = c.take<uint32_t>(P);
+    w.tr_pre = c.take<uint8_t>((size_t)P * tr_stride);
+  }
   w.total = c.off + 256;
   return w;
 }
@@ -455,6 +487,19 @@ bool wire_commit_from_evals() {
   }();
   const int m = g_wire_commit.load(std::memory_order_relaxed);
   return (m < 0 ? env_default : m) != 0;
+}
+
+// Where the Fiat-Shamir transcript of a prove call runs (capgpu_plonk_set_transcript; CAPGPU_TRANSCRIPT=device|host sets
+// the process default): on the host - between the rounds the commitments come back, the host hashes them and sends the
+// challenges - or on the device (transcript_dev.hpp), where the whole call is enqueued at once and waited for once.
+std::atomic<int> g_transcript{-1};
+int transcript_mode() {
+  static const int env_default = [] {
+    const char* e = getenv("CAPGPU_TRANSCRIPT");
+    return (e && (!strcmp(e, "device") || !strcmp(e, "1"))) ? CAPGPU_TRANSCRIPT_DEVICE : CAPGPU_TRANSCRIPT_HOST;
+  }();
+  const int m = g_transcript.load(std::memory_order_relaxed);
+  return m < 0 ? env_default : m;
 }
 
 // The stream the chunks of host-resident wire columns are copied on: a copy on the launch stream itself would queue up
@@ -818,10 +863,26 @@ int prove_batch(const ProvingKey& K, uint32_t P, const fe* d_wires, const uint64
     (void)hipGetLastError();
     trace("pb_lagrange_fallback", c.slot, rc);
   }
+  // the transcript on the device (capgpu_plonk_set_transcript) - except under sharded commitment MSMs, whose partial
+  // commitments meet through a host-driven exchange: those calls keep the host transcript
+  const bool dev_tr = transcript_mode() == CAPGPU_TRANSCRIPT_DEVICE && !comm_shard_prover();
+  uint32_t tr_stride = 0;  // bytes per proof of the transcript's prefix: init message || vk_bytes || public inputs
+  if (dev_tr) {
+    size_t longest = 0;
+    for (uint32_t p = 0; p < P; p++) {
+      const size_t ml = msgs ? (msgs[p] ? msg_lens[p] : 0) : (ext_msg ? ext_len : 0);
+      longest = std::max(longest, ml + key_of(p).vk_bytes.size() + 32 * key_of(p).num_inputs);
+    }
+    if (longest > (1u << 30)) {
+      set_error("capgpu_plonk_prove: transcript init message of %zu bytes", longest);
+      return CAPGPU_ERR_INVALID_ARG;
+    }
+    tr_stride = (uint32_t)((longest + 256) / 256 * 256);  // (in steps: the stride is part of a captured graph's signature)
+  }
   // workspace
   const bool coeffs = form == CAPGPU_INPUT_COEFFS;
-  if ((rc = scratch_reserve(c.prove_ws, carve(nullptr, K, P, num_inputs, coeffs).total))) return rc;
-  BatchWs w = carve(c.prove_ws.p, K, P, num_inputs, coeffs);
+  if ((rc = scratch_reserve(c.prove_ws, carve(nullptr, K, P, num_inputs, coeffs, tr_stride).total))) return rc;
+  BatchWs w = carve(c.prove_ws.p, K, P, num_inputs, coeffs, tr_stride);
   const NttDomain* dom_n = nullptr;
   const Ntt3Domain* dom_q = nullptr;
   if ((rc = get_domain(K.log_n, &dom_n))) return rc;
@@ -859,17 +920,25 @@ int prove_batch(const ProvingKey& K, uint32_t P, const fe* d_wires, const uint64
     sig.lagrange = Lag ? Lag->ext : nullptr;
     sig.stream = s;
     sig.overlap = overlap;
+    sig.transcript = dev_tr ? CAPGPU_TRANSCRIPT_DEVICE : CAPGPU_TRANSCRIPT_HOST;
+    sig.tr_stride = tr_stride;
     gs = graph_set_for(c, sig);
   }
   auto seg = [&](int id, const std::function<int()>& enqueue) -> int { return run_segment(c, gs, id, enqueue); };
-  static const bool inv_on_device = [] {  // the round-2 inversion as a device kernel (the pre-round-4 schedule)
+  static const bool inv_env = [] {  // the round-2 inversion as a device kernel (the pre-round-4 schedule)
     const char* e = getenv("CAPGPU_PERM_INV_ON_DEVICE");
     return e && atoi(e) != 0;
   }();
+  const bool inv_on_device = inv_env || dev_tr;
+  g_prove_calls++;
+  auto wait_stream = [&]() -> hipError_t {  // every host wait on the proving stream goes through here (capgpu_plonk_sync_stats)
+    g_stream_waits++;
+    return hipStreamSynchronize(s);
+  };
 
   // ---- transcripts (host) --------------------------------------------------------------------------------
-  std::vector<SolidityTranscript> tr(P);
-  parallel_for(P, [&](uint32_t p) {
+  std::vector<SolidityTranscript> tr(dev_tr ? 0 : P);
+  if (!dev_tr) parallel_for(P, [&](uint32_t p) {
     if (msgs) {
       if (msgs[p] && msg_lens[p]) tr[p].append(msgs[p], msg_lens[p]);
     } else if (ext_msg && ext_len) {
@@ -912,7 +981,14 @@ int prove_batch(const ProvingKey& K, uint32_t P, const fe* d_wires, const uint64
   fe* h_tot = nullptr;       // [P] grand-product totals out, their inverses back
   fe* h_evals = nullptr;     // [10 P]
   uint32_t* h_flags = nullptr;  // [P]
-  {
+  uint8_t* h_proofs = nullptr;  // [P] device transcript: the proofs in ABI layout, then the degree flags
+  const size_t proofs_bytes = (size_t)P * td::kPrBytes;
+  if (dev_tr) {
+    // (reserved before the first launch: a growing area drains the context's streams)
+    if ((rc = pinned_reserve(c, proofs_bytes + sizeof(uint32_t) * P + 512))) return rc;
+    h_proofs = (uint8_t*)c.pin_host;
+    h_flags = (uint32_t*)(h_proofs + (proofs_bytes + 255) / 256 * 256);
+  } else {
     const size_t need = sizeof(g1_jac) * P * NW + sizeof(fe) * P * 11 + sizeof(uint32_t) * P + 1024;
     if ((rc = pinned_reserve(c, need))) return rc;
     char* b = (char*)c.pin_host;
@@ -929,7 +1005,7 @@ int prove_batch(const ProvingKey& K, uint32_t P, const fe* d_wires, const uint64
   // commitments into challenges
   auto fetch_comms = [&](uint32_t count, const std::function<int()>& keep_busy = nullptr) -> int {
     CAP_HIP(hipMemcpyAsync(hj, w.comms, sizeof(g1_jac) * count, hipMemcpyDeviceToHost, s));
-    CAP_HIP(hipStreamSynchronize(s));
+    CAP_HIP(wait_stream());
     if (keep_busy) {
       int brc = keep_busy();
       if (brc) return brc;
@@ -1075,33 +1151,11 @@ int prove_batch(const ProvingKey& K, uint32_t P, const fe* d_wires, const uint64
     CAP_HIP(hipStreamWaitEvent(s, c.ev_join, 0));
     return CAPGPU_OK;
   };
-  if ((rc = seg(0, [&]() -> int {
-         if (overlap) return r1_overlapped();
-         int r = chunks == 1 ? r1_chunk_kernels(0, P, false) : CAPGPU_OK;
-         return r ? r : r1_tail_kernels();
-       })))
-    return rc;
-  // (enqueued behind the commitments while the host hashes - unless the side stream already ran them beside the MSMs)
-  if ((rc = fetch_comms(P * NW, [&]() -> int {
-         if (overlap) return CAPGPU_OK;
-         return seg(1, [&]() -> int { return r3_wire_cosets(s); });
-       })))
-    return rc;
-  trace("pb_r1_done", c.slot);
-  std::vector<Chal> chal(P);
-  parallel_for(P, [&](uint32_t p) {
-    for (int i = 0; i < NW; i++) {
-      append_g1(tr[p], ha[p * NW + i]);
-      affine_to_words(ha[p * NW + i], proofs[p].wires_poly_comms[i]);
-    }
-    (void)get_challenge(tr[p]);  // plookup's tau: drawn by jf-plonk even when the circuit has no lookups
-    chal[p].beta = get_challenge(tr[p]);
-    chal[p].gamma = get_challenge(tr[p]);
-    chal[p].alpha = Fr::zero();
-    chal[p].alpha2 = Fr::zero();
-  });
-  CAP_HIP(hipMemcpyAsync(w.chal, chal.data(), sizeof(Chal) * P, hipMemcpyHostToDevice, s));
-
+  auto r1_body = [&]() -> int {
+    if (overlap) return r1_overlapped();
+    int r = chunks == 1 ? r1_chunk_kernels(0, P, false) : CAPGPU_OK;
+    return r ? r : r1_tail_kernels();
+  };
   // the commitment to z and - independent of it - z's coset evaluations for round 3: one after the other (the second while
   // the host hashes), or, for the small batches of `overlap`, side by side on the two streams
   auto z_cosets = [&](hipStream_t st) -> int {
@@ -1139,33 +1193,222 @@ int prove_batch(const ProvingKey& K, uint32_t P, const fe* d_wires, const uint64
     return r;
   };
   // ---- round 2: permutation grand product --------------------------------------------------------------
-  if ((rc = seg(2, [&]() -> int {
-         launch("k_perm_numden", k_perm_numden, dim3(cdiv(n, kThreads), P), dim3(kThreads), 0, s,
-                coeffs ? (const fe*)w.wev : d_wires, (const fe*)K.sig_eval, sig_of, (const fe*)dom_n->tw_fwd,
-                (const Chal*)w.chal, K.qc29, n, w.num, w.den);
-         {
-           uint32_t nb = cdiv(n, kScanBlock);
-           scan_exclusive<0, 0>(s, w.num, w.pre, n, n, P, w.scan_tot);
-           scan_exclusive<0, 1>(s, w.den, w.sfx, n, n, P, w.scan_tot + (size_t)P * nb);
-         }
-         if (inv_on_device) {
-           launch("k_perm_inv_total", k_perm_inv_total, dim3(cdiv(P, 64)), dim3(64), 0, s, (const fe*)w.sfx,
-                  (const fe*)w.den, n, w.inv_total, P);
-         } else {
-           launch("k_perm_total", k_perm_total, dim3(cdiv(P, 64)), dim3(64), 0, s, (const fe*)w.sfx, (const fe*)w.den, n,
-                  w.inv_total, P);
-           return CAPGPU_OK;  // the segment ends here: the host inverts the totals (below)
-         }
-         return finish_and_commit_z();
+  auto r2_body = [&]() -> int {
+    launch("k_perm_numden", k_perm_numden, dim3(cdiv(n, kThreads), P), dim3(kThreads), 0, s,
+           coeffs ? (const fe*)w.wev : d_wires, (const fe*)K.sig_eval, sig_of, (const fe*)dom_n->tw_fwd,
+           (const Chal*)w.chal, K.qc29, n, w.num, w.den);
+    {
+      uint32_t nb = cdiv(n, kScanBlock);
+      scan_exclusive<0, 0>(s, w.num, w.pre, n, n, P, w.scan_tot);
+      scan_exclusive<0, 1>(s, w.den, w.sfx, n, n, P, w.scan_tot + (size_t)P * nb);
+    }
+    if (inv_on_device) {
+      // (the product is a function of the secret witness: the device kernel runs a fixed-length chain, as the host does)
+      launch("k_perm_inv_total", k_perm_inv_total, dim3(cdiv(P, 64)), dim3(64), 0, s, (const fe*)w.sfx,
+             (const fe*)w.den, n, w.inv_total, P);
+    } else {
+      launch("k_perm_total", k_perm_total, dim3(cdiv(P, 64)), dim3(64), 0, s, (const fe*)w.sfx, (const fe*)w.den, n,
+             w.inv_total, P);
+      return CAPGPU_OK;  // the segment ends here: the host inverts the totals (below)
+    }
+    return finish_and_commit_z();
+  };
+  // ---- round 3: quotient polynomial (its seven coset transforms were enqueued behind the round 1 and 2 MSMs) ------
+  auto r3_body = [&]() -> int {
+    int r;
+    const fe* pkc = K.pk_coset;
+    if (K.recompute) {
+      // reference schedule: the 18 selector / sigma polynomials are re-transformed for every proof
+      for (uint32_t p = 0; p < P; p++)
+        if ((r = compute_pk_coset(s, K, w.pkc))) return r;
+      pkc = w.pkc;
+    }
+    launch("k_quotient", k_quotient, dim3(P, cdiv(m, kThreads)), dim3(kThreads), 0, s, pkc, pkc_of,
+           (const fe*)w.coset, (const fe*)dom_q->xs29, (const fe*)K.inv_nx1, (const Chal*)w.chal29, K.qc29, m, w.t);
+    if ((r = run_ntt3_inv(s, K.log_m, w.t, P))) return r;
+    {
+      size_t lo = NW * (n + 1) + 3;  // first index that must be zero: degree is exactly 5(n+1)+2
+      launch("k_check_degree", k_check_degree, dim3(cdiv(m - (lo - 1), kThreads), P), dim3(kThreads), 0, s,
+             (const fe*)w.t, m, lo, w.flags);
+    }
+    return run_msm(s, *B, w.t, m, NW, n + 2, n + 2, P * NW, w.comms);
+  };
+  // ---- round 4: evaluations -------------------------------------------------------------------------------
+  // what is evaluated where: pointers only, known when the call starts
+  auto make_edesc = [&]() {
+    std::vector<EvalDesc> ed((size_t)P * 10);
+    for (uint32_t p = 0; p < P; p++) {
+      const fe* pz = w.pows + ((size_t)p * 4 + 0) * ps;
+      const fe* pzw = w.pows + ((size_t)p * 4 + 1) * ps;
+      for (int i = 0; i < NW; i++) ed[p * 10 + i] = EvalDesc{w.wpoly + ((size_t)p * NW + i) * ps, pz, (uint32_t)(n + 2), 0};
+      for (int i = 0; i < NW - 1; i++)
+        ed[p * 10 + NW + i] = EvalDesc{key_of(p).coef + (size_t)(NS + i) * ps, pz, (uint32_t)n, 0};
+      ed[p * 10 + 9] = EvalDesc{w.zpoly + (size_t)p * ps, pzw, (uint32_t)(n + 3), 0};
+    }
+    return ed;
+  };
+  auto r4_body = [&]() -> int {
+    const uint32_t small_len = kPowLow + cdiv(ps, kPowLow);
+    launch("k_powers_small", k_powers_small, dim3(cdiv(small_len, kThreads), P * 4), dim3(kThreads), 0, s,
+           w.pows_small, small_len, (const fe*)w.pw);
+    launch("k_powers", k_powers, dim3(cdiv(ps, kThreads), P * 4), dim3(kThreads), 0, s, w.pows, ps, ps,
+           (const fe*)w.pows_small, small_len);
+    uint32_t per_chunk = cdiv(n + 3, kEvalChunks);
+    launch("k_eval_partial", k_eval_partial, dim3(kEvalChunks, P * 10), dim3(kThreads), 0, s,
+           (const EvalDesc*)w.edesc, w.eval_partial, kEvalChunks, per_chunk);
+    launch("k_eval_final", k_eval_final, dim3(P * 10), dim3(64), 0, s, (const fe*)w.eval_partial, kEvalChunks,
+           w.evals);
+    return CAPGPU_OK;
+  };
+  // ---- round 5: linearisation + opening proofs ---------------------------------------------------------
+  // the polynomials and lengths of proof p's 29 linear terms, in the order td::lin_scalars derives their scalars
+  auto term_polys = [&](uint32_t p, LinTerm* T) {
+    int t = 0;
+    auto add = [&](const fe* poly, size_t len) {
+      T[t].poly = poly;
+      T[t].len = (uint32_t)len;
+      t++;
+    };
+    const fe* const coef = key_of(p).coef;
+    for (int j = 0; j < NS; j++) add(coef + (size_t)j * ps, n);
+    add(w.zpoly + (size_t)p * ps, n + 3);
+    add(coef + (size_t)(NS + NW - 1) * ps, n);
+    for (int j = 0; j < NW; j++) add(w.t + (size_t)p * m + (size_t)j * (n + 2), n + 2);
+    for (int j = 0; j < NW; j++) add(w.wpoly + ((size_t)p * NW + j) * ps, n + 2);
+    for (int j = 0; j < NW - 1; j++) add(coef + (size_t)(NS + j) * ps, n);
+  };
+  // batchpoly[p][0] = linear combination, batchpoly[p][1] = z polynomial
+  auto r5_body = [&]() -> int {
+    launch("k_lincomb", k_lincomb, dim3(cdiv(ps, kThreads), P), dim3(kThreads), 0, s, (const LinTerm*)w.terms,
+           kLinTerms, w.batchpoly, 2 * ps, ps);
+    pad_copy(s, w.batchpoly + ps, 2 * ps, 0, w.zpoly, ps, 0, 1, P, n + 3, ps);
+    launch("k_div_prepare", k_div_prepare, dim3(cdiv(n + 3, kThreads), P * 2), dim3(kThreads), 0, s,
+           (const fe*)w.batchpoly, (const fe*)w.pows, ps, n + 3, w.hbuf);
+    // the suffix sums go to batchpoly (its contents are dead once h is formed)
+    scan_exclusive<1, 1>(s, w.hbuf, w.batchpoly, n + 3, ps, P * 2, w.scan_tot);
+    launch("k_div_finish", k_div_finish, dim3(cdiv(ps, kThreads), P * 2), dim3(kThreads), 0, s,
+           (const fe*)w.batchpoly, (const fe*)w.pows, ps, n + 3, w.quot);
+    return run_msm(s, *B, w.quot, ps, 1, 0, n + 2, P * 2, w.comms);
+  };
+  auto degree_verdict = [&](const uint32_t* flags) -> int {
+    for (uint32_t p = 0; p < P; p++) {
+      if (flags[p]) {
+        set_error("capgpu_plonk_prove: proof %u: quotient polynomial has the wrong degree (flags %u): "
+                  "the circuit is not satisfied by this witness",
+                  p, flags[p]);
+        return CAPGPU_ERR_PROOF;
+      }
+    }
+    return CAPGPU_OK;
+  };
+  const fe omega = ntt_root_of_unity(K.log_n);
+
+  if (dev_tr) {
+    // ---- the transcript on the device: every per-call value goes up now, the five rounds are ONE run of launches (one
+    // graph segment), the proofs come back in ABI layout with the degree flags, and the host waits once ----------------
+    // (The uploads below come from pageable vectors, like the blinders and public inputs above: the runtime may stage
+    // such a copy on the host before it returns.  They sit at the head of the call, ahead of every launch - the host is
+    // never made to wait for the call's own kernels - and are not counted by capgpu_plonk_sync_stats.)
+    std::vector<uint8_t> h_pre((size_t)P * tr_stride, 0);
+    std::vector<uint32_t> h_pre_len(P);
+    parallel_for(P, [&](uint32_t p) {
+      uint8_t* b = &h_pre[(size_t)p * tr_stride];
+      size_t o = 0;
+      auto put = [&](const void* src, size_t len) {
+        memcpy(b + o, src, len);
+        o += len;
+      };
+      if (msgs) {
+        if (msgs[p] && msg_lens[p]) put(msgs[p], msg_lens[p]);
+      } else if (ext_msg && ext_len) {
+        put(ext_msg, ext_len);
+      }
+      const ProvingKey& Kp = key_of(p);
+      put(Kp.vk_bytes.data(), Kp.vk_bytes.size());
+      for (size_t i = 0; i < Kp.num_inputs; i++) {
+        uint8_t e[32];
+        serialize_fr(fe_from_words(pub_inputs + 4 * (p * num_inputs + i)), e);
+        put(e, 32);
+      }
+      h_pre_len[p] = (uint32_t)o;
+    });
+    CAP_HIP(hipMemcpyAsync(w.tr_pre, h_pre.data(), h_pre.size(), hipMemcpyHostToDevice, s));
+    CAP_HIP(hipMemcpyAsync(w.tr_pre_len, h_pre_len.data(), sizeof(uint32_t) * P, hipMemcpyHostToDevice, s));
+    CAP_HIP(hipMemsetAsync(w.tr_state, 0, (size_t)P * 64, s));
+    const std::vector<EvalDesc> ed = make_edesc();
+    CAP_HIP(hipMemcpyAsync(w.edesc, ed.data(), sizeof(EvalDesc) * ed.size(), hipMemcpyHostToDevice, s));
+    std::vector<LinTerm> terms((size_t)P * kLinTerms);
+    memset((void*)terms.data(), 0, sizeof(LinTerm) * terms.size());
+    for (uint32_t p = 0; p < P; p++) term_polys(p, &terms[(size_t)p * kLinTerms]);
+    CAP_HIP(hipMemcpyAsync(w.terms, terms.data(), sizeof(LinTerm) * terms.size(), hipMemcpyHostToDevice, s));
+    const td::TrBufs tb{w.tr_state, w.tr_pre, w.tr_pre_len, w.tr_app, tr_stride};
+    td::LinIn lin_base;
+    memset((void*)&lin_base, 0, sizeof lin_base);
+    for (int i = 0; i < NW; i++) lin_base.k[i] = K.qc.k[i];
+    lin_base.n = n;
+    if ((rc = seg(0, [&]() -> int {
+           int r;
+           if ((r = r1_body())) return r;
+           launch("k_tr_comms_r1", td::k_tr_comms<1>, dim3(P), dim3(64), 0, s, tb, (const g1_jac*)w.comms, w.d_proofs, w.chal,
+                  w.chal29, w.zeta, w.pw, omega, P);
+           if (!overlap && (r = r3_wire_cosets(s))) return r;
+           if ((r = r2_body())) return r;
+           launch("k_tr_comms_r2", td::k_tr_comms<2>, dim3(P), dim3(64), 0, s, tb, (const g1_jac*)w.comms, w.d_proofs, w.chal,
+                  w.chal29, w.zeta, w.pw, omega, P);
+           if (!overlap && (r = z_cosets(s))) return r;
+           if ((r = r3_body())) return r;
+           launch("k_tr_comms_r3", td::k_tr_comms<3>, dim3(P), dim3(64), 0, s, tb, (const g1_jac*)w.comms, w.d_proofs, w.chal,
+                  w.chal29, w.zeta, w.pw, omega, P);
+           if ((r = r4_body())) return r;
+           launch("k_tr_evals", td::k_tr_evals, dim3(P), dim3(64), 0, s, tb, (const fe*)w.evals, w.d_proofs,
+                  (const Chal*)w.chal, (const fe*)w.zeta, w.terms, lin_base, P);
+           if ((r = r5_body())) return r;
+           launch("k_tr_open", td::k_tr_open, dim3(cdiv(P, 64)), dim3(64), 0, s, (const g1_jac*)w.comms, w.d_proofs, P);
+           return CAPGPU_OK;
+         })))
+      return rc;
+    uint32_t* flags = h_flags;
+    CAP_HIP(hipMemcpyAsync(h_proofs, w.d_proofs, proofs_bytes, hipMemcpyDeviceToHost, s));
+    CAP_HIP(hipMemcpyAsync(flags, w.flags, sizeof(uint32_t) * P, hipMemcpyDeviceToHost, s));
+    CAP_HIP(wait_stream());
+    trace("pb_r5_done", c.slot);
+    if ((rc = take_launch_error())) return rc;
+    if ((rc = degree_verdict(flags))) return rc;
+    memcpy(proofs, h_proofs, proofs_bytes);
+    side_drain.armed = false;  // (every join was waited for in stream order and the stream has drained)
+    return CAPGPU_OK;
+  }
+
+  if ((rc = seg(0, r1_body))) return rc;
+  // (enqueued behind the commitments while the host hashes - unless the side stream already ran them beside the MSMs)
+  if ((rc = fetch_comms(P * NW, [&]() -> int {
+         if (overlap) return CAPGPU_OK;
+         return seg(1, [&]() -> int { return r3_wire_cosets(s); });
        })))
     return rc;
+  trace("pb_r1_done", c.slot);
+  std::vector<Chal> chal(P);
+  parallel_for(P, [&](uint32_t p) {
+    for (int i = 0; i < NW; i++) {
+      append_g1(tr[p], ha[p * NW + i]);
+      affine_to_words(ha[p * NW + i], proofs[p].wires_poly_comms[i]);
+    }
+    (void)get_challenge(tr[p]);  // plookup's tau: drawn by jf-plonk even when the circuit has no lookups
+    chal[p].beta = get_challenge(tr[p]);
+    chal[p].gamma = get_challenge(tr[p]);
+    chal[p].alpha = Fr::zero();
+    chal[p].alpha2 = Fr::zero();
+  });
+  CAP_HIP(hipMemcpyAsync(w.chal, chal.data(), sizeof(Chal) * P, hipMemcpyHostToDevice, s));
+
+  if ((rc = seg(2, r2_body))) return rc;
   if (!inv_on_device) {
     // 1 / prod(den) per proof on the host: P products come back (32 B each), one shared inversion (Montgomery's trick),
     // P inverses go out - a round trip of tens of microseconds against 0.17 ms of a single device thread
     std::vector<fe> pref(P);
     fe* tot = h_tot;
     CAP_HIP(hipMemcpyAsync(tot, w.inv_total, sizeof(fe) * P, hipMemcpyDeviceToHost, s));
-    CAP_HIP(hipStreamSynchronize(s));
+    CAP_HIP(wait_stream());
     // (a proof whose product is zero - one of its denominators vanished, probability ~ 2^-236 - must not poison the
     // shared inversion: it is left out of the chain and gets the inverse 0, as the per-proof device inversion gave it)
     fe acc = Fr::one();
@@ -1211,51 +1454,22 @@ int prove_batch(const ProvingKey& K, uint32_t P, const fe* d_wires, const uint64
   });
   CAP_HIP(hipMemcpyAsync(w.chal29, chal29.data(), sizeof(Chal) * P, hipMemcpyHostToDevice, s));
 
-  // ---- round 3: quotient polynomial (its seven coset transforms were enqueued behind the round 1 and 2 MSMs) ------
-  if ((rc = seg(4, [&]() -> int {
-         int r;
-         const fe* pkc = K.pk_coset;
-         if (K.recompute) {
-           // reference schedule: the 18 selector / sigma polynomials are re-transformed for every proof
-           for (uint32_t p = 0; p < P; p++)
-             if ((r = compute_pk_coset(s, K, w.pkc))) return r;
-           pkc = w.pkc;
-         }
-         launch("k_quotient", k_quotient, dim3(P, cdiv(m, kThreads)), dim3(kThreads), 0, s, pkc, pkc_of,
-                (const fe*)w.coset, (const fe*)dom_q->xs29, (const fe*)K.inv_nx1, (const Chal*)w.chal29, K.qc29, m, w.t);
-         if ((r = run_ntt3_inv(s, K.log_m, w.t, P))) return r;
-         {
-           size_t lo = NW * (n + 1) + 3;  // first index that must be zero: degree is exactly 5(n+1)+2
-           launch("k_check_degree", k_check_degree, dim3(cdiv(m - (lo - 1), kThreads), P), dim3(kThreads), 0, s,
-                  (const fe*)w.t, m, lo, w.flags);
-         }
-         return run_msm(s, *B, w.t, m, NW, n + 2, n + 2, P * NW, w.comms);
-       })))
-    return rc;
+  if ((rc = seg(4, r3_body))) return rc;
   uint32_t* flags = h_flags;
   CAP_HIP(hipMemcpyAsync(flags, w.flags, sizeof(uint32_t) * P, hipMemcpyDeviceToHost, s));
   if ((rc = fetch_comms(P * NW))) return rc;
   trace("pb_r3_done", c.slot);
-  for (uint32_t p = 0; p < P; p++) {
-    if (flags[p]) {
-      set_error("capgpu_plonk_prove: proof %u: quotient polynomial has the wrong degree (flags %u): "
-                "the circuit is not satisfied by this witness",
-                p, flags[p]);
-      return CAPGPU_ERR_PROOF;
-    }
-  }
-  std::vector<fe> zeta(P), zeta_w(P);
+  if ((rc = degree_verdict(flags))) return rc;
+  std::vector<fe> zeta(P);
   std::vector<fe> pw((size_t)P * 4 * 24);
-  const fe omega = ntt_root_of_unity(K.log_n);
   parallel_for(P, [&](uint32_t p) {
     for (int i = 0; i < NW; i++) {
       append_g1(tr[p], ha[p * NW + i]);
       affine_to_words(ha[p * NW + i], proofs[p].split_quot_poly_comms[i]);
     }
     zeta[p] = get_challenge(tr[p]);
-    zeta_w[p] = Fr::mul(zeta[p], omega);
-    fe zi = Fr::inv(Fr::mul(zeta[p], zeta_w[p]));  // one inversion for both: 1/z = zw * zi, 1/zw = z * zi
-    fe bases4[4] = {zeta[p], zeta_w[p], Fr::mul(zeta_w[p], zi), Fr::mul(zeta[p], zi)};
+    fe bases4[4];  // zeta, zeta omega and their inverses, from one inversion
+    td::zeta_bases(zeta[p], omega, bases4);
     for (int q = 0; q < 4; q++) {
       fe x = bases4[q];
       for (int b = 0; b < 24; b++) {
@@ -1265,127 +1479,42 @@ int prove_batch(const ProvingKey& K, uint32_t P, const fe* d_wires, const uint64
     }
   });
 
-  // ---- round 4: evaluations -------------------------------------------------------------------------------
   CAP_HIP(hipMemcpyAsync(w.pw, pw.data(), sizeof(fe) * pw.size(), hipMemcpyHostToDevice, s));
-  std::vector<EvalDesc> ed((size_t)P * 10);
-  for (uint32_t p = 0; p < P; p++) {
-    const fe* pz = w.pows + ((size_t)p * 4 + 0) * ps;
-    const fe* pzw = w.pows + ((size_t)p * 4 + 1) * ps;
-    for (int i = 0; i < NW; i++) ed[p * 10 + i] = EvalDesc{w.wpoly + ((size_t)p * NW + i) * ps, pz, (uint32_t)(n + 2), 0};
-    for (int i = 0; i < NW - 1; i++)
-      ed[p * 10 + NW + i] = EvalDesc{key_of(p).coef + (size_t)(NS + i) * ps, pz, (uint32_t)n, 0};
-    ed[p * 10 + 9] = EvalDesc{w.zpoly + (size_t)p * ps, pzw, (uint32_t)(n + 3), 0};
-  }
+  const std::vector<EvalDesc> ed = make_edesc();
   CAP_HIP(hipMemcpyAsync(w.edesc, ed.data(), sizeof(EvalDesc) * ed.size(), hipMemcpyHostToDevice, s));
-  if ((rc = seg(5, [&]() -> int {
-         const uint32_t small_len = kPowLow + cdiv(ps, kPowLow);
-         launch("k_powers_small", k_powers_small, dim3(cdiv(small_len, kThreads), P * 4), dim3(kThreads), 0, s,
-                w.pows_small, small_len, (const fe*)w.pw);
-         launch("k_powers", k_powers, dim3(cdiv(ps, kThreads), P * 4), dim3(kThreads), 0, s, w.pows, ps, ps,
-                (const fe*)w.pows_small, small_len);
-         uint32_t per_chunk = cdiv(n + 3, kEvalChunks);
-         launch("k_eval_partial", k_eval_partial, dim3(kEvalChunks, P * 10), dim3(kThreads), 0, s,
-                (const EvalDesc*)w.edesc, w.eval_partial, kEvalChunks, per_chunk);
-         launch("k_eval_final", k_eval_final, dim3(P * 10), dim3(64), 0, s, (const fe*)w.eval_partial, kEvalChunks,
-                w.evals);
-         return CAPGPU_OK;
-       })))
-    return rc;
+  if ((rc = seg(5, r4_body))) return rc;
   fe* evals = h_evals;
   CAP_HIP(hipMemcpyAsync(evals, w.evals, sizeof(fe) * (size_t)P * 10, hipMemcpyDeviceToHost, s));
-  CAP_HIP(hipStreamSynchronize(s));
+  CAP_HIP(wait_stream());
   trace("pb_r4_done", c.slot);
 
-  // ---- round 5: linearisation + opening proofs ---------------------------------------------------------
   std::vector<LinTerm> terms((size_t)P * kLinTerms);
-  const fe n_mont = fr_from_u64((uint64_t)n);
-  std::atomic<int> lin_err{0};
   parallel_for(P, [&](uint32_t p) {
     const fe* ev = &evals[(size_t)p * 10];
     const fe *we = ev, *se = ev + NW;
-    const fe znext = ev[9];
     for (int i = 0; i < 10; i++) append_fr(tr[p], ev[i]);
     for (int i = 0; i < NW; i++) fe_to_words(we[i], proofs[p].wires_evals[i]);
     for (int i = 0; i < NW - 1; i++) fe_to_words(se[i], proofs[p].wire_sigma_evals[i]);
-    fe_to_words(znext, proofs[p].perm_next_eval);
-    const fe v = get_challenge(tr[p]);
-    const Chal& ch = chal[p];
-    // scalars
-    uint32_t e_n[8] = {(uint32_t)n, (uint32_t)((uint64_t)n >> 32), 0, 0, 0, 0, 0, 0};
-    fe zeta_n = Fr::pow(zeta[p], e_n);
-    fe zh = Fr::sub(zeta_n, Fr::one());
-    fe l1 = Fr::mul(zh, Fr::inv(Fr::mul(n_mont, Fr::sub(zeta[p], Fr::one()))));
+    fe_to_words(ev[9], proofs[p].perm_next_eval);
+    // the scalars of the linear terms: the derivation the device transcript runs as well (td::lin_scalars)
+    td::LinIn in;
+    for (int i = 0; i < 10; i++) in.ev[i] = ev[i];
+    in.beta = chal[p].beta;
+    in.gamma = chal[p].gamma;
+    in.alpha = chal[p].alpha;
+    in.alpha2 = chal[p].alpha2;
+    in.zeta = zeta[p];
+    in.v = get_challenge(tr[p]);
+    for (int i = 0; i < NW; i++) in.k[i] = K.qc.k[i];
+    in.n = n;
+    fe sc[td::kLinScalars];
+    td::lin_scalars(in, sc);
     LinTerm* T = &terms[(size_t)p * kLinTerms];
-    int t = 0;
-    auto add_term = [&](const fe* poly, const fe& sc, size_t len) {
-      T[t].poly = poly;
-      T[t].scalar = Fr29::pack(Fr29::canonical(Fr29::from_ext(sc)));  // internal form: k_lincomb is on the lazy field
-      T[t].len = (uint32_t)len;
-      t++;
-    };
-    const fe* const coef = key_of(p).coef;
-    auto sel = [&](int i) { return coef + (size_t)i * ps; };
-    for (int j = 0; j < 4; j++) add_term(sel(j), we[j], n);
-    fe w01 = Fr::mul(we[0], we[1]), w23 = Fr::mul(we[2], we[3]);
-    add_term(sel(4), w01, n);
-    add_term(sel(5), w23, n);
-    for (int j = 0; j < 4; j++) {
-      fe w2 = Fr::sqr(we[j]);
-      add_term(sel(6 + j), Fr::mul(Fr::sqr(w2), we[j]), n);
-    }
-    add_term(sel(10), Fr::neg(we[4]), n);
-    add_term(sel(11), Fr::one(), n);
-    add_term(sel(12), Fr::mul(Fr::mul(w01, w23), we[4]), n);
-    // z(X) coefficient: alpha * prod(w_i + beta k_i zeta + gamma) + alpha^2 L1(zeta)
-    fe bz = Fr::mul(ch.beta, zeta[p]);
-    fe cz = ch.alpha;
-    for (int j = 0; j < NW; j++)
-      cz = Fr::mul(cz, Fr::add(Fr::add(we[j], ch.gamma), j == 0 ? bz : Fr::mul(K.qc.k[j], bz)));
-    cz = Fr::add(cz, Fr::mul(ch.alpha2, l1));
-    add_term(w.zpoly + (size_t)p * ps, cz, n + 3);
-    // last sigma polynomial: - alpha beta z(zeta w) prod_{i<4}(w_i + beta sigma_i + gamma)
-    fe cs = Fr::mul(Fr::mul(ch.alpha, ch.beta), znext);
-    for (int j = 0; j < NW - 1; j++) cs = Fr::mul(cs, Fr::add(Fr::add(we[j], ch.gamma), Fr::mul(ch.beta, se[j])));
-    add_term(coef + (size_t)(NS + NW - 1) * ps, Fr::neg(cs), n);
-    // quotient part: - Z_H(zeta) * sum zeta^(i(n+2)) t_i(X)
-    uint32_t e_n2[8] = {(uint32_t)(n + 2), (uint32_t)((uint64_t)(n + 2) >> 32), 0, 0, 0, 0, 0, 0};
-    fe zp = Fr::pow(zeta[p], e_n2);
-    fe cq = Fr::neg(zh);
-    for (int j = 0; j < NW; j++) {
-      add_term(w.t + (size_t)p * m + (size_t)j * (n + 2), cq, n + 2);
-      cq = Fr::mul(cq, zp);
-    }
-    // batched opening at zeta: + v^(j+1) * {wire polys, first 4 sigma polys}
-    fe cf = v;
-    for (int j = 0; j < NW; j++) {
-      add_term(w.wpoly + ((size_t)p * NW + j) * ps, cf, n + 2);
-      cf = Fr::mul(cf, v);
-    }
-    for (int j = 0; j < NW - 1; j++) {
-      add_term(coef + (size_t)(NS + j) * ps, cf, n);
-      cf = Fr::mul(cf, v);
-    }
-    if (t != (int)kLinTerms) lin_err = t;
+    term_polys(p, T);
+    for (uint32_t t = 0; t < kLinTerms; t++) T[t].scalar = td::to_internal(sc[t]);  // k_lincomb is on the lazy field
   });
-  if (lin_err) {
-    set_error("capgpu: internal error: %d linear terms", lin_err.load());
-    return CAPGPU_ERR_PROOF;
-  }
   CAP_HIP(hipMemcpyAsync(w.terms, terms.data(), sizeof(LinTerm) * terms.size(), hipMemcpyHostToDevice, s));
-  // batchpoly[p][0] = linear combination, batchpoly[p][1] = z polynomial
-  if ((rc = seg(6, [&]() -> int {
-         launch("k_lincomb", k_lincomb, dim3(cdiv(ps, kThreads), P), dim3(kThreads), 0, s, (const LinTerm*)w.terms,
-                kLinTerms, w.batchpoly, 2 * ps, ps);
-         pad_copy(s, w.batchpoly + ps, 2 * ps, 0, w.zpoly, ps, 0, 1, P, n + 3, ps);
-         launch("k_div_prepare", k_div_prepare, dim3(cdiv(n + 3, kThreads), P * 2), dim3(kThreads), 0, s,
-                (const fe*)w.batchpoly, (const fe*)w.pows, ps, n + 3, w.hbuf);
-         // the suffix sums go to batchpoly (its contents are dead once h is formed)
-         scan_exclusive<1, 1>(s, w.hbuf, w.batchpoly, n + 3, ps, P * 2, w.scan_tot);
-         launch("k_div_finish", k_div_finish, dim3(cdiv(ps, kThreads), P * 2), dim3(kThreads), 0, s,
-                (const fe*)w.batchpoly, (const fe*)w.pows, ps, n + 3, w.quot);
-         return run_msm(s, *B, w.quot, ps, 1, 0, n + 2, P * 2, w.comms);
-       })))
-    return rc;
+  if ((rc = seg(6, r5_body))) return rc;
   if ((rc = fetch_comms(P * 2))) return rc;
   trace("pb_r5_done", c.slot);
   for (uint32_t p = 0; p < P; p++) {
@@ -2709,6 +2838,66 @@ int capgpu_plonk_set_wire_commit(int mode) {
   }
   g_wire_commit.store(mode);
   return CAPGPU_OK;
+}
+
+int capgpu_plonk_set_transcript(int mode) {
+  if (mode != CAPGPU_TRANSCRIPT_HOST && mode != CAPGPU_TRANSCRIPT_DEVICE) {
+    set_error("capgpu_plonk_set_transcript: mode must be CAPGPU_TRANSCRIPT_HOST (0) or CAPGPU_TRANSCRIPT_DEVICE (1)");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  g_transcript.store(mode);
+  return CAPGPU_OK;
+}
+
+int capgpu_plonk_get_transcript(int* mode_out) {
+  if (!mode_out) {
+    set_error("capgpu_plonk_get_transcript: bad argument");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  *mode_out = transcript_mode();
+  return CAPGPU_OK;
+}
+
+int capgpu_plonk_sync_stats(uint64_t* prove_calls_out, uint64_t* stream_waits_out) {
+  if (prove_calls_out) *prove_calls_out = g_prove_calls.load();
+  if (stream_waits_out) *stream_waits_out = g_stream_waits.load();
+  return CAPGPU_OK;
+}
+
+int capgpu_keccak256_batch_dev(const uint8_t* data, const uint64_t* offsets, int count, uint8_t* digests_out) {
+  CAP_CHECK_INIT();
+  Context& c = ctx();
+  Entry lk(c);
+  if (count < 0 || (count && (!offsets || !digests_out))) {
+    set_error("capgpu_keccak256_batch_dev: bad argument");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  if (count == 0) return CAPGPU_OK;
+  for (int i = 0; i < count; i++)
+    if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] >= (1ull << 31)) {
+      set_error("capgpu_keccak256_batch_dev: offsets must not decrease, and a message must be shorter than 2^31 bytes");
+      return CAPGPU_ERR_INVALID_ARG;
+    }
+  const uint64_t lo = offsets[0], total = offsets[count] - lo;
+  if (total && !data) {
+    set_error("capgpu_keccak256_batch_dev: bad argument");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  hipStream_t s = c.stream;
+  DevTmp<uint8_t> d_data, d_out;
+  DevTmp<uint64_t> d_off;
+  CAP_HIP(d_data.alloc(total));
+  CAP_HIP(d_out.alloc((size_t)count * 32));
+  CAP_HIP(d_off.alloc((size_t)count + 1));
+  std::vector<uint64_t> rel(offsets, offsets + count + 1);
+  for (auto& o : rel) o -= lo;
+  if (total) CAP_HIP(hipMemcpyAsync(d_data, data + lo, total, hipMemcpyHostToDevice, s));
+  CAP_HIP(hipMemcpyAsync(d_off, rel.data(), sizeof(uint64_t) * rel.size(), hipMemcpyHostToDevice, s));
+  launch("k_keccak_batch", td::k_keccak_batch, dim3((uint32_t)count), dim3(64), 0, s, (const uint8_t*)d_data.p,
+         (const uint64_t*)d_off.p, (uint32_t)count, d_out.p);
+  CAP_HIP(hipMemcpyAsync(digests_out, d_out, (size_t)count * 32, hipMemcpyDeviceToHost, s));
+  CAP_HIP(hipStreamSynchronize(s));
+  return take_launch_error();
 }
 
 int capgpu_plonk_graph_stats(uint64_t* segments_captured_out, uint64_t* segments_replayed_out) {

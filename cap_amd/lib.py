@@ -706,6 +706,46 @@ def plonk_graph_stats():
     return a.value, b.value
 
 
+TRANSCRIPT_HOST, TRANSCRIPT_DEVICE = 0, 1  # CAPGPU_TRANSCRIPT_* of include/capgpu.h
+
+
+def plonk_set_transcript(mode):
+    """capgpu_plonk_set_transcript: 'host' / 'device' (or the integers) - where the Fiat-Shamir transcript of the next
+    prove calls runs.  Process-wide; callable before init.  Same proof bytes either way."""
+    if isinstance(mode, str):
+        mode = {"host": TRANSCRIPT_HOST, "device": TRANSCRIPT_DEVICE}[mode]
+    check(load().capgpu_plonk_set_transcript(ctypes.c_int(int(mode))))
+
+
+def plonk_get_transcript() -> int:
+    m = ctypes.c_int(-1)
+    check(load().capgpu_plonk_get_transcript(ctypes.byref(m)))
+    return m.value
+
+
+def plonk_sync_stats():
+    """(device batches proved, host waits on the proving stream inside them) since process start"""
+    a, b = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    check(load().capgpu_plonk_sync_stats(ctypes.byref(a), ctypes.byref(b)))
+    return a.value, b.value
+
+
+def keccak256_batch_dev(messages):
+    """Keccak-256 of every bytes object of `messages` by the device transcript's sponge (one wavefront per message):
+    a list of 32-byte digests."""
+    messages = [bytes(m) for m in messages]
+    count = len(messages)
+    offs = np.zeros(count + 1, dtype=np.uint64)
+    if count:
+        offs[1:] = np.cumsum([len(m) for m in messages], dtype=np.uint64)
+    data = np.frombuffer(b"".join(messages) + b"\0", dtype=np.uint8).copy()
+    out = np.zeros(32 * max(count, 1), dtype=np.uint8)
+    check(load().capgpu_keccak256_batch_dev(data.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                            offs.ctypes.data_as(u64p), ctypes.c_int(count),
+                                            out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
+    return [out[32 * i:32 * i + 32].tobytes() for i in range(count)]
+
+
 def plonk_coalescing_stats():
     b, p = ctypes.c_uint64(0), ctypes.c_uint64(0)
     check(load().capgpu_plonk_coalescing_stats(ctypes.byref(b), ctypes.byref(p)))

@@ -392,10 +392,39 @@ int capgpu_plonk_set_wire_commit(int mode);
 /* device batches run and proofs made through the coalescer so far */
 int capgpu_plonk_coalescing_stats(uint64_t* batches_out, uint64_t* proofs_out);
 /* Small batches (count <= CAPGPU_GRAPH_MAX_BATCH, default 16; 0 switches it off) replay their kernel schedule as
- * hipGraphs: the ~100 launches of a proof fall into seven segments between the host's transcript steps; the second call
- * with the same key, batch size and buffers captures them, later calls launch seven graphs instead.  Proofs are the same
- * bytes either way.  Counters since process start: segments captured (instantiated) and segments replayed. */
+ * hipGraphs: the ~100 launches of a proof fall into up to eight segments between the host's transcript steps, or into ONE
+ * with the transcript on the device (capgpu_plonk_set_transcript).  The second call with the same key, batch size,
+ * buffers and transcript mode captures them; later calls launch the graphs instead.  Proofs are the same bytes either
+ * way.  Counters since process start: segments captured (instantiated) and segments replayed. */
 int capgpu_plonk_graph_stats(uint64_t* segments_captured_out, uint64_t* segments_replayed_out);
+/* Where the Fiat-Shamir transcript of a prove call runs.  Replaces the per-round use of
+ * `jf_plonk::transcript::SolidityTranscript` inside `PlonkKzgSnark::prove` (src/proof/transfer.rs:39-45, :181-186).
+ *  - CAPGPU_TRANSCRIPT_HOST (the default): after every round the commitments come back to the host, which converts them
+ *    to affine, hashes them and sends the challenges - the proving stream is waited for six or seven times per call.
+ *  - CAPGPU_TRANSCRIPT_DEVICE: Keccak-256, the challenge arithmetic, Jacobian -> affine of the 13 commitments, zeta's
+ *    tables and the linearisation scalars run on the device (cap_amd/csrc/transcript_dev.hpp, one wavefront per proof):
+ *    the five rounds are enqueued without a host wait, the proofs come back in this header's layout with ONE copy and
+ *    ONE synchronisation, and a small batch replays as one graph segment instead of up to eight.  Proofs are the same bytes.
+ *    A witness that does not satisfy its circuit is refused with the same code and message as in host mode, after the
+ *    call's single synchronisation instead of after round 3.
+ * Every prove entry point honours the mode.  While capgpu_plonk_shard_msm is on, the commitments meet through a
+ * host-driven exchange between the ranks and calls use the host transcript whatever the mode says.
+ * Process-wide, callable before capgpu_init; takes effect with the next prove call.  CAPGPU_TRANSCRIPT=device|host in
+ * the environment sets the initial mode.  An unknown mode returns CAPGPU_ERR_INVALID_ARG. */
+#define CAPGPU_TRANSCRIPT_HOST 0
+#define CAPGPU_TRANSCRIPT_DEVICE 1
+int capgpu_plonk_set_transcript(int mode);
+int capgpu_plonk_get_transcript(int* mode_out);
+/* Counters since process start: device batches proved (one per context part of a dealt call) and the times those calls
+ * made the host wait for the proving stream, from the batch's first launch to its return (the optional witness check
+ * of capgpu_plonk_set_precheck, which runs and is waited for before anything is committed to, is not counted).  Either
+ * pointer may be NULL. */
+int capgpu_plonk_sync_stats(uint64_t* prove_calls_out, uint64_t* stream_waits_out);
+/* Keccak-256 (original 0x01 padding, as sha3 0.10.1's Keccak256 under jf-plonk's transcript) of `count` messages by the
+ * device transcript's sponge, one wavefront per message: message i is data[offsets[i] .. offsets[i + 1]) (host memory,
+ * offsets non-decreasing, each message shorter than 2^31 bytes); digests_out receives count * 32 bytes.  The handle by
+ * which the hash kernel is checked on its own. */
+int capgpu_keccak256_batch_dev(const uint8_t* data, const uint64_t* offsets, int count, uint8_t* digests_out);
 /* Same, `count` independent proofs under one key pipelined on the device; per-proof arrays are
  * consecutive (wires: count * 5 * n, pub_inputs: count * num_inputs, blinders: count * 13).  With several device
  * contexts bound (capgpu_init) and a calling thread that did not bind itself to one, the batch is cut into contiguous
