@@ -24,6 +24,7 @@ pub const CAPGPU_ERR_NOT_INITIALISED: c_int = -6;
 pub const CAPGPU_ERR_PROOF: c_int = -7;
 pub const CAPGPU_ERR_SERIALIZATION: c_int = -8;
 pub const CAPGPU_ERR_COMM: c_int = -9;
+pub const CAPGPU_ERR_BUSY: c_int = -10;
 
 pub const NUM_WIRE_TYPES: usize = 5;
 pub const NUM_SELECTORS: usize = 13;
@@ -90,6 +91,7 @@ extern "C" {
     pub fn capgpu_trim(bytes_released_out: *mut u64, contexts_busy_out: *mut c_int) -> c_int;
     pub fn capgpu_set_memory_limit(scratch_bytes_per_device: u64) -> c_int;
     pub fn capgpu_scratch_info(scratch_bytes_out: *mut u64, limit_out: *mut u64) -> c_int;
+    pub fn capgpu_scratch_stats(grow_events_out: *mut u64, grow_bytes_out: *mut u64, grow_ms_out: *mut f64) -> c_int;
     pub fn capgpu_trace_enable(on: c_int) -> c_int;
     pub fn capgpu_trace_dump(path: *const c_char, events_out: *mut u64) -> c_int;
     // ---- device memory / stream
@@ -223,6 +225,18 @@ extern "C" {
                                             pub_inputs: *const u64, num_inputs: usize, input_form: c_int,
                                             faults_out: *mut capgpu_witness_fault) -> c_int;
     pub fn capgpu_plonk_set_precheck(on: c_int) -> c_int;
+
+    pub fn capgpu_plonk_prove_batch_async(pk_handle: u64, count: c_int, wires: *const u64, pub_inputs: *const u64,
+                                          num_inputs: usize, ext_msg: *const u8, ext_msg_len: usize,
+                                          blinders: *const u64, input_form: c_int, proofs_out: *mut capgpu_proof,
+                                          ticket_out: *mut u64) -> c_int;
+    pub fn capgpu_plonk_prove_multi_async(pk_handles: *const u64, count: c_int, wires: *const u64,
+                                          pub_inputs: *const u64, num_inputs: usize, ext_msgs: *const *const u8,
+                                          ext_msg_lens: *const usize, blinders: *const u64, input_form: c_int,
+                                          proofs_out: *mut capgpu_proof, ticket_out: *mut u64) -> c_int;
+    pub fn capgpu_wait(ticket: u64, timeout_ms: u32, done_out: *mut c_int) -> c_int;
+    pub fn capgpu_async_stats(submitted_out: *mut u64, completed_out: *mut u64, max_running_out: *mut u32) -> c_int;
+    pub fn capgpu_plonk_reserve(pk_handle: u64, count: c_int, input_form: c_int, slot: c_int) -> c_int;
     // ---- verification (host only)
     pub fn capgpu_g2_generator(out: *mut u64) -> c_int;
     pub fn capgpu_g2_mul(q: *const u64, scalar: *const u64, out: *mut u64) -> c_int;
@@ -354,6 +368,21 @@ pub fn set_memory_limit(scratch_bytes_per_device: u64) -> Result<()> {
     check(unsafe { capgpu_set_memory_limit(scratch_bytes_per_device) })
 }
 
+/// (growths of scratch buffers and pinned areas since `init`, bytes of new capacity, milliseconds spent growing): read
+/// around a timed section - a non-zero difference says an allocation landed inside it (`ProvingKey::reserve` avoids it).
+pub fn scratch_stats() -> Result<(u64, u64, f64)> {
+    let (mut events, mut bytes, mut ms) = (0u64, 0u64, 0f64);
+    check(unsafe { capgpu_scratch_stats(&mut events, &mut bytes, &mut ms) })?;
+    Ok((events, bytes, ms))
+}
+
+/// (tickets accepted, tickets finished, most running at once on one device) since `init`.
+pub fn async_stats() -> Result<(u64, u64, u32)> {
+    let (mut submitted, mut completed, mut max_running) = (0u64, 0u64, 0u32);
+    check(unsafe { capgpu_async_stats(&mut submitted, &mut completed, &mut max_running) })?;
+    Ok((submitted, completed, max_running))
+}
+
 /// A device-resident commit key (`UniversalSrs::powers_of_g` / `CommitKey::powers_of_g`).
 pub struct Srs {
     handle: u64,
@@ -473,6 +502,32 @@ impl ProvingKey {
         })?;
         Ok(proof)
     }
+    /// Starts proving `proofs.len()` notes from host memory and returns at once: the ticket borrows the witnesses, public
+    /// inputs, blinders and the output slice for its lifetime, `wait()` - or its `Drop` - ends the borrow.  A `Vec` of
+    /// notes is proved from ONE thread by keeping two tickets in flight: no rayon pool, no
+    /// `capgpu_set_device`.  `wires`: per proof the 5 columns of n values (or coefficients, `input_form`), consecutive;
+    /// `blinders`: 13 per proof.  `CAPGPU_ERR_BUSY`: 64 tickets outstanding - wait for one and submit again.
+    pub fn prove_batch_async<'a>(&self, wires: &'a [[u64; 4]], pub_inputs: &'a [[u64; 4]], ext_msg: &[u8],
+                                 blinders: &'a [[u64; 4]], input_form: c_int, proofs: &'a mut [capgpu_proof])
+                                 -> Result<ProveTicket<'a>> {
+        let count = proofs.len();
+        assert_eq!(wires.len(), count * NUM_WIRE_TYPES * self.domain_size);
+        assert_eq!(pub_inputs.len(), count * self.num_inputs);
+        assert_eq!(blinders.len(), count * 13);
+        let mut ticket = 0u64;
+        check(unsafe {
+            capgpu_plonk_prove_batch_async(self.handle, count as c_int, wires.as_ptr() as *const u64,
+                                           pub_inputs.as_ptr() as *const u64, self.num_inputs, ext_msg.as_ptr(),
+                                           ext_msg.len(), blinders.as_ptr() as *const u64, input_form,
+                                           proofs.as_mut_ptr(), &mut ticket)
+        })?;
+        Ok(ProveTicket { ticket, done: false, _borrow: std::marker::PhantomData })
+    }
+    /// Sizes context `slot` (-1: every context) ahead for batches of `count` host-resident proofs under this key, so that
+    /// no allocation lands inside a steady-state call (`scratch_stats` then stays put).
+    pub fn reserve(&self, count: usize, input_form: c_int, slot: i32) -> Result<()> {
+        check(unsafe { capgpu_plonk_reserve(self.handle, count as c_int, input_form, slot) })
+    }
     pub fn handle(&self) -> u64 {
         self.handle
     }
@@ -480,6 +535,45 @@ impl ProvingKey {
 impl Drop for ProvingKey {
     fn drop(&mut self) {
         unsafe { capgpu_plonk_free_key(self.handle) };
+    }
+}
+
+/// A batch being proved by a worker thread of the library (`ProvingKey::prove_batch_async`).  It holds the borrows of the
+/// input slices and of the output slice: the compiler keeps the caller from touching `proofs` - or freeing the witnesses -
+/// until the ticket is gone, which is what the C ABI asks for.  Dropping a ticket waits for it.
+pub struct ProveTicket<'a> {
+    ticket: u64,
+    done: bool,
+    _borrow: std::marker::PhantomData<&'a mut [capgpu_proof]>,
+}
+impl<'a> ProveTicket<'a> {
+    /// Blocks until the batch is proved; the proving call's error, if any, is the result.
+    pub fn wait(mut self) -> Result<()> {
+        self.wait_inner(u32::MAX).map(|_| ())
+    }
+    /// `Ok(true)`: done (the proofs are in the output slice once the ticket is dropped); `Ok(false)`: not yet.
+    pub fn wait_timeout(&mut self, timeout_ms: u32) -> Result<bool> {
+        self.wait_inner(timeout_ms)
+    }
+    fn wait_inner(&mut self, timeout_ms: u32) -> Result<bool> {
+        if self.done {
+            return Ok(true);
+        }
+        let mut done: c_int = 0;
+        let rc = unsafe { capgpu_wait(self.ticket, timeout_ms, &mut done) };
+        if rc != CAPGPU_OK || done != 0 {
+            self.done = true; // consumed (or unknown to the library: nothing is borrowed any more)
+        }
+        check(rc)?;
+        Ok(done != 0)
+    }
+}
+impl<'a> Drop for ProveTicket<'a> {
+    fn drop(&mut self) {
+        if !self.done {
+            let mut done: c_int = 0;
+            unsafe { capgpu_wait(self.ticket, u32::MAX, &mut done) };
+        }
     }
 }
 

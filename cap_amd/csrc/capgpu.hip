@@ -189,9 +189,28 @@ void context_trim_if_pending(Context& c) {
   (void)trim_context(c);
 }
 
+// capgpu_scratch_stats: growths of scratch buffers and of the pinned result area since capgpu_init, over all contexts.  One
+// event per reserve that actually allocates; bytes: the new capacity; time: the whole growth - the drain of the context's
+// streams and the free of the old buffer included.  The same moment goes to the phase trace ("scratch_grow").
+static std::atomic<uint64_t> g_grow_events{0}, g_grow_bytes{0}, g_grow_ns{0};
+namespace {
+struct GrowTimer {
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  void done(size_t new_cap) const {
+    const uint64_t ns =
+        (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+    g_grow_events++;
+    g_grow_bytes += new_cap;
+    g_grow_ns += ns;
+    trace("scratch_grow", (int64_t)new_cap, (int64_t)(ns / 1000));
+  }
+};
+}  // namespace
+
 int scratch_reserve(Scratch& s, size_t bytes) {
   if (bytes <= s.cap) return CAPGPU_OK;
   Context& c = ctx();
+  const GrowTimer grow;
   if (c.capturing) {  // (the capture is abandoned and the work enqueued directly: plonk.hip, GraphRun)
     set_error("capgpu: scratch growth during stream capture");
     return CAPGPU_ERR_HIP;
@@ -229,11 +248,13 @@ int scratch_reserve(Scratch& s, size_t bytes) {
   }
   s.cap = want;
   scratch_count(c.device, want, 0);
+  grow.done(want);
   return CAPGPU_OK;
 }
 
 int pinned_reserve(Context& c, size_t bytes) {
   if (bytes <= c.pin_cap) return CAPGPU_OK;
+  const GrowTimer grow;
   if (c.pin_host) {
     CAP_HIP(drain_context_streams(c));
     CAP_HIP(hipHostFree(c.pin_host));
@@ -243,6 +264,7 @@ int pinned_reserve(Context& c, size_t bytes) {
   const size_t want = std::max<size_t>(bytes + bytes / 4, (size_t)1 << 16);
   CAP_HIP(hipHostMalloc(&c.pin_host, want, hipHostMallocDefault));
   c.pin_cap = want;
+  grow.done(want);
   return CAPGPU_OK;
 }
 
@@ -1024,6 +1046,8 @@ int capgpu_init(const int* device_ids, int n_devices) {
 void capgpu_shutdown(void) {
   Runtime& R = rt();
   if (!R.initialised.load()) return;
+  // tickets first: running ones finish, queued ones are dropped, the workers are joined - while the contexts still exist
+  plonk_async_shutdown();
   (void)capgpu_comm_destroy();
   plonk_reset_staging();
   {
@@ -1083,6 +1107,9 @@ void capgpu_shutdown(void) {
   tl_ctx = nullptr;
   tl_bound = -1;
   R.ctxs.clear();
+  g_grow_events = 0;
+  g_grow_bytes = 0;
+  g_grow_ns = 0;
 }
 
 int capgpu_device_count(int* count_out) {
@@ -1166,6 +1193,13 @@ int capgpu_scratch_info(uint64_t* scratch_bytes_out, uint64_t* limit_out) {
   CAP_CHECK_INIT();
   if (scratch_bytes_out) *scratch_bytes_out = (uint64_t)g_scratch_bytes[(size_t)ctx().device & 63].load();
   if (limit_out) *limit_out = (uint64_t)g_scratch_limit.load();
+  return CAPGPU_OK;
+}
+int capgpu_scratch_stats(uint64_t* grow_events_out, uint64_t* grow_bytes_out, double* grow_ms_out) {
+  CAP_CHECK_INIT();
+  if (grow_events_out) *grow_events_out = g_grow_events.load();
+  if (grow_bytes_out) *grow_bytes_out = g_grow_bytes.load();
+  if (grow_ms_out) *grow_ms_out = (double)g_grow_ns.load() * 1e-6;
   return CAPGPU_OK;
 }
 int capgpu_trace_enable(int on) {

@@ -39,6 +39,7 @@
 #include "launch.hpp"
 #include "params.hpp"
 #include "plonk_kernels.hpp"
+#include "tickets.hpp"
 #include "transcript_dev.hpp"
 
 namespace cap {
@@ -296,12 +297,20 @@ void scan_exclusive(hipStream_t s, const fe* in, fe* out, size_t len, size_t str
   }
 }
 
+// Bytes of Context::ntt_scratch the transforms below ask for.  One expression each, shared with prove_needs
+// (capgpu_plonk_reserve sizes a context ahead from what prove_batch WOULD request).
+inline size_t ntt_scratch_inplace(size_t stride, size_t count) { return sizeof(fe) * stride * count; }
+inline size_t ntt_scratch_from(uint32_t log_n, size_t count) { return (sizeof(fe) << log_n) * count; }
+inline size_t ntt3_scratch(uint32_t log_mm, size_t count) { return (sizeof(fe) << log_mm) * 6 * count; }
+// ... of Context::stage_b for `cnt` host-resident witnesses on a domain of n points
+inline size_t wires_stage_bytes(size_t cnt, size_t n) { return sizeof(fe) * cnt * NW * n; }
+
 int run_ntt(hipStream_t s, uint32_t log_n, fe* data, size_t stride, uint32_t count, int dir, int coset) {
   Context& c = ctx();
   const NttDomain* dom = nullptr;
   int rc = get_domain(log_n, &dom);
   if (rc) return rc;
-  rc = scratch_reserve(c.ntt_scratch, sizeof(fe) * stride * count);
+  rc = scratch_reserve(c.ntt_scratch, ntt_scratch_inplace(stride, count));
   if (rc) return rc;
   rc = ntt_run(*dom, c.small, data, (fe*)c.ntt_scratch.p, stride, count, dir, coset, s);
   if (rc) return hip_fail((hipError_t)rc, "ntt_run");
@@ -316,7 +325,7 @@ int run_ntt_from(hipStream_t s, uint32_t log_n, const fe* src, size_t src_stride
   const NttDomain* dom = nullptr;
   int rc = get_domain(log_n, &dom);
   if (rc) return rc;
-  rc = scratch_reserve(c.ntt_scratch, (sizeof(fe) << log_n) * count);
+  rc = scratch_reserve(c.ntt_scratch, ntt_scratch_from(log_n, count));
   if (rc) return rc;
   NttIo io{};
   io.src = src;
@@ -345,7 +354,7 @@ int run_ntt3_fwd(hipStream_t s, uint32_t log_mm, fe* data, uint32_t count, const
   const NttDomain* dm = nullptr;
   int rc = quot_domains(log_mm, &d3, &dm);
   if (rc) return rc;
-  if ((rc = scratch_reserve(c.ntt_scratch, (sizeof(fe) << log_mm) * 6 * count))) return rc;
+  if ((rc = scratch_reserve(c.ntt_scratch, ntt3_scratch(log_mm, count)))) return rc;
   rc = ntt3_forward(*d3, *dm, c.small, data, io, count, (fe*)c.ntt_scratch.p, s);
   if (rc) return hip_fail((hipError_t)rc, "ntt3_forward");
   return CAPGPU_OK;
@@ -356,7 +365,7 @@ int run_ntt3_inv(hipStream_t s, uint32_t log_mm, fe* data, uint32_t count) {
   const NttDomain* dm = nullptr;
   int rc = quot_domains(log_mm, &d3, &dm);
   if (rc) return rc;
-  if ((rc = scratch_reserve(c.ntt_scratch, (sizeof(fe) << log_mm) * 6 * count))) return rc;
+  if ((rc = scratch_reserve(c.ntt_scratch, ntt3_scratch(log_mm, count)))) return rc;
   rc = ntt3_inverse(*d3, *dm, c.small, data, count, (fe*)c.ntt_scratch.p, s);
   if (rc) return hip_fail((hipError_t)rc, "ntt3_inverse");
   return CAPGPU_OK;
@@ -712,6 +721,15 @@ int check_batch(const ProvingKey& K, const std::vector<const ProvingKey*>* keys,
   return CAPGPU_OK;
 }
 
+// check_resident's layout of Context::stage_a; returns the bytes it takes (base == nullptr: sizes only)
+size_t check_carve(void* base, uint32_t P, size_t pub_stride, bool coeffs, size_t n, void** small, fe** pub, fe** vals) {
+  Carver k(base);
+  *small = k.take<char>(check_small_bytes(P));
+  *pub = k.take<fe>((size_t)P * (pub_stride ? pub_stride : 1));
+  *vals = coeffs ? k.take<fe>((size_t)P * NW * n) : nullptr;
+  return k.off + 256;
+}
+
 // The same for witnesses resident at d_wires in `form` with their public inputs still on the host (`pubs`: P rows of
 // pub_stride elements).  Scratch: Context::stage_a.  Coefficient-form input is transformed to values out of place, into
 // stage_a; d_wires is never written.
@@ -721,19 +739,11 @@ int check_resident(const ProvingKey& K, const std::vector<const ProvingKey*>* ke
   hipStream_t s = c.stream;
   const size_t n = K.n;
   const bool coeffs = form == CAPGPU_INPUT_COEFFS;
-  Carver cv(nullptr);
-  auto carve_all = [&](Carver& k, void** small, fe** pub, fe** v) {
-    *small = k.take<char>(check_small_bytes(P));
-    *pub = k.take<fe>((size_t)P * (pub_stride ? pub_stride : 1));
-    *v = coeffs ? k.take<fe>((size_t)P * NW * n) : nullptr;
-  };
   void* d_small = nullptr;
   fe *d_pub = nullptr, *d_vals = nullptr;
-  carve_all(cv, &d_small, &d_pub, &d_vals);
-  int rc = scratch_reserve(c.stage_a, cv.off + 256);
+  int rc = scratch_reserve(c.stage_a, check_carve(nullptr, P, pub_stride, coeffs, n, &d_small, &d_pub, &d_vals));
   if (rc) return rc;
-  Carver cr(c.stage_a.p);
-  carve_all(cr, &d_small, &d_pub, &d_vals);
+  (void)check_carve(c.stage_a.p, P, pub_stride, coeffs, n, &d_small, &d_pub, &d_vals);
   if (pub_stride) CAP_HIP(hipMemcpyAsync(d_pub, pubs, sizeof(fe) * P * pub_stride, hipMemcpyHostToDevice, s));
   if (coeffs) {
     if ((rc = run_ntt_from(s, K.log_n, d_wires, n, n, d_vals, n, P * NW, 0, 0))) return rc;
@@ -765,6 +775,16 @@ int precheck_verdict(const capgpu_witness_fault* faults, uint32_t P) {
             fault_text(first, faults[first]).c_str());
   return CAPGPU_ERR_PROOF;
 }
+
+// the pinned result area of a batch of P proofs: the proofs and degree flags (device transcript), or a round's
+// commitments, the grand-product totals, the evaluations and the flags (host transcript)
+size_t prove_pinned_bytes(uint32_t P, bool dev_tr) {
+  if (dev_tr) return (size_t)P * td::kPrBytes + sizeof(uint32_t) * P + 512;
+  return sizeof(g1_jac) * P * NW + sizeof(fe) * P * 11 + sizeof(uint32_t) * P + 1024;
+}
+// bytes per proof of the device transcript's prefix (init message || vk_bytes || public inputs), in steps of 256: the
+// stride is part of a captured graph's signature
+uint32_t transcript_stride(size_t longest) { return (uint32_t)((longest + 256) / 256 * 256); }
 
 // msgs / msg_lens (optional): one transcript init message per proof; otherwise ext_msg is shared by the batch.
 // keys (optional): the proving key of every proof - keys of ONE domain size under ONE SRS (the reference proves transfer,
@@ -877,7 +897,7 @@ int prove_batch(const ProvingKey& K, uint32_t P, const fe* d_wires, const uint64
       set_error("capgpu_plonk_prove: transcript init message of %zu bytes", longest);
       return CAPGPU_ERR_INVALID_ARG;
     }
-    tr_stride = (uint32_t)((longest + 256) / 256 * 256);  // (in steps: the stride is part of a captured graph's signature)
+    tr_stride = transcript_stride(longest);
   }
   // workspace
   const bool coeffs = form == CAPGPU_INPUT_COEFFS;
@@ -985,12 +1005,11 @@ int prove_batch(const ProvingKey& K, uint32_t P, const fe* d_wires, const uint64
   const size_t proofs_bytes = (size_t)P * td::kPrBytes;
   if (dev_tr) {
     // (reserved before the first launch: a growing area drains the context's streams)
-    if ((rc = pinned_reserve(c, proofs_bytes + sizeof(uint32_t) * P + 512))) return rc;
+    if ((rc = pinned_reserve(c, prove_pinned_bytes(P, true)))) return rc;
     h_proofs = (uint8_t*)c.pin_host;
     h_flags = (uint32_t*)(h_proofs + (proofs_bytes + 255) / 256 * 256);
   } else {
-    const size_t need = sizeof(g1_jac) * P * NW + sizeof(fe) * P * 11 + sizeof(uint32_t) * P + 1024;
-    if ((rc = pinned_reserve(c, need))) return rc;
+    if ((rc = pinned_reserve(c, prove_pinned_bytes(P, false)))) return rc;
     char* b = (char*)c.pin_host;
     hj = (g1_jac*)b;
     b += (sizeof(g1_jac) * P * NW + 255) / 256 * 256;
@@ -1122,7 +1141,7 @@ int prove_batch(const ProvingKey& K, uint32_t P, const fe* d_wires, const uint64
     int r;
     // every transform below shares c.ntt_scratch: those of the side stream run in its order, the one in front of the
     // fork before them.  The largest size is reserved now - a growth later would free a buffer still in use.
-    if ((r = scratch_reserve(c.ntt_scratch, (sizeof(fe) << K.log_m) * 6 * (size_t)P * NW))) return r;
+    if ((r = scratch_reserve(c.ntt_scratch, ntt3_scratch(K.log_m, (size_t)P * NW)))) return r;
     auto interpolate_and_blind = [&](hipStream_t st) -> int {
       int q = CAPGPU_OK;
       if (coeffs) pad_copy(st, w.wpoly, ps, 0, d_wires, n, 0, 1, P * NW, n, n);
@@ -1523,6 +1542,69 @@ int prove_batch(const ProvingKey& K, uint32_t P, const fe* d_wires, const uint64
   }
   side_drain.armed = false;  // (every join was waited for in stream order and the stream has drained)
   return take_launch_error();
+}
+
+// ---- capgpu_plonk_reserve: what prove_batch would ask of the context's scratch -----------------------------------
+// The largest request prove_batch makes of every buffer for a batch of P proofs under K, in the modes in force now, through
+// the SAME size functions its launches use (carve, msm_workspace_bytes, ntt*_scratch, check_carve, prove_pinned_bytes):
+// the list below follows the schedule above, lambda by lambda.  B / Lag: the commit keys the batch would commit with (Lag
+// null: from coefficients).  host_wires: the witnesses arrive in host memory (stage_b, round 1 in chunks).
+// The device transcript's prefix is sized for an EMPTY init message - the caller's is not known here; it takes
+// P * (length rounded up to 256) bytes of a workspace of megabytes per proof, well inside scratch_reserve's slack.
+struct ProveNeeds {
+  size_t prove_ws = 0, msm_ws = 0, ntt_scratch = 0, stage_a = 0, stage_b = 0, pinned = 0;
+};
+ProveNeeds prove_needs(const ProvingKey& K, const MsmBases& B, const MsmBases* Lag, uint32_t P, int form, bool host_wires) {
+  ProveNeeds nd;
+  const size_t n = K.n, ps = K.ps;
+  const bool coeffs = form == CAPGPU_INPUT_COEFFS;
+  const bool precheck = g_precheck.load(std::memory_order_relaxed) != 0;
+  const bool dev_tr = transcript_mode() == CAPGPU_TRANSCRIPT_DEVICE && !comm_shard_prover();
+  auto ntt = [&](size_t bytes) { nd.ntt_scratch = std::max(nd.ntt_scratch, bytes); };
+  auto msm = [&](const MsmBases& T, size_t len, uint32_t batch) {
+    nd.msm_ws = std::max(nd.msm_ws, msm_workspace_bytes(T, len, batch));
+  };
+  const MsmBases& W = Lag ? *Lag : B;  // rounds 1 and 2 commit on the Lagrange-form key when there is one
+  // staging of host witnesses; the witness check reads whole witnesses, so round 1 is then not chunked
+  if (host_wires) nd.stage_b = wires_stage_bytes(P, n);
+  if (precheck) {
+    void* a = nullptr;
+    fe *b = nullptr, *v = nullptr;
+    nd.stage_a = check_carve(nullptr, P, K.num_inputs, coeffs, n, &a, &b, &v);
+    if (coeffs) ntt(ntt_scratch_from(K.log_n, (size_t)P * NW));  // check_resident
+  }
+  const uint32_t tr_stride = dev_tr ? transcript_stride(K.vk_bytes.size() + 32 * K.num_inputs) : 0;
+  nd.prove_ws = carve(nullptr, K, P, K.num_inputs, coeffs, tr_stride).total;
+  nd.pinned = prove_pinned_bytes(P, dev_tr);
+  const uint32_t chunks = host_wires && !precheck ? h2d_chunks(P) : 1;
+  // round 1: r1_chunk_kernels + commit_wires per chunk (either placement of the short first chunk), or for the whole batch
+  if (chunks > 1) {
+    for (int short_first = 0; short_first < 2; short_first++)
+      for (uint32_t ck = 0; ck < chunks; ck++) {
+        const uint32_t cnt = h2d_chunk_start(P, chunks, ck + 1, short_first != 0) - h2d_chunk_start(P, chunks, ck, short_first != 0);
+        if (!cnt) continue;
+        ntt(ntt_scratch_from(K.log_n, (size_t)cnt * NW));
+        msm(W, n + 2, cnt * NW);
+      }
+  } else {
+    ntt(ntt_scratch_from(K.log_n, (size_t)P * NW));
+    msm(W, n + 2, P * NW);
+    if (P <= r1_overlap_max()) ntt(ntt3_scratch(K.log_m, (size_t)P * NW));  // r1_overlapped reserves the largest first
+  }
+  if (K.num_inputs) ntt(ntt_scratch_from(K.log_n, P));  // r1_tail_kernels: the public-input polynomial
+  // r3_wire_cosets, z_cosets
+  ntt(ntt3_scratch(K.log_m, (size_t)P * NW));
+  ntt(ntt3_scratch(K.log_m, P));
+  // round 2: finish_and_commit_z
+  ntt(ntt_scratch_inplace(ps, P));
+  msm(W, n + 3, P);
+  // round 3: r3_body
+  if (K.recompute) ntt(ntt3_scratch(K.log_m, 18));
+  ntt(ntt3_scratch(K.log_m, P));
+  msm(B, n + 2, P * NW);
+  // round 5: r5_body
+  msm(B, n + 2, P * 2);
+  return nd;
 }
 
 // ---- proving-key construction shared by preprocess and the blob loader -------------------------------------
@@ -2260,6 +2342,50 @@ static int deal(int count, const std::function<int(int first, int cnt)>& part) {
   return CAPGPU_OK;
 }
 
+// The key of a part on the current context.  `home` (tickets only): the reference the ticket took at submission - a key
+// freed since then (capgpu_plonk_free_key with the ticket outstanding) is proved from that reference instead of refused.
+static int part_key(uint64_t h, const std::shared_ptr<ProvingKey>* home, std::shared_ptr<ProvingKey>* out) {
+  const int rc = lookup_key(h, out);
+  if (rc != CAPGPU_ERR_BAD_HANDLE || !home || !*home) return rc;
+  if ((*home)->device == ctx().device) {
+    *out = *home;
+    return CAPGPU_OK;
+  }
+  return clone_key_to_current(**home, (*home)->device, out);
+}
+
+// Proofs [first, first + cnt) of a host-resident batch under one key, on the calling thread's context: the part
+// capgpu_plonk_prove_batch_ex deals to a context, and - whole - the body of a ticket.
+struct HostBatch {
+  uint64_t pk;
+  const uint64_t *wires, *pub_inputs;
+  size_t num_inputs;
+  const uint8_t* ext_msg;
+  size_t ext_msg_len;
+  const uint64_t* blinders;
+  int input_form;
+  capgpu_proof* proofs_out;
+  size_t n;
+  const std::shared_ptr<ProvingKey>* home;  // tickets: see part_key
+};
+static int host_batch_part(const HostBatch& b, int first, int cnt) {
+  Context& c = ctx();
+  Entry lk(c);
+  const size_t n = b.n;
+  std::shared_ptr<ProvingKey> K;
+  int rc = part_key(b.pk, b.home, &K);
+  if (rc) return rc;
+  rc = scratch_reserve(c.stage_b, wires_stage_bytes((size_t)cnt, n));
+  if (rc) return rc;
+  // the columns are copied inside round 1, chunk by chunk, behind the commitments of the chunk before
+  std::vector<const uint64_t*> rows(cnt);
+  for (int i = 0; i < cnt; i++) rows[i] = b.wires + (size_t)4 * (first + i) * NW * n;
+  return prove_batch(*K, (uint32_t)cnt, (const fe*)c.stage_b.p,
+                     b.pub_inputs ? b.pub_inputs + (size_t)4 * first * b.num_inputs : nullptr, b.num_inputs, b.ext_msg,
+                     b.ext_msg_len, b.blinders + (size_t)4 * 13 * first, b.proofs_out + first, nullptr, nullptr, nullptr,
+                     rows.data(), b.input_form);
+}
+
 int capgpu_plonk_prove_batch_ex(uint64_t pk_handle, int count, const uint64_t* wires, const uint64_t* pub_inputs,
                                 size_t num_inputs, const uint8_t* ext_msg, size_t ext_msg_len, const uint64_t* blinders,
                                 int input_form, capgpu_proof* proofs_out) {
@@ -2277,22 +2403,9 @@ int capgpu_plonk_prove_batch_ex(uint64_t pk_handle, int count, const uint64_t* w
     set_error("capgpu_plonk_prove: bad argument");
     return CAPGPU_ERR_INVALID_ARG;
   }
-  const size_t n = K0->n;
-  return deal(count, [&](int first, int cnt) -> int {
-    Context& c = ctx();
-    Entry lk(c);
-    std::shared_ptr<ProvingKey> K;
-    int rc = lookup_key(pk_handle, &K);
-    if (rc) return rc;
-    rc = scratch_reserve(c.stage_b, sizeof(fe) * (size_t)cnt * NW * n);
-    if (rc) return rc;
-    // the columns are copied inside round 1, chunk by chunk, behind the commitments of the chunk before
-    std::vector<const uint64_t*> rows(cnt);
-    for (int i = 0; i < cnt; i++) rows[i] = wires + (size_t)4 * (first + i) * NW * n;
-    return prove_batch(*K, (uint32_t)cnt, (const fe*)c.stage_b.p, pub_inputs ? pub_inputs + (size_t)4 * first * num_inputs : nullptr,
-                       num_inputs, ext_msg, ext_msg_len, blinders + (size_t)4 * 13 * first, proofs_out + first, nullptr,
-                       nullptr, nullptr, rows.data(), input_form);
-  });
+  const HostBatch b{pk_handle, wires, pub_inputs, num_inputs, ext_msg, ext_msg_len, blinders, input_form, proofs_out, K0->n,
+                    nullptr};
+  return deal(count, [&](int first, int cnt) -> int { return host_batch_part(b, first, cnt); });
 }
 int capgpu_plonk_prove_batch(uint64_t pk_handle, int count, const uint64_t* wires, const uint64_t* pub_inputs,
                              size_t num_inputs, const uint8_t* ext_msg, size_t ext_msg_len, const uint64_t* blinders,
@@ -2333,6 +2446,54 @@ int capgpu_plonk_prove_multi_dev(const uint64_t* pk_handles, int count, const vo
                                          blinders, CAPGPU_INPUT_EVALS, proofs_out);
 }
 
+// The same for a batch of several keys (capgpu_plonk_prove_multi_ex).
+struct HostMulti {
+  const uint64_t* pk_handles;
+  const uint64_t *wires, *pub_inputs;
+  size_t num_inputs;
+  const uint8_t* const* ext_msgs;
+  const size_t* ext_msg_lens;
+  const uint64_t* blinders;
+  int input_form;
+  capgpu_proof* proofs_out;
+  size_t n;
+  const std::shared_ptr<ProvingKey>* homes;  // tickets: [count], see part_key
+};
+static int host_multi_part(const HostMulti& b, int first, int cnt) {
+  Context& c = ctx();
+  Entry lk(c);
+  const size_t n = b.n, num_inputs = b.num_inputs;
+  std::vector<std::shared_ptr<ProvingKey>> hold(cnt);
+  std::vector<const ProvingKey*> keys(cnt);
+  int rc;
+  for (int i = 0; i < cnt; i++) {
+    if ((rc = part_key(b.pk_handles[first + i], b.homes ? b.homes + first + i : nullptr, &hold[i]))) return rc;
+    keys[i] = hold[i].get();
+  }
+  // a part's rows carry `num_inputs` = the largest count among the keys of the WHOLE call; prove_batch wants the
+  // largest among its own keys: re-pack when the part's maximum is smaller
+  size_t ni = 0;
+  for (int i = 0; i < cnt; i++) ni = std::max(ni, keys[i]->num_inputs);
+  std::vector<uint64_t> pubs;
+  const uint64_t* pp = b.pub_inputs ? b.pub_inputs + (size_t)4 * first * num_inputs : nullptr;
+  if (ni != num_inputs) {
+    if (ni > num_inputs) {
+      set_error("capgpu_plonk_prove_multi: rows of %zu public inputs given, the keys need %zu", num_inputs, ni);
+      return CAPGPU_ERR_INVALID_ARG;
+    }
+    pubs.assign((size_t)4 * ni * cnt + 4, 0);
+    for (int i = 0; i < cnt; i++)
+      if (ni) memcpy(&pubs[(size_t)4 * ni * i], pp + (size_t)4 * num_inputs * i, 32 * ni);
+    pp = pubs.data();
+  }
+  if ((rc = scratch_reserve(c.stage_b, wires_stage_bytes((size_t)cnt, n)))) return rc;
+  std::vector<const uint64_t*> rows(cnt);
+  for (int i = 0; i < cnt; i++) rows[i] = b.wires + (size_t)4 * (first + i) * NW * n;
+  return prove_batch(*keys[0], (uint32_t)cnt, (const fe*)c.stage_b.p, pp, ni, nullptr, 0,
+                     b.blinders + (size_t)4 * 13 * first, b.proofs_out + first, b.ext_msgs ? b.ext_msgs + first : nullptr,
+                     b.ext_msg_lens ? b.ext_msg_lens + first : nullptr, &keys, rows.data(), b.input_form);
+}
+
 int capgpu_plonk_prove_multi_ex(const uint64_t* pk_handles, int count, const uint64_t* wires,
                                 const uint64_t* pub_inputs, size_t num_inputs, const uint8_t* const* ext_msgs,
                                 const size_t* ext_msg_lens, const uint64_t* blinders, int input_form,
@@ -2351,46 +2512,348 @@ int capgpu_plonk_prove_multi_ex(const uint64_t* pk_handles, int count, const uin
     set_error("capgpu_plonk_prove_multi: bad argument");
     return CAPGPU_ERR_INVALID_ARG;
   }
-  const size_t n = K0->n;
-  return deal(count, [&](int first, int cnt) -> int {
-    Context& c = ctx();
-    Entry lk(c);
-    std::vector<std::shared_ptr<ProvingKey>> hold(cnt);
-    std::vector<const ProvingKey*> keys(cnt);
-    int rc;
-    for (int i = 0; i < cnt; i++) {
-      if ((rc = lookup_key(pk_handles[first + i], &hold[i]))) return rc;
-      keys[i] = hold[i].get();
-    }
-    // a part's rows carry `num_inputs` = the largest count among the keys of the WHOLE call; prove_batch wants the
-    // largest among its own keys: re-pack when the part's maximum is smaller
-    size_t ni = 0;
-    for (int i = 0; i < cnt; i++) ni = std::max(ni, keys[i]->num_inputs);
-    std::vector<uint64_t> pubs;
-    const uint64_t* pp = pub_inputs ? pub_inputs + (size_t)4 * first * num_inputs : nullptr;
-    if (ni != num_inputs) {
-      if (ni > num_inputs) {
-        set_error("capgpu_plonk_prove_multi: rows of %zu public inputs given, the keys need %zu", num_inputs, ni);
-        return CAPGPU_ERR_INVALID_ARG;
-      }
-      pubs.assign((size_t)4 * ni * cnt + 4, 0);
-      for (int i = 0; i < cnt; i++)
-        if (ni) memcpy(&pubs[(size_t)4 * ni * i], pp + (size_t)4 * num_inputs * i, 32 * ni);
-      pp = pubs.data();
-    }
-    if ((rc = scratch_reserve(c.stage_b, sizeof(fe) * (size_t)cnt * NW * n))) return rc;
-    std::vector<const uint64_t*> rows(cnt);
-    for (int i = 0; i < cnt; i++) rows[i] = wires + (size_t)4 * (first + i) * NW * n;
-    return prove_batch(*keys[0], (uint32_t)cnt, (const fe*)c.stage_b.p, pp, ni, nullptr, 0,
-                       blinders + (size_t)4 * 13 * first, proofs_out + first, ext_msgs ? ext_msgs + first : nullptr,
-                       ext_msg_lens ? ext_msg_lens + first : nullptr, &keys, rows.data(), input_form);
-  });
+  const HostMulti b{pk_handles, wires, pub_inputs, num_inputs, ext_msgs, ext_msg_lens, blinders, input_form, proofs_out, K0->n,
+                    nullptr};
+  return deal(count, [&](int first, int cnt) -> int { return host_multi_part(b, first, cnt); });
 }
 int capgpu_plonk_prove_multi(const uint64_t* pk_handles, int count, const uint64_t* wires, const uint64_t* pub_inputs,
                              size_t num_inputs, const uint8_t* const* ext_msgs, const size_t* ext_msg_lens,
                              const uint64_t* blinders, capgpu_proof* proofs_out) {
   return capgpu_plonk_prove_multi_ex(pk_handles, count, wires, pub_inputs, num_inputs, ext_msgs, ext_msg_lens, blinders,
                                      CAPGPU_INPUT_EVALS, proofs_out);
+}
+
+}  // extern "C"
+
+// ---- asynchronous prove tickets ------------------------------------------------------------------------------------------
+// capgpu_plonk_prove_batch_async / _multi_async check their arguments, copy what is small (messages, handles), take a
+// reference to the key(s) and queue a ticket (tickets.hpp); a worker thread of the library then proves the whole batch on
+// ONE context - the body is the part function of the synchronous call with first = 0, cnt = count, not deal(): two tickets
+// in flight are two bound callers (0.995 of the resident rate, profiles/phase_trace_r06.md), four quarter-parts are slower
+// (deal_max_parts above).  Coalescing is not involved.
+namespace cap {
+namespace {
+struct AsyncJob {
+  bool multi = false;
+  int count = 0;
+  std::vector<uint64_t> pks;                        // one, or one per proof (_multi)
+  std::vector<std::shared_ptr<ProvingKey>> homes;   // shared ownership, as home_key gives it: [pks.size()]
+  const uint64_t *wires = nullptr, *pub_inputs = nullptr, *blinders = nullptr;  // borrowed until the ticket is done
+  capgpu_proof* proofs_out = nullptr;               // borrowed likewise
+  size_t num_inputs = 0, n = 0;
+  int input_form = CAPGPU_INPUT_EVALS;
+  bool has_msgs = false;                            // _multi with ext_msgs != NULL
+  std::vector<std::vector<uint8_t>> msgs;           // copies: one (batch; empty = none) or one per proof
+  int bound_slot = -1;                              // the submitting thread's capgpu_set_device, -1: none
+};
+using Tickets = TicketTable<AsyncJob>;
+
+uint32_t async_inflight() {  // tickets of one physical device running at once (CAPGPU_ASYNC_INFLIGHT, default 2)
+  static const uint32_t v = [] {
+    const char* e = getenv("CAPGPU_ASYNC_INFLIGHT");
+    const int x = e ? atoi(e) : 2;
+    return (uint32_t)(x >= 1 && x <= 16 ? x : 2);
+  }();
+  return v;
+}
+// HIP devices behind the contexts, in slot order: a ticket's lane is the index of its device
+std::vector<int> async_devices() {
+  std::vector<int> seen;
+  for (auto& c : rt().ctxs)
+    if (std::find(seen.begin(), seen.end(), c->device) == seen.end()) seen.push_back(c->device);
+  return seen;
+}
+// a context of `device` nobody is using right now (returned LOCKED), else nullptr
+Context* try_acquire_context_on(int device) {
+  Runtime& R = rt();
+  const size_t n = R.ctxs.size();
+  const uint32_t start = R.rr.load(std::memory_order_relaxed);
+  for (size_t i = 0; i < n; i++) {
+    Context* c = R.ctxs[(start + i) % n].get();
+    if (c->device != device) continue;
+    if (c->mu.try_lock()) {
+      R.rr.store((uint32_t)((start + i + 1) % n), std::memory_order_relaxed);
+      return c;
+    }
+  }
+  return nullptr;
+}
+
+int run_ticket(AsyncJob& j, int lane, std::string* err) {
+  Runtime& R = rt();
+  const std::vector<int> devs = async_devices();
+  if (!R.initialised.load(std::memory_order_acquire) || (size_t)lane >= devs.size()) {
+    *err = "capgpu: not initialised (call capgpu_init first)";
+    return CAPGPU_ERR_NOT_INITIALISED;
+  }
+  // the context: the submitter's bound slot, else a free one of the lane's device, else that device's round-robin pick
+  Context* c = nullptr;
+  bool locked = false;
+  if (j.bound_slot >= 0 && (size_t)j.bound_slot < R.ctxs.size()) {
+    c = R.ctxs[(size_t)j.bound_slot].get();
+  } else if (devs.size() == 1 && (c = try_acquire_context()) != nullptr) {
+    locked = true;
+  } else if (devs.size() > 1 && (c = try_acquire_context_on(devs[(size_t)lane])) != nullptr) {
+    locked = true;
+  } else {
+    std::vector<Context*> mine;
+    for (auto& cp : R.ctxs)
+      if (cp->device == devs[(size_t)lane]) mine.push_back(cp.get());
+    c = mine[R.rr.fetch_add(1, std::memory_order_relaxed) % mine.size()];
+  }
+  trace("tk_run", c->slot, j.count);
+  int rc;
+  {
+    ScopedCtx sc(*c);
+    if (j.multi) {
+      std::vector<const uint8_t*> mp(j.msgs.size());
+      std::vector<size_t> ml(j.msgs.size());
+      for (size_t i = 0; i < j.msgs.size(); i++) {
+        mp[i] = j.msgs[i].empty() ? nullptr : j.msgs[i].data();
+        ml[i] = j.msgs[i].size();
+      }
+      const HostMulti b{j.pks.data(), j.wires, j.pub_inputs, j.num_inputs, j.has_msgs ? mp.data() : nullptr,
+                        j.has_msgs ? ml.data() : nullptr, j.blinders, j.input_form, j.proofs_out, j.n, j.homes.data()};
+      rc = host_multi_part(b, 0, j.count);
+    } else {
+      const std::vector<uint8_t>& m = j.msgs[0];
+      const HostBatch b{j.pks[0], j.wires, j.pub_inputs, j.num_inputs, m.empty() ? nullptr : m.data(), m.size(),
+                        j.blinders, j.input_form, j.proofs_out, j.n, &j.homes[0]};
+      rc = host_batch_part(b, 0, j.count);
+    }
+    if (rc) *err = last_error();
+  }
+  if (locked) c->mu.unlock();
+  return rc;
+}
+
+Tickets& tickets() {
+  // (never destroyed: a process may exit without capgpu_shutdown while a worker sleeps on the table's condition variable)
+  static Tickets* t = [] {
+    Tickets* x = new Tickets;
+    x->run = run_ticket;
+    return x;
+  }();
+  return *t;
+}
+std::atomic<uint32_t> g_async_rr{0};  // lane of the next unbound ticket when several devices are bound
+
+int submit_ticket(AsyncJob&& j, uint64_t* ticket_out) {
+  const std::vector<int> devs = async_devices();
+  int lane = 0;
+  if (j.bound_slot >= 0) {
+    const int d = rt().ctxs[(size_t)j.bound_slot]->device;
+    lane = (int)(std::find(devs.begin(), devs.end(), d) - devs.begin());
+  } else if (devs.size() > 1) {
+    lane = (int)(g_async_rr.fetch_add(1, std::memory_order_relaxed) % devs.size());
+  }
+  Tickets& T = tickets();
+  {
+    std::lock_guard<std::mutex> lk(T.mu);
+    T.limit = async_inflight();
+  }
+  switch (T.submit(std::move(j), lane, ticket_out)) {
+    case Tickets::kOk:
+      return CAPGPU_OK;
+    case Tickets::kBusy:
+      set_error("capgpu: %zu tickets outstanding; wait for one", Tickets::kMaxOutstanding);
+      return CAPGPU_ERR_BUSY;
+    default:
+      set_error("capgpu: not initialised (call capgpu_init first)");
+      return CAPGPU_ERR_NOT_INITIALISED;
+  }
+}
+// the ranks of a communicator must prove in lock step (capgpu_plonk_shard_msm): no tickets then
+bool async_refused_by_sharding() {
+  if (comm_shard_slot() < 0 && !comm_shard_prover()) return false;
+  set_error("capgpu_plonk_prove_async: not available while capgpu_plonk_shard_msm is on (the ranks prove in lock step)");
+  return true;
+}
+}  // namespace
+
+void plonk_async_shutdown() {
+  Tickets& T = tickets();
+  T.drain(CAPGPU_ERR_NOT_INITIALISED, "capgpu: shut down before this ticket ran");
+  T.reset_stats();
+}
+}  // namespace cap
+
+extern "C" {
+
+int capgpu_plonk_prove_batch_async(uint64_t pk_handle, int count, const uint64_t* wires, const uint64_t* pub_inputs,
+                                   size_t num_inputs, const uint8_t* ext_msg, size_t ext_msg_len, const uint64_t* blinders,
+                                   int input_form, capgpu_proof* proofs_out, uint64_t* ticket_out) {
+  CAP_CHECK_INIT();
+  // the checks of capgpu_plonk_prove_batch_ex, in its order, with its codes and messages
+  if (bad_form(input_form)) return CAPGPU_ERR_INVALID_ARG;
+  if (count < 0 || (count && !wires) || !ticket_out) {
+    set_error("capgpu_plonk_prove: bad argument");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  *ticket_out = 0;
+  if (count == 0) return CAPGPU_OK;
+  AsyncJob j;
+  j.homes.resize(1);
+  int rc = home_key(pk_handle, &j.homes[0]);
+  if (rc) return rc;
+  if (!blinders || !proofs_out || (num_inputs && !pub_inputs)) {
+    set_error("capgpu_plonk_prove: bad argument");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  if (num_inputs != j.homes[0]->num_inputs) {  // (prove_batch's own check, made before anything is queued)
+    set_error("capgpu_plonk_prove: %zu public inputs given, key expects %zu", num_inputs, j.homes[0]->num_inputs);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  if (async_refused_by_sharding()) return CAPGPU_ERR_INVALID_ARG;
+  j.count = count;
+  j.pks.assign(1, pk_handle);
+  j.wires = wires;
+  j.pub_inputs = pub_inputs;
+  j.blinders = blinders;
+  j.proofs_out = proofs_out;
+  j.num_inputs = num_inputs;
+  j.n = j.homes[0]->n;
+  j.input_form = input_form;
+  j.msgs.resize(1);
+  if (ext_msg && ext_msg_len) j.msgs[0].assign(ext_msg, ext_msg + ext_msg_len);
+  j.bound_slot = thread_bound_slot();
+  return submit_ticket(std::move(j), ticket_out);
+}
+
+int capgpu_plonk_prove_multi_async(const uint64_t* pk_handles, int count, const uint64_t* wires,
+                                   const uint64_t* pub_inputs, size_t num_inputs, const uint8_t* const* ext_msgs,
+                                   const size_t* ext_msg_lens, const uint64_t* blinders, int input_form,
+                                   capgpu_proof* proofs_out, uint64_t* ticket_out) {
+  CAP_CHECK_INIT();
+  if (bad_form(input_form)) return CAPGPU_ERR_INVALID_ARG;
+  if (count < 0 || (count && (!wires || !pk_handles)) || !ticket_out) {
+    set_error("capgpu_plonk_prove_multi: bad argument");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  *ticket_out = 0;
+  if (count == 0) return CAPGPU_OK;
+  AsyncJob j;
+  j.homes.resize((size_t)count);
+  int rc = home_key(pk_handles[0], &j.homes[0]);
+  if (rc) return rc;
+  if (!blinders || !proofs_out || (num_inputs && !pub_inputs) || (ext_msgs && !ext_msg_lens)) {
+    set_error("capgpu_plonk_prove_multi: bad argument");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  // every key is known, and they share the domain size and the SRS: what the synchronous call finds out on the device
+  size_t max_ni = 0;
+  for (int i = 0; i < count; i++) {
+    if (i && (rc = home_key(pk_handles[i], &j.homes[(size_t)i]))) return rc;
+    const ProvingKey &K = *j.homes[0], &Kp = *j.homes[(size_t)i];
+    if (Kp.n != K.n || Kp.srs_handle != K.srs_handle || Kp.recompute || K.recompute) {
+      set_error("capgpu_plonk_prove_multi: the keys of one batch must share the domain size and the SRS");
+      return CAPGPU_ERR_INVALID_ARG;
+    }
+    max_ni = std::max(max_ni, Kp.num_inputs);
+  }
+  if (num_inputs != max_ni) {
+    set_error("capgpu_plonk_prove_multi: rows of %zu public inputs given, the keys need %zu", num_inputs, max_ni);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  if (async_refused_by_sharding()) return CAPGPU_ERR_INVALID_ARG;
+  j.multi = true;
+  j.count = count;
+  j.pks.assign(pk_handles, pk_handles + count);
+  j.wires = wires;
+  j.pub_inputs = pub_inputs;
+  j.blinders = blinders;
+  j.proofs_out = proofs_out;
+  j.num_inputs = num_inputs;
+  j.n = j.homes[0]->n;
+  j.input_form = input_form;
+  j.has_msgs = ext_msgs != nullptr;
+  if (ext_msgs) {
+    j.msgs.resize((size_t)count);
+    for (int i = 0; i < count; i++)
+      if (ext_msgs[i] && ext_msg_lens[i]) j.msgs[(size_t)i].assign(ext_msgs[i], ext_msgs[i] + ext_msg_lens[i]);
+  }
+  j.bound_slot = thread_bound_slot();
+  return submit_ticket(std::move(j), ticket_out);
+}
+
+int capgpu_wait(uint64_t ticket, uint32_t timeout_ms, int* done_out) {
+  CAP_CHECK_INIT();
+  if (!done_out) {
+    set_error("capgpu_wait: bad argument");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  *done_out = 0;
+  if (ticket == 0) {  // the ticket of an empty batch
+    *done_out = 1;
+    return CAPGPU_OK;
+  }
+  int rc = CAPGPU_OK;
+  std::string err;
+  if (tickets().wait(ticket, timeout_ms, done_out, &rc, &err) == Tickets::kUnknown) {
+    *done_out = 0;
+    set_error("capgpu_wait: unknown ticket %llu (never issued, or its result was already taken)", (unsigned long long)ticket);
+    return CAPGPU_ERR_BAD_HANDLE;
+  }
+  if (!*done_out) return CAPGPU_OK;
+  if (rc) set_error("%s", err.c_str());
+  return rc;
+}
+
+int capgpu_async_stats(uint64_t* submitted_out, uint64_t* completed_out, uint32_t* max_running_out) {
+  CAP_CHECK_INIT();
+  tickets().stats(submitted_out, completed_out, max_running_out);
+  return CAPGPU_OK;
+}
+
+// Sizes, without proving anything, what a `count`-proof host-resident batch under this key would grow on context `slot`
+// (-1: every context) - see prove_needs - and brings the key, the SRS and the Lagrange-form commit key there.
+int capgpu_plonk_reserve(uint64_t pk_handle, int count, int input_form, int slot) {
+  CAP_CHECK_INIT();
+  if (bad_form(input_form)) return CAPGPU_ERR_INVALID_ARG;
+  if (count < 0 || slot < -1 || slot >= (int)num_contexts()) {
+    set_error("capgpu_plonk_reserve: bad argument (count >= 0, slot -1 .. %zu)", num_contexts() - 1);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  std::shared_ptr<ProvingKey> K0;
+  int rc = home_key(pk_handle, &K0);
+  if (rc) return rc;
+  if (count == 0) return CAPGPU_OK;
+  struct ScaleOne {  // exact sizes: a growth scale the thread carries (gathered batches) does not apply
+    double saved = scratch_growth_scale();
+    ScaleOne() { scratch_growth_scale() = 1.0; }
+    ~ScaleOne() { scratch_growth_scale() = saved; }
+  } scale_one;
+  for (int sl = slot < 0 ? 0 : slot, end = slot < 0 ? (int)num_contexts() : slot + 1; sl < end; sl++) {
+    Context& c = *rt().ctxs[(size_t)sl];
+    ScopedCtx sc(c);
+    Entry lk(c);
+    std::shared_ptr<ProvingKey> K;
+    if ((rc = lookup_key(pk_handle, &K))) return rc;
+    const MsmBases* B = nullptr;
+    if ((rc = find_srs(K->srs_handle, &B))) return rc;
+    const MsmBases* Lag = nullptr;
+    if (wire_commit_from_evals() && !comm_shard_prover() && (rc = find_lagrange(K->srs_handle, K->log_n, &Lag))) {
+      if (rc == CAPGPU_ERR_BAD_HANDLE) return rc;
+      Lag = nullptr;  // (the proof would commit from coefficients instead: prove_batch)
+      (void)hipGetLastError();
+    }
+    // the domain tables and the streams a first proof would create
+    const NttDomain* dn = nullptr;
+    const Ntt3Domain* d3 = nullptr;
+    if ((rc = get_domain(K->log_n, &dn)) || (rc = quot_domains(K->log_m, &d3, &dn))) return rc;
+    (void)h2d_stream();
+    (void)side_stream(c);
+    const ProveNeeds nd = prove_needs(*K, *B, Lag, (uint32_t)count, input_form, true);
+    if ((rc = scratch_reserve(c.stage_b, nd.stage_b))) return rc;
+    if ((rc = scratch_reserve(c.stage_a, nd.stage_a))) return rc;
+    if ((rc = scratch_reserve(c.prove_ws, nd.prove_ws))) return rc;
+    if ((rc = scratch_reserve(c.msm_ws, nd.msm_ws))) return rc;
+    if ((rc = scratch_reserve(c.ntt_scratch, nd.ntt_scratch))) return rc;
+    if ((rc = pinned_reserve(c, nd.pinned))) return rc;
+    CAP_HIP(hipStreamSynchronize(c.stream));
+    trace("reserve", c.slot, count);
+  }
+  return CAPGPU_OK;
 }
 
 // one gathered batch: device staging of every request's wires, per-proof messages and keys; a batch that fails because
@@ -2730,7 +3193,7 @@ static int check_part(const uint64_t* pk_handles, uint64_t pk_handle, uint32_t c
   }
   const size_t n = keys[0]->n;
   if (h_wires) {
-    if ((rc = scratch_reserve(c.stage_b, sizeof(fe) * (size_t)cnt * NW * n))) return rc;
+    if ((rc = scratch_reserve(c.stage_b, wires_stage_bytes((size_t)cnt, n)))) return rc;
     CAP_HIP(hipMemcpyAsync(c.stage_b.p, h_wires, sizeof(fe) * (size_t)cnt * NW * n, hipMemcpyHostToDevice, c.stream));
     d_wires = c.stage_b.p;
   }

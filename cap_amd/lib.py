@@ -811,6 +811,122 @@ def plonk_prove_multi(pk_handles, wires, pub_rows: np.ndarray, blinders: np.ndar
     return list(proofs)
 
 
+# ---- asynchronous proving: tickets (capgpu_plonk_prove_batch_async / capgpu_wait) ---------------------------------------
+ERR_BUSY = -10  # CAPGPU_ERR_BUSY of include/capgpu.h
+
+
+class Ticket:
+    """A batch being proved by a worker thread of the library.  The object keeps the numpy inputs and the output array
+    alive - the library borrows them until the ticket is done - and hands the proofs out through wait()."""
+
+    def __init__(self, ticket: int, proofs, keep):
+        self.ticket = ticket
+        self._proofs = proofs
+        self._keep = keep  # the arrays the library reads: referenced until the result has been taken
+        self._result = None
+        self._consumed = False
+
+    def wait(self, timeout_ms: int | None = None):
+        """-> the list of proofs, or None when the batch is not done within timeout_ms (None: no limit; 0: poll).  Raises
+        CapGpuError with the proving call's code and message; a second wait after the result was taken raises
+        CapGpuError(-4) (CAPGPU_ERR_BAD_HANDLE), as the C ABI does."""
+        done = ctypes.c_int(0)
+        t = 0xFFFFFFFF if timeout_ms is None else int(timeout_ms)
+        rc = load().capgpu_wait(ctypes.c_uint64(self.ticket), ctypes.c_uint32(t), ctypes.byref(done))
+        if rc == 0 and not done.value:
+            return None
+        if (rc != 0 and rc != -4) or done.value:  # the ticket is consumed: nothing is borrowed any more
+            self._consumed = True
+            self._keep = None
+        check(rc)
+        return list(self._proofs)
+
+    def __del__(self):
+        # a ticket dropped without wait(): the library still reads the inputs and writes the proofs - wait for it
+        try:
+            if not self._consumed and self._keep is not None:
+                done = ctypes.c_int(0)
+                load().capgpu_wait(ctypes.c_uint64(self.ticket), ctypes.c_uint32(0xFFFFFFFF), ctypes.byref(done))
+        except Exception:
+            pass
+
+
+def plonk_prove_batch_async(pk_handle: int, wires: np.ndarray, pub_inputs: np.ndarray, blinders: np.ndarray,
+                            ext_msg: bytes | None = None, count: int = 1, input_form=INPUT_EVALS) -> Ticket:
+    """plonk_prove_batch without the wait: returns a Ticket at once; Ticket.wait() gives the proofs.  Keep two in flight
+    from one thread to overlap one batch's copies and host steps with the other's kernels."""
+    wires = np.ascontiguousarray(wires, dtype=np.uint64)
+    pub_inputs = np.ascontiguousarray(pub_inputs, dtype=np.uint64).reshape(-1)
+    blinders = np.ascontiguousarray(blinders, dtype=np.uint64).reshape(-1)
+    num_inputs = _check_prove_shapes(pk_handle, count, wires.size // 4 if wires.size % 4 == 0 else -1, pub_inputs,
+                                     blinders)
+    proofs = (Proof * count)()
+    mbuf, mlen = _bytes_arg(ext_msg)
+    pub_ptr = _p(pub_inputs) if pub_inputs.size else None
+    flat = wires.reshape(-1)
+    t = ctypes.c_uint64(0)
+    check(load().capgpu_plonk_prove_batch_async(ctypes.c_uint64(pk_handle), count, _p(flat), pub_ptr,
+                                                ctypes.c_size_t(num_inputs), mbuf, ctypes.c_size_t(mlen), _p(blinders),
+                                                ctypes.c_int(_form(input_form)), proofs, ctypes.byref(t)))
+    return Ticket(t.value, proofs, (wires, flat, pub_inputs, blinders))
+
+
+def plonk_prove_multi_async(pk_handles, wires: np.ndarray, pub_rows: np.ndarray, blinders: np.ndarray, ext_msgs=None,
+                            input_form=INPUT_EVALS) -> Ticket:
+    """plonk_prove_multi (host-resident wires) without the wait: a Ticket."""
+    count = len(pk_handles)
+    shapes = [plonk_key_info(h) for h in pk_handles]
+    n = shapes[0][0]
+    max_in = max(sh[1] for sh in shapes)
+    pub_rows = np.ascontiguousarray(pub_rows, dtype=np.uint64).reshape(-1)
+    blinders = np.ascontiguousarray(blinders, dtype=np.uint64).reshape(-1)
+    wires = np.ascontiguousarray(wires, dtype=np.uint64).reshape(-1)
+    if pub_rows.size != count * max_in * 4 or blinders.size != count * 13 * 4:
+        raise ValueError(f"plonk_prove_multi_async: pub_rows must hold {count} x {max_in} and blinders {count} x 13 elements")
+    if wires.size != count * NUM_WIRE_TYPES * n * 4:
+        raise ValueError("plonk_prove_multi_async: wires must hold count x 5 x n elements")
+    handles = (ctypes.c_uint64 * count)(*pk_handles)
+    msgs_arg = lens_arg = None
+    keep = []
+    if ext_msgs is not None:
+        if len(ext_msgs) != count:
+            raise ValueError("plonk_prove_multi_async: one message per proof")
+        msgs_arg = (ctypes.c_char_p * count)()
+        lens_arg = (ctypes.c_size_t * count)()
+        for i, m in enumerate(ext_msgs):
+            keep.append(bytes(m) if m else b"")
+            msgs_arg[i] = keep[-1] if keep[-1] else None
+            lens_arg[i] = len(keep[-1])
+    proofs = (Proof * count)()
+    pub_ptr = _p(pub_rows) if pub_rows.size else None
+    t = ctypes.c_uint64(0)
+    check(load().capgpu_plonk_prove_multi_async(handles, count, _p(wires), pub_ptr, ctypes.c_size_t(max_in), msgs_arg,
+                                                lens_arg, _p(blinders), ctypes.c_int(_form(input_form)), proofs,
+                                                ctypes.byref(t)))
+    return Ticket(t.value, proofs, (wires, pub_rows, blinders))
+
+
+def async_stats() -> dict:
+    """tickets accepted / finished since init and the most that ran at once on one device"""
+    a, b, m = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(0)
+    check(load().capgpu_async_stats(ctypes.byref(a), ctypes.byref(b), ctypes.byref(m)))
+    return {"submitted": a.value, "completed": b.value, "max_running": m.value}
+
+
+def plonk_reserve(pk_handle: int, count: int, input_form=INPUT_EVALS, slot: int = -1):
+    """capgpu_plonk_reserve: size context `slot` (-1: all) ahead for a `count`-proof host-resident batch under this key,
+    in the modes in force now, without proving anything."""
+    check(load().capgpu_plonk_reserve(ctypes.c_uint64(pk_handle), ctypes.c_int(count), ctypes.c_int(_form(input_form)),
+                                      ctypes.c_int(slot)))
+
+
+def scratch_stats() -> dict:
+    """growths of scratch buffers / pinned areas since init: events, bytes of new capacity, milliseconds spent"""
+    e, b, ms = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_double(0.0)
+    check(load().capgpu_scratch_stats(ctypes.byref(e), ctypes.byref(b), ctypes.byref(ms)))
+    return {"grow_events": e.value, "grow_bytes": b.value, "grow_ms": ms.value}
+
+
 def proof_to_arrays(pr: Proof) -> dict:
     """ctypes Proof -> dict of numpy arrays (Montgomery words)."""
     def a(x):

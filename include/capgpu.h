@@ -67,6 +67,7 @@ extern "C" {
 #define CAPGPU_ERR_SERIALIZATION (-8) /* malformed parameter blob: ark_serialize::SerializationError, which the
                                          reference maps to TxnApiError::DeserializationError (src/errors.rs:81-85) */
 #define CAPGPU_ERR_COMM (-9) /* multi-process exchange: a peer rank failed its part, or did not arrive in time */
+#define CAPGPU_ERR_BUSY (-10) /* capgpu_plonk_prove_*_async: 64 tickets outstanding; wait for one and submit again */
 
 #define CAPGPU_NUM_WIRE_TYPES 5
 #define CAPGPU_NUM_SELECTORS 13
@@ -147,6 +148,14 @@ int capgpu_mem_info(uint64_t* free_bytes_out, uint64_t* total_bytes_out);
 int capgpu_trim(uint64_t* bytes_released_out, int* contexts_busy_out);
 int capgpu_set_memory_limit(uint64_t scratch_bytes_per_device);
 int capgpu_scratch_info(uint64_t* scratch_bytes_out, uint64_t* limit_out);
+/* The allocator's counters, since capgpu_init and summed over all contexts: how often a scratch buffer or a context's
+ * pinned result area GREW (one event per growth that actually allocated), the new capacities in bytes, and the wall time
+ * those growths took in milliseconds - the drain of the context's streams and the release of the old buffer included.  A
+ * benchmark reads them around its timed part: a non-zero difference says that an allocation (0.1 - 0.6 s for the
+ * gigabytes of a large batch) landed inside it.  capgpu_plonk_reserve sizes a context ahead so that the difference is
+ * zero.  With the phase trace on, every growth is also an event "scratch_grow" (a = bytes, b = microseconds).  Any pointer
+ * may be NULL. */
+int capgpu_scratch_stats(uint64_t* grow_events_out, uint64_t* grow_bytes_out, double* grow_ms_out);
 /* Host-side phase trace (diagnostics; no reference counterpart): while on, the library timestamps the phases the kernel
  * profiler cannot see - a coalesced call's queueing, window and context wait, the host-to-device copies of a batch's
  * witnesses, the host steps between the prover's rounds, the release of the callers - into a ring of 2^20 events.
@@ -473,6 +482,65 @@ int capgpu_plonk_prove_multi_dev_ex(const uint64_t* pk_handles, int count, const
 int capgpu_plonk_prove_batch_dev_ex(uint64_t pk_handle, int count, const void* d_wires, const uint64_t* pub_inputs,
                                     size_t num_inputs, const uint8_t* ext_msg, size_t ext_msg_len,
                                     const uint64_t* blinders, int input_form, capgpu_proof* proofs_out);
+
+/* ---- asynchronous proving: tickets ---------------------------------------------------------------------------------
+ * Every prove entry point above returns when its proofs are made, so a caller with its witnesses in host memory pays the
+ * fill and the drain of the device once per call: one thread proving 256 host witnesses per call reaches 0.95 - 0.97 of
+ * the resident rate, two threads bound to two contexts (capgpu_set_device), each proving half, 0.995.  A TICKET is such a
+ * bound caller inside the library: submission checks the arguments and returns at once; a worker thread of the library
+ * takes a context - the submitting thread's bound one, else a free one, else the round-robin pick - and proves the WHOLE
+ * batch there (it is not cut over contexts, and coalescing is not involved); capgpu_wait collects the result.  One thread
+ * that keeps two tickets in flight - submit A, submit B, wait A, submit C, wait B, ... - is the two-callers pattern without
+ * threads of the caller's own.
+ *
+ * Submission.  Arguments as capgpu_plonk_prove_batch_ex / _multi_ex.  Every check those calls make before they touch the
+ * device is made now, with the same code and message (input form, null pointers, unknown key, the public-input count, keys
+ * of different domain sizes or SRS in _multi); a failed check creates no ticket.  count == 0: CAPGPU_OK and ticket 0,
+ * which capgpu_wait reports as done.  The transcript messages and the pk_handles array are COPIED.  `wires`,
+ * `pub_inputs`, `blinders` and `proofs_out` are BORROWED: the caller keeps them alive and neither writes the inputs nor
+ * touches proofs_out until capgpu_wait has reported the ticket done.  The ticket shares ownership of its key(s):
+ * capgpu_plonk_free_key with a ticket outstanding is safe, and the ticket is still proved.
+ * Tickets of a device start in submission order, at most CAPGPU_ASYNC_INFLIGHT (environment, default 2) of them run at
+ * once per physical device, later ones queue.  With 64 tickets outstanding - queued, running, or done and not yet waited
+ * for - a submission returns CAPGPU_ERR_BUSY instead of blocking.  The process-wide modes (capgpu_plonk_set_transcript,
+ * _set_wire_commit, _set_precheck) are read when the ticket STARTS, as a synchronous call made at that moment would read
+ * them; changing them with tickets outstanding is unspecified.  While capgpu_plonk_shard_msm is on, submission returns
+ * CAPGPU_ERR_INVALID_ARG: the ranks must prove in lock step.  The worker threads (at most CAPGPU_ASYNC_INFLIGHT per
+ * device) are created with the first ticket. */
+int capgpu_plonk_prove_batch_async(uint64_t pk_handle, int count, const uint64_t* wires, const uint64_t* pub_inputs,
+                                   size_t num_inputs, const uint8_t* ext_msg, size_t ext_msg_len,
+                                   const uint64_t* blinders, int input_form, capgpu_proof* proofs_out,
+                                   uint64_t* ticket_out);
+int capgpu_plonk_prove_multi_async(const uint64_t* pk_handles, int count, const uint64_t* wires,
+                                   const uint64_t* pub_inputs, size_t num_inputs, const uint8_t* const* ext_msgs,
+                                   const size_t* ext_msg_lens, const uint64_t* blinders, int input_form,
+                                   capgpu_proof* proofs_out, uint64_t* ticket_out);
+/* Waits for a ticket, from any thread, for at most timeout_ms milliseconds (0 polls, UINT32_MAX: no limit) - blocked on
+ * a condition variable, never spinning.
+ *  - not done in time: CAPGPU_OK with *done_out = 0; the ticket stays valid;
+ *  - done: *done_out = 1, the return value is the proving call's own code and capgpu_last_error() of the CALLING thread
+ *    its message - an unsatisfied witness gives the code and text the synchronous call gives in the transcript / precheck
+ *    mode the ticket ran in.  The ticket is then CONSUMED;
+ *  - unknown or consumed ticket: CAPGPU_ERR_BAD_HANDLE.  Of two threads waiting for one ticket one gets the result, the
+ *    other CAPGPU_ERR_BAD_HANDLE.
+ * Tickets may be waited for in any order.  capgpu_shutdown lets running tickets finish, drops queued ones (a thread blocked
+ * in capgpu_wait receives CAPGPU_ERR_NOT_INITIALISED for them), discards results nobody waits for and joins the workers
+ * before any context goes.  capgpu_trim sees a context with a running ticket as busy. */
+int capgpu_wait(uint64_t ticket, uint32_t timeout_ms, int* done_out);
+/* Counters since capgpu_init: tickets accepted, tickets finished (dropped ones included), and the most tickets that were
+ * running at the same moment on one device.  Any pointer may be NULL. */
+int capgpu_async_stats(uint64_t* submitted_out, uint64_t* completed_out, uint32_t* max_running_out);
+/* Sizes context `slot` (-1: every context) AHEAD for a batch of `count` host-resident proofs under this key in
+ * `input_form`, without proving anything: every scratch buffer such a batch would grow - the prover's workspace, the MSM
+ * workspace, the NTT scratch, the staging of the witnesses, with capgpu_plonk_set_precheck on the check's scratch - and the
+ * pinned result area, in the transcript / wire-commit / precheck modes in force NOW, from the same size expressions the
+ * prover uses.  The key, its SRS and the Lagrange-form commit key are brought to that context as the first proof would
+ * bring them.  No kernel of the prover runs (capgpu_plonk_sync_stats does not move).  A steady-state call - synchronous
+ * from a thread bound to that context, or a ticket that runs there - of at most `count` proofs then allocates nothing:
+ * capgpu_scratch_stats stays where it was.  (A synchronous call of an UNBOUND thread is cut into parts, each smaller than
+ * the call: reserve the contexts for the call's size, or the part's.)  Buffers get the usual 25 % slack; the call respects
+ * capgpu_set_memory_limit and fails as a proving call would: CAPGPU_ERR_OOM naming the bytes. */
+int capgpu_plonk_reserve(uint64_t pk_handle, int count, int input_form, int slot);
 
 /* ---- witness check: replaces Circuit::check_circuit_satisfiability as the reference's prove() calls it ------------
  * The reference checks every witness against its circuit BEFORE it calls the SNARK (src/proof/transfer.rs:167-177,

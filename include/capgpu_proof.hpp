@@ -327,6 +327,83 @@ inline Result<Unit> check_satisfiability(const ProvingKey& pk, const Assignment&
   return Unit{};
 }
 
+// A batch of proofs being made by a worker thread of the library (capgpu_plonk_prove_batch_async).  The handle OWNS the
+// blinders and the output array; the witnesses and public inputs stay the caller's and must outlive it.  wait() hands the
+// proofs out; the destructor waits for a ticket nobody waited for, so the library never writes into freed memory.
+class ProveTicket {
+ public:
+  ProveTicket() = default;
+  ProveTicket(uint64_t ticket, std::vector<uint64_t> blinders, std::unique_ptr<std::vector<Proof>> proofs)
+      : ticket_(ticket), pending_(true), blinders_(std::move(blinders)), proofs_(std::move(proofs)) {}
+  ProveTicket(ProveTicket&& o) noexcept { *this = std::move(o); }
+  ProveTicket& operator=(ProveTicket&& o) noexcept {
+    if (this != &o) {
+      finish();
+      ticket_ = o.ticket_;
+      pending_ = o.pending_;
+      blinders_ = std::move(o.blinders_);
+      proofs_ = std::move(o.proofs_);
+      o.pending_ = false;
+    }
+    return *this;
+  }
+  ProveTicket(const ProveTicket&) = delete;
+  ProveTicket& operator=(const ProveTicket&) = delete;
+  ~ProveTicket() { finish(); }
+  // true: done (then `result` holds the proofs or the proving call's error); false: not within timeout_ms (0 polls)
+  bool wait_for(uint32_t timeout_ms, Result<std::vector<Proof>>* result) {
+    if (!pending_) {
+      *result = TxnApiError::failed_snark("prove_batch_async: the ticket's result was already taken");
+      return true;
+    }
+    int done = 0;
+    const int rc = capgpu_wait(ticket_, timeout_ms, &done);
+    if (rc == CAPGPU_OK && !done) return false;
+    pending_ = false;
+    if (rc != CAPGPU_OK) *result = detail::map_error(rc, "prove_batch_async");
+    else *result = std::move(*proofs_);
+    return true;
+  }
+  Result<std::vector<Proof>> wait() {
+    Result<std::vector<Proof>> r(TxnApiError::failed_snark("prove_batch_async"));
+    (void)wait_for(UINT32_MAX, &r);
+    return r;
+  }
+
+ private:
+  void finish() {
+    if (!pending_) return;
+    int done = 0;
+    (void)capgpu_wait(ticket_, UINT32_MAX, &done);
+    pending_ = false;
+  }
+  uint64_t ticket_ = 0;
+  bool pending_ = false;
+  std::vector<uint64_t> blinders_;                // borrowed by the library until the ticket is done
+  std::unique_ptr<std::vector<Proof>> proofs_;    // written by the library: a stable address across moves of the handle
+};
+
+// `count` proofs under one key from host memory without waiting for them: a.wires holds count x 5 x n field elements,
+// a.pub_inputs count x num_inputs; the blinders are drawn now, in proof order, as count calls of prove() would draw them.
+// One thread that keeps two tickets in flight reaches the rate of two bound threads.
+template <class Rng>
+Result<ProveTicket> prove_batch_async(Rng& rng, const ProvingKey& pk, const Assignment& a, size_t count,
+                                      const std::vector<uint8_t>* ext_msg = nullptr) {
+  if (!a.wires || (!a.pub_inputs && pk.num_inputs())) return TxnApiError::failed_snark("prove_batch_async: empty assignment");
+  std::vector<uint64_t> blinders(count * 13 * 4);
+  for (size_t i = 0; i < count * 13; i++) {
+    Fr b = rng();
+    std::memcpy(&blinders[4 * i], b.data(), 32);
+  }
+  auto proofs = std::make_unique<std::vector<Proof>>(count);
+  uint64_t ticket = 0;
+  int rc = capgpu_plonk_prove_batch_async(pk.handle(), (int)count, a.wires, a.pub_inputs, pk.num_inputs(),
+                                          ext_msg ? ext_msg->data() : nullptr, ext_msg ? ext_msg->size() : 0,
+                                          blinders.data(), a.input_form, proofs->data(), &ticket);
+  if (rc != CAPGPU_OK) return detail::map_error(rc, "prove_batch_async");
+  return ProveTicket(ticket, std::move(blinders), std::move(proofs));
+}
+
 }  // namespace proof
 
 // ---- Transfer (src/proof/transfer.rs) ----------------------------------------------------------------------------
