@@ -33,6 +33,7 @@ pub const NUM_SELECTORS: usize = 13;
 /// jf-relation's `Arithmetization` trait returns, passed through without a CPU transform.
 pub const CAPGPU_INPUT_EVALS: c_int = 0;
 pub const CAPGPU_INPUT_COEFFS: c_int = 1;
+pub const CAPGPU_INPUT_VARS: c_int = 2;
 
 /// `capgpu_proof`: the fields of `jf_plonk::proof_system::structs::Proof`, in order (plookup_proof = None).
 #[repr(C)]
@@ -167,6 +168,12 @@ extern "C" {
     pub fn capgpu_plonk_preprocess_ex(srs_handle: u64, n: usize, num_inputs: usize, selectors: *const u64,
                                       sigmas: *const u64, input_form: c_int, pk_handle_out: *mut u64,
                                       vk_out: *mut capgpu_verifying_key) -> c_int;
+    pub fn capgpu_plonk_preprocess_vars(srs_handle: u64, n: usize, num_inputs: usize, selectors: *const u64,
+                                        selector_form: c_int, wire_vars: *const u32, num_vars: usize,
+                                        pk_handle_out: *mut u64, vk_out: *mut capgpu_verifying_key) -> c_int;
+    pub fn capgpu_plonk_key_set_vars(pk_handle: u64, wire_vars: *const u32, num_vars: usize) -> c_int;
+    pub fn capgpu_plonk_key_num_vars(pk_handle: u64, num_vars_out: *mut usize) -> c_int;
+    pub fn capgpu_plonk_input_stats(witness_bytes_h2d_out: *mut u64, gather_launches_out: *mut u64) -> c_int;
     pub fn capgpu_plonk_free_key(pk_handle: u64) -> c_int;
     pub fn capgpu_plonk_key_info(pk_handle: u64, domain_size_out: *mut usize, num_inputs_out: *mut usize,
                                  srs_handle_out: *mut u64) -> c_int;
@@ -476,6 +483,49 @@ impl ProvingKey {
         })?;
         Ok(ProvingKey { handle, vk, domain_size: n, num_inputs })
     }
+    /// `PlonkKzgSnark::preprocess` from what a jf-relation `PlonkCircuit` holds about its copy constraints: the wire ->
+    /// variable table, `circuit.wire_variables[..5]` flattened column-major (5 columns of n ids below `num_vars` =
+    /// `circuit.num_vars()`).  The permutation is built on the device; the key bytes are those of `preprocess` on the
+    /// permutation's values.  The key keeps the table: it is the one that `prove_vars` works with.  `selectors` in
+    /// `selector_form` (`CAPGPU_INPUT_EVALS` / `CAPGPU_INPUT_COEFFS`).
+    pub fn preprocess_vars(srs: &Srs, n: usize, num_inputs: usize, selectors: &[[u64; 4]], selector_form: c_int,
+                           wire_vars: &[u32], num_vars: usize) -> Result<ProvingKey> {
+        assert_eq!(selectors.len(), NUM_SELECTORS * n);
+        assert_eq!(wire_vars.len(), NUM_WIRE_TYPES * n);
+        let mut handle = 0u64;
+        let mut vk: capgpu_verifying_key = unsafe { std::mem::zeroed() };
+        check(unsafe {
+            capgpu_plonk_preprocess_vars(srs.handle, n, num_inputs, selectors.as_ptr() as *const u64, selector_form,
+                                         wire_vars.as_ptr(), num_vars, &mut handle, &mut vk)
+        })?;
+        Ok(ProvingKey { handle, vk, domain_size: n, num_inputs })
+    }
+    /// Attaches the table to a key made another way (`preprocess`, a deserialised blob); refused when the permutation
+    /// it implies is not the key's.
+    pub fn set_vars(&self, wire_vars: &[u32], num_vars: usize) -> Result<()> {
+        assert_eq!(wire_vars.len(), NUM_WIRE_TYPES * self.domain_size);
+        check(unsafe { capgpu_plonk_key_set_vars(self.handle, wire_vars.as_ptr(), num_vars) })
+    }
+    /// Length of a `prove_vars` witness; 0: the key has no table.
+    pub fn num_vars(&self) -> Result<usize> {
+        let mut nv = 0usize;
+        check(unsafe { capgpu_plonk_key_num_vars(self.handle, &mut nv) })?;
+        Ok(nv)
+    }
+    /// The same proof from the circuit's variable assignment (`CAPGPU_INPUT_VARS`): `witness` = `circuit.witness`, one
+    /// value per variable - an eighth of the bytes of the five columns for a CAP transfer; the columns are gathered on
+    /// the device through the key's table.  Same proof bytes as `prove` on the expanded columns.
+    pub fn prove_vars(&self, witness: &[[u64; 4]], pub_inputs: &[[u64; 4]], ext_msg: &[u8], blinders: &[[u64; 4]; 13]) -> Result<capgpu_proof> {
+        assert_eq!(witness.len(), self.num_vars()?);
+        assert_eq!(pub_inputs.len(), self.num_inputs);
+        let mut proof: capgpu_proof = unsafe { std::mem::zeroed() };
+        check(unsafe {
+            capgpu_plonk_prove_ex(self.handle, witness.as_ptr() as *const u64, pub_inputs.as_ptr() as *const u64,
+                                  pub_inputs.len(), ext_msg.as_ptr(), ext_msg.len(), blinders.as_ptr() as *const u64,
+                                  CAPGPU_INPUT_VARS, &mut proof)
+        })?;
+        Ok(proof)
+    }
     /// `PlonkKzgSnark::prove::<_, _, SolidityTranscript>(rng, circuit, pk, Some(ext_msg))` for one note: callable from
     /// any thread; with coalescing on, concurrent calls share device batches.  `wires`: the 5 finalised wire COLUMNS, n
     /// VALUES each (`CAPGPU_INPUT_EVALS` - what this name has always taken); `blinders`: 13 `Fr::rand(rng)` draws in
@@ -511,7 +561,8 @@ impl ProvingKey {
                                  blinders: &'a [[u64; 4]], input_form: c_int, proofs: &'a mut [capgpu_proof])
                                  -> Result<ProveTicket<'a>> {
         let count = proofs.len();
-        assert_eq!(wires.len(), count * NUM_WIRE_TYPES * self.domain_size);
+        let per = if input_form == CAPGPU_INPUT_VARS { self.num_vars()? } else { NUM_WIRE_TYPES * self.domain_size };
+        assert_eq!(wires.len(), count * per);
         assert_eq!(pub_inputs.len(), count * self.num_inputs);
         assert_eq!(blinders.len(), count * 13);
         let mut ticket = 0u64;

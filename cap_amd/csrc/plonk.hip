@@ -41,6 +41,7 @@
 #include "plonk_kernels.hpp"
 #include "tickets.hpp"
 #include "transcript_dev.hpp"
+#include "vars_kernels.hpp"
 
 namespace cap {
 
@@ -75,11 +76,18 @@ struct ProvingKey {
   mutable uint32_t* chk_perm = nullptr;  // [5 n] index form of the extended permutation: cell i n + j -> i' n + j'
   mutable int chk_rc = 1;                // 1: not derived yet; CAPGPU_OK: ready; < 0: sigma was refused (chk_err), for good
   mutable std::string chk_err;
+  // The wire -> variable table of CAPGPU_INPUT_VARS ([5 n] ids below num_vars; null / 0: the key has none).  Set before the
+  // key is published (capgpu_plonk_preprocess_vars, replicas) or attached later by capgpu_plonk_key_set_vars, which must
+  // not run beside calls that use the key; a table it replaces is freed once every context's stream has drained.  A key
+  // with a table has chk_perm from the start - the permutation's index form is what the table was turned into.
+  mutable uint32_t* wire_vars = nullptr;
+  mutable size_t num_vars = 0;
   ProvingKey() = default;
   ProvingKey(const ProvingKey&) = delete;
   ProvingKey& operator=(const ProvingKey&) = delete;
   ~ProvingKey() {
-    for (void* p : {(void*)coef, (void*)sig_eval, (void*)pk_coset, (void*)inv_nx1, (void*)chk_sel, (void*)chk_perm})
+    for (void* p : {(void*)coef, (void*)sig_eval, (void*)pk_coset, (void*)inv_nx1, (void*)chk_sel, (void*)chk_perm,
+                    (void*)wire_vars})
       if (p) hipFree(p);
   }
 };
@@ -603,6 +611,47 @@ uint32_t h2d_chunk_start(uint32_t P, uint32_t chunks, uint32_t ck, bool short_fi
   return first + (uint32_t)((uint64_t)(P - first) * (ck - 1) / (chunks - 1));
 }
 
+// ---- variable-form input (CAPGPU_INPUT_VARS; kernels: vars_kernels.hpp) ------------------------------------------------
+// A witness arrives as one value per variable and becomes the five wire columns on the device, through the table its key
+// keeps: 32 B x num_vars over the link instead of 32 B x 5 n.  Everything behind the gather is the evals path.
+std::atomic<uint64_t> g_witness_h2d{0}, g_gather_launches{0};  // capgpu_plonk_input_stats
+inline void count_witness_h2d(size_t bytes) { g_witness_h2d.fetch_add(bytes, std::memory_order_relaxed); }
+
+// Context::stage_b for `cnt` witnesses in variable form: the five columns the gather writes ([cnt][5 n], where the evals
+// path copies them) and - host-resident input only - behind them the staged value vectors ([cnt][stride])
+inline size_t vars_stage_bytes(size_t cnt, size_t n, size_t stride, bool host) {
+  return wires_stage_bytes(cnt, n) + (host ? sizeof(fe) * cnt * stride : 0);
+}
+// the value vectors of a batch on the device: proof p's at d_vars + p * stride, its key's num_vars <= stride of them used
+struct VarsIn {
+  const fe* d_vars;
+  size_t stride;
+};
+bool key_lacks_table(const ProvingKey& K) {
+  if (K.wire_vars) return false;
+  set_error("capgpu_plonk: CAPGPU_INPUT_VARS: key has no variable table (capgpu_plonk_preprocess_vars or "
+            "capgpu_plonk_key_set_vars gives it one)");
+  return true;
+}
+// columns of proofs [p0, p0 + cnt) into d_cols ([P][5][n]): one launch per run of proofs that share a key
+void gather_vars(hipStream_t s, const ProvingKey& K, const std::vector<const ProvingKey*>* keys, uint32_t p0, uint32_t cnt,
+                 const VarsIn& in, fe* d_cols) {
+  const size_t cells = (size_t)NW * K.n;
+  for (uint32_t p = p0; p < p0 + cnt;) {
+    uint32_t q = p0 + cnt;
+    if (keys)
+      for (q = p + 1; q < p0 + cnt && (*keys)[q] == (*keys)[p];) q++;
+    const ProvingKey& Kp = keys ? *(*keys)[p] : K;
+    // enough lanes to fill the chip; the proofs beyond that are the lane's loop (the table stays in its register)
+    const uint32_t rows = std::min<uint32_t>(q - p, (uint32_t)std::max<size_t>(1, ((size_t)1 << 20) / (2 * cells)));
+    launch("k_gather_vars", k_gather_vars, dim3(cdiv(2 * cells, kThreads), rows), dim3(kThreads), 0, s,
+           (const uint4*)(in.d_vars + (size_t)p * in.stride), in.stride, (const uint32_t*)Kp.wire_vars, cells, q - p,
+           (uint4*)(d_cols + (size_t)p * cells));
+    g_gather_launches.fetch_add(1, std::memory_order_relaxed);
+    p = q;
+  }
+}
+
 // ---- witness check ---------------------------------------------------------------------------------------------------
 // The reference refuses a witness that does not satisfy its circuit before it calls the SNARK, and names the constraint
 // (`check_circuit_satisfiability`, src/proof/transfer.rs:167-177; mint.rs and freeze.rs likewise).  Here: two launches over
@@ -623,11 +672,19 @@ int key_check_tables(const ProvingKey& K) {
   DevTmp<fe> sel;
   DevTmp<uint32_t> perm, bad;
   CAP_HIP(sel.alloc((size_t)NS * n));
-  CAP_HIP(perm.alloc(cells));
-  CAP_HIP(bad.alloc(1));
   int rc = run_ntt_from(s, K.log_n, K.coef, K.ps, n, sel, n, NS, 0, 0);
   if (rc) return rc;
   ntt_table_to_internal(sel, sel, (size_t)NS * n, s);
+  if (K.chk_perm) {  // a key that knows its variable table has the index form already: no discrete logarithms
+    CAP_HIP(hipStreamSynchronize(s));
+    if ((rc = take_launch_error())) return rc;
+    K.chk_sel = sel.p;
+    sel.p = nullptr;
+    K.chk_rc = CAPGPU_OK;
+    return CAPGPU_OK;
+  }
+  CAP_HIP(perm.alloc(cells));
+  CAP_HIP(bad.alloc(1));
   wc29::PermConsts pc;
   memset(&pc, 0, sizeof pc);
   pc.log_n = K.log_n;
@@ -665,9 +722,10 @@ size_t check_small_bytes(uint32_t P) {
 }
 
 // Verdicts of P witnesses whose VALUES are resident at d_vals ([P][5][n]); d_pub: [P][pub_stride] on the device; d_small:
-// check_small_bytes(P) of device scratch.  Runs on the current context's stream and waits for it.
+// check_small_bytes(P) of device scratch.  Runs on the current context's stream and waits for it.  gates_only: the values
+// were gathered from variables through the keys' own tables - every copy constraint holds by construction.
 int check_batch(const ProvingKey& K, const std::vector<const ProvingKey*>* keys, uint32_t P, const fe* d_vals,
-                const fe* d_pub, size_t pub_stride, void* d_small, capgpu_witness_fault* faults) {
+                const fe* d_pub, size_t pub_stride, void* d_small, capgpu_witness_fault* faults, bool gates_only = false) {
   Context& c = ctx();
   hipStream_t s = c.stream;
   const size_t n = K.n;
@@ -691,12 +749,14 @@ int check_batch(const ProvingKey& K, const std::vector<const ProvingKey*>* keys,
   CAP_HIP(hipMemcpyAsync(dout, ho.data(), sizeof(CheckOut) * P, hipMemcpyHostToDevice, s));
   launch("k_check_gates", k_check_gates, dim3(cdiv(n, kThreads), P), dim3(kThreads), 0, s, d_vals, d_pub, pub_stride,
          (const CheckKey*)dk, n, dout);
-  launch("k_check_copies", k_check_copies, dim3(cdiv((size_t)NW * n, kThreads), P), dim3(kThreads), 0, s, d_vals,
-         (const CheckKey*)dk, n, dout);
-  launch("k_check_targets", k_check_targets, dim3(cdiv(P, 64)), dim3(64), 0, s, (const CheckKey*)dk, (const CheckOut*)dout,
-         P, (size_t)NW * n, dto);
+  if (!gates_only) {
+    launch("k_check_copies", k_check_copies, dim3(cdiv((size_t)NW * n, kThreads), P), dim3(kThreads), 0, s, d_vals,
+           (const CheckKey*)dk, n, dout);
+    launch("k_check_targets", k_check_targets, dim3(cdiv(P, 64)), dim3(64), 0, s, (const CheckKey*)dk,
+           (const CheckOut*)dout, P, (size_t)NW * n, dto);
+  }
   CAP_HIP(hipMemcpyAsync(ho.data(), dout, sizeof(CheckOut) * P, hipMemcpyDeviceToHost, s));
-  CAP_HIP(hipMemcpyAsync(hto.data(), dto, sizeof(uint32_t) * P, hipMemcpyDeviceToHost, s));
+  if (!gates_only) CAP_HIP(hipMemcpyAsync(hto.data(), dto, sizeof(uint32_t) * P, hipMemcpyDeviceToHost, s));
   CAP_HIP(hipStreamSynchronize(s));
   if ((rc = take_launch_error())) return rc;
   for (uint32_t p = 0; p < P; p++) {
@@ -734,7 +794,8 @@ size_t check_carve(void* base, uint32_t P, size_t pub_stride, bool coeffs, size_
 // pub_stride elements).  Scratch: Context::stage_a.  Coefficient-form input is transformed to values out of place, into
 // stage_a; d_wires is never written.
 int check_resident(const ProvingKey& K, const std::vector<const ProvingKey*>* keys, uint32_t P, const fe* d_wires,
-                   const uint64_t* pubs, size_t pub_stride, int form, capgpu_witness_fault* faults) {
+                   const uint64_t* pubs, size_t pub_stride, int form, capgpu_witness_fault* faults,
+                   bool gates_only = false) {
   Context& c = ctx();
   hipStream_t s = c.stream;
   const size_t n = K.n;
@@ -750,7 +811,7 @@ int check_resident(const ProvingKey& K, const std::vector<const ProvingKey*>* ke
   } else {
     d_vals = const_cast<fe*>(d_wires);
   }
-  return check_batch(K, keys, P, d_vals, d_pub, pub_stride, d_small, faults);
+  return check_batch(K, keys, P, d_vals, d_pub, pub_stride, d_small, faults, gates_only);
 }
 
 std::string fault_text(uint32_t p, const capgpu_witness_fault& f) {
@@ -796,13 +857,16 @@ int prove_batch(const ProvingKey& K, uint32_t P, const fe* d_wires, const uint64
                 const uint8_t* ext_msg, size_t ext_len, const uint64_t* blinders, capgpu_proof* proofs,
                 const uint8_t* const* msgs = nullptr, const size_t* msg_lens = nullptr,
                 const std::vector<const ProvingKey*>* keys = nullptr, const uint64_t* const* h_wires = nullptr,
-                int form = CAPGPU_INPUT_EVALS) {
+                int form = CAPGPU_INPUT_EVALS, const VarsIn* vin = nullptr) {
   // form: CAPGPU_INPUT_EVALS - d_wires / h_wires hold the wire assignment, 5 columns of n values per proof (round 1
   // interpolates them); CAPGPU_INPUT_COEFFS - they hold the 5 wire POLYNOMIALS, n coefficients each, as jf-relation's
   // compute_wire_polynomials returns them (src/proof/transfer.rs:181-186 holds that circuit): round 1 takes them as they
   // are and round 2's witness values come from ONE forward transform on the device.  The proofs are the same bytes.
-  // h_wires (optional): the wire columns are still in host memory - h_wires[p] points to the 5 n elements of proof p -
-  // and d_wires is an empty device buffer for them.
+  // CAPGPU_INPUT_VARS - the input is one value per variable, `vin->stride` elements per proof at vin->d_vars; d_wires is
+  // device scratch for the five columns, which k_gather_vars writes there through the keys' tables (chunk by chunk behind
+  // the chunk's copy when the values are still on the host); from there on the call is the evals form.
+  // h_wires (optional): the input is still in host memory - h_wires[p] points to the 5 n elements (variable form:
+  // num_vars values) of proof p - and d_wires (variable form: vin->d_vars) is an empty device buffer for them.
   // Round 1 then runs in chunks of proofs - copy, interpolate, blind, commit - so that the copy of a chunk (pageable
   // memory: the call blocks the host, not the device) overlaps the commitments of the one before.
   Context& c = ctx();
@@ -824,6 +888,36 @@ int prove_batch(const ProvingKey& K, uint32_t P, const fe* d_wires, const uint64
   } drain{c, h_wires != nullptr};
   const size_t n = K.n, m = K.m, ps = K.ps;
   auto key_of = [&](uint32_t p) -> const ProvingKey& { return keys ? *(*keys)[p] : K; };
+  const bool vars = form == CAPGPU_INPUT_VARS;
+  if (vars) {
+    for (uint32_t p = 0; p < P && (keys || p == 0); p++) {
+      if (key_lacks_table(key_of(p))) return CAPGPU_ERR_INVALID_ARG;
+      if (!vin || key_of(p).num_vars > vin->stride) {
+        set_error("capgpu_plonk_prove: rows of %zu variables given, the key of proof %u has %zu", vin ? vin->stride : (size_t)0,
+                  p, key_of(p).num_vars);
+        return CAPGPU_ERR_INVALID_ARG;
+      }
+    }
+  }
+  // elements per proof of the input as it arrives, and where host-resident input is copied to
+  const size_t in_elems = vars ? vin->stride : (size_t)NW * n;
+  fe* const in_dst = const_cast<fe*>(vars ? vin->d_vars : d_wires);
+  // Host-resident input of proofs [p0, p1) -> its rows of the device buffer, on stream `st`.  A proof in variable form
+  // brings the num_vars values of ITS key - callers of different keys gathered into one batch do not pad their buffers to
+  // the row length -, so only full rows that follow each other in host memory travel as one copy (a plain batch: one per
+  // chunk).
+  auto in_len = [&](uint32_t p) -> size_t { return vars ? key_of(p).num_vars : in_elems; };
+  auto copy_input = [&](uint32_t p0, uint32_t p1, hipStream_t st) -> int {
+    for (uint32_t p = p0; p < p1;) {
+      uint32_t q = p + 1;
+      while (q < p1 && in_len(q - 1) == in_elems && h_wires[q] == h_wires[q - 1] + (size_t)4 * in_elems) q++;
+      const size_t bytes = sizeof(fe) * ((size_t)(q - 1 - p) * in_elems + in_len(q - 1));
+      CAP_HIP(hipMemcpyAsync(in_dst + (size_t)p * in_elems, h_wires[p], bytes, hipMemcpyHostToDevice, st));
+      count_witness_h2d(bytes);
+      p = q;
+    }
+    return CAPGPU_OK;
+  };
   if (keys) {
     size_t max_ni = 0;
     for (uint32_t p = 0; p < P; p++) {
@@ -854,21 +948,20 @@ int prove_batch(const ProvingKey& K, uint32_t P, const fe* d_wires, const uint64
   // check reads whole witnesses, so host-resident ones are copied now, in one go, instead of chunk by chunk in round 1.
   const bool precheck = g_precheck.load(std::memory_order_relaxed) != 0 && !tl_prechecked;
   if (precheck && h_wires) {
-    for (uint32_t p = 0; p < P;) {
-      uint32_t q = p + 1;
-      while (q < P && h_wires[q] == h_wires[q - 1] + (size_t)4 * NW * n) q++;
-      CAP_HIP(hipMemcpyAsync(const_cast<fe*>(d_wires) + (size_t)p * NW * n, h_wires[p], sizeof(fe) * (size_t)(q - p) * NW * n,
-                             hipMemcpyHostToDevice, s));
-      p = q;
-    }
+    if ((rc = copy_input(0, P, s))) return rc;
     h_wires = nullptr;
   }
+  // variable form with the values resident (a caller's device buffer, or copied a moment ago): all columns at once
+  if (vars && !h_wires) gather_vars(s, K, keys, 0, P, *vin, const_cast<fe*>(d_wires));
   if (precheck) {
     // Ahead of everything the proof itself needs - the Lagrange-form commit key a domain's first proof may have to build,
     // the workspace, every MSM and NTT: a refused batch has cost the check's launches.  (Coefficient-form input is first
     // transformed to values, in scratch of the check's own.)
     std::vector<capgpu_witness_fault> faults(P);
-    if ((rc = check_resident(K, keys, P, d_wires, pub_inputs, num_inputs, form, faults.data()))) return rc;
+    // (gathered columns satisfy every copy constraint by construction: the gate pass only)
+    if ((rc = check_resident(K, keys, P, d_wires, pub_inputs, num_inputs, vars ? CAPGPU_INPUT_EVALS : form, faults.data(),
+                             vars)))
+      return rc;
     if ((rc = precheck_verdict(faults.data(), P))) return rc;
   }
   // the Lagrange-form commit key (built on the first proof of this domain size under this SRS if preprocess did not);
@@ -1106,13 +1199,7 @@ int prove_batch(const ProvingKey& K, uint32_t P, const fe* d_wires, const uint64
       }
       // one copy per run of proofs that are contiguous in host memory (a plain batch: one per chunk)
       trace("pb_h2d_issue", c.slot, ck);
-      for (uint32_t p = p0; p < p1;) {
-        uint32_t q = p + 1;
-        while (q < p1 && h_wires[q] == h_wires[q - 1] + (size_t)4 * NW * n) q++;
-        CAP_HIP(hipMemcpyAsync(const_cast<fe*>(d_wires) + (size_t)p * NW * n, h_wires[p],
-                               sizeof(fe) * (size_t)(q - p) * NW * n, hipMemcpyHostToDevice, cs));
-        p = q;
-      }
+      if ((rc = copy_input(p0, p1, cs))) return rc;
       trace("pb_h2d_issued", c.slot, ck);
       if (cs != s) {  // the chunk's kernels wait for its copy, not for the copies after it
         hipEvent_t ev;
@@ -1121,6 +1208,7 @@ int prove_batch(const ProvingKey& K, uint32_t P, const fe* d_wires, const uint64
         (void)hipEventDestroy(ev);  // released once the recorded work is done
         CAP_HIP(e2);
       }
+      if (vars) gather_vars(s, K, keys, p0, p1 - p0, *vin, const_cast<fe*>(d_wires));  // the chunk's columns, behind its copy
     }
     if (chunks > 1 && (rc = r1_chunk_kernels(p0, p1 - p0, true))) return rc;
   }
@@ -1567,6 +1655,7 @@ ProveNeeds prove_needs(const ProvingKey& K, const MsmBases& B, const MsmBases* L
   const MsmBases& W = Lag ? *Lag : B;  // rounds 1 and 2 commit on the Lagrange-form key when there is one
   // staging of host witnesses; the witness check reads whole witnesses, so round 1 is then not chunked
   if (host_wires) nd.stage_b = wires_stage_bytes(P, n);
+  if (form == CAPGPU_INPUT_VARS) nd.stage_b = vars_stage_bytes(P, n, K.num_vars, host_wires);
   if (precheck) {
     void* a = nullptr;
     fe *b = nullptr, *v = nullptr;
@@ -1820,7 +1909,12 @@ Coalescer& coalescer() {
 }  // namespace
 
 size_t plonk_trim_staging() { return stage_pool().trim(); }
-void plonk_reset_staging() { stage_pool().reset(); }
+void plonk_reset_staging() {
+  stage_pool().reset();
+  // (capgpu_shutdown: capgpu_plonk_input_stats counts since capgpu_init)
+  g_witness_h2d.store(0);
+  g_gather_launches.store(0);
+}
 
 // the registry's (home) copy of a key, without replicating it
 static int home_key(uint64_t h, std::shared_ptr<ProvingKey>* out) {
@@ -1862,6 +1956,18 @@ int clone_key_to_current(const ProvingKey& src, int src_device, std::shared_ptr<
   if ((rc = dup(&K->sig_eval, src.sig_eval, (size_t)NW * src.n))) return rc;
   if ((rc = dup(&K->pk_coset, src.pk_coset, 18 * src.m))) return rc;
   if ((rc = dup(&K->inv_nx1, src.inv_nx1, src.m))) return rc;
+  {
+    // the variable table and, with it, the permutation's index form (4 B x 5 n each) travel with the key
+    std::lock_guard<std::mutex> lk(src.chk_mu);
+    if (src.wire_vars && src.chk_perm) {
+      const size_t bytes = sizeof(uint32_t) * NW * src.n;
+      CAP_HIP(hipMalloc(&K->wire_vars, bytes));
+      CAP_HIP(hipMalloc(&K->chk_perm, bytes));
+      CAP_HIP(copy_between(K->wire_vars, c.device, src.wire_vars, src_device, bytes, c.stream));
+      CAP_HIP(copy_between(K->chk_perm, c.device, src.chk_perm, src_device, bytes, c.stream));
+      K->num_vars = src.num_vars;
+    }
+  }
   CAP_HIP(hipStreamSynchronize(c.stream));
   *out = K;
   return CAPGPU_OK;
@@ -1889,25 +1995,103 @@ int lookup_key(uint64_t h, std::shared_ptr<ProvingKey>* out) {
 
 }  // namespace cap
 
+namespace cap {
+// ---- the extended permutation from a wire -> variable table (vars_kernels.hpp) ---------------------------------------
+// d_perm[c] = the cell after c among the cells of c's variable in ascending order, the first after the last: the unique keys
+// (variable << 32) | cell are sorted - bitonic network, stages inside a tile of 2048 keys in LDS, the wider ones one launch
+// each - and neighbours linked.  On stream s; waits for it (the key array is scratch of this call).
+int vars_build_perm(hipStream_t s, const uint32_t* d_table, size_t n, uint32_t* d_perm) {
+  const size_t cells = (size_t)NW * n;
+  size_t padded = kSortTile;
+  while (padded < cells) padded <<= 1;
+  DevTmp<unsigned long long> keys;
+  CAP_HIP(keys.alloc(padded));
+  launch("k_vars_keys", k_vars_keys, dim3(cdiv(padded, kThreads)), dim3(kThreads), 0, s, d_table, cells, padded, keys.p);
+  const dim3 tiles((unsigned)(padded / kSortTile));
+  launch("k_vars_sort_tile", k_vars_sort_tile, tiles, dim3(kThreads), 0, s, keys.p, (size_t)2, (size_t)kSortTile);
+  for (size_t k = 2 * (size_t)kSortTile; k <= padded; k <<= 1) {
+    for (size_t j = k / 2; j >= kSortTile; j >>= 1)
+      launch("k_vars_sort_step", k_vars_sort_step, dim3(cdiv(padded / 2, kThreads)), dim3(kThreads), 0, s, keys.p, padded / 2,
+             k, j);
+    launch("k_vars_sort_tile", k_vars_sort_tile, tiles, dim3(kThreads), 0, s, keys.p, k, k);
+  }
+  launch("k_vars_link", k_vars_link, dim3(cdiv(cells, kThreads)), dim3(kThreads), 0, s, (const unsigned long long*)keys.p,
+         cells, d_perm);
+  CAP_HIP(hipStreamSynchronize(s));
+  return take_launch_error();
+}
+// index form -> sigma_i(omega^j) = k_i' omega^j' in arkworks' Montgomery form ([5 n]: what ProvingKey::sig_eval holds)
+void vars_sigma_values(hipStream_t s, uint32_t log_n, const uint32_t* d_perm, fe* d_sigma) {
+  SigmaConsts sc;
+  memset(&sc, 0, sizeof sc);
+  sc.log_n = log_n;
+  for (int i = 0; i < NW; i++) sc.k[i] = Fr::to_mont(fe_from_words(K_CANON[i]));
+  fe w = ntt_root_of_unity(log_n);
+  for (uint32_t b = 0; b < log_n && b < 28; b++) {
+    sc.wpow[b] = w;
+    w = Fr::sqr(w);
+  }
+  const size_t cells = (size_t)NW << log_n;
+  launch("k_vars_sigma", k_vars_sigma, dim3(cdiv(cells, kThreads)), dim3(kThreads), 0, s, d_perm, sc, cells, d_sigma);
+}
+// first id of the table ([5][n], host) that is not below num_vars: CAPGPU_ERR_INVALID_ARG naming its (wire, row)
+int vars_table_valid(const char* who, const uint32_t* wire_vars, size_t n, size_t num_vars) {
+  if (!wire_vars || num_vars < 1 || num_vars > 0xffffffffull) {
+    set_error("%s: bad argument (wire_vars: 5 columns of n ids, 1 <= num_vars < 2^32)", who);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  for (size_t c = 0; c < (size_t)NW * n; c++)
+    if (wire_vars[c] >= num_vars) {
+      set_error("%s: wire_vars holds id %u at (wire %zu, row %zu), num_vars is %zu", who, wire_vars[c], c / n, c % n, num_vars);
+      return CAPGPU_ERR_INVALID_ARG;
+    }
+  return CAPGPU_OK;
+}
+}  // namespace cap
+
 using namespace cap;
 
 extern "C" {
 
 static bool bad_form(int form) {
-  if (form == CAPGPU_INPUT_EVALS || form == CAPGPU_INPUT_COEFFS) return false;
-  set_error("capgpu_plonk: input_form %d is neither CAPGPU_INPUT_EVALS (0) nor CAPGPU_INPUT_COEFFS (1)", form);
+  if (form == CAPGPU_INPUT_EVALS || form == CAPGPU_INPUT_COEFFS || form == CAPGPU_INPUT_VARS) return false;
+  set_error("capgpu_plonk: input_form %d is none of CAPGPU_INPUT_EVALS (0), CAPGPU_INPUT_COEFFS (1), CAPGPU_INPUT_VARS (2)",
+            form);
   return true;
 }
+// the forms a key's COLUMNS (selectors, sigmas) come in
+static bool bad_column_form(int form) {
+  if (form == CAPGPU_INPUT_EVALS || form == CAPGPU_INPUT_COEFFS) return false;
+  set_error("capgpu_plonk_preprocess: form %d is neither CAPGPU_INPUT_EVALS (0) nor CAPGPU_INPUT_COEFFS (1)", form);
+  return true;
+}
+// CAPGPU_INPUT_VARS asks for a key with a table: refused before the device is touched.  *stride_out: elements per proof of
+// the input in `form` under the keys of one call - 5 n, or the largest num_vars among them.
+static int input_stride(const uint64_t* pks, int count, int form, size_t n, size_t* stride_out) {
+  *stride_out = (size_t)NW * n;
+  if (form != CAPGPU_INPUT_VARS) return CAPGPU_OK;
+  size_t stride = 0;
+  for (int i = 0; i < count; i++) {
+    std::shared_ptr<ProvingKey> K;
+    int rc = home_key(pks[i], &K);
+    if (rc) return rc;
+    if (key_lacks_table(*K)) return CAPGPU_ERR_INVALID_ARG;
+    stride = std::max(stride, K->num_vars);
+  }
+  *stride_out = stride;
+  return CAPGPU_OK;
+}
 
-int capgpu_plonk_preprocess_ex(uint64_t srs_handle, size_t n, size_t num_inputs, const uint64_t* selectors,
-                               const uint64_t* sigma_evals, int input_form, uint64_t* pk_handle_out,
-                               capgpu_verifying_key* vk_out) {
-  CAP_CHECK_INIT();
-  if (bad_form(input_form)) return CAPGPU_ERR_INVALID_ARG;
+// capgpu_plonk_preprocess_ex, or - wire_vars != nullptr: capgpu_plonk_preprocess_vars - the same with the extended
+// permutation built on the device from the circuit's wire -> variable table (`sigma_evals` is then unused and
+// `input_form` is the selectors' alone); from the sigma values on, one code path finishes both keys.
+static int preprocess_impl(uint64_t srs_handle, size_t n, size_t num_inputs, const uint64_t* selectors,
+                           const uint64_t* sigma_evals, int input_form, const uint32_t* wire_vars, size_t num_vars,
+                           uint64_t* pk_handle_out, capgpu_verifying_key* vk_out) {
   Context& c = ctx();
   Entry lk(c);
   // n >= 16: the five split-quotient commitments read 5 (n + 2) coefficients of the 6n-point quotient array
-  if (!selectors || !sigma_evals || !pk_handle_out || n < 16 || (n & (n - 1)) || num_inputs >= n) {
+  if (!selectors || (!sigma_evals && !wire_vars) || !pk_handle_out || n < 16 || (n & (n - 1)) || num_inputs >= n) {
     set_error("capgpu_plonk_preprocess: bad argument (n must be a power of two >= 16, num_inputs < n)");
     return CAPGPU_ERR_INVALID_ARG;
   }
@@ -1927,10 +2111,24 @@ int capgpu_plonk_preprocess_ex(uint64_t srs_handle, size_t n, size_t num_inputs,
   DevTmp<g1_jac> d_comms;
   CAP_HIP(stage.alloc(18 * n));
   CAP_HIP(hipMemcpyAsync(stage, selectors, sizeof(fe) * NS * n, hipMemcpyHostToDevice, s));
-  CAP_HIP(hipMemcpyAsync(stage.p + (size_t)NS * n, sigma_evals, sizeof(fe) * NW * n, hipMemcpyHostToDevice, s));
+  if (wire_vars) {
+    // the permutation comes from the table, on the device: its index form stays with the key (the witness check needs no
+    // discrete logarithm for it), its field form is the sigma VALUES a caller of capgpu_plonk_preprocess would have sent
+    CAP_HIP(hipMalloc(&K->wire_vars, sizeof(uint32_t) * NW * n));
+    CAP_HIP(hipMalloc(&K->chk_perm, sizeof(uint32_t) * NW * n));
+    CAP_HIP(hipMemcpyAsync(K->wire_vars, wire_vars, sizeof(uint32_t) * NW * n, hipMemcpyHostToDevice, s));
+    K->num_vars = num_vars;
+    if ((rc = vars_build_perm(s, K->wire_vars, n, K->chk_perm))) return rc;
+    vars_sigma_values(s, K->log_n, K->chk_perm, stage.p + (size_t)NS * n);
+  } else {
+    CAP_HIP(hipMemcpyAsync(stage.p + (size_t)NS * n, sigma_evals, sizeof(fe) * NW * n, hipMemcpyHostToDevice, s));
+  }
   CAP_HIP(hipMemcpyAsync(K->sig_eval, stage.p + (size_t)NS * n, sizeof(fe) * NW * n, hipMemcpyDeviceToDevice, s));
   pad_copy(s, K->coef, ps, 0, stage.p, n, 0, 1, 18, n, ps);
-  if (input_form == CAPGPU_INPUT_COEFFS) {
+  if (input_form == CAPGPU_INPUT_COEFFS && wire_vars) {
+    // selector polynomials as they are; the table's sigma is VALUES: interpolate those five columns only
+    if ((rc = run_ntt(s, K->log_n, K->coef + (size_t)NS * ps, ps, NW, 1, 0))) return rc;
+  } else if (input_form == CAPGPU_INPUT_COEFFS) {
     // the 18 polynomials arrive as jf-relation computes them (compute_selector_polynomials /
     // compute_extended_permutation_polynomials): nothing to interpolate; round 2 reads sigma's VALUES on the domain
     if ((rc = run_ntt(s, K->log_n, K->sig_eval, n, NW, 0, 0))) return rc;
@@ -1958,6 +2156,29 @@ int capgpu_plonk_preprocess_ex(uint64_t srs_handle, size_t n, size_t num_inputs,
   }
   *pk_handle_out = register_key(K);
   return take_launch_error();
+}
+
+int capgpu_plonk_preprocess_ex(uint64_t srs_handle, size_t n, size_t num_inputs, const uint64_t* selectors,
+                               const uint64_t* sigma_evals, int input_form, uint64_t* pk_handle_out,
+                               capgpu_verifying_key* vk_out) {
+  CAP_CHECK_INIT();
+  if (bad_column_form(input_form)) return CAPGPU_ERR_INVALID_ARG;
+  return preprocess_impl(srs_handle, n, num_inputs, selectors, sigma_evals, input_form, nullptr, 0, pk_handle_out, vk_out);
+}
+
+int capgpu_plonk_preprocess_vars(uint64_t srs_handle, size_t n, size_t num_inputs, const uint64_t* selectors,
+                                 int selector_form, const uint32_t* wire_vars, size_t num_vars, uint64_t* pk_handle_out,
+                                 capgpu_verifying_key* vk_out) {
+  CAP_CHECK_INIT();
+  if (bad_column_form(selector_form)) return CAPGPU_ERR_INVALID_ARG;
+  if (n < 16 || (n & (n - 1))) {
+    set_error("capgpu_plonk_preprocess: bad argument (n must be a power of two >= 16, num_inputs < n)");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  int rc = vars_table_valid("capgpu_plonk_preprocess_vars", wire_vars, n, num_vars);
+  if (rc) return rc;
+  return preprocess_impl(srs_handle, n, num_inputs, selectors, nullptr, selector_form, wire_vars, num_vars, pk_handle_out,
+                         vk_out);
 }
 
 int capgpu_plonk_preprocess(uint64_t srs_handle, size_t n, size_t num_inputs, const uint64_t* selectors,
@@ -2192,6 +2413,89 @@ int capgpu_plonk_key_info(uint64_t pk_handle, size_t* domain_size_out, size_t* n
   return CAPGPU_OK;
 }
 
+int capgpu_plonk_key_num_vars(uint64_t pk_handle, size_t* num_vars_out) {
+  CAP_CHECK_INIT();
+  std::shared_ptr<ProvingKey> K;
+  int rc = home_key(pk_handle, &K);
+  if (rc) return rc;
+  if (num_vars_out) *num_vars_out = K->wire_vars ? K->num_vars : 0;
+  return CAPGPU_OK;
+}
+
+int capgpu_plonk_input_stats(uint64_t* witness_bytes_h2d_out, uint64_t* gather_launches_out) {
+  if (witness_bytes_h2d_out) *witness_bytes_h2d_out = g_witness_h2d.load();
+  if (gather_launches_out) *gather_launches_out = g_gather_launches.load();
+  return CAPGPU_OK;
+}
+
+// Attaches a wire -> variable table to a key made without one.  Runs on a context of the key's home device: the table's
+// permutation is built there (vars_build_perm) and compared, cell for cell, with the index form of the key's own sigma.
+int capgpu_plonk_key_set_vars(uint64_t pk_handle, const uint32_t* wire_vars, size_t num_vars) {
+  CAP_CHECK_INIT();
+  std::shared_ptr<ProvingKey> K;
+  int rc = home_key(pk_handle, &K);
+  if (rc) return rc;
+  if ((rc = vars_table_valid("capgpu_plonk_key_set_vars", wire_vars, K->n, num_vars))) return rc;
+  Runtime& R = rt();
+  Context* home = nullptr;
+  for (auto& cp : R.ctxs)
+    if (cp->device == K->device) {
+      home = cp.get();
+      break;
+    }
+  if (!home) {
+    set_error("capgpu_plonk_key_set_vars: no context on the key's device %d", K->device);
+    return CAPGPU_ERR_BAD_HANDLE;
+  }
+  uint32_t* replaced = nullptr;  // the table the key had: freed below, behind whatever launch may still read it
+  {
+    ScopedCtx sc(*home);
+    Entry lk(*home);
+    hipStream_t s = home->stream;
+    const size_t n = K->n, cells = (size_t)NW * n;
+    DevTmp<uint32_t> table, perm;
+    DevTmp<unsigned long long> first;
+    CAP_HIP(table.alloc(cells));
+    CAP_HIP(perm.alloc(cells));
+    CAP_HIP(first.alloc(1));
+    CAP_HIP(hipMemcpyAsync(table, wire_vars, sizeof(uint32_t) * cells, hipMemcpyHostToDevice, s));
+    if ((rc = vars_build_perm(s, table, n, perm))) return rc;
+    if ((rc = key_check_tables(*K))) return rc;  // the key's own permutation in index form (derived once per key)
+    unsigned long long h_first = ~0ull;
+    CAP_HIP(hipMemcpyAsync(first, &h_first, sizeof h_first, hipMemcpyHostToDevice, s));
+    launch("k_vars_differ", k_vars_differ, dim3(cdiv(cells, kThreads)), dim3(kThreads), 0, s, (const uint32_t*)perm.p,
+           (const uint32_t*)K->chk_perm, cells, first.p);
+    CAP_HIP(hipMemcpyAsync(&h_first, first, sizeof h_first, hipMemcpyDeviceToHost, s));
+    CAP_HIP(hipStreamSynchronize(s));
+    if ((rc = take_launch_error())) return rc;
+    if (h_first != ~0ull) {
+      set_error("capgpu_plonk_key_set_vars: the table's permutation is not the key's: first difference at (wire %llu, row "
+                "%llu); the key is unchanged", h_first / n, h_first % n);
+      return CAPGPU_ERR_INVALID_ARG;
+    }
+    std::lock_guard<std::mutex> klk(K->chk_mu);
+    replaced = K->wire_vars;
+    K->wire_vars = table.p;
+    K->num_vars = num_vars;
+    table.p = nullptr;
+  }
+  // replicas on other devices were cloned without the table (or with the old one): they are made again on next use
+  for (auto& cp : R.ctxs) {
+    Context& c = *cp;
+    ScopedCtx sc(c);
+    Entry lk(c);
+    auto it = c.keys.find(pk_handle);
+    if (it == c.keys.end()) continue;
+    if (replaced || it->second.get() != K.get()) (void)hipStreamSynchronize(c.stream);
+    if (it->second.get() != K.get()) c.keys.erase(it);
+  }
+  if (replaced) {
+    ScopedCtx sc(*home);
+    (void)hipFree(replaced);
+  }
+  return CAPGPU_OK;
+}
+
 int capgpu_plonk_free_key(uint64_t pk_handle) {
   CAP_CHECK_INIT();
   Runtime& R = rt();
@@ -2229,9 +2533,18 @@ int capgpu_plonk_prove_batch_dev_ex(uint64_t pk_handle, int count, const void* d
     return CAPGPU_ERR_INVALID_ARG;
   }
   if (count == 0) return CAPGPU_OK;
-  std::shared_ptr<ProvingKey> K;
-  int rc = lookup_key(pk_handle, &K);
+  size_t stride = 0;
+  int rc = input_stride(&pk_handle, 1, input_form, 0, &stride);
   if (rc) return rc;
+  std::shared_ptr<ProvingKey> K;
+  if ((rc = lookup_key(pk_handle, &K))) return rc;
+  if (input_form == CAPGPU_INPUT_VARS) {
+    // the caller's buffer holds count * num_vars values and is only read: the columns are gathered into staging
+    if ((rc = scratch_reserve(c.stage_b, vars_stage_bytes((size_t)count, K->n, 0, false)))) return rc;
+    const VarsIn vin{(const fe*)d_wires, stride};
+    return prove_batch(*K, (uint32_t)count, (const fe*)c.stage_b.p, pub_inputs, num_inputs, ext_msg, ext_msg_len, blinders,
+                       proofs_out, nullptr, nullptr, nullptr, nullptr, input_form, &vin);
+  }
   return prove_batch(*K, (uint32_t)count, (const fe*)d_wires, pub_inputs, num_inputs, ext_msg, ext_msg_len, blinders,
                      proofs_out, nullptr, nullptr, nullptr, nullptr, input_form);
 }
@@ -2367,6 +2680,7 @@ struct HostBatch {
   capgpu_proof* proofs_out;
   size_t n;
   const std::shared_ptr<ProvingKey>* home;  // tickets: see part_key
+  size_t stride;  // elements per proof of `wires`: 5 n, or the key's num_vars (input_stride)
 };
 static int host_batch_part(const HostBatch& b, int first, int cnt) {
   Context& c = ctx();
@@ -2375,15 +2689,18 @@ static int host_batch_part(const HostBatch& b, int first, int cnt) {
   std::shared_ptr<ProvingKey> K;
   int rc = part_key(b.pk, b.home, &K);
   if (rc) return rc;
-  rc = scratch_reserve(c.stage_b, wires_stage_bytes((size_t)cnt, n));
+  const bool vars = b.input_form == CAPGPU_INPUT_VARS;
+  rc = scratch_reserve(c.stage_b, vars ? vars_stage_bytes((size_t)cnt, n, b.stride, true) : wires_stage_bytes((size_t)cnt, n));
   if (rc) return rc;
-  // the columns are copied inside round 1, chunk by chunk, behind the commitments of the chunk before
+  // the columns (variable form: the value vectors) are copied inside round 1, chunk by chunk, behind the commitments of
+  // the chunk before
   std::vector<const uint64_t*> rows(cnt);
-  for (int i = 0; i < cnt; i++) rows[i] = b.wires + (size_t)4 * (first + i) * NW * n;
+  for (int i = 0; i < cnt; i++) rows[i] = b.wires + (size_t)4 * (first + i) * b.stride;
+  const VarsIn vin{(const fe*)c.stage_b.p + (size_t)cnt * NW * n, b.stride};
   return prove_batch(*K, (uint32_t)cnt, (const fe*)c.stage_b.p,
                      b.pub_inputs ? b.pub_inputs + (size_t)4 * first * b.num_inputs : nullptr, b.num_inputs, b.ext_msg,
                      b.ext_msg_len, b.blinders + (size_t)4 * 13 * first, b.proofs_out + first, nullptr, nullptr, nullptr,
-                     rows.data(), b.input_form);
+                     rows.data(), b.input_form, vars ? &vin : nullptr);
 }
 
 int capgpu_plonk_prove_batch_ex(uint64_t pk_handle, int count, const uint64_t* wires, const uint64_t* pub_inputs,
@@ -2403,8 +2720,10 @@ int capgpu_plonk_prove_batch_ex(uint64_t pk_handle, int count, const uint64_t* w
     set_error("capgpu_plonk_prove: bad argument");
     return CAPGPU_ERR_INVALID_ARG;
   }
+  size_t stride = 0;
+  if ((rc0 = input_stride(&pk_handle, 1, input_form, K0->n, &stride))) return rc0;
   const HostBatch b{pk_handle, wires, pub_inputs, num_inputs, ext_msg, ext_msg_len, blinders, input_form, proofs_out, K0->n,
-                    nullptr};
+                    nullptr, stride};
   return deal(count, [&](int first, int cnt) -> int { return host_batch_part(b, first, cnt); });
 }
 int capgpu_plonk_prove_batch(uint64_t pk_handle, int count, const uint64_t* wires, const uint64_t* pub_inputs,
@@ -2436,6 +2755,15 @@ int capgpu_plonk_prove_multi_dev_ex(const uint64_t* pk_handles, int count, const
     if (rc) return rc;
     keys[i] = hold[i].get();
   }
+  if (input_form == CAPGPU_INPUT_VARS) {
+    size_t stride = 0;
+    int rc = input_stride(pk_handles, count, input_form, 0, &stride);
+    if (rc) return rc;
+    if ((rc = scratch_reserve(c.stage_b, vars_stage_bytes((size_t)count, keys[0]->n, 0, false)))) return rc;
+    const VarsIn vin{(const fe*)d_wires, stride};
+    return prove_batch(*keys[0], (uint32_t)count, (const fe*)c.stage_b.p, pub_inputs, num_inputs, nullptr, 0, blinders,
+                       proofs_out, ext_msgs, ext_msg_lens, &keys, nullptr, input_form, &vin);
+  }
   return prove_batch(*keys[0], (uint32_t)count, (const fe*)d_wires, pub_inputs, num_inputs, nullptr, 0, blinders,
                      proofs_out, ext_msgs, ext_msg_lens, &keys, nullptr, input_form);
 }
@@ -2458,6 +2786,7 @@ struct HostMulti {
   capgpu_proof* proofs_out;
   size_t n;
   const std::shared_ptr<ProvingKey>* homes;  // tickets: [count], see part_key
+  size_t stride;  // elements per proof of `wires`: 5 n, or the largest num_vars among the keys of the WHOLE call
 };
 static int host_multi_part(const HostMulti& b, int first, int cnt) {
   Context& c = ctx();
@@ -2486,12 +2815,17 @@ static int host_multi_part(const HostMulti& b, int first, int cnt) {
       if (ni) memcpy(&pubs[(size_t)4 * ni * i], pp + (size_t)4 * num_inputs * i, 32 * ni);
     pp = pubs.data();
   }
-  if ((rc = scratch_reserve(c.stage_b, wires_stage_bytes((size_t)cnt, n)))) return rc;
+  const bool vars = b.input_form == CAPGPU_INPUT_VARS;
+  if ((rc = scratch_reserve(c.stage_b,
+                            vars ? vars_stage_bytes((size_t)cnt, n, b.stride, true) : wires_stage_bytes((size_t)cnt, n))))
+    return rc;
   std::vector<const uint64_t*> rows(cnt);
-  for (int i = 0; i < cnt; i++) rows[i] = b.wires + (size_t)4 * (first + i) * NW * n;
+  for (int i = 0; i < cnt; i++) rows[i] = b.wires + (size_t)4 * (first + i) * b.stride;
+  const VarsIn vin{(const fe*)c.stage_b.p + (size_t)cnt * NW * n, b.stride};
   return prove_batch(*keys[0], (uint32_t)cnt, (const fe*)c.stage_b.p, pp, ni, nullptr, 0,
                      b.blinders + (size_t)4 * 13 * first, b.proofs_out + first, b.ext_msgs ? b.ext_msgs + first : nullptr,
-                     b.ext_msg_lens ? b.ext_msg_lens + first : nullptr, &keys, rows.data(), b.input_form);
+                     b.ext_msg_lens ? b.ext_msg_lens + first : nullptr, &keys, rows.data(), b.input_form,
+                     vars ? &vin : nullptr);
 }
 
 int capgpu_plonk_prove_multi_ex(const uint64_t* pk_handles, int count, const uint64_t* wires,
@@ -2512,8 +2846,10 @@ int capgpu_plonk_prove_multi_ex(const uint64_t* pk_handles, int count, const uin
     set_error("capgpu_plonk_prove_multi: bad argument");
     return CAPGPU_ERR_INVALID_ARG;
   }
+  size_t stride = 0;
+  if ((rc0 = input_stride(pk_handles, count, input_form, K0->n, &stride))) return rc0;
   const HostMulti b{pk_handles, wires, pub_inputs, num_inputs, ext_msgs, ext_msg_lens, blinders, input_form, proofs_out, K0->n,
-                    nullptr};
+                    nullptr, stride};
   return deal(count, [&](int first, int cnt) -> int { return host_multi_part(b, first, cnt); });
 }
 int capgpu_plonk_prove_multi(const uint64_t* pk_handles, int count, const uint64_t* wires, const uint64_t* pub_inputs,
@@ -2540,7 +2876,7 @@ struct AsyncJob {
   std::vector<std::shared_ptr<ProvingKey>> homes;   // shared ownership, as home_key gives it: [pks.size()]
   const uint64_t *wires = nullptr, *pub_inputs = nullptr, *blinders = nullptr;  // borrowed until the ticket is done
   capgpu_proof* proofs_out = nullptr;               // borrowed likewise
-  size_t num_inputs = 0, n = 0;
+  size_t num_inputs = 0, n = 0, stride = 0;          // stride: elements per proof of `wires` (input_stride)
   int input_form = CAPGPU_INPUT_EVALS;
   bool has_msgs = false;                            // _multi with ext_msgs != NULL
   std::vector<std::vector<uint8_t>> msgs;           // copies: one (batch; empty = none) or one per proof
@@ -2613,12 +2949,13 @@ int run_ticket(AsyncJob& j, int lane, std::string* err) {
         ml[i] = j.msgs[i].size();
       }
       const HostMulti b{j.pks.data(), j.wires, j.pub_inputs, j.num_inputs, j.has_msgs ? mp.data() : nullptr,
-                        j.has_msgs ? ml.data() : nullptr, j.blinders, j.input_form, j.proofs_out, j.n, j.homes.data()};
+                        j.has_msgs ? ml.data() : nullptr, j.blinders, j.input_form, j.proofs_out, j.n, j.homes.data(),
+                        j.stride};
       rc = host_multi_part(b, 0, j.count);
     } else {
       const std::vector<uint8_t>& m = j.msgs[0];
       const HostBatch b{j.pks[0], j.wires, j.pub_inputs, j.num_inputs, m.empty() ? nullptr : m.data(), m.size(),
-                        j.blinders, j.input_form, j.proofs_out, j.n, &j.homes[0]};
+                        j.blinders, j.input_form, j.proofs_out, j.n, &j.homes[0], j.stride};
       rc = host_batch_part(b, 0, j.count);
     }
     if (rc) *err = last_error();
@@ -2704,6 +3041,7 @@ int capgpu_plonk_prove_batch_async(uint64_t pk_handle, int count, const uint64_t
     set_error("capgpu_plonk_prove: %zu public inputs given, key expects %zu", num_inputs, j.homes[0]->num_inputs);
     return CAPGPU_ERR_INVALID_ARG;
   }
+  if ((rc = input_stride(&pk_handle, 1, input_form, j.homes[0]->n, &j.stride))) return rc;
   if (async_refused_by_sharding()) return CAPGPU_ERR_INVALID_ARG;
   j.count = count;
   j.pks.assign(1, pk_handle);
@@ -2755,6 +3093,7 @@ int capgpu_plonk_prove_multi_async(const uint64_t* pk_handles, int count, const 
     set_error("capgpu_plonk_prove_multi: rows of %zu public inputs given, the keys need %zu", num_inputs, max_ni);
     return CAPGPU_ERR_INVALID_ARG;
   }
+  if ((rc = input_stride(pk_handles, count, input_form, j.homes[0]->n, &j.stride))) return rc;
   if (async_refused_by_sharding()) return CAPGPU_ERR_INVALID_ARG;
   j.multi = true;
   j.count = count;
@@ -2817,6 +3156,7 @@ int capgpu_plonk_reserve(uint64_t pk_handle, int count, int input_form, int slot
   std::shared_ptr<ProvingKey> K0;
   int rc = home_key(pk_handle, &K0);
   if (rc) return rc;
+  if (input_form == CAPGPU_INPUT_VARS && key_lacks_table(*K0)) return CAPGPU_ERR_INVALID_ARG;
   if (count == 0) return CAPGPU_OK;
   struct ScaleOne {  // exact sizes: a growth scale the thread carries (gathered batches) does not apply
     double saved = scratch_growth_scale();
@@ -2873,11 +3213,15 @@ static void run_coalesced(std::vector<ProveReq*>& reqs) {
   auto prove_one = [&](ProveReq* r) {
     std::shared_ptr<ProvingKey> K;
     int rc = lookup_key(r->pk, &K);
-    if (rc == CAPGPU_OK) rc = scratch_reserve(c.stage_b, sizeof(fe) * NW * K->n);
+    const bool rv = r->form == CAPGPU_INPUT_VARS;
+    if (rc == CAPGPU_OK && rv && key_lacks_table(*K)) rc = CAPGPU_ERR_INVALID_ARG;
+    if (rc == CAPGPU_OK)
+      rc = scratch_reserve(c.stage_b, rv ? vars_stage_bytes(1, K->n, K->num_vars, true) : wires_stage_bytes(1, K->n));
     if (rc == CAPGPU_OK) {
       const uint64_t* row = r->wires;
+      const VarsIn vin{(const fe*)c.stage_b.p + (size_t)NW * K->n, K->num_vars};
       rc = prove_batch(*K, 1, (const fe*)c.stage_b.p, r->pubs, r->num_inputs, r->msg, r->msg_len, r->blinders, r->out,
-                       nullptr, nullptr, nullptr, &row, r->form);
+                       nullptr, nullptr, nullptr, &row, r->form, rv ? &vin : nullptr);
     }
     r->rc = rc;
     if (rc) r->err = capgpu_last_error();
@@ -2891,6 +3235,7 @@ static void run_coalesced(std::vector<ProveReq*>& reqs) {
       set_error("capgpu_plonk_prove: %zu public inputs given, key expects %zu", r->num_inputs, K->num_inputs);
       rc = CAPGPU_ERR_INVALID_ARG;
     }
+    if (rc == CAPGPU_OK && r->form == CAPGPU_INPUT_VARS && key_lacks_table(*K)) rc = CAPGPU_ERR_INVALID_ARG;
     if (rc != CAPGPU_OK) {
       r->rc = rc;
       r->err = capgpu_last_error();
@@ -2921,7 +3266,12 @@ static void run_coalesced(std::vector<ProveReq*>& reqs) {
     coalescer().proofs += g;
     return;
   }
-  const size_t per = sizeof(fe) * NW * n;
+  // variable form: rows of the largest num_vars among the batch's keys, staged behind the columns they are gathered into
+  const bool vars = good[0]->form == CAPGPU_INPUT_VARS;
+  size_t vstride = 0;
+  for (size_t i = 0; i < g && vars; i++) vstride = std::max(vstride, hold[i]->num_vars);
+  const size_t per = vars ? sizeof(fe) * vstride : sizeof(fe) * NW * n;
+  auto own_bytes = [&](size_t i) { return vars ? sizeof(fe) * hold[i]->num_vars : per; };  // what request i brings
   // gathered batches differ in size from one to the next: scratch that has to grow for one grows to the next multiple of
   // 32 proofs (64 at least) at once - a context otherwise re-allocates gigabytes (0.1 - 0.6 s each time) whenever a batch
   // is a few proofs larger than every batch it has seen (round 6: it cost the bench's coalesced leg a third)
@@ -2930,8 +3280,9 @@ static void run_coalesced(std::vector<ProveReq*>& reqs) {
     explicit GrowthScale(double f) : prev(scratch_growth_scale()) { scratch_growth_scale() = f; }
     ~GrowthScale() { scratch_growth_scale() = prev; }
   } growth((double)std::max<size_t>(64, (g + 31) / 32 * 32) / (double)g);
-  int rc = scratch_reserve(c.stage_b, per * g);
+  int rc = scratch_reserve(c.stage_b, vars ? vars_stage_bytes(g, n, vstride, true) : per * g);
   if (rc) return fail_all(rc);
+  char* const in_base = (char*)c.stage_b.p + (vars ? wires_stage_bytes(g, n) : 0);  // (g: the batch as it arrived)
   // capgpu_plonk_set_precheck: every witness of the gathered batch is checked where it will be proved from; a request
   // whose witness does not satisfy its circuit gets its own CAPGPU_ERR_PROOF and fault text, the others close ranks in
   // the input array and are proved as ONE batch - no request-by-request re-run, whoever shares the batch.
@@ -2940,12 +3291,13 @@ static void run_coalesced(std::vector<ProveReq*>& reqs) {
   auto gather_all = [&]() -> hipError_t {
     hipError_t e = hipSuccess;
     for (size_t i = 0; i < g && e == hipSuccess; i++) {
-      char* dst = (char*)c.stage_b.p + per * i;
+      char* dst = in_base + per * i;
       if (good[i]->d_wires) {
         e = hipStreamWaitEvent(c.stream, good[i]->staged, 0);
-        if (e == hipSuccess) e = hipMemcpyAsync(dst, good[i]->d_wires, per, hipMemcpyDeviceToDevice, c.stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(dst, good[i]->d_wires, own_bytes(i), hipMemcpyDeviceToDevice, c.stream);
       } else {
-        e = hipMemcpyAsync(dst, good[i]->wires, per, hipMemcpyHostToDevice, c.stream);
+        e = hipMemcpyAsync(dst, good[i]->wires, own_bytes(i), hipMemcpyHostToDevice, c.stream);
+        count_witness_h2d(own_bytes(i));
       }
     }
     return e;
@@ -2961,8 +3313,11 @@ static void run_coalesced(std::vector<ProveReq*>& reqs) {
       ks[i] = hold[i].get();
     }
     std::vector<capgpu_witness_fault> faults(g);
-    rc = check_resident(*ks[0], mixed ? &ks : nullptr, (uint32_t)g, (const fe*)c.stage_b.p, rows.data(), ni, good[0]->form,
-                        faults.data());
+    if (vars)
+      gather_vars(c.stream, *ks[0], mixed ? &ks : nullptr, 0, (uint32_t)g, VarsIn{(const fe*)in_base, vstride},
+                  (fe*)c.stage_b.p);
+    rc = check_resident(*ks[0], mixed ? &ks : nullptr, (uint32_t)g, (const fe*)c.stage_b.p, rows.data(), ni,
+                        vars ? CAPGPU_INPUT_EVALS : good[0]->form, faults.data(), vars);
     if (rc) return fail_all(rc);
     size_t k = 0;
     for (size_t i = 0; i < g && e == hipSuccess; i++) {
@@ -2973,7 +3328,7 @@ static void run_coalesced(std::vector<ProveReq*>& reqs) {
         continue;
       }
       if (k != i) {  // (row k < i has been read or dropped: the copies run in stream order)
-        e = hipMemcpyAsync((char*)c.stage_b.p + per * k, (char*)c.stage_b.p + per * i, per, hipMemcpyDeviceToDevice, c.stream);
+        e = hipMemcpyAsync(in_base + per * k, in_base + per * i, per, hipMemcpyDeviceToDevice, c.stream);
         good[k] = good[i];
         hold[k] = hold[i];
       }
@@ -3013,8 +3368,10 @@ static void run_coalesced(std::vector<ProveReq*>& reqs) {
     resident = true;
   }
   tl_prechecked = prechecked;
+  const VarsIn vin{(const fe*)in_base, vstride};
   rc = prove_batch(*keys[0], (uint32_t)g, (const fe*)c.stage_b.p, pubs.data(), ni, nullptr, 0, blind.data(), out.data(),
-                   msgs.data(), lens.data(), mixed ? &keys : nullptr, resident ? nullptr : rows.data(), good[0]->form);
+                   msgs.data(), lens.data(), mixed ? &keys : nullptr, resident ? nullptr : rows.data(), good[0]->form,
+                   vars ? &vin : nullptr);
   tl_prechecked = false;
   if (rc == CAPGPU_OK) rc = take_launch_error();
   if (rc == CAPGPU_OK) {
@@ -3044,13 +3401,18 @@ int capgpu_plonk_prove_ex(uint64_t pk_handle, const uint64_t* wires, const uint6
     set_error("capgpu_plonk_prove: bad argument");
     return CAPGPU_ERR_INVALID_ARG;
   }
+  size_t var_elems = 0;  // variable form: the values this call brings (and the refusal of a key without a table)
+  if (input_form == CAPGPU_INPUT_VARS) {
+    int rc = input_stride(&pk_handle, 1, input_form, 0, &var_elems);
+    if (rc) return rc;
+  }
   ProveReq req{pk_handle, wires, pub_inputs, num_inputs, ext_msg, ext_msg_len, blinders, proof_out, input_form};
   std::unique_lock<std::mutex> lk(co.mu);
   uint64_t group = 0;
   size_t key_n = 0;
   {
-    // (key, form) -> group: bit 7 of the group id is the input form, the bits below it the domain size
-    const uint64_t gkey = (pk_handle << 1) | (uint64_t)(input_form == CAPGPU_INPUT_COEFFS);
+    // (key, form) -> group: bits 6-7 of the group id are the input form, the bits below them the domain size
+    const uint64_t gkey = (pk_handle << 2) | (uint64_t)input_form;
     auto it = co.group_of.find(gkey);
     if (it == co.group_of.end()) {
       // first call for this key: its domain size and SRS make the group
@@ -3061,7 +3423,7 @@ int capgpu_plonk_prove_ex(uint64_t pk_handle, const uint64_t* wires, const uint6
       if (rc) return rc;
       lk.lock();
       group = (ksrs << 8) ^ (uint64_t)__builtin_ctzll(kn | (1ull << 63)) ^
-              ((uint64_t)(input_form == CAPGPU_INPUT_COEFFS) << 7);
+              ((uint64_t)input_form << 6);
       co.group_of[gkey] = {group, kn};
       key_n = kn;
     } else {
@@ -3079,10 +3441,11 @@ int capgpu_plonk_prove_ex(uint64_t pk_handle, const uint64_t* wires, const uint6
       co.arriving++;  // (a leader's window stays open for callers that are on their way)
       lk.unlock();
       const int dev = ctx().device;
-      const size_t per = sizeof(fe) * NW * key_n;
+      const size_t per = input_form == CAPGPU_INPUT_VARS ? sizeof(fe) * var_elems : sizeof(fe) * NW * key_n;
       slot = stage_pool().acquire(dev, per);
       if (slot.d) {
         hipError_t e = hipMemcpyAsync(slot.d, wires, per, hipMemcpyHostToDevice, slot.stream);
+        if (e == hipSuccess) count_witness_h2d(per);
         if (e == hipSuccess) e = hipEventRecord(slot.ev, slot.stream);
         if (e != hipSuccess) {  // not fatal: the witness travels with the batch instead
           (void)hipGetLastError();
@@ -3177,7 +3540,7 @@ int capgpu_plonk_prove(uint64_t pk_handle, const uint64_t* wires, const uint64_t
 // (d_wires), keys per proof (pk_handles) or one for all.
 static int check_part(const uint64_t* pk_handles, uint64_t pk_handle, uint32_t cnt, const uint64_t* h_wires,
                       const void* d_wires, const uint64_t* pubs, size_t num_inputs, int form,
-                      capgpu_witness_fault* faults) {
+                      capgpu_witness_fault* faults, size_t stride) {
   Context& c = ctx();
   Entry lk(c);
   std::vector<std::shared_ptr<ProvingKey>> hold(pk_handles ? cnt : 1);
@@ -3192,9 +3555,27 @@ static int check_part(const uint64_t* pk_handles, uint64_t pk_handle, uint32_t c
     }
   }
   const size_t n = keys[0]->n;
+  if (form == CAPGPU_INPUT_VARS) {
+    // rows of `stride` values per witness -> the five columns, in staging; then the gate pass alone: gathered columns
+    // satisfy every copy constraint
+    for (const ProvingKey* k : keys)
+      if (key_lacks_table(*k)) return CAPGPU_ERR_INVALID_ARG;
+    if ((rc = scratch_reserve(c.stage_b, vars_stage_bytes((size_t)cnt, n, stride, h_wires != nullptr)))) return rc;
+    if (h_wires) {
+      fe* d_vars = (fe*)c.stage_b.p + (size_t)cnt * NW * n;
+      CAP_HIP(hipMemcpyAsync(d_vars, h_wires, sizeof(fe) * (size_t)cnt * stride, hipMemcpyHostToDevice, c.stream));
+      count_witness_h2d(sizeof(fe) * (size_t)cnt * stride);
+      d_wires = d_vars;
+    }
+    gather_vars(c.stream, *keys[0], pk_handles ? &keys : nullptr, 0, cnt, VarsIn{(const fe*)d_wires, stride},
+                (fe*)c.stage_b.p);
+    return check_resident(*keys[0], pk_handles ? &keys : nullptr, cnt, (const fe*)c.stage_b.p, pubs, num_inputs,
+                          CAPGPU_INPUT_EVALS, faults, true);
+  }
   if (h_wires) {
     if ((rc = scratch_reserve(c.stage_b, wires_stage_bytes((size_t)cnt, n)))) return rc;
     CAP_HIP(hipMemcpyAsync(c.stage_b.p, h_wires, sizeof(fe) * (size_t)cnt * NW * n, hipMemcpyHostToDevice, c.stream));
+    count_witness_h2d(sizeof(fe) * (size_t)cnt * NW * n);
     d_wires = c.stage_b.p;
   }
   return check_resident(*keys[0], pk_handles ? &keys : nullptr, cnt, (const fe*)d_wires, pubs, num_inputs, form, faults);
@@ -3216,7 +3597,10 @@ int capgpu_plonk_check_witness_batch_dev(uint64_t pk_handle, int count, const vo
     set_error("capgpu_plonk_check_witness: %zu public inputs given, key expects %zu", num_inputs, K0->num_inputs);
     return CAPGPU_ERR_INVALID_ARG;
   }
-  return check_part(nullptr, pk_handle, (uint32_t)count, nullptr, d_wires, pub_inputs, num_inputs, input_form, faults_out);
+  size_t stride = 0;
+  if ((rc = input_stride(&pk_handle, 1, input_form, K0->n, &stride))) return rc;
+  return check_part(nullptr, pk_handle, (uint32_t)count, nullptr, d_wires, pub_inputs, num_inputs, input_form, faults_out,
+                    stride);
 }
 
 int capgpu_plonk_check_witness_batch(uint64_t pk_handle, int count, const uint64_t* wires, const uint64_t* pub_inputs,
@@ -3235,11 +3619,12 @@ int capgpu_plonk_check_witness_batch(uint64_t pk_handle, int count, const uint64
     set_error("capgpu_plonk_check_witness: %zu public inputs given, key expects %zu", num_inputs, K0->num_inputs);
     return CAPGPU_ERR_INVALID_ARG;
   }
-  const size_t n = K0->n;
+  size_t stride = 0;
+  if ((rc0 = input_stride(&pk_handle, 1, input_form, K0->n, &stride))) return rc0;
   return deal(count, [&](int first, int cnt) -> int {
-    return check_part(nullptr, pk_handle, (uint32_t)cnt, wires + (size_t)4 * first * NW * n, nullptr,
+    return check_part(nullptr, pk_handle, (uint32_t)cnt, wires + (size_t)4 * first * stride, nullptr,
                       pub_inputs ? pub_inputs + (size_t)4 * first * num_inputs : nullptr, num_inputs, input_form,
-                      faults_out + first);
+                      faults_out + first, stride);
   });
 }
 
@@ -3274,10 +3659,12 @@ int capgpu_plonk_check_witness_multi(const uint64_t* pk_handles, int count, cons
     set_error("capgpu_plonk_check_witness_multi: rows of %zu public inputs given, the keys need %zu", num_inputs, max_ni);
     return CAPGPU_ERR_INVALID_ARG;
   }
+  size_t stride = 0;
+  if (int rc = input_stride(pk_handles, count, input_form, n, &stride)) return rc;
   return deal(count, [&](int first, int cnt) -> int {
-    return check_part(pk_handles + first, 0, (uint32_t)cnt, wires + (size_t)4 * first * NW * n, nullptr,
+    return check_part(pk_handles + first, 0, (uint32_t)cnt, wires + (size_t)4 * first * stride, nullptr,
                       pub_inputs ? pub_inputs + (size_t)4 * first * num_inputs : nullptr, num_inputs, input_form,
-                      faults_out + first);
+                      faults_out + first, stride);
   });
 }
 

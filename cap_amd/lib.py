@@ -520,14 +520,24 @@ def profile_stats() -> dict:
 
 
 # ---- PLONK ---------------------------------------------------------------------------------------
-INPUT_EVALS, INPUT_COEFFS = 0, 1  # CAPGPU_INPUT_* of include/capgpu.h
+INPUT_EVALS, INPUT_COEFFS, INPUT_VARS = 0, 1, 2  # CAPGPU_INPUT_* of include/capgpu.h
 
 
 def _form(input_form) -> int:
-    """'evals' / 'coeffs' / 0 / 1 -> the ABI's input_form integer (anything else is passed on for the library to refuse)"""
+    """'evals' / 'coeffs' / 'vars' / 0 / 1 / 2 -> the ABI's input_form integer (anything else is passed on for the
+    library to refuse)"""
     if isinstance(input_form, str):
-        return {"evals": INPUT_EVALS, "coeffs": INPUT_COEFFS}[input_form]
+        return {"evals": INPUT_EVALS, "coeffs": INPUT_COEFFS, "vars": INPUT_VARS}[input_form]
     return int(input_form)
+
+
+def _wires_per_proof(pk_handles, n: int, input_form) -> int | None:
+    """field elements of `wires` per proof: 5 n, or - variable form - the largest num_vars among the keys.  None: a key
+    without a table was asked for the variable form; the library refuses the call itself."""
+    if _form(input_form) != INPUT_VARS:
+        return NUM_WIRE_TYPES * n
+    nv = [_cached_num_vars(h) for h in set(pk_handles)]
+    return None if 0 in nv else max(nv)
 
 
 def plonk_preprocess(srs_handle: int, n: int, num_inputs: int, selectors: np.ndarray, sigma_evals: np.ndarray,
@@ -546,6 +556,70 @@ def plonk_preprocess(srs_handle: int, n: int, num_inputs: int, selectors: np.nda
     return h.value, vk
 
 
+def plonk_preprocess_vars(srs_handle: int, n: int, num_inputs: int, selectors: np.ndarray, wire_vars: np.ndarray,
+                          num_vars: int, selector_form=INPUT_EVALS):
+    """capgpu_plonk_preprocess_vars: selectors (13, n, 4) in selector_form, wire_vars (5, n) ids below num_vars - the
+    circuit's wire -> variable table; the permutation is built on the device -> (pk handle, VerifyingKey).  The key keeps
+    the table and proves from input_form='vars'."""
+    selectors = np.ascontiguousarray(selectors, dtype=np.uint64)
+    wire_vars = np.asarray(wire_vars)
+    if wire_vars.size and (wire_vars.min() < 0 or wire_vars.max() > 0xFFFFFFFF):
+        raise CapGpuError(-1, "wire_vars ids must fit 32 bits")
+    wire_vars = np.ascontiguousarray(wire_vars, dtype=np.uint32)
+    assert selectors.size == NUM_SELECTORS * n * 4 and wire_vars.size == NUM_WIRE_TYPES * n
+    h = ctypes.c_uint64()
+    vk = VerifyingKey()
+    check(load().capgpu_plonk_preprocess_vars(ctypes.c_uint64(srs_handle), ctypes.c_size_t(n),
+                                              ctypes.c_size_t(num_inputs), _p(selectors.reshape(-1)),
+                                              ctypes.c_int(_form(selector_form)),
+                                              wire_vars.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                              ctypes.c_size_t(num_vars), ctypes.byref(h), ctypes.byref(vk)))
+    return h.value, vk
+
+
+def plonk_key_set_vars(pk_handle: int, wire_vars: np.ndarray, num_vars: int):
+    """capgpu_plonk_key_set_vars: attach the wire -> variable table (5, n) to a key made without one; refused (-1) when
+    the permutation it implies is not the key's."""
+    n = plonk_key_info(pk_handle)[0]
+    wire_vars = np.asarray(wire_vars)
+    if wire_vars.size and (wire_vars.min() < 0 or wire_vars.max() > 0xFFFFFFFF):
+        raise CapGpuError(-1, "wire_vars ids must fit 32 bits")
+    wire_vars = np.ascontiguousarray(wire_vars, dtype=np.uint32)
+    if wire_vars.size != NUM_WIRE_TYPES * n:
+        raise CapGpuError(-1, f"wire_vars holds {wire_vars.size} ids, key (n = {n}) needs 5 * n")
+    _num_vars_of.pop(pk_handle, None)
+    check(load().capgpu_plonk_key_set_vars(ctypes.c_uint64(pk_handle),
+                                           wire_vars.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                           ctypes.c_size_t(num_vars)))
+
+
+_num_vars_of = {}  # pk handle -> num_vars of its table, for the shape checks of variable-form calls (handles are never
+                   # reused; plonk_key_set_vars and plonk_free_key drop the entry; keys without a table are not cached)
+
+
+def plonk_key_num_vars(pk_handle: int) -> int:
+    """length of an input_form='vars' witness under this key; 0: the key has no variable table"""
+    nv = ctypes.c_size_t(0)
+    check(load().capgpu_plonk_key_num_vars(ctypes.c_uint64(pk_handle), ctypes.byref(nv)))
+    return nv.value
+
+
+def _cached_num_vars(pk_handle: int) -> int:
+    nv = _num_vars_of.get(pk_handle)
+    if nv is None:
+        nv = plonk_key_num_vars(pk_handle)
+        if nv:
+            _num_vars_of[pk_handle] = nv
+    return nv
+
+
+def plonk_input_stats() -> dict:
+    """bytes of witness input copied host -> device by prove and check calls, and launches of the variable form's gather"""
+    b, g = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    check(load().capgpu_plonk_input_stats(ctypes.byref(b), ctypes.byref(g)))
+    return {"witness_bytes_h2d": b.value, "gather_launches": g.value}
+
+
 def plonk_key_info(pk_handle: int):
     """-> (domain size n, number of public inputs, SRS handle) of a resident proving key."""
     n, ni, srs = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_uint64(0)
@@ -553,15 +627,18 @@ def plonk_key_info(pk_handle: int):
     return n.value, ni.value, srs.value
 
 
-def _check_prove_shapes(pk_handle: int, count: int, wires_elems, pub_inputs: np.ndarray, blinders: np.ndarray) -> int:
+def _check_prove_shapes(pk_handle: int, count: int, wires_elems, pub_inputs: np.ndarray, blinders: np.ndarray,
+                        input_form=INPUT_EVALS) -> int:
     """The C ABI takes bare pointers: a mis-shaped array would be read out of bounds.  Every size is checked against
-    the key here (wires: count * 5 * n elements, pub_inputs: count * num_inputs, blinders: count * 13)."""
+    the key here (wires: count * 5 * n elements - variable form: count * num_vars -, pub_inputs: count * num_inputs,
+    blinders: count * 13)."""
     n, num_inputs, _ = plonk_key_info(pk_handle)
     if count < 1:
         raise CapGpuError(-1, f"count must be >= 1, got {count}")
-    if wires_elems != count * NUM_WIRE_TYPES * n:
-        raise CapGpuError(-1, f"wires hold {wires_elems} field elements, key (n = {n}) needs count * 5 * n = "
-                              f"{count * NUM_WIRE_TYPES * n}")
+    per = _wires_per_proof([pk_handle], n, input_form)
+    if per is not None and wires_elems != count * per:
+        raise CapGpuError(-1, f"wires hold {wires_elems} field elements, key (n = {n}) needs count * "
+                              f"{'num_vars' if _form(input_form) == INPUT_VARS else '5 * n'} = {count * per}")
     if blinders.size != count * 13 * 4:
         raise CapGpuError(-1, f"blinders hold {blinders.size // 4} field elements, need count * 13 = {count * 13}")
     if pub_inputs.size % 4 or pub_inputs.size != count * num_inputs * 4:
@@ -571,6 +648,7 @@ def _check_prove_shapes(pk_handle: int, count: int, wires_elems, pub_inputs: np.
 
 
 def plonk_free_key(pk_handle: int):
+    _num_vars_of.pop(pk_handle, None)
     check(load().capgpu_plonk_free_key(ctypes.c_uint64(pk_handle)))
 
 
@@ -584,12 +662,13 @@ def _bytes_arg(b):
 def plonk_prove_batch(pk_handle: int, wires: np.ndarray, pub_inputs: np.ndarray, blinders: np.ndarray,
                       ext_msg: bytes | None = None, count: int = 1, input_form=INPUT_EVALS):
     """wires (count, 5, n, 4), pub_inputs (count, l, 4), blinders (count, 13, 4), all Montgomery.  input_form =
-    'coeffs': wires are the unblinded wire polynomials in coefficient form."""
+    'coeffs': wires are the unblinded wire polynomials in coefficient form; 'vars': wires is (count, num_vars, 4), the
+    value of every variable (a key with a table: plonk_preprocess_vars / plonk_key_set_vars)."""
     wires = np.ascontiguousarray(wires, dtype=np.uint64)
     pub_inputs = np.ascontiguousarray(pub_inputs, dtype=np.uint64).reshape(-1)
     blinders = np.ascontiguousarray(blinders, dtype=np.uint64).reshape(-1)
     num_inputs = _check_prove_shapes(pk_handle, count, wires.size // 4 if wires.size % 4 == 0 else -1, pub_inputs,
-                                     blinders)
+                                     blinders, input_form)
     proofs = (Proof * count)()
     mbuf, mlen = _bytes_arg(ext_msg)
     pub_ptr = _p(pub_inputs) if pub_inputs.size else None
@@ -606,7 +685,8 @@ def plonk_prove(pk_handle: int, wires: np.ndarray, pub_inputs: np.ndarray, blind
     wires = np.ascontiguousarray(wires, dtype=np.uint64)
     pub_inputs = np.ascontiguousarray(pub_inputs, dtype=np.uint64).reshape(-1)
     blinders = np.ascontiguousarray(blinders, dtype=np.uint64).reshape(-1)
-    num_inputs = _check_prove_shapes(pk_handle, 1, wires.size // 4 if wires.size % 4 == 0 else -1, pub_inputs, blinders)
+    num_inputs = _check_prove_shapes(pk_handle, 1, wires.size // 4 if wires.size % 4 == 0 else -1, pub_inputs, blinders,
+                                     input_form)
     proof = Proof()
     mbuf, mlen = _bytes_arg(ext_msg)
     check(load().capgpu_plonk_prove_ex(ctypes.c_uint64(pk_handle), _p(wires.reshape(-1)),
@@ -653,7 +733,8 @@ class WitnessFault(ctypes.Structure):
 
 def plonk_check_witness_batch(pk_handle, wires, pub_inputs: np.ndarray, count: int = 1, input_form=INPUT_EVALS) -> list:
     """One WitnessFault per witness: gates and copy constraints checked on the device before anything is proved.
-    wires: (count, 5, n, 4) numpy array (host: the batch is dealt over the contexts) or a DevBuf of that content;
+    wires: (count, 5, n, 4) numpy array (host: the batch is dealt over the contexts) or a DevBuf of that content -
+    input_form='vars': (count, num_vars, 4), one value per variable, gathered on the device; only gates can then fail;
     pk_handle: one key, or a list of `count` keys of one domain (capgpu_plonk_check_witness_multi; pub_inputs then has
     rows of the largest public-input count)."""
     pub_inputs = np.ascontiguousarray(pub_inputs, dtype=np.uint64).reshape(-1)
@@ -665,9 +746,10 @@ def plonk_check_witness_batch(pk_handle, wires, pub_inputs: np.ndarray, count: i
     if count < 1:
         raise CapGpuError(-1, f"count must be >= 1, got {count}")
     elems = wires.nbytes // 32 if isinstance(wires, DevBuf) else np.asarray(wires).size // 4
-    if elems != count * NUM_WIRE_TYPES * n:
-        raise CapGpuError(-1, f"wires hold {elems} field elements, key (n = {n}) needs count * 5 * n = "
-                              f"{count * NUM_WIRE_TYPES * n}")
+    per = _wires_per_proof(pk_handle if multi else [pk_handle], n, input_form)
+    if per is not None and elems != count * per:
+        raise CapGpuError(-1, f"wires hold {elems} field elements, key (n = {n}) needs count * "
+                              f"{'num_vars' if _form(input_form) == INPUT_VARS else '5 * n'} = {count * per}")
     if pub_inputs.size != count * num_inputs * 4:
         raise CapGpuError(-1, f"pub_inputs hold {pub_inputs.size / 4:g} field elements, need count * {num_inputs}")
     faults = (WitnessFault * count)()
@@ -757,7 +839,7 @@ def plonk_prove_batch_dev(pk_handle: int, d_wires: DevBuf, pub_inputs: np.ndarra
     pub_inputs = np.ascontiguousarray(pub_inputs, dtype=np.uint64).reshape(-1)
     blinders = np.ascontiguousarray(blinders, dtype=np.uint64).reshape(-1)
     num_inputs = _check_prove_shapes(pk_handle, count, d_wires.nbytes // 32 if d_wires.nbytes % 32 == 0 else -1,
-                                     pub_inputs, blinders)
+                                     pub_inputs, blinders, input_form)
     proofs = (Proof * count)()
     mbuf, mlen = _bytes_arg(ext_msg)
     pub_ptr = _p(pub_inputs) if pub_inputs.size else None
@@ -796,16 +878,17 @@ def plonk_prove_multi(pk_handles, wires, pub_rows: np.ndarray, blinders: np.ndar
             lens_arg[i] = len(keep[-1])
     proofs = (Proof * count)()
     pub_ptr = _p(pub_rows) if pub_rows.size else None
+    per = _wires_per_proof(pk_handles, n, input_form)  # variable form: rows of the largest num_vars among the keys
     if isinstance(wires, DevBuf):
-        if wires.nbytes != count * NUM_WIRE_TYPES * n * 32:
-            raise ValueError("plonk_prove_multi: the wire buffer does not hold count x 5 x n elements")
+        if per is not None and wires.nbytes != count * per * 32:
+            raise ValueError("plonk_prove_multi: the wire buffer does not hold count x 5 x n elements (count x num_vars)")
         check(load().capgpu_plonk_prove_multi_dev_ex(handles, count, wires.ptr, pub_ptr, ctypes.c_size_t(max_in),
                                                      msgs_arg, lens_arg, _p(blinders), ctypes.c_int(_form(input_form)),
                                                      proofs))
     else:
         wires = np.ascontiguousarray(wires, dtype=np.uint64).reshape(-1)
-        if wires.size != count * NUM_WIRE_TYPES * n * 4:
-            raise ValueError("plonk_prove_multi: wires must hold count x 5 x n elements")
+        if per is not None and wires.size != count * per * 4:
+            raise ValueError("plonk_prove_multi: wires must hold count x 5 x n elements (count x num_vars)")
         check(load().capgpu_plonk_prove_multi_ex(handles, count, _p(wires), pub_ptr, ctypes.c_size_t(max_in), msgs_arg,
                                                  lens_arg, _p(blinders), ctypes.c_int(_form(input_form)), proofs))
     return list(proofs)
@@ -859,7 +942,7 @@ def plonk_prove_batch_async(pk_handle: int, wires: np.ndarray, pub_inputs: np.nd
     pub_inputs = np.ascontiguousarray(pub_inputs, dtype=np.uint64).reshape(-1)
     blinders = np.ascontiguousarray(blinders, dtype=np.uint64).reshape(-1)
     num_inputs = _check_prove_shapes(pk_handle, count, wires.size // 4 if wires.size % 4 == 0 else -1, pub_inputs,
-                                     blinders)
+                                     blinders, input_form)
     proofs = (Proof * count)()
     mbuf, mlen = _bytes_arg(ext_msg)
     pub_ptr = _p(pub_inputs) if pub_inputs.size else None
@@ -883,8 +966,9 @@ def plonk_prove_multi_async(pk_handles, wires: np.ndarray, pub_rows: np.ndarray,
     wires = np.ascontiguousarray(wires, dtype=np.uint64).reshape(-1)
     if pub_rows.size != count * max_in * 4 or blinders.size != count * 13 * 4:
         raise ValueError(f"plonk_prove_multi_async: pub_rows must hold {count} x {max_in} and blinders {count} x 13 elements")
-    if wires.size != count * NUM_WIRE_TYPES * n * 4:
-        raise ValueError("plonk_prove_multi_async: wires must hold count x 5 x n elements")
+    per = _wires_per_proof(pk_handles, n, input_form)
+    if per is not None and wires.size != count * per * 4:
+        raise ValueError("plonk_prove_multi_async: wires must hold count x 5 x n elements (count x num_vars)")
     handles = (ctypes.c_uint64 * count)(*pk_handles)
     msgs_arg = lens_arg = None
     keep = []

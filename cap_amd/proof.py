@@ -157,9 +157,22 @@ def preprocess(srs: UniversalSrs, n: int, num_inputs: int, selectors: np.ndarray
     return ProvingKey(h, n, num_inputs, srs), VerifyingKey(vk, n, num_inputs, srs.h, srs.beta_h), n
 
 
+def preprocess_vars(srs: UniversalSrs, n: int, num_inputs: int, selectors: np.ndarray, wire_vars: np.ndarray, num_vars: int,
+                    selector_form="evals"):
+    """Key generation from the circuit's wire -> variable table (jf-relation's wire_variables[..5]: (5, n) ids below
+    num_vars) instead of sigma's values; the permutation is built on the device.  The key proves from
+    input_form='vars': one value per variable (PlonkCircuit::witness)."""
+    try:
+        h, vk = _lib.plonk_preprocess_vars(srs.handle, n, num_inputs, selectors, wire_vars, num_vars, selector_form)
+    except _lib.CapGpuError as e:
+        raise TxnApiError.FailedSnark(f"Preprocessing circuit of domain size {n} failed: {e}") from e
+    return ProvingKey(h, n, num_inputs, srs), VerifyingKey(vk, n, num_inputs, srs.h, srs.beta_h), n
+
+
 def prove(proving_key: ProvingKey, wires: np.ndarray, public_inputs: np.ndarray, blinders: np.ndarray,
           ext_msg: bytes | None = None, input_form="evals"):
-    """One proof.  wires (5, n, 4), public_inputs (l, 4), blinders (13, 4): Montgomery words."""
+    """One proof.  wires (5, n, 4) - input_form 'vars': (num_vars, 4), the value of every variable -, public_inputs
+    (l, 4), blinders (13, 4): Montgomery words."""
     return prove_batch(proving_key, np.asarray(wires)[None], np.asarray(public_inputs)[None],
                        np.asarray(blinders)[None], ext_msg, input_form)[0]
 
@@ -175,13 +188,15 @@ def prove_batch(proving_key: ProvingKey, wires: np.ndarray, public_inputs: np.nd
         raise TxnApiError.FailedSnark(f"Proof Creation failure: {e}") from e
 
 
-def prove_mixed(proving_keys, wires: np.ndarray, public_input_rows: np.ndarray, blinders: np.ndarray, ext_msgs=None):
+def prove_mixed(proving_keys, wires: np.ndarray, public_input_rows: np.ndarray, blinders: np.ndarray, ext_msgs=None,
+                input_form="evals"):
     """One proof per entry of `proving_keys` (keys of ONE domain size under ONE SRS, e.g. transfer 2x3 and freeze 3) in a
     single device batch - the device-side form of the reference proving its transfer / mint / freeze notes side by side
     (src/utils/params_builder.rs:194-226).  public_input_rows: (count, max inputs, 4); a key with fewer inputs uses the
     first of its row."""
     try:
-        return _lib.plonk_prove_multi([k.handle for k in proving_keys], wires, public_input_rows, blinders, ext_msgs)
+        return _lib.plonk_prove_multi([k.handle for k in proving_keys], wires, public_input_rows, blinders, ext_msgs,
+                                      input_form)
     except (_lib.CapGpuError, ValueError) as e:
         raise TxnApiError.FailedSnark(f"Proof Creation failure: {e}") from e
 

@@ -82,9 +82,16 @@ extern "C" {
  *                        freeze.rs:102/151).  The device then skips its own interpolation and runs one forward
  *                        transform where the permutation product needs the values; a Rust binding passes the trait's
  *                        output straight through instead of undoing its interpolation on the CPU.
- * Both forms give the same proof and the same keys, byte for byte. */
+ *   CAPGPU_INPUT_VARS    (witnesses only) one value per VARIABLE of the circuit - what a jf-relation `PlonkCircuit` holds
+ *                        (`witness: Vec<F>`); the five wire columns are that vector gathered through the circuit's wire ->
+ *                        variable table (`wire_variables`), which is fixed per circuit and therefore kept by the key
+ *                        (capgpu_plonk_preprocess_vars, capgpu_plonk_key_set_vars).  The gather runs on the device: a
+ *                        host-resident witness costs 32 B x num_vars on the link instead of 32 B x 5 n (0.66 MB instead
+ *                        of 5.24 MB for a 2-in-2-out transfer at n = 2^15); behind the gather the call is the evals form.
+ * All forms give the same proof and the same keys, byte for byte. */
 #define CAPGPU_INPUT_EVALS 0
 #define CAPGPU_INPUT_COEFFS 1
+#define CAPGPU_INPUT_VARS 2
 
 /* ---- lifecycle ------------------------------------------------------------------------- */
 /* Binds this process to the n_devices GPUs listed in device_ids (NULL / 0 selects HIP device 0): one device context
@@ -347,6 +354,28 @@ int capgpu_plonk_preprocess(uint64_t srs_handle, size_t n, size_t num_inputs, co
 int capgpu_plonk_preprocess_ex(uint64_t srs_handle, size_t n, size_t num_inputs, const uint64_t* selectors,
                                const uint64_t* sigmas, int input_form, uint64_t* pk_handle_out,
                                capgpu_verifying_key* vk_out);
+/* Key generation from the circuit's wire -> variable table instead of sigma's 5 n field elements: wire_vars is 5 columns
+ * of n ids, column-major like the wire columns (the first five of jf-relation's `wire_variables`), every id below num_vars
+ * (1 <= num_vars < 2^32; CAPGPU_ERR_INVALID_ARG naming the first offending (wire, row) otherwise; ids that occur in no cell
+ * are allowed, num_vars may exceed 5 n).  The extended permutation is built ON THE DEVICE by jf-relation's
+ * compute_wire_permutation rule - the cells c = wire * n + row of one variable form a cycle in ascending c, the last cell
+ * pointing to the first - from a sort of the unique keys (variable, cell): the result is a function of the table alone.
+ * selectors come in selector_form (CAPGPU_INPUT_EVALS / _COEFFS), as in capgpu_plonk_preprocess_ex.  The key, its vk and
+ * its capgpu_plonk_key_serialize bytes equal those of capgpu_plonk_preprocess fed the same permutation as sigma_evals.
+ * The key keeps the table (4 B x 5 n, device-resident, replicated to a context like the rest of the key) and the index form
+ * of the permutation, which the witness check would otherwise derive by one discrete logarithm per cell: it accepts
+ * CAPGPU_INPUT_VARS in every entry point that takes an input_form. */
+int capgpu_plonk_preprocess_vars(uint64_t srs_handle, size_t n, size_t num_inputs, const uint64_t* selectors,
+                                 int selector_form, const uint32_t* wire_vars, size_t num_vars, uint64_t* pk_handle_out,
+                                 capgpu_verifying_key* vk_out);
+/* Attaches a table to a key made another way - capgpu_plonk_preprocess[_ex], or capgpu_plonk_key_deserialize, whose blob
+ * has no place for it - after checking on the device that the permutation the table implies is the key's own, cell for
+ * cell: a mismatch is CAPGPU_ERR_INVALID_ARG naming the first differing cell and the key stays as it was.  A key that has
+ * a table already takes another one under the same check (ids may be renumbered, not regrouped).  Not to be called while
+ * other calls use the key. */
+int capgpu_plonk_key_set_vars(uint64_t pk_handle, const uint32_t* wire_vars, size_t num_vars);
+/* num_vars of the key's table: the length of a CAPGPU_INPUT_VARS witness; 0 when the key has no table */
+int capgpu_plonk_key_num_vars(uint64_t pk_handle, size_t* num_vars_out);
 int capgpu_plonk_free_key(uint64_t pk_handle);
 /* Shape of a resident proving key: the sizes every prove call's arrays must have (wires: count * 5 * domain_size
  * field elements, pub_inputs: count * num_inputs, blinders: count * 13) and the SRS it commits with.  Any out
@@ -465,6 +494,13 @@ int capgpu_plonk_prove_batch_dev(uint64_t pk_handle, int count, const void* d_wi
  * the 5 UNBLINDED wire polynomials of n coefficients (jf-relation's compute_wire_polynomials; the blinders are added on
  * the device as before).  Everything else - layouts, batching over contexts, coalescing (calls of different forms are
  * gathered separately), errors - is that of the entry point without _ex, which is the _ex one with CAPGPU_INPUT_EVALS. */
+/* CAPGPU_INPUT_VARS: `wires` holds, per proof, num_vars field elements (capgpu_plonk_key_num_vars; Montgomery) - the value
+ * of variable v at index v -, proofs consecutive; _multi takes rows of the LARGEST num_vars among the call's keys, a key
+ * with fewer variables using the first of its row, as pub_inputs rows work.  Host-resident input is staged as count *
+ * num_vars * 32 bytes through the chunks, part order and copy streams the wire columns take, and one gather per chunk
+ * (w[i][j] = vars[wire_vars[i][j]]) writes the columns where the evals form would have copied them; the _dev forms read a
+ * device buffer of count * num_vars elements and never write it.  A key without a table refuses the form before the
+ * device is touched (tickets: at submission): CAPGPU_ERR_INVALID_ARG, "key has no variable table". */
 int capgpu_plonk_prove_ex(uint64_t pk_handle, const uint64_t* wires, const uint64_t* pub_inputs, size_t num_inputs,
                           const uint8_t* ext_msg, size_t ext_msg_len, const uint64_t* blinders, int input_form,
                           capgpu_proof* proof_out);
@@ -569,6 +605,10 @@ typedef struct capgpu_witness_fault {
   uint64_t gates_failed, copies_failed;
 } capgpu_witness_fault;     /* 48 bytes */
 
+/* CAPGPU_INPUT_VARS: the values are gathered into columns (scratch) and only the gates are checked - a witness gathered
+ * through the key's table satisfies every copy constraint by construction: copies_failed is 0 and kind is never 2; the
+ * gate verdict is that of the expanded columns.  A key with a table needs no discrete logarithms for the other forms
+ * either: it has the permutation's index form from its table. */
 int capgpu_plonk_check_witness(uint64_t pk_handle, const uint64_t* wires, const uint64_t* pub_inputs, size_t num_inputs,
                                int input_form, capgpu_witness_fault* fault_out);
 int capgpu_plonk_check_witness_batch(uint64_t pk_handle, int count, const uint64_t* wires, const uint64_t* pub_inputs,
@@ -589,6 +629,10 @@ int capgpu_plonk_check_witness_multi(const uint64_t* pk_handles, int count, cons
  * Host-resident witnesses are then copied in one go instead of chunk by chunk under round 1.  Off (the default):
  * nothing changes.  Process-wide; takes effect with the next prove call. */
 int capgpu_plonk_set_precheck(int on);
+/* Counters since capgpu_init: bytes of witness input (wire columns, wire polynomials or variable values) that prove and
+ * check calls copied from host to device, and launches of the variable form's gather kernel.  _dev calls copy no witness.
+ * Either pointer may be NULL. */
+int capgpu_plonk_input_stats(uint64_t* witness_bytes_h2d_out, uint64_t* gather_launches_out);
 
 /* ---- verification (host only: needs neither a GPU nor capgpu_init) ---------------------------------------- */
 /* G2 elements: x.c0, x.c1, y.c0, y.c1 of the twist point (Fq2 = Fq[u]/(u^2+1)), Montgomery, 16 words;

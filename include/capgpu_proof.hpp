@@ -142,11 +142,24 @@ struct FinalisedCircuit {
   // jf-relation's Arithmetization trait returns (compute_selector_polynomials / compute_extended_permutation_polynomials),
   // n coefficients each, passed through untransformed
   int input_form = CAPGPU_INPUT_EVALS;
+  // Key generation from the circuit's wire -> variable table (PlonkCircuit::wire_variables[..5], 5 x n ids below
+  // num_vars, column-major) instead of `sigma`: the permutation is built on the device and the key keeps the table, so
+  // that prove() takes a VariableAssignment.  `input_form` is then the selectors' form alone.
+  const uint32_t* wire_vars = nullptr;
+  size_t num_vars = 0;
 };
 struct Assignment {
   const uint64_t* wires = nullptr;       // 5 x n x 4 words
   const uint64_t* pub_inputs = nullptr;  // num_inputs x 4 words  (PublicInput::to_scalars())
   int input_form = CAPGPU_INPUT_EVALS;   // CAPGPU_INPUT_COEFFS: wires = compute_wire_polynomials(), unblinded
+};
+// What a jf-relation PlonkCircuit holds after witness generation: one value per variable (`witness: Vec<F>`,
+// CAPGPU_INPUT_VARS).  For keys preprocessed from a FinalisedCircuit with wire_vars (or given the table by
+// capgpu_plonk_key_set_vars); the five columns are gathered on the device.
+struct VariableAssignment {
+  const uint64_t* values = nullptr;      // num_vars x 4 words
+  const uint64_t* pub_inputs = nullptr;  // num_inputs x 4 words
+  Assignment as_assignment() const { return Assignment{values, pub_inputs, CAPGPU_INPUT_VARS}; }
 };
 
 namespace proof {
@@ -261,11 +274,13 @@ inline Result<UniversalSrs> universal_setup_for_staging(size_t max_degree, Rng& 
 namespace detail_snark {
 inline Result<std::pair<ProvingKey, VerifyingKey>> preprocess(const UniversalSrs& srs, const FinalisedCircuit& c,
                                                               const std::string& what) {
-  if (!c.selectors || !c.sigma) return TxnApiError::failed_snark(what + ": circuit not finalised");
+  if (!c.selectors || (!c.sigma && !c.wire_vars)) return TxnApiError::failed_snark(what + ": circuit not finalised");
   ProvingKey pk;
   uint64_t h = 0;
-  int rc = capgpu_plonk_preprocess_ex(srs.handle(), c.domain_size, c.num_inputs, c.selectors, c.sigma, c.input_form, &h,
-                                      &pk.vk.raw);
+  int rc = c.wire_vars ? capgpu_plonk_preprocess_vars(srs.handle(), c.domain_size, c.num_inputs, c.selectors, c.input_form,
+                                                      c.wire_vars, c.num_vars, &h, &pk.vk.raw)
+                       : capgpu_plonk_preprocess_ex(srs.handle(), c.domain_size, c.num_inputs, c.selectors, c.sigma,
+                                                    c.input_form, &h, &pk.vk.raw);
   if (rc != CAPGPU_OK) return detail::map_error(rc, what);
   pk.key = std::make_shared<detail::KeyHandle>(h);
   pk.srs = srs;
@@ -476,6 +491,12 @@ Result<Proof> prove(Rng& rng, const TransferProvingKey& pk, const Assignment& wi
   const std::vector<uint8_t> ext_msg = detail_snark::bound_message(txn_memo_ver_key, extra_proof_bound_data);
   return detail_snark::prove(rng, pk.proving_key, witness, &ext_msg, "Transfer Proof Creation failure");
 }
+// the same from the circuit's variable assignment (a key whose circuit came with wire_vars)
+template <class Rng>
+Result<Proof> prove(Rng& rng, const TransferProvingKey& pk, const VariableAssignment& witness,
+                    const std::vector<uint8_t>& txn_memo_ver_key) {
+  return prove(rng, pk, witness.as_assignment(), txn_memo_ver_key);
+}
 // transfer.rs:192-212
 inline Result<Unit> verify(const TransferVerifyingKey& vk, const std::vector<Fr>& public_inputs, const Proof& proof,
                            const std::vector<uint8_t>& recv_memos_ver_key,
@@ -504,6 +525,11 @@ template <class Rng>
 Result<Proof> prove(Rng& rng, const MintProvingKey& pk, const Assignment& witness,
                     const std::vector<uint8_t>& txn_memo_ver_key) {
   return detail_snark::prove(rng, pk.proving_key, witness, &txn_memo_ver_key, "Mint Proof creation failure");
+}
+template <class Rng>
+Result<Proof> prove(Rng& rng, const MintProvingKey& pk, const VariableAssignment& witness,
+                    const std::vector<uint8_t>& txn_memo_ver_key) {
+  return prove(rng, pk, witness.as_assignment(), txn_memo_ver_key);
 }
 // mint.rs:124-140
 inline Result<Unit> verify(const MintVerifyingKey& vk, const std::vector<Fr>& public_inputs, const Proof& proof,
@@ -535,6 +561,11 @@ template <class Rng>
 Result<Proof> prove(Rng& rng, const FreezeProvingKey& pk, const Assignment& witness,
                     const std::vector<uint8_t>& txn_memo_ver_key) {
   return detail_snark::prove(rng, pk.proving_key, witness, &txn_memo_ver_key, "Freeze Proof creation failure");
+}
+template <class Rng>
+Result<Proof> prove(Rng& rng, const FreezeProvingKey& pk, const VariableAssignment& witness,
+                    const std::vector<uint8_t>& txn_memo_ver_key) {
+  return prove(rng, pk, witness.as_assignment(), txn_memo_ver_key);
 }
 // freeze.rs:162-178
 inline Result<Unit> verify(const FreezeVerifyingKey& vk, const std::vector<Fr>& public_inputs, const Proof& proof,
