@@ -142,6 +142,14 @@ extern "C" {
     pub fn capgpu_msm_shard_stats(scalar_bytes_out: *mut u64, partial_bytes_out: *mut u64, calls_out: *mut u64,
                                   replications_out: *mut u64) -> c_int;
     pub fn capgpu_msm_plan(srs_handle: u64, n: usize, count: c_int, buf: *mut c_char, cap: usize) -> c_int;
+    // ---- one-shot MSM over caller points (no handle, no table)
+    pub fn capgpu_msm_g1_var(bases: *const c_void, stride_bytes: usize, coords_montgomery: c_int, scalars: *const u64,
+                             n: usize, out_xyz: *mut u64) -> c_int;
+    pub fn capgpu_msm_g1_var_batch(bases: *const *const u64, scalars: *const *const u64, ns: *const usize, count: c_int,
+                                   out_xyz: *mut u64) -> c_int;
+    pub fn capgpu_msm_g1_var_dev(d_bases: *const c_void, d_scalars: *const c_void, scalar_stride: usize, n: usize,
+                                 count: c_int, scalars_montgomery: c_int, d_out_xyz: *mut c_void) -> c_int;
+    pub fn capgpu_msm_var_plan(n: usize, count: c_int, buf: *mut c_char, cap: usize) -> c_int;
     pub fn capgpu_g1_sum(points_xyz: *const u64, n: usize, out_xyz: *mut u64) -> c_int;
     // ---- one process per GPU: the RCCL exchange
     pub fn capgpu_comm_unique_id(id_out: *mut u8) -> c_int;
@@ -437,6 +445,18 @@ impl Drop for Srs {
     fn drop(&mut self) {
         unsafe { capgpu_srs_free(self.handle) };
     }
+}
+
+/// `VariableBaseMSM::multi_scalar_mul(bases, scalars)` for bases that were never uploaded: packed (x, y) pairs in
+/// arkworks' Montgomery words ((0, 0) = infinity), canonical scalars (`into_repr()`); the result is (X, Y, Z) of a
+/// `GroupProjective`.  Nothing stays on the device.  Bases that serve many MSMs belong in an [`Srs`] instead.
+pub fn multi_scalar_mul(bases: &[[u64; 8]], scalars: &[[u64; 4]]) -> Result<[u64; 12]> {
+    let n = bases.len().min(scalars.len()); // (as ark-ec: the shorter of the two)
+    let mut out = [0u64; 12];
+    check(unsafe {
+        capgpu_msm_g1_var(bases.as_ptr() as *const c_void, 64, 1, scalars.as_ptr() as *const u64, n, out.as_mut_ptr())
+    })?;
+    Ok(out)
 }
 
 /// `Radix2EvaluationDomain::{fft, ifft, coset_fft, coset_ifft}_in_place` on a `Vec<Fr>` viewed as words.

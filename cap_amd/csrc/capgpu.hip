@@ -1913,6 +1913,121 @@ int capgpu_msm_g1(uint64_t srs_handle, size_t offset, const uint64_t* scalars, s
   return capgpu_msm_g1_batch(srs_handle, &offset, sp, &n, 1, out_xyz);
 }
 
+// ---- one-shot MSM over caller points (msm.hpp: msm_var_run; no handle, no table) -----------------------------------
+int capgpu_msm_g1_var_dev(const void* d_bases, const void* d_scalars, size_t scalar_stride, size_t n, int count,
+                          int scalars_montgomery, void* d_out_xyz) {
+  if (count < 0 || (count && (!d_out_xyz || (n && (!d_bases || !d_scalars)))) || (count > 1 && scalar_stride < n) ||
+      n >= ((size_t)1 << 31)) {
+    set_error("capgpu_msm_g1_var_dev: bad argument (null pointer, count %d < 0, stride %zu < n %zu, or n >= 2^31)", count,
+              scalar_stride, n);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  CAP_CHECK_INIT();
+  if (count == 0) return CAPGPU_OK;
+  Context& c = ctx();
+  Entry lk(c);
+  const MsmVarPlan pl = msm_var_plan(n, n, (uint32_t)count);
+  int rc = scratch_reserve(c.msm_ws, pl.workspace_bytes);
+  if (rc) return rc;
+  rc = msm_var_run((const g1_affine*)d_bases, n, (const fe*)d_scalars, scalar_stride, nullptr, n, (uint32_t)count,
+                   scalars_montgomery, (g1_jac*)d_out_xyz, c.msm_ws.p, c.msm_ws.cap, c.stream);
+  if (rc) return hip_fail((hipError_t)rc, "msm_var_run");
+  return take_launch_error();
+}
+
+namespace {
+// `count` MSMs over their own host points and scalars: everything is packed into one staging buffer, uploaded, and run
+// as one pass of launches (msm_var_run with one descriptor per MSM)
+int msm_var_host(const unsigned char* const* bases, size_t stride_bytes, int coords_montgomery,
+                 const uint64_t* const* scalars, const size_t* ns, int count, uint64_t* out_xyz) {
+  size_t total = 0, n_max = 0;
+  for (int g = 0; g < count; g++) {
+    if (ns[g] && (!bases[g] || !scalars[g])) {
+      set_error("capgpu_msm_g1_var: null bases or scalars for an MSM of %zu points", ns[g]);
+      return CAPGPU_ERR_INVALID_ARG;
+    }
+    total += ns[g];
+    n_max = std::max(n_max, ns[g]);
+  }
+  if (total >= ((size_t)1 << 31)) {
+    set_error("capgpu_msm_g1_var: %zu points in one call (the limit is 2^31 - 1)", total);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  CAP_CHECK_INIT();
+  Context& c = ctx();
+  Entry lk(c);
+  const size_t slots = total ? total : 1;
+  const size_t off_sc = sizeof(g1_affine) * slots, off_desc = off_sc + sizeof(fe) * slots,
+               off_out = (off_desc + sizeof(MsmVarDesc) * (size_t)count + 255) / 256 * 256;
+  int rc = scratch_reserve(c.stage_a, off_out + sizeof(g1_jac) * (size_t)count);
+  if (rc) return rc;
+  char* d = (char*)c.stage_a.p;
+  std::vector<g1_affine> packed;  // only a 72-byte stride needs repacking on the host
+  std::vector<MsmVarDesc> desc((size_t)count);
+  if (stride_bytes != 64) packed.resize(slots);
+  size_t at = 0;
+  for (int g = 0; g < count; g++) {
+    desc[(size_t)g] = MsmVarDesc{(uint64_t)at, (uint32_t)at, (uint32_t)ns[g]};
+    if (ns[g] == 0) continue;
+    const void* src = bases[g];
+    if (stride_bytes != 64) {
+      for (size_t i = 0; i < ns[g]; i++) {
+        memcpy(&packed[at + i], bases[g] + i * stride_bytes, 64);
+        if (bases[g][i * stride_bytes + 64]) memset(&packed[at + i], 0, 64);  // infinity flag
+      }
+      src = &packed[at];
+    }
+    CAP_HIP(hipMemcpyAsync(d + sizeof(g1_affine) * at, src, sizeof(g1_affine) * ns[g], hipMemcpyHostToDevice, c.stream));
+    CAP_HIP(hipMemcpyAsync(d + off_sc + sizeof(fe) * at, scalars[g], sizeof(fe) * ns[g], hipMemcpyHostToDevice, c.stream));
+    at += ns[g];
+  }
+  CAP_HIP(hipMemcpyAsync(d + off_desc, desc.data(), sizeof(MsmVarDesc) * (size_t)count, hipMemcpyHostToDevice, c.stream));
+  if (!coords_montgomery && total) {
+    const size_t cnt = 2 * total;
+    launch("fq_to_mont_kernel", fq_to_mont_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, c.stream,
+           reinterpret_cast<fe*>(d), cnt);
+  }
+  const MsmVarPlan pl = msm_var_plan(n_max, total, (uint32_t)count);
+  if ((rc = scratch_reserve(c.msm_ws, pl.workspace_bytes))) return rc;
+  rc = msm_var_run((const g1_affine*)d, total, (const fe*)(d + off_sc), 0, (const MsmVarDesc*)(d + off_desc), n_max,
+                   (uint32_t)count, 0, (g1_jac*)(d + off_out), c.msm_ws.p, c.msm_ws.cap, c.stream);
+  if (rc) return hip_fail((hipError_t)rc, "msm_var_run");
+  CAP_HIP(hipMemcpyAsync(out_xyz, d + off_out, sizeof(g1_jac) * (size_t)count, hipMemcpyDeviceToHost, c.stream));
+  CAP_HIP(hipStreamSynchronize(c.stream));  // (also keeps `packed` and `desc` alive until the copies are done)
+  return take_launch_error();
+}
+}  // namespace
+
+int capgpu_msm_g1_var(const void* bases, size_t stride_bytes, int coords_montgomery, const uint64_t* scalars, size_t n,
+                      uint64_t out_xyz[12]) {
+  if (!out_xyz || (n && (!bases || !scalars)) || (stride_bytes != 64 && stride_bytes != 72)) {
+    set_error("capgpu_msm_g1_var: bad argument (null pointer, or a stride other than 64 or 72)");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  const unsigned char* bp[1] = {(const unsigned char*)bases};
+  const uint64_t* sp[1] = {scalars};
+  return msm_var_host(bp, stride_bytes, coords_montgomery, sp, &n, 1, out_xyz);
+}
+
+int capgpu_msm_g1_var_batch(const uint64_t* const* bases, const uint64_t* const* scalars, const size_t* ns, int count,
+                            uint64_t* out_xyz) {
+  if (count < 0 || (count && (!bases || !scalars || !ns || !out_xyz))) {
+    set_error("capgpu_msm_g1_var_batch: bad argument (null pointer or count %d < 0)", count);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  if (count == 0) return CAPGPU_OK;
+  return msm_var_host((const unsigned char* const*)bases, 64, 1, scalars, ns, count, out_xyz);
+}
+
+int capgpu_msm_var_plan(size_t n, int count, char* buf, size_t cap) {
+  if (!buf || cap == 0 || count < 0 || n >= ((size_t)1 << 31)) {
+    set_error("capgpu_msm_var_plan: bad argument");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  msm_var_describe(msm_var_plan(n, n, (uint32_t)count), buf, cap);  // host arithmetic only: works without a device
+  return CAPGPU_OK;
+}
+
 // KZG commitment of a polynomial given by its VALUES on the 2^log_n-th roots of unity (+ the two blinders of jf-plonk's
 // wire polynomials): an MSM on the Lagrange-form commit key (lagrange.hip), the form round 1 of the prover uses
 int capgpu_msm_g1_lagrange(uint64_t srs_handle, uint32_t log_n, const uint64_t* scalars, size_t count,

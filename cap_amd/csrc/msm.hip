@@ -11,6 +11,7 @@
 // the MSM kernels run long dependent chains of field multiplications per thread: column-wise schedule (field29.hpp)
 #define CAP_FL_SCHED 1
 #include "msm.hpp"
+#include "msm_recode.hpp"
 #include "curve29.hpp"
 #include "quad29.hpp"
 #include "launch.hpp"
@@ -2161,6 +2162,15 @@ bool chained_enabled() {
   }();
   return on;
 }
+// points per batch entry the bucket reduction keeps in `partial`, whichever form run_tail picks for the launch
+size_t reduce_partial_points(uint32_t c, size_t half, size_t nseg, uint32_t sb) {
+  size_t chunks = kReduceMaxChunks;  // room for any choice of reduce_chunks
+  size_t npart = use_segment_reduce((uint32_t)half, sb) ? 2 * nseg : c * chunks;
+  // the grid reduction's row and column sums (msm_reduce_grid): 2^ceil(k/2) + 2^floor(k/2) per entry
+  uint32_t k = 0;
+  while (((size_t)1 << k) < half) k++;
+  return std::max(npart, ((size_t)half >> (k / 2)) + ((size_t)1 << (k / 2)) + 3);  // (+ 3: msm_reduce_grid_final_quad)
+}
 // sb = sub-MSMs of the launch (batch * parts), n = points per sub-MSM
 WsLayout ws_layout(uint32_t c, uint32_t windows, size_t n, uint32_t sb, uint32_t sub_bits, bool has_parts) {
   WsLayout L{};
@@ -2174,13 +2184,7 @@ WsLayout ws_layout(uint32_t c, uint32_t windows, size_t n, uint32_t sb, uint32_t
   L.offsets = o; o = align_up(o + sizeof(uint32_t) * half * sb, 256);
   L.sorted = o;  o = align_up(o + sizeof(uint32_t) * per * sb, 256);
   {
-    size_t chunks = kReduceMaxChunks;  // room for any choice of reduce_chunks
-    size_t npart = use_segment_reduce((uint32_t)half, sb) ? 2 * nseg : c * chunks;
-    {  // the grid reduction's row and column sums (msm_reduce_grid): 2^ceil(k/2) + 2^floor(k/2) per entry
-      uint32_t k = 0;
-      while (((size_t)1 << k) < half) k++;
-      npart = std::max(npart, ((size_t)half >> (k / 2)) + ((size_t)1 << (k / 2)) + 3);  // (+ 3: msm_reduce_grid_final_quad)
-    }
+    const size_t npart = reduce_partial_points(c, half, nseg, sb);
     L.buckets = o; o = align_up(o + sizeof(g1_xyzz) * half * sb, 256);
     L.partial = o; o = align_up(o + sizeof(g1_xyzz) * npart * sb, 256);
   }
@@ -2280,11 +2284,7 @@ uint32_t msm_choose_window(size_t n) {
   return wide_c();  // long MSMs are run as batches of sub-MSMs on the wide windows (choose_plan)
 }
 
-uint32_t msm_num_windows(uint32_t c) {
-  uint32_t w = (256 + c - 1) / c;
-  if (256 % c == 0) w += 1;  // room for the final signed-digit carry
-  return w;
-}
+uint32_t msm_num_windows(uint32_t c) { return msm_recode_windows(c); }  // (+ 1 when c divides 256: the top carry)
 
 int msm_precompute(MsmBases* out, const g1_affine* d_bases, size_t n, uint32_t c, hipStream_t stream) {
   out->n = n;
@@ -2808,6 +2808,303 @@ int msm_run(const MsmBases& bases, size_t offset, const fe* d_scalars, size_t ou
     if (rc) return rc;
   }
   return 0;
+}
+
+// ---- one-shot MSM over caller points: no table -------------------------------------------------------------------------
+// The fixed-base plan above trades ~500 doublings per point at upload for one bucket set per MSM.  Points that are used
+// once cannot pay that, so here every window keeps its own bucket set: (MSM m, window w, part p) is one sub-MSM of the
+// common tail (run_tail: work items, msm_accumulate, bucket reduction) whose "table" is the caller's points themselves,
+// converted once to the internal field form (64 B per point, no multiples).  New around the tail:
+//   msm_var_convert  arkworks affine -> internal affine, one thread per point
+//   msm_var_sort     one workgroup per sub-MSM: digit w of the part's scalars (msm_recode.hpp: no carry chain) histogrammed
+//                    and placed by bucket in LDS - no [bucket][tile] tables, no global atomics; the scalars are read twice
+//                    per window (32 B x 2 W per point against the 2 KB of a table row set)
+//   msm_var_horner   S = sum_w 2^(c w) S_w per MSM: c (W - 1) dependent doublings on one quad, all MSMs in one launch
+// Long inputs: a launch holds at most var_max_sub() sub-MSMs (their bucket sets are the workspace); more points are run
+// range after range and msm_sum_parts adds the ranges' results, more MSMs slice after slice.
+namespace {
+
+constexpr uint32_t kVarSortThreads = 1024;
+constexpr uint32_t kVarMaxHalf = 4096;            // buckets of a sub-MSM (c <= 13): the sort's two LDS arrays
+constexpr size_t kVarMaxSubPoints = (size_t)1 << 16;  // points of a part
+
+__global__ __launch_bounds__(kThreads) void msm_var_convert(g1_affine* __restrict__ dst,
+                                                            const g1_affine* __restrict__ src, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const g1_affine b = src[i];
+  g1a p;
+  if (G1::is_inf(b)) {
+    p.x = Fq29::zero();
+    p.y = Fq29::zero();
+  } else {
+    p.x = Fq29::canonical(Fq29::from_ext(b.x));
+    p.y = Fq29::canonical(Fq29::from_ext(b.y));
+  }
+  dst[i] = G1L::store_affine(p);
+}
+
+// Sub-MSM b of the launch = (MSM m0 + b / (W parts), window (b / parts) % W, part b % parts); the part covers points
+// [range_lo + part * n_sub, + n_sub) of its MSM, cut to the MSM's length.  desc == nullptr: every MSM has n_uniform points
+// on the SAME bases and its scalars at scalars + m * scalar_stride.  Entries are (index into the converted points | sign).
+__global__ __launch_bounds__(kVarSortThreads) void msm_var_sort(const fe* __restrict__ scalars, size_t scalar_stride,
+                                                                const MsmVarDesc* __restrict__ desc, size_t n_uniform,
+                                                                uint32_t m0, size_t range_lo, size_t n_sub, uint32_t parts,
+                                                                uint32_t windows, uint32_t c, msm_biased bias,
+                                                                int montgomery, uint32_t* __restrict__ counts,
+                                                                uint32_t* __restrict__ offsets,
+                                                                uint32_t* __restrict__ sorted,
+                                                                uint32_t* __restrict__ sync, uint32_t n_sync) {
+  __shared__ uint32_t hist[kVarMaxHalf];
+  __shared__ uint32_t cursor[kVarMaxHalf];
+  __shared__ uint32_t sh[17];
+  // the flag words of the launch's chained item kernel (msm_items), as msm_digits_local zeroes them
+  if (blockIdx.x == 0)
+    for (uint32_t j = threadIdx.x; j < n_sync; j += kVarSortThreads) sync[j] = 0;
+  const uint32_t half = 1u << (c - 1);
+  const uint32_t b = blockIdx.x, part = b % parts, w = (b / parts) % windows, m = m0 + b / (parts * windows);
+  size_t n_m = n_uniform, base_m = 0;
+  const fe* sc = scalars + (size_t)m * scalar_stride;
+  if (desc) {
+    const MsmVarDesc d = desc[m];
+    n_m = d.n;
+    base_m = d.base_off;
+    sc = scalars + d.scalar_off;
+  }
+  const size_t lo = range_lo + (size_t)part * n_sub;
+  const uint32_t len = lo < n_m ? (uint32_t)(n_m - lo < n_sub ? n_m - lo : n_sub) : 0u;
+  for (uint32_t j = threadIdx.x; j < half; j += kVarSortThreads) hist[j] = 0;
+  __syncthreads();
+  auto digit = [&](uint32_t i) {
+    fe k = sc[lo + i];
+    if (montgomery) k = Fr::from_mont(k);
+    return msm_recode_digit(msm_recode_add(k.v, bias), w, c);
+  };
+  for (uint32_t i = threadIdx.x; i < len; i += kVarSortThreads) {
+    const int32_t d = digit(i);
+    if (d) atomicAdd(&hist[(uint32_t)(d < 0 ? -d : d) - 1u], 1u);
+  }
+  __syncthreads();
+  {  // exclusive scan: each thread owns up to four consecutive buckets
+    const uint32_t per_t = (half + kVarSortThreads - 1) / kVarSortThreads, j0 = threadIdx.x * per_t;
+    uint32_t run = 0;
+    for (uint32_t t = 0; t < per_t && j0 + t < half; t++) run += hist[j0 + t];
+    uint32_t tot;
+    uint32_t pre = block_scan_1024(run, sh, &tot);
+    for (uint32_t t = 0; t < per_t && j0 + t < half; t++) {
+      const uint32_t cnt = hist[j0 + t];
+      cursor[j0 + t] = pre;
+      counts[(size_t)b * half + j0 + t] = cnt;
+      offsets[(size_t)b * half + j0 + t] = pre;
+      pre += cnt;
+    }
+  }
+  __syncthreads();
+  uint32_t* dst = sorted + (size_t)b * n_sub;
+  for (uint32_t i = threadIdx.x; i < len; i += kVarSortThreads) {
+    const int32_t d = digit(i);
+    if (d) {
+      const uint32_t pos = atomicAdd(&cursor[(uint32_t)(d < 0 ? -d : d) - 1u], 1u);
+      dst[pos] = (uint32_t)(base_m + lo + i) | (d < 0 ? 0x80000000u : 0u);
+    }
+  }
+}
+
+// One workgroup of 16 quads per MSM.  The quads first add up the parts of their windows (w = quad, quad + 16), then quad 0
+// walks the windows from the top: c doublings, one addition.  The walk is a chain of c (W - 1) + W dependent point
+// operations four multiplications deep each (quad29.hpp) - it cannot be spread any further without multiples of the points.
+// out_range != nullptr: the MSM's result for this point range, XYZZ, at out_range[m * range_stride] (msm_sum_parts adds them).
+__global__ __launch_bounds__(64) void msm_var_horner(const g1_xyzz* __restrict__ win_pts, uint32_t windows, uint32_t parts,
+                                                     uint32_t c, g1_jac* __restrict__ out,
+                                                     g1_xyzz* __restrict__ out_range, uint32_t range_stride) {
+  __shared__ g1_xyzz tw[32];
+  const uint32_t m = blockIdx.x, quad = threadIdx.x >> 2;
+  for (uint32_t w = quad; w < windows; w += 16) {
+    const g1_xyzz* src = win_pts + ((size_t)m * windows + w) * parts;
+    fl acc = quad_load(src);
+#pragma unroll 1
+    for (uint32_t p = 1; p < parts; p++) acc = quad_add_call(acc, quad_load(src + p));
+    quad_store(&tw[w], acc);
+  }
+  __syncthreads();
+  if (quad != 0) return;
+  fl acc = quad_load(&tw[windows - 1]);
+#pragma unroll 1
+  for (int w = (int)windows - 2; w >= 0; w--) {
+#pragma unroll 1
+    for (uint32_t k = 0; k < c; k++) acc = quad_dbl_call(acc);
+    acc = quad_add_call(acc, quad_load(&tw[w]));
+  }
+  const g1x r = QD::gather(acc);
+  if (threadIdx.x == 0) {
+    if (out_range) out_range[(size_t)m * range_stride] = G1S::store(r);
+    else out[m] = G1S::to_jac_ext(r);
+  }
+}
+
+long long env_ll(const char* name, long long dflt) {  // read per call: tests switch these between calls
+  const char* e = getenv(name);
+  return e && *e ? atoll(e) : dflt;
+}
+// sub-MSMs (bucket sets) of one launch: 2^21 buckets, 256 MB of bucket points
+size_t var_max_sub(uint32_t c, uint32_t windows) {
+  return std::max<size_t>(windows, ((size_t)1 << 21) >> (c - 1));
+}
+
+struct VarLayout {
+  size_t conv, counts, offsets, sorted, buckets, partial, item_off, item_base, totals, item_bucket, item_sub, item_pts,
+      win_pts, range_pts, max_items, total;
+  uint32_t item_len;  // of every launch of the call (chosen for the largest one, so that max_items bounds them all)
+};
+VarLayout var_layout(const MsmVarPlan& pl, size_t total_points, uint32_t count) {
+  VarLayout L{};
+  const size_t half = (size_t)1 << (pl.c - 1), per = pl.n_sub;
+  const uint32_t sb = pl.slice * pl.windows * pl.range_parts;
+  const size_t seg_len = reduce_seg_len((uint32_t)half), nseg = (half + seg_len - 1) / seg_len;
+  size_t o = 0;
+  auto take = [&](size_t bytes) {
+    const size_t at = o;
+    o = align_up(o + bytes, 256);
+    return at;
+  };
+  L.conv = take(sizeof(g1_affine) * total_points);
+  L.counts = take(4 * half * sb);
+  L.offsets = take(4 * half * sb);
+  L.sorted = take(4 * per * sb);
+  L.buckets = take(sizeof(g1_xyzz) * half * sb);
+  // (a shorter last launch may reduce by another form than the full one: room for either)
+  L.partial = take(sizeof(g1_xyzz) * std::max(reduce_partial_points(pl.c, half, nseg, sb), reduce_partial_points(pl.c, half, nseg, 1)) * sb);
+  L.item_len = choose_item_len(per * sb, half * sb);
+  L.max_items = per * sb / L.item_len + half * sb;
+  L.item_off = take(4 * half * sb);
+  L.item_base = take(4 * ((size_t)sb + 3));
+  L.totals = take(4 * ((size_t)sb + 1));
+  L.item_bucket = take(4 * L.max_items);
+  L.item_sub = take(4 * L.max_items);
+  L.item_pts = take(sizeof(g1_xyzz) * L.max_items);
+  L.win_pts = take(sizeof(g1_xyzz) * sb);
+  L.range_pts = take(sizeof(g1_xyzz) * (pl.ranges > 1 ? (size_t)count * pl.ranges : 0));
+  L.total = o;
+  return L;
+}
+
+}  // namespace
+
+MsmVarPlan msm_var_plan(size_t n_max, size_t total_points, uint32_t count) {
+  MsmVarPlan pl{};
+  if (n_max == 0 || count == 0) {
+    pl.workspace_bytes = 256;
+    return pl;
+  }
+  // points of a part: up to 2^16 (CAPGPU_MSM_VAR_SUB: tests cut short inputs into parts)
+  size_t n_sub = std::min(n_max, kVarMaxSubPoints);
+  {
+    const long long x = env_ll("CAPGPU_MSM_VAR_SUB", 0);
+    if (x >= 1) n_sub = std::min<size_t>(n_sub, (size_t)x);
+  }
+  // Window: (256 / c) (n_sub + 2^c) group operations per part - n_sub entries and about two operations per bucket - is
+  // flat around c = log2(n_sub) - 3; 9 .. 13 bits (256 .. 4096 buckets, the sort's LDS arrays)
+  uint32_t lg = 0;
+  while (((size_t)2 << lg) <= n_sub) lg++;
+  uint32_t c = lg > 12 ? lg - 3 : 9;
+  c = std::min(c, 13u);
+  {
+    const long long x = env_ll("CAPGPU_MSM_VAR_C", 0);
+    if (x >= 9 && x <= 13) c = (uint32_t)x;
+  }
+  pl.c = c;
+  pl.windows = msm_recode_windows(c);
+  pl.n_sub = n_sub;
+  pl.parts = (uint32_t)((n_max + n_sub - 1) / n_sub);
+  const size_t group = std::max<size_t>(1, var_max_sub(c, pl.windows) / pl.windows);  // (MSM, part) pairs of a launch
+  pl.range_parts = (uint32_t)std::min<size_t>(pl.parts, group);
+  {  // CAPGPU_MSM_VAR_RANGE: points per range (tests force the range split at small sizes)
+    const long long x = env_ll("CAPGPU_MSM_VAR_RANGE", 0);
+    if (x >= 1) pl.range_parts = (uint32_t)std::min<size_t>(pl.range_parts, std::max<size_t>(1, (size_t)x / n_sub));
+  }
+  pl.ranges = (pl.parts + pl.range_parts - 1) / pl.range_parts;
+  pl.slice = (uint32_t)std::min<size_t>(count, std::max<size_t>(1, group / pl.range_parts));
+  {  // CAPGPU_MSM_VAR_SLICE: MSMs per launch
+    const long long x = env_ll("CAPGPU_MSM_VAR_SLICE", 0);
+    if (x >= 1) pl.slice = (uint32_t)std::min<size_t>(pl.slice, (size_t)x);
+  }
+  pl.workspace_bytes = var_layout(pl, total_points, count).total;
+  return pl;
+}
+
+const char* msm_var_describe(const MsmVarPlan& pl, char* buf, size_t cap) {
+  if (pl.c == 0) {
+    snprintf(buf, cap, "path=empty workspace_bytes=%zu", pl.workspace_bytes);
+    return buf;
+  }
+  snprintf(buf, cap,
+           "path=bucket c=%u windows=%u n_sub=%zu parts=%u sub_msms=%u ranges=%u slice=%u tail=horner-quad "
+           "workspace_bytes=%zu",
+           pl.c, pl.windows, pl.n_sub, pl.parts, pl.slice * pl.windows * pl.range_parts, pl.ranges, pl.slice,
+           pl.workspace_bytes);
+  return buf;
+}
+
+int msm_var_run(const g1_affine* d_bases, size_t total_points, const fe* d_scalars, size_t scalar_stride,
+                const MsmVarDesc* d_desc, size_t n_max, uint32_t count, int montgomery, g1_jac* d_out, void* ws,
+                size_t ws_bytes, hipStream_t stream) {
+  if (count == 0) return 0;
+  if (n_max == 0) {
+    launch("msm_fill_inf", msm_fill_inf, dim3((count + 255) / 256), dim3(256), 0, stream, d_out, count);
+    return 0;
+  }
+  if (total_points >= ((size_t)1 << 31) || n_max > total_points) return (int)hipErrorInvalidValue;
+  const MsmVarPlan pl = msm_var_plan(n_max, total_points, count);
+  const VarLayout L = var_layout(pl, total_points, count);
+  if (ws_bytes < L.total) return (int)hipErrorInvalidValue;
+  char* base = reinterpret_cast<char*>(ws);
+  auto u32 = [&](size_t off) { return reinterpret_cast<uint32_t*>(base + off); };
+  auto pts = [&](size_t off) { return reinterpret_cast<g1_xyzz*>(base + off); };
+  g1_affine* conv = reinterpret_cast<g1_affine*>(base + L.conv);
+  launch("msm_var_convert", msm_var_convert, dim3((unsigned)((total_points + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+         stream, conv, d_bases, total_points);
+  const uint32_t c = pl.c, W = pl.windows, half = 1u << (c - 1);
+  const msm_biased bias = msm_recode_bias(c);
+  const bool chained = chained_enabled();
+  g1_xyzz* range_pts = pl.ranges > 1 ? pts(L.range_pts) : nullptr;
+  for (uint32_t m0 = 0; m0 < count; m0 += pl.slice) {
+    const uint32_t cnt = std::min(pl.slice, count - m0);
+    for (uint32_t r = 0; r < pl.ranges; r++) {
+      const uint32_t parts = std::min(pl.range_parts, pl.parts - r * pl.range_parts);
+      const uint32_t sb = cnt * W * parts;
+      const size_t range_lo = (size_t)r * pl.range_parts * pl.n_sub;
+      launch("msm_var_sort", msm_var_sort, dim3(sb), dim3(kVarSortThreads), 0, stream, d_scalars, scalar_stride, d_desc,
+             n_max, m0, range_lo, pl.n_sub, parts, W, c, bias, montgomery, u32(L.counts), u32(L.offsets), u32(L.sorted),
+             u32(L.totals), chained ? sb + 1 : 0u);
+      Tail t{};
+      t.ext = conv;
+      t.counts = u32(L.counts);
+      t.offsets = u32(L.offsets);
+      t.sorted = u32(L.sorted);
+      t.item_off = u32(L.item_off);
+      t.item_base = u32(L.item_base);
+      t.totals = u32(L.totals);
+      t.item_bucket = u32(L.item_bucket);
+      t.item_sub = u32(L.item_sub);
+      t.item_pts = pts(L.item_pts);
+      t.buckets = pts(L.buckets);
+      t.partial = pts(L.partial);
+      t.per = pl.n_sub;
+      t.entries = pl.n_sub * sb;
+      t.half = half;
+      t.sb = sb;
+      t.item_len = L.item_len;
+      t.max_items = t.entries / t.item_len + (size_t)half * sb;
+      t.planes = c;
+      t.chained = chained;
+      run_tail(t, nullptr, pts(L.win_pts), nullptr, stream);
+      launch("msm_var_horner", msm_var_horner, dim3(cnt), dim3(64), 0, stream, (const g1_xyzz*)pts(L.win_pts), W, parts, c,
+             d_out + m0, range_pts ? range_pts + (size_t)m0 * pl.ranges + r : (g1_xyzz*)nullptr, pl.ranges);
+    }
+  }
+  if (range_pts)
+    launch("msm_sum_parts", msm_sum_parts, dim3(count), dim3(64), 0, stream, (const g1_xyzz*)range_pts, pl.ranges, d_out);
+  return 0;  // launch failures are latched by launch() and reported by take_launch_error()
 }
 
 }  // namespace cap

@@ -89,4 +89,31 @@ int msm_run(const MsmBases& bases, size_t offset, const fe* d_scalars, size_t ou
             size_t inner_stride, size_t n, uint32_t batch, int montgomery, g1_jac* d_out, void* ws, size_t ws_bytes,
             hipStream_t stream);
 
+// ---- one-shot MSM over caller points (msm.hip, "no table") -----------------------------------------------------------
+// Replaces VariableBaseMSM::multi_scalar_mul for bases that are used ONCE: nothing is precomputed, every window has its
+// own bucket set, the windows are combined by Horner at the end.  Per point: W mixed additions and 64 B of workspace.
+struct MsmVarDesc {     // one MSM of a ragged batch
+  uint64_t scalar_off;  // its scalars start at d_scalars + scalar_off (elements)
+  uint32_t base_off;    // its points start at d_bases + base_off
+  uint32_t n;
+};
+struct MsmVarPlan {
+  uint32_t c, windows;  // c == 0: nothing to run (no points or no MSMs)
+  size_t n_sub;         // points of a part; an MSM of n points has `parts` of them
+  uint32_t parts;
+  uint32_t range_parts, ranges;  // parts that go through the kernels together; launches per slice
+  uint32_t slice;                // MSMs that go through the kernels together
+  size_t workspace_bytes;
+};
+// n_max: the longest MSM of the call; total_points: points behind d_bases (n for MSMs on shared points, the sum for a batch)
+MsmVarPlan msm_var_plan(size_t n_max, size_t total_points, uint32_t count);
+const char* msm_var_describe(const MsmVarPlan& pl, char* buf, size_t cap);
+// out[m] = sum_i scalars_m[i] * bases_m[i], m < count.  d_bases: arkworks affine ((0,0) = infinity), never written.
+// d_desc == nullptr: all MSMs over the same n_max points, scalars_m = d_scalars + m * scalar_stride; else one descriptor
+// per MSM (device).  Refuses total_points >= 2^31 (an entry is a 31-bit point index and a sign).  ws must hold
+// msm_var_plan().workspace_bytes.
+int msm_var_run(const g1_affine* d_bases, size_t total_points, const fe* d_scalars, size_t scalar_stride,
+                const MsmVarDesc* d_desc, size_t n_max, uint32_t count, int montgomery, g1_jac* d_out, void* ws,
+                size_t ws_bytes, hipStream_t stream);
+
 }  // namespace cap

@@ -399,6 +399,64 @@ def msm_plan(handle: int, n: int, count: int = 1) -> dict:
     return out
 
 
+# ---- one-shot MSM over caller points (no SRS handle, no table) ---------------------------------------------------
+def msm_g1_var(bases: np.ndarray, scalars: np.ndarray, montgomery: bool = True) -> np.ndarray:
+    """bases (n, 8) uint64 packed affine points - or (n, 72) uint8: arkworks' GroupAffine with its infinity byte -,
+    scalars (n, 4) canonical -> Jacobian (12,) Montgomery.  Nothing stays on the device."""
+    bases = np.ascontiguousarray(bases)
+    if bases.dtype == np.uint8:
+        bases = bases.reshape(-1, 72)
+        stride = 72
+    else:
+        bases = np.ascontiguousarray(bases, dtype=np.uint64).reshape(-1, 8)
+        stride = 64
+    scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+    assert bases.shape[0] == scalars.shape[0]
+    out = np.zeros(12, dtype=np.uint64)
+    check(load().capgpu_msm_g1_var(bases.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(stride), int(montgomery),
+                                   _p(scalars), ctypes.c_size_t(scalars.shape[0]), _p(out)))
+    return out
+
+
+def msm_g1_var_batch(bases_list, scalar_list) -> np.ndarray:
+    """one MSM per (bases, scalars) pair, each over its own points, in one pass of launches -> (count, 12)"""
+    cnt = len(scalar_list)
+    assert len(bases_list) == cnt
+    pts = [np.ascontiguousarray(b, dtype=np.uint64).reshape(-1, 8) for b in bases_list]
+    arrs = [np.ascontiguousarray(s, dtype=np.uint64).reshape(-1, 4) for s in scalar_list]
+    assert all(p.shape[0] == a.shape[0] for p, a in zip(pts, arrs))
+    ns = (ctypes.c_size_t * cnt)(*[a.shape[0] for a in arrs])
+    bptrs = (u64p * cnt)(*[_p(p) for p in pts])
+    sptrs = (u64p * cnt)(*[_p(a) for a in arrs])
+    out = np.zeros((cnt, 12), dtype=np.uint64)
+    check(load().capgpu_msm_g1_var_batch(bptrs, sptrs, ns, cnt, _p(out)))
+    return out
+
+
+def msm_g1_var_dev(d_bases: DevBuf, d_scalars: DevBuf, n: int, count: int = 1, stride: int | None = None,
+                   montgomery: bool = False, d_out: DevBuf | None = None) -> DevBuf:
+    """`count` MSMs over the same n device-resident points (packed Montgomery affine); results stay on the device"""
+    if d_out is None:
+        d_out = DevBuf(96 * count)
+    check(load().capgpu_msm_g1_var_dev(d_bases.ptr, d_scalars.ptr, ctypes.c_size_t(n if stride is None else stride),
+                                       ctypes.c_size_t(n), count, int(montgomery), d_out.ptr))
+    return d_out
+
+
+def msm_var_plan(n: int, count: int = 1) -> dict:
+    """How `count` one-shot MSMs of n points would run: {'path': 'bucket', 'c': 13, 'windows': 20, 'n_sub': 65536,
+    'parts': 1, 'sub_msms': 20, 'ranges': 1, 'slice': 1, 'tail': 'horner-quad', 'workspace_bytes': ...}; no device needed."""
+    buf = ctypes.create_string_buffer(256)
+    check(load().capgpu_msm_var_plan(ctypes.c_size_t(n), count, buf, ctypes.c_size_t(256)))
+    out = {}
+    for kv in buf.value.decode().split():
+        if "=" not in kv:
+            continue
+        k, v = kv.split("=")
+        out[k] = int(v) if v.isdigit() else v
+    return out
+
+
 # ---- multi-GPU (one process per GPU; RCCL inside the library) -----------------------------------------------------
 def comm_unique_id() -> bytes:
     buf = (ctypes.c_uint8 * 128)()

@@ -243,6 +243,38 @@ int capgpu_msm_g1_batch(uint64_t srs_handle, const size_t* offsets, const uint64
 int capgpu_msm_g1_dev(uint64_t srs_handle, size_t offset, const void* d_scalars, size_t scalar_stride, size_t n,
                       int count, int scalars_montgomery, void* d_out_xyz);
 
+/* ---- one-shot MSM: points that are used ONCE ---------------------------------------------------------------------
+ * VariableBaseMSM::multi_scalar_mul(bases, scalars) as ark-ec has it (ark-ec 0.3.0 src/msm/variable_base.rs): the
+ * caller's points, no handle, nothing kept.  capgpu_srs_upload expands every point into its window multiples (about 500
+ * doublings and 1.3 - 2.4 KB per point) - right for a commit key that serves many proofs, more work than the MSM itself
+ * for points seen once.  These entry points read the points as they are: one bucket set per window, signed digits, the
+ * windows combined by Horner at the end (64 B of workspace per point, W mixed additions).  Upload an SRS when the same
+ * points serve more than a handful of MSMs; call these when they serve one.
+ * All of them run on the calling thread's context and its stream (capgpu_set_stream is honoured; sharding over devices
+ * is not done here), take their workspace from the context's scratch (capgpu_scratch_stats counts it,
+ * capgpu_set_memory_limit caps it: CAPGPU_ERR_OOM naming the bytes), check their arguments before they look for a
+ * device (CAPGPU_ERR_INVALID_ARG, then CAPGPU_ERR_NOT_INITIALISED) and have no CPU fallback.  Points are taken as
+ * capgpu_srs_upload takes them: not checked for being on the curve.  n = 0 gives infinity (Z = 0), count = 0 nothing.
+ * A call refuses (CAPGPU_ERR_INVALID_ARG) 2^31 points or more - for the batch form: in the sum over its MSMs; up to
+ * there a long input is run as point ranges of about 1.6 million points whose results are added. */
+/* out = sum_i scalars[i] * bases[i]; bases as capgpu_srs_upload takes them (stride 64 / 72, coords_montgomery), scalars
+ * canonical 4 x u64 (any 256-bit integer, as capgpu_msm_g1), out Jacobian 96 B.
+ * Replaces VariableBaseMSM::multi_scalar_mul(&bases, &scalars) on bases that were never uploaded. */
+int capgpu_msm_g1_var(const void* bases, size_t stride_bytes, int coords_montgomery, const uint64_t* scalars, size_t n,
+                      uint64_t out_xyz[12]);
+/* `count` independent MSMs, each over its OWN bases (packed 64-byte Montgomery affine), in one pass of launches
+ * (replaces a loop of multi_scalar_mul calls, e.g. the two sides of a batched KZG check) */
+int capgpu_msm_g1_var_batch(const uint64_t* const* bases, const uint64_t* const* scalars, const size_t* ns, int count,
+                            uint64_t* out_xyz /* count*12 */);
+/* Device-resident form, arguments in the order of capgpu_msm_g1_dev: d_bases n packed 64-byte Montgomery affine points
+ * ((0,0) = infinity), never written; `count` scalar arrays over the SAME points, scalar_stride elements apart;
+ * d_out_xyz count * 96 B on device.  Nothing is copied to or from the host and the call does not wait for the device. */
+int capgpu_msm_g1_var_dev(const void* d_bases, const void* d_scalars, size_t scalar_stride, size_t n, int count,
+                          int scalars_montgomery, void* d_out_xyz);
+/* Diagnostic, as capgpu_msm_plan: "path=bucket c=13 windows=20 n_sub=65536 parts=1 sub_msms=20 ranges=1 slice=1
+ * tail=horner-quad workspace_bytes=<what the launch requests from the scratch>".  Needs no device. */
+int capgpu_msm_var_plan(size_t n, int count, char* buf, size_t cap);
+
 /* ---- scalars resident with their points ("GPU g holds its bases resident and receives the matching scalar
  * slice") ------------------------------------------------------------------------------------------------------------
  * capgpu_msm_g1_dev on a sharded SRS has to scatter the caller's scalars over the devices on EVERY call (32 B x n leaving
