@@ -276,6 +276,13 @@ extern "C" {
                                         num_inputs: *const usize, proofs: *const *const capgpu_proof,
                                         ext_msgs: *const *const u8, ext_msg_lens: *const usize, count: usize,
                                         ok_out: *mut c_int) -> c_int;
+    // ---- the pairing check's two forms (CAPGPU_PAIRING_LANE / CAPGPU_PAIRING_WAVE)
+    pub fn capgpu_pairing_set_form(form: c_int) -> c_int;
+    pub fn capgpu_pairing_get_form(form_out: *mut c_int) -> c_int;
+    pub fn capgpu_pairing_stats(lane_checks_out: *mut u64, wave_checks_out: *mut u64) -> c_int;
+    pub fn capgpu_plonk_verify_dev(vk: *const capgpu_verifying_key, g2_h: *const u64, g2_beta_h: *const u64,
+                                   pub_inputs: *const u64, num_inputs: usize, ext_msg: *const u8, ext_msg_len: usize,
+                                   proof: *const capgpu_proof, ok_out: *mut c_int) -> c_int;
     pub fn capgpu_proof_serialize(proof: *const capgpu_proof, out: *mut u8, cap: usize, len_out: *mut usize) -> c_int;
     pub fn capgpu_proof_deserialize(bytes: *const u8, len: usize, proof_out: *mut capgpu_proof,
                                     consumed_out: *mut usize) -> c_int;
@@ -350,6 +357,10 @@ pub fn set_coalescing(window_us: u32, max_batch: u32) -> Result<()> {
 pub fn set_wire_commit_from_evals(on: bool) -> Result<()> {
     check(unsafe { capgpu_plonk_set_wire_commit(if on { 1 } else { 0 }) })
 }
+
+/// `form` of `capgpu_pairing_set_form`: one pairing check per lane (the default), or one per group of six lanes.
+pub const CAPGPU_PAIRING_LANE: c_int = 0;
+pub const CAPGPU_PAIRING_WAVE: c_int = 1;
 
 pub const CAPGPU_TRANSCRIPT_HOST: c_int = 0;
 pub const CAPGPU_TRANSCRIPT_DEVICE: c_int = 1;

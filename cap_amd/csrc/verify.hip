@@ -469,8 +469,9 @@ int capgpu_plonk_batch_verify(const capgpu_verifying_key* const* vks, const uint
 // the weight r_i folded into the scalars - are two multi-scalar multiplications, run by the MSM kernels of the prover
 // (K3-K6; the bases are uploaded like an SRS, their window tables built on the device).  SURVEY 8f row 4.  Needs an
 // initialised library (CAPGPU_ERR_NOT_INITIALISED otherwise - there is no silent host path behind this entry point);
-// the transcript work per proof and the final pairing product stay on the host.  Accepts and rejects exactly what
-// capgpu_plonk_batch_verify does: both evaluate the same terms with the same weights.
+// the transcript work per proof stays on the host, and so does the final pairing product unless the pairing form is
+// CAPGPU_PAIRING_WAVE (capgpu_pairing_set_form): then the folded (A, -B) is decided by one wave-form check on the device.
+// Accepts and rejects exactly what capgpu_plonk_batch_verify does: both evaluate the same terms with the same weights.
 int capgpu_plonk_batch_verify_dev(const capgpu_verifying_key* const* vks, const uint64_t g2_h[16],
                                   const uint64_t g2_beta_h[16], const uint64_t* const* pub_inputs,
                                   const size_t* num_inputs, const capgpu_proof* const* proofs,
@@ -529,6 +530,8 @@ int capgpu_plonk_batch_verify_dev(const capgpu_verifying_key* const* vks, const 
   };
   g1_affine a = to_affine(a_xyz), b = to_affine(b_xyz);
   b.y = Fq::neg(b.y);
+  // with the wave form in force the final product is one group's check on the device (verify_dev.hip)
+  if (pairing_form() == CAPGPU_PAIRING_WAVE) return pairing_check2_wave_dev(a, beta_h, b, h, ok_out);
   std::vector<std::pair<g1_affine, g2_affine>> pairs = {{a, beta_h}, {b, h}};
   *ok_out = pairing::pairing_product_is_one(pairs) ? 1 : 0;
   return CAPGPU_OK;

@@ -32,4 +32,10 @@ g1_affine g1_from_abi(const uint64_t w[8]);
 // canonical coordinates and on the curve (infinity included)
 bool g1_abi_on_curve(const g1_affine& p);
 
+// What verify_dev.hip offers the batch verifier: the pairing form in force (capgpu_pairing_set_form) and
+// *ok_out = (e(p, q1) e(r, q2) == 1) decided on the device by one wave-form check ((0, 0) = infinity in p and r)
+int pairing_form();
+int pairing_check2_wave_dev(const g1_affine& p, const pairing::g2_affine& q1, const g1_affine& r,
+                            const pairing::g2_affine& q2, int* ok_out);
+
 }  // namespace cap

@@ -1178,6 +1178,44 @@ def plonk_verify_each(vks, g2_h: np.ndarray, g2_beta_h: np.ndarray, pub_inputs_l
     return ok[:cnt] != 0
 
 
+PAIRING_LANE, PAIRING_WAVE = 0, 1
+
+
+def pairing_set_form(form: int) -> None:
+    """Which kernel decides the device pairing checks from now on, process-wide (capgpu_pairing_set_form): PAIRING_LANE,
+    one check per lane (the default; the environment's CAPGPU_PAIRING=lane|wave sets the initial value), or PAIRING_WAVE,
+    one check per group of six lanes - meant for one proof or a small block, not yet timed against LANE.  Callable before init()."""
+    check(load().capgpu_pairing_set_form(ctypes.c_int(form)))
+
+
+def pairing_get_form() -> int:
+    form = ctypes.c_int(-1)
+    check(load().capgpu_pairing_get_form(ctypes.byref(form)))
+    return form.value
+
+
+def pairing_stats() -> dict:
+    """checks decided since process start by each of the two kernels (capgpu_pairing_stats)"""
+    lane, wave = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    check(load().capgpu_pairing_stats(ctypes.byref(lane), ctypes.byref(wave)))
+    return {"lane_checks": lane.value, "wave_checks": wave.value}
+
+
+def plonk_verify_dev(vk: VerifyingKey, g2_h: np.ndarray, g2_beta_h: np.ndarray, pub_inputs: np.ndarray, proof: Proof,
+                     ext_msg: bytes | None = None) -> bool:
+    """plonk_verify with the proof's group arithmetic and its pairing check on the GPU (capgpu_plonk_verify_dev; needs
+    init()): same verdict, same errors, the check always in the wave form."""
+    pub_inputs = np.ascontiguousarray(pub_inputs, dtype=np.uint64).reshape(-1)
+    mbuf, mlen = _bytes_arg(ext_msg)
+    ok = ctypes.c_int(0)
+    check(load().capgpu_plonk_verify_dev(ctypes.byref(vk), _p(np.ascontiguousarray(g2_h, dtype=np.uint64)),
+                                         _p(np.ascontiguousarray(g2_beta_h, dtype=np.uint64)),
+                                         _p(pub_inputs) if pub_inputs.size else None,
+                                         ctypes.c_size_t(pub_inputs.size // 4), mbuf, ctypes.c_size_t(mlen),
+                                         ctypes.byref(proof), ctypes.byref(ok)))
+    return bool(ok.value)
+
+
 def proof_serialize(proof: Proof) -> bytes:
     buf = (ctypes.c_uint8 * 1024)()
     n = ctypes.c_size_t(0)

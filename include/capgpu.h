@@ -690,7 +690,8 @@ int capgpu_plonk_batch_verify(const capgpu_verifying_key* const* vks, const uint
 /* The same predicate with its group arithmetic on the device: the ~35 (point, scalar) terms of every
  * proof, weights folded in, are two multi-scalar multiplications on the prover's MSM kernels (the bases are uploaded
  * like an SRS and their window tables built on the device); the transcripts and the final pairing product stay on the
- * host.  Accepts and rejects exactly what capgpu_plonk_batch_verify does.  Needs capgpu_init
+ * host - the product too moves to the device, as one wave-form check, while the pairing form is CAPGPU_PAIRING_WAVE
+ * (below).  Accepts and rejects exactly what capgpu_plonk_batch_verify does.  Needs capgpu_init
  * (CAPGPU_ERR_NOT_INITIALISED otherwise: no host path hides behind this entry point). */
 int capgpu_plonk_batch_verify_dev(const capgpu_verifying_key* const* vks, const uint64_t g2_h[16],
                                   const uint64_t g2_beta_h[16], const uint64_t* const* pub_inputs,
@@ -714,6 +715,31 @@ int capgpu_plonk_verify_each_dev(const capgpu_verifying_key* const* vks, const u
                                  const uint64_t g2_beta_h[16], const uint64_t* const* pub_inputs,
                                  const size_t* num_inputs, const capgpu_proof* const* proofs,
                                  const uint8_t* const* ext_msgs, const size_t* ext_msg_lens, size_t count, int* ok_out);
+/* ---- the pairing check's two forms ------------------------------------------------------------------------------
+ * CAPGPU_PAIRING_LANE  one check per lane (k_pairing_check2): the throughput form.  Its duration is one lane's whole
+ *                      pairing (~22 ms) for 1 check or for thousands.
+ * CAPGPU_PAIRING_WAVE  one check per group of six lanes, ten per wavefront (k_pairing_check2_wave): meant for a
+ *                      single proof or a small block; not yet timed against LANE.
+ * The setting is process-wide, may be made before capgpu_init, starts as the environment's CAPGPU_PAIRING=lane|wave
+ * (LANE when unset) and is honoured by capgpu_pairing_check_pairs_dev, capgpu_plonk_verify_each_dev and - for its
+ * final pairing product, which LANE leaves on the host - capgpu_plonk_batch_verify_dev.  Verdicts do not depend on it.
+ * An unknown value: CAPGPU_ERR_INVALID_ARG.  No reference counterpart (a scheduling choice of this library). */
+#define CAPGPU_PAIRING_LANE 0
+#define CAPGPU_PAIRING_WAVE 1
+int capgpu_pairing_set_form(int form);
+int capgpu_pairing_get_form(int* form_out);
+/* Checks decided since process start by the lane-form and by the wave-form kernel (diagnostics: which path ran).
+ * Either out pointer may be NULL. */
+int capgpu_pairing_stats(uint64_t* lane_checks_out, uint64_t* wave_checks_out);
+/* Replaces PlonkKzgSnark::verify::<SolidityTranscript> (proof::transfer::verify, src/proof/transfer.rs:192-212,
+ * mint.rs:124-140, freeze.rs:162-178) for a caller that has a device: capgpu_plonk_verify's arguments (ext_msg before
+ * proof here), the same range checks on every field word, the same verdict and return code in every case.  Transcript
+ * and scalars on the host; the proof's ~35 scalar multiplications and its pairing check on the device, the check
+ * always in the wave form whatever capgpu_pairing_set_form says.  Needs capgpu_init (CAPGPU_ERR_NOT_INITIALISED
+ * otherwise: no host path hides behind this entry point). */
+int capgpu_plonk_verify_dev(const capgpu_verifying_key* vk, const uint64_t g2_h[16], const uint64_t g2_beta_h[16],
+                            const uint64_t* pub_inputs, size_t num_inputs, const uint8_t* ext_msg, size_t ext_msg_len,
+                            const capgpu_proof* proof, int* ok_out);
 /* ark-serialize 0.3 CanonicalSerialize bytes of the Proof as it sits inside a TransferNote / MintNote / FreezeNote
  * (src/transfer.rs:60): compressed G1 (32 B), Fr little-endian, Vec = u64 length prefix, plookup_proof = None.
  * 769 bytes; *len_out receives the size. */
