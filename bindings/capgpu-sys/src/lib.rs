@@ -283,6 +283,17 @@ extern "C" {
     pub fn capgpu_plonk_verify_dev(vk: *const capgpu_verifying_key, g2_h: *const u64, g2_beta_h: *const u64,
                                    pub_inputs: *const u64, num_inputs: usize, ext_msg: *const u8, ext_msg_len: usize,
                                    proof: *const capgpu_proof, ok_out: *mut c_int) -> c_int;
+    pub fn capgpu_plonk_vk_upload(vk: *const capgpu_verifying_key, vk_handle_out: *mut u64) -> c_int;
+    pub fn capgpu_plonk_vk_release(vk_handle: u64) -> c_int;
+    pub fn capgpu_plonk_verify_block_dev(vk_handles: *const u64, g2_h: *const u64, g2_beta_h: *const u64,
+                                         pub_inputs: *const u64, num_inputs: usize, proofs: *const capgpu_proof,
+                                         ext_msgs: *const *const u8, ext_msg_lens: *const usize, count: usize,
+                                         block_ok_out: *mut c_int, each_ok_out: *mut c_int) -> c_int;
+    pub fn capgpu_plonk_verify_block_resident(vk_handles: *const u64, g2_h: *const u64, g2_beta_h: *const u64,
+                                              d_pub_inputs: *const c_void, num_inputs: usize, d_proofs: *const c_void,
+                                              ext_msgs: *const *const u8, ext_msg_lens: *const usize, count: usize,
+                                              block_ok_out: *mut c_int, each_ok_out: *mut c_int) -> c_int;
+    pub fn capgpu_verify_sync_stats(block_calls_out: *mut u64, stream_waits_out: *mut u64) -> c_int;
     pub fn capgpu_proof_serialize(proof: *const capgpu_proof, out: *mut u8, cap: usize, len_out: *mut usize) -> c_int;
     pub fn capgpu_proof_deserialize(bytes: *const u8, len: usize, proof_out: *mut capgpu_proof,
                                     consumed_out: *mut usize) -> c_int;

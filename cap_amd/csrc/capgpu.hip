@@ -1050,6 +1050,7 @@ void capgpu_shutdown(void) {
   plonk_async_shutdown();
   (void)capgpu_comm_destroy();
   plonk_reset_staging();
+  verify_block_reset();
   {
     AllEntries all;
     for (auto& cp : R.ctxs) {

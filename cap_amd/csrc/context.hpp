@@ -216,6 +216,7 @@ void scratch_account(int device, size_t add, size_t sub);
 bool scratch_room_for(int device, size_t bytes);
 size_t plonk_trim_staging();  // plonk.hip: frees the unused staging slots of coalesced callers; returns the bytes
 void plonk_reset_staging();   // ... and the pool's streams (capgpu_shutdown)
+void verify_block_reset();    // verify_dev.hip: frees the block verifier's per-context key copies and line tables (capgpu_shutdown)
 // plonk.hip, capgpu_shutdown: lets running tickets (capgpu_plonk_prove_batch_async) finish, drops the queued ones and joins
 // the worker threads; called before any context is locked or destroyed
 void plonk_async_shutdown();

@@ -19,7 +19,8 @@
 
 #include "curve.hpp"
 #include "field29.hpp"
-#if defined(__HIPCC__)
+// CAP_TD_NO_KERNELS: a second translation unit (verify_dev.hip) takes the sponge and the lanes without the prover's kernels
+#if defined(__HIPCC__) && !defined(CAP_TD_NO_KERNELS)
 #include "plonk_kernels.hpp"
 #endif
 
@@ -390,6 +391,7 @@ struct LaneDev {
   static __device__ __forceinline__ void sync() { __syncthreads(); }
 };
 
+#if !defined(CAP_TD_NO_KERNELS)
 // the transcript of `count` proofs on the device
 struct TrBufs {
   uint8_t* state;           // [count][64]
@@ -535,6 +537,7 @@ __global__ __launch_bounds__(64) void k_tr_open(const g1_jac* __restrict__ comms
   store_fe(pr + 64, out[1].x);
   store_fe(pr + 96, out[1].y);
 }
+#endif  // CAP_TD_NO_KERNELS
 #endif  // __HIPCC__
 
 }  // namespace td

@@ -17,10 +17,15 @@
 //                     the device's counterpart of capgpu_plonk_verify - always takes the wave form.
 // A proof holds iff e(A, [tau]H) e(-B, H) == 1 (the predicate of capgpu_plonk_verify): Q1 = beta_h, Q2 = h.
 #define CAP_FL_SCHED 0
+#define CAP_TD_NO_KERNELS
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <atomic>
+#include <map>
+#include <memory>
+#include <mutex>
 #include <vector>
 
 #include "context.hpp"
@@ -28,6 +33,7 @@
 #include "launch.hpp"
 #include "pairing29.hpp"
 #include "pairing_wave.hpp"
+#include "verify_front.hpp"
 #include "verify_terms.hpp"
 
 namespace cap {
@@ -153,19 +159,25 @@ int upload_lines(const pairing::g2_affine& q1, const pairing::g2_affine& q2, Lin
   return CAPGPU_OK;
 }
 
+// enqueues `count` checks whose G1 inputs are already on the device; verdicts to d_ok (device)
+int launch_checks(const g1_affine* d_p, const g1_affine* d_r, size_t count, const p29::line_coeffs* l1,
+                  const p29::line_coeffs* l2, int* d_ok, hipStream_t s, int form) {
+  if (form == CAPGPU_PAIRING_WAVE)
+    launch("k_pairing_check2_wave", k_pairing_check2_wave,
+           dim3((unsigned)((count + pw::kGroupsPerWave - 1) / pw::kGroupsPerWave)), dim3(64), 0, s, d_p, d_r,
+           (uint32_t)count, l1, l2, d_ok);
+  else
+    launch("k_pairing_check2", k_pairing_check2, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, s, d_p, d_r,
+           (uint32_t)count, l1, l2, d_ok);
+  return take_launch_error();
+}
+
 // verdicts of `count` checks whose G1 inputs are already on the device
 int run_checks(const g1_affine* d_p, const g1_affine* d_r, size_t count, const Lines& L, int* ok_host, hipStream_t s,
                int form) {
   DevTmp<int> d_ok;
   CAP_HIP(d_ok.alloc(count));
-  if (form == CAPGPU_PAIRING_WAVE)
-    launch("k_pairing_check2_wave", k_pairing_check2_wave,
-           dim3((unsigned)((count + pw::kGroupsPerWave - 1) / pw::kGroupsPerWave)), dim3(64), 0, s, d_p, d_r,
-           (uint32_t)count, (const p29::line_coeffs*)L.d1.p, (const p29::line_coeffs*)L.d2.p, d_ok.p);
-  else
-    launch("k_pairing_check2", k_pairing_check2, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, s, d_p, d_r,
-           (uint32_t)count, (const p29::line_coeffs*)L.d1.p, (const p29::line_coeffs*)L.d2.p, d_ok.p);
-  int rc = take_launch_error();
+  int rc = launch_checks(d_p, d_r, count, L.d1.p, L.d2.p, d_ok.p, s, form);
   if (rc) return rc;
   CAP_HIP(hipMemcpyAsync(ok_host, d_ok.p, sizeof(int) * count, hipMemcpyDeviceToHost, s));
   CAP_HIP(hipStreamSynchronize(s));
@@ -238,6 +250,442 @@ int verify_each(const capgpu_verifying_key* const* vks, const pairing::g2_affine
   rc = run_checks(d_a, d_nb, m, L, ok.data(), c.stream, form);
   if (rc) return rc;
   for (size_t k = 0; k < m; k++) ok_out[idx[k]] = ok[k];
+  return CAPGPU_OK;
+}
+
+// ---- the block verifier: front end, weights, fold, two one-shot MSMs, one check (K13) -----------------------------------
+// capgpu_plonk_verify_block_dev / _resident: everything from the proofs' bytes to the verdicts is enqueued on the
+// context's stream and the host waits once.  verify_front.hpp has the term order and the weight rule.
+struct FrontArgs {
+  const uint8_t* proofs;          // count x capgpu_proof
+  const fe* pubs;                 // count rows of pub_stride
+  const vf::DevVk* const* keys;   // the call's keys
+  const uint32_t* meta;           // per proof: key index, message offset, message length, 0
+  const uint8_t* msgs;
+  uint8_t *state, *pre, *app, *ubytes;  // per proof: 64, pre_stride, vf::kAppBytes, 32 bytes
+  int* valid;
+  fe* sc;                         // count x vf::kTerms
+  uint32_t pub_stride, pre_stride, count;
+};
+
+// proof p's point of own term t (< vf::kOwnTerms): the 13 points of a capgpu_proof are contiguous
+__device__ __forceinline__ uint32_t own_point_offset(uint32_t t) {
+  if (t == vf::kTermWzeta || t == vf::kTermBWzeta) return td::kPrOpen;
+  if (t == vf::kTermWzetaW || t == vf::kTermBWzetaW) return td::kPrShifted;
+  return 64 * (t - vf::kTermWires);  // wires, z, quotient parts in the struct's order
+}
+
+// One wavefront per proof: verify.hip's verifier_terms, in its order.  Lanes 0..12 check and compress the proof's points,
+// lanes 13..22 its evaluations, all lanes stride over the public inputs, the message and the key's prefix; the wavefront
+// draws the seven challenges; the lanes stride over PI(zeta); lane 0 derives the scalars.
+__global__ __launch_bounds__(64) void k_verify_front(FrontArgs a) {
+  __shared__ fe sh[64];
+  const uint32_t p = blockIdx.x, t = threadIdx.x;
+  if (p >= a.count) return;
+  const uint8_t* pr = a.proofs + (size_t)p * td::kPrBytes;
+  const uint32_t moff = a.meta[4 * p + 1], mlen = a.meta[4 * p + 2];
+  const vf::DevVk* vk = a.keys[a.meta[4 * p]];
+  const uint32_t nin = vk->num_inputs;
+  const fe* pubs = a.pubs + (size_t)p * a.pub_stride;
+  uint8_t* pre = a.pre + (size_t)p * a.pre_stride;
+  uint8_t* app = a.app + (size_t)p * vf::kAppBytes;
+  uint8_t* st = a.state + (size_t)p * 64;
+  fe* sc = a.sc + (size_t)p * vf::kTerms;
+  bool ok = true;
+  if (t < 13) {
+    const g1_affine pt = *(const g1_affine*)(pr + 64 * t);
+    ok = vf::g1_valid(pt);
+    td::compress_g1(pt, app + (t < 11 ? 32 * t : 32 * (t + 10)));  // the two openings follow the ten evaluations
+  } else if (t < 23) {
+    const fe e = *(const fe*)(pr + td::kPrWireEvals + 32 * (t - 13));
+    ok = !Fr::geq_mod(e);
+    td::serialize_fr(e, app + td::kAppEvals + 32 * (t - 13));
+  }
+  for (uint32_t j = t; j < nin; j += 64) {
+    const fe v = pubs[j];
+    ok = ok && !Fr::geq_mod(v);
+    td::serialize_fr(v, pre + mlen + vf::kPrefixBytes + 32 * j);
+  }
+  for (uint32_t k = t; k < mlen; k += 64) pre[k] = a.msgs[moff + k];
+  for (uint32_t k = t; k < vf::kPrefixBytes; k += 64) pre[mlen + k] = vk->prefix[k];
+  st[t] = 0;
+  bool valid = __syncthreads_and(ok) != 0;
+  fe beta, gamma, alpha, zeta, v, u, zh;
+  if (valid) {
+    td::KeccakTabs<td::LaneDev> tabs;
+    tabs.init();
+    const uint32_t lpre = mlen + vf::kPrefixBytes + 32 * nin;
+    auto draw = [&](uint32_t lapp) {
+      td::transcript_challenge<td::LaneDev>(st, pre, lpre, app, lapp, tabs);
+      return td::reduce48(st);
+    };
+    (void)draw(td::kAppZ);  // plookup's tau
+    beta = draw(td::kAppZ);
+    gamma = draw(td::kAppZ);
+    alpha = draw(td::kAppQuot);
+    zeta = draw(td::kAppEvals);
+    v = draw(vf::kAppOpen);
+    u = draw(vf::kAppBytes);
+    valid = vf::vanishing(zeta, vk->n, &zh);
+  }
+  if (!valid) {  // uniform: every lane saw the same flags and challenges
+    for (uint32_t k = t; k < vf::kTerms; k += 64) sc[k] = Fr::zero();
+    if (t < 32) a.ubytes[(size_t)p * 32 + t] = 0;
+    if (t == 0) a.valid[p] = 0;
+    return;
+  }
+  sh[t] = vf::pi_partial(pubs, nin, t, 64, zeta, zh, vk->omega, vk->n_mont);
+  __syncthreads();
+  if (t == 0) {
+    fe pi = sh[0];
+#pragma unroll 1
+    for (int i = 1; i < 64; i++) pi = Fr::add(pi, sh[i]);
+    const vf::FrontIn in{(const fe*)(pr + td::kPrWireEvals), vk->k, beta, gamma, alpha, zeta, v, u, vk->omega, vk->n_mont,
+                         zh, pi, vk->n};
+    vf::front_scalars(in, sc);
+    td::serialize_fr(u, a.ubytes + (size_t)p * 32);
+    a.valid[p] = 1;
+  }
+}
+
+// S = Keccak-256 of the block's u bytes: one wavefront
+__global__ __launch_bounds__(64) void k_verify_seed(const uint8_t* __restrict__ ubytes, uint32_t count, uint8_t* __restrict__ S) {
+  td::KeccakTabs<td::LaneDev> tabs;
+  tabs.init();
+  vf::weight_seed<td::LaneDev>(ubytes, count, tabs, S);
+}
+// r_i, one wavefront per proof
+__global__ __launch_bounds__(64) void k_verify_weights(const uint8_t* __restrict__ S, uint32_t count, fe* __restrict__ w) {
+  __shared__ uint8_t idx8[8], dig[32];
+  const uint32_t i = blockIdx.x;
+  if (i >= count) return;
+  td::KeccakTabs<td::LaneDev> tabs;
+  tabs.init();
+  const fe r = vf::weight<td::LaneDev>(S, i, tabs, idx8, dig);
+  if (threadIdx.x == 0) w[i] = r;
+}
+
+// The points and weighted scalars of the two MSMs: A over [0, 2 count), B's own terms over the next 13 count.  One thread
+// per (proof, own term).  An invalid proof contributes points at infinity and zero scalars.
+__global__ __launch_bounds__(64) void k_verify_gather(const uint8_t* __restrict__ proofs, const fe* __restrict__ sc,
+                                                      const fe* __restrict__ w, const int* __restrict__ valid,
+                                                      uint32_t count, g1_affine* __restrict__ pts, fe* __restrict__ out) {
+  const uint32_t g = blockIdx.x * 64 + threadIdx.x;
+  if (g >= count * vf::kOwnTerms) return;
+  const uint32_t i = g / vf::kOwnTerms, t = g % vf::kOwnTerms;
+  const uint32_t at = t < vf::kATerms ? vf::kATerms * i + t
+                                      : vf::kATerms * count + (vf::kOwnTerms - vf::kATerms) * i + (t - vf::kATerms);
+  g1_affine pt;
+  fe s = Fr::zero();
+  pt.x = Fq::zero();
+  pt.y = Fq::zero();
+  if (valid[i]) {
+    pt = *(const g1_affine*)(proofs + (size_t)i * td::kPrBytes + own_point_offset(t));
+    s = Fr::mul(w[i], sc[(size_t)i * vf::kTerms + t]);
+  }
+  pts[at] = pt;
+  out[at] = s;
+}
+// Block (k, j): sum over the valid proofs i of key k of r_i s_ij for key term j, lanes striding over the proofs; written
+// with the key's point behind the own terms of B
+__global__ __launch_bounds__(64) void k_verify_fold(const vf::DevVk* const* __restrict__ keys,
+                                                    const uint32_t* __restrict__ meta, const fe* __restrict__ sc,
+                                                    const fe* __restrict__ w, const int* __restrict__ valid,
+                                                    uint32_t count, g1_affine* __restrict__ pts, fe* __restrict__ out) {
+  __shared__ fe sh[64];
+  const uint32_t k = blockIdx.x, j = blockIdx.y, t = threadIdx.x;
+  fe acc = Fr::zero();
+  for (uint32_t i = t; i < count; i += 64)
+    if (meta[4 * i] == k && valid[i]) acc = Fr::add(acc, Fr::mul(w[i], sc[(size_t)i * vf::kTerms + vf::kOwnTerms + j]));
+  sh[t] = acc;
+  __syncthreads();
+  for (uint32_t s = 32; s >= 1; s >>= 1) {
+    if (t < s) sh[t] = Fr::add(sh[t], sh[t + s]);
+    __syncthreads();
+  }
+  if (t == 0) {
+    const uint32_t at = vf::kOwnTerms * count + vf::kKeyTerms * k + j;
+    pts[at] = keys[k]->pts[j];
+    out[at] = sh[0];
+  }
+}
+// the two sums to affine form, B negated: what the check takes
+__global__ __launch_bounds__(64) void k_verify_affine(const g1_jac* __restrict__ sums, g1_affine* __restrict__ a_out,
+                                                      g1_affine* __restrict__ negb_out) {
+  if (blockIdx.x || threadIdx.x) return;
+  const g1_jac in[2] = {sums[0], sums[1]};
+  g1_affine o[2];
+  td::to_affine(in, 2, o);
+  if (!G1::is_inf(o[1])) o[1].y = Fq::neg(o[1].y);
+  a_out[0] = o[0];
+  negb_out[0] = o[1];
+}
+// The unweighted terms of every proof for k_verify_terms: one thread per (proof, term); scalars as canonical integers
+__global__ __launch_bounds__(64) void k_verify_each_terms(const uint8_t* __restrict__ proofs,
+                                                          const vf::DevVk* const* __restrict__ keys,
+                                                          const uint32_t* __restrict__ meta, const fe* __restrict__ sc,
+                                                          const int* __restrict__ valid, uint32_t count,
+                                                          g1_affine* __restrict__ pts, fe* __restrict__ out,
+                                                          uint32_t* __restrict__ first, uint32_t* __restrict__ na) {
+  const uint32_t g = blockIdx.x * 64 + threadIdx.x;
+  if (g >= count * vf::kTerms) return;
+  const uint32_t i = g / vf::kTerms, t = g % vf::kTerms;
+  g1_affine pt;
+  fe s = Fr::zero();
+  pt.x = Fq::zero();
+  pt.y = Fq::zero();
+  if (valid[i]) {
+    pt = t < vf::kOwnTerms ? *(const g1_affine*)(proofs + (size_t)i * td::kPrBytes + own_point_offset(t))
+                           : keys[meta[4 * i]]->pts[t - vf::kOwnTerms];
+    s = Fr::from_mont(sc[g]);
+  }
+  pts[g] = pt;
+  out[g] = s;
+  if (t == 0) {
+    first[i] = g;
+    na[i] = vf::kATerms;
+    if (i == count - 1) first[count] = count * vf::kTerms;
+  }
+}
+// out[0] = the block's check and every proof valid; out[1 + i] = proof i's check and its flag (each_ok null: out[0] only)
+__global__ __launch_bounds__(64) void k_verify_verdicts(const int* __restrict__ valid, const int* __restrict__ block_ok,
+                                                        const int* __restrict__ each_ok, uint32_t count,
+                                                        int* __restrict__ out) {
+  bool all = true;
+  for (uint32_t i = threadIdx.x; i < count; i += 64) {
+    const bool v = valid[i] != 0;
+    all = all && v;
+    if (each_ok) out[1 + i] = (v && each_ok[i]) ? 1 : 0;
+  }
+  const bool every = __syncthreads_and(all) != 0;
+  if (threadIdx.x == 0) out[0] = (every && block_ok[0]) ? 1 : 0;
+}
+
+// ---- uploaded verifying keys --------------------------------------------------------------------------------------------
+struct VkRecord {
+  vf::DevVk host;
+  std::mutex mu;
+  std::map<int, vf::DevVk*> dev;  // context slot -> replica
+  void drop_replicas() {
+    std::lock_guard<std::mutex> lk(mu);
+    for (auto& kv : dev) (void)hipFree(kv.second);
+    dev.clear();
+  }
+  ~VkRecord() { drop_replicas(); }
+};
+std::mutex g_vk_mu;
+std::map<uint64_t, std::shared_ptr<VkRecord>> g_vks;
+std::atomic<uint64_t> g_block_calls{0}, g_block_waits{0};
+
+// the key's table on context c, copied there on first use
+int vk_on_context(VkRecord& r, Context& c, const vf::DevVk** out) {
+  std::lock_guard<std::mutex> lk(r.mu);
+  auto it = r.dev.find(c.slot);
+  if (it == r.dev.end()) {
+    vf::DevVk* d = nullptr;
+    CAP_HIP(hipMalloc(&d, sizeof(vf::DevVk)));
+    hipError_t e = hipMemcpyAsync(d, &r.host, sizeof(vf::DevVk), hipMemcpyHostToDevice, c.stream);
+    if (e != hipSuccess) {
+      (void)hipFree(d);
+      return hip_fail(e, "hipMemcpyAsync(verifying key)");
+    }
+    it = r.dev.emplace(c.slot, d).first;
+  }
+  *out = it->second;
+  return CAPGPU_OK;
+}
+
+// the prepared lines of the last (beta_h, h) a context saw, by value
+struct LinesCache {
+  uint64_t words[32];
+  Lines L;
+};
+std::mutex g_lines_mu;
+std::map<int, std::unique_ptr<LinesCache>> g_lines;
+int lines_on_context(Context& c, const uint64_t g2_h[16], const uint64_t g2_beta_h[16], const pairing::g2_affine& h,
+                     const pairing::g2_affine& beta_h, const Lines** out) {
+  std::lock_guard<std::mutex> lk(g_lines_mu);
+  std::unique_ptr<LinesCache>& e = g_lines[c.slot];
+  if (!e || memcmp(e->words, g2_beta_h, 128) || memcmp(e->words + 16, g2_h, 128)) {
+    std::unique_ptr<LinesCache> fresh(new LinesCache);
+    memcpy(fresh->words, g2_beta_h, 128);
+    memcpy(fresh->words + 16, g2_h, 128);
+    int rc = upload_lines(beta_h, h, &fresh->L, c.stream);
+    if (rc) return rc;
+    if (e) CAP_HIP(hipStreamSynchronize(c.stream));  // nothing enqueued may still read the tables about to go
+    e = std::move(fresh);
+  }
+  *out = &e->L;
+  return CAPGPU_OK;
+}
+
+size_t up256(size_t v) { return (v + 255) / 256 * 256; }
+
+// body of the two entry points.  resident: pub_inputs and proofs are device memory
+int verify_block(const char* who, const uint64_t* vk_handles, const uint64_t g2_h[16], const uint64_t g2_beta_h[16],
+                 const uint64_t* pub_inputs, size_t num_inputs, const capgpu_proof* proofs, const uint8_t* const* ext_msgs,
+                 const size_t* ext_msg_lens, size_t count, int* block_ok_out, int* each_ok_out, bool resident) {
+  if (!block_ok_out || !g2_h || !g2_beta_h || (count && (!vk_handles || !proofs)) || count > ((size_t)1 << 24)) {
+    set_error("%s: bad argument (null pointer, or more than 2^24 proofs)", who);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  *block_ok_out = 0;
+  pairing::g2_affine h, beta_h;
+  int rc = open_key_from_abi(g2_h, g2_beta_h, &h, &beta_h);
+  if (rc) return rc;
+  // the call's keys, each once, in order of first appearance
+  std::vector<std::shared_ptr<VkRecord>> recs;
+  std::vector<uint32_t> meta(4 * count, 0);
+  size_t msg_bytes = 0, max_msg = 0;
+  {
+    std::map<uint64_t, uint32_t> seen;
+    std::lock_guard<std::mutex> lk(g_vk_mu);
+    for (size_t i = 0; i < count; i++) {
+      auto s = seen.find(vk_handles[i]);
+      if (s == seen.end()) {
+        auto it = g_vks.find(vk_handles[i]);
+        if (it == g_vks.end()) {
+          set_error("%s: proof %zu names the unknown verifying-key handle %llu", who, i, (unsigned long long)vk_handles[i]);
+          return CAPGPU_ERR_INVALID_ARG;
+        }
+        s = seen.emplace(vk_handles[i], (uint32_t)recs.size()).first;
+        recs.push_back(it->second);
+      }
+      meta[4 * i] = s->second;
+    }
+  }
+  for (const auto& r : recs)
+    if (r->host.num_inputs > num_inputs) {
+      set_error("%s: rows of %zu public inputs, a key expects %u", who, num_inputs, r->host.num_inputs);
+      return CAPGPU_ERR_INVALID_ARG;
+    }
+  if (count && num_inputs && !pub_inputs) {
+    set_error("%s: bad argument (no public inputs)", who);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  for (size_t i = 0; i < count; i++) {
+    const size_t len = (ext_msgs && ext_msg_lens && ext_msgs[i]) ? ext_msg_lens[i] : 0;
+    if (len > ((size_t)1 << 20)) {
+      set_error("%s: message %zu has %zu bytes (the limit is 2^20)", who, i, len);
+      return CAPGPU_ERR_INVALID_ARG;
+    }
+    meta[4 * i + 1] = (uint32_t)msg_bytes;
+    meta[4 * i + 2] = (uint32_t)len;
+    msg_bytes += len;
+    max_msg = std::max(max_msg, len);
+  }
+  if (msg_bytes >= ((size_t)1 << 31)) {
+    set_error("%s: %zu message bytes in one call (the limit is 2^31 - 1)", who, msg_bytes);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  CAP_CHECK_INIT();
+  if (count == 0) {
+    *block_ok_out = 1;
+    return CAPGPU_OK;
+  }
+  std::vector<uint8_t> msgs(msg_bytes ? msg_bytes : 1);
+  for (size_t i = 0; i < count; i++)
+    if (meta[4 * i + 2]) memcpy(&msgs[meta[4 * i + 1]], ext_msgs[i], meta[4 * i + 2]);
+
+  Context& c = ctx();
+  Entry lk(c);
+  const Lines* L = nullptr;
+  rc = lines_on_context(c, g2_h, g2_beta_h, h, beta_h, &L);
+  if (rc) return rc;
+  const size_t nkeys = recs.size();
+  std::vector<const vf::DevVk*> keytab(nkeys);
+  for (size_t k = 0; k < nkeys; k++)
+    if ((rc = vk_on_context(*recs[k], c, &keytab[k]))) return rc;
+
+  // the workspace, carved out of the context's staging scratch
+  const size_t pre_stride = (max_msg + vf::kPrefixBytes + 32 * num_inputs + 15) / 16 * 16;
+  const size_t msm_pts = vf::kOwnTerms * count + vf::kKeyTerms * nkeys, each_pts = each_ok_out ? vf::kTerms * count : 0;
+  size_t at = 0;
+  auto carve = [&](size_t bytes) {
+    const size_t o = at;
+    at += up256(bytes ? bytes : 1);
+    return o;
+  };
+  const size_t o_proofs = carve(resident ? 0 : sizeof(capgpu_proof) * count),
+               o_pubs = carve(resident ? 0 : sizeof(fe) * num_inputs * count), o_meta = carve(16 * count),
+               o_msgs = carve(msg_bytes), o_keys = carve(sizeof(void*) * nkeys), o_state = carve(64 * count),
+               o_pre = carve(pre_stride * count), o_app = carve((size_t)vf::kAppBytes * count), o_ub = carve(32 * count),
+               o_seed = carve(32), o_valid = carve(sizeof(int) * count), o_sc = carve(sizeof(fe) * vf::kTerms * count),
+               o_w = carve(sizeof(fe) * count), o_mpts = carve(sizeof(g1_affine) * msm_pts),
+               o_msc = carve(sizeof(fe) * msm_pts), o_desc = carve(sizeof(MsmVarDesc) * 2), o_sums = carve(sizeof(g1_jac) * 2),
+               o_ab = carve(sizeof(g1_affine) * 2), o_bok = carve(sizeof(int)), o_epts = carve(sizeof(g1_affine) * each_pts),
+               o_esc = carve(sizeof(fe) * each_pts), o_first = carve(sizeof(uint32_t) * (count + 1)),
+               o_na = carve(sizeof(uint32_t) * count), o_ea = carve(each_ok_out ? sizeof(g1_affine) * count : 0),
+               o_enb = carve(each_ok_out ? sizeof(g1_affine) * count : 0), o_eok = carve(sizeof(int) * count),
+               o_out = carve(sizeof(int) * (count + 1));
+  const MsmVarDesc desc[2] = {{0, 0, (uint32_t)(vf::kATerms * count)},
+                              {(uint64_t)(vf::kATerms * count), (uint32_t)(vf::kATerms * count),
+                               (uint32_t)(msm_pts - vf::kATerms * count)}};
+  const MsmVarPlan pl = msm_var_plan(desc[1].n, msm_pts, 2);
+  if ((rc = scratch_reserve(c.stage_a, at))) return rc;
+  if ((rc = scratch_reserve(c.msm_ws, pl.workspace_bytes))) return rc;
+  char* d = (char*)c.stage_a.p;
+  hipStream_t s = c.stream;
+  const uint8_t* d_proofs = resident ? (const uint8_t*)proofs : (const uint8_t*)(d + o_proofs);
+  const fe* d_pubs = resident ? (const fe*)pub_inputs : (const fe*)(d + o_pubs);
+  if (!resident) {
+    CAP_HIP(hipMemcpyAsync(d + o_proofs, proofs, sizeof(capgpu_proof) * count, hipMemcpyHostToDevice, s));
+    if (num_inputs) CAP_HIP(hipMemcpyAsync(d + o_pubs, pub_inputs, sizeof(fe) * num_inputs * count, hipMemcpyHostToDevice, s));
+  }
+  CAP_HIP(hipMemcpyAsync(d + o_meta, meta.data(), 16 * count, hipMemcpyHostToDevice, s));
+  if (msg_bytes) CAP_HIP(hipMemcpyAsync(d + o_msgs, msgs.data(), msg_bytes, hipMemcpyHostToDevice, s));
+  CAP_HIP(hipMemcpyAsync(d + o_keys, keytab.data(), sizeof(void*) * nkeys, hipMemcpyHostToDevice, s));
+  CAP_HIP(hipMemcpyAsync(d + o_desc, desc, sizeof desc, hipMemcpyHostToDevice, s));
+
+  const uint32_t n = (uint32_t)count;
+  const vf::DevVk* const* d_keys = (const vf::DevVk* const*)(d + o_keys);
+  const uint32_t* d_meta = (const uint32_t*)(d + o_meta);
+  int* d_valid = (int*)(d + o_valid);
+  fe *d_sc = (fe*)(d + o_sc), *d_w = (fe*)(d + o_w), *d_msc = (fe*)(d + o_msc);
+  g1_affine *d_mpts = (g1_affine*)(d + o_mpts), *d_ab = (g1_affine*)(d + o_ab);
+  FrontArgs fa{d_proofs, d_pubs, d_keys, d_meta, (const uint8_t*)(d + o_msgs), (uint8_t*)(d + o_state),
+               (uint8_t*)(d + o_pre), (uint8_t*)(d + o_app), (uint8_t*)(d + o_ub), d_valid, d_sc,
+               (uint32_t)num_inputs, (uint32_t)pre_stride, n};
+  launch("k_verify_front", k_verify_front, dim3(n), dim3(64), 0, s, fa);
+  launch("k_verify_seed", k_verify_seed, dim3(1), dim3(64), 0, s, (const uint8_t*)(d + o_ub), n, (uint8_t*)(d + o_seed));
+  launch("k_verify_weights", k_verify_weights, dim3(n), dim3(64), 0, s, (const uint8_t*)(d + o_seed), n, d_w);
+  launch("k_verify_gather", k_verify_gather, dim3((n * vf::kOwnTerms + 63) / 64), dim3(64), 0, s, d_proofs,
+         (const fe*)d_sc, (const fe*)d_w, (const int*)d_valid, n, d_mpts, d_msc);
+  launch("k_verify_fold", k_verify_fold, dim3((unsigned)nkeys, vf::kKeyTerms), dim3(64), 0, s, d_keys, d_meta,
+         (const fe*)d_sc, (const fe*)d_w, (const int*)d_valid, n, d_mpts, d_msc);
+  if ((rc = take_launch_error())) return rc;
+  rc = msm_var_run(d_mpts, msm_pts, d_msc, 0, (const MsmVarDesc*)(d + o_desc), desc[1].n, 2, 1, (g1_jac*)(d + o_sums),
+                   c.msm_ws.p, c.msm_ws.cap, s);
+  if (rc) return hip_fail((hipError_t)rc, "msm_var_run");
+  launch("k_verify_affine", k_verify_affine, dim3(1), dim3(64), 0, s, (const g1_jac*)(d + o_sums), d_ab, d_ab + 1);
+  if ((rc = take_launch_error())) return rc;
+  if ((rc = launch_checks(d_ab, d_ab + 1, 1, L->d1.p, L->d2.p, (int*)(d + o_bok), s, CAPGPU_PAIRING_WAVE))) return rc;
+  int form = CAPGPU_PAIRING_WAVE;
+  if (each_ok_out) {
+    form = current_form();
+    launch("k_verify_each_terms", k_verify_each_terms, dim3((n * vf::kTerms + 63) / 64), dim3(64), 0, s, d_proofs, d_keys,
+           d_meta, (const fe*)d_sc, (const int*)d_valid, n, (g1_affine*)(d + o_epts), (fe*)(d + o_esc),
+           (uint32_t*)(d + o_first), (uint32_t*)(d + o_na));
+    launch("k_verify_terms", k_verify_terms, dim3(n), dim3(kTermLanes), 0, s, (const g1_affine*)(d + o_epts),
+           (const fe*)(d + o_esc), (const uint32_t*)(d + o_first), (const uint32_t*)(d + o_na), (g1_affine*)(d + o_ea),
+           (g1_affine*)(d + o_enb));
+    if ((rc = take_launch_error())) return rc;
+    if ((rc = launch_checks((const g1_affine*)(d + o_ea), (const g1_affine*)(d + o_enb), count, L->d1.p, L->d2.p,
+                            (int*)(d + o_eok), s, form)))
+      return rc;
+  }
+  launch("k_verify_verdicts", k_verify_verdicts, dim3(1), dim3(64), 0, s, (const int*)d_valid, (const int*)(d + o_bok),
+         each_ok_out ? (const int*)(d + o_eok) : (const int*)nullptr, n, (int*)(d + o_out));
+  if ((rc = take_launch_error())) return rc;
+  std::vector<int> out(each_ok_out ? count + 1 : 1);
+  CAP_HIP(hipMemcpyAsync(out.data(), d + o_out, sizeof(int) * out.size(), hipMemcpyDeviceToHost, s));
+  g_block_calls.fetch_add(1, std::memory_order_relaxed);
+  g_block_waits.fetch_add(1, std::memory_order_relaxed);
+  CAP_HIP(hipStreamSynchronize(s));  // the call's one wait (also keeps the host arrays above alive until the copies are done)
+  g_wave_checks.fetch_add(1, std::memory_order_relaxed);
+  if (each_ok_out) (form == CAPGPU_PAIRING_WAVE ? g_wave_checks : g_lane_checks).fetch_add(count, std::memory_order_relaxed);
+  *block_ok_out = out[0];
+  if (each_ok_out) memcpy(each_ok_out, out.data() + 1, sizeof(int) * count);
   return CAPGPU_OK;
 }
 
@@ -335,10 +783,105 @@ int capgpu_pairing_stats(uint64_t* lane_checks_out, uint64_t* wave_checks_out) {
   return CAPGPU_OK;
 }
 
+// ---- the block verifier (verify_front.hpp; kernels above) ---------------------------------------------------------------
+// Checks a key once and keeps it for capgpu_plonk_verify_block_*: needs no device (a context gets its copy on first use)
+int capgpu_plonk_vk_upload(const capgpu_verifying_key* vk, uint64_t* vk_handle_out) {
+  if (!vk || !vk_handle_out) {
+    set_error("capgpu_plonk_vk_upload: bad argument");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  const uint64_t n = vk->domain_size;
+  if (n < 4 || (n & (n - 1)) || n > ((uint64_t)1 << 28)) {
+    set_error("capgpu_plonk_vk_upload: domain_size %llu is not a power of two in [4, 2^28]", (unsigned long long)n);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  if (vk->num_inputs > n) {
+    set_error("capgpu_plonk_vk_upload: num_inputs %llu exceeds the domain", (unsigned long long)vk->num_inputs);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  auto rec = std::make_shared<VkRecord>();
+  vf::DevVk& k = rec->host;
+  memset(&k, 0, sizeof k);
+  for (int i = 0; i < 5; i++) {
+    memcpy(&k.k[i], vk->k[i], 32);
+    if (Fr::geq_mod(k.k[i])) {
+      set_error("capgpu_plonk_vk_upload: k[%d] is not canonical", i);
+      return CAPGPU_ERR_INVALID_ARG;
+    }
+  }
+  for (int i = 0; i < 18; i++) {
+    const bool sel = i < 13;
+    k.pts[i] = g1_from_abi(sel ? vk->selector_comms[i] : vk->sigma_comms[i - 13]);
+    if (!g1_abi_on_curve(k.pts[i])) {
+      set_error("capgpu_plonk_vk_upload: %s[%d] is not a canonical point of the curve", sel ? "selector_comms" : "sigma_comms",
+                sel ? i : i - 13);
+      return CAPGPU_ERR_INVALID_ARG;
+    }
+  }
+  k.pts[18].x = Fq::one();
+  k.pts[18].y = Fq::dbl(Fq::one());
+  k.n = n;
+  k.num_inputs = (uint32_t)vk->num_inputs;
+  fe nw = Fr::zero();
+  nw.v[0] = (uint32_t)n;
+  nw.v[1] = (uint32_t)(n >> 32);
+  k.n_mont = Fr::to_mont(nw);
+  k.omega = vf::domain_generator(n);
+  vf::prefix_bytes(k, k.prefix);
+  const uint64_t hnd = rt().next_handle.fetch_add(1);
+  std::lock_guard<std::mutex> lk(g_vk_mu);
+  g_vks[hnd] = rec;
+  *vk_handle_out = hnd;
+  return CAPGPU_OK;
+}
+int capgpu_plonk_vk_release(uint64_t vk_handle) {
+  std::shared_ptr<VkRecord> rec;  // its device copies go when the last call that uses it has returned
+  std::lock_guard<std::mutex> lk(g_vk_mu);
+  auto it = g_vks.find(vk_handle);
+  if (it == g_vks.end()) {
+    set_error("capgpu_plonk_vk_release: unknown verifying-key handle %llu", (unsigned long long)vk_handle);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  rec = it->second;
+  g_vks.erase(it);
+  return CAPGPU_OK;
+}
+// txn_batch_verify (src/lib.rs:455-529) for a block: transcripts, scalars, group arithmetic and the pairing check on the
+// device, one host wait.  *block_ok_out: the predicate of capgpu_plonk_batch_verify; each_ok_out[i]: capgpu_plonk_verify's
+int capgpu_plonk_verify_block_dev(const uint64_t* vk_handles, const uint64_t g2_h[16], const uint64_t g2_beta_h[16],
+                                  const uint64_t* pub_inputs, size_t num_inputs, const capgpu_proof* proofs,
+                                  const uint8_t* const* ext_msgs, const size_t* ext_msg_lens, size_t count,
+                                  int* block_ok_out, int* each_ok_out) {
+  return verify_block("capgpu_plonk_verify_block_dev", vk_handles, g2_h, g2_beta_h, pub_inputs, num_inputs, proofs, ext_msgs,
+                      ext_msg_lens, count, block_ok_out, each_ok_out, false);
+}
+int capgpu_plonk_verify_block_resident(const uint64_t* vk_handles, const uint64_t g2_h[16], const uint64_t g2_beta_h[16],
+                                       const void* d_pub_inputs, size_t num_inputs, const void* d_proofs,
+                                       const uint8_t* const* ext_msgs, const size_t* ext_msg_lens, size_t count,
+                                       int* block_ok_out, int* each_ok_out) {
+  return verify_block("capgpu_plonk_verify_block_resident", vk_handles, g2_h, g2_beta_h, (const uint64_t*)d_pub_inputs,
+                      num_inputs, (const capgpu_proof*)d_proofs, ext_msgs, ext_msg_lens, count, block_ok_out, each_ok_out,
+                      true);
+}
+int capgpu_verify_sync_stats(uint64_t* block_calls_out, uint64_t* stream_waits_out) {
+  if (block_calls_out) *block_calls_out = g_block_calls.load(std::memory_order_relaxed);
+  if (stream_waits_out) *stream_waits_out = g_block_waits.load(std::memory_order_relaxed);
+  return CAPGPU_OK;
+}
+
 }  // extern "C"
 
 // ---- for the batch verifier (verify.hip) ---------------------------------------------------------------------------
 namespace cap {
+// capgpu_shutdown: the contexts go, and with them what the block verifier keeps on them (uploaded keys stay, on the host)
+void verify_block_reset() {
+  {
+    std::lock_guard<std::mutex> lk(g_vk_mu);
+    for (auto& kv : g_vks) kv.second->drop_replicas();
+  }
+  std::lock_guard<std::mutex> lk(g_lines_mu);
+  g_lines.clear();
+}
 int pairing_form() { return current_form(); }
 int pairing_check2_wave_dev(const g1_affine& p, const pairing::g2_affine& q1, const g1_affine& r,
                             const pairing::g2_affine& q2, int* ok_out) {

@@ -1216,6 +1216,78 @@ def plonk_verify_dev(vk: VerifyingKey, g2_h: np.ndarray, g2_beta_h: np.ndarray, 
     return bool(ok.value)
 
 
+# ---- the block verifier (capgpu_plonk_verify_block_*; needs init()) ------------------------------------------------------
+def plonk_vk_upload(vk: VerifyingKey) -> int:
+    """Checks a verifying key once and keeps it for plonk_verify_block (capgpu_plonk_vk_upload) -> handle"""
+    h = ctypes.c_uint64(0)
+    check(load().capgpu_plonk_vk_upload(ctypes.byref(vk), ctypes.byref(h)))
+    return h.value
+
+
+def plonk_vk_release(vk_handle: int):
+    check(load().capgpu_plonk_vk_release(ctypes.c_uint64(vk_handle)))
+
+
+def plonk_verify_block(vk_handles, g2_h: np.ndarray, g2_beta_h: np.ndarray, pub_rows, proofs, ext_msgs=None,
+                       each: bool = False, num_inputs: int | None = None):
+    """A whole block decided on the device with one host wait.  vk_handles[i]: proof i's uploaded key; pub_rows: (count,
+    num_inputs, 4) array in plonk_prove_multi's layout (a key with fewer inputs uses the first of its row) or a DevBuf of
+    that content; proofs: a list of Proof / a (Proof * count) array, or a DevBuf holding the contiguous array - the resident
+    entry point is taken when both are DevBufs (then num_inputs must be given).  Returns block_ok, or (block_ok, each_ok)
+    with each=True: each_ok[i] == plonk_verify(...) of proof i and block_ok == all(each_ok)."""
+    count = len(vk_handles)
+    handles = (ctypes.c_uint64 * max(count, 1))(*vk_handles)
+    msgs_arg = lens_arg = None
+    keep = []
+    if ext_msgs is not None and count:
+        if len(ext_msgs) != count:
+            raise ValueError("plonk_verify_block: one message per proof")
+        msgs_arg = (ctypes.POINTER(ctypes.c_uint8) * count)()
+        lens_arg = (ctypes.c_size_t * count)()
+        for i, m in enumerate(ext_msgs):
+            m = bytes(m) if m else b""
+            keep.append((ctypes.c_uint8 * max(len(m), 1)).from_buffer_copy(m or b"\0"))
+            msgs_arg[i] = ctypes.cast(keep[-1], ctypes.POINTER(ctypes.c_uint8))
+            lens_arg[i] = len(m)
+    block_ok = ctypes.c_int(0)
+    each_ok = np.zeros(max(count, 1), dtype=np.int32)
+    each_arg = each_ok.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if each else None
+    h2 = _p(np.ascontiguousarray(g2_h, dtype=np.uint64))
+    bh = _p(np.ascontiguousarray(g2_beta_h, dtype=np.uint64))
+    if isinstance(proofs, DevBuf) != isinstance(pub_rows, DevBuf):
+        raise ValueError("plonk_verify_block: proofs and pub_rows must both be host data or both DevBufs")
+    if isinstance(proofs, DevBuf):
+        if num_inputs is None or proofs.nbytes < count * ctypes.sizeof(Proof) or pub_rows.nbytes < count * num_inputs * 32:
+            raise ValueError("plonk_verify_block: resident buffers need num_inputs and room for count proofs and rows")
+        check(load().capgpu_plonk_verify_block_resident(handles, h2, bh, pub_rows.ptr, ctypes.c_size_t(num_inputs),
+                                                        proofs.ptr, msgs_arg, lens_arg, ctypes.c_size_t(count),
+                                                        ctypes.byref(block_ok), each_arg))
+    else:
+        pub_rows = np.ascontiguousarray(pub_rows, dtype=np.uint64).reshape(-1)
+        if num_inputs is None:
+            num_inputs = pub_rows.size // (4 * count) if count else 0
+        if pub_rows.size != count * num_inputs * 4:
+            raise ValueError(f"plonk_verify_block: pub_rows must hold {count} x {num_inputs} elements")
+        if not isinstance(proofs, ctypes.Array):
+            arr = (Proof * max(count, 1))()
+            for i, pr in enumerate(proofs):
+                ctypes.memmove(ctypes.byref(arr[i]), ctypes.byref(pr), ctypes.sizeof(Proof))
+            proofs = arr
+        check(load().capgpu_plonk_verify_block_dev(handles, h2, bh, _p(pub_rows) if pub_rows.size else None,
+                                                   ctypes.c_size_t(num_inputs), proofs, msgs_arg, lens_arg,
+                                                   ctypes.c_size_t(count), ctypes.byref(block_ok), each_arg))
+    if each:
+        return bool(block_ok.value), each_ok[:count] != 0
+    return bool(block_ok.value)
+
+
+def verify_sync_stats() -> dict:
+    """block-verifier calls that reached the device, and the host waits on the stream they made (capgpu_verify_sync_stats)"""
+    a, b = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    check(load().capgpu_verify_sync_stats(ctypes.byref(a), ctypes.byref(b)))
+    return {"block_calls": a.value, "stream_waits": b.value}
+
+
 def proof_serialize(proof: Proof) -> bytes:
     buf = (ctypes.c_uint8 * 1024)()
     n = ctypes.c_size_t(0)

@@ -201,6 +201,32 @@ def prove_mixed(proving_keys, wires: np.ndarray, public_input_rows: np.ndarray, 
         raise TxnApiError.FailedSnark(f"Proof Creation failure: {e}") from e
 
 
+def upload_verifying_key(verifying_key: VerifyingKey) -> int:
+    """checks a verifying key once and keeps it for txn_batch_verify -> handle (release with release_verifying_key)"""
+    try:
+        return _lib.plonk_vk_upload(verifying_key.raw)
+    except _lib.CapGpuError as e:
+        raise TxnApiError.FailedSnark(f"Proof Verification failure: {e}") from e
+
+
+def release_verifying_key(handle: int) -> None:
+    _lib.plonk_vk_release(handle)
+
+
+def txn_batch_verify(vk_handles, g2_h: np.ndarray, g2_beta_h: np.ndarray, public_input_rows, proofs, ext_msgs=None,
+                     num_inputs: int | None = None) -> None:
+    """src/lib.rs:455-529 over uploaded keys: Ok(()) or TxnApiError::FailedSnark for the whole block, decided on the
+    device with one host wait (capgpu_plonk_verify_block_dev; _resident when proofs and rows are DevBufs).
+    public_input_rows: (count, max inputs, 4) as prove_mixed takes them; proofs: what prove_mixed returned."""
+    try:
+        ok = _lib.plonk_verify_block(vk_handles, g2_h, g2_beta_h, public_input_rows, proofs, ext_msgs,
+                                     num_inputs=num_inputs)
+    except (_lib.CapGpuError, ValueError) as e:
+        raise TxnApiError.FailedSnark(f"Proof Verification failure: {e}") from e
+    if not ok:
+        raise TxnApiError.FailedSnark("Proof Verification failure: WrongProof")
+
+
 def verify(verifying_key: VerifyingKey, public_inputs: np.ndarray, proof, ext_msg: bytes | None = None) -> None:
     """src/proof/transfer.rs:192-212 / mint.rs:124-140 / freeze.rs:162-178: Ok(()) or TxnApiError::FailedSnark.
     Runs on the host (pairing check); it does not need the GPU."""

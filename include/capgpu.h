@@ -740,6 +740,41 @@ int capgpu_pairing_stats(uint64_t* lane_checks_out, uint64_t* wave_checks_out);
 int capgpu_plonk_verify_dev(const capgpu_verifying_key* vk, const uint64_t g2_h[16], const uint64_t g2_beta_h[16],
                             const uint64_t* pub_inputs, size_t num_inputs, const uint8_t* ext_msg, size_t ext_msg_len,
                             const capgpu_proof* proof, int* ok_out);
+/* ---- the block verifier: a whole block decided on the device, one host wait ------------------------------------------
+ * Replaces txn_batch_verify (src/lib.rs:455-529) for a validator that replays blocks: each proof's transcript and its
+ * ~35 scalars are derived by one wavefront (k_verify_front), the block is folded with 128-bit weights into two one-shot
+ * MSMs (no window table) and one wave-form pairing check.  Only the preparation of the G2 lines of (beta_h, h) stays on
+ * the host, and a context keeps the last pair's lines.
+ *
+ * capgpu_plonk_vk_upload checks a key once - domain_size a power of two >= 4, every point canonical and on the curve,
+ * every k_i canonical; CAPGPU_ERR_INVALID_ARG names the field - and keeps its points, constants and transcript prefix
+ * under a process-wide handle (needs no device; a context gets its copy on first use).  capgpu_plonk_vk_release drops it;
+ * an unknown handle is CAPGPU_ERR_INVALID_ARG here and in the calls below.
+ *
+ * capgpu_plonk_verify_block_dev takes its arguments in capgpu_plonk_prove_multi's layouts: proofs one contiguous array,
+ * pub_inputs `count` rows of num_inputs (at least the largest count among the call's keys; a key with fewer uses the
+ * first of its row), ext_msgs / ext_msg_lens NULL or one entry per proof.  capgpu_plonk_verify_block_resident is the
+ * same with d_pub_inputs and d_proofs in device memory (never written); the messages stay host arrays.
+ *   *block_ok_out   the predicate of capgpu_plonk_batch_verify (up to the 2^-128 soundness of the weights);
+ *   each_ok_out[i]  (NULL, or count ints) capgpu_plonk_verify's verdict for proof i, from the unweighted terms through
+ *                   k_verify_terms and the pairing form in force, behind the block check and in the same wait.
+ * block_ok == all(each_ok).  A bad proof (off-curve, non-canonical, zeta in the domain) gets 0 and never fails the call;
+ * negative codes are for malformed arguments (unknown handle, num_inputs below a key's, G2 off the twist) and, after
+ * those checks, CAPGPU_ERR_NOT_INITIALISED.  count == 0: *block_ok_out = 1.  Conventions of capgpu_msm_g1_var_dev: the
+ * calling thread's context and stream, workspace from the context's scratch (capgpu_scratch_stats,
+ * capgpu_set_memory_limit).  capgpu_verify_sync_stats: block calls that reached the device, and host waits on the stream
+ * they made - one per call.  Either pointer may be NULL. */
+int capgpu_plonk_vk_upload(const capgpu_verifying_key* vk, uint64_t* vk_handle_out);
+int capgpu_plonk_vk_release(uint64_t vk_handle);
+int capgpu_plonk_verify_block_dev(const uint64_t* vk_handles, const uint64_t g2_h[16], const uint64_t g2_beta_h[16],
+                                  const uint64_t* pub_inputs, size_t num_inputs, const capgpu_proof* proofs,
+                                  const uint8_t* const* ext_msgs, const size_t* ext_msg_lens, size_t count,
+                                  int* block_ok_out, int* each_ok_out);
+int capgpu_plonk_verify_block_resident(const uint64_t* vk_handles, const uint64_t g2_h[16], const uint64_t g2_beta_h[16],
+                                       const void* d_pub_inputs, size_t num_inputs, const void* d_proofs,
+                                       const uint8_t* const* ext_msgs, const size_t* ext_msg_lens, size_t count,
+                                       int* block_ok_out, int* each_ok_out);
+int capgpu_verify_sync_stats(uint64_t* block_calls_out, uint64_t* stream_waits_out);
 /* ark-serialize 0.3 CanonicalSerialize bytes of the Proof as it sits inside a TransferNote / MintNote / FreezeNote
  * (src/transfer.rs:60): compressed G1 (32 B), Fr little-endian, Vec = u64 length prefix, plookup_proof = None.
  * 769 bytes; *len_out receives the size. */
