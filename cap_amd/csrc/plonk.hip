@@ -283,381 +283,19 @@ void parallel_for(uint32_t count, F&& fn) {
   pool.run(count, job);
 }
 
-// ---- launch helpers -----------------------------------------------------------------------------------------
-inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
+}  // namespace
+}  // namespace cap
 
-void pad_copy(hipStream_t s, fe* dst, size_t dst_outer, size_t dst_inner, const fe* src, size_t src_outer,
-              size_t src_inner, uint32_t inner, uint32_t count, size_t len, size_t total) {
-  if (count == 0 || total == 0) return;
-  launch("k_pad_copy", k_pad_copy, dim3(cdiv(total, kThreads), count), dim3(kThreads), 0, s, dst, dst_outer, dst_inner,
-         src, src_outer, src_inner, inner, len, total);
-}
+// the prover proper: launch wrappers, workspace, ProvePlan / ProveRun / ProveNeeds
+#include "prove_run.hpp"
 
-template <int OP, int REV>
-void scan_exclusive(hipStream_t s, const fe* in, fe* out, size_t len, size_t stride, uint32_t batch, fe* tot) {
-  uint32_t nblocks = cdiv(len, kScanBlock);
-  launch(OP == 0 ? "k_scan_local_mul" : "k_scan_local_add", k_scan_local<OP, REV>, dim3(nblocks, batch), dim3(kThreads),
-         0, s, in, out, len, stride, tot, nblocks);
-  if (nblocks > 1) {
-    launch("k_scan_totals", k_scan_totals<OP>, dim3(batch), dim3(64), 0, s, tot, nblocks);
-    launch("k_scan_apply", k_scan_apply<OP, REV>, dim3(nblocks, batch), dim3(kThreads), 0, s, out, len, stride,
-           (const fe*)tot, nblocks);
-  }
-}
-
-// Bytes of Context::ntt_scratch the transforms below ask for.  One expression each, shared with prove_needs
-// (capgpu_plonk_reserve sizes a context ahead from what prove_batch WOULD request).
-inline size_t ntt_scratch_inplace(size_t stride, size_t count) { return sizeof(fe) * stride * count; }
-inline size_t ntt_scratch_from(uint32_t log_n, size_t count) { return (sizeof(fe) << log_n) * count; }
-inline size_t ntt3_scratch(uint32_t log_mm, size_t count) { return (sizeof(fe) << log_mm) * 6 * count; }
-// ... of Context::stage_b for `cnt` host-resident witnesses on a domain of n points
-inline size_t wires_stage_bytes(size_t cnt, size_t n) { return sizeof(fe) * cnt * NW * n; }
-
-int run_ntt(hipStream_t s, uint32_t log_n, fe* data, size_t stride, uint32_t count, int dir, int coset) {
-  Context& c = ctx();
-  const NttDomain* dom = nullptr;
-  int rc = get_domain(log_n, &dom);
-  if (rc) return rc;
-  rc = scratch_reserve(c.ntt_scratch, ntt_scratch_inplace(stride, count));
-  if (rc) return rc;
-  rc = ntt_run(*dom, c.small, data, (fe*)c.ntt_scratch.p, stride, count, dir, coset, s);
-  if (rc) return hip_fail((hipError_t)rc, "ntt_run");
-  return CAPGPU_OK;
-}
-
-// out-of-place form: `count` arrays of src_len elements at src (src_stride apart; zero-extended to the transform
-// size inside the kernel) -> transforms at dst (dst_stride apart).  Saves the padded copy an in-place call needs.
-int run_ntt_from(hipStream_t s, uint32_t log_n, const fe* src, size_t src_stride, size_t src_len, fe* dst,
-                 size_t dst_stride, uint32_t count, int dir, int coset) {
-  Context& c = ctx();
-  const NttDomain* dom = nullptr;
-  int rc = get_domain(log_n, &dom);
-  if (rc) return rc;
-  rc = scratch_reserve(c.ntt_scratch, ntt_scratch_from(log_n, count));
-  if (rc) return rc;
-  NttIo io{};
-  io.src = src;
-  io.src_outer = src_stride;
-  io.src_inner = 0;
-  io.src_group = 1;
-  io.src_len = src_len;
-  io.dst_outer = dst_stride;
-  io.dst_inner = 0;
-  io.dst_group = 1;
-  rc = ntt_run(*dom, c.small, dst, (fe*)c.ntt_scratch.p, dst_stride, count, dir, coset, s, &io);
-  if (rc) return hip_fail((hipError_t)rc, "ntt_run");
-  return CAPGPU_OK;
-}
-
-// the quotient domain: N = 6n = 3 * 2^(log n + 1) points (ntt.hpp)
-int quot_domains(uint32_t log_mm, const Ntt3Domain** d3, const NttDomain** dm) {
-  int rc = get_domain3(log_mm, d3);
-  if (rc) return rc;
-  return get_domain(log_mm, dm);
-}
-// coset evaluations on the 6n domain of `count` polynomials read through io (one polynomial family per call)
-int run_ntt3_fwd(hipStream_t s, uint32_t log_mm, fe* data, uint32_t count, const NttIo& io) {
-  Context& c = ctx();
-  const Ntt3Domain* d3 = nullptr;
-  const NttDomain* dm = nullptr;
-  int rc = quot_domains(log_mm, &d3, &dm);
-  if (rc) return rc;
-  if ((rc = scratch_reserve(c.ntt_scratch, ntt3_scratch(log_mm, count)))) return rc;
-  rc = ntt3_forward(*d3, *dm, c.small, data, io, count, (fe*)c.ntt_scratch.p, s);
-  if (rc) return hip_fail((hipError_t)rc, "ntt3_forward");
-  return CAPGPU_OK;
-}
-int run_ntt3_inv(hipStream_t s, uint32_t log_mm, fe* data, uint32_t count) {
-  Context& c = ctx();
-  const Ntt3Domain* d3 = nullptr;
-  const NttDomain* dm = nullptr;
-  int rc = quot_domains(log_mm, &d3, &dm);
-  if (rc) return rc;
-  if ((rc = scratch_reserve(c.ntt_scratch, ntt3_scratch(log_mm, count)))) return rc;
-  rc = ntt3_inverse(*d3, *dm, c.small, data, count, (fe*)c.ntt_scratch.p, s);
-  if (rc) return hip_fail((hipError_t)rc, "ntt3_inverse");
-  return CAPGPU_OK;
-}
-
-int run_msm(hipStream_t s, const MsmBases& B, const fe* scalars, size_t outer_stride, uint32_t inner,
-            size_t inner_stride, size_t n, uint32_t batch, g1_jac* d_out) {
-  Context& c = ctx();
-  auto local = [&](size_t lo, size_t len) -> int {
-    int rc = scratch_reserve(c.msm_ws, msm_workspace_bytes(B, len, batch));
-    if (rc) return rc;
-    rc = msm_run(B, lo, scalars + lo, outer_stride, inner, inner_stride, len, batch, 1, d_out, c.msm_ws.p, c.msm_ws.cap, s);
-    return rc ? hip_fail((hipError_t)rc, "msm_run") : CAPGPU_OK;
-  };
-  if (!comm_shard_prover()) return local(0, n);
-  // Mode A of BASELINE config 4 (capgpu_plonk_shard_msm): every rank proves the same batch, each commitment MSM is cut
-  // by point range over the ranks and finished by one all-gather of 96-byte partials + G - 1 additions.
-  // All ranks then hold the same commitments, derive the same challenges and stay in lock step.  A rank whose local
-  // part fails still enters the exchange (comm_allgather_sum), so every rank leaves with an error.  Under the loopback
-  // communicator this process plays the ranks one after the other.
-  const size_t world = (size_t)comm_world();
-  const bool loop = comm_loopback();
-  for (size_t rank = loop ? 0 : (size_t)comm_rank(), last = loop ? world - 1 : rank; rank <= last; rank++) {
-    if (loop) comm_loopback_rank((int)rank);
-    const size_t base = n / world, rem = n % world;
-    const size_t lo = rank * base + std::min(rank, rem), len = base + (rank < rem ? 1 : 0);
-    int rc = comm_allgather_sum(d_out, batch, s, local(lo, len));
-    if (rc) return rc;
-  }
-  return CAPGPU_OK;
-}
-
-struct Carver {
-  char* base;
-  size_t off = 0;
-  explicit Carver(void* b) : base((char*)b) {}
-  template <class T>
-  T* take(size_t count) {
-    off = (off + 255) / 256 * 256;
-    T* p = base ? (T*)(base + off) : nullptr;
-    off += sizeof(T) * count;
-    return p;
-  }
-};
-
-struct BatchWs {
-  fe *wpoly, *wev, *pi, *num, *den, *pre, *sfx, *scan_tot, *inv_total, *zpoly, *coset, *pkc, *t, *pows, *pows_small, *pw, *batchpoly,
-      *hbuf, *quot, *evals, *eval_partial, *d_pub, *d_blind;
-  Chal* chal;
-  Chal* chal29;  // the same challenges in the internal form
-  uint32_t* flags;
-  g1_jac* comms;
-  EvalDesc* edesc;
-  LinTerm* terms;
-  const fe** key_ptrs;  // [2][P]: sigma evaluations / coset columns of every proof's key (mixed-key batches)
-  // device transcript only (capgpu_plonk_set_transcript): the proofs in ABI layout, zeta, and the transcript's bytes
-  uint8_t *d_proofs, *tr_state, *tr_pre, *tr_app;
-  uint32_t* tr_pre_len;
-  fe* zeta;
-  size_t total;
-};
-constexpr uint32_t kEvalChunks = 16;
-constexpr uint32_t kLinTerms = 29;
-static_assert(kLinTerms == (uint32_t)td::kLinScalars, "transcript_dev.hpp derives the scalars of k_lincomb's terms");
-
-BatchWs carve(void* base, const ProvingKey& K, uint32_t P, size_t num_inputs, bool coeffs, uint32_t tr_stride = 0) {
-  Carver c(base);
-  BatchWs w{};
-  size_t n = K.n, m = K.m, ps = K.ps;
-  w.wpoly = c.take<fe>((size_t)P * NW * ps);
-  // coefficient-form input: the witness VALUES round 2 reads are one forward transform of the caller's polynomials
-  w.wev = coeffs ? c.take<fe>((size_t)P * NW * n) : nullptr;
-  w.pi = c.take<fe>((size_t)P * n);
-  w.num = c.take<fe>((size_t)P * n);
-  w.den = c.take<fe>((size_t)P * n);
-  w.pre = c.take<fe>((size_t)P * n);
-  w.sfx = c.take<fe>((size_t)P * n);
-  w.scan_tot = c.take<fe>((size_t)P * 2 * (cdiv(ps, kScanBlock) + 1));
-  w.inv_total = c.take<fe>(P);
-  w.zpoly = c.take<fe>((size_t)P * ps);
-  w.coset = c.take<fe>((size_t)P * 7 * m);
-  w.pkc = K.recompute ? c.take<fe>((size_t)18 * m) : nullptr;
-  w.t = c.take<fe>((size_t)P * m);
-  w.pows = c.take<fe>((size_t)P * 4 * ps);
-  w.pw = c.take<fe>((size_t)P * 4 * 24);
-  w.pows_small = c.take<fe>((size_t)P * 4 * (kPowLow + (ps + kPowLow - 1) / kPowLow));
-  w.batchpoly = c.take<fe>((size_t)P * 2 * ps);
-  w.hbuf = c.take<fe>((size_t)P * 2 * ps);
-  w.quot = c.take<fe>((size_t)P * 2 * ps);
-  w.evals = c.take<fe>((size_t)P * 10);
-  w.eval_partial = c.take<fe>((size_t)P * 10 * kEvalChunks);
-  w.d_pub = c.take<fe>((size_t)P * (num_inputs ? num_inputs : 1));
-  w.d_blind = c.take<fe>((size_t)P * 13);
-  w.chal = c.take<Chal>(P);
-  w.chal29 = c.take<Chal>(P);
-  w.flags = c.take<uint32_t>(P);
-  w.comms = c.take<g1_jac>((size_t)P * 5);
-  w.edesc = c.take<EvalDesc>((size_t)P * 10);
-  w.terms = c.take<LinTerm>((size_t)P * kLinTerms);
-  w.key_ptrs = c.take<const fe*>((size_t)P * 2);
-  if (tr_stride) {  // (last: the host mode's layout is a prefix of this one)
-    w.d_proofs = c.take<uint8_t>((size_t)P * td::kPrBytes);
-    w.zeta = c.take<fe>(P);
-    w.tr_state = c.take<uint8_t>((size_t)P * 64);
-    w.tr_app = c.take<uint8_t>((size_t)P * td::kAppBytes);
-    w.tr_pre_len = c.take<uint32_t>(P);
-    w.tr_pre = c.take<uint8_t>((size_t)P * tr_stride);
-  }
-  w.total = c.off + 256;
-  return w;
-}
-
-// the 18 fixed polynomials -> coset evaluations on the 6n quotient domain
-int compute_pk_coset(hipStream_t s, const ProvingKey& K, fe* dst) {
-  return run_ntt3_fwd(s, K.log_m, dst, 18, NttIo{K.coef, K.ps, 0, K.n, 1, K.m, 0, 1});
-}
-
-// Round 1's wire commitments: from the wire polynomials' coefficients (jf-plonk's way: KZG10::commit under
-// src/proof/transfer.rs:181-186) or from the witness VALUES on the Lagrange-form commit key of the domain (lagrange.hip) -
-// the same group elements, the same proof bytes; a CAP witness is mostly zeros, booleans and small limbs, whose MSM scalars
-// have one non-zero digit or none.  capgpu_plonk_set_wire_commit: 0 coefficients, 1 evaluations, -1 the default
-// (evaluations; CAPGPU_WIRE_COMMIT=coeffs turns it off for the process).
-std::atomic<int> g_wire_commit{-1};
-bool wire_commit_from_evals() {
-  static const int env_default = [] {
-    const char* e = getenv("CAPGPU_WIRE_COMMIT");
-    return (e && (!strcmp(e, "coeffs") || !strcmp(e, "0"))) ? 0 : 1;
-  }();
-  const int m = g_wire_commit.load(std::memory_order_relaxed);
-  return (m < 0 ? env_default : m) != 0;
-}
-
-// Where the Fiat-Shamir transcript of a prove call runs (capgpu_plonk_set_transcript; CAPGPU_TRANSCRIPT=device|host sets
-// the process default): on the host - between the rounds the commitments come back, the host hashes them and sends the
-// challenges - or on the device (transcript_dev.hpp), where the whole call is enqueued at once and waited for once.
-std::atomic<int> g_transcript{-1};
-int transcript_mode() {
-  static const int env_default = [] {
-    const char* e = getenv("CAPGPU_TRANSCRIPT");
-    return (e && (!strcmp(e, "device") || !strcmp(e, "1"))) ? CAPGPU_TRANSCRIPT_DEVICE : CAPGPU_TRANSCRIPT_HOST;
-  }();
-  const int m = g_transcript.load(std::memory_order_relaxed);
-  return m < 0 ? env_default : m;
-}
-
-// The stream the chunks of host-resident wire columns are copied on: a copy on the launch stream itself would queue up
-// behind the kernels of the chunk before it (calls are serialised by the process lock; created on first use).
-hipStream_t h2d_stream() {
-  Context& c = ctx();
-  if (!c.copy_stream && hipStreamCreateWithFlags(&c.copy_stream, hipStreamNonBlocking) != hipSuccess)
-    c.copy_stream = nullptr;
-  return c.copy_stream;
-}
-// Small batches leave most of the chip idle during round 1's commitment MSMs (a chain of a dozen short launches per MSM
-// launch): the wire polynomials' interpolation, blinding and coset transforms - which round 3 needs, not the commitments
-// when those are taken from evaluations - run beside them on a side stream of the context (fork / join by events inside
-// segment 0, so a captured graph gets two branches).  CAPGPU_R1_OVERLAP_MAX: largest batch that does so (default 3, 0 =
-// off).  Measured, same box (profiles/small_launch_ab_r05.txt): batch 1 2.59 -> 2.38 ms, batch 2 3.8 -> 3.7 ms, batch 4
-// even, batches of 8 and 16 1-2 % SLOWER - there the transforms no longer fit beside the MSMs, they only slow them down.
-uint32_t r1_overlap_max() {
-  static const uint32_t v = [] {
-    const char* e = getenv("CAPGPU_R1_OVERLAP_MAX");
-    const int x = e ? atoi(e) : 3;
-    return (uint32_t)(x < 0 ? 0 : (x > 4096 ? 4096 : x));
-  }();
-  return v;
-}
-hipStream_t side_stream(Context& c) {
-  if (!c.side_stream) {
-    if (hipStreamCreateWithFlags(&c.side_stream, hipStreamNonBlocking) != hipSuccess) c.side_stream = nullptr;
-    if (c.side_stream && (hipEventCreateWithFlags(&c.ev_fork, hipEventDisableTiming) != hipSuccess ||
-                          hipEventCreateWithFlags(&c.ev_join, hipEventDisableTiming) != hipSuccess)) {
-      (void)hipStreamDestroy(c.side_stream);
-      c.side_stream = nullptr;
-    }
-    (void)hipGetLastError();
-  }
-  return c.side_stream;
-}
-// The parts of ONE dealt host batch (capgpu_plonk_prove_batch cuts it over two contexts of a device) copy their witnesses
-// in PART ORDER, not side by side: two copies at once share the link, both parts' first chunks land late and the GPU idles
-// for both; in part order the first part's first chunk lands after half that time and its kernels run while the second
-// part's witnesses arrive (round-5 VERDICT item 2: pcie_inclusive 0.92 of the resident rate).  A part takes its turn
-// before its first copy - for a BOUNDED time: it holds its context's lock while it waits, and a concurrent batch whose
-// parts picked the contexts in the other order would otherwise deadlock with it (tests/test_gpu_multidev.py found that);
-// after 100 ms it copies anyway, side by side as before round 6 - and passes it on when its last copy has landed; the
-// dealer passes a part's turn on when the part returns, whatever happened inside (an error path never holds the others
-// up).  Only batches of 64 proofs and more take turns: below that the copies are too short to matter.
-struct H2dTurn {
-  std::mutex mu;
-  std::condition_variable cv;
-  uint32_t next = 0;
-  bool wait_for(uint32_t idx, uint32_t timeout_ms) {  // false: timed out (the caller goes ahead regardless)
-    std::unique_lock<std::mutex> lk(mu);
-    return cv.wait_for(lk, std::chrono::milliseconds(timeout_ms), [&] { return next >= idx; });
-  }
-  void pass(uint32_t idx) {  // part idx is done copying (idempotent)
-    std::lock_guard<std::mutex> lk(mu);
-    if (next < idx + 1) next = idx + 1;
-    cv.notify_all();
-  }
-};
-thread_local H2dTurn* tl_h2d_turn = nullptr;
-thread_local uint32_t tl_h2d_index = 0;
-static bool h2d_in_part_order() {
-  static const bool on = [] {
-    const char* e = getenv("CAPGPU_H2D_PART_ORDER");
-    return !e || atoi(e) != 0;
-  }();
-  return on;
-}
-
-// chunks of proofs the host-resident wire columns of a batch are copied and committed in (round 1 of prove_batch)
-uint32_t h2d_chunks(uint32_t P) {
-  static const int forced = [] {
-    const char* e = getenv("CAPGPU_PROVE_CHUNKS");  // tests: any batch in 1..16 chunks
-    const int x = e ? atoi(e) : 0;
-    return x >= 1 && x <= 16 ? x : 0;
-  }();
-  if (forced) return std::min<uint32_t>((uint32_t)forced, P);
-  return P >= 64 ? 4u : (P >= 32 ? 2u : 1u);  // a chunk's commitments should still fill the chip (>= 80 MSMs)
-}
-// first proof of chunk ck (ck = chunks: P).  Equal chunks - except that the FIRST chunk of a batch of >= 64 proofs that
-// starts on an idle device is kept short (CAPGPU_PROVE_FIRST_CHUNK proofs, default 16; 0 = equal chunks): nothing runs
-// until it has landed.
-uint32_t h2d_chunk_start(uint32_t P, uint32_t chunks, uint32_t ck, bool short_first) {
-  static const uint32_t first = [] {
-    const char* e = getenv("CAPGPU_PROVE_FIRST_CHUNK");
-    const int x = e ? atoi(e) : 16;
-    return (uint32_t)(x >= 0 && x <= 4096 ? x : 16);
-  }();
-  if (ck == 0) return 0;
-  if (ck >= chunks) return P;
-  if (!short_first || first == 0 || chunks < 3 || first * chunks >= P) return (uint32_t)((uint64_t)P * ck / chunks);
-  return first + (uint32_t)((uint64_t)(P - first) * (ck - 1) / (chunks - 1));
-}
-
-// ---- variable-form input (CAPGPU_INPUT_VARS; kernels: vars_kernels.hpp) ------------------------------------------------
-// A witness arrives as one value per variable and becomes the five wire columns on the device, through the table its key
-// keeps: 32 B x num_vars over the link instead of 32 B x 5 n.  Everything behind the gather is the evals path.
-std::atomic<uint64_t> g_witness_h2d{0}, g_gather_launches{0};  // capgpu_plonk_input_stats
-inline void count_witness_h2d(size_t bytes) { g_witness_h2d.fetch_add(bytes, std::memory_order_relaxed); }
-
-// Context::stage_b for `cnt` witnesses in variable form: the five columns the gather writes ([cnt][5 n], where the evals
-// path copies them) and - host-resident input only - behind them the staged value vectors ([cnt][stride])
-inline size_t vars_stage_bytes(size_t cnt, size_t n, size_t stride, bool host) {
-  return wires_stage_bytes(cnt, n) + (host ? sizeof(fe) * cnt * stride : 0);
-}
-// the value vectors of a batch on the device: proof p's at d_vars + p * stride, its key's num_vars <= stride of them used
-struct VarsIn {
-  const fe* d_vars;
-  size_t stride;
-};
-bool key_lacks_table(const ProvingKey& K) {
-  if (K.wire_vars) return false;
-  set_error("capgpu_plonk: CAPGPU_INPUT_VARS: key has no variable table (capgpu_plonk_preprocess_vars or "
-            "capgpu_plonk_key_set_vars gives it one)");
-  return true;
-}
-// columns of proofs [p0, p0 + cnt) into d_cols ([P][5][n]): one launch per run of proofs that share a key
-void gather_vars(hipStream_t s, const ProvingKey& K, const std::vector<const ProvingKey*>* keys, uint32_t p0, uint32_t cnt,
-                 const VarsIn& in, fe* d_cols) {
-  const size_t cells = (size_t)NW * K.n;
-  for (uint32_t p = p0; p < p0 + cnt;) {
-    uint32_t q = p0 + cnt;
-    if (keys)
-      for (q = p + 1; q < p0 + cnt && (*keys)[q] == (*keys)[p];) q++;
-    const ProvingKey& Kp = keys ? *(*keys)[p] : K;
-    // enough lanes to fill the chip; the proofs beyond that are the lane's loop (the table stays in its register)
-    const uint32_t rows = std::min<uint32_t>(q - p, (uint32_t)std::max<size_t>(1, ((size_t)1 << 20) / (2 * cells)));
-    launch("k_gather_vars", k_gather_vars, dim3(cdiv(2 * cells, kThreads), rows), dim3(kThreads), 0, s,
-           (const uint4*)(in.d_vars + (size_t)p * in.stride), in.stride, (const uint32_t*)Kp.wire_vars, cells, q - p,
-           (uint4*)(d_cols + (size_t)p * cells));
-    g_gather_launches.fetch_add(1, std::memory_order_relaxed);
-    p = q;
-  }
-}
+namespace cap {
+namespace {
 
 // ---- witness check ---------------------------------------------------------------------------------------------------
 // The reference refuses a witness that does not satisfy its circuit before it calls the SNARK, and names the constraint
 // (`check_circuit_satisfiability`, src/proof/transfer.rs:167-177; mint.rs and freeze.rs likewise).  Here: two launches over
 // the resident witnesses (check_kernels.hpp) against two tables a key derives on its first check.
-std::atomic<int> g_precheck{0};             // capgpu_plonk_set_precheck
-thread_local bool tl_prechecked = false;    // the batch this thread is about to prove has been checked already (coalescer)
 
 // selector values on the domain and the index form of sigma, on the current context's stream; synchronous
 int key_check_tables(const ProvingKey& K) {
@@ -837,40 +475,30 @@ int precheck_verdict(const capgpu_witness_fault* faults, uint32_t P) {
   return CAPGPU_ERR_PROOF;
 }
 
-// the pinned result area of a batch of P proofs: the proofs and degree flags (device transcript), or a round's
-// commitments, the grand-product totals, the evaluations and the flags (host transcript)
-size_t prove_pinned_bytes(uint32_t P, bool dev_tr) {
-  if (dev_tr) return (size_t)P * td::kPrBytes + sizeof(uint32_t) * P + 512;
-  return sizeof(g1_jac) * P * NW + sizeof(fe) * P * 11 + sizeof(uint32_t) * P + 1024;
+// ---- capgpu_plonk_reserve: what prove_batch would ask of the context's scratch -----------------------------------
+// The witness check is prove_batch's own step: its requests (check_resident's: stage_a, and the transform of
+// coefficient-form input to values) ...
+void precheck_needs(const ProvePlan& pl, const ProvingKey& K, ProveNeeds& nd) {
+  if (!pl.precheck) return;
+  void* a = nullptr;
+  fe *b = nullptr, *v = nullptr;
+  nd.stage_a = check_carve(nullptr, pl.P, K.num_inputs, pl.coeffs, K.n, &a, &b, &v);
+  if (pl.coeffs) nd.ntt(ntt_scratch_from(K.log_n, (size_t)pl.P * NW));
 }
-// bytes per proof of the device transcript's prefix (init message || vk_bytes || public inputs), in steps of 256: the
-// stride is part of a captured graph's signature
-uint32_t transcript_stride(size_t longest) { return (uint32_t)((longest + 256) / 256 * 256); }
+// ... and with them the largest request a planned batch under K makes of every buffer (ProveRun::needs).  The device
+// transcript's prefix is sized for an EMPTY init message - the caller's is not known to a reserve; it takes P * (length
+// rounded up to 256) bytes of a workspace of megabytes per proof, well inside scratch_reserve's slack.
+ProveNeeds prove_needs(const ProvePlan& pl, const ProvingKey& K) {
+  ProveNeeds nd;
+  precheck_needs(pl, K, nd);
+  ProveRun::needs(pl, K, nd);
+  return nd;
+}
 
-// msgs / msg_lens (optional): one transcript init message per proof; otherwise ext_msg is shared by the batch.
-// keys (optional): the proving key of every proof - keys of ONE domain size under ONE SRS (the reference proves transfer,
-// mint and freeze notes side by side, src/utils/params_builder.rs:194-226; proofs of different circuits on the same
-// domain share every MSM and NTT launch, only k_perm_numden / k_quotient and the descriptors of rounds 4-5 read key
-// data).  K is then keys[0] - it lends the domain-level tables and the workspace - and pub_inputs holds P rows of
-// `num_inputs` = the largest count among the keys, a key with fewer inputs using the first of its row.
-int prove_batch(const ProvingKey& K, uint32_t P, const fe* d_wires, const uint64_t* pub_inputs, size_t num_inputs,
-                const uint8_t* ext_msg, size_t ext_len, const uint64_t* blinders, capgpu_proof* proofs,
-                const uint8_t* const* msgs = nullptr, const size_t* msg_lens = nullptr,
-                const std::vector<const ProvingKey*>* keys = nullptr, const uint64_t* const* h_wires = nullptr,
-                int form = CAPGPU_INPUT_EVALS, const VarsIn* vin = nullptr) {
-  // form: CAPGPU_INPUT_EVALS - d_wires / h_wires hold the wire assignment, 5 columns of n values per proof (round 1
-  // interpolates them); CAPGPU_INPUT_COEFFS - they hold the 5 wire POLYNOMIALS, n coefficients each, as jf-relation's
-  // compute_wire_polynomials returns them (src/proof/transfer.rs:181-186 holds that circuit): round 1 takes them as they
-  // are and round 2's witness values come from ONE forward transform on the device.  The proofs are the same bytes.
-  // CAPGPU_INPUT_VARS - the input is one value per variable, `vin->stride` elements per proof at vin->d_vars; d_wires is
-  // device scratch for the five columns, which k_gather_vars writes there through the keys' tables (chunk by chunk behind
-  // the chunk's copy when the values are still on the host); from there on the call is the evals form.
-  // h_wires (optional): the input is still in host memory - h_wires[p] points to the 5 n elements (variable form:
-  // num_vars values) of proof p - and d_wires (variable form: vin->d_vars) is an empty device buffer for them.
-  // Round 1 then runs in chunks of proofs - copy, interpolate, blind, commit - so that the copy of a chunk (pageable
-  // memory: the call blocks the host, not the device) overlaps the commitments of the one before.
+// One batch of P proofs under K (mixed keys: K = keys[0]) on the calling thread's context - see ProveRequest for the
+// arguments, ProvePlan for the modes and ProveRun for the schedule.
+int prove_batch(const ProvingKey& K, uint32_t P, const ProveRequest& rq) {
   Context& c = ctx();
-  hipStream_t s = c.stream;
   trace("pb_begin", c.slot, P);
   struct TraceEnd {
     int slot;
@@ -885,11 +513,12 @@ int prove_batch(const ProvingKey& K, uint32_t P, const fe* d_wires, const uint64
     ~CopyDrain() {
       if (armed && c.copy_stream) (void)hipStreamSynchronize(c.copy_stream);
     }
-  } drain{c, h_wires != nullptr};
-  const size_t n = K.n, m = K.m, ps = K.ps;
+  } drain{c, rq.h_wires != nullptr};
+  const std::vector<const ProvingKey*>* const keys = rq.keys;
+  const size_t num_inputs = rq.num_inputs;
   auto key_of = [&](uint32_t p) -> const ProvingKey& { return keys ? *(*keys)[p] : K; };
-  const bool vars = form == CAPGPU_INPUT_VARS;
-  if (vars) {
+  if (rq.form == CAPGPU_INPUT_VARS) {
+    const VarsIn* const vin = rq.vin;
     for (uint32_t p = 0; p < P && (keys || p == 0); p++) {
       if (key_lacks_table(key_of(p))) return CAPGPU_ERR_INVALID_ARG;
       if (!vin || key_of(p).num_vars > vin->stride) {
@@ -899,25 +528,6 @@ int prove_batch(const ProvingKey& K, uint32_t P, const fe* d_wires, const uint64
       }
     }
   }
-  // elements per proof of the input as it arrives, and where host-resident input is copied to
-  const size_t in_elems = vars ? vin->stride : (size_t)NW * n;
-  fe* const in_dst = const_cast<fe*>(vars ? vin->d_vars : d_wires);
-  // Host-resident input of proofs [p0, p1) -> its rows of the device buffer, on stream `st`.  A proof in variable form
-  // brings the num_vars values of ITS key - callers of different keys gathered into one batch do not pad their buffers to
-  // the row length -, so only full rows that follow each other in host memory travel as one copy (a plain batch: one per
-  // chunk).
-  auto in_len = [&](uint32_t p) -> size_t { return vars ? key_of(p).num_vars : in_elems; };
-  auto copy_input = [&](uint32_t p0, uint32_t p1, hipStream_t st) -> int {
-    for (uint32_t p = p0; p < p1;) {
-      uint32_t q = p + 1;
-      while (q < p1 && in_len(q - 1) == in_elems && h_wires[q] == h_wires[q - 1] + (size_t)4 * in_elems) q++;
-      const size_t bytes = sizeof(fe) * ((size_t)(q - 1 - p) * in_elems + in_len(q - 1));
-      CAP_HIP(hipMemcpyAsync(in_dst + (size_t)p * in_elems, h_wires[p], bytes, hipMemcpyHostToDevice, st));
-      count_witness_h2d(bytes);
-      p = q;
-    }
-    return CAPGPU_OK;
-  };
   if (keys) {
     size_t max_ni = 0;
     for (uint32_t p = 0; p < P; p++) {
@@ -941,759 +551,53 @@ int prove_batch(const ProvingKey& K, uint32_t P, const fe* d_wires, const uint64
               "this call runs on context %d and would prove unsharded while its peers wait", ss, c.slot);
     return CAPGPU_ERR_INVALID_ARG;
   }
-  const MsmBases* B = nullptr;
-  int rc = find_srs(K.srs_handle, &B);
-  if (rc) return rc;
-  // capgpu_plonk_set_precheck: the witnesses are checked against their circuits before anything is committed to.  The
-  // check reads whole witnesses, so host-resident ones are copied now, in one go, instead of chunk by chunk in round 1.
-  const bool precheck = g_precheck.load(std::memory_order_relaxed) != 0 && !tl_prechecked;
-  if (precheck && h_wires) {
-    if ((rc = copy_input(0, P, s))) return rc;
-    h_wires = nullptr;
+  size_t longest = 0;  // the longest transcript prefix: init message || vk_bytes || public inputs
+  for (uint32_t p = 0; p < P; p++) {
+    const size_t ml = rq.msgs ? (rq.msgs[p] ? rq.msg_lens[p] : 0) : (rq.ext_msg ? rq.ext_len : 0);
+    longest = std::max(longest, ml + key_of(p).vk_bytes.size() + 32 * key_of(p).num_inputs);
   }
+  ProvePlan pl;
+  int rc = make_plan(c, K, P, rq.form, rq.h_wires != nullptr, longest, false, &pl);
+  if (rc) return rc;
+  ProveRun run(c, pl, K, rq);
+  // the witness check reads whole witnesses: host-resident ones are copied now, in one go
+  if (pl.precheck && rq.h_wires && (rc = run.copy_input(0, P, c.stream))) return rc;
   // variable form with the values resident (a caller's device buffer, or copied a moment ago): all columns at once
-  if (vars && !h_wires) gather_vars(s, K, keys, 0, P, *vin, const_cast<fe*>(d_wires));
-  if (precheck) {
-    // Ahead of everything the proof itself needs - the Lagrange-form commit key a domain's first proof may have to build,
-    // the workspace, every MSM and NTT: a refused batch has cost the check's launches.  (Coefficient-form input is first
-    // transformed to values, in scratch of the check's own.)
+  if (pl.vars && !pl.r1_copies) run.gather_vars(0, P);
+  if (pl.precheck) {
+    // Ahead of everything the proof itself needs - the workspace, every MSM and NTT: a refused batch has cost the
+    // check's launches.  (Coefficient-form input is first transformed to values, in scratch of the check's own.)
     std::vector<capgpu_witness_fault> faults(P);
     // (gathered columns satisfy every copy constraint by construction: the gate pass only)
-    if ((rc = check_resident(K, keys, P, d_wires, pub_inputs, num_inputs, vars ? CAPGPU_INPUT_EVALS : form, faults.data(),
-                             vars)))
+    if ((rc = check_resident(K, keys, P, rq.d_wires, rq.pub_inputs, num_inputs, pl.vars ? CAPGPU_INPUT_EVALS : rq.form,
+                             faults.data(), pl.vars)))
       return rc;
     if ((rc = precheck_verdict(faults.data(), P))) return rc;
   }
-  // the Lagrange-form commit key (built on the first proof of this domain size under this SRS if preprocess did not);
-  // sharded commitment MSMs (mode A of config 4) cut the monomial key by point range: they keep the coefficient form
-  // The Lagrange-form key is an OPTIMISATION (the same commitments come from the coefficients): when it cannot be had -
-  // its table is as large as the SRS's window table and is built on first use with temporaries of its own - the proof is
-  // made the coefficient way instead of failing.  Only a bad handle is an error of the call.
-  const MsmBases* Lag = nullptr;
-  if (wire_commit_from_evals() && !comm_shard_prover() && (rc = find_lagrange(K.srs_handle, K.log_n, &Lag))) {
-    if (rc == CAPGPU_ERR_BAD_HANDLE) return rc;
-    Lag = nullptr;
-    (void)hipGetLastError();
-    trace("pb_lagrange_fallback", c.slot, rc);
-  }
-  // the transcript on the device (capgpu_plonk_set_transcript) - except under sharded commitment MSMs, whose partial
-  // commitments meet through a host-driven exchange: those calls keep the host transcript
-  const bool dev_tr = transcript_mode() == CAPGPU_TRANSCRIPT_DEVICE && !comm_shard_prover();
-  uint32_t tr_stride = 0;  // bytes per proof of the transcript's prefix: init message || vk_bytes || public inputs
-  if (dev_tr) {
-    size_t longest = 0;
-    for (uint32_t p = 0; p < P; p++) {
-      const size_t ml = msgs ? (msgs[p] ? msg_lens[p] : 0) : (ext_msg ? ext_len : 0);
-      longest = std::max(longest, ml + key_of(p).vk_bytes.size() + 32 * key_of(p).num_inputs);
-    }
-    if (longest > (1u << 30)) {
-      set_error("capgpu_plonk_prove: transcript init message of %zu bytes", longest);
-      return CAPGPU_ERR_INVALID_ARG;
-    }
-    tr_stride = transcript_stride(longest);
-  }
   // workspace
-  const bool coeffs = form == CAPGPU_INPUT_COEFFS;
-  if ((rc = scratch_reserve(c.prove_ws, carve(nullptr, K, P, num_inputs, coeffs, tr_stride).total))) return rc;
-  BatchWs w = carve(c.prove_ws.p, K, P, num_inputs, coeffs, tr_stride);
-  const NttDomain* dom_n = nullptr;
-  const Ntt3Domain* dom_q = nullptr;
-  if ((rc = get_domain(K.log_n, &dom_n))) return rc;
-  if ((rc = get_domain3(K.log_m, &dom_q))) return rc;
-  // small batches replay their kernel segments as hipGraphs (see ProveGraphSet)
-  const uint32_t chunks = h_wires ? h2d_chunks(P) : 1;
-  // small batches run rounds 1-2 on two streams (r1_overlap_max); decided here, once, because it shapes the captured graphs
-  hipStream_t s2 = nullptr;
-  const bool overlap = chunks == 1 && P <= r1_overlap_max() && !c.prof.on && !comm_shard_prover() && s == c.own_stream &&
-                       (s2 = side_stream(c)) != nullptr;
-  // no exit path - an error between a fork and its join in particular - may leave the side stream running kernels on this
-  // context's workspace: the next call (or a scratch growth) would pull it from under them
-  struct SideDrain {
-    Context& c;
-    bool armed;
-    ~SideDrain() {
-      if (armed && c.side_stream) (void)hipStreamSynchronize(c.side_stream);
-    }
-  } side_drain{c, overlap};
-  ProveGraphSet* gs = nullptr;
-  // (only on the library's own stream: a caller's stream - capgpu_set_stream - may carry work of its own)
-  if (P <= graph_max_batch() && chunks == 1 && !c.prof.on && comm_shard_slot() < 0 && s == c.own_stream) {
+  if ((rc = scratch_reserve(c.prove_ws, carve(nullptr, K, P, num_inputs, pl.coeffs, pl.tr_stride).total))) return rc;
+  run.w = carve(c.prove_ws.p, K, P, num_inputs, pl.coeffs, pl.tr_stride);
+  if (pl.graphs) {
     ProveGraphSig sig;
     sig.key_uid = K.uid;
     sig.srs = K.srs_handle;
     sig.P = P;
     sig.num_inputs = num_inputs;
-    sig.form = form;
+    sig.form = rq.form;
     sig.multi = keys != nullptr;
-    sig.d_wires = d_wires;
+    sig.d_wires = rq.d_wires;
     sig.ws = c.prove_ws.p;
     sig.msm_ws = c.msm_ws.p;
     sig.ntt_scratch = c.ntt_scratch.p;
-    sig.bases = B->ext;
-    sig.lagrange = Lag ? Lag->ext : nullptr;
-    sig.stream = s;
-    sig.overlap = overlap;
-    sig.transcript = dev_tr ? CAPGPU_TRANSCRIPT_DEVICE : CAPGPU_TRANSCRIPT_HOST;
-    sig.tr_stride = tr_stride;
-    gs = graph_set_for(c, sig);
+    sig.bases = pl.B->ext;
+    sig.lagrange = pl.Lag ? pl.Lag->ext : nullptr;
+    sig.stream = c.stream;
+    sig.overlap = pl.overlap;
+    sig.transcript = pl.dev_tr ? CAPGPU_TRANSCRIPT_DEVICE : CAPGPU_TRANSCRIPT_HOST;
+    sig.tr_stride = pl.tr_stride;
+    run.gs = graph_set_for(c, sig);
   }
-  auto seg = [&](int id, const std::function<int()>& enqueue) -> int { return run_segment(c, gs, id, enqueue); };
-  static const bool inv_env = [] {  // the round-2 inversion as a device kernel (the pre-round-4 schedule)
-    const char* e = getenv("CAPGPU_PERM_INV_ON_DEVICE");
-    return e && atoi(e) != 0;
-  }();
-  const bool inv_on_device = inv_env || dev_tr;
-  g_prove_calls++;
-  auto wait_stream = [&]() -> hipError_t {  // every host wait on the proving stream goes through here (capgpu_plonk_sync_stats)
-    g_stream_waits++;
-    return hipStreamSynchronize(s);
-  };
-
-  // ---- transcripts (host) --------------------------------------------------------------------------------
-  std::vector<SolidityTranscript> tr(dev_tr ? 0 : P);
-  if (!dev_tr) parallel_for(P, [&](uint32_t p) {
-    if (msgs) {
-      if (msgs[p] && msg_lens[p]) tr[p].append(msgs[p], msg_lens[p]);
-    } else if (ext_msg && ext_len) {
-      tr[p].append(ext_msg, ext_len);
-    }
-    const ProvingKey& Kp = key_of(p);
-    tr[p].append(Kp.vk_bytes.data(), Kp.vk_bytes.size());
-    for (size_t i = 0; i < Kp.num_inputs; i++) append_fr(tr[p], fe_from_words(pub_inputs + 4 * (p * num_inputs + i)));
-  });
-  std::vector<uint64_t> pub_rows;  // mixed keys: the unused tail of a shorter key's row must be zero on the device
-  if (keys && num_inputs) {
-    pub_rows.assign(pub_inputs, pub_inputs + (size_t)4 * P * num_inputs);
-    for (uint32_t p = 0; p < P; p++)
-      for (size_t i = key_of(p).num_inputs; i < num_inputs; i++)
-        for (int k = 0; k < 4; k++) pub_rows[4 * (p * num_inputs + i) + k] = 0;
-    pub_inputs = pub_rows.data();
-  }
-  if (num_inputs)
-    CAP_HIP(hipMemcpyAsync(w.d_pub, pub_inputs, sizeof(fe) * P * num_inputs, hipMemcpyHostToDevice, s));
-  std::vector<const fe*> key_ptrs;
-  const fe* const* sig_of = nullptr;
-  const fe* const* pkc_of = nullptr;
-  if (keys) {
-    key_ptrs.resize((size_t)2 * P);
-    for (uint32_t p = 0; p < P; p++) {
-      key_ptrs[p] = key_of(p).sig_eval;
-      key_ptrs[P + p] = key_of(p).pk_coset;
-    }
-    CAP_HIP(hipMemcpyAsync(w.key_ptrs, key_ptrs.data(), sizeof(const fe*) * key_ptrs.size(), hipMemcpyHostToDevice, s));
-    sig_of = w.key_ptrs;
-    pkc_of = w.key_ptrs + P;
-  }
-  CAP_HIP(hipMemcpyAsync(w.d_blind, blinders, sizeof(fe) * P * 13, hipMemcpyHostToDevice, s));
-  CAP_HIP(hipMemsetAsync(w.flags, 0, sizeof(uint32_t) * P, s));
-
-  // Results the host needs between the rounds come back into PINNED memory of the context: a device-to-host copy into
-  // pageable memory makes the runtime wait for the stream on the host first and copy through a staging buffer of its own
-  // - two host round trips where one is needed, seven times per proof.
-  g1_jac* hj = nullptr;      // [5 P] commitments of a round
-  fe* h_tot = nullptr;       // [P] grand-product totals out, their inverses back
-  fe* h_evals = nullptr;     // [10 P]
-  uint32_t* h_flags = nullptr;  // [P]
-  uint8_t* h_proofs = nullptr;  // [P] device transcript: the proofs in ABI layout, then the degree flags
-  const size_t proofs_bytes = (size_t)P * td::kPrBytes;
-  if (dev_tr) {
-    // (reserved before the first launch: a growing area drains the context's streams)
-    if ((rc = pinned_reserve(c, prove_pinned_bytes(P, true)))) return rc;
-    h_proofs = (uint8_t*)c.pin_host;
-    h_flags = (uint32_t*)(h_proofs + (proofs_bytes + 255) / 256 * 256);
-  } else {
-    if ((rc = pinned_reserve(c, prove_pinned_bytes(P, false)))) return rc;
-    char* b = (char*)c.pin_host;
-    hj = (g1_jac*)b;
-    b += (sizeof(g1_jac) * P * NW + 255) / 256 * 256;
-    h_tot = (fe*)b;
-    b += (sizeof(fe) * P + 255) / 256 * 256;
-    h_evals = (fe*)b;
-    b += (sizeof(fe) * P * 10 + 255) / 256 * 256;
-    h_flags = (uint32_t*)b;
-  }
-  std::vector<g1_affine> ha;
-  // `keep_busy` enqueues work that does not depend on the next challenge: it runs on the GPU while the host turns the
-  // commitments into challenges
-  auto fetch_comms = [&](uint32_t count, const std::function<int()>& keep_busy = nullptr) -> int {
-    CAP_HIP(hipMemcpyAsync(hj, w.comms, sizeof(g1_jac) * count, hipMemcpyDeviceToHost, s));
-    CAP_HIP(wait_stream());
-    if (keep_busy) {
-      int brc = keep_busy();
-      if (brc) return brc;
-    }
-    // Jacobian -> affine on the host while the GPU waits for the next challenge: chunks of 64 points (one shared
-    // inversion each) spread over the pool instead of one serial pass over up to 5P points
-    ha.resize(count);
-    const uint32_t chunk = 64, nchunks = (count + chunk - 1) / chunk;
-    parallel_for(nchunks, [&](uint32_t ci) {
-      const uint32_t lo = ci * chunk, hi = std::min(count, lo + chunk);
-      std::vector<g1_jac> in(hj + lo, hj + hi);
-      std::vector<g1_affine> out;
-      batch_to_affine(in, out);
-      std::copy(out.begin(), out.end(), ha.begin() + lo);
-    });
-    return CAPGPU_OK;
-  };
-
-  // ---- round 1: wire polynomials, public-input polynomial, 5 commitments ------------------------------
-  // the interpolations read the witness columns / public inputs where they are and write the coefficient arrays (no
-  // padded copies); k_blind sets the 8-element tail of every wire polynomial (two blinders, six zeros)
-  // kernels of one chunk of proofs [p0, p0 + cnt): interpolation (or, from coefficient-form input, the copy into place
-  // and the forward transform round 2 reads), blinding, and - when the batch is chunked - the chunk's commitments
-  // the five commitments of proofs [p0, p0 + cnt): MSMs of the blinded polynomials' n + 2 coefficients on the monomial key,
-  // or - same group elements - of each column's n VALUES followed by its two blinders on the Lagrange-form key.  The
-  // scalars of the second form are staged in the quotient's array, which round 3 writes long after these MSMs.
-  auto commit_wires = [&](uint32_t p0, uint32_t cnt) -> int {
-    g1_jac* out = w.comms + (size_t)p0 * NW;
-    if (!Lag) return run_msm(s, *B, w.wpoly + (size_t)p0 * NW * ps, ps, 1, 0, n + 2, cnt * NW, out);
-    fe* stage = w.t + (size_t)p0 * NW * (n + 2);
-    const fe* ev = (coeffs ? (const fe*)w.wev : d_wires) + (size_t)p0 * NW * n;
-    launch("k_stage_evals", k_stage_evals, dim3(cdiv(n + 2, kThreads), cnt * NW), dim3(kThreads), 0, s, ev, n, n,
-           (const fe*)(w.d_blind + (size_t)p0 * 13), (uint32_t)NW, 0u, 2u, stage);
-    return run_msm(s, *Lag, stage, n + 2, 1, 0, n + 2, cnt * NW, out);
-  };
-  auto r1_chunk_kernels = [&](uint32_t p0, uint32_t cnt, bool commit) -> int {
-    const size_t wo = (size_t)p0 * NW * n;
-    fe* wp = w.wpoly + (size_t)p0 * NW * ps;
-    int r;
-    if (coeffs) {
-      pad_copy(s, wp, ps, 0, d_wires + wo, n, 0, 1, cnt * NW, n, n);
-      if ((r = run_ntt_from(s, K.log_n, d_wires + wo, n, n, w.wev + wo, n, cnt * NW, 0, 0))) return r;
-    } else if ((r = run_ntt_from(s, K.log_n, d_wires + wo, n, n, wp, ps, cnt * NW, 1, 0))) {
-      return r;
-    }
-    launch("k_blind", k_blind<1>, dim3(cnt * NW), dim3(64), 0, s, wp, ps, n, (const fe*)(w.d_blind + (size_t)p0 * 13),
-           (uint32_t)NW, 0u, 2u, cnt * NW);
-    if (commit && (r = commit_wires(p0, cnt))) return r;
-    return CAPGPU_OK;
-  };
-  auto r1_tail_kernels = [&]() -> int {
-    int r;
-    if (num_inputs) {
-      if ((r = run_ntt_from(s, K.log_n, w.d_pub, num_inputs, num_inputs, w.pi, n, P, 1, 0))) return r;
-    } else {
-      CAP_HIP(hipMemsetAsync(w.pi, 0, sizeof(fe) * (size_t)P * n, s));
-    }
-    if (chunks == 1 && (r = commit_wires(0, P))) return r;
-    return CAPGPU_OK;
-  };
-  H2dTurn* const turn = h_wires ? tl_h2d_turn : nullptr;
-  const uint32_t turn_idx = tl_h2d_index;
-  if (turn) {
-    const bool in_time = turn->wait_for(turn_idx, 100);
-    trace("pb_h2d_turn", c.slot, in_time ? (int64_t)turn_idx : -1);
-  }
-  const bool short_first = h_wires && (!turn || turn_idx == 0);  // (a later part's copies run under the first part's kernels)
-  for (uint32_t ck = 0; ck < chunks; ck++) {
-    const uint32_t p0 = h2d_chunk_start(P, chunks, ck, short_first), p1 = h2d_chunk_start(P, chunks, ck + 1, short_first);
-    if (h_wires) {
-      hipStream_t cs = chunks > 1 ? h2d_stream() : nullptr;
-      if (!cs) cs = s;
-      if (cs != s && ck == 0) {  // the staging area may still be read by kernels of a call that returned early
-        hipEvent_t ev;
-        CAP_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        hipError_t e1 = hipEventRecord(ev, s), e2 = e1 == hipSuccess ? hipStreamWaitEvent(cs, ev, 0) : e1;
-        (void)hipEventDestroy(ev);
-        CAP_HIP(e2);
-      }
-      // one copy per run of proofs that are contiguous in host memory (a plain batch: one per chunk)
-      trace("pb_h2d_issue", c.slot, ck);
-      if ((rc = copy_input(p0, p1, cs))) return rc;
-      trace("pb_h2d_issued", c.slot, ck);
-      if (cs != s) {  // the chunk's kernels wait for its copy, not for the copies after it
-        hipEvent_t ev;
-        CAP_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        hipError_t e1 = hipEventRecord(ev, cs), e2 = e1 == hipSuccess ? hipStreamWaitEvent(s, ev, 0) : e1;
-        (void)hipEventDestroy(ev);  // released once the recorded work is done
-        CAP_HIP(e2);
-      }
-      if (vars) gather_vars(s, K, keys, p0, p1 - p0, *vin, const_cast<fe*>(d_wires));  // the chunk's columns, behind its copy
-    }
-    if (chunks > 1 && (rc = r1_chunk_kernels(p0, p1 - p0, true))) return rc;
-  }
-  if (turn) {
-    // (a pageable source has landed when hipMemcpyAsync returns; a pinned one when its stream has drained: the next part
-    // gets the link to itself either way.  This part's kernels are already enqueued behind their chunks.)
-    if (chunks > 1 && c.copy_stream) CAP_HIP(hipStreamSynchronize(c.copy_stream));
-    turn->pass(turn_idx);
-  }
-  // round 3's coset evaluations of the wire and public-input polynomials (on the 6n quotient domain, straight from
-  // their coefficient arrays: the transform zero-extends them) depend on nothing the transcript still has to produce
-  auto r3_wire_cosets = [&](hipStream_t st) -> int {
-    int r = run_ntt3_fwd(st, K.log_m, w.coset, P * NW, NttIo{w.wpoly, NW * ps, ps, n + 2, NW, 7 * m, m, NW});
-    if (r) return r;
-    return run_ntt3_fwd(st, K.log_m, w.coset + 6 * m, P, NttIo{w.pi, n, 0, n, 1, 7 * m, 0, 1});
-  };
-  auto r1_overlapped = [&]() -> int {
-    int r;
-    // every transform below shares c.ntt_scratch: those of the side stream run in its order, the one in front of the
-    // fork before them.  The largest size is reserved now - a growth later would free a buffer still in use.
-    if ((r = scratch_reserve(c.ntt_scratch, ntt3_scratch(K.log_m, (size_t)P * NW)))) return r;
-    auto interpolate_and_blind = [&](hipStream_t st) -> int {
-      int q = CAPGPU_OK;
-      if (coeffs) pad_copy(st, w.wpoly, ps, 0, d_wires, n, 0, 1, P * NW, n, n);
-      else q = run_ntt_from(st, K.log_n, d_wires, n, n, w.wpoly, ps, P * NW, 1, 0);
-      if (q) return q;
-      launch("k_blind", k_blind<1>, dim3(P * NW), dim3(64), 0, st, w.wpoly, ps, n, (const fe*)w.d_blind, (uint32_t)NW, 0u,
-             2u, P * NW);
-      return CAPGPU_OK;
-    };
-    // in front of the fork: what the commitments read
-    if (coeffs && (r = run_ntt_from(s, K.log_n, d_wires, n, n, w.wev, n, P * NW, 0, 0))) return r;
-    if (!Lag && (r = interpolate_and_blind(s))) return r;
-    CAP_HIP(hipEventRecord(c.ev_fork, s));
-    CAP_HIP(hipStreamWaitEvent(s2, c.ev_fork, 0));
-    // side stream: the polynomials and their coset evaluations
-    if (Lag && (r = interpolate_and_blind(s2))) return r;
-    if (num_inputs) {
-      if ((r = run_ntt_from(s2, K.log_n, w.d_pub, num_inputs, num_inputs, w.pi, n, P, 1, 0))) return r;
-    } else {
-      CAP_HIP(hipMemsetAsync(w.pi, 0, sizeof(fe) * (size_t)P * n, s2));
-    }
-    if ((r = r3_wire_cosets(s2))) return r;
-    // main stream: the five commitments
-    if ((r = commit_wires(0, P))) return r;
-    CAP_HIP(hipEventRecord(c.ev_join, s2));
-    CAP_HIP(hipStreamWaitEvent(s, c.ev_join, 0));
-    return CAPGPU_OK;
-  };
-  auto r1_body = [&]() -> int {
-    if (overlap) return r1_overlapped();
-    int r = chunks == 1 ? r1_chunk_kernels(0, P, false) : CAPGPU_OK;
-    return r ? r : r1_tail_kernels();
-  };
-  // the commitment to z and - independent of it - z's coset evaluations for round 3: one after the other (the second while
-  // the host hashes), or, for the small batches of `overlap`, side by side on the two streams
-  auto z_cosets = [&](hipStream_t st) -> int {
-    return run_ntt3_fwd(st, K.log_m, w.coset + 5 * m, P, NttIo{w.zpoly, ps, 0, n + 3, 1, 7 * m, 0, 1});
-  };
-  // z's values -> its commitment.  From coefficients (jf-plonk's way): interpolate, blind, MSM on the monomial key.  From
-  // evaluations (the Lagrange-form key): the MSM of the n values and the three blinders needs neither - it starts at
-  // once, and the small batches of `overlap` interpolate, blind and transform z to the cosets beside it.
-  auto finish_and_commit_z = [&]() -> int {
-    int r;
-    launch("k_perm_finish", k_perm_finish, dim3(cdiv(ps, kThreads), P), dim3(kThreads), 0, s, (const fe*)w.pre,
-           (const fe*)w.sfx, (const fe*)w.den, (const fe*)w.inv_total, n, w.zpoly, ps);
-    auto interpolate_and_blind = [&](hipStream_t st) -> int {
-      int q = run_ntt(st, K.log_n, w.zpoly, ps, P, 1, 0);
-      if (q) return q;
-      launch("k_blind", k_blind<0>, dim3(P), dim3(64), 0, st, w.zpoly, ps, n, (const fe*)w.d_blind, 1u, 10u, 3u, P);
-      return CAPGPU_OK;
-    };
-    if (Lag) {  // (the values are staged before the in-place interpolation overwrites them)
-      launch("k_stage_evals", k_stage_evals, dim3(cdiv(n + 3, kThreads), P), dim3(kThreads), 0, s, (const fe*)w.zpoly, ps, n,
-             (const fe*)w.d_blind, 1u, 10u, 3u, w.t);
-    }
-    if (!overlap) {
-      if ((r = interpolate_and_blind(s))) return r;
-      return Lag ? run_msm(s, *Lag, w.t, n + 3, 1, 0, n + 3, P, w.comms) : run_msm(s, *B, w.zpoly, ps, 1, 0, n + 3, P, w.comms);
-    }
-    if (!Lag && (r = interpolate_and_blind(s))) return r;  // the monomial MSM reads the blinded coefficients
-    CAP_HIP(hipEventRecord(c.ev_fork, s));
-    CAP_HIP(hipStreamWaitEvent(s2, c.ev_fork, 0));
-    if (Lag && (r = interpolate_and_blind(s2))) return r;
-    if ((r = z_cosets(s2))) return r;
-    r = Lag ? run_msm(s, *Lag, w.t, n + 3, 1, 0, n + 3, P, w.comms) : run_msm(s, *B, w.zpoly, ps, 1, 0, n + 3, P, w.comms);
-    CAP_HIP(hipEventRecord(c.ev_join, s2));
-    CAP_HIP(hipStreamWaitEvent(s, c.ev_join, 0));
-    return r;
-  };
-  // ---- round 2: permutation grand product --------------------------------------------------------------
-  auto r2_body = [&]() -> int {
-    launch("k_perm_numden", k_perm_numden, dim3(cdiv(n, kThreads), P), dim3(kThreads), 0, s,
-           coeffs ? (const fe*)w.wev : d_wires, (const fe*)K.sig_eval, sig_of, (const fe*)dom_n->tw_fwd,
-           (const Chal*)w.chal, K.qc29, n, w.num, w.den);
-    {
-      uint32_t nb = cdiv(n, kScanBlock);
-      scan_exclusive<0, 0>(s, w.num, w.pre, n, n, P, w.scan_tot);
-      scan_exclusive<0, 1>(s, w.den, w.sfx, n, n, P, w.scan_tot + (size_t)P * nb);
-    }
-    if (inv_on_device) {
-      // (the product is a function of the secret witness: the device kernel runs a fixed-length chain, as the host does)
-      launch("k_perm_inv_total", k_perm_inv_total, dim3(cdiv(P, 64)), dim3(64), 0, s, (const fe*)w.sfx,
-             (const fe*)w.den, n, w.inv_total, P);
-    } else {
-      launch("k_perm_total", k_perm_total, dim3(cdiv(P, 64)), dim3(64), 0, s, (const fe*)w.sfx, (const fe*)w.den, n,
-             w.inv_total, P);
-      return CAPGPU_OK;  // the segment ends here: the host inverts the totals (below)
-    }
-    return finish_and_commit_z();
-  };
-  // ---- round 3: quotient polynomial (its seven coset transforms were enqueued behind the round 1 and 2 MSMs) ------
-  auto r3_body = [&]() -> int {
-    int r;
-    const fe* pkc = K.pk_coset;
-    if (K.recompute) {
-      // reference schedule: the 18 selector / sigma polynomials are re-transformed for every proof
-      for (uint32_t p = 0; p < P; p++)
-        if ((r = compute_pk_coset(s, K, w.pkc))) return r;
-      pkc = w.pkc;
-    }
-    launch("k_quotient", k_quotient, dim3(P, cdiv(m, kThreads)), dim3(kThreads), 0, s, pkc, pkc_of,
-           (const fe*)w.coset, (const fe*)dom_q->xs29, (const fe*)K.inv_nx1, (const Chal*)w.chal29, K.qc29, m, w.t);
-    if ((r = run_ntt3_inv(s, K.log_m, w.t, P))) return r;
-    {
-      size_t lo = NW * (n + 1) + 3;  // first index that must be zero: degree is exactly 5(n+1)+2
-      launch("k_check_degree", k_check_degree, dim3(cdiv(m - (lo - 1), kThreads), P), dim3(kThreads), 0, s,
-             (const fe*)w.t, m, lo, w.flags);
-    }
-    return run_msm(s, *B, w.t, m, NW, n + 2, n + 2, P * NW, w.comms);
-  };
-  // ---- round 4: evaluations -------------------------------------------------------------------------------
-  // what is evaluated where: pointers only, known when the call starts
-  auto make_edesc = [&]() {
-    std::vector<EvalDesc> ed((size_t)P * 10);
-    for (uint32_t p = 0; p < P; p++) {
-      const fe* pz = w.pows + ((size_t)p * 4 + 0) * ps;
-      const fe* pzw = w.pows + ((size_t)p * 4 + 1) * ps;
-      for (int i = 0; i < NW; i++) ed[p * 10 + i] = EvalDesc{w.wpoly + ((size_t)p * NW + i) * ps, pz, (uint32_t)(n + 2), 0};
-      for (int i = 0; i < NW - 1; i++)
-        ed[p * 10 + NW + i] = EvalDesc{key_of(p).coef + (size_t)(NS + i) * ps, pz, (uint32_t)n, 0};
-      ed[p * 10 + 9] = EvalDesc{w.zpoly + (size_t)p * ps, pzw, (uint32_t)(n + 3), 0};
-    }
-    return ed;
-  };
-  auto r4_body = [&]() -> int {
-    const uint32_t small_len = kPowLow + cdiv(ps, kPowLow);
-    launch("k_powers_small", k_powers_small, dim3(cdiv(small_len, kThreads), P * 4), dim3(kThreads), 0, s,
-           w.pows_small, small_len, (const fe*)w.pw);
-    launch("k_powers", k_powers, dim3(cdiv(ps, kThreads), P * 4), dim3(kThreads), 0, s, w.pows, ps, ps,
-           (const fe*)w.pows_small, small_len);
-    uint32_t per_chunk = cdiv(n + 3, kEvalChunks);
-    launch("k_eval_partial", k_eval_partial, dim3(kEvalChunks, P * 10), dim3(kThreads), 0, s,
-           (const EvalDesc*)w.edesc, w.eval_partial, kEvalChunks, per_chunk);
-    launch("k_eval_final", k_eval_final, dim3(P * 10), dim3(64), 0, s, (const fe*)w.eval_partial, kEvalChunks,
-           w.evals);
-    return CAPGPU_OK;
-  };
-  // ---- round 5: linearisation + opening proofs ---------------------------------------------------------
-  // the polynomials and lengths of proof p's 29 linear terms, in the order td::lin_scalars derives their scalars
-  auto term_polys = [&](uint32_t p, LinTerm* T) {
-    int t = 0;
-    auto add = [&](const fe* poly, size_t len) {
-      T[t].poly = poly;
-      T[t].len = (uint32_t)len;
-      t++;
-    };
-    const fe* const coef = key_of(p).coef;
-    for (int j = 0; j < NS; j++) add(coef + (size_t)j * ps, n);
-    add(w.zpoly + (size_t)p * ps, n + 3);
-    add(coef + (size_t)(NS + NW - 1) * ps, n);
-    for (int j = 0; j < NW; j++) add(w.t + (size_t)p * m + (size_t)j * (n + 2), n + 2);
-    for (int j = 0; j < NW; j++) add(w.wpoly + ((size_t)p * NW + j) * ps, n + 2);
-    for (int j = 0; j < NW - 1; j++) add(coef + (size_t)(NS + j) * ps, n);
-  };
-  // batchpoly[p][0] = linear combination, batchpoly[p][1] = z polynomial
-  auto r5_body = [&]() -> int {
-    launch("k_lincomb", k_lincomb, dim3(cdiv(ps, kThreads), P), dim3(kThreads), 0, s, (const LinTerm*)w.terms,
-           kLinTerms, w.batchpoly, 2 * ps, ps);
-    pad_copy(s, w.batchpoly + ps, 2 * ps, 0, w.zpoly, ps, 0, 1, P, n + 3, ps);
-    launch("k_div_prepare", k_div_prepare, dim3(cdiv(n + 3, kThreads), P * 2), dim3(kThreads), 0, s,
-           (const fe*)w.batchpoly, (const fe*)w.pows, ps, n + 3, w.hbuf);
-    // the suffix sums go to batchpoly (its contents are dead once h is formed)
-    scan_exclusive<1, 1>(s, w.hbuf, w.batchpoly, n + 3, ps, P * 2, w.scan_tot);
-    launch("k_div_finish", k_div_finish, dim3(cdiv(ps, kThreads), P * 2), dim3(kThreads), 0, s,
-           (const fe*)w.batchpoly, (const fe*)w.pows, ps, n + 3, w.quot);
-    return run_msm(s, *B, w.quot, ps, 1, 0, n + 2, P * 2, w.comms);
-  };
-  auto degree_verdict = [&](const uint32_t* flags) -> int {
-    for (uint32_t p = 0; p < P; p++) {
-      if (flags[p]) {
-        set_error("capgpu_plonk_prove: proof %u: quotient polynomial has the wrong degree (flags %u): "
-                  "the circuit is not satisfied by this witness",
-                  p, flags[p]);
-        return CAPGPU_ERR_PROOF;
-      }
-    }
-    return CAPGPU_OK;
-  };
-  const fe omega = ntt_root_of_unity(K.log_n);
-
-  if (dev_tr) {
-    // ---- the transcript on the device: every per-call value goes up now, the five rounds are ONE run of launches (one
-    // graph segment), the proofs come back in ABI layout with the degree flags, and the host waits once ----------------
-    // (The uploads below come from pageable vectors, like the blinders and public inputs above: the runtime may stage
-    // such a copy on the host before it returns.  They sit at the head of the call, ahead of every launch - the host is
-    // never made to wait for the call's own kernels - and are not counted by capgpu_plonk_sync_stats.)
-    std::vector<uint8_t> h_pre((size_t)P * tr_stride, 0);
-    std::vector<uint32_t> h_pre_len(P);
-    parallel_for(P, [&](uint32_t p) {
-      uint8_t* b = &h_pre[(size_t)p * tr_stride];
-      size_t o = 0;
-      auto put = [&](const void* src, size_t len) {
-        memcpy(b + o, src, len);
-        o += len;
-      };
-      if (msgs) {
-        if (msgs[p] && msg_lens[p]) put(msgs[p], msg_lens[p]);
-      } else if (ext_msg && ext_len) {
-        put(ext_msg, ext_len);
-      }
-      const ProvingKey& Kp = key_of(p);
-      put(Kp.vk_bytes.data(), Kp.vk_bytes.size());
-      for (size_t i = 0; i < Kp.num_inputs; i++) {
-        uint8_t e[32];
-        serialize_fr(fe_from_words(pub_inputs + 4 * (p * num_inputs + i)), e);
-        put(e, 32);
-      }
-      h_pre_len[p] = (uint32_t)o;
-    });
-    CAP_HIP(hipMemcpyAsync(w.tr_pre, h_pre.data(), h_pre.size(), hipMemcpyHostToDevice, s));
-    CAP_HIP(hipMemcpyAsync(w.tr_pre_len, h_pre_len.data(), sizeof(uint32_t) * P, hipMemcpyHostToDevice, s));
-    CAP_HIP(hipMemsetAsync(w.tr_state, 0, (size_t)P * 64, s));
-    const std::vector<EvalDesc> ed = make_edesc();
-    CAP_HIP(hipMemcpyAsync(w.edesc, ed.data(), sizeof(EvalDesc) * ed.size(), hipMemcpyHostToDevice, s));
-    std::vector<LinTerm> terms((size_t)P * kLinTerms);
-    memset((void*)terms.data(), 0, sizeof(LinTerm) * terms.size());
-    for (uint32_t p = 0; p < P; p++) term_polys(p, &terms[(size_t)p * kLinTerms]);
-    CAP_HIP(hipMemcpyAsync(w.terms, terms.data(), sizeof(LinTerm) * terms.size(), hipMemcpyHostToDevice, s));
-    const td::TrBufs tb{w.tr_state, w.tr_pre, w.tr_pre_len, w.tr_app, tr_stride};
-    td::LinIn lin_base;
-    memset((void*)&lin_base, 0, sizeof lin_base);
-    for (int i = 0; i < NW; i++) lin_base.k[i] = K.qc.k[i];
-    lin_base.n = n;
-    if ((rc = seg(0, [&]() -> int {
-           int r;
-           if ((r = r1_body())) return r;
-           launch("k_tr_comms_r1", td::k_tr_comms<1>, dim3(P), dim3(64), 0, s, tb, (const g1_jac*)w.comms, w.d_proofs, w.chal,
-                  w.chal29, w.zeta, w.pw, omega, P);
-           if (!overlap && (r = r3_wire_cosets(s))) return r;
-           if ((r = r2_body())) return r;
-           launch("k_tr_comms_r2", td::k_tr_comms<2>, dim3(P), dim3(64), 0, s, tb, (const g1_jac*)w.comms, w.d_proofs, w.chal,
-                  w.chal29, w.zeta, w.pw, omega, P);
-           if (!overlap && (r = z_cosets(s))) return r;
-           if ((r = r3_body())) return r;
-           launch("k_tr_comms_r3", td::k_tr_comms<3>, dim3(P), dim3(64), 0, s, tb, (const g1_jac*)w.comms, w.d_proofs, w.chal,
-                  w.chal29, w.zeta, w.pw, omega, P);
-           if ((r = r4_body())) return r;
-           launch("k_tr_evals", td::k_tr_evals, dim3(P), dim3(64), 0, s, tb, (const fe*)w.evals, w.d_proofs,
-                  (const Chal*)w.chal, (const fe*)w.zeta, w.terms, lin_base, P);
-           if ((r = r5_body())) return r;
-           launch("k_tr_open", td::k_tr_open, dim3(cdiv(P, 64)), dim3(64), 0, s, (const g1_jac*)w.comms, w.d_proofs, P);
-           return CAPGPU_OK;
-         })))
-      return rc;
-    uint32_t* flags = h_flags;
-    CAP_HIP(hipMemcpyAsync(h_proofs, w.d_proofs, proofs_bytes, hipMemcpyDeviceToHost, s));
-    CAP_HIP(hipMemcpyAsync(flags, w.flags, sizeof(uint32_t) * P, hipMemcpyDeviceToHost, s));
-    CAP_HIP(wait_stream());
-    trace("pb_r5_done", c.slot);
-    if ((rc = take_launch_error())) return rc;
-    if ((rc = degree_verdict(flags))) return rc;
-    memcpy(proofs, h_proofs, proofs_bytes);
-    side_drain.armed = false;  // (every join was waited for in stream order and the stream has drained)
-    return CAPGPU_OK;
-  }
-
-  if ((rc = seg(0, r1_body))) return rc;
-  // (enqueued behind the commitments while the host hashes - unless the side stream already ran them beside the MSMs)
-  if ((rc = fetch_comms(P * NW, [&]() -> int {
-         if (overlap) return CAPGPU_OK;
-         return seg(1, [&]() -> int { return r3_wire_cosets(s); });
-       })))
-    return rc;
-  trace("pb_r1_done", c.slot);
-  std::vector<Chal> chal(P);
-  parallel_for(P, [&](uint32_t p) {
-    for (int i = 0; i < NW; i++) {
-      append_g1(tr[p], ha[p * NW + i]);
-      affine_to_words(ha[p * NW + i], proofs[p].wires_poly_comms[i]);
-    }
-    (void)get_challenge(tr[p]);  // plookup's tau: drawn by jf-plonk even when the circuit has no lookups
-    chal[p].beta = get_challenge(tr[p]);
-    chal[p].gamma = get_challenge(tr[p]);
-    chal[p].alpha = Fr::zero();
-    chal[p].alpha2 = Fr::zero();
-  });
-  CAP_HIP(hipMemcpyAsync(w.chal, chal.data(), sizeof(Chal) * P, hipMemcpyHostToDevice, s));
-
-  if ((rc = seg(2, r2_body))) return rc;
-  if (!inv_on_device) {
-    // 1 / prod(den) per proof on the host: P products come back (32 B each), one shared inversion (Montgomery's trick),
-    // P inverses go out - a round trip of tens of microseconds against 0.17 ms of a single device thread
-    std::vector<fe> pref(P);
-    fe* tot = h_tot;
-    CAP_HIP(hipMemcpyAsync(tot, w.inv_total, sizeof(fe) * P, hipMemcpyDeviceToHost, s));
-    CAP_HIP(wait_stream());
-    // (a proof whose product is zero - one of its denominators vanished, probability ~ 2^-236 - must not poison the
-    // shared inversion: it is left out of the chain and gets the inverse 0, as the per-proof device inversion gave it)
-    fe acc = Fr::one();
-    for (uint32_t p = 0; p < P; p++) {
-      pref[p] = acc;
-      if (!Fr::is_zero(tot[p])) acc = Fr::mul(acc, tot[p]);
-    }
-    // (the product is a function of the secret witness: a fixed-length Fermat chain - 254 squarings whatever the value,
-    // ~20 us once per batch - instead of the variable-time Euclidean Fr::inv the public scalars of the other rounds use)
-    acc = Fr::inv_fermat(acc);
-    for (uint32_t p = P; p-- > 0;) {
-      if (Fr::is_zero(tot[p])) continue;
-      const fe inv_p = Fr::mul(acc, pref[p]);
-      acc = Fr::mul(acc, tot[p]);
-      tot[p] = inv_p;
-    }
-    CAP_HIP(hipMemcpyAsync(w.inv_total, tot, sizeof(fe) * P, hipMemcpyHostToDevice, s));
-    if ((rc = seg(7, [&]() -> int {
-           return finish_and_commit_z();
-         })))
-      return rc;
-  }
-  if ((rc = fetch_comms(P, [&]() -> int {  // likewise the coset evaluations of z
-         if (overlap) return CAPGPU_OK;
-         return seg(3, [&]() -> int { return z_cosets(s); });
-       })))
-    return rc;
-  trace("pb_r2_done", c.slot);
-  parallel_for(P, [&](uint32_t p) {
-    append_g1(tr[p], ha[p]);
-    affine_to_words(ha[p], proofs[p].prod_perm_poly_comm);
-    chal[p].alpha = get_challenge(tr[p]);
-    chal[p].alpha2 = Fr::sqr(chal[p].alpha);
-  });
-  CAP_HIP(hipMemcpyAsync(w.chal, chal.data(), sizeof(Chal) * P, hipMemcpyHostToDevice, s));
-  std::vector<Chal> chal29(P);
-  parallel_for(P, [&](uint32_t p) {
-    auto conv = [](const fe& a) { return Fr29::pack(Fr29::canonical(Fr29::from_ext(a))); };
-    chal29[p].beta = conv(chal[p].beta);
-    chal29[p].gamma = conv(chal[p].gamma);
-    chal29[p].alpha = conv(chal[p].alpha);
-    chal29[p].alpha2 = conv(chal[p].alpha2);
-  });
-  CAP_HIP(hipMemcpyAsync(w.chal29, chal29.data(), sizeof(Chal) * P, hipMemcpyHostToDevice, s));
-
-  if ((rc = seg(4, r3_body))) return rc;
-  uint32_t* flags = h_flags;
-  CAP_HIP(hipMemcpyAsync(flags, w.flags, sizeof(uint32_t) * P, hipMemcpyDeviceToHost, s));
-  if ((rc = fetch_comms(P * NW))) return rc;
-  trace("pb_r3_done", c.slot);
-  if ((rc = degree_verdict(flags))) return rc;
-  std::vector<fe> zeta(P);
-  std::vector<fe> pw((size_t)P * 4 * 24);
-  parallel_for(P, [&](uint32_t p) {
-    for (int i = 0; i < NW; i++) {
-      append_g1(tr[p], ha[p * NW + i]);
-      affine_to_words(ha[p * NW + i], proofs[p].split_quot_poly_comms[i]);
-    }
-    zeta[p] = get_challenge(tr[p]);
-    fe bases4[4];  // zeta, zeta omega and their inverses, from one inversion
-    td::zeta_bases(zeta[p], omega, bases4);
-    for (int q = 0; q < 4; q++) {
-      fe x = bases4[q];
-      for (int b = 0; b < 24; b++) {
-        pw[((size_t)p * 4 + q) * 24 + b] = x;
-        x = Fr::sqr(x);
-      }
-    }
-  });
-
-  CAP_HIP(hipMemcpyAsync(w.pw, pw.data(), sizeof(fe) * pw.size(), hipMemcpyHostToDevice, s));
-  const std::vector<EvalDesc> ed = make_edesc();
-  CAP_HIP(hipMemcpyAsync(w.edesc, ed.data(), sizeof(EvalDesc) * ed.size(), hipMemcpyHostToDevice, s));
-  if ((rc = seg(5, r4_body))) return rc;
-  fe* evals = h_evals;
-  CAP_HIP(hipMemcpyAsync(evals, w.evals, sizeof(fe) * (size_t)P * 10, hipMemcpyDeviceToHost, s));
-  CAP_HIP(wait_stream());
-  trace("pb_r4_done", c.slot);
-
-  std::vector<LinTerm> terms((size_t)P * kLinTerms);
-  parallel_for(P, [&](uint32_t p) {
-    const fe* ev = &evals[(size_t)p * 10];
-    const fe *we = ev, *se = ev + NW;
-    for (int i = 0; i < 10; i++) append_fr(tr[p], ev[i]);
-    for (int i = 0; i < NW; i++) fe_to_words(we[i], proofs[p].wires_evals[i]);
-    for (int i = 0; i < NW - 1; i++) fe_to_words(se[i], proofs[p].wire_sigma_evals[i]);
-    fe_to_words(ev[9], proofs[p].perm_next_eval);
-    // the scalars of the linear terms: the derivation the device transcript runs as well (td::lin_scalars)
-    td::LinIn in;
-    for (int i = 0; i < 10; i++) in.ev[i] = ev[i];
-    in.beta = chal[p].beta;
-    in.gamma = chal[p].gamma;
-    in.alpha = chal[p].alpha;
-    in.alpha2 = chal[p].alpha2;
-    in.zeta = zeta[p];
-    in.v = get_challenge(tr[p]);
-    for (int i = 0; i < NW; i++) in.k[i] = K.qc.k[i];
-    in.n = n;
-    fe sc[td::kLinScalars];
-    td::lin_scalars(in, sc);
-    LinTerm* T = &terms[(size_t)p * kLinTerms];
-    term_polys(p, T);
-    for (uint32_t t = 0; t < kLinTerms; t++) T[t].scalar = td::to_internal(sc[t]);  // k_lincomb is on the lazy field
-  });
-  CAP_HIP(hipMemcpyAsync(w.terms, terms.data(), sizeof(LinTerm) * terms.size(), hipMemcpyHostToDevice, s));
-  if ((rc = seg(6, r5_body))) return rc;
-  if ((rc = fetch_comms(P * 2))) return rc;
-  trace("pb_r5_done", c.slot);
-  for (uint32_t p = 0; p < P; p++) {
-    affine_to_words(ha[p * 2], proofs[p].opening_proof);
-    affine_to_words(ha[p * 2 + 1], proofs[p].shifted_opening_proof);
-  }
-  side_drain.armed = false;  // (every join was waited for in stream order and the stream has drained)
-  return take_launch_error();
-}
-
-// ---- capgpu_plonk_reserve: what prove_batch would ask of the context's scratch -----------------------------------
-// The largest request prove_batch makes of every buffer for a batch of P proofs under K, in the modes in force now, through
-// the SAME size functions its launches use (carve, msm_workspace_bytes, ntt*_scratch, check_carve, prove_pinned_bytes):
-// the list below follows the schedule above, lambda by lambda.  B / Lag: the commit keys the batch would commit with (Lag
-// null: from coefficients).  host_wires: the witnesses arrive in host memory (stage_b, round 1 in chunks).
-// The device transcript's prefix is sized for an EMPTY init message - the caller's is not known here; it takes
-// P * (length rounded up to 256) bytes of a workspace of megabytes per proof, well inside scratch_reserve's slack.
-struct ProveNeeds {
-  size_t prove_ws = 0, msm_ws = 0, ntt_scratch = 0, stage_a = 0, stage_b = 0, pinned = 0;
-};
-ProveNeeds prove_needs(const ProvingKey& K, const MsmBases& B, const MsmBases* Lag, uint32_t P, int form, bool host_wires) {
-  ProveNeeds nd;
-  const size_t n = K.n, ps = K.ps;
-  const bool coeffs = form == CAPGPU_INPUT_COEFFS;
-  const bool precheck = g_precheck.load(std::memory_order_relaxed) != 0;
-  const bool dev_tr = transcript_mode() == CAPGPU_TRANSCRIPT_DEVICE && !comm_shard_prover();
-  auto ntt = [&](size_t bytes) { nd.ntt_scratch = std::max(nd.ntt_scratch, bytes); };
-  auto msm = [&](const MsmBases& T, size_t len, uint32_t batch) {
-    nd.msm_ws = std::max(nd.msm_ws, msm_workspace_bytes(T, len, batch));
-  };
-  const MsmBases& W = Lag ? *Lag : B;  // rounds 1 and 2 commit on the Lagrange-form key when there is one
-  // staging of host witnesses; the witness check reads whole witnesses, so round 1 is then not chunked
-  if (host_wires) nd.stage_b = wires_stage_bytes(P, n);
-  if (form == CAPGPU_INPUT_VARS) nd.stage_b = vars_stage_bytes(P, n, K.num_vars, host_wires);
-  if (precheck) {
-    void* a = nullptr;
-    fe *b = nullptr, *v = nullptr;
-    nd.stage_a = check_carve(nullptr, P, K.num_inputs, coeffs, n, &a, &b, &v);
-    if (coeffs) ntt(ntt_scratch_from(K.log_n, (size_t)P * NW));  // check_resident
-  }
-  const uint32_t tr_stride = dev_tr ? transcript_stride(K.vk_bytes.size() + 32 * K.num_inputs) : 0;
-  nd.prove_ws = carve(nullptr, K, P, K.num_inputs, coeffs, tr_stride).total;
-  nd.pinned = prove_pinned_bytes(P, dev_tr);
-  const uint32_t chunks = host_wires && !precheck ? h2d_chunks(P) : 1;
-  // round 1: r1_chunk_kernels + commit_wires per chunk (either placement of the short first chunk), or for the whole batch
-  if (chunks > 1) {
-    for (int short_first = 0; short_first < 2; short_first++)
-      for (uint32_t ck = 0; ck < chunks; ck++) {
-        const uint32_t cnt = h2d_chunk_start(P, chunks, ck + 1, short_first != 0) - h2d_chunk_start(P, chunks, ck, short_first != 0);
-        if (!cnt) continue;
-        ntt(ntt_scratch_from(K.log_n, (size_t)cnt * NW));
-        msm(W, n + 2, cnt * NW);
-      }
-  } else {
-    ntt(ntt_scratch_from(K.log_n, (size_t)P * NW));
-    msm(W, n + 2, P * NW);
-    if (P <= r1_overlap_max()) ntt(ntt3_scratch(K.log_m, (size_t)P * NW));  // r1_overlapped reserves the largest first
-  }
-  if (K.num_inputs) ntt(ntt_scratch_from(K.log_n, P));  // r1_tail_kernels: the public-input polynomial
-  // r3_wire_cosets, z_cosets
-  ntt(ntt3_scratch(K.log_m, (size_t)P * NW));
-  ntt(ntt3_scratch(K.log_m, P));
-  // round 2: finish_and_commit_z
-  ntt(ntt_scratch_inplace(ps, P));
-  msm(W, n + 3, P);
-  // round 3: r3_body
-  if (K.recompute) ntt(ntt3_scratch(K.log_m, 18));
-  ntt(ntt3_scratch(K.log_m, P));
-  msm(B, n + 2, P * NW);
-  // round 5: r5_body
-  msm(B, n + 2, P * 2);
-  return nd;
+  return pl.dev_tr ? run.run_device_transcript() : run.run_host_transcript();
 }
 
 // ---- proving-key construction shared by preprocess and the blob loader -------------------------------------
@@ -2150,7 +1054,7 @@ static int preprocess_impl(uint64_t srs_handle, size_t n, size_t num_inputs, con
   // with the SRS): made here so that the first proof does not pay for it
   if (wire_commit_from_evals() && !comm_shard_prover()) {
     const MsmBases* Lag = nullptr;
-    // (an optimisation: a key whose Lagrange-form table cannot be built proves from coefficients - see prove_batch)
+    // (an optimisation: a key whose Lagrange-form table cannot be built proves from coefficients - see make_plan)
     if ((rc = find_lagrange(srs_handle, K->log_n, &Lag)) == CAPGPU_ERR_BAD_HANDLE) return rc;
     (void)hipGetLastError();
   }
@@ -2538,15 +1442,24 @@ int capgpu_plonk_prove_batch_dev_ex(uint64_t pk_handle, int count, const void* d
   if (rc) return rc;
   std::shared_ptr<ProvingKey> K;
   if ((rc = lookup_key(pk_handle, &K))) return rc;
+  ProveRequest rq;
+  rq.d_wires = (const fe*)d_wires;
+  rq.pub_inputs = pub_inputs;
+  rq.num_inputs = num_inputs;
+  rq.blinders = blinders;
+  rq.proofs = proofs_out;
+  rq.ext_msg = ext_msg;
+  rq.ext_len = ext_msg_len;
+  rq.form = input_form;
+  VarsIn vin{};
   if (input_form == CAPGPU_INPUT_VARS) {
     // the caller's buffer holds count * num_vars values and is only read: the columns are gathered into staging
     if ((rc = scratch_reserve(c.stage_b, vars_stage_bytes((size_t)count, K->n, 0, false)))) return rc;
-    const VarsIn vin{(const fe*)d_wires, stride};
-    return prove_batch(*K, (uint32_t)count, (const fe*)c.stage_b.p, pub_inputs, num_inputs, ext_msg, ext_msg_len, blinders,
-                       proofs_out, nullptr, nullptr, nullptr, nullptr, input_form, &vin);
+    vin = VarsIn{(const fe*)d_wires, stride};
+    rq.d_wires = (const fe*)c.stage_b.p;
+    rq.vin = &vin;
   }
-  return prove_batch(*K, (uint32_t)count, (const fe*)d_wires, pub_inputs, num_inputs, ext_msg, ext_msg_len, blinders,
-                     proofs_out, nullptr, nullptr, nullptr, nullptr, input_form);
+  return prove_batch(*K, (uint32_t)count, rq);
 }
 int capgpu_plonk_prove_batch_dev(uint64_t pk_handle, int count, const void* d_wires, const uint64_t* pub_inputs,
                                  size_t num_inputs, const uint8_t* ext_msg, size_t ext_msg_len,
@@ -2697,10 +1610,18 @@ static int host_batch_part(const HostBatch& b, int first, int cnt) {
   std::vector<const uint64_t*> rows(cnt);
   for (int i = 0; i < cnt; i++) rows[i] = b.wires + (size_t)4 * (first + i) * b.stride;
   const VarsIn vin{(const fe*)c.stage_b.p + (size_t)cnt * NW * n, b.stride};
-  return prove_batch(*K, (uint32_t)cnt, (const fe*)c.stage_b.p,
-                     b.pub_inputs ? b.pub_inputs + (size_t)4 * first * b.num_inputs : nullptr, b.num_inputs, b.ext_msg,
-                     b.ext_msg_len, b.blinders + (size_t)4 * 13 * first, b.proofs_out + first, nullptr, nullptr, nullptr,
-                     rows.data(), b.input_form, vars ? &vin : nullptr);
+  ProveRequest rq;
+  rq.d_wires = (const fe*)c.stage_b.p;
+  rq.pub_inputs = b.pub_inputs ? b.pub_inputs + (size_t)4 * first * b.num_inputs : nullptr;
+  rq.num_inputs = b.num_inputs;
+  rq.blinders = b.blinders + (size_t)4 * 13 * first;
+  rq.proofs = b.proofs_out + first;
+  rq.ext_msg = b.ext_msg;
+  rq.ext_len = b.ext_msg_len;
+  rq.h_wires = rows.data();
+  rq.form = b.input_form;
+  rq.vin = vars ? &vin : nullptr;
+  return prove_batch(*K, (uint32_t)cnt, rq);
 }
 
 int capgpu_plonk_prove_batch_ex(uint64_t pk_handle, int count, const uint64_t* wires, const uint64_t* pub_inputs,
@@ -2755,17 +1676,27 @@ int capgpu_plonk_prove_multi_dev_ex(const uint64_t* pk_handles, int count, const
     if (rc) return rc;
     keys[i] = hold[i].get();
   }
+  ProveRequest rq;
+  rq.d_wires = (const fe*)d_wires;
+  rq.pub_inputs = pub_inputs;
+  rq.num_inputs = num_inputs;
+  rq.blinders = blinders;
+  rq.proofs = proofs_out;
+  rq.msgs = ext_msgs;
+  rq.msg_lens = ext_msg_lens;
+  rq.keys = &keys;
+  rq.form = input_form;
+  VarsIn vin{};
   if (input_form == CAPGPU_INPUT_VARS) {
     size_t stride = 0;
     int rc = input_stride(pk_handles, count, input_form, 0, &stride);
     if (rc) return rc;
     if ((rc = scratch_reserve(c.stage_b, vars_stage_bytes((size_t)count, keys[0]->n, 0, false)))) return rc;
-    const VarsIn vin{(const fe*)d_wires, stride};
-    return prove_batch(*keys[0], (uint32_t)count, (const fe*)c.stage_b.p, pub_inputs, num_inputs, nullptr, 0, blinders,
-                       proofs_out, ext_msgs, ext_msg_lens, &keys, nullptr, input_form, &vin);
+    vin = VarsIn{(const fe*)d_wires, stride};
+    rq.d_wires = (const fe*)c.stage_b.p;
+    rq.vin = &vin;
   }
-  return prove_batch(*keys[0], (uint32_t)count, (const fe*)d_wires, pub_inputs, num_inputs, nullptr, 0, blinders,
-                     proofs_out, ext_msgs, ext_msg_lens, &keys, nullptr, input_form);
+  return prove_batch(*keys[0], (uint32_t)count, rq);
 }
 int capgpu_plonk_prove_multi_dev(const uint64_t* pk_handles, int count, const void* d_wires, const uint64_t* pub_inputs,
                                  size_t num_inputs, const uint8_t* const* ext_msgs, const size_t* ext_msg_lens,
@@ -2822,10 +1753,19 @@ static int host_multi_part(const HostMulti& b, int first, int cnt) {
   std::vector<const uint64_t*> rows(cnt);
   for (int i = 0; i < cnt; i++) rows[i] = b.wires + (size_t)4 * (first + i) * b.stride;
   const VarsIn vin{(const fe*)c.stage_b.p + (size_t)cnt * NW * n, b.stride};
-  return prove_batch(*keys[0], (uint32_t)cnt, (const fe*)c.stage_b.p, pp, ni, nullptr, 0,
-                     b.blinders + (size_t)4 * 13 * first, b.proofs_out + first, b.ext_msgs ? b.ext_msgs + first : nullptr,
-                     b.ext_msg_lens ? b.ext_msg_lens + first : nullptr, &keys, rows.data(), b.input_form,
-                     vars ? &vin : nullptr);
+  ProveRequest rq;
+  rq.d_wires = (const fe*)c.stage_b.p;
+  rq.pub_inputs = pp;
+  rq.num_inputs = ni;
+  rq.blinders = b.blinders + (size_t)4 * 13 * first;
+  rq.proofs = b.proofs_out + first;
+  rq.msgs = b.ext_msgs ? b.ext_msgs + first : nullptr;
+  rq.msg_lens = b.ext_msg_lens ? b.ext_msg_lens + first : nullptr;
+  rq.keys = &keys;
+  rq.h_wires = rows.data();
+  rq.form = b.input_form;
+  rq.vin = vars ? &vin : nullptr;
+  return prove_batch(*keys[0], (uint32_t)cnt, rq);
 }
 
 int capgpu_plonk_prove_multi_ex(const uint64_t* pk_handles, int count, const uint64_t* wires,
@@ -3169,21 +2109,17 @@ int capgpu_plonk_reserve(uint64_t pk_handle, int count, int input_form, int slot
     Entry lk(c);
     std::shared_ptr<ProvingKey> K;
     if ((rc = lookup_key(pk_handle, &K))) return rc;
-    const MsmBases* B = nullptr;
-    if ((rc = find_srs(K->srs_handle, &B))) return rc;
-    const MsmBases* Lag = nullptr;
-    if (wire_commit_from_evals() && !comm_shard_prover() && (rc = find_lagrange(K->srs_handle, K->log_n, &Lag))) {
-      if (rc == CAPGPU_ERR_BAD_HANDLE) return rc;
-      Lag = nullptr;  // (the proof would commit from coefficients instead: prove_batch)
-      (void)hipGetLastError();
-    }
+    // the plan of such a batch - it brings the SRS and the Lagrange-form commit key along; an empty init message
+    ProvePlan pl;
+    if ((rc = make_plan(c, *K, (uint32_t)count, input_form, true, K->vk_bytes.size() + 32 * K->num_inputs, true, &pl)))
+      return rc;
     // the domain tables and the streams a first proof would create
     const NttDomain* dn = nullptr;
     const Ntt3Domain* d3 = nullptr;
     if ((rc = get_domain(K->log_n, &dn)) || (rc = quot_domains(K->log_m, &d3, &dn))) return rc;
     (void)h2d_stream();
     (void)side_stream(c);
-    const ProveNeeds nd = prove_needs(*K, *B, Lag, (uint32_t)count, input_form, true);
+    const ProveNeeds nd = prove_needs(pl, *K);
     if ((rc = scratch_reserve(c.stage_b, nd.stage_b))) return rc;
     if ((rc = scratch_reserve(c.stage_a, nd.stage_a))) return rc;
     if ((rc = scratch_reserve(c.prove_ws, nd.prove_ws))) return rc;
@@ -3220,8 +2156,18 @@ static void run_coalesced(std::vector<ProveReq*>& reqs) {
     if (rc == CAPGPU_OK) {
       const uint64_t* row = r->wires;
       const VarsIn vin{(const fe*)c.stage_b.p + (size_t)NW * K->n, K->num_vars};
-      rc = prove_batch(*K, 1, (const fe*)c.stage_b.p, r->pubs, r->num_inputs, r->msg, r->msg_len, r->blinders, r->out,
-                       nullptr, nullptr, nullptr, &row, r->form, rv ? &vin : nullptr);
+      ProveRequest rq;
+      rq.d_wires = (const fe*)c.stage_b.p;
+      rq.pub_inputs = r->pubs;
+      rq.num_inputs = r->num_inputs;
+      rq.blinders = r->blinders;
+      rq.proofs = r->out;
+      rq.ext_msg = r->msg;
+      rq.ext_len = r->msg_len;
+      rq.h_wires = &row;
+      rq.form = r->form;
+      rq.vin = rv ? &vin : nullptr;
+      rc = prove_batch(*K, 1, rq);
     }
     r->rc = rc;
     if (rc) r->err = capgpu_last_error();
@@ -3369,9 +2315,19 @@ static void run_coalesced(std::vector<ProveReq*>& reqs) {
   }
   tl_prechecked = prechecked;
   const VarsIn vin{(const fe*)in_base, vstride};
-  rc = prove_batch(*keys[0], (uint32_t)g, (const fe*)c.stage_b.p, pubs.data(), ni, nullptr, 0, blind.data(), out.data(),
-                   msgs.data(), lens.data(), mixed ? &keys : nullptr, resident ? nullptr : rows.data(), good[0]->form,
-                   vars ? &vin : nullptr);
+  ProveRequest rq;
+  rq.d_wires = (const fe*)c.stage_b.p;
+  rq.pub_inputs = pubs.data();
+  rq.num_inputs = ni;
+  rq.blinders = blind.data();
+  rq.proofs = out.data();
+  rq.msgs = msgs.data();
+  rq.msg_lens = lens.data();
+  rq.keys = mixed ? &keys : nullptr;
+  rq.h_wires = resident ? nullptr : rows.data();
+  rq.form = good[0]->form;
+  rq.vin = vars ? &vin : nullptr;
+  rc = prove_batch(*keys[0], (uint32_t)g, rq);
   tl_prechecked = false;
   if (rc == CAPGPU_OK) rc = take_launch_error();
   if (rc == CAPGPU_OK) {

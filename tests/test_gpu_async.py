@@ -310,34 +310,67 @@ def test_free_key_with_a_ticket_outstanding(cg, tau):
 
 
 # ---- 6. reserve -------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("form,mode", [("evals", "host"), ("coeffs", "host"), ("evals", "device")])
-def test_reserved_context_grows_nothing_in_the_proving_call(cg, log10, form, mode):
-    sc, pk, vk, insts = log10
-    ws, ps, bs = stack(insts[:8])
+# (log n, proofs, form, transcript, precheck, wire commitments from evaluations: None = the library default)
+RESERVE_CASES = [
+    pytest.param(10, 8, "evals", "host", False, None, id="evals-host"),
+    pytest.param(10, 8, "coeffs", "host", False, None, id="coeffs-host"),
+    pytest.param(10, 8, "evals", "device", False, None, id="evals-device"),
+    # the witness check: stage_a, the whole batch copied up front, round 1 unchunked
+    pytest.param(10, 8, "evals", "host", True, None, id="precheck-evals"),
+    pytest.param(10, 8, "coeffs", "host", True, None, id="precheck-coeffs"),
+    pytest.param(10, 8, "evals", "host", False, False, id="wire-commit-coeffs"),
+    # <= CAPGPU_R1_OVERLAP_MAX (default 3): rounds 1-2 beside the side stream, segments replayed as graphs
+    pytest.param(10, 2, "evals", "host", False, None, id="batch2-side-stream"),
+    # round 1 in chunks: 32 proofs are the fewest that make two, 64 make four with the short first chunk
+    pytest.param(6, 32, "evals", "host", False, None, id="batch32-two-chunks"),
+    pytest.param(6, 64, "evals", "host", False, None, id="batch64-four-chunks"),
+    pytest.param(10, 4, "vars", "host", False, None, id="vars-host"),
+]
+
+
+@pytest.mark.parametrize("log_n,P,form,mode,precheck,wire_evals", RESERVE_CASES)
+def test_reserved_context_grows_nothing_in_the_proving_call(request, cg, tau, log_n, P, form, mode, precheck, wire_evals):
+    sc, pk, vk, insts = request.getfixturevalue("log%d" % log_n)
+    h = None
+    if form == "vars":  # a key that knows its variable table; the values still on the host
+        from tests.test_gpu_vars_prove import batch
+        h = cg.srs_generate(tau, sc.n + 3)
+        pk, _ = cg.plonk_preprocess_vars(h, sc.n, sc.num_inputs, sc.selectors_mont(), np.array(sc.wire_vars), sc.num_vars)
+        _, ws, ps, bs = batch(sc, [300 + i for i in range(P)])
+    else:
+        ws, ps, bs = stack([insts[i % len(insts)] for i in range(P)])
     if form == "coeffs":
-        ws = to_coeffs(ws, 10)
-    cg.plonk_set_precheck(False)
-    with transcript(cg, mode), bound(cg, 0):
-        cg.trim()
-        c0 = cg.plonk_sync_stats()
-        cg.plonk_reserve(pk, 8, form, slot=0)
-        assert cg.plonk_sync_stats()[0] == c0[0], "reserve proves nothing"
-        g0 = cg.scratch_stats()
-        with_reserve = cg.plonk_prove_batch(pk, ws, ps, bs, b"reserve", 8, input_form=form)
-        g1 = cg.scratch_stats()
-        print(form, mode, "after reserve:", g0, "->", g1)
-        assert g1["grow_events"] == g0["grow_events"] and g1["grow_bytes"] == g0["grow_bytes"], (g0, g1)
-        # ... and a ticket of the bound thread finds the same context ready
-        same_proofs(cg.plonk_prove_batch_async(pk, ws, ps, bs, b"reserve", 8, input_form=form).wait(), with_reserve)
-        assert cg.scratch_stats()["grow_events"] == g0["grow_events"]
-        # control: the same proof on a trimmed context allocates
-        cg.trim()
-        g2 = cg.scratch_stats()
-        same_proofs(cg.plonk_prove_batch(pk, ws, ps, bs, b"reserve", 8, input_form=form), with_reserve)
-        g3 = cg.scratch_stats()
-        print(form, mode, "without    :", g2, "->", g3)
-        assert g3["grow_events"] - g2["grow_events"] >= 1 and g3["grow_bytes"] - g2["grow_bytes"] > 0
-        assert g3["grow_ms"] > g2["grow_ms"]
+        ws = to_coeffs(ws, log_n)
+    try:
+        cg.plonk_set_precheck(precheck)
+        cg.plonk_set_wire_commit_from_evals(wire_evals)
+        with transcript(cg, mode), bound(cg, 0):
+            cg.trim()
+            c0 = cg.plonk_sync_stats()
+            cg.plonk_reserve(pk, P, form, slot=0)
+            assert cg.plonk_sync_stats()[0] == c0[0], "reserve proves nothing"
+            g0 = cg.scratch_stats()
+            with_reserve = cg.plonk_prove_batch(pk, ws, ps, bs, b"reserve", P, input_form=form)
+            g1 = cg.scratch_stats()
+            print(form, mode, P, "after reserve:", g0, "->", g1)
+            assert g1["grow_events"] == g0["grow_events"] and g1["grow_bytes"] == g0["grow_bytes"], (g0, g1)
+            # ... and a ticket of the bound thread finds the same context ready
+            same_proofs(cg.plonk_prove_batch_async(pk, ws, ps, bs, b"reserve", P, input_form=form).wait(), with_reserve)
+            assert cg.scratch_stats()["grow_events"] == g0["grow_events"]
+            # control: the same proof on a trimmed context allocates
+            cg.trim()
+            g2 = cg.scratch_stats()
+            same_proofs(cg.plonk_prove_batch(pk, ws, ps, bs, b"reserve", P, input_form=form), with_reserve)
+            g3 = cg.scratch_stats()
+            print(form, mode, P, "without    :", g2, "->", g3)
+            assert g3["grow_events"] - g2["grow_events"] >= 1 and g3["grow_bytes"] - g2["grow_bytes"] > 0
+            assert g3["grow_ms"] > g2["grow_ms"]
+    finally:
+        cg.plonk_set_precheck(False)
+        cg.plonk_set_wire_commit_from_evals(None)
+        if h is not None:
+            cg.plonk_free_key(pk)
+            cg.srs_free(h)
 
 
 def test_reserve_respects_the_memory_limit(cg, log10):

@@ -159,7 +159,7 @@ def test_coalesced_callers_stage_their_witnesses_and_the_trace_says_so(cg, setup
 
 
 def test_host_batch_parts_in_any_split_make_the_same_proofs(cg, setup):
-    """the dealer's uneven cut and the copy turns of a host batch's parts (plonk.hip: deal, H2dTurn) change the schedule,
+    """the dealer's uneven cut and the copy turns of a host batch's parts (plonk.hip: deal; prove_run.hpp: H2dTurn) change the schedule,
     never the proofs: a batch of 64 host witnesses against the same witnesses proved one context at a time"""
     sc = bu.synthetic_circuit(10, 3, seed=17)
     from oracle import bn254 as bn
