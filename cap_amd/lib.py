@@ -1,6 +1,7 @@
 """ctypes binding of include/capgpu.h (the drop-in C ABI).  No compute happens in Python."""
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 
@@ -118,6 +119,25 @@ def timer_end() -> float:
     return out.value
 
 
+def set_stream(stream=None):
+    """capgpu_set_stream: the calling thread's context enqueues on the caller's hipStream_t from now on - an int handle or
+    anything with a .cuda_stream attribute (torch.cuda.Stream); None restores the library's own stream.  The stream being
+    left is drained first."""
+    handle = getattr(stream, "cuda_stream", stream)
+    check(load().capgpu_set_stream(ctypes.c_void_p(int(handle) if handle else None)))
+
+
+@contextlib.contextmanager
+def on_stream(stream):
+    """the body's calls of this thread's context run on `stream` (see set_stream); the library's own stream is restored
+    on the way out, exceptions included"""
+    set_stream(stream)
+    try:
+        yield stream
+    finally:
+        set_stream(None)
+
+
 def set_device(slot: int):
     """bind the calling thread to context `slot` (-1: unbind)"""
     check(load().capgpu_set_device(int(slot)))
@@ -191,6 +211,17 @@ class DevBuf:
         assert 0 <= offset_bytes and offset_bytes + nbytes <= self.nbytes
         v = DevBuf.__new__(DevBuf)
         v.ptr = ctypes.c_void_p(self.ptr.value + offset_bytes)
+        v.nbytes = nbytes
+        v._view = True
+        return v
+
+    @classmethod
+    def from_ptr(cls, ptr: int, nbytes: int) -> "DevBuf":
+        """a non-owning buffer over device memory someone else allocated (a torch tensor's data_ptr()): never freed here;
+        the owner must outlive it"""
+        assert ptr and nbytes >= 0
+        v = cls.__new__(cls)
+        v.ptr = ctypes.c_void_p(int(ptr))
         v.nbytes = nbytes
         v._view = True
         return v

@@ -194,7 +194,31 @@ int capgpu_runtime_info(int* hip_runtime_version_out, int* hip_driver_version_ou
 int capgpu_timer_begin(void);
 int capgpu_timer_end(double* ms_out);
 /* Run all subsequent work on the caller's hipStream_t (e.g. torch's current stream); NULL
- * restores the library's own stream. */
+ * restores the library's own stream.  Needs capgpu_init (CAPGPU_ERR_NOT_INITIALISED otherwise).
+ *  - Scope: the stream belongs to ONE context - the calling thread's (capgpu_set_device; slot 0 for an unbound thread) -
+ *    and stays until the next capgpu_set_stream on that context; the other contexts keep theirs.  Host-buffer calls of an
+ *    UNBOUND thread are dealt over the contexts (capgpu_init) and so may run on a context whose stream was not switched:
+ *    a caller that wants all its work on its stream binds the thread first.
+ *  - Order: every launch, copy, event and wait of an entry point goes to that stream.  A *_dev call reads its device
+ *    input behind whatever the caller enqueued there before, and the caller's next work on the stream sees its output;
+ *    where an entry point says it does not wait for the device, that holds on the caller's stream too.  The library's
+ *    helper streams (the prover's side stream and its copy stream) are joined back into the stream by events before an
+ *    entry point returns.
+ *  - Drain: the call waits (hipStreamSynchronize) for the stream the context is LEAVING, then switches; it does not wait
+ *    for the new stream, and the helper streams hold nothing between entry points.  So work enqueued after the switch may
+ *    read what work before it wrote, and tables built lazily under one stream (NTT domains, the Lagrange-form commit key,
+ *    witness-check and verifier tables - each build ends with a wait of its own) are valid under the next.  The caller
+ *    keeps its stream alive until it has switched away from it.
+ *  - Prover: on a caller's stream a proving call neither replays captured graphs nor forks round 1 onto the side stream
+ *    (the stream may carry work of the caller's); the proofs are the same bytes.  capgpu_plonk_reserve sizes for either
+ *    schedule.
+ *  - Tickets (capgpu_plonk_prove_*_async) are accepted.  A ticket runs on the submitter's bound context - else on any
+ *    free one - and on the stream that context has when a worker starts the ticket, which need not be the one it had at
+ *    submission; the proofs are the synchronous call's either way.  A caller's stream must stay alive, and should stay
+ *    set, until its tickets have been waited for (capgpu_set_stream itself waits for a ticket running on the context).
+ *  - Timer: capgpu_set_stream between capgpu_timer_begin and _end is allowed.  _begin's event sits in the stream that
+ *    was left - drained by the switch, so it has completed - and _end's in the stream in force at _end: the time returned
+ *    is the device time between those two points. */
 int capgpu_set_stream(void* hip_stream);
 
 /* ---- SRS / commit key: stays device-resident across proofs -------------------------------- */

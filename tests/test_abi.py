@@ -72,6 +72,30 @@ def test_no_silent_fallback_without_device():
         proof.universal_setup(10, 5)
 
 
+def test_set_stream_before_init_is_refused():
+    """capgpu_set_stream needs a context to switch: before capgpu_init it returns CAPGPU_ERR_NOT_INITIALISED (-6 in
+    include/capgpu.h) and says so, for a stream handle and for NULL alike; the Python wrappers raise it."""
+    from tests import helpers as H
+    L = cg.load()
+    if H.gpu_present():
+        pytest.skip("GPU present: another test of this process may have initialised the library")
+    hdr = open(os.path.join(ROOT, "include", "capgpu.h")).read()
+    assert re.search(r"#define CAPGPU_ERR_NOT_INITIALISED \(-6\)", hdr)
+    for handle in (None, ctypes.c_void_p(0x1000)):
+        L.capgpu_msm_var_plan(ctypes.c_size_t(1), -1, None, ctypes.c_size_t(0))      # leaves another message behind
+        assert b"not initialised" not in L.capgpu_last_error()
+        assert L.capgpu_set_stream(handle) == -6
+        assert b"not initialised" in L.capgpu_last_error()
+    with pytest.raises(cg.CapGpuError) as e:
+        cg.set_stream(None)
+    assert e.value.code == -6 and "CAPGPU_ERR_NOT_INITIALISED" in str(e.value)
+    entered = False
+    with pytest.raises(cg.CapGpuError) as e:
+        with cg.on_stream(0x1000):
+            entered = True
+    assert e.value.code == -6 and not entered
+
+
 def test_product_does_not_import_oracle():
     """only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may touch oracle/."""
     pkg = os.path.join(ROOT, "cap_amd")
