@@ -60,6 +60,20 @@ pub struct capgpu_verifying_key {
     pub sigma_comms: [[u64; 8]; NUM_WIRE_TYPES],
 }
 
+/// `capgpu_ntt_plan_info`: how `capgpu_ntt_plan` says a transform is launched (72 bytes); one entry per pass in the
+/// order the passes run, the row pass last.
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct capgpu_ntt_plan_info {
+    pub passes: u32,
+    pub tile_log: u32,
+    pub digits: [u32; 3],
+    pub log_c: [u32; 3],
+    pub tiles: [u64; 3],
+    pub persistent: [u32; 3],
+    pub reserved: u32,
+}
+
 /// `capgpu_witness_fault`: the verdict of the witness check for one proof (48 bytes).
 /// `kind`: 0 satisfied, 1 gate `row`, 2 copy constraint `(wire, row) -> (wire2, row2)`.
 #[repr(C)]
@@ -169,6 +183,7 @@ extern "C" {
     pub fn capgpu_ntt_fr_batch(data: *const *mut u64, count: c_int, log_n: u32, dir: c_int, coset: c_int) -> c_int;
     pub fn capgpu_ntt_fr_dev(d_data: *mut c_void, stride_elems: usize, count: c_int, log_n: u32, dir: c_int,
                              coset: c_int) -> c_int;
+    pub fn capgpu_ntt_plan(log_n: u32, count: c_int, out: *mut capgpu_ntt_plan_info) -> c_int;
     // ---- PLONK
     pub fn capgpu_plonk_preprocess(srs_handle: u64, n: usize, num_inputs: usize, selectors: *const u64,
                                    sigma_evals: *const u64, pk_handle_out: *mut u64,

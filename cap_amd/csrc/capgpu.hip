@@ -2123,6 +2123,25 @@ int capgpu_ntt_fr(uint64_t* data, uint32_t log_n, int dir, int coset) {
   return capgpu_ntt_fr_batch(p, 1, log_n, dir, coset);
 }
 
+int capgpu_ntt_plan(uint32_t log_n, int count, capgpu_ntt_plan_info* out) {
+  if (!out || count < 1 || log_n > 28) {
+    set_error("capgpu_ntt_plan: bad argument (log_n %u, count %d)", log_n, count);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  NttPlan pl;
+  if (ntt_plan(log_n, (uint32_t)count, &pl)) return CAPGPU_ERR_INVALID_ARG;
+  *out = capgpu_ntt_plan_info{};
+  out->passes = pl.passes;
+  out->tile_log = pl.tile_log;
+  for (int i = 0; i < 3; i++) {
+    out->digits[i] = pl.digits[i];
+    out->log_c[i] = pl.log_c[i];
+    out->tiles[i] = pl.tiles[i];
+    out->persistent[i] = pl.persistent[i];
+  }
+  return CAPGPU_OK;
+}
+
 // ---- instrumentation ------------------------------------------------------------------------------
 int capgpu_ubench_mad_rate(double* lane_ops_per_s_out) {
   CAP_CHECK_INIT();

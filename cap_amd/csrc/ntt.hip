@@ -622,24 +622,86 @@ unsigned ntt_persistent() {
 }
 template <class K>
 void launch_pass(const char* name, K kernel, K kernel_persistent, PassParams& p, const NttSmallTables& small, size_t tiles,
-                 uint32_t count, size_t lds, hipStream_t stream) {
+                 uint32_t count, size_t lds, bool persistent, hipStream_t stream) {
   p.tile_counter = nullptr;
   p.tiles_x = (uint32_t)tiles;
   p.tiles_y = count;
-  const unsigned per_cu = ntt_persistent();
-  const uint64_t total = (uint64_t)tiles * count;
-  if (per_cu && small.pass_counters && total > 4ull * 256 * per_cu && total < (1ull << 32)) {
-    uint32_t* ctr = small.pass_counters + (small.next_counter++ % kNttPassCounters);
-    if (hipMemsetAsync(ctr, 0, sizeof(uint32_t), stream) == hipSuccess) {
-      p.tile_counter = ctr;
-      launch(name, kernel_persistent, dim3(256u * per_cu), dim3(kThreads), lds, stream, p);
+  if (persistent) {
+    // the plan says persistent, and capgpu_ntt_plan reports it: a pass that cannot get its tile counter is an error of
+    // the call (latched like a failed launch), not a quiet one-shot launch
+    uint32_t* ctr = small.pass_counters ? small.pass_counters + (small.next_counter++ % kNttPassCounters) : nullptr;
+    const hipError_t e = ctr ? hipMemsetAsync(ctr, 0, sizeof(uint32_t), stream) : hipErrorInvalidValue;
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      LaunchError& le = launch_error();
+      if (le.code == hipSuccess) {
+        le.code = e;
+        le.kernel = name;
+      }
       return;
     }
-    (void)hipGetLastError();
+    p.tile_counter = ctr;
+    launch(name, kernel_persistent, dim3(256u * ntt_persistent()), dim3(kThreads), lds, stream, p);
+    return;
   }
   launch(name, kernel, dim3((unsigned)tiles, count), dim3(kThreads), lds, stream, p);
 }
 }  // namespace
+
+int ntt_plan(uint32_t log_n, uint32_t count, NttPlan* out) {
+  NttPlan pl{};
+  if (log_n == 0 || count == 0) {  // n = 1 is the identity in every mode: nothing is launched
+    *out = pl;
+    return 0;
+  }
+  pl.tile_log = tile_log_for(log_n, count);
+  // digit split
+  uint32_t lg[3] = {0, 0, 0};
+  if (log_n <= 10) {
+    pl.passes = 1;
+    lg[2] = log_n;
+  } else if (log_n <= 20) {
+    pl.passes = 2;
+    lg[0] = (log_n + 1) / 2;
+    lg[2] = log_n / 2;
+  } else {
+    pl.passes = 3;
+    lg[0] = (log_n + 2) / 3;
+    lg[1] = (log_n - lg[0] + 1) / 2;
+    lg[2] = log_n - lg[0] - lg[1];
+  }
+  if (lg[0] > 10 || lg[1] > 10 || lg[2] > 10) return (int)hipErrorInvalidValue;
+  const unsigned per_cu = ntt_persistent();
+  auto finish = [&](uint32_t i, uint32_t log_len, uint32_t log_c) {
+    pl.digits[i] = log_len;
+    pl.log_c[i] = log_c;
+    pl.tiles[i] = (uint64_t)1 << (log_n - log_len - log_c);
+    const uint64_t total = pl.tiles[i] * count;
+    pl.persistent[i] = per_cu && total > 4ull * 256 * per_cu && total < (1ull << 32);
+  };
+  // column passes: the tile is C adjacent columns of a segment of 2^log_m elements
+  uint32_t log_m = log_n;
+  for (uint32_t d = 0; d + 1 < pl.passes; d++) {
+    const uint32_t log_len = lg[d];
+    const uint32_t log_s = log_m - log_len;
+    uint32_t log_c = pl.tile_log > log_len ? pl.tile_log - log_len : 0;
+    if (log_c > log_s) log_c = log_s;
+    if (log_c > 4) log_c = 4;
+    finish(d, log_len, log_c);
+    log_m -= log_len;
+  }
+  // row pass: the tile is C rows with adjacent leading digit
+  {
+    const uint32_t log_len = lg[2];
+    const uint32_t log_n1 = pl.passes >= 2 ? lg[0] : 0;
+    uint32_t log_c = pl.tile_log > log_len ? pl.tile_log - log_len : 0;
+    if (log_c > log_n1) log_c = log_n1;
+    if (log_c > 4) log_c = 4;
+    finish(pl.passes - 1, log_len, log_c);
+  }
+  *out = pl;
+  return 0;
+}
 
 int ntt_run(const NttDomain& dom, const NttSmallTables& small, fe* data, fe* scratch, size_t stride_elems,
             uint32_t count, int dir, int coset, hipStream_t stream, const NttIo* io) {
@@ -649,24 +711,9 @@ int ntt_run(const NttDomain& dom, const NttSmallTables& small, fe* data, fe* scr
     // n = 1: forward is the identity (5^0 = 1); inverse multiplies by 1^-1 = 1.
     return 0;
   }
-  const uint32_t tile_log = tile_log_for(log_n, count);
-  // digit split
-  uint32_t lg[3] = {0, 0, 0};
-  int passes;
-  if (log_n <= 10) {
-    passes = 1;
-    lg[2] = log_n;
-  } else if (log_n <= 20) {
-    passes = 2;
-    lg[0] = (log_n + 1) / 2;
-    lg[2] = log_n / 2;
-  } else {
-    passes = 3;
-    lg[0] = (log_n + 2) / 3;
-    lg[1] = (log_n - lg[0] + 1) / 2;
-    lg[2] = log_n - lg[0] - lg[1];
-  }
-  if (lg[0] > 10 || lg[1] > 10 || lg[2] > 10) return (int)hipErrorInvalidValue;
+  NttPlan plan;
+  if (int rc = ntt_plan(log_n, count, &plan)) return rc;
+  const int passes = (int)plan.passes;
   uint32_t* const* tws = dir ? small.inv_u : small.fwd_u;
   const fe* tw_full = dir ? dom.tw29_inv : dom.tw29_fwd;
 
@@ -718,11 +765,7 @@ int ntt_run(const NttDomain& dom, const NttSmallTables& small, fe* data, fe* scr
   // column passes
   uint32_t log_m = log_n;
   for (int d = 0; d < passes - 1; d++) {
-    uint32_t log_len = lg[d];
-    uint32_t log_s = log_m - log_len;
-    uint32_t log_c = tile_log > log_len ? tile_log - log_len : 0;
-    if (log_c > log_s) log_c = log_s;
-    if (log_c > 4) log_c = 4;
+    const uint32_t log_len = plan.digits[d], log_c = plan.log_c[d];
     p.in = cur_in;
     p.out = scratch;
     set_in(first ? a_src : a_tmp, first ? src_len : ~(size_t)0, first ? src_es : 1);
@@ -733,21 +776,19 @@ int ntt_run(const NttDomain& dom, const NttSmallTables& small, fe* data, fe* scr
     p.log_len = log_len;
     p.log_c = log_c;
     p.log_m = log_m;
-    size_t tiles = (size_t)1 << (log_n - log_len - log_c);
     size_t lds = sizeof(fl) << (log_len + log_c);
-    launch_pass("ntt_col_pass", ntt_col_pass<false>, ntt_col_pass<true>, p, small, tiles, count, lds, stream);
+    launch_pass("ntt_col_pass", ntt_col_pass<false>, ntt_col_pass<true>, p, small, (size_t)plan.tiles[d], count, lds,
+                plan.persistent[d] != 0, stream);
     cur_in = scratch;
     first = false;
     log_m -= log_len;
   }
   // row pass
   {
-    uint32_t log_len = lg[2];
-    uint32_t log_n1 = passes >= 2 ? lg[0] : 0;
-    uint32_t log_n2 = passes == 3 ? lg[1] : 0;
-    uint32_t log_c = tile_log > log_len ? tile_log - log_len : 0;
-    if (log_c > log_n1) log_c = log_n1;
-    if (log_c > 4) log_c = 4;
+    const int last = passes - 1;
+    const uint32_t log_len = plan.digits[last], log_c = plan.log_c[last];
+    const uint32_t log_n1 = passes >= 2 ? plan.digits[0] : 0;
+    const uint32_t log_n2 = passes == 3 ? plan.digits[1] : 0;
     p.in = cur_in;
     p.out = data;
     set_in(first ? a_src : a_tmp, first ? src_len : ~(size_t)0, first ? src_es : 1);
@@ -762,9 +803,9 @@ int ntt_run(const NttDomain& dom, const NttSmallTables& small, fe* data, fe* scr
     p.log_c = log_c;
     p.log_n1 = log_n1;
     p.log_n2 = log_n2;
-    size_t tiles = (size_t)1 << (log_n - log_len - log_c);
     size_t lds = sizeof(fl) << (log_len + log_c);
-    launch_pass("ntt_row_pass", ntt_row_pass<false>, ntt_row_pass<true>, p, small, tiles, count, lds, stream);
+    launch_pass("ntt_row_pass", ntt_row_pass<false>, ntt_row_pass<true>, p, small, (size_t)plan.tiles[last], count, lds,
+                plan.persistent[last] != 0, stream);
   }
   return 0;  // launch failures are latched by launch() and reported by take_launch_error()
 }

@@ -82,6 +82,20 @@ struct NttIo {
 int ntt_run(const NttDomain& dom, const NttSmallTables& small, fe* data, fe* scratch, size_t stride_elems,
             uint32_t count, int dir, int coset, hipStream_t stream, const NttIo* io = nullptr);
 
+// How ntt_run transforms `count` arrays of 2^log_n elements: the one place that decides it (host only, no device
+// needed; CAPGPU_NTT_TILE_LOG, CAPGPU_NTT_TILE_ADAPT and CAPGPU_NTT_PERSISTENT are read once per process).  Passes are
+// listed in the order they run: passes - 1 column passes, then the row pass.  passes == 0: log_n == 0 or count == 0,
+// nothing is launched.
+struct NttPlan {
+  uint32_t passes = 0;
+  uint32_t tile_log = 0;              // log2 of the LDS tile the launch aims for (tile_log_for)
+  uint32_t digits[3] = {0, 0, 0};     // log2 of the sub-transform size of each pass
+  uint32_t log_c[3] = {0, 0, 0};      // log2 of the tile width of each pass: a tile is 2^(digit + log_c) elements
+  uint64_t tiles[3] = {0, 0, 0};      // tiles per array of each pass
+  uint32_t persistent[3] = {0, 0, 0}; // 1: the pass is launched as a few workgroups per CU that take tiles from a counter
+};
+int ntt_plan(uint32_t log_n, uint32_t count, NttPlan* out);  // 0, or hipErrorInvalidValue for a size that has no plan
+
 // ---- evaluation on N = 3 * 2^k points ------------------------------------------------------------------------
 // The quotient polynomial of the prover has degree < 5n + 8, so 6n = 3 * 2^(log n + 1) points carry it; jf-plonk
 // evaluates on 8n only because it wants a power of two.  With M = 2^k = 2n and omega_N = omega_3 * omega_M^c,

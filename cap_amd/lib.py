@@ -571,6 +571,24 @@ def ntt_fr_dev(d_data: DevBuf, log_n: int, count: int = 1, stride: int | None = 
                                    ctypes.c_uint32(log_n), int(inverse), int(coset)))
 
 
+class NttPlanInfo(ctypes.Structure):
+    """capgpu_ntt_plan_info (include/capgpu.h)"""
+    _fields_ = [("passes", ctypes.c_uint32), ("tile_log", ctypes.c_uint32), ("digits", ctypes.c_uint32 * 3),
+                ("log_c", ctypes.c_uint32 * 3), ("tiles", ctypes.c_uint64 * 3), ("persistent", ctypes.c_uint32 * 3),
+                ("reserved", ctypes.c_uint32)]
+
+
+def ntt_plan(log_n: int, count: int = 1) -> dict:
+    """How `count` transforms of 2^log_n elements in one call are launched: {'passes': 2, 'tile_log': 10,
+    'digits': [6, 6], 'log_c': [4, 4], 'tiles': [4, 4], 'persistent': [False, False]}, one entry per pass in the order
+    they run (the row pass last); no device needed."""
+    info = NttPlanInfo()
+    check(load().capgpu_ntt_plan(ctypes.c_uint32(log_n), count, ctypes.byref(info)))
+    k = info.passes
+    return {"passes": k, "tile_log": info.tile_log, "digits": list(info.digits)[:k], "log_c": list(info.log_c)[:k],
+            "tiles": list(info.tiles)[:k], "persistent": [bool(x) for x in list(info.persistent)[:k]]}
+
+
 # ---- instrumentation ---------------------------------------------------------------------------
 def ubench_mad_rate() -> float:
     """measured v_mad_u64_u32 lane-operations per second of the bound device"""

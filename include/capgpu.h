@@ -373,10 +373,27 @@ int capgpu_plonk_shard_msm(int on);
 
 /* ---- NTT: replaces Radix2EvaluationDomain::{fft, ifft, coset_fft, coset_ifft}_in_place -------- */
 /* in place, natural order in/out, Montgomery Fr; dir: 0 forward, 1 inverse (includes n^-1);
- * coset: 0/1 (generator 5: scale by 5^i before the forward transform / by 5^-i after the inverse). */
+ * coset: 0/1 (generator 5: scale by 5^i before the forward transform / by 5^-i after the inverse).
+ * Inputs may be any 256-bit image of their residue (x + r gives the output of x; tests/test_gpu_ntt_plans.py); outputs
+ * are canonical (< r). */
 int capgpu_ntt_fr(uint64_t* data, uint32_t log_n, int dir, int coset);
 int capgpu_ntt_fr_batch(uint64_t* const* data, int count, uint32_t log_n, int dir, int coset);
 int capgpu_ntt_fr_dev(void* d_data, size_t stride_elems, int count, uint32_t log_n, int dir, int coset);
+/* Diagnostic, as capgpu_msm_plan: how `count` transforms of 2^log_n elements in one call (capgpu_ntt_fr_dev; a batch
+ * call is one such call) are launched.  Passes are listed in the order they run, the row pass last; entries beyond
+ * `passes` are 0.  A tile is 2^(digits[i] + log_c[i]) <= 2^tile_log elements of LDS.  Reads CAPGPU_NTT_TILE_LOG,
+ * CAPGPU_NTT_TILE_ADAPT and CAPGPU_NTT_PERSISTENT as the transforms do (once per process).  Needs no device.  Tests
+ * use it to assert which path a shape took. */
+typedef struct capgpu_ntt_plan_info {
+  uint32_t passes;        /* 0 (log_n = 0: nothing runs), 1, 2 or 3 */
+  uint32_t tile_log;      /* log2 of the LDS tile chosen for count << log_n elements */
+  uint32_t digits[3];     /* log2 of the sub-transform size of each pass */
+  uint32_t log_c[3];      /* log2 of the tile width of each pass */
+  uint64_t tiles[3];      /* tiles per array of each pass */
+  uint32_t persistent[3]; /* 1: workgroups take tile after tile from a counter (CAPGPU_NTT_PERSISTENT) */
+  uint32_t reserved;
+} capgpu_ntt_plan_info;
+int capgpu_ntt_plan(uint32_t log_n, int count, capgpu_ntt_plan_info* out);
 
 /* ---- PLONK (TurboPlonk, 5 wires, 13 selectors) ------------------------------------------------ */
 typedef struct capgpu_proof {

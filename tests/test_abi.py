@@ -21,7 +21,7 @@ def declared_symbols():
 def test_header_declares_the_boundary():
     syms = declared_symbols()
     for must in ("capgpu_init", "capgpu_msm_g1", "capgpu_msm_g1_batch", "capgpu_ntt_fr", "capgpu_ntt_fr_batch",
-                 "capgpu_srs_upload", "capgpu_plonk_preprocess", "capgpu_plonk_prove", "capgpu_last_error"):
+                 "capgpu_ntt_plan", "capgpu_srs_upload", "capgpu_plonk_preprocess", "capgpu_plonk_prove", "capgpu_last_error"):
         assert must in syms
 
 
@@ -47,6 +47,7 @@ def test_rust_bindings_cover_the_header():
 def test_struct_layouts_match_header():
     assert ctypes.sizeof(cg.Proof) == 13 * 64 + 10 * 32
     assert ctypes.sizeof(cg.VerifyingKey) == 16 + 5 * 32 + 18 * 64
+    assert ctypes.sizeof(cg.NttPlanInfo) == 2 * 4 + 2 * 12 + 3 * 8 + 12 + 4
 
 
 def test_no_silent_fallback_without_device():
