@@ -312,6 +312,23 @@ extern "C" {
     pub fn capgpu_proof_serialize(proof: *const capgpu_proof, out: *mut u8, cap: usize, len_out: *mut usize) -> c_int;
     pub fn capgpu_proof_deserialize(bytes: *const u8, len: usize, proof_out: *mut capgpu_proof,
                                     consumed_out: *mut usize) -> c_int;
+    pub fn capgpu_proof_decode_batch(bytes: *const u8, stride: usize, count: usize, proofs_out: *mut capgpu_proof,
+                                     status_out: *mut c_int) -> c_int;
+    pub fn capgpu_proof_decode_batch_dev(d_bytes: *const c_void, stride: usize, count: usize, d_proofs_out: *mut c_void,
+                                         d_status_out: *mut c_int) -> c_int;
+    pub fn capgpu_proof_encode_batch(proofs: *const capgpu_proof, count: usize, bytes_out: *mut u8, stride: usize) -> c_int;
+    pub fn capgpu_proof_encode_batch_dev(d_proofs: *const c_void, count: usize, d_bytes_out: *mut c_void,
+                                         stride: usize) -> c_int;
+    pub fn capgpu_plonk_verify_block_bytes(vk_handles: *const u64, g2_h: *const u64, g2_beta_h: *const u64,
+                                           pub_inputs: *const u64, num_inputs: usize, proof_bytes: *const u8, stride: usize,
+                                           ext_msgs: *const *const u8, ext_msg_lens: *const usize, count: usize,
+                                           block_ok_out: *mut c_int, each_ok_out: *mut c_int,
+                                           decode_status_out: *mut c_int) -> c_int;
+    pub fn capgpu_plonk_verify_block_bytes_resident(vk_handles: *const u64, g2_h: *const u64, g2_beta_h: *const u64,
+                                                    d_pub_inputs: *const c_void, num_inputs: usize,
+                                                    d_proof_bytes: *const c_void, stride: usize, ext_msgs: *const *const u8,
+                                                    ext_msg_lens: *const usize, count: usize, block_ok_out: *mut c_int,
+                                                    each_ok_out: *mut c_int, decode_status_out: *mut c_int) -> c_int;
     // ---- on-disk parameter formats
     pub fn capgpu_g1_decompress(input: *const u8, n: usize, out_xy: *mut u64) -> c_int;
     pub fn capgpu_g1_compress(xy: *const u64, n: usize, out: *mut u8) -> c_int;
@@ -692,6 +709,52 @@ pub fn proof_bytes(proof: &capgpu_proof) -> Result<Vec<u8>> {
     check(unsafe { capgpu_proof_serialize(proof, out.as_mut_ptr(), out.len(), &mut len) })?;
     out.truncate(len);
     Ok(out)
+}
+
+/// Bytes of one serialized proof (`CAPGPU_PROOF_BYTES`).
+pub const PROOF_BYTES: usize = 769;
+
+/// `Proof::deserialize` for a block of notes on the device: `records` holds one `PROOF_BYTES` record per proof, packed.
+/// A record that does not decode is not an error: its status is 1 + the byte offset of the first malformed field (0:
+/// decoded) and its proof is all-ones words, which every verifier of the library refuses.
+pub fn proofs_from_bytes(records: &[u8]) -> Result<(Vec<capgpu_proof>, Vec<c_int>)> {
+    assert!(records.len() % PROOF_BYTES == 0, "not a whole number of proof records");
+    let count = records.len() / PROOF_BYTES;
+    let mut proofs: Vec<capgpu_proof> = Vec::with_capacity(count);
+    let mut status = vec![0 as c_int; count];
+    check(unsafe { capgpu_proof_decode_batch(records.as_ptr(), PROOF_BYTES, count, proofs.as_mut_ptr(), status.as_mut_ptr()) })?;
+    unsafe { proofs.set_len(count) }; // every struct was written by the call
+    Ok((proofs, status))
+}
+
+/// The inverse: the note bytes of a batch of proofs (`capgpu_proof_serialize` for each), packed.
+pub fn proofs_to_bytes(proofs: &[capgpu_proof]) -> Result<Vec<u8>> {
+    let mut out = vec![0u8; proofs.len() * PROOF_BYTES];
+    check(unsafe { capgpu_proof_encode_batch(proofs.as_ptr(), proofs.len(), out.as_mut_ptr(), PROOF_BYTES) })?;
+    Ok(out)
+}
+
+/// `txn_batch_verify` (src/lib.rs:455-529) for a validator that holds each note's proof as its bytes: keys uploaded once
+/// (`capgpu_plonk_vk_upload`), `records` as above, `pub_inputs` one row of `num_inputs` elements per proof, `ext_msgs`
+/// empty or one message per proof.  Decoding and verification run on the device behind one host wait.  `Ok(true)`: every
+/// proof of the block holds; a record that does not decode makes it `Ok(false)` like any wrong proof.
+pub fn verify_block_bytes(vk_handles: &[u64], g2_h: &[u64; 16], g2_beta_h: &[u64; 16], pub_inputs: &[[u64; 4]],
+                          num_inputs: usize, records: &[u8], ext_msgs: &[&[u8]]) -> Result<bool> {
+    let count = vk_handles.len();
+    assert!(records.len() == count * PROOF_BYTES && pub_inputs.len() == count * num_inputs);
+    assert!(ext_msgs.is_empty() || ext_msgs.len() == count);
+    let msgs: Vec<*const u8> = ext_msgs.iter().map(|m| if m.is_empty() { std::ptr::null() } else { m.as_ptr() }).collect();
+    let lens: Vec<usize> = ext_msgs.iter().map(|m| m.len()).collect();
+    let mut ok: c_int = 0;
+    check(unsafe {
+        capgpu_plonk_verify_block_bytes(vk_handles.as_ptr(), g2_h.as_ptr(), g2_beta_h.as_ptr(),
+                                        if pub_inputs.is_empty() { std::ptr::null() } else { pub_inputs.as_ptr() as *const u64 },
+                                        num_inputs, records.as_ptr(), PROOF_BYTES,
+                                        if msgs.is_empty() { std::ptr::null() } else { msgs.as_ptr() },
+                                        if lens.is_empty() { std::ptr::null() } else { lens.as_ptr() }, count, &mut ok,
+                                        std::ptr::null_mut(), std::ptr::null_mut())
+    })?;
+    Ok(ok != 0)
 }
 
 /// Conversions between arkworks 0.3 values and the ABI's words, and the circuit columns from jf-relation's PUBLIC API.

@@ -3,7 +3,9 @@
 // Reference: src/parameters.rs:560-577 (store_data / load_data write `CanonicalSerialize` bytes),
 // src/proof/mod.rs:74-109 (load_srs deserialises a UniversalSrs blob).
 #pragma once
+#if defined(__HIPCC__) || defined(__HIP__)
 #include <hip/hip_runtime.h>
+#endif
 #include <stdint.h>
 #include <string.h>
 
@@ -302,6 +304,7 @@ inline const char* read_vk(Reader& rd, capgpu_verifying_key* vk, OpenKey* ok) {
 }
 
 // ---- bulk G1 on the device (params.hip) ------------------------------------------------------------------
+#if defined(__HIPCC__) || defined(__HIP__)
 // `n` compressed points (host, 32 B each, any alignment) -> device affine points in arkworks' Montgomery form,
 // (0, 0) = infinity.  CAPGPU_ERR_SERIALIZATION (with the index of the first bad point in the message) if any
 // encoding is invalid.
@@ -313,6 +316,7 @@ int compress_g1(const g1_affine* d_pts, int internal_form, size_t n, uint8_t* ho
 // between consecutive vectors)
 int fr_bytes_to_mont(const uint8_t* host_bytes, size_t n, fe* d_out, hipStream_t s);  // rejects values >= r
 int fr_mont_to_bytes(const fe* d_in, size_t n, uint8_t* host_out, hipStream_t s);
+#endif  // the host-only part above also builds without HIP (tests/cpp/proof_codec_check.cpp)
 
 }  // namespace params
 }  // namespace cap

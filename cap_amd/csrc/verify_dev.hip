@@ -33,6 +33,7 @@
 #include "launch.hpp"
 #include "pairing29.hpp"
 #include "pairing_wave.hpp"
+#include "proof_codec.hpp"
 #include "verify_front.hpp"
 #include "verify_terms.hpp"
 
@@ -521,10 +522,12 @@ int lines_on_context(Context& c, const uint64_t g2_h[16], const uint64_t g2_beta
 
 size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 
-// body of the two entry points.  resident: pub_inputs and proofs are device memory
+// body of the four entry points.  resident: pub_inputs and proofs are device memory.  byte_stride != 0: `proofs` are wire
+// records (proof_codec.hpp) that far apart, decoded into the workspace first; decode_status_out: NULL or their statuses
 int verify_block(const char* who, const uint64_t* vk_handles, const uint64_t g2_h[16], const uint64_t g2_beta_h[16],
-                 const uint64_t* pub_inputs, size_t num_inputs, const capgpu_proof* proofs, const uint8_t* const* ext_msgs,
-                 const size_t* ext_msg_lens, size_t count, int* block_ok_out, int* each_ok_out, bool resident) {
+                 const uint64_t* pub_inputs, size_t num_inputs, const void* proofs, const uint8_t* const* ext_msgs,
+                 const size_t* ext_msg_lens, size_t count, int* block_ok_out, int* each_ok_out, bool resident,
+                 size_t byte_stride = 0, int* decode_status_out = nullptr) {
   if (!block_ok_out || !g2_h || !g2_beta_h || (count && (!vk_handles || !proofs)) || count > ((size_t)1 << 24)) {
     set_error("%s: bad argument (null pointer, or more than 2^24 proofs)", who);
     return CAPGPU_ERR_INVALID_ARG;
@@ -606,7 +609,8 @@ int verify_block(const char* who, const uint64_t* vk_handles, const uint64_t g2_
     at += up256(bytes ? bytes : 1);
     return o;
   };
-  const size_t o_proofs = carve(resident ? 0 : sizeof(capgpu_proof) * count),
+  const bool from_bytes = byte_stride != 0;
+  const size_t o_proofs = carve(resident || from_bytes ? 0 : sizeof(capgpu_proof) * count),
                o_pubs = carve(resident ? 0 : sizeof(fe) * num_inputs * count), o_meta = carve(16 * count),
                o_msgs = carve(msg_bytes), o_keys = carve(sizeof(void*) * nkeys), o_state = carve(64 * count),
                o_pre = carve(pre_stride * count), o_app = carve((size_t)vf::kAppBytes * count), o_ub = carve(32 * count),
@@ -618,6 +622,11 @@ int verify_block(const char* who, const uint64_t* vk_handles, const uint64_t g2_
                o_na = carve(sizeof(uint32_t) * count), o_ea = carve(each_ok_out ? sizeof(g1_affine) * count : 0),
                o_enb = carve(each_ok_out ? sizeof(g1_affine) * count : 0), o_eok = carve(sizeof(int) * count),
                o_out = carve(sizeof(int) * (count + 1));
+  // from bytes: the records (a host caller's), the structs they decode to and their statuses
+  const size_t rec_bytes = from_bytes ? (count - 1) * byte_stride + pc::kBytes : 0;
+  const size_t o_rec = from_bytes && !resident ? carve(rec_bytes) : 0,
+               o_dec = from_bytes ? carve(sizeof(capgpu_proof) * count) : 0,
+               o_dst = from_bytes ? carve(sizeof(int) * count) : 0;
   const MsmVarDesc desc[2] = {{0, 0, (uint32_t)(vf::kATerms * count)},
                               {(uint64_t)(vf::kATerms * count), (uint32_t)(vf::kATerms * count),
                                (uint32_t)(msm_pts - vf::kATerms * count)}};
@@ -626,10 +635,12 @@ int verify_block(const char* who, const uint64_t* vk_handles, const uint64_t g2_
   if ((rc = scratch_reserve(c.msm_ws, pl.workspace_bytes))) return rc;
   char* d = (char*)c.stage_a.p;
   hipStream_t s = c.stream;
-  const uint8_t* d_proofs = resident ? (const uint8_t*)proofs : (const uint8_t*)(d + o_proofs);
+  const uint8_t* d_proofs = from_bytes ? (const uint8_t*)(d + o_dec)
+                                       : (resident ? (const uint8_t*)proofs : (const uint8_t*)(d + o_proofs));
   const fe* d_pubs = resident ? (const fe*)pub_inputs : (const fe*)(d + o_pubs);
   if (!resident) {
-    CAP_HIP(hipMemcpyAsync(d + o_proofs, proofs, sizeof(capgpu_proof) * count, hipMemcpyHostToDevice, s));
+    if (from_bytes) CAP_HIP(hipMemcpyAsync(d + o_rec, proofs, rec_bytes, hipMemcpyHostToDevice, s));
+    else CAP_HIP(hipMemcpyAsync(d + o_proofs, proofs, sizeof(capgpu_proof) * count, hipMemcpyHostToDevice, s));
     if (num_inputs) CAP_HIP(hipMemcpyAsync(d + o_pubs, pub_inputs, sizeof(fe) * num_inputs * count, hipMemcpyHostToDevice, s));
   }
   CAP_HIP(hipMemcpyAsync(d + o_meta, meta.data(), 16 * count, hipMemcpyHostToDevice, s));
@@ -637,6 +648,10 @@ int verify_block(const char* who, const uint64_t* vk_handles, const uint64_t g2_
   CAP_HIP(hipMemcpyAsync(d + o_keys, keytab.data(), sizeof(void*) * nkeys, hipMemcpyHostToDevice, s));
   CAP_HIP(hipMemcpyAsync(d + o_desc, desc, sizeof desc, hipMemcpyHostToDevice, s));
 
+  if (from_bytes &&
+      (rc = pc::decode_launch(resident ? (const uint8_t*)proofs : (const uint8_t*)(d + o_rec), byte_stride, count, d + o_dec,
+                              (int*)(d + o_dst), s)))
+    return rc;
   const uint32_t n = (uint32_t)count;
   const vf::DevVk* const* d_keys = (const vf::DevVk* const*)(d + o_keys);
   const uint32_t* d_meta = (const uint32_t*)(d + o_meta);
@@ -679,6 +694,7 @@ int verify_block(const char* who, const uint64_t* vk_handles, const uint64_t g2_
   if ((rc = take_launch_error())) return rc;
   std::vector<int> out(each_ok_out ? count + 1 : 1);
   CAP_HIP(hipMemcpyAsync(out.data(), d + o_out, sizeof(int) * out.size(), hipMemcpyDeviceToHost, s));
+  if (decode_status_out) CAP_HIP(hipMemcpyAsync(decode_status_out, d + o_dst, sizeof(int) * count, hipMemcpyDeviceToHost, s));
   g_block_calls.fetch_add(1, std::memory_order_relaxed);
   g_block_waits.fetch_add(1, std::memory_order_relaxed);
   CAP_HIP(hipStreamSynchronize(s));  // the call's one wait (also keeps the host arrays above alive until the copies are done)
@@ -862,6 +878,31 @@ int capgpu_plonk_verify_block_resident(const uint64_t* vk_handles, const uint64_
   return verify_block("capgpu_plonk_verify_block_resident", vk_handles, g2_h, g2_beta_h, (const uint64_t*)d_pub_inputs,
                       num_inputs, (const capgpu_proof*)d_proofs, ext_msgs, ext_msg_lens, count, block_ok_out, each_ok_out,
                       true);
+}
+// the same two with the proofs as their 769 wire bytes (k_proof_decode in front of the launch sequence, the same one wait)
+int capgpu_plonk_verify_block_bytes(const uint64_t* vk_handles, const uint64_t g2_h[16], const uint64_t g2_beta_h[16],
+                                    const uint64_t* pub_inputs, size_t num_inputs, const uint8_t* proof_bytes,
+                                    size_t stride, const uint8_t* const* ext_msgs, const size_t* ext_msg_lens,
+                                    size_t count, int* block_ok_out, int* each_ok_out, int* decode_status_out) {
+  if (stride < pc::kBytes) {
+    set_error("capgpu_plonk_verify_block_bytes: stride %zu below the %u bytes of a record", stride, pc::kBytes);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  return verify_block("capgpu_plonk_verify_block_bytes", vk_handles, g2_h, g2_beta_h, pub_inputs, num_inputs, proof_bytes,
+                      ext_msgs, ext_msg_lens, count, block_ok_out, each_ok_out, false, stride, decode_status_out);
+}
+int capgpu_plonk_verify_block_bytes_resident(const uint64_t* vk_handles, const uint64_t g2_h[16],
+                                             const uint64_t g2_beta_h[16], const void* d_pub_inputs, size_t num_inputs,
+                                             const void* d_proof_bytes, size_t stride, const uint8_t* const* ext_msgs,
+                                             const size_t* ext_msg_lens, size_t count, int* block_ok_out,
+                                             int* each_ok_out, int* decode_status_out) {
+  if (stride < pc::kBytes) {
+    set_error("capgpu_plonk_verify_block_bytes_resident: stride %zu below the %u bytes of a record", stride, pc::kBytes);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  return verify_block("capgpu_plonk_verify_block_bytes_resident", vk_handles, g2_h, g2_beta_h,
+                      (const uint64_t*)d_pub_inputs, num_inputs, d_proof_bytes, ext_msgs, ext_msg_lens, count, block_ok_out,
+                      each_ok_out, true, stride, decode_status_out);
 }
 int capgpu_verify_sync_stats(uint64_t* block_calls_out, uint64_t* stream_waits_out) {
   if (block_calls_out) *block_calls_out = g_block_calls.load(std::memory_order_relaxed);

@@ -1277,15 +1277,8 @@ def plonk_vk_release(vk_handle: int):
     check(load().capgpu_plonk_vk_release(ctypes.c_uint64(vk_handle)))
 
 
-def plonk_verify_block(vk_handles, g2_h: np.ndarray, g2_beta_h: np.ndarray, pub_rows, proofs, ext_msgs=None,
-                       each: bool = False, num_inputs: int | None = None):
-    """A whole block decided on the device with one host wait.  vk_handles[i]: proof i's uploaded key; pub_rows: (count,
-    num_inputs, 4) array in plonk_prove_multi's layout (a key with fewer inputs uses the first of its row) or a DevBuf of
-    that content; proofs: a list of Proof / a (Proof * count) array, or a DevBuf holding the contiguous array - the resident
-    entry point is taken when both are DevBufs (then num_inputs must be given).  Returns block_ok, or (block_ok, each_ok)
-    with each=True: each_ok[i] == plonk_verify(...) of proof i and block_ok == all(each_ok)."""
-    count = len(vk_handles)
-    handles = (ctypes.c_uint64 * max(count, 1))(*vk_handles)
+def _block_msgs(ext_msgs, count: int):
+    """ext_msgs / ext_msg_lens of a block call (None, None for no messages) and the buffers they point into"""
     msgs_arg = lens_arg = None
     keep = []
     if ext_msgs is not None and count:
@@ -1298,6 +1291,19 @@ def plonk_verify_block(vk_handles, g2_h: np.ndarray, g2_beta_h: np.ndarray, pub_
             keep.append((ctypes.c_uint8 * max(len(m), 1)).from_buffer_copy(m or b"\0"))
             msgs_arg[i] = ctypes.cast(keep[-1], ctypes.POINTER(ctypes.c_uint8))
             lens_arg[i] = len(m)
+    return msgs_arg, lens_arg, keep
+
+
+def plonk_verify_block(vk_handles, g2_h: np.ndarray, g2_beta_h: np.ndarray, pub_rows, proofs, ext_msgs=None,
+                       each: bool = False, num_inputs: int | None = None):
+    """A whole block decided on the device with one host wait.  vk_handles[i]: proof i's uploaded key; pub_rows: (count,
+    num_inputs, 4) array in plonk_prove_multi's layout (a key with fewer inputs uses the first of its row) or a DevBuf of
+    that content; proofs: a list of Proof / a (Proof * count) array, or a DevBuf holding the contiguous array - the resident
+    entry point is taken when both are DevBufs (then num_inputs must be given).  Returns block_ok, or (block_ok, each_ok)
+    with each=True: each_ok[i] == plonk_verify(...) of proof i and block_ok == all(each_ok)."""
+    count = len(vk_handles)
+    handles = (ctypes.c_uint64 * max(count, 1))(*vk_handles)
+    msgs_arg, lens_arg, keep = _block_msgs(ext_msgs, count)
     block_ok = ctypes.c_int(0)
     each_ok = np.zeros(max(count, 1), dtype=np.int32)
     each_arg = each_ok.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if each else None
@@ -1350,6 +1356,114 @@ def proof_deserialize(data: bytes):
     buf = (ctypes.c_uint8 * max(len(data), 1)).from_buffer_copy(data if data else b"\0")
     check(load().capgpu_proof_deserialize(buf, ctypes.c_size_t(len(data)), ctypes.byref(pr), ctypes.byref(used)))
     return pr, used.value
+
+
+# ---- proofs as note bytes, in bulk and on the device (capgpu_proof_*_batch, capgpu_plonk_verify_block_bytes) -------------
+PROOF_BYTES = 769
+
+
+def _record_array(data, stride: int, count: int | None):
+    """bytes / bytearray / np.uint8 array of records `stride` apart -> (contiguous np.uint8 array, count)"""
+    if stride < PROOF_BYTES:
+        raise ValueError(f"a proof record has {PROOF_BYTES} bytes: stride {stride} is too small")
+    a = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview))
+                             else np.asarray(data, dtype=np.uint8)).reshape(-1)
+    if count is None:
+        count = 0 if a.size < PROOF_BYTES else (a.size - PROOF_BYTES) // stride + 1
+    if count and a.size < (count - 1) * stride + PROOF_BYTES:
+        raise ValueError(f"{a.size} bytes do not hold {count} records {stride} bytes apart")
+    return a, count
+
+
+def _u8p(a: np.ndarray):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)) if a.size else None
+
+
+def proof_decode_batch(data, count: int | None = None, stride: int = PROOF_BYTES):
+    """Bulk Proof::deserialize on the device (capgpu_proof_decode_batch[_dev]).  data: the records as bytes / an np.uint8
+    array (count defaults to what they hold) -> ((Proof * count) array, status int32 array), after one wait; or a DevBuf
+    (count required) -> (DevBuf of count Proof structs, DevBuf of count ints), enqueued without a wait.  status[i] is 0
+    for a record proof_deserialize accepts, else 1 + the byte offset of the first malformed field; such a record decodes
+    to all-ones words.  A malformed record never raises."""
+    if isinstance(data, DevBuf):
+        if count is None or stride < PROOF_BYTES or (count and data.nbytes < (count - 1) * stride + PROOF_BYTES):
+            raise ValueError("proof_decode_batch: a DevBuf needs count, stride >= 769 and room for count records")
+        d_proofs, d_status = DevBuf(max(count, 1) * ctypes.sizeof(Proof)), DevBuf(max(count, 1) * 4)
+        check(load().capgpu_proof_decode_batch_dev(data.ptr, ctypes.c_size_t(stride), ctypes.c_size_t(count), d_proofs.ptr,
+                                                   d_status.ptr))
+        return d_proofs, d_status
+    a, count = _record_array(data, stride, count)
+    proofs = (Proof * max(count, 1))()
+    status = np.zeros(max(count, 1), dtype=np.int32)
+    check(load().capgpu_proof_decode_batch(_u8p(a), ctypes.c_size_t(stride), ctypes.c_size_t(count), proofs,
+                                           status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+    return proofs, status[:count]
+
+
+def proof_encode_batch(proofs, count: int | None = None, stride: int = PROOF_BYTES):
+    """Bulk capgpu_proof_serialize on the device (capgpu_proof_encode_batch[_dev]).  proofs: a list of Proof / a
+    (Proof * count) array -> bytes of (count - 1) * stride + 769 (zero between the records), after one wait; or a DevBuf
+    of count contiguous structs (count required) -> a DevBuf of those bytes, enqueued without a wait."""
+    if stride < PROOF_BYTES:
+        raise ValueError(f"a proof record has {PROOF_BYTES} bytes: stride {stride} is too small")
+    if isinstance(proofs, DevBuf):
+        if count is None or proofs.nbytes < count * ctypes.sizeof(Proof):
+            raise ValueError("proof_encode_batch: a DevBuf needs count and room for count proofs")
+        d_bytes = DevBuf((count - 1) * stride + PROOF_BYTES if count else 1)
+        check(load().capgpu_proof_encode_batch_dev(proofs.ptr, ctypes.c_size_t(count), d_bytes.ptr, ctypes.c_size_t(stride)))
+        return d_bytes
+    count = len(proofs) if count is None else count
+    if not isinstance(proofs, ctypes.Array):
+        arr = (Proof * max(count, 1))()
+        for i, pr in enumerate(proofs):
+            ctypes.memmove(ctypes.byref(arr[i]), ctypes.byref(pr), ctypes.sizeof(Proof))
+        proofs = arr
+    out = np.zeros((count - 1) * stride + PROOF_BYTES if count else 0, dtype=np.uint8)
+    check(load().capgpu_proof_encode_batch(proofs, ctypes.c_size_t(count), _u8p(out), ctypes.c_size_t(stride)))
+    return out.tobytes()
+
+
+def plonk_verify_block_bytes(vk_handles, g2_h: np.ndarray, g2_beta_h: np.ndarray, pub_rows, proof_bytes, ext_msgs=None,
+                             each: bool = False, num_inputs: int | None = None, stride: int = PROOF_BYTES,
+                             status: bool = False):
+    """plonk_verify_block with the proofs as their 769 note bytes, `stride` apart: bytes / an np.uint8 array with pub_rows
+    an array, or both DevBufs (capgpu_plonk_verify_block_bytes / _bytes_resident; then num_inputs must be given).  The
+    records are decoded on the device in front of the block verifier's launches, inside its one wait.  Returns block_ok,
+    (block_ok, each_ok) with each=True, and the decode statuses (proof_decode_batch's) as a last element with status=True:
+    each_ok[i] == (status[i] == 0 and plonk_verify(...) of the decoded proof), block_ok == all(each_ok)."""
+    count = len(vk_handles)
+    handles = (ctypes.c_uint64 * max(count, 1))(*vk_handles)
+    msgs_arg, lens_arg, keep = _block_msgs(ext_msgs, count)
+    block_ok = ctypes.c_int(0)
+    each_ok = np.zeros(max(count, 1), dtype=np.int32)
+    st = np.zeros(max(count, 1), dtype=np.int32)
+    each_arg = each_ok.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if each else None
+    st_arg = st.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if status else None
+    h2 = _p(np.ascontiguousarray(g2_h, dtype=np.uint64))
+    bh = _p(np.ascontiguousarray(g2_beta_h, dtype=np.uint64))
+    if isinstance(proof_bytes, DevBuf) != isinstance(pub_rows, DevBuf):
+        raise ValueError("plonk_verify_block_bytes: proof_bytes and pub_rows must both be host data or both DevBufs")
+    if isinstance(proof_bytes, DevBuf):
+        if num_inputs is None or stride < PROOF_BYTES or pub_rows.nbytes < count * num_inputs * 32 or \
+                (count and proof_bytes.nbytes < (count - 1) * stride + PROOF_BYTES):
+            raise ValueError("plonk_verify_block_bytes: resident buffers need num_inputs and room for count records and rows")
+        check(load().capgpu_plonk_verify_block_bytes_resident(handles, h2, bh, pub_rows.ptr, ctypes.c_size_t(num_inputs),
+                                                              proof_bytes.ptr, ctypes.c_size_t(stride), msgs_arg, lens_arg,
+                                                              ctypes.c_size_t(count), ctypes.byref(block_ok), each_arg,
+                                                              st_arg))
+    else:
+        pub_rows = np.ascontiguousarray(pub_rows, dtype=np.uint64).reshape(-1)
+        if num_inputs is None:
+            num_inputs = pub_rows.size // (4 * count) if count else 0
+        if pub_rows.size != count * num_inputs * 4:
+            raise ValueError(f"plonk_verify_block_bytes: pub_rows must hold {count} x {num_inputs} elements")
+        a, _ = _record_array(proof_bytes, stride, count)
+        check(load().capgpu_plonk_verify_block_bytes(handles, h2, bh, _p(pub_rows) if pub_rows.size else None,
+                                                     ctypes.c_size_t(num_inputs), _u8p(a), ctypes.c_size_t(stride), msgs_arg,
+                                                     lens_arg, ctypes.c_size_t(count), ctypes.byref(block_ok), each_arg,
+                                                     st_arg))
+    out = (bool(block_ok.value),) + ((each_ok[:count] != 0,) if each else ()) + ((st[:count],) if status else ())
+    return out[0] if len(out) == 1 else out
 
 
 # ---- on-disk parameter formats (include/capgpu.h, SURVEY 8f row 3) ----------------------------------------

@@ -213,14 +213,35 @@ def release_verifying_key(handle: int) -> None:
     _lib.plonk_vk_release(handle)
 
 
+def _as_records(proofs):
+    """proofs a caller holds as note bytes - one bytes object of 769-byte records, an np.uint8 array of them, or a list of
+    769-byte objects - as one bytes-like of packed records; None for proof structs"""
+    if isinstance(proofs, (bytes, bytearray, memoryview)) or (isinstance(proofs, np.ndarray) and proofs.dtype == np.uint8):
+        return proofs
+    if isinstance(proofs, (list, tuple)) and proofs and all(isinstance(p, (bytes, bytearray)) for p in proofs):
+        if any(len(p) != _lib.PROOF_BYTES for p in proofs):
+            raise ValueError(f"a serialized proof has {_lib.PROOF_BYTES} bytes")
+        return b"".join(proofs)
+    return None
+
+
 def txn_batch_verify(vk_handles, g2_h: np.ndarray, g2_beta_h: np.ndarray, public_input_rows, proofs, ext_msgs=None,
-                     num_inputs: int | None = None) -> None:
+                     num_inputs: int | None = None, proof_stride: int | None = None) -> None:
     """src/lib.rs:455-529 over uploaded keys: Ok(()) or TxnApiError::FailedSnark for the whole block, decided on the
     device with one host wait (capgpu_plonk_verify_block_dev; _resident when proofs and rows are DevBufs).
-    public_input_rows: (count, max inputs, 4) as prove_mixed takes them; proofs: what prove_mixed returned."""
+    public_input_rows: (count, max inputs, 4) as prove_mixed takes them; proofs: what prove_mixed returned - or the proofs
+    as a validator holds them, the 769 ark-serialize bytes of each note (one bytes object / np.uint8 array of packed
+    records, or a list of 769-byte objects; a DevBuf of records with proof_stride given): those are decoded on the device
+    inside the same wait (capgpu_plonk_verify_block_bytes / _bytes_resident), and a record that does not decode fails
+    the block like any other wrong proof."""
     try:
-        ok = _lib.plonk_verify_block(vk_handles, g2_h, g2_beta_h, public_input_rows, proofs, ext_msgs,
-                                     num_inputs=num_inputs)
+        records = proofs if proof_stride is not None else _as_records(proofs)
+        if records is not None:
+            ok = _lib.plonk_verify_block_bytes(vk_handles, g2_h, g2_beta_h, public_input_rows, records, ext_msgs,
+                                               num_inputs=num_inputs, stride=proof_stride or _lib.PROOF_BYTES)
+        else:
+            ok = _lib.plonk_verify_block(vk_handles, g2_h, g2_beta_h, public_input_rows, proofs, ext_msgs,
+                                         num_inputs=num_inputs)
     except (_lib.CapGpuError, ValueError) as e:
         raise TxnApiError.FailedSnark(f"Proof Verification failure: {e}") from e
     if not ok:

@@ -825,6 +825,51 @@ int capgpu_proof_serialize(const capgpu_proof* proof, uint8_t* out, size_t cap, 
  * proof).  Host only.  *consumed_out receives the bytes read. */
 int capgpu_proof_deserialize(const uint8_t* bytes, size_t len, capgpu_proof* proof_out, size_t* consumed_out);
 
+/* ---- proofs as note bytes, in bulk and on the device ------------------------------------------------------------------
+ * A validator holds a proof as the 769 bytes above, never as a capgpu_proof.  These calls run the rule of
+ * capgpu_proof_deserialize / capgpu_proof_serialize on the device for a whole block (k_proof_decode: one lane per
+ * compressed point, whole wavefronts on the square-root chain; k_proof_encode), and the two _bytes verifiers below take
+ * a block from note bytes to verdicts with one host wait.
+ *
+ * Records: `count` of them, record i at bytes + i * stride, stride >= CAPGPU_PROOF_BYTES, any byte address (nothing is
+ * read wider than a byte); the bytes between records are neither read nor written.
+ *   status_out[i]  0 for a record capgpu_proof_deserialize accepts, else 1 + the byte offset of the first field it
+ *                  would have stopped at: a length prefix (0, 200, 432, 600), a compressed point (8 + 32 k, 168,
+ *                  208 + 32 k, 368, 400), an evaluation (440 + 32 k, 608 + 32 k, 736) or the Option tag (768).
+ *   proofs_out[i]  the decoded proof, word for word capgpu_proof_deserialize's; for a record whose status is not 0
+ *                  every word is 0xFFFFFFFFFFFFFFFF - no coordinate or evaluation of it is canonical, so every verifier
+ *                  of this library rejects it by its own range checks.
+ * A malformed record never fails a call: CAPGPU_OK whatever the records hold.  stride < CAPGPU_PROOF_BYTES, a null
+ * pointer with count > 0 or count > 2^24: CAPGPU_ERR_INVALID_ARG before a device is looked for; count == 0 is CAPGPU_OK
+ * (after CAPGPU_ERR_NOT_INITIALISED). */
+#define CAPGPU_PROOF_BYTES 769
+/* Replaces a loop of capgpu_proof_deserialize (Proof::deserialize per note, 13 square roots in Fq each on one host
+ * thread): host buffers, one upload, one launch sequence, one wait. */
+int capgpu_proof_decode_batch(const uint8_t* bytes, size_t stride, size_t count, capgpu_proof* proofs_out, int* status_out);
+/* The same on device buffers (d_proofs_out 16-byte aligned, d_status_out 4-byte aligned): enqueued on the calling
+ * context's stream, no wait - the conventions of capgpu_msm_g1_var_dev. */
+int capgpu_proof_decode_batch_dev(const void* d_bytes, size_t stride, size_t count, void* d_proofs_out, int* d_status_out);
+/* Replaces a loop of capgpu_proof_serialize: record i receives exactly its bytes for proofs[i] (the inverse of the
+ * decoder on canonical proofs).  _dev: device buffers, enqueued, no wait - a prover's proofs become note bytes without
+ * leaving the device. */
+int capgpu_proof_encode_batch(const capgpu_proof* proofs, size_t count, uint8_t* bytes_out, size_t stride);
+int capgpu_proof_encode_batch_dev(const void* d_proofs, size_t count, void* d_bytes_out, size_t stride);
+/* capgpu_plonk_verify_block_dev / capgpu_plonk_verify_block_resident with the proofs given as note bytes (replaces a loop
+ * of capgpu_proof_deserialize in front of them): the records are decoded into the call's scratch and the block
+ * verifier's launch sequence runs on that buffer.  decode_status_out: NULL or count ints, the statuses above.
+ * each_ok_out[i] = (status i == 0) && capgpu_plonk_verify's verdict on the decoded proof; *block_ok_out == all(each_ok).
+ * A malformed record never fails the call.  Still one stream wait per call (capgpu_verify_sync_stats); workspace from
+ * the context's scratch.  _resident: d_pub_inputs and d_proof_bytes in device memory, never written. */
+int capgpu_plonk_verify_block_bytes(const uint64_t* vk_handles, const uint64_t g2_h[16], const uint64_t g2_beta_h[16],
+                                    const uint64_t* pub_inputs, size_t num_inputs, const uint8_t* proof_bytes,
+                                    size_t stride, const uint8_t* const* ext_msgs, const size_t* ext_msg_lens,
+                                    size_t count, int* block_ok_out, int* each_ok_out, int* decode_status_out);
+int capgpu_plonk_verify_block_bytes_resident(const uint64_t* vk_handles, const uint64_t g2_h[16],
+                                             const uint64_t g2_beta_h[16], const void* d_pub_inputs, size_t num_inputs,
+                                             const void* d_proof_bytes, size_t stride, const uint8_t* const* ext_msgs,
+                                             const size_t* ext_msg_lens, size_t count, int* block_ok_out,
+                                             int* each_ok_out, int* decode_status_out);
+
 /* ---- on-disk parameter formats ------------------------------------------------------
  * The reference stores and loads its parameters as ark-serialize 0.3 `CanonicalSerialize` bytes
  * (store_data / load_data, src/parameters.rs:560-577; load_srs, src/proof/mod.rs:74-109) and notes that

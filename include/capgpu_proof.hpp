@@ -626,6 +626,59 @@ inline Result<Proof> deserialize_proof(const std::vector<uint8_t>& bytes) {
   return p;
 }
 
+
+// The same for a block of notes, on the device (capgpu_proof_decode_batch / _encode_batch): `records` holds one
+// CAPGPU_PROOF_BYTES record per proof, packed.  A record that does not decode is no error of the call: its status is
+// 1 + the byte offset of the first malformed field and its Proof is all-ones words, which every verifier here refuses.
+struct DecodedProofs {
+  std::vector<Proof> proofs;
+  std::vector<int> status;  // 0: decoded
+};
+inline Result<DecodedProofs> deserialize_proofs(const std::vector<uint8_t>& records) {
+  DecodedProofs out;
+  const size_t count = records.size() / CAPGPU_PROOF_BYTES;
+  if (records.size() != count * CAPGPU_PROOF_BYTES) return TxnApiError::failed_snark("Proof deserialization: not a whole number of records");
+  out.proofs.resize(count);
+  out.status.resize(count);
+  int rc = capgpu_proof_decode_batch(records.data(), CAPGPU_PROOF_BYTES, count, out.proofs.data(), out.status.data());
+  if (rc != CAPGPU_OK) return detail::map_error(rc, "Proof deserialization");
+  return out;
+}
+inline Result<std::vector<uint8_t>> serialize_proofs(const std::vector<Proof>& proofs) {
+  std::vector<uint8_t> out(proofs.size() * CAPGPU_PROOF_BYTES);
+  int rc = capgpu_proof_encode_batch(proofs.data(), proofs.size(), out.data(), CAPGPU_PROOF_BYTES);
+  if (rc != CAPGPU_OK) return detail::map_error(rc, "Proof serialization");
+  return out;
+}
+
+// txn_batch_verify (src/lib.rs:455-529) for a validator that holds each note's proof as its bytes: keys uploaded once
+// (capgpu_plonk_vk_upload), `records` as above, pub_inputs `count` rows of num_inputs elements, ext_msgs empty or one
+// entry per proof.  Decoding, transcripts, scalars, group arithmetic and the pairing check run on the device behind one
+// host wait (capgpu_plonk_verify_block_bytes); a record that does not decode fails the block like a wrong proof.
+inline Result<Unit> batch_verify_bytes(const std::vector<uint64_t>& vk_handles, const std::array<uint64_t, 16>& h,
+                                       const std::array<uint64_t, 16>& beta_h, const std::vector<Fr>& pub_inputs,
+                                       size_t num_inputs, const std::vector<uint8_t>& records,
+                                       const std::vector<std::vector<uint8_t>>& ext_msgs = {}) {
+  const size_t count = vk_handles.size();
+  if (records.size() != count * CAPGPU_PROOF_BYTES || pub_inputs.size() != count * num_inputs ||
+      (!ext_msgs.empty() && ext_msgs.size() != count))
+    return TxnApiError::failed_snark("Batch Proof Verification failure: one record, one row and one message per key handle");
+  std::vector<const uint8_t*> msgs;
+  std::vector<size_t> lens;
+  for (const auto& m : ext_msgs) {
+    msgs.push_back(m.empty() ? nullptr : m.data());
+    lens.push_back(m.size());
+  }
+  int ok = 0;
+  int rc = capgpu_plonk_verify_block_bytes(vk_handles.data(), h.data(), beta_h.data(),
+                                           pub_inputs.empty() ? nullptr : pub_inputs[0].data(), num_inputs, records.data(),
+                                           CAPGPU_PROOF_BYTES, msgs.empty() ? nullptr : msgs.data(),
+                                           lens.empty() ? nullptr : lens.data(), count, &ok, nullptr, nullptr);
+  if (rc != CAPGPU_OK) return detail::map_error(rc, "Batch Proof Verification failure");
+  if (!ok) return TxnApiError::failed_snark("Batch Proof Verification failure: WrongProof");
+  return Unit{};
+}
+
 }  // namespace capgpu
 
 #endif  // CAPGPU_PROOF_HPP
