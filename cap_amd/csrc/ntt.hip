@@ -446,9 +446,12 @@ __global__ void powers_table(fe* out, size_t n, const fe* __restrict__ pw, fe sc
 //   X[k] = Y0 + T1 + T2,  X[k + M] = Y0 - T2 + D,  X[k + 2M] = Y0 - T1 - D,  D = w3 (T1 - T2)     (3 multiplications)
 // post != null (inverse transform): every output is multiplied by post[index] (an arkworks-form integer table, which
 // takes internal-form data to arkworks' form) and leaves canonical; otherwise outputs leave weakly reduced.
+// add != null (with post only): [count][M / 2] arkworks-form values (< r); output k + M b of array q takes
+// add[q][k mod M / 2] after the post product - one load serves the thread's three outputs.
 __global__ __launch_bounds__(kThreads) void ntt3_combine(const fe* __restrict__ y, fe* __restrict__ out, size_t out_outer,
                                                          size_t out_inner, uint32_t out_group, size_t m_len,
-                                                         const fe* __restrict__ tw, fe w3, const fe* __restrict__ post) {
+                                                         const fe* __restrict__ tw, fe w3, const fe* __restrict__ post,
+                                                         const fe* __restrict__ add) {
   using F = Fr29;
   const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= m_len) return;
@@ -463,9 +466,17 @@ __global__ __launch_bounds__(kThreads) void ntt3_combine(const fe* __restrict__ 
   fl x1 = F::normalize(F::add(F::sub(y0, t2), d));
   fl x2 = F::sub(F::sub(y0, t1), d);
   if (post) {
-    o[k] = F::pack(F::canonical(F::mul(x0, F::load(post[k]))));
-    o[m_len + k] = F::pack(F::canonical(F::mul(x1, F::load(post[m_len + k]))));
-    o[2 * m_len + k] = F::pack(F::canonical(F::mul(x2, F::load(post[2 * m_len + k]))));
+    // products < 2p plus a value < p: normalized and well inside what canonical takes
+    const size_t half = m_len >> 1;
+    const fl a = add ? F::load(add[(size_t)q * half + (k & (half - 1))]) : F::zero();
+    auto finish = [&](const fl& x, const fe& ps) {
+      fl v = F::mul(x, F::load(ps));
+      if (add) v = F::add_norm(v, a);
+      return F::pack(F::canonical(v));
+    };
+    o[k] = finish(x0, post[k]);
+    o[m_len + k] = finish(x1, post[m_len + k]);
+    o[2 * m_len + k] = finish(x2, post[2 * m_len + k]);
   } else {
     o[k] = F::store(x0);
     o[m_len + k] = F::store(x1);
@@ -797,7 +808,7 @@ int ntt_run(const NttDomain& dom, const NttSmallTables& small, fe* data, fe* scr
     p.pre_scale = first ? pre : nullptr;
     p.post_scale = (dir && coset) ? dom.coset29_inv : nullptr;
     p.use_post_scalar = (dir && !coset) ? 1 : 0;
-    p.post_scalar = dom.n_inv29;
+    p.post_scalar = (io && io->has_post_scalar) ? io->post_scalar : dom.n_inv29;
     p.lazy_out = (io && io->lazy_out) ? 1 : 0;
     p.log_len = log_len;
     p.log_c = log_c;
@@ -859,6 +870,10 @@ int ntt3_build_domain(Ntt3Domain* d, uint32_t log_m, hipStream_t stream) {
     s_a = Fr::mul(s_a, wN);
   }
   if ((rc = build_powers(d->tw29_inv, 2 * M, Fr::inv(wN), nullptr, stream))) return rc;
+  // kappa = 1 / (5^N - 1) (5 generates the whole multiplicative group: 5^N != 1), and kappa / n for n = M / 2
+  uint32_t eN[8] = {(uint32_t)N, (uint32_t)((uint64_t)N >> 32), 0, 0, 0, 0, 0, 0};
+  d->kappa = Fr::inv(Fr::sub(Fr::pow(g, eN), Fr::one()));
+  d->kappa_n_inv29 = to_internal(Fr::mul(Fr::add(d->kappa, d->kappa), Fr::inv(host_from_u64((uint64_t)M))));
   const fe third = Fr::inv(host_from_u64(3));
   if ((rc = build_powers(d->coset_inv_ext, N, Fr::inv(g), &third, stream))) return rc;
   const unsigned blocks = (unsigned)((N + 255) / 256);
@@ -902,8 +917,9 @@ int ntt3_forward(const Ntt3Domain& d3, const NttDomain& dom_m, const NttSmallTab
 }
 
 int ntt3_inverse(const Ntt3Domain& d3, const NttDomain& dom_m, const NttSmallTables& small, fe* data, uint32_t count,
-                 fe* scratch, hipStream_t stream) {
+                 fe* scratch, hipStream_t stream, const fe* add) {
   if (dom_m.log_n != d3.log_m) return (int)hipErrorInvalidValue;
+  if (add && d3.log_m == 0) return (int)hipErrorInvalidValue;  // blocks of M / 2
   const size_t M = (size_t)1 << d3.log_m, N = 3 * M;
   fe* y = scratch;
   fe* sub_scratch = scratch + (size_t)count * 3 * M;
@@ -922,7 +938,7 @@ int ntt3_inverse(const Ntt3Domain& d3, const NttDomain& dom_m, const NttSmallTab
   int rc = ntt_run(dom_m, small, y, sub_scratch, M, count * 3, 1, 0, stream, &sub);
   if (rc) return rc;
   launch("ntt3_combine", ntt3_combine, dim3((unsigned)((M + kThreads - 1) / kThreads), count), dim3(kThreads), 0, stream,
-         (const fe*)y, data, N, (size_t)0, 1u, M, (const fe*)d3.tw29_inv, d3.w3inv_29, (const fe*)d3.coset_inv_ext);
+         (const fe*)y, data, N, (size_t)0, 1u, M, (const fe*)d3.tw29_inv, d3.w3inv_29, (const fe*)d3.coset_inv_ext, add);
   return 0;  // launch failures are latched by launch() and reported by take_launch_error()
 }
 

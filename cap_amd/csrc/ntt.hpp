@@ -78,6 +78,10 @@ struct NttIo {
   size_t pre_inner = 0;           // pre-scale table of array q: pre_scale + (q % src_group) * pre_inner
   const fe* pre_scale = nullptr;  // overrides the coset table of the domain (internal form)
   int lazy_out = 0;               // leave results weakly reduced (< 2r) instead of canonical
+  // plain inverse transforms (dir 1, coset 0) only: multiply every output by this scalar (internal form) in place of the
+  // domain's n^-1 - a constant factor of the result rides on the multiplication the transform performs anyway
+  int has_post_scalar = 0;
+  fe post_scalar = {};
 };
 int ntt_run(const NttDomain& dom, const NttSmallTables& small, fe* data, fe* scratch, size_t stride_elems,
             uint32_t count, int dir, int coset, hipStream_t stream, const NttIo* io = nullptr);
@@ -116,6 +120,13 @@ struct Ntt3Domain {
   fe* coset_inv_ext = nullptr;  // 5^-i / 3, i < N, as an arkworks-form integer: internal-form data in, arkworks out
   fe w3inv_29;                  // omega_N^-M, internal form
   fe omega;                     // omega_N, arkworks form (host)
+  // kappa = 1 / (5^N - 1): every point x of the coset has x^N = 5^N, so with n = M / 2 (N = 6n)
+  //   1 / (x^n - 1) = kappa (1 + x^n + ... + x^(5n))  there,
+  // and the interpolant of A(x) / (x^n - 1) for a polynomial A of degree < n is kappa A(X) (1 + X^n + ... + X^(5n)):
+  // A's coefficients, scaled, repeated in the six blocks of n (the `add` of ntt3_inverse)
+  fe kappa;                     // arkworks form (host)
+  fe kappa_n_inv29;             // kappa / n, internal form: NttIo::post_scalar of the n-point inverse transform that
+                                // interpolates such an A from its values
 };
 int ntt3_build_domain(Ntt3Domain* d, uint32_t log_m, hipStream_t stream);
 void ntt3_free_domain(Ntt3Domain* d);
@@ -126,8 +137,10 @@ int ntt3_forward(const Ntt3Domain& d3, const NttDomain& dom_m, const NttSmallTab
                  uint32_t count, fe* scratch, hipStream_t stream);
 // Inverse in place: data[q * N .. +N) internal-form evaluations (block order) -> arkworks-form coefficients (natural
 // order, canonical).  scratch: 6 M count elements.
+// add (optional): [count][M / 2] arkworks-form values; coefficient i of array q leaves as t[i] + add[q][i mod M / 2] - all
+// six blocks of M / 2, inside the radix-3 stage.  Null: nothing is added.
 int ntt3_inverse(const Ntt3Domain& d3, const NttDomain& dom_m, const NttSmallTables& small, fe* data, uint32_t count,
-                 fe* scratch, hipStream_t stream);
+                 fe* scratch, hipStream_t stream, const fe* add = nullptr);
 
 // out[i] = internal Montgomery form (x * 2^261, canonical) of the arkworks-form value in[i]
 void ntt_table_to_internal(fe* out, const fe* in, size_t n, hipStream_t stream);

@@ -5,9 +5,9 @@
 // and :113, src/proof/freeze.rs:102 and :151 (algorithm: SURVEY.md §3.2 / Appendix A).
 // The host keeps only what is O(1) per proof: the Keccak transcript, the challenge
 // arithmetic and Jacobian -> affine of the 13 commitments.  All O(n) work - 7 iNTT(n),
-// the coset transforms of the quotient step (jf-plonk: 26 of size 8n; here 8 of size 6n per
-// proof, the 18 key columns being cached), 13 MSM, grand product, quotient, evaluations,
-// linearisation, openings - runs on the GPU without leaving HBM between rounds.  With capgpu_plonk_set_transcript(DEVICE)
+// the coset transforms of the quotient step (jf-plonk: 26 of size 8n; here 7 of size 6n per
+// proof, the 18 key columns being cached and the public-input term added as coefficients),
+// 13 MSM, grand product, quotient, evaluations, linearisation, openings - runs on the GPU without leaving HBM between rounds.  With capgpu_plonk_set_transcript(DEVICE)
 // the O(1) steps move there too (transcript_dev.hpp) and a call is enqueued whole: one host wait instead of six or seven.
 //
 // MI355X-first choices: a batch of P proofs is proved in lockstep so that every launch

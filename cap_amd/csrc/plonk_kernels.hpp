@@ -257,7 +257,9 @@ __global__ __launch_bounds__(kThreads) void k_perm_finish(const fe* __restrict__
 // All inputs are in the internal Montgomery form of the lazy 29-bit field (x * 2^261): the forward coset NTTs emit
 // it (ntt3_forward) and the inverse coset NTT that follows consumes it (ntt3_inverse).
 // pkc: [18][m] coset evaluations of 13 selectors then 5 sigmas (shared by all proofs)
-// cos: [P][7][m] coset evaluations of 5 wires, z, pi;   tw_m: omega_m^i;   inv_nx1: 1 / (n (x_i - 1))
+// cos: [P][6][m] coset evaluations of 5 wires, z;   tw_m: omega_m^i;   inv_nx1: 1 / (n (x_i - 1))
+// The public-input term of the numerator is NOT evaluated here: PI(x) / Z_H(x) is added to the result as coefficients
+// by the inverse transform that follows (ntt.hpp: Ntt3Domain::kappa; prove_run.hpp: pi_fold).
 // Sums of products share one Montgomery reduction (at most 6 products per 64-bit column accumulator).
 struct ColAcc {
   uint64_t c[18];
@@ -289,7 +291,7 @@ __global__ __launch_bounds__(kThreads) void k_quotient(const fe* __restrict__ pk
   if (pkc_of) pkc = pkc_of[p];
   const uint32_t mm = (uint32_t)(m / 3);                                  // block length M (uniform: scalar unit)
   const uint32_t blk = (i >= mm ? 1u : 0u) + (i >= 2 * (size_t)mm ? 1u : 0u);  // which of the three cosets
-  const fe* c = cos + (size_t)p * 7 * m;
+  const fe* c = cos + (size_t)p * 6 * m;
   auto sel = [&](int s) { return F::load(pkc[(size_t)s * m + i]); };
   fl w0 = F::load(c[i]), w1 = F::load(c[m + i]), w2 = F::load(c[2 * m + i]), w3 = F::load(c[3 * m + i]),
      w4 = F::load(c[4 * m + i]);
@@ -318,8 +320,8 @@ __global__ __launch_bounds__(kThreads) void k_quotient(const fe* __restrict__ pk
   acc.mad(sel(12), F::mul(F::mul(w01, w23), w4));
   acc.mad(F::neg(sel(10)), w4);
   fl gate2 = acc.reduce();
-  // gate + q_c + pi: four values < 2p each, limbs < 2^31 after the lazy adds
-  fl total = F::normalize(F::add(F::add(gate, gate2), F::add(sel(11), F::load(c[6 * m + i]))));
+  // gate + q_c: three values < 2p each, limbs < 2^31 after the lazy adds
+  fl total = F::normalize(F::add(F::add(gate, gate2), sel(11)));
   // permutation part
   const fl beta = F::load(chal[p].beta), gamma = F::load(chal[p].gamma);
   const fl zx = F::load(c[5 * m + i]);

@@ -63,8 +63,9 @@ int run_ntt(hipStream_t s, uint32_t log_n, fe* data, size_t stride, uint32_t cou
 
 // out-of-place form: `count` arrays of src_len elements at src (src_stride apart; zero-extended to the transform
 // size inside the kernel) -> transforms at dst (dst_stride apart).  Saves the padded copy an in-place call needs.
+// post_scalar (plain inverse transforms only): takes the place of n^-1 (NttIo::post_scalar)
 int run_ntt_from(hipStream_t s, uint32_t log_n, const fe* src, size_t src_stride, size_t src_len, fe* dst,
-                 size_t dst_stride, uint32_t count, int dir, int coset) {
+                 size_t dst_stride, uint32_t count, int dir, int coset, const fe* post_scalar = nullptr) {
   Context& c = ctx();
   const NttDomain* dom = nullptr;
   int rc = get_domain(log_n, &dom);
@@ -80,6 +81,10 @@ int run_ntt_from(hipStream_t s, uint32_t log_n, const fe* src, size_t src_stride
   io.dst_outer = dst_stride;
   io.dst_inner = 0;
   io.dst_group = 1;
+  if (post_scalar) {
+    io.has_post_scalar = 1;
+    io.post_scalar = *post_scalar;
+  }
   rc = ntt_run(*dom, c.small, dst, (fe*)c.ntt_scratch.p, dst_stride, count, dir, coset, s, &io);
   if (rc) return hip_fail((hipError_t)rc, "ntt_run");
   return CAPGPU_OK;
@@ -103,14 +108,15 @@ int run_ntt3_fwd(hipStream_t s, uint32_t log_mm, fe* data, uint32_t count, const
   if (rc) return hip_fail((hipError_t)rc, "ntt3_forward");
   return CAPGPU_OK;
 }
-int run_ntt3_inv(hipStream_t s, uint32_t log_mm, fe* data, uint32_t count) {
+// add: see ntt3_inverse
+int run_ntt3_inv(hipStream_t s, uint32_t log_mm, fe* data, uint32_t count, const fe* add = nullptr) {
   Context& c = ctx();
   const Ntt3Domain* d3 = nullptr;
   const NttDomain* dm = nullptr;
   int rc = quot_domains(log_mm, &d3, &dm);
   if (rc) return rc;
   if ((rc = scratch_reserve(c.ntt_scratch, ntt3_scratch(log_mm, count)))) return rc;
-  rc = ntt3_inverse(*d3, *dm, c.small, data, count, (fe*)c.ntt_scratch.p, s);
+  rc = ntt3_inverse(*d3, *dm, c.small, data, count, (fe*)c.ntt_scratch.p, s, add);
   if (rc) return hip_fail((hipError_t)rc, "ntt3_inverse");
   return CAPGPU_OK;
 }
@@ -182,7 +188,8 @@ BatchWs carve(void* base, const ProvingKey& K, uint32_t P, size_t num_inputs, bo
   w.wpoly = c.take<fe>((size_t)P * NW * ps);
   // coefficient-form input: the witness VALUES round 2 reads are one forward transform of the caller's polynomials
   w.wev = coeffs ? c.take<fe>((size_t)P * NW * n) : nullptr;
-  w.pi = c.take<fe>((size_t)P * n);
+  // kappa PI(X), kappa = 1 / (5^(6n) - 1): what round 3 adds to the quotient's coefficients (pi_fold)
+  w.pi = num_inputs ? c.take<fe>((size_t)P * n) : nullptr;
   w.num = c.take<fe>((size_t)P * n);
   w.den = c.take<fe>((size_t)P * n);
   w.pre = c.take<fe>((size_t)P * n);
@@ -190,7 +197,7 @@ BatchWs carve(void* base, const ProvingKey& K, uint32_t P, size_t num_inputs, bo
   w.scan_tot = c.take<fe>((size_t)P * 2 * (cdiv(ps, kScanBlock) + 1));
   w.inv_total = c.take<fe>(P);
   w.zpoly = c.take<fe>((size_t)P * ps);
-  w.coset = c.take<fe>((size_t)P * 7 * m);
+  w.coset = c.take<fe>((size_t)P * 6 * m);
   w.pkc = K.recompute ? c.take<fe>((size_t)18 * m) : nullptr;
   w.t = c.take<fe>((size_t)P * m);
   w.pows = c.take<fe>((size_t)P * 4 * ps);
@@ -823,30 +830,34 @@ struct ProveRun {
     nd.ntt(ntt_scratch_from(K.log_n, (size_t)cnt * NW));
     nd.msm(pl.wire_key(), K.n + 2, cnt * NW);
   }
+  // The public-input polynomial enters the quotient's numerator linearly and multiplies nothing, so it never goes to the
+  // 6n domain: on the coset 5 <omega_6n> every point has x^(6n) = 5^(6n), hence 1 / Z_H(x) = kappa (1 + x^n + ... + x^(5n))
+  // with kappa = 1 / (5^(6n) - 1), and the interpolant of PI(x) / Z_H(x) is kappa PI(X) (1 + X^n + ... + X^(5n)) exactly.
+  // w.pi holds kappa PI(X) - kappa rides on the interpolation's n^-1 - and round 3's inverse transform adds it to each of
+  // the six blocks of n coefficients (ntt3_inverse).  No public inputs: nothing to add, no array.
+  int pi_fold(hipStream_t st) {
+    if (!num_inputs) return CAPGPU_OK;
+    return run_ntt_from(st, K.log_n, w.d_pub, num_inputs, num_inputs, w.pi, n, P, 1, 0, &dom_q->kappa_n_inv29);
+  }
   int r1_tail_kernels() {
     int r;
-    if (num_inputs) {
-      if ((r = run_ntt_from(s, K.log_n, w.d_pub, num_inputs, num_inputs, w.pi, n, P, 1, 0))) return r;
-    } else {
-      CAP_HIP(hipMemsetAsync(w.pi, 0, sizeof(fe) * (size_t)P * n, s));
-    }
+    if ((r = pi_fold(s))) return r;
     if (pl.chunks == 1 && (r = commit_wires(0, P))) return r;
     return CAPGPU_OK;
   }
   static void r1_tail_needs(const ProvePlan&, const ProvingKey& K, uint32_t cnt, ProveNeeds& nd) {
     if (K.num_inputs) nd.ntt(ntt_scratch_from(K.log_n, cnt));  // the public-input polynomial
   }
-  // round 3's coset evaluations of the wire and public-input polynomials (on the 6n quotient domain, straight from
-  // their coefficient arrays: the transform zero-extends them) depend on nothing the transcript still has to produce
+  // round 3's coset evaluations of the wire polynomials (on the 6n quotient domain, straight from their coefficient
+  // arrays: the transform zero-extends them) depend on nothing the transcript still has to produce.  w.coset: [P][6][m],
+  // the wires at 0..4, z at 5.
   int r3_wire_cosets(hipStream_t st) {
-    int r = run_ntt3_fwd(st, K.log_m, w.coset, P * NW, NttIo{w.wpoly, NW * ps, ps, n + 2, NW, 7 * m, m, NW});
-    if (r) return r;
-    return run_ntt3_fwd(st, K.log_m, w.coset + 6 * m, P, NttIo{w.pi, n, 0, n, 1, 7 * m, 0, 1});
+    return run_ntt3_fwd(st, K.log_m, w.coset, P * NW, NttIo{w.wpoly, NW * ps, ps, n + 2, NW, 6 * m, m, NW});
   }
   // the commitment to z and - independent of it - z's coset evaluations for round 3: one after the other (the second while
   // the host hashes), or, for the small batches of `overlap`, side by side on the two streams
   int z_cosets(hipStream_t st) {
-    return run_ntt3_fwd(st, K.log_m, w.coset + 5 * m, P, NttIo{w.zpoly, ps, 0, n + 3, 1, 7 * m, 0, 1});
+    return run_ntt3_fwd(st, K.log_m, w.coset + 5 * m, P, NttIo{w.zpoly, ps, 0, n + 3, 1, 6 * m, 0, 1});
   }
   // (r3_wire_cosets and z_cosets)
   static void cosets_needs(const ProvePlan&, const ProvingKey& K, uint32_t cnt, ProveNeeds& nd) {
@@ -875,11 +886,7 @@ struct ProveRun {
     CAP_HIP(hipStreamWaitEvent(s2, c.ev_fork, 0));
     // side stream: the polynomials and their coset evaluations
     if (pl.Lag && (r = interpolate_and_blind(s2))) return r;
-    if (num_inputs) {
-      if ((r = run_ntt_from(s2, K.log_n, w.d_pub, num_inputs, num_inputs, w.pi, n, P, 1, 0))) return r;
-    } else {
-      CAP_HIP(hipMemsetAsync(w.pi, 0, sizeof(fe) * (size_t)P * n, s2));
-    }
+    if ((r = pi_fold(s2))) return r;
     if ((r = r3_wire_cosets(s2))) return r;
     // main stream: the five commitments
     if ((r = commit_wires(0, P))) return r;
@@ -955,7 +962,7 @@ struct ProveRun {
     return finish_and_commit_z();
   }
 
-  // ---- round 3: quotient polynomial (its seven coset transforms were enqueued behind the round 1 and 2 MSMs) ------
+  // ---- round 3: quotient polynomial (its six coset transforms were enqueued behind the round 1 and 2 MSMs) ------
   int r3_body() {
     int r;
     const fe* pkc = K.pk_coset;
@@ -967,7 +974,8 @@ struct ProveRun {
     }
     launch("k_quotient", k_quotient, dim3(P, cdiv(m, kThreads)), dim3(kThreads), 0, s, pkc, pkc_of,
            (const fe*)w.coset, (const fe*)dom_q->xs29, (const fe*)K.inv_nx1, (const Chal*)w.chal29, K.qc29, m, w.t);
-    if ((r = run_ntt3_inv(s, K.log_m, w.t, P))) return r;
+    // k_quotient leaves the public-input term out; it arrives here as coefficients (pi_fold), before the degree check
+    if ((r = run_ntt3_inv(s, K.log_m, w.t, P, w.pi))) return r;
     {
       size_t lo = NW * (n + 1) + 3;  // first index that must be zero: degree is exactly 5(n+1)+2
       launch("k_check_degree", k_check_degree, dim3(cdiv(m - (lo - 1), kThreads), P), dim3(kThreads), 0, s,
