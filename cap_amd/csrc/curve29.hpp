@@ -179,6 +179,36 @@ struct G1LT {
     a = o;
     return true;
   }
+  // The first addition of an item of msm_accumulate: out = (+-q0) + (+-q1) for two AFFINE table points (canonical, as
+  // the table holds them), common case only.  With both z = 1 the cross products u2, s2 and the two products into zz,
+  // zzz of the mixed addition fall away: 2 squarings, 2 products and the fused pair, 5 reductions, against the 2 + 10.5
+  // multiplication-equivalents of add_mixed from infinity followed by madd_acc.
+  // Returns false - out untouched - when the x-difference vanishes: q1 == +-q0; the caller then starts the item as
+  // before.  Neither point may be the point at infinity (the caller tests both).
+  // Carries and bounds:
+  //   * p = x1 - x0 + 2p is carried (it is squared) and < 3p, so that zz = p^2 and zzz = p^3 come out < 1.1p;
+  //   * +-y is y or 2p - y with un-carried limbs (< 2^30): the operands of one carried subtraction (r < 18p) and, with
+  //     the opposite sign, the un-carried multiplicand of the fused product, as 4p - acc.y is in madd_acc;
+  //   * x3 and y3 exactly as in madd_acc: y3 = r (qq - x3 + 2p) + (-+y0) ppp < (18 * 3.1 + 2 * 1.1) p^2 / 169p + p < 1.4p.
+  // Out: the invariants madd_acc states - x < 2p, y < 3p, zz, zzz < 1.2p, normalized limbs.
+  static CAP_HD bool add_affine_pair(g1x& out, const g1a& q0, bool neg0, const g1a& q1, bool neg1) {
+    const fl p = F::sub2p(q1.x, q0.x);
+    if (F::is_zero(p)) return false;
+    const fl n0 = F::neg2p_lazy(q0.y);
+    const fl y0 = neg0 ? n0 : q0.y, my0 = neg0 ? q0.y : n0;
+    const fl y1 = neg1 ? F::neg2p_lazy(q1.y) : q1.y;
+    const fl r = F::sub(y1, y0);
+    const fl pp = F::sqr(p);
+    const fl ppp = F::mul(p, pp);
+    const fl qq = F::mul(q0.x, pp);
+    g1x o;
+    o.x = F::weak_reduce(F::sub_from_lazy(F::sub2p_lazy(F::sqr(r), ppp), F::add(qq, qq)));
+    o.y = F::mul_add_mul(r, F::sub2p_lazy(qq, o.x), my0, ppp);
+    o.zz = pp;
+    o.zzz = ppp;
+    out = o;
+    return true;
+  }
   // a += b for two XYZZ points, common case only - the running sums of the bucket reduction (msm_reduce_segments).
   // Returns false - a untouched - when the x-difference vanishes: either side at infinity (zz = 0 and x = 0 make both
   // cross products 0), a == b, a == -b; the caller falls back to add().  Carries as in madd_acc.

@@ -1121,7 +1121,21 @@ __global__ __launch_bounds__(kThreads) CAP_ACC_ATTR void msm_accumulate(const g1
   // vanish, a table point at infinity is caught by the OR over its limbs, and both go to the general G1L::add_mixed
   // in a branch of its own, so that its selects and copies never sit in the hot block (2650 -> 2260 instructions per
   // addition on the common path).
-  for (uint32_t e = lo; e < hi; e++) {
+  // The first two entries of an item are two affine table points: their sum is G1L::add_affine_pair (5.5 multiplication-
+  // equivalents) instead of a copy through add_mixed (2, for the u2 and s2 that find the accumulator at infinity) plus a
+  // full mixed addition (10.5).  The lanes of a wave start their items together and the items are sorted by length, so
+  // the peeled block is wave-uniform.  A one-entry item, a table point at infinity and q1 == +-q0 (add_affine_pair
+  // refuses) start from infinity in the loop as before.  -DCAP_ACC_NO_PAIR: every item starts from infinity.
+  uint32_t e = lo;
+#ifndef CAP_ACC_NO_PAIR
+  if (hi - lo >= 2) {
+    const uint32_t v0 = lst[lo], v1 = lst[lo + 1];
+    const g1a p0 = G1L::load(ext[v0 & 0x7FFFFFFFu]), p1 = G1L::load(ext[v1 & 0x7FFFFFFFu]);
+    if (!G1L::is_inf(p0) && !G1L::is_inf(p1) && G1L::add_affine_pair(acc, p0, (v0 >> 31) != 0, p1, (v1 >> 31) != 0))
+      e = lo + 2;
+  }
+#endif
+  for (; e < hi; e++) {
     const uint32_t v = lst[e];
     const g1a pt = G1L::load(ext[v & 0x7FFFFFFFu]);
     const bool negate = (v >> 31) != 0;

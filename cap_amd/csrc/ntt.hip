@@ -85,6 +85,7 @@ struct PassParams {
   const fe* post_scale;      // indexed by global output index, or null
   fe post_scalar;            // used when use_post_scalar
   uint32_t use_post_scalar;
+  uint32_t tw_scaled;        // col pass: tw_full is the 1/n-scaled inverse table - entry 0 is 1/n, not 1: no product is skipped
   uint32_t lazy_out;         // row pass: leave results weakly reduced (< 2r) instead of canonical
   uint32_t log_n;
   uint32_t log_len;          // sub-transform size
@@ -297,7 +298,7 @@ __device__ __forceinline__ void col_tile(const PassParams& p, fl* sh, const uint
       const uint32_t e = e0 + u * kThreads;
       const uint32_t c = e & cmask, k = e >> p.log_c;
       exs[u] = e < tile ? ((size_t)(col0 + c) * k) << tw_shift : 0;
-      if (exs[u]) tw[u] = p.tw_full[exs[u]];
+      if (exs[u] || p.tw_scaled) tw[u] = p.tw_full[exs[u]];
     }
 #pragma unroll
     for (int u = 0; u < kIoBatch; u++) {
@@ -305,7 +306,7 @@ __device__ __forceinline__ void col_tile(const PassParams& p, fl* sh, const uint
       if (e >= tile) break;
       const uint32_t c = e & cmask, k = e >> p.log_c;
       fl v = sh[e];
-      v = exs[u] ? Fr29::mul(v, Fr29::load(tw[u])) : Fr29::weak_reduce(v);
+      v = (exs[u] || p.tw_scaled) ? Fr29::mul(v, Fr29::load(tw[u])) : Fr29::weak_reduce(v);
       out[base + ((size_t)k << log_s) + c] = Fr29::pack(v);   // < 2p: fits the 32-byte image
     }
   }
@@ -386,6 +387,9 @@ __device__ __forceinline__ void row_tile(const PassParams& p, fl* sh, const uint
     size_t g = (size_t)(r0 + c) + ((size_t)k2 << p.log_n1) + ((size_t)k << (p.log_n1 + p.log_n2));
     if (p.post_scale) v = Fr29::mul(v, Fr29::load(p.post_scale[g]));
     else if (p.use_post_scalar) v = Fr29::mul(v, Fr29::load(p.post_scalar));
+    // (a plain inverse transform of two or more passes took its 1/n with the inter-pass twiddles - ntt_run - and, like
+    // a forward transform, arrives here straight from the butterflies: normalized limbs, far below the 169p that store
+    // and canonical take)
     // results leave the transform canonical (< r), as arkworks stores them - except the internal-form coset
     // evaluations, whose only reader (k_quotient) takes any representative below 2^256
     out[g] = p.lazy_out ? Fr29::store(v) : Fr29::pack(Fr29::canonical(v));
@@ -590,6 +594,13 @@ int ntt_build_domain(NttDomain* d, uint32_t log_n, hipStream_t stream) {
   if ((rc = build_powers(d->coset_inv, n, Fr::inv(g), &d->n_inv, stream))) return rc;
   fe* src[4] = {d->tw_fwd, d->tw_inv, d->coset_fwd, d->coset_inv};
   fe** dst[4] = {&d->tw29_fwd, &d->tw29_inv, &d->coset29_fwd, &d->coset29_inv};
+#ifndef CAP_NTT_NO_INV_FOLD
+  // omega^-e / n: the inter-pass twiddles of a plain inverse transform, its 1/n folded in (ntt_run)
+  if ((e = hipMalloc(&d->tw29_inv_n, sizeof(fe) * n)) != hipSuccess) return (int)e;
+  if ((rc = build_powers(d->tw29_inv_n, n, Fr::inv(w), &d->n_inv, stream))) return rc;
+  launch("table_to_internal", table_to_internal, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d->tw29_inv_n,
+         (const fe*)d->tw29_inv_n, n);
+#endif
   for (int k = 0; k < 4; k++) {
     if ((e = hipMalloc(dst[k], sizeof(fe) * n)) != hipSuccess) return (int)e;
     launch("table_to_internal", table_to_internal, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, *dst[k],
@@ -610,10 +621,10 @@ void ntt_free_domain(NttDomain* d) {
   if (d->tw_inv) hipFree(d->tw_inv);
   if (d->coset_fwd) hipFree(d->coset_fwd);
   if (d->coset_inv) hipFree(d->coset_inv);
-  for (fe* t : {d->tw29_fwd, d->tw29_inv, d->coset29_fwd, d->coset29_inv})
+  for (fe* t : {d->tw29_fwd, d->tw29_inv, d->tw29_inv_n, d->coset29_fwd, d->coset29_inv})
     if (t) hipFree(t);
   d->tw_fwd = d->tw_inv = d->coset_fwd = d->coset_inv = nullptr;
-  d->tw29_fwd = d->tw29_inv = d->coset29_fwd = d->coset29_inv = nullptr;
+  d->tw29_fwd = d->tw29_inv = d->tw29_inv_n = d->coset29_fwd = d->coset29_inv = nullptr;
 }
 
 void ntt_table_to_internal(fe* out, const fe* in, size_t n, hipStream_t stream) {
@@ -768,6 +779,15 @@ int ntt_run(const NttDomain& dom, const NttSmallTables& small, fe* data, fe* scr
   p.log_n = log_n;
   p.tw_full = tw_full;
   p.use_post_scalar = 0;
+  // A plain inverse transform of two or more passes that ends in the domain's own 1/n takes it with the inter-pass
+  // twiddles of its first column pass (tw29_inv_n[e] = omega^-e / n: the product is there anyway) and its row pass
+  // multiplies by nothing.  One-pass transforms have no column pass, coset inverses carry 1/n in coset29_inv, and a
+  // caller's own post_scalar (the public-input fold's kappa / n) stays a product of the row pass.
+#ifndef CAP_NTT_NO_INV_FOLD
+  const bool inv_fold = dir && !coset && passes >= 2 && !(io && io->has_post_scalar) && dom.tw29_inv_n;
+#else
+  const bool inv_fold = false;
+#endif
 
   const fe* pre = (!dir && coset) ? dom.coset29_fwd : nullptr;
   if (io && io->pre_scale) pre = io->pre_scale;
@@ -787,6 +807,8 @@ int ntt_run(const NttDomain& dom, const NttSmallTables& small, fe* data, fe* scr
     p.log_len = log_len;
     p.log_c = log_c;
     p.log_m = log_m;
+    p.tw_full = (inv_fold && d == 0) ? dom.tw29_inv_n : tw_full;
+    p.tw_scaled = (inv_fold && d == 0) ? 1 : 0;
     size_t lds = sizeof(fl) << (log_len + log_c);
     launch_pass("ntt_col_pass", ntt_col_pass<false>, ntt_col_pass<true>, p, small, (size_t)plan.tiles[d], count, lds,
                 plan.persistent[d] != 0, stream);
@@ -807,7 +829,7 @@ int ntt_run(const NttDomain& dom, const NttSmallTables& small, fe* data, fe* scr
     p.tw_small = reinterpret_cast<const fl*>(tws[log_len]);
     p.pre_scale = first ? pre : nullptr;
     p.post_scale = (dir && coset) ? dom.coset29_inv : nullptr;
-    p.use_post_scalar = (dir && !coset) ? 1 : 0;
+    p.use_post_scalar = (dir && !coset && !inv_fold) ? 1 : 0;
     p.post_scalar = (io && io->has_post_scalar) ? io->post_scalar : dom.n_inv29;
     p.lazy_out = (io && io->lazy_out) ? 1 : 0;
     p.log_len = log_len;

@@ -25,6 +25,7 @@ struct NttDomain {
   // NTT kernels multiply by.  (tw_fwd above stays in arkworks' form for the kernels that have not moved yet.)
   fe* tw29_fwd = nullptr;
   fe* tw29_inv = nullptr;
+  fe* tw29_inv_n = nullptr;  // omega_n^-e / n: inter-pass twiddles of the plain inverse transforms (null: -DCAP_NTT_NO_INV_FOLD)
   fe* coset29_fwd = nullptr;
   fe* coset29_inv = nullptr;
   fe n_inv29;

@@ -54,7 +54,7 @@ struct ProvingKey {
   uint64_t srs_handle = 0;
   fe* coef = nullptr;      // [18][ps]: 13 selector + 5 sigma polynomials (coefficients)
   fe* sig_eval = nullptr;  // [5][n]
-  fe* pk_coset = nullptr;  // [18][m]
+  fe* pk_coset = nullptr;  // [22][m]: 13 selectors, 5 sigmas, k_j x for j = 1 .. 4 (pk::kPkcCols)
   fe* inv_nx1 = nullptr;   // [m]
   QuotConst qc;    // arkworks form (host arithmetic, k_perm_numden)
   QuotConst qc29;  // internal form of the lazy field (k_quotient)
@@ -655,8 +655,9 @@ int key_finish_tables(hipStream_t s, ProvingKey& K) {
     for (int i = 0; i < 8; i++) K.qc29.zh_inv[i] = conv(K.qc.zh_inv[i]);
   }
   if (!K.recompute) {
-    CAP_HIP(hipMalloc(&K.pk_coset, sizeof(fe) * 18 * m));
+    CAP_HIP(hipMalloc(&K.pk_coset, sizeof(fe) * kPkcCols * m));
     if ((rc = compute_pk_coset(s, K, K.pk_coset))) return rc;
+    if ((rc = compute_pk_kx(s, K, K.pk_coset))) return rc;
   }
   return CAPGPU_OK;
 }
@@ -858,7 +859,7 @@ int clone_key_to_current(const ProvingKey& src, int src_device, std::shared_ptr<
   int rc;
   if ((rc = dup(&K->coef, src.coef, 18 * src.ps))) return rc;
   if ((rc = dup(&K->sig_eval, src.sig_eval, (size_t)NW * src.n))) return rc;
-  if ((rc = dup(&K->pk_coset, src.pk_coset, 18 * src.m))) return rc;
+  if ((rc = dup(&K->pk_coset, src.pk_coset, kPkcCols * src.m))) return rc;
   if ((rc = dup(&K->inv_nx1, src.inv_nx1, src.m))) return rc;
   {
     // the variable table and, with it, the permutation's index form (4 B x 5 n each) travel with the key

@@ -17,13 +17,16 @@ namespace pk {
 
 constexpr int NW = 5;    // wire types
 constexpr int NS = 13;   // selectors: q_lc x4, q_mul x2, q_hash x4, q_o, q_c, q_ecc
+constexpr int NKX = NW - 1;           // columns k_j x, j = 1 .. 4, of the quotient domain (k_kx_columns)
+constexpr int kPkcCols = NS + NW + NKX;  // columns of a key's coset table: 13 selectors, 5 sigmas, 4 x k_j x
 constexpr int kThreads = 256;
 constexpr int kScanPerThread = 4;
 constexpr int kScanBlock = kThreads * kScanPerThread;  // 1024 elements per workgroup
 
 // per-proof challenges, device layout
+// beta_inv = 1 / beta (0 for beta = 0) and alpha_beta5 = alpha beta^5: k_quotient's permutation terms with beta folded out
 struct Chal {
-  fe beta, gamma, alpha, alpha2;
+  fe beta, gamma, alpha, alpha2, beta_inv, alpha_beta5;
 };
 
 struct QuotConst {
@@ -256,7 +259,7 @@ __global__ __launch_bounds__(kThreads) void k_perm_finish(const fe* __restrict__
 // (jf-plonk uses 8n; the quotient has degree < 5n + 8, so 6n = 3 * 2^(log n + 1) points determine it - ntt.hpp)
 // All inputs are in the internal Montgomery form of the lazy 29-bit field (x * 2^261): the forward coset NTTs emit
 // it (ntt3_forward) and the inverse coset NTT that follows consumes it (ntt3_inverse).
-// pkc: [18][m] coset evaluations of 13 selectors then 5 sigmas (shared by all proofs)
+// pkc: [22][m] coset evaluations of 13 selectors then 5 sigmas, then k_j x_i for j = 1 .. 4 (shared by all proofs)
 // cos: [P][6][m] coset evaluations of 5 wires, z;   tw_m: omega_m^i;   inv_nx1: 1 / (n (x_i - 1))
 // The public-input term of the numerator is NOT evaluated here: PI(x) / Z_H(x) is added to the result as coefficients
 // by the inverse transform that follows (ntt.hpp: Ntt3Domain::kappa; prove_run.hpp: pi_fold).
@@ -276,18 +279,43 @@ struct ColAcc {
   __device__ __forceinline__ fl reduce() { return Fr29::reduce_cols(c); }
 };
 
+// columns 18 .. 21 of a key's coset table: dst[j][i] = k_(j+1) x_i, internal form, canonical.  A function of the key's
+// separators and the domain only: built once per key (per launch of k_quotient under the reference schedule).
+__global__ __launch_bounds__(kThreads) void k_kx_columns(fe* __restrict__ dst, const fe* __restrict__ xs, QuotConst qc,
+                                                         size_t m) {
+  using F = Fr29;
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  const fl x = F::load(xs[i]);
+#pragma unroll
+  for (int j = 0; j < NKX; j++) dst[(size_t)j * m + i] = F::pack(F::canonical(F::mul(F::load(qc.k[j + 1]), x)));
+}
+
 // pkc_of (optional): the key columns of proof p's own key (mixed-key batches), otherwise pkc for all
+// FOLD: the permutation terms with beta folded out (below).  That form needs 1 / beta: a proof with beta = 0 (beta_inv = 0)
+// is left to the direct form, k_quotient<false>, launched behind it with only_unfoldable = 1 - there every other proof
+// leaves at once.  p is blockIdx.x, so either exit is taken by whole workgroups.  (One kernel with both forms behind a
+// uniform branch takes 256 VGPRs + 71 AGPRs - one wave per SIMD; each form alone stays at two: 252 and 228 VGPRs.)
+// k_quotient<false> with only_unfoldable = 0 is the direct form for every proof (CAPGPU_QUOT_FOLD=0).
+__device__ __forceinline__ bool fe_nonzero(const fe& a) {
+  uint32_t o = 0;
+#pragma unroll
+  for (int k = 0; k < 8; k++) o |= a.v[k];
+  return o != 0;
+}
+template <bool FOLD>
 __global__ __launch_bounds__(kThreads) void k_quotient(const fe* __restrict__ pkc, const fe* const* __restrict__ pkc_of,
                                                        const fe* __restrict__ cos, const fe* __restrict__ xs,
                                                        const fe* __restrict__ inv_nx1,
                                                        const Chal* __restrict__ chal, QuotConst qc, size_t m,
-                                                       fe* __restrict__ t_out) {
+                                                       uint32_t only_unfoldable, fe* __restrict__ t_out) {
   using F = Fr29;
   // grid (proofs, tiles): the proofs of one tile run together, so the 18 shared selector / sigma tiles are read from
   // HBM once per tile and served from L2 to the other proofs of the batch
   size_t i = (size_t)blockIdx.y * blockDim.x + threadIdx.x;
   if (i >= m) return;
   const uint32_t p = blockIdx.x;
+  if (FOLD ? !fe_nonzero(chal[p].beta_inv) : (only_unfoldable && fe_nonzero(chal[p].beta_inv))) return;
   if (pkc_of) pkc = pkc_of[p];
   const uint32_t mm = (uint32_t)(m / 3);                                  // block length M (uniform: scalar unit)
   const uint32_t blk = (i >= mm ? 1u : 0u) + (i >= 2 * (size_t)mm ? 1u : 0u);  // which of the three cosets
@@ -322,15 +350,43 @@ __global__ __launch_bounds__(kThreads) void k_quotient(const fe* __restrict__ pk
   fl gate2 = acc.reduce();
   // gate + q_c: three values < 2p each, limbs < 2^31 after the lazy adds
   fl total = F::normalize(F::add(F::add(gate, gate2), sel(11)));
-  // permutation part
-  const fl beta = F::load(chal[p].beta), gamma = F::load(chal[p].gamma);
+  // permutation part:  alpha (z prod_j (w_j + gamma + beta k_j x) - z_omega prod_j (w_j + gamma + beta sigma_j)).
+  // With u_j = (w_j + gamma) / beta every factor is beta (u_j + k_j x) resp. beta (u_j + sigma_j): five products by
+  // 1 / beta take the place of the ten by beta (beta x, four k_j (beta x), five beta sigma_j), k_j x comes from the key's
+  // table (columns 18 .. 21; k_0 = 1: x itself), and the five betas leave with alpha: alpha beta^5 (a' - b').  The same
+  // field element as the direct form (the else branch: k_quotient<false>).
+  const fl gamma = F::load(chal[p].gamma);
   const fl zx = F::load(c[5 * m + i]);
-  {
+  // index a M + k (ntt.hpp): x * omega_n = x * omega_M^2 is two steps further inside the same block of M = m / 3
+  const uint32_t k1 = (uint32_t)i - blk * mm;
+  const size_t inext = (size_t)blk * mm + ((k1 + 2) & (mm - 1));
+  if constexpr (FOLD) {
+    const fl beta_inv = F::load(chal[p].beta_inv);
+    // w_j (a stored value: normalized, < 2^256) + gamma (canonical) is a lazy sum of two - limbs < 2^30, what a product
+    // takes as it is; u_j is a product (normalized, < 1.2p), and u_j + k_j x (canonical) resp. u_j + sigma_j (stored,
+    // < 2^256) again a lazy sum of two that feeds one product: no carry is propagated anywhere in this block
+    fl a = zx, b = F::load(c[5 * m + inext]);
+    fl u = F::mul(F::add(w0, gamma), beta_inv);
+    a = F::mul(a, F::add(u, F::load(xs[i])));  // the point itself (internal form): s_a * omega_M^k at index a * M + k
+    b = F::mul(b, F::add(u, sel(NS + 0)));
+    u = F::mul(F::add(w1, gamma), beta_inv);
+    a = F::mul(a, F::add(u, sel(NS + NW + 0)));
+    b = F::mul(b, F::add(u, sel(NS + 1)));
+    u = F::mul(F::add(w2, gamma), beta_inv);
+    a = F::mul(a, F::add(u, sel(NS + NW + 1)));
+    b = F::mul(b, F::add(u, sel(NS + 2)));
+    u = F::mul(F::add(w3, gamma), beta_inv);
+    a = F::mul(a, F::add(u, sel(NS + NW + 2)));
+    b = F::mul(b, F::add(u, sel(NS + 3)));
+    u = F::mul(F::add(w4, gamma), beta_inv);
+    a = F::mul(a, F::add(u, sel(NS + NW + 3)));
+    b = F::mul(b, F::add(u, sel(NS + 4)));
+    // a, b: products (normalized, < 1.2p), as in the direct form
+    total = F::normalize(F::add(total, F::mul(F::load(chal[p].alpha_beta5), F::sub(a, b))));
+  } else {
+    const fl beta = F::load(chal[p].beta);
     fl x = F::load(xs[i]);  // the point itself (internal form): s_a * omega_M^k at index a * M + k
     fl bx = F::mul(beta, x);
-    // index a M + k (ntt.hpp): x * omega_n = x * omega_M^2 is two steps further inside the same block of M = m / 3
-    const uint32_t k1 = (uint32_t)i - blk * mm;
-    const size_t inext = (size_t)blk * mm + ((k1 + 2) & (mm - 1));
     fl a = zx, b = F::load(c[5 * m + inext]);
     fl wg = F::add(w0, gamma);
     a = F::mul(a, F::normalize(F::add(wg, bx)));

@@ -198,7 +198,7 @@ BatchWs carve(void* base, const ProvingKey& K, uint32_t P, size_t num_inputs, bo
   w.inv_total = c.take<fe>(P);
   w.zpoly = c.take<fe>((size_t)P * ps);
   w.coset = c.take<fe>((size_t)P * 6 * m);
-  w.pkc = K.recompute ? c.take<fe>((size_t)18 * m) : nullptr;
+  w.pkc = K.recompute ? c.take<fe>((size_t)kPkcCols * m) : nullptr;
   w.t = c.take<fe>((size_t)P * m);
   w.pows = c.take<fe>((size_t)P * 4 * ps);
   w.pw = c.take<fe>((size_t)P * 4 * 24);
@@ -232,6 +232,22 @@ BatchWs carve(void* base, const ProvingKey& K, uint32_t P, size_t num_inputs, bo
 // the 18 fixed polynomials -> coset evaluations on the 6n quotient domain
 int compute_pk_coset(hipStream_t s, const ProvingKey& K, fe* dst) {
   return run_ntt3_fwd(s, K.log_m, dst, 18, NttIo{K.coef, K.ps, 0, K.n, 1, K.m, 0, 1});
+}
+// columns 18 .. 21 of the same table: k_j x_i, j = 1 .. 4 (k_quotient's folded permutation terms)
+int compute_pk_kx(hipStream_t s, const ProvingKey& K, fe* dst) {
+  const Ntt3Domain* dq = nullptr;
+  if (int rc = get_domain3(K.log_m, &dq)) return rc;
+  launch("k_kx_columns", k_kx_columns, dim3(cdiv(K.m, kThreads)), dim3(kThreads), 0, s, dst + (size_t)18 * K.m,
+         (const fe*)dq->xs29, K.qc29, K.m);
+  return CAPGPU_OK;
+}
+// CAPGPU_QUOT_FOLD (read per call): 1, the default - k_quotient's permutation terms with beta folded out; 0 - the direct
+// form for every proof (A/B in one build); 2 - folded, with every proof's 1 / beta zeroed first: all of them take the route
+// of a proof with beta = 0 (the folded launch leaves them out, the direct launch behind it takes them) - for tests.
+int quotient_fold() {
+  const char* e = getenv("CAPGPU_QUOT_FOLD");
+  const int v = e ? atoi(e) : 1;
+  return v >= 0 && v <= 2 ? v : 1;
 }
 
 // Round 1's wire commitments: from the wire polynomials' coefficients (jf-plonk's way: KZG10::commit under
@@ -486,7 +502,8 @@ int make_plan(Context& c, const ProvingKey& K, uint32_t P, int form, bool host, 
   const bool own = !c.prof.on && c.stream == c.own_stream;
   pl.overlap = pl.chunks == 1 && P <= r1_overlap_max() && (sizing || (own && !comm_shard_prover())) &&
                (pl.s2 = side_stream(c)) != nullptr;
-  pl.graphs = P <= graph_max_batch() && pl.chunks == 1 && own && comm_shard_slot() < 0;
+  // (a captured segment keeps the launches it was captured with: only the default form of k_quotient is captured)
+  pl.graphs = P <= graph_max_batch() && pl.chunks == 1 && own && comm_shard_slot() < 0 && quotient_fold() == 1;
   *out = pl;
   return CAPGPU_OK;
 }
@@ -575,6 +592,7 @@ struct ProveRun {
   // - two host round trips where one is needed, seven times per proof.
   g1_jac* hj = nullptr;         // [5 P] commitments of a round
   fe* h_tot = nullptr;          // [P] grand-product totals out, their inverses back
+  bool beta_zero_possible = true;  // some proof's beta may be 0 (r3_body); the host transcript knows better
   fe* h_evals = nullptr;        // [10 P]
   uint32_t* h_flags = nullptr;  // [P]
   uint8_t* h_proofs = nullptr;  // [P] device transcript: the proofs in ABI layout, then the degree flags
@@ -970,10 +988,22 @@ struct ProveRun {
       // reference schedule: the 18 selector / sigma polynomials are re-transformed for every proof
       for (uint32_t p = 0; p < P; p++)
         if ((r = compute_pk_coset(s, K, w.pkc))) return r;
+      if ((r = compute_pk_kx(s, K, w.pkc))) return r;
       pkc = w.pkc;
     }
-    launch("k_quotient", k_quotient, dim3(P, cdiv(m, kThreads)), dim3(kThreads), 0, s, pkc, pkc_of,
-           (const fe*)w.coset, (const fe*)dom_q->xs29, (const fe*)K.inv_nx1, (const Chal*)w.chal29, K.qc29, m, w.t);
+    const int fold = quotient_fold();
+    if (fold == 2)
+      CAP_HIP(hipMemset2DAsync(&w.chal29[0].beta_inv, sizeof(Chal), 0, sizeof(fe), P, s));
+    if (fold)
+      launch("k_quotient", k_quotient<true>, dim3(P, cdiv(m, kThreads)), dim3(kThreads), 0, s, pkc, pkc_of,
+             (const fe*)w.coset, (const fe*)dom_q->xs29, (const fe*)K.inv_nx1, (const Chal*)w.chal29, K.qc29, m, 1u, w.t);
+    // the direct form: for every proof (fold = 0), or behind the folded launch for the proofs it left out - beta = 0.
+    // The host transcript knows whether there is one; the device transcript does not, and its launch is P x m / 256
+    // workgroups that load one word and leave.
+    if (!fold || fold == 2 || beta_zero_possible)
+      launch("k_quotient_direct", k_quotient<false>, dim3(P, cdiv(m, kThreads)), dim3(kThreads), 0, s,
+             pkc, pkc_of, (const fe*)w.coset, (const fe*)dom_q->xs29, (const fe*)K.inv_nx1, (const Chal*)w.chal29, K.qc29, m,
+             fold ? 1u : 0u, w.t);
     // k_quotient leaves the public-input term out; it arrives here as coefficients (pi_fold), before the degree check
     if ((r = run_ntt3_inv(s, K.log_m, w.t, P, w.pi))) return r;
     {
@@ -1155,7 +1185,12 @@ struct ProveRun {
       chal[p].gamma = get_challenge(tr[p]);
       chal[p].alpha = Fr::zero();
       chal[p].alpha2 = Fr::zero();
+      chal[p].beta_inv = Fr::is_zero(chal[p].beta) ? Fr::zero() : Fr::inv(chal[p].beta);  // beta is public
+      chal[p].alpha_beta5 = Fr::zero();
     });
+    // (a segment replayed as a graph keeps the launches of its capture: there the direct launch always follows)
+    beta_zero_possible = pl.graphs;
+    for (uint32_t p = 0; p < P; p++) beta_zero_possible = beta_zero_possible || Fr::is_zero(chal[p].beta);
     CAP_HIP(hipMemcpyAsync(w.chal, chal.data(), sizeof(Chal) * P, hipMemcpyHostToDevice, s));
 
     if ((rc = seg(2, [&]() -> int { return r2_body(); }))) return rc;
@@ -1196,6 +1231,8 @@ struct ProveRun {
       affine_to_words(ha[p], proofs[p].prod_perm_poly_comm);
       chal[p].alpha = get_challenge(tr[p]);
       chal[p].alpha2 = Fr::sqr(chal[p].alpha);
+      const fe b2 = Fr::sqr(chal[p].beta);
+      chal[p].alpha_beta5 = Fr::mul(chal[p].alpha, Fr::mul(Fr::sqr(b2), chal[p].beta));
     });
     CAP_HIP(hipMemcpyAsync(w.chal, chal.data(), sizeof(Chal) * P, hipMemcpyHostToDevice, s));
     std::vector<Chal> chal29(P);
@@ -1205,6 +1242,8 @@ struct ProveRun {
       chal29[p].gamma = conv(chal[p].gamma);
       chal29[p].alpha = conv(chal[p].alpha);
       chal29[p].alpha2 = conv(chal[p].alpha2);
+      chal29[p].beta_inv = conv(chal[p].beta_inv);
+      chal29[p].alpha_beta5 = conv(chal[p].alpha_beta5);
     });
     CAP_HIP(hipMemcpyAsync(w.chal29, chal29.data(), sizeof(Chal) * P, hipMemcpyHostToDevice, s));
 

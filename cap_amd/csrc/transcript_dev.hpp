@@ -460,10 +460,15 @@ __global__ __launch_bounds__(64) void k_tr_comms(TrBufs t, const g1_jac* __restr
       chal[p].gamma = gamma;
       chal[p].alpha = Fr::zero();
       chal[p].alpha2 = Fr::zero();
+      const fe beta_inv = fr_inv_public(beta);  // beta is public; inv(0) = 0: k_quotient then takes the direct form
+      chal[p].beta_inv = beta_inv;
+      chal[p].alpha_beta5 = Fr::zero();
       chal29[p].beta = to_internal(beta);
       chal29[p].gamma = to_internal(gamma);
       chal29[p].alpha = Fr::zero();
       chal29[p].alpha2 = Fr::zero();
+      chal29[p].beta_inv = to_internal(beta_inv);
+      chal29[p].alpha_beta5 = Fr::zero();
     }
   } else if (ROUND == 2) {
     const fe alpha = draw(t, p, lapp, tabs);
@@ -473,6 +478,10 @@ __global__ __launch_bounds__(64) void k_tr_comms(TrBufs t, const g1_jac* __restr
       chal[p].alpha2 = a2;
       chal29[p].alpha = to_internal(alpha);
       chal29[p].alpha2 = to_internal(a2);
+      const fe beta = chal[p].beta, b2 = Fr::sqr(beta);
+      const fe ab5 = Fr::mul(alpha, Fr::mul(Fr::sqr(b2), beta));
+      chal[p].alpha_beta5 = ab5;
+      chal29[p].alpha_beta5 = to_internal(ab5);
     }
   } else {
     const fe zeta = draw(t, p, lapp, tabs);
