@@ -89,6 +89,16 @@ pub struct capgpu_witness_fault {
     pub copies_failed: u64,
 }
 
+/// `capgpu_prove_outcome`: the verdict of one proof of a `capgpu_plonk_prove_each*` call (56 bytes).  `status` is
+/// `CAPGPU_ERR_PROOF` exactly when `degree_flags != 0 || fault.kind != 0`; the record of such a proof is all-ones words.
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct capgpu_prove_outcome {
+    pub status: i32,
+    pub degree_flags: u32,
+    pub fault: capgpu_witness_fault,
+}
+
 #[link(name = "capgpu")]
 extern "C" {
     // ---- lifecycle, devices
@@ -265,6 +275,21 @@ extern "C" {
                                           ext_msg_lens: *const usize, blinders: *const u64, input_form: c_int,
                                           proofs_out: *mut capgpu_proof, ticket_out: *mut u64) -> c_int;
     pub fn capgpu_wait(ticket: u64, timeout_ms: u32, done_out: *mut c_int) -> c_int;
+    // ---- per-proof outcomes: a batch is proved past its unsatisfied witnesses
+    pub fn capgpu_plonk_prove_each(pk_handles: *const u64, count: c_int, wires: *const u64, pub_inputs: *const u64,
+                                   num_inputs: usize, ext_msgs: *const *const u8, ext_msg_lens: *const usize,
+                                   blinders: *const u64, input_form: c_int, proofs_out: *mut capgpu_proof,
+                                   outcomes_out: *mut capgpu_prove_outcome) -> c_int;
+    pub fn capgpu_plonk_prove_each_dev(pk_handles: *const u64, count: c_int, d_wires: *const c_void,
+                                       pub_inputs: *const u64, num_inputs: usize, ext_msgs: *const *const u8,
+                                       ext_msg_lens: *const usize, blinders: *const u64, input_form: c_int,
+                                       proofs_out: *mut capgpu_proof, outcomes_out: *mut capgpu_prove_outcome) -> c_int;
+    pub fn capgpu_plonk_prove_each_async(pk_handles: *const u64, count: c_int, wires: *const u64,
+                                         pub_inputs: *const u64, num_inputs: usize, ext_msgs: *const *const u8,
+                                         ext_msg_lens: *const usize, blinders: *const u64, input_form: c_int,
+                                         proofs_out: *mut capgpu_proof, outcomes_out: *mut capgpu_prove_outcome,
+                                         ticket_out: *mut u64) -> c_int;
+    pub fn capgpu_prove_outcome_text(outcome: *const capgpu_prove_outcome, buf: *mut c_char, cap: usize) -> c_int;
     pub fn capgpu_async_stats(submitted_out: *mut u64, completed_out: *mut u64, max_running_out: *mut u32) -> c_int;
     pub fn capgpu_plonk_reserve(pk_handle: u64, count: c_int, input_form: c_int, slot: c_int) -> c_int;
     // ---- verification (host only)
@@ -648,6 +673,32 @@ impl ProvingKey {
         })?;
         Ok(ProveTicket { ticket, done: false, _borrow: std::marker::PhantomData })
     }
+    /// One `prove()` per note with a `Result` of its own - the reference's rayon map over a `Vec` of notes
+    /// (src/utils/params_builder.rs:194-226) - as ONE device batch under this key (`capgpu_plonk_prove_each`): a note
+    /// whose witness does not satisfy the circuit gets `Err(ProveError)` with the message its own `prove` would give and
+    /// costs the others nothing; an `Ok` proof is bit for bit `prove_form`'s.  The outer `Err`: the batch could not run.
+    /// `wires`, `pub_inputs`, `blinders`: per proof, consecutive (as `prove_batch_async`); `ext_msgs`: one per proof.
+    pub fn prove_each(&self, wires: &[[u64; 4]], pub_inputs: &[[u64; 4]], ext_msgs: &[&[u8]], blinders: &[[u64; 4]],
+                      input_form: c_int) -> Result<Vec<std::result::Result<capgpu_proof, ProveError>>> {
+        let count = ext_msgs.len();
+        let per = if input_form == CAPGPU_INPUT_VARS { self.num_vars()? } else { NUM_WIRE_TYPES * self.domain_size };
+        assert_eq!(wires.len(), count * per);
+        assert_eq!(pub_inputs.len(), count * self.num_inputs);
+        assert_eq!(blinders.len(), count * 13);
+        let handles = vec![self.handle; count];
+        let msgs: Vec<*const u8> = ext_msgs.iter().map(|m| if m.is_empty() { std::ptr::null() } else { m.as_ptr() }).collect();
+        let lens: Vec<usize> = ext_msgs.iter().map(|m| m.len()).collect();
+        let mut proofs: Vec<capgpu_proof> = (0..count).map(|_| unsafe { std::mem::zeroed() }).collect();
+        let mut outcomes = vec![capgpu_prove_outcome::default(); count];
+        check(unsafe {
+            capgpu_plonk_prove_each(handles.as_ptr(), count as c_int, wires.as_ptr() as *const u64,
+                                    pub_inputs.as_ptr() as *const u64, self.num_inputs, msgs.as_ptr(), lens.as_ptr(),
+                                    blinders.as_ptr() as *const u64, input_form, proofs.as_mut_ptr(),
+                                    outcomes.as_mut_ptr())
+        })?;
+        Ok(proofs.into_iter().zip(outcomes).map(|(p, o)| if o.status == CAPGPU_OK { Ok(p) } else { Err(ProveError::from(o)) })
+            .collect())
+    }
     /// Sizes context `slot` (-1: every context) ahead for batches of `count` host-resident proofs under this key, so that
     /// no allocation lands inside a steady-state call (`scratch_stats` then stays put).
     pub fn reserve(&self, count: usize, input_form: c_int, slot: i32) -> Result<()> {
@@ -655,6 +706,25 @@ impl ProvingKey {
     }
     pub fn handle(&self) -> u64 {
         self.handle
+    }
+}
+/// Why one note of `ProvingKey::prove_each` has no proof: the outcome record and `capgpu_prove_outcome_text` of it.
+#[derive(Clone)]
+pub struct ProveError {
+    pub outcome: capgpu_prove_outcome,
+    pub message: String,
+}
+impl From<capgpu_prove_outcome> for ProveError {
+    fn from(outcome: capgpu_prove_outcome) -> Self {
+        let mut buf = [0 as c_char; 512];
+        unsafe { capgpu_prove_outcome_text(&outcome, buf.as_mut_ptr(), buf.len()) };
+        let message = unsafe { std::ffi::CStr::from_ptr(buf.as_ptr()) }.to_string_lossy().into_owned();
+        ProveError { outcome, message }
+    }
+}
+impl std::fmt::Display for ProveError {
+    fn fmt(&self, f: &mut std::fmt::Formatter<'_>) -> std::fmt::Result {
+        write!(f, "{}", self.message)
     }
 }
 impl Drop for ProvingKey {

@@ -119,11 +119,14 @@ struct ProveGraphSig {
   // modes cut the schedule differently (eight segments / one), and the stride is baked into the captured launches
   int transcript = 0;
   uint32_t tr_stride = 0;
+  // capgpu_plonk_prove_each*: 0 a plain call, 1 an outcome call, 2 one whose witnesses were checked first - the device
+  // transcript's segment of an outcome call ends in k_prove_outcomes, which reads the check's verdicts or does not
+  int outcomes = 0;
   bool operator==(const ProveGraphSig& o) const {
     return key_uid == o.key_uid && srs == o.srs && P == o.P && num_inputs == o.num_inputs && form == o.form &&
            multi == o.multi && d_wires == o.d_wires && ws == o.ws && msm_ws == o.msm_ws && ntt_scratch == o.ntt_scratch &&
            bases == o.bases && lagrange == o.lagrange && stream == o.stream && overlap == o.overlap && transcript == o.transcript &&
-           tr_stride == o.tr_stride;
+           tr_stride == o.tr_stride && outcomes == o.outcomes;
   }
 };
 struct ProveGraphSet {
@@ -205,7 +208,7 @@ ProveGraphSet* graph_set_for(Context& c, const ProveGraphSig& sig) {
   ProveGraphSet* slot = nullptr;
   for (auto& sp : gc.sets)
     if (sp->sig.key_uid == sig.key_uid && sp->sig.P == sig.P && sp->sig.form == sig.form && sp->sig.multi == sig.multi &&
-        sp->sig.d_wires == sig.d_wires && sp->sig.transcript == sig.transcript)
+        sp->sig.d_wires == sig.d_wires && sp->sig.transcript == sig.transcript && sp->sig.outcomes == sig.outcomes)
       slot = sp.get();
   if (!slot && gc.sets.size() >= 8) {
     slot = gc.sets[0].get();
@@ -355,6 +358,11 @@ int key_check_tables(const ProvingKey& K) {
   return CAPGPU_OK;
 }
 
+// check_batch's verdicts inside its d_small (the head of check_resident's Context::stage_a): they stay there until the
+// next check, and an outcome call's k_prove_outcomes takes its copy of CheckOut::first from them (prove_batch)
+CheckOut* check_out_at(void* d_small, uint32_t P) {
+  return (CheckOut*)((char*)d_small + (sizeof(CheckKey) * P + 255) / 256 * 256);
+}
 size_t check_small_bytes(uint32_t P) {
   return (sizeof(CheckKey) + sizeof(CheckOut) + sizeof(uint32_t)) * (size_t)P + 768;
 }
@@ -379,7 +387,7 @@ int check_batch(const ProvingKey& K, const std::vector<const ProvingKey*>* keys,
     hk[p] = CheckKey{Kp.chk_sel, Kp.chk_perm, (uint32_t)Kp.num_inputs, 0};
   }
   CheckKey* dk = (CheckKey*)d_small;
-  CheckOut* dout = (CheckOut*)((char*)d_small + (sizeof(CheckKey) * P + 255) / 256 * 256);
+  CheckOut* dout = check_out_at(d_small, P);
   uint32_t* dto = (uint32_t*)((char*)dout + (sizeof(CheckOut) * P + 255) / 256 * 256);
   std::vector<CheckOut> ho(P, CheckOut{kNoFault, 0, 0});
   std::vector<uint32_t> hto(P);
@@ -454,11 +462,7 @@ int check_resident(const ProvingKey& K, const std::vector<const ProvingKey*>* ke
 
 std::string fault_text(uint32_t p, const capgpu_witness_fault& f) {
   char b[160];
-  if (f.kind == 1)
-    snprintf(b, sizeof b, "proof %u: gate %llu not satisfied", p, (unsigned long long)f.row);
-  else
-    snprintf(b, sizeof b, "proof %u: copy constraint (%u,%llu) -> (%u,%llu) violated", p, f.wire,
-             (unsigned long long)f.row, f.wire2, (unsigned long long)f.row2);
+  oc::fault_text(p, f, b, sizeof b);
   return b;
 }
 // CAPGPU_OK when every witness holds; else CAPGPU_ERR_PROOF with the number of bad proofs, the first one and its fault
@@ -470,8 +474,9 @@ int precheck_verdict(const capgpu_witness_fault* faults, uint32_t P) {
       bad++;
     }
   if (!bad) return CAPGPU_OK;
-  set_error("capgpu_plonk_prove: %u of %u witnesses do not satisfy their circuit; first: %s", bad, P,
-            fault_text(first, faults[first]).c_str());
+  char b[320];
+  oc::precheck_text(bad, P, first, faults[first], b, sizeof b);
+  set_error("%s", b);
   return CAPGPU_ERR_PROOF;
 }
 
@@ -564,19 +569,36 @@ int prove_batch(const ProvingKey& K, uint32_t P, const ProveRequest& rq) {
   if (pl.precheck && rq.h_wires && (rc = run.copy_input(0, P, c.stream))) return rc;
   // variable form with the values resident (a caller's device buffer, or copied a moment ago): all columns at once
   if (pl.vars && !pl.r1_copies) run.gather_vars(0, P);
+  std::vector<capgpu_witness_fault> faults;
   if (pl.precheck) {
     // Ahead of everything the proof itself needs - the workspace, every MSM and NTT: a refused batch has cost the
     // check's launches.  (Coefficient-form input is first transformed to values, in scratch of the check's own.)
-    std::vector<capgpu_witness_fault> faults(P);
+    faults.resize(P);
     // (gathered columns satisfy every copy constraint by construction: the gate pass only)
     if ((rc = check_resident(K, keys, P, rq.d_wires, rq.pub_inputs, num_inputs, pl.vars ? CAPGPU_INPUT_EVALS : rq.form,
                              faults.data(), pl.vars)))
       return rc;
-    if ((rc = precheck_verdict(faults.data(), P))) return rc;
+    if (!rq.outcomes) {
+      if ((rc = precheck_verdict(faults.data(), P))) return rc;
+    } else {
+      // an outcome call keeps the verdicts and goes on - unless EVERY witness was refused: then nothing is left to prove
+      run.faults = faults.data();
+      uint32_t bad = 0;
+      for (uint32_t p = 0; p < P; p++) bad += faults[p].kind != 0;
+      if (bad == P) {
+        for (uint32_t p = 0; p < P; p++) oc::finish_outcome(0, &faults[p], &rq.outcomes[p], &rq.proofs[p]);
+        return CAPGPU_OK;
+      }
+    }
   }
   // workspace
   if ((rc = scratch_reserve(c.prove_ws, carve(nullptr, K, P, num_inputs, pl.coeffs, pl.tr_stride).total))) return rc;
   run.w = carve(c.prove_ws.p, K, P, num_inputs, pl.coeffs, pl.tr_stride);
+  // the check's device-side verdicts, for k_prove_outcomes: out of the check's scratch into the workspace (outside the
+  // segments, like every per-call value; nothing has touched stage_a since the check)
+  if (run.faults && pl.dev_tr)
+    CAP_HIP(hipMemcpy2DAsync(run.w.chk_first, sizeof(unsigned long long), &check_out_at(c.stage_a.p, P)->first,
+                             sizeof(CheckOut), sizeof(unsigned long long), P, hipMemcpyDeviceToDevice, c.stream));
   if (pl.graphs) {
     ProveGraphSig sig;
     sig.key_uid = K.uid;
@@ -595,6 +617,7 @@ int prove_batch(const ProvingKey& K, uint32_t P, const ProveRequest& rq) {
     sig.overlap = pl.overlap;
     sig.transcript = pl.dev_tr ? CAPGPU_TRANSCRIPT_DEVICE : CAPGPU_TRANSCRIPT_HOST;
     sig.tr_stride = pl.tr_stride;
+    sig.outcomes = rq.outcomes ? (run.faults ? 2 : 1) : 0;
     run.gs = graph_set_for(c, sig);
   }
   return pl.dev_tr ? run.run_device_transcript() : run.run_host_transcript();
@@ -1595,6 +1618,10 @@ struct HostBatch {
   size_t n;
   const std::shared_ptr<ProvingKey>* home;  // tickets: see part_key
   size_t stride;  // elements per proof of `wires`: 5 n, or the key's num_vars (input_stride)
+  // capgpu_plonk_prove_each* of one key: a message per proof in place of ext_msg, and the outcome records
+  const uint8_t* const* msgs = nullptr;
+  const size_t* msg_lens = nullptr;
+  capgpu_prove_outcome* outcomes = nullptr;
 };
 static int host_batch_part(const HostBatch& b, int first, int cnt) {
   Context& c = ctx();
@@ -1619,6 +1646,9 @@ static int host_batch_part(const HostBatch& b, int first, int cnt) {
   rq.proofs = b.proofs_out + first;
   rq.ext_msg = b.ext_msg;
   rq.ext_len = b.ext_msg_len;
+  rq.msgs = b.msgs ? b.msgs + first : nullptr;
+  rq.msg_lens = b.msgs ? b.msg_lens + first : nullptr;
+  rq.outcomes = b.outcomes ? b.outcomes + first : nullptr;
   rq.h_wires = rows.data();
   rq.form = b.input_form;
   rq.vin = vars ? &vin : nullptr;
@@ -1719,6 +1749,7 @@ struct HostMulti {
   size_t n;
   const std::shared_ptr<ProvingKey>* homes;  // tickets: [count], see part_key
   size_t stride;  // elements per proof of `wires`: 5 n, or the largest num_vars among the keys of the WHOLE call
+  capgpu_prove_outcome* outcomes = nullptr;  // capgpu_plonk_prove_each*
 };
 static int host_multi_part(const HostMulti& b, int first, int cnt) {
   Context& c = ctx();
@@ -1763,6 +1794,7 @@ static int host_multi_part(const HostMulti& b, int first, int cnt) {
   rq.msgs = b.ext_msgs ? b.ext_msgs + first : nullptr;
   rq.msg_lens = b.ext_msg_lens ? b.ext_msg_lens + first : nullptr;
   rq.keys = &keys;
+  rq.outcomes = b.outcomes ? b.outcomes + first : nullptr;
   rq.h_wires = rows.data();
   rq.form = b.input_form;
   rq.vin = vars ? &vin : nullptr;
@@ -1800,6 +1832,116 @@ int capgpu_plonk_prove_multi(const uint64_t* pk_handles, int count, const uint64
                                      CAPGPU_INPUT_EVALS, proofs_out);
 }
 
+// ---- per-proof outcomes (capgpu_plonk_prove_each*) ---------------------------------------------------------------------
+// The arguments of capgpu_plonk_prove_multi_ex plus one outcome record per proof; the pointer checks come before the
+// device is looked for.  A call whose handles all name one key takes the single-key path (ProveRequest::keys == nullptr:
+// the launches of capgpu_plonk_prove_batch_ex) with its messages per proof.
+static int each_bad_args(const uint64_t* pk_handles, int count, const void* wires, const uint64_t* pub_inputs,
+                         size_t num_inputs, const uint8_t* const* ext_msgs, const size_t* ext_msg_lens,
+                         const uint64_t* blinders, int input_form, const capgpu_proof* proofs_out,
+                         const capgpu_prove_outcome* outcomes_out) {
+  if (bad_form(input_form)) return CAPGPU_ERR_INVALID_ARG;
+  if (count < 0 || (count && (!pk_handles || !wires || !blinders || !proofs_out || !outcomes_out ||
+                              (num_inputs && !pub_inputs) || (ext_msgs && !ext_msg_lens)))) {
+    set_error("capgpu_plonk_prove_multi: bad argument");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  return CAPGPU_OK;
+}
+static bool each_one_key(const uint64_t* pk_handles, int count) {
+  for (int i = 1; i < count; i++)
+    if (pk_handles[i] != pk_handles[0]) return false;
+  return true;
+}
+// the ranks of a communicator prove in lock step (capgpu_plonk_shard_msm): there is no per-proof exit
+static bool each_refused_by_sharding() {
+  if (comm_shard_slot() < 0 && !comm_shard_prover()) return false;
+  set_error("capgpu_plonk_prove_each: not available while capgpu_plonk_shard_msm is on (the ranks prove in lock step)");
+  return true;
+}
+
+int capgpu_plonk_prove_each(const uint64_t* pk_handles, int count, const uint64_t* wires, const uint64_t* pub_inputs,
+                            size_t num_inputs, const uint8_t* const* ext_msgs, const size_t* ext_msg_lens,
+                            const uint64_t* blinders, int input_form, capgpu_proof* proofs_out,
+                            capgpu_prove_outcome* outcomes_out) {
+  if (int rc = each_bad_args(pk_handles, count, wires, pub_inputs, num_inputs, ext_msgs, ext_msg_lens, blinders, input_form,
+                             proofs_out, outcomes_out))
+    return rc;
+  CAP_CHECK_INIT();
+  if (count == 0) return CAPGPU_OK;
+  if (each_refused_by_sharding()) return CAPGPU_ERR_INVALID_ARG;
+  std::shared_ptr<ProvingKey> K0;
+  int rc0 = home_key(pk_handles[0], &K0);
+  if (rc0) return rc0;
+  size_t stride = 0;
+  if ((rc0 = input_stride(pk_handles, count, input_form, K0->n, &stride))) return rc0;
+  if (each_one_key(pk_handles, count)) {
+    HostBatch b{pk_handles[0], wires, pub_inputs, num_inputs, nullptr, 0, blinders, input_form, proofs_out, K0->n, nullptr,
+                stride};
+    b.msgs = ext_msgs;
+    b.msg_lens = ext_msg_lens;
+    b.outcomes = outcomes_out;
+    return deal(count, [&](int first, int cnt) -> int { return host_batch_part(b, first, cnt); });
+  }
+  HostMulti b{pk_handles, wires, pub_inputs, num_inputs, ext_msgs, ext_msg_lens, blinders, input_form, proofs_out, K0->n,
+              nullptr, stride};
+  b.outcomes = outcomes_out;
+  return deal(count, [&](int first, int cnt) -> int { return host_multi_part(b, first, cnt); });
+}
+
+int capgpu_plonk_prove_each_dev(const uint64_t* pk_handles, int count, const void* d_wires, const uint64_t* pub_inputs,
+                                size_t num_inputs, const uint8_t* const* ext_msgs, const size_t* ext_msg_lens,
+                                const uint64_t* blinders, int input_form, capgpu_proof* proofs_out,
+                                capgpu_prove_outcome* outcomes_out) {
+  if (int rc = each_bad_args(pk_handles, count, d_wires, pub_inputs, num_inputs, ext_msgs, ext_msg_lens, blinders,
+                             input_form, proofs_out, outcomes_out))
+    return rc;
+  CAP_CHECK_INIT();
+  Context& c = ctx();
+  Entry lk(c);
+  if (count == 0) return CAPGPU_OK;
+  if (each_refused_by_sharding()) return CAPGPU_ERR_INVALID_ARG;
+  const bool one_key = each_one_key(pk_handles, count);
+  std::vector<std::shared_ptr<ProvingKey>> hold(one_key ? 1 : count);
+  std::vector<const ProvingKey*> keys(hold.size());
+  for (size_t i = 0; i < hold.size(); i++) {
+    int rc = lookup_key(pk_handles[i], &hold[i]);
+    if (rc) return rc;
+    keys[i] = hold[i].get();
+  }
+  ProveRequest rq;
+  rq.d_wires = (const fe*)d_wires;
+  rq.pub_inputs = pub_inputs;
+  rq.num_inputs = num_inputs;
+  rq.blinders = blinders;
+  rq.proofs = proofs_out;
+  rq.msgs = ext_msgs;
+  rq.msg_lens = ext_msg_lens;
+  rq.keys = one_key ? nullptr : &keys;
+  rq.form = input_form;
+  rq.outcomes = outcomes_out;
+  VarsIn vin{};
+  if (input_form == CAPGPU_INPUT_VARS) {
+    size_t stride = 0;
+    int rc = input_stride(pk_handles, count, input_form, 0, &stride);
+    if (rc) return rc;
+    if ((rc = scratch_reserve(c.stage_b, vars_stage_bytes((size_t)count, keys[0]->n, 0, false)))) return rc;
+    vin = VarsIn{(const fe*)d_wires, stride};
+    rq.d_wires = (const fe*)c.stage_b.p;
+    rq.vin = &vin;
+  }
+  return prove_batch(*keys[0], (uint32_t)count, rq);
+}
+
+int capgpu_prove_outcome_text(const capgpu_prove_outcome* outcome, char* buf, size_t cap) {
+  if (!outcome || (cap && !buf)) {
+    set_error("capgpu_prove_outcome_text: bad argument");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  (void)oc::outcome_text(*outcome, buf, cap);
+  return CAPGPU_OK;
+}
+
 }  // extern "C"
 
 // ---- asynchronous prove tickets ------------------------------------------------------------------------------------------
@@ -1822,6 +1964,7 @@ struct AsyncJob {
   bool has_msgs = false;                            // _multi with ext_msgs != NULL
   std::vector<std::vector<uint8_t>> msgs;           // copies: one (batch; empty = none) or one per proof
   int bound_slot = -1;                              // the submitting thread's capgpu_set_device, -1: none
+  capgpu_prove_outcome* outcomes = nullptr;         // capgpu_plonk_prove_each_async: borrowed like proofs_out
 };
 using Tickets = TicketTable<AsyncJob>;
 
@@ -1882,17 +2025,24 @@ int run_ticket(AsyncJob& j, int lane, std::string* err) {
   int rc;
   {
     ScopedCtx sc(*c);
+    std::vector<const uint8_t*> mp(j.msgs.size());
+    std::vector<size_t> ml(j.msgs.size());
+    for (size_t i = 0; i < j.msgs.size(); i++) {
+      mp[i] = j.msgs[i].empty() ? nullptr : j.msgs[i].data();
+      ml[i] = j.msgs[i].size();
+    }
     if (j.multi) {
-      std::vector<const uint8_t*> mp(j.msgs.size());
-      std::vector<size_t> ml(j.msgs.size());
-      for (size_t i = 0; i < j.msgs.size(); i++) {
-        mp[i] = j.msgs[i].empty() ? nullptr : j.msgs[i].data();
-        ml[i] = j.msgs[i].size();
-      }
-      const HostMulti b{j.pks.data(), j.wires, j.pub_inputs, j.num_inputs, j.has_msgs ? mp.data() : nullptr,
-                        j.has_msgs ? ml.data() : nullptr, j.blinders, j.input_form, j.proofs_out, j.n, j.homes.data(),
-                        j.stride};
+      HostMulti b{j.pks.data(), j.wires, j.pub_inputs, j.num_inputs, j.has_msgs ? mp.data() : nullptr,
+                  j.has_msgs ? ml.data() : nullptr, j.blinders, j.input_form, j.proofs_out, j.n, j.homes.data(), j.stride};
+      b.outcomes = j.outcomes;
       rc = host_multi_part(b, 0, j.count);
+    } else if (j.outcomes) {  // an outcome call of one key: the single-key path with a message per proof
+      HostBatch b{j.pks[0], j.wires, j.pub_inputs, j.num_inputs, nullptr, 0, j.blinders, j.input_form, j.proofs_out, j.n,
+                  &j.homes[0], j.stride};
+      b.msgs = j.has_msgs ? mp.data() : nullptr;
+      b.msg_lens = j.has_msgs ? ml.data() : nullptr;
+      b.outcomes = j.outcomes;
+      rc = host_batch_part(b, 0, j.count);
     } else {
       const std::vector<uint8_t>& m = j.msgs[0];
       const HostBatch b{j.pks[0], j.wires, j.pub_inputs, j.num_inputs, m.empty() ? nullptr : m.data(), m.size(),
@@ -2056,6 +2206,63 @@ int capgpu_plonk_prove_multi_async(const uint64_t* pk_handles, int count, const 
   return submit_ticket(std::move(j), ticket_out);
 }
 
+int capgpu_plonk_prove_each_async(const uint64_t* pk_handles, int count, const uint64_t* wires,
+                                  const uint64_t* pub_inputs, size_t num_inputs, const uint8_t* const* ext_msgs,
+                                  const size_t* ext_msg_lens, const uint64_t* blinders, int input_form,
+                                  capgpu_proof* proofs_out, capgpu_prove_outcome* outcomes_out, uint64_t* ticket_out) {
+  if (int rc = each_bad_args(pk_handles, count, wires, pub_inputs, num_inputs, ext_msgs, ext_msg_lens, blinders, input_form,
+                             proofs_out, outcomes_out))
+    return rc;
+  if (!ticket_out) {
+    set_error("capgpu_plonk_prove_multi: bad argument");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  CAP_CHECK_INIT();
+  *ticket_out = 0;
+  if (count == 0) return CAPGPU_OK;
+  if (each_refused_by_sharding()) return CAPGPU_ERR_INVALID_ARG;
+  const bool one_key = each_one_key(pk_handles, count);
+  AsyncJob j;
+  j.homes.resize(one_key ? 1 : (size_t)count);
+  int rc;
+  // every key is known, and they share the domain size and the SRS (capgpu_plonk_prove_multi_async's checks)
+  size_t max_ni = 0;
+  for (size_t i = 0; i < j.homes.size(); i++) {
+    if ((rc = home_key(pk_handles[i], &j.homes[i]))) return rc;
+    const ProvingKey &K = *j.homes[0], &Kp = *j.homes[i];
+    if (Kp.n != K.n || Kp.srs_handle != K.srs_handle || (!one_key && (Kp.recompute || K.recompute))) {
+      set_error("capgpu_plonk_prove_multi: the keys of one batch must share the domain size and the SRS");
+      return CAPGPU_ERR_INVALID_ARG;
+    }
+    max_ni = std::max(max_ni, Kp.num_inputs);
+  }
+  if (num_inputs != max_ni) {
+    if (one_key) set_error("capgpu_plonk_prove: %zu public inputs given, key expects %zu", num_inputs, max_ni);
+    else set_error("capgpu_plonk_prove_multi: rows of %zu public inputs given, the keys need %zu", num_inputs, max_ni);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  if ((rc = input_stride(pk_handles, one_key ? 1 : count, input_form, j.homes[0]->n, &j.stride))) return rc;
+  j.multi = !one_key;
+  j.count = count;
+  j.pks.assign(pk_handles, pk_handles + (one_key ? 1 : count));
+  j.wires = wires;
+  j.pub_inputs = pub_inputs;
+  j.blinders = blinders;
+  j.proofs_out = proofs_out;
+  j.outcomes = outcomes_out;
+  j.num_inputs = num_inputs;
+  j.n = j.homes[0]->n;
+  j.input_form = input_form;
+  j.has_msgs = ext_msgs != nullptr;
+  if (ext_msgs) {
+    j.msgs.resize((size_t)count);
+    for (int i = 0; i < count; i++)
+      if (ext_msgs[i] && ext_msg_lens[i]) j.msgs[(size_t)i].assign(ext_msgs[i], ext_msgs[i] + ext_msg_lens[i]);
+  }
+  j.bound_slot = thread_bound_slot();
+  return submit_ticket(std::move(j), ticket_out);
+}
+
 int capgpu_wait(uint64_t ticket, uint32_t timeout_ms, int* done_out) {
   CAP_CHECK_INIT();
   if (!done_out) {
@@ -2133,8 +2340,9 @@ int capgpu_plonk_reserve(uint64_t pk_handle, int count, int input_form, int slot
   return CAPGPU_OK;
 }
 
-// one gathered batch: device staging of every request's wires, per-proof messages and keys; a batch that fails because
-// ONE witness does not satisfy its circuit is re-run request by request so that only its owner sees the failure.
+// one gathered batch: device staging of every request's wires, per-proof messages and keys.  Without the witness check
+// the batch is proved in outcome mode (ProveRequest::outcomes): a request whose witness does not satisfy its circuit gets
+// its own CAPGPU_ERR_PROOF with the message its lone call would set, the others get their proofs - nothing is proved twice.
 // Runs on the calling thread's context (the leader took its lock).
 static void run_coalesced(std::vector<ProveReq*>& reqs) {
   Context& c = ctx();
@@ -2293,6 +2501,7 @@ static void run_coalesced(std::vector<ProveReq*>& reqs) {
   std::vector<const uint8_t*> msgs(g);
   std::vector<size_t> lens(g);
   std::vector<capgpu_proof> out(g);
+  std::vector<capgpu_prove_outcome> outs(prechecked ? 0 : g);  // (a checked batch has no bad witness left)
   std::vector<const ProvingKey*> keys(g);
   std::vector<const uint64_t*> rows(g);  // every caller's own buffer: copied inside round 1, chunk by chunk
   size_t staged = 0;
@@ -2328,13 +2537,21 @@ static void run_coalesced(std::vector<ProveReq*>& reqs) {
   rq.h_wires = resident ? nullptr : rows.data();
   rq.form = good[0]->form;
   rq.vin = vars ? &vin : nullptr;
+  rq.outcomes = prechecked ? nullptr : outs.data();
   rc = prove_batch(*keys[0], (uint32_t)g, rq);
   tl_prechecked = false;
   if (rc == CAPGPU_OK) rc = take_launch_error();
   if (rc == CAPGPU_OK) {
-    for (size_t i = 0; i < g; i++) *good[i]->out = out[i];
-  } else if (rc == CAPGPU_ERR_PROOF && g > 1) {
-    for (size_t i = 0; i < g; i++) prove_one(good[i]);  // find the owner(s) of the unsatisfied witness
+    for (size_t i = 0; i < g; i++) {
+      if (prechecked || outs[i].status == CAPGPU_OK) {
+        *good[i]->out = out[i];
+        continue;
+      }
+      char text[320];  // what this request's own call would have set: proof 0, its flags
+      oc::outcome_text(outs[i], text, sizeof text);
+      good[i]->rc = outs[i].status;
+      good[i]->err = text;
+    }
   } else {
     for (ProveReq* r : good) {
       r->rc = rc;

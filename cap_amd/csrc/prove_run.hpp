@@ -8,9 +8,11 @@
 //   ProveNeeds what a plan asks of a context's buffers (capgpu_plonk_reserve).
 // prove_batch (plonk.hip) validates, plans, checks the witnesses, carves, picks the graph set and calls a driver.
 #pragma once
+#include "check_kernels.hpp"
 #include "context.hpp"
 #include "host_util.hpp"
 #include "launch.hpp"
+#include "outcome.hpp"
 #include "params.hpp"
 #include "plonk_kernels.hpp"
 #include "transcript_dev.hpp"
@@ -175,10 +177,15 @@ struct BatchWs {
   uint8_t *d_proofs, *tr_state, *tr_pre, *tr_app;
   uint32_t* tr_pre_len;
   fe* zeta;
+  // ... and what k_prove_outcomes reads and writes (capgpu_plonk_prove_each*): the witness check's verdicts, the status words
+  unsigned long long* chk_first;
+  int32_t* status;
   size_t total;
 };
 constexpr uint32_t kEvalChunks = 16;
 constexpr uint32_t kLinTerms = 29;
+static_assert(oc::kCheckNoFault == pk::kNoFault && sizeof(pk::CheckOut::first) == sizeof(unsigned long long),
+              "k_prove_outcomes reads the witness check's verdicts (CheckOut::first)");
 static_assert(kLinTerms == (uint32_t)td::kLinScalars, "transcript_dev.hpp derives the scalars of k_lincomb's terms");
 
 BatchWs carve(void* base, const ProvingKey& K, uint32_t P, size_t num_inputs, bool coeffs, uint32_t tr_stride = 0) {
@@ -224,6 +231,8 @@ BatchWs carve(void* base, const ProvingKey& K, uint32_t P, size_t num_inputs, bo
     w.tr_app = c.take<uint8_t>((size_t)P * td::kAppBytes);
     w.tr_pre_len = c.take<uint32_t>(P);
     w.tr_pre = c.take<uint8_t>((size_t)P * tr_stride);
+    w.chk_first = c.take<unsigned long long>(P);
+    w.status = c.take<int32_t>(P);
   }
   w.total = c.off + 256;
   return w;
@@ -422,10 +431,10 @@ void gather_vars(hipStream_t s, const ProvingKey& K, const std::vector<const Pro
   }
 }
 
-// the pinned result area of a batch of P proofs: the proofs and degree flags (device transcript), or a round's
-// commitments, the grand-product totals, the evaluations and the flags (host transcript)
+// the pinned result area of a batch of P proofs: the proofs, the degree flags and the status words of an outcome call
+// (device transcript), or a round's commitments, the grand-product totals, the evaluations and the flags (host transcript)
 size_t prove_pinned_bytes(uint32_t P, bool dev_tr) {
-  if (dev_tr) return (size_t)P * td::kPrBytes + sizeof(uint32_t) * P + 512;
+  if (dev_tr) return (size_t)P * td::kPrBytes + sizeof(uint32_t) * P + sizeof(int32_t) * P + 768;
   return sizeof(g1_jac) * P * NW + sizeof(fe) * P * 11 + sizeof(uint32_t) * P + 1024;
 }
 // bytes per proof of the device transcript's prefix (init message || vk_bytes || public inputs), in steps of 256: the
@@ -550,6 +559,9 @@ struct ProveRequest {
   const uint64_t* const* h_wires = nullptr;
   int form = CAPGPU_INPUT_EVALS;
   const VarsIn* vin = nullptr;
+  // capgpu_plonk_prove_each*: one record per proof.  The call then proves PAST an unsatisfied witness - neither the
+  // witness check nor the degree check ends it - and every proof gets its own verdict (outcome.hpp); null: all or nothing.
+  capgpu_prove_outcome* outcomes = nullptr;
 };
 
 // ---- one call's run ---------------------------------------------------------------------------------------------------
@@ -596,6 +608,10 @@ struct ProveRun {
   fe* h_evals = nullptr;        // [10 P]
   uint32_t* h_flags = nullptr;  // [P]
   uint8_t* h_proofs = nullptr;  // [P] device transcript: the proofs in ABI layout, then the degree flags
+  int32_t* h_status = nullptr;  // [P] device transcript, outcome calls: k_prove_outcomes' status words
+  // outcome calls under capgpu_plonk_set_precheck: the check's verdicts (prove_batch keeps them instead of returning);
+  // on the device they are in w.chk_first
+  const capgpu_witness_fault* faults = nullptr;
   const size_t proofs_bytes;
   std::vector<g1_affine> ha;
 
@@ -759,6 +775,7 @@ struct ProveRun {
     if (pl.dev_tr) {
       h_proofs = (uint8_t*)c.pin_host;
       h_flags = (uint32_t*)(h_proofs + (proofs_bytes + 255) / 256 * 256);
+      h_status = (int32_t*)((char*)h_flags + (sizeof(uint32_t) * P + 255) / 256 * 256);
     } else {
       char* b = (char*)c.pin_host;
       hj = (g1_jac*)b;
@@ -802,13 +819,17 @@ struct ProveRun {
   int degree_verdict(const uint32_t* flags) const {
     for (uint32_t p = 0; p < P; p++) {
       if (flags[p]) {
-        set_error("capgpu_plonk_prove: proof %u: quotient polynomial has the wrong degree (flags %u): "
-                  "the circuit is not satisfied by this witness",
-                  p, flags[p]);
+        char b[256];
+        oc::degree_text(p, flags[p], b, sizeof b);
+        set_error("%s", b);
         return CAPGPU_ERR_PROOF;
       }
     }
     return CAPGPU_OK;
+  }
+  // outcome calls, host transcript: every proof's record from its flags word and the check's verdict, on the host
+  void host_outcomes(const uint32_t* flags) const {
+    for (uint32_t p = 0; p < P; p++) oc::finish_outcome(flags[p], faults ? &faults[p] : nullptr, &rq.outcomes[p], &rq.proofs[p]);
   }
 
   // ---- round 1: wire polynomials, public-input polynomial, 5 commitments ------------------------------
@@ -1145,16 +1166,31 @@ struct ProveRun {
                   (const Chal*)w.chal, (const fe*)w.zeta, w.terms, lin_base, P);
            if ((r = r5_body())) return r;
            launch("k_tr_open", td::k_tr_open, dim3(cdiv(P, 64)), dim3(64), 0, s, (const g1_jac*)w.comms, w.d_proofs, P);
+           // outcome calls: the status words, and the records of failed proofs blanked before the copy below takes them
+           if (rq.outcomes)
+             launch("k_prove_outcomes", oc::k_prove_outcomes, dim3(P), dim3(64), 0, s, P, (const uint32_t*)w.flags,
+                    faults ? (const unsigned long long*)w.chk_first : nullptr, w.status, w.d_proofs);
            return CAPGPU_OK;
          })))
       return rc;
     uint32_t* flags = h_flags;
     CAP_HIP(hipMemcpyAsync(h_proofs, w.d_proofs, proofs_bytes, hipMemcpyDeviceToHost, s));
     CAP_HIP(hipMemcpyAsync(flags, w.flags, sizeof(uint32_t) * P, hipMemcpyDeviceToHost, s));
+    if (rq.outcomes) CAP_HIP(hipMemcpyAsync(h_status, w.status, sizeof(int32_t) * P, hipMemcpyDeviceToHost, s));
     CAP_HIP(wait_stream());
     trace("pb_r5_done", c.slot);
     if ((rc = take_launch_error())) return rc;
-    if ((rc = degree_verdict(flags))) return rc;
+    if (rq.outcomes) {
+      for (uint32_t p = 0; p < P; p++) {  // (the device applied the rule: its status word, its blanked record)
+        capgpu_prove_outcome& o = rq.outcomes[p];
+        memset(&o, 0, sizeof o);
+        o.status = h_status[p];
+        o.degree_flags = flags[p];
+        if (faults) o.fault = faults[p];
+      }
+    } else if ((rc = degree_verdict(flags))) {
+      return rc;
+    }
     memcpy(rq.proofs, h_proofs, proofs_bytes);
     side_drain.armed = false;  // (every join was waited for in stream order and the stream has drained)
     return CAPGPU_OK;
@@ -1252,7 +1288,8 @@ struct ProveRun {
     CAP_HIP(hipMemcpyAsync(flags, w.flags, sizeof(uint32_t) * P, hipMemcpyDeviceToHost, s));
     if ((rc = fetch_comms(P * NW))) return rc;
     trace("pb_r3_done", c.slot);
-    if ((rc = degree_verdict(flags))) return rc;
+    // (an outcome call goes on through rounds 4 and 5 for every proof: a failed one is blanked at the end)
+    if (!rq.outcomes && (rc = degree_verdict(flags))) return rc;
     std::vector<fe> zeta(P);
     std::vector<fe> pw((size_t)P * 4 * 24);
     parallel_for(P, [&](uint32_t p) {
@@ -1314,6 +1351,7 @@ struct ProveRun {
       affine_to_words(ha[p * 2], proofs[p].opening_proof);
       affine_to_words(ha[p * 2 + 1], proofs[p].shifted_opening_proof);
     }
+    if (rq.outcomes) host_outcomes(flags);
     side_drain.armed = false;  // (every join was waited for in stream order and the stream has drained)
     return take_launch_error();
   }

@@ -17,7 +17,9 @@
 //   * drain() (capgpu_shutdown) refuses new tickets, gives every queued ticket `dropped_rc` without running it, lets the
 //     running ones finish, joins the workers and discards the results nobody is waiting for; a waiter blocked at that
 //     moment still receives its ticket's result.
-// The "run" step is a callback, which is what lets the protocol be exercised on the host.
+// The "run" step is a callback, which is what lets the protocol be exercised on the host.  What a ticket borrows from its
+// submitter travels in its Job (plonk.hip: AsyncJob - the witnesses, the proof array and, for capgpu_plonk_prove_each_async,
+// the outcome array); a ticket that RAN is done with code 0 whatever the outcomes say.
 #pragma once
 #include <chrono>
 #include <condition_variable>

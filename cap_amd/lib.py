@@ -1104,6 +1104,116 @@ def async_stats() -> dict:
     return {"submitted": a.value, "completed": b.value, "max_running": m.value}
 
 
+# ---- per-proof outcomes (capgpu_plonk_prove_each*): a batch is proved past its unsatisfied witnesses ---------------------
+ERR_PROOF = -7  # CAPGPU_ERR_PROOF of include/capgpu.h
+
+
+class ProveOutcome(ctypes.Structure):
+    """capgpu_prove_outcome (include/capgpu.h): the verdict of one proof of a prove_each call.  A failed proof's record
+    is all-ones words."""
+    _fields_ = [
+        ("status", ctypes.c_int32),        # 0, or ERR_PROOF: this witness does not satisfy its circuit
+        ("degree_flags", ctypes.c_uint32),
+        ("fault", WitnessFault),           # precheck on: the check's verdict; off: kind 0
+    ]
+
+    def __str__(self):
+        return prove_outcome_text(self)
+
+
+def prove_outcome_text(outcome: ProveOutcome) -> str:
+    """capgpu_prove_outcome_text: the message a lone plonk_prove of that witness raises ('' for a proof that was made)"""
+    buf = ctypes.create_string_buffer(512)
+    check(load().capgpu_prove_outcome_text(ctypes.byref(outcome), buf, ctypes.c_size_t(len(buf))))
+    return buf.value.decode()
+
+
+def _each_args(who: str, pk_handles, wires_elems, pub_rows, blinders, ext_msgs, input_form):
+    count = len(pk_handles)
+    pub_rows = np.ascontiguousarray(pub_rows, dtype=np.uint64).reshape(-1)
+    blinders = np.ascontiguousarray(blinders, dtype=np.uint64).reshape(-1)
+    max_in = 0
+    if count:
+        shapes = [plonk_key_info(h) for h in set(pk_handles)]
+        n = shapes[0][0]
+        max_in = max(sh[1] for sh in shapes)
+        if any(sh[0] != n for sh in shapes):
+            raise ValueError(f"{who}: the keys of one batch must share the domain size")
+        per = _wires_per_proof(pk_handles, n, input_form)
+        if per is not None and wires_elems != count * per:
+            raise ValueError(f"{who}: wires must hold count x 5 x n elements (count x num_vars)")
+    if pub_rows.size != count * max_in * 4 or blinders.size != count * 13 * 4:
+        raise ValueError(f"{who}: pub_rows must hold {count} x {max_in} and blinders {count} x 13 elements")
+    handles = (ctypes.c_uint64 * max(count, 1))(*pk_handles)
+    msgs_arg = lens_arg = None
+    keep = [pub_rows, blinders]
+    if ext_msgs is not None:
+        if len(ext_msgs) != count:
+            raise ValueError(f"{who}: one message per proof")
+        msgs_arg = (ctypes.c_char_p * max(count, 1))()
+        lens_arg = (ctypes.c_size_t * max(count, 1))()
+        for i, m in enumerate(ext_msgs):
+            keep.append(bytes(m) if m else b"")
+            msgs_arg[i] = keep[-1] if keep[-1] else None
+            lens_arg[i] = len(keep[-1])
+    proofs = (Proof * max(count, 1))()
+    outcomes = (ProveOutcome * max(count, 1))()
+    pub_ptr = _p(pub_rows) if pub_rows.size else None
+    return count, handles, pub_ptr, max_in, msgs_arg, lens_arg, blinders, proofs, outcomes, keep
+
+
+def plonk_prove_each(pk_handles, wires: np.ndarray, pub_rows: np.ndarray, blinders: np.ndarray, ext_msgs=None,
+                     input_form=INPUT_EVALS):
+    """capgpu_plonk_prove_each: plonk_prove_multi that keeps going past an unsatisfied witness -> (proofs, outcomes),
+    one ProveOutcome per proof.  Raises only when the batch could not run.  A proof whose outcome has status 0 is the
+    lone plonk_prove's proof; a failed one is all-ones words."""
+    wires = np.ascontiguousarray(wires, dtype=np.uint64).reshape(-1)
+    count, handles, pub_ptr, max_in, msgs, lens, blinders, proofs, outcomes, _keep = _each_args(
+        "plonk_prove_each", list(pk_handles), wires.size // 4, pub_rows, blinders, ext_msgs, input_form)
+    check(load().capgpu_plonk_prove_each(handles, count, _p(wires), pub_ptr, ctypes.c_size_t(max_in), msgs, lens,
+                                         _p(blinders), ctypes.c_int(_form(input_form)), proofs, outcomes))
+    return list(proofs)[:count], list(outcomes)[:count]
+
+
+def plonk_prove_each_dev(pk_handles, d_wires: DevBuf, pub_rows: np.ndarray, blinders: np.ndarray, ext_msgs=None,
+                         input_form=INPUT_EVALS):
+    """capgpu_plonk_prove_each_dev: the same from a device buffer, on the calling context's stream."""
+    count, handles, pub_ptr, max_in, msgs, lens, blinders, proofs, outcomes, _keep = _each_args(
+        "plonk_prove_each_dev", list(pk_handles), d_wires.nbytes // 32, pub_rows, blinders, ext_msgs, input_form)
+    check(load().capgpu_plonk_prove_each_dev(handles, count, d_wires.ptr, pub_ptr, ctypes.c_size_t(max_in), msgs, lens,
+                                             _p(blinders), ctypes.c_int(_form(input_form)), proofs, outcomes))
+    return list(proofs)[:count], list(outcomes)[:count]
+
+
+class EachTicket(Ticket):
+    """The Ticket of plonk_prove_each_async: wait() -> (proofs, outcomes).  The outcome array is borrowed by the library
+    like the proofs."""
+
+    def __init__(self, ticket: int, proofs, outcomes, count: int, keep):
+        super().__init__(ticket, proofs, keep)
+        self._outcomes = outcomes
+        self._count = count
+
+    def wait(self, timeout_ms: int | None = None):
+        proofs = super().wait(timeout_ms)
+        if proofs is None:
+            return None
+        return proofs[:self._count], list(self._outcomes)[:self._count]
+
+
+def plonk_prove_each_async(pk_handles, wires: np.ndarray, pub_rows: np.ndarray, blinders: np.ndarray, ext_msgs=None,
+                           input_form=INPUT_EVALS) -> EachTicket:
+    """capgpu_plonk_prove_each_async: plonk_prove_each without the wait; EachTicket.wait() -> (proofs, outcomes)."""
+    wires = np.ascontiguousarray(wires, dtype=np.uint64).reshape(-1)
+    count, handles, pub_ptr, max_in, msgs, lens, blinders, proofs, outcomes, keep = _each_args(
+        "plonk_prove_each_async", list(pk_handles), wires.size // 4, pub_rows, blinders, ext_msgs, input_form)
+    t = ctypes.c_uint64(0)
+    check(load().capgpu_plonk_prove_each_async(handles, count, _p(wires), pub_ptr, ctypes.c_size_t(max_in), msgs, lens,
+                                               _p(blinders), ctypes.c_int(_form(input_form)), proofs, outcomes,
+                                               ctypes.byref(t)))
+    return EachTicket(t.value, proofs, outcomes, count, (wires, keep))
+
+
 def plonk_reserve(pk_handle: int, count: int, input_form=INPUT_EVALS, slot: int = -1):
     """capgpu_plonk_reserve: size context `slot` (-1: all) ahead for a `count`-proof host-resident batch under this key,
     in the modes in force now, without proving anything."""

@@ -201,6 +201,22 @@ def prove_mixed(proving_keys, wires: np.ndarray, public_input_rows: np.ndarray, 
         raise TxnApiError.FailedSnark(f"Proof Creation failure: {e}") from e
 
 
+def prove_each(proving_keys, wires: np.ndarray, public_input_rows: np.ndarray, blinders: np.ndarray, ext_msgs=None,
+               input_form="evals") -> list:
+    """prove_mixed with a Result per note, the reference's `Vec<Result<..>>` of one prove() per note
+    (src/utils/params_builder.rs:194-226): a list with, per entry of `proving_keys`, the proof or the
+    TxnApiError.FailedSnark (RETURNED, not raised) its own prove() would have raised, carrying the library's message.
+    One device batch; a note whose witness does not satisfy its circuit costs the others nothing.  Raises only when the
+    batch itself could not run."""
+    try:
+        proofs, outcomes = _lib.plonk_prove_each([k.handle for k in proving_keys], wires, public_input_rows, blinders,
+                                                 ext_msgs, input_form)
+    except (_lib.CapGpuError, ValueError) as e:
+        raise TxnApiError.FailedSnark(f"Proof Creation failure: {e}") from e
+    return [p if o.status == 0 else TxnApiError.FailedSnark(f"Proof Creation failure: {_lib.prove_outcome_text(o)}")
+            for p, o in zip(proofs, outcomes)]
+
+
 def upload_verifying_key(verifying_key: VerifyingKey) -> int:
     """checks a verifying key once and keeps it for txn_batch_verify -> handle (release with release_verifying_key)"""
     try:

@@ -698,7 +698,8 @@ int capgpu_plonk_check_witness_multi(const uint64_t* pk_handles, int count, cons
  * returns CAPGPU_ERR_PROOF and a message with the number of bad proofs, the first one and its fault in the reference's
  * wording ("... 2 of 8 witnesses do not satisfy their circuit; first: proof 3: gate 1234 not satisfied", "proof 3: copy
  * constraint (2,40) -> (0,7) violated").  A coalesced call with a bad witness fails alone, with its own message; the
- * other calls of its batch are proved as ONE batch (without the check, the whole batch is proved again call by call).
+ * other calls of its batch are proved as ONE batch (without the check the batch is proved once as well, in outcome mode
+ * - see capgpu_plonk_prove_each -, and the bad call fails with the degree check's message).
  * Host-resident witnesses are then copied in one go instead of chunk by chunk under round 1.  Off (the default):
  * nothing changes.  Process-wide; takes effect with the next prove call. */
 int capgpu_plonk_set_precheck(int on);
@@ -706,6 +707,53 @@ int capgpu_plonk_set_precheck(int on);
  * check calls copied from host to device, and launches of the variable form's gather kernel.  _dev calls copy no witness.
  * Either pointer may be NULL. */
 int capgpu_plonk_input_stats(uint64_t* witness_bytes_h2d_out, uint64_t* gather_launches_out);
+
+/* ---- per-proof outcomes: a batch is proved PAST its unsatisfied witnesses -------------------------------------------
+ * The batch entry points above are all-or-nothing: one unsatisfied witness fails the call for every proof.  The
+ * reference's callers are a map of one prove() per note, each with a Result of its own (src/utils/params_builder.rs:
+ * 194-226, src/proof/transfer.rs:159-188); these calls are that map as ONE batch.  Arguments, layouts, input forms and
+ * argument checks are those of capgpu_plonk_prove_multi_ex / _multi_dev_ex / _multi_async (same codes, same messages; the
+ * pointer checks are made before a device is looked for), plus outcomes_out: `count` records, NULL with count > 0 is
+ * CAPGPU_ERR_INVALID_ARG.  A call whose pk_handles all name one key makes the launches of capgpu_plonk_prove_batch_ex.
+ * Host-resident calls are dealt over the contexts as capgpu_plonk_prove_batch deals them; each part fills its slice.
+ *
+ * Return value: CAPGPU_OK whenever the batch RAN (the convention of capgpu_plonk_check_witness*); argument errors,
+ * CAPGPU_ERR_OOM, HIP errors and CAPGPU_ERR_BUSY fail the call as they fail the others.  count == 0: CAPGPU_OK, nothing
+ * written.  Per proof: status is CAPGPU_ERR_PROOF exactly when degree_flags != 0 || fault.kind != 0.  A proof with status
+ * CAPGPU_OK is bit for bit what capgpu_plonk_prove_ex makes from the same inputs.  The record of a failed proof is
+ * all-ones words - no verifier accepts it (its points and scalars are out of range), so a caller that forgets to look at
+ * the status cannot ship it.  Nothing is compacted: a failing witness rides the batch to the end and is blanked (bad
+ * witnesses are rare, and the _dev form may not write the caller's buffer).  One exception: with the witness check on and
+ * EVERY witness refused the call returns after the check, before the prover reserves anything.
+ * Both transcript homes, both wire-commit modes, all three input forms, graphs for small batches and capgpu_set_stream
+ * are honoured; while capgpu_plonk_shard_msm is on the three calls return CAPGPU_ERR_INVALID_ARG (the ranks' lock step has
+ * no per-proof exit). */
+typedef struct capgpu_prove_outcome {
+  int32_t status;             /* CAPGPU_OK, or CAPGPU_ERR_PROOF: this witness does not satisfy its circuit */
+  uint32_t degree_flags;      /* the degree check's word for this proof (0 = the quotient had its degree) */
+  capgpu_witness_fault fault; /* capgpu_plonk_set_precheck on: the check's verdict; off: kind 0 */
+} capgpu_prove_outcome;       /* 56 bytes */
+
+int capgpu_plonk_prove_each(const uint64_t* pk_handles, int count, const uint64_t* wires, const uint64_t* pub_inputs,
+                            size_t num_inputs, const uint8_t* const* ext_msgs, const size_t* ext_msg_lens,
+                            const uint64_t* blinders, int input_form, capgpu_proof* proofs_out,
+                            capgpu_prove_outcome* outcomes_out);
+int capgpu_plonk_prove_each_dev(const uint64_t* pk_handles, int count, const void* d_wires, const uint64_t* pub_inputs,
+                                size_t num_inputs, const uint8_t* const* ext_msgs, const size_t* ext_msg_lens,
+                                const uint64_t* blinders, int input_form, capgpu_proof* proofs_out,
+                                capgpu_prove_outcome* outcomes_out);
+/* The ticket form (see capgpu_plonk_prove_multi_async): outcomes_out is BORROWED like proofs_out until capgpu_wait has
+ * reported the ticket done; capgpu_wait returns CAPGPU_OK for a ticket that ran, whatever its outcomes say. */
+int capgpu_plonk_prove_each_async(const uint64_t* pk_handles, int count, const uint64_t* wires,
+                                  const uint64_t* pub_inputs, size_t num_inputs, const uint8_t* const* ext_msgs,
+                                  const size_t* ext_msg_lens, const uint64_t* blinders, int input_form,
+                                  capgpu_proof* proofs_out, capgpu_prove_outcome* outcomes_out, uint64_t* ticket_out);
+/* The message capgpu_plonk_prove_ex of that witness ALONE sets in the mode the outcome was made in: with a fault the
+ * check's wording ("capgpu_plonk_prove: 1 of 1 witnesses do not satisfy their circuit; first: proof 0: gate 1234 not
+ * satisfied" / "... proof 0: copy constraint (2,40) -> (0,7) violated"), otherwise the degree wording with `proof 0` and
+ * the outcome's flags; an empty string for CAPGPU_OK.  At most cap - 1 characters and a NUL are written (cap 0: nothing).
+ * Needs no device.  CAPGPU_ERR_INVALID_ARG for a NULL outcome, or a NULL buf with cap > 0. */
+int capgpu_prove_outcome_text(const capgpu_prove_outcome* outcome, char* buf, size_t cap);
 
 /* ---- verification (host only: needs neither a GPU nor capgpu_init) ---------------------------------------- */
 /* G2 elements: x.c0, x.c1, y.c0, y.c1 of the twist point (Fq2 = Fq[u]/(u^2+1)), Montgomery, 16 words;

@@ -26,10 +26,12 @@
 #ifndef CAPGPU_PROOF_HPP
 #define CAPGPU_PROOF_HPP
 
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <cstring>
 #include <memory>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -417,6 +419,78 @@ Result<ProveTicket> prove_batch_async(Rng& rng, const ProvingKey& pk, const Assi
                                           blinders.data(), a.input_form, proofs->data(), &ticket);
   if (rc != CAPGPU_OK) return detail::map_error(rc, "prove_batch_async");
   return ProveTicket(ticket, std::move(blinders), std::move(proofs));
+}
+
+// One entry per note of prove_each: the proof, or the message its own prove() would have failed with (the reference's
+// Vec<Result<..>> of one prove() per note, src/utils/params_builder.rs:194-226).
+struct ProveEachEntry {
+  std::optional<Proof> proof;
+  std::string error;  // empty when the proof was made
+};
+// One proof per entry of `pks` (keys of ONE domain size under ONE SRS) in a single device batch that goes on PAST an
+// unsatisfied witness (capgpu_plonk_prove_each): assignment i belongs to key i and is in the input form of the first.  A
+// proof that was made is bit for bit what prove() makes of the same assignment and blinders; a note whose witness does
+// not satisfy its circuit gets its error and costs the others nothing.  Err only when the batch could not run.
+template <class Rng>
+Result<std::vector<ProveEachEntry>> prove_each(Rng& rng, const std::vector<const ProvingKey*>& pks,
+                                               const std::vector<Assignment>& as,
+                                               const std::vector<std::vector<uint8_t>>* ext_msgs = nullptr) {
+  const size_t count = pks.size();
+  if (as.size() != count || (ext_msgs && ext_msgs->size() != count))
+    return TxnApiError::failed_snark("prove_each: one assignment (and message) per key");
+  std::vector<ProveEachEntry> out(count);
+  if (!count) return out;
+  size_t n = 0, ni = 0, per = 0;
+  std::vector<uint64_t> handles(count);
+  for (size_t i = 0; i < count; i++) {
+    if (!pks[i] || !as[i].wires || (!as[i].pub_inputs && pks[i]->num_inputs()) || as[i].input_form != as[0].input_form)
+      return TxnApiError::failed_snark("prove_each: empty assignment, or assignments of different input forms");
+    handles[i] = pks[i]->handle();
+    ni = std::max(ni, pks[i]->num_inputs());
+  }
+  int rc = capgpu_plonk_key_info(handles[0], &n, nullptr, nullptr);
+  if (rc != CAPGPU_OK) return detail::map_error(rc, "prove_each");
+  per = 5 * n;
+  if (as[0].input_form == CAPGPU_INPUT_VARS)
+    for (size_t i = per = 0; i < count; i++) {
+      size_t nv = 0;
+      if ((rc = capgpu_plonk_key_num_vars(handles[i], &nv)) != CAPGPU_OK) return detail::map_error(rc, "prove_each");
+      per = std::max(per, nv);
+    }
+  // the library takes one array of rows: the notes' own buffers are gathered (rows of the largest count, zero-filled)
+  std::vector<uint64_t> wires(count * per * 4, 0), pubs(count * ni * 4 + 4, 0), blinders(count * 13 * 4);
+  std::vector<const uint8_t*> mp(count, nullptr);
+  std::vector<size_t> ml(count, 0);
+  for (size_t i = 0; i < count; i++) {
+    size_t own = per;
+    if (as[0].input_form == CAPGPU_INPUT_VARS) capgpu_plonk_key_num_vars(handles[i], &own);
+    std::memcpy(&wires[i * per * 4], as[i].wires, own * 32);
+    if (pks[i]->num_inputs()) std::memcpy(&pubs[i * ni * 4], as[i].pub_inputs, pks[i]->num_inputs() * 32);
+    for (int k = 0; k < 13; k++) {  // drawn in proof order, as count calls of prove() would draw them
+      Fr b = rng();
+      std::memcpy(&blinders[(i * 13 + k) * 4], b.data(), 32);
+    }
+    if (ext_msgs && !(*ext_msgs)[i].empty()) {
+      mp[i] = (*ext_msgs)[i].data();
+      ml[i] = (*ext_msgs)[i].size();
+    }
+  }
+  std::vector<Proof> proofs(count);
+  std::vector<capgpu_prove_outcome> oc(count);
+  rc = capgpu_plonk_prove_each(handles.data(), (int)count, wires.data(), ni ? pubs.data() : nullptr, ni,
+                               ext_msgs ? mp.data() : nullptr, ext_msgs ? ml.data() : nullptr, blinders.data(),
+                               as[0].input_form, proofs.data(), oc.data());
+  if (rc != CAPGPU_OK) return detail::map_error(rc, "prove_each");
+  for (size_t i = 0; i < count; i++) {
+    if (oc[i].status == CAPGPU_OK) {
+      out[i].proof = proofs[i];
+      continue;
+    }
+    char text[512];
+    capgpu_prove_outcome_text(&oc[i], text, sizeof text);
+    out[i].error = text;
+  }
+  return out;
 }
 
 }  // namespace proof
