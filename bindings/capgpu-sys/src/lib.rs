@@ -290,6 +290,11 @@ extern "C" {
                                          proofs_out: *mut capgpu_proof, outcomes_out: *mut capgpu_prove_outcome,
                                          ticket_out: *mut u64) -> c_int;
     pub fn capgpu_prove_outcome_text(outcome: *const capgpu_prove_outcome, buf: *mut c_char, cap: usize) -> c_int;
+    // ---- batch compaction of the outcome calls: witnesses the check refused leave the batch before round 1
+    pub fn capgpu_plonk_set_compaction(on: c_int) -> c_int;
+    pub fn capgpu_plonk_get_compaction(on_out: *mut c_int) -> c_int;
+    pub fn capgpu_plonk_compaction_stats(calls_out: *mut u64, proofs_dropped_out: *mut u64,
+                                         rows_moved_out: *mut u64) -> c_int;
     pub fn capgpu_async_stats(submitted_out: *mut u64, completed_out: *mut u64, max_running_out: *mut u32) -> c_int;
     pub fn capgpu_plonk_reserve(pk_handle: u64, count: c_int, input_form: c_int, slot: c_int) -> c_int;
     // ---- verification (host only)

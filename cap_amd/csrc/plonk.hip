@@ -34,6 +34,8 @@
 
 #include "check_kernels.hpp"
 #include "coalescer.hpp"
+#include "compact.hpp"
+#include "compact_kernels.hpp"
 #include "context.hpp"
 #include "host_util.hpp"
 #include "launch.hpp"
@@ -500,6 +502,154 @@ ProveNeeds prove_needs(const ProvePlan& pl, const ProvingKey& K) {
   return nd;
 }
 
+// The tail of prove_batch, behind the witness check: the workspace, the graph set of the call's signature, a driver.
+int prove_planned(Context& c, const ProvingKey& K, uint32_t P, const ProveRequest& rq, const ProvePlan& pl, ProveRun& run) {
+  const size_t num_inputs = rq.num_inputs;
+  int rc;
+  // workspace
+  if ((rc = scratch_reserve(c.prove_ws, carve(nullptr, K, P, num_inputs, pl.coeffs, pl.tr_stride).total))) return rc;
+  run.w = carve(c.prove_ws.p, K, P, num_inputs, pl.coeffs, pl.tr_stride);
+  // the check's device-side verdicts, for k_prove_outcomes: out of the check's scratch into the workspace (outside the
+  // segments, like every per-call value; nothing has touched stage_a since the check)
+  if (run.faults && pl.dev_tr)
+    CAP_HIP(hipMemcpy2DAsync(run.w.chk_first, sizeof(unsigned long long), &check_out_at(c.stage_a.p, P)->first,
+                             sizeof(CheckOut), sizeof(unsigned long long), P, hipMemcpyDeviceToDevice, c.stream));
+  if (pl.graphs) {
+    ProveGraphSig sig;
+    sig.key_uid = K.uid;
+    sig.srs = K.srs_handle;
+    sig.P = P;
+    sig.num_inputs = num_inputs;
+    sig.form = rq.form;
+    sig.multi = rq.keys != nullptr;
+    sig.d_wires = rq.d_wires;
+    sig.ws = c.prove_ws.p;
+    sig.msm_ws = c.msm_ws.p;
+    sig.ntt_scratch = c.ntt_scratch.p;
+    sig.bases = pl.B->ext;
+    sig.lagrange = pl.Lag ? pl.Lag->ext : nullptr;
+    sig.stream = c.stream;
+    sig.overlap = pl.overlap;
+    sig.transcript = pl.dev_tr ? CAPGPU_TRANSCRIPT_DEVICE : CAPGPU_TRANSCRIPT_HOST;
+    sig.tr_stride = pl.tr_stride;
+    sig.outcomes = rq.outcomes ? (run.faults ? 2 : 1) : 0;
+    run.gs = graph_set_for(c, sig);
+  }
+  return pl.dev_tr ? run.run_device_transcript() : run.run_host_transcript();
+}
+
+// ---- batch compaction (capgpu_plonk_set_compaction; the plan: compact.hpp, the kernel: compact_kernels.hpp) ------------
+// An outcome call whose witnesses were checked knows, before the prover has reserved anything, which proofs will be blanked
+// at the end.  With the mode on it proves the P' survivors as a batch of P' - the refused ones cost their check, not a proof.
+std::atomic<int> g_compact{-1};  // -1: the process default (CAPGPU_COMPACT=1 turns it on)
+std::atomic<uint64_t> g_compact_calls{0}, g_compact_dropped{0}, g_compact_rows{0};  // capgpu_plonk_compaction_stats
+bool compaction_on() {
+  static const int env_default = [] {
+    const char* e = getenv("CAPGPU_COMPACT");
+    return (e && atoi(e) != 0) ? 1 : 0;
+  }();
+  const int m = g_compact.load(std::memory_order_relaxed);
+  return (m < 0 ? env_default : m) != 0;
+}
+static_assert(sizeof(CheckKey) >= sizeof(uint2), "the move table takes the place of the check's key array");
+
+// The survivors of an outcome call of P proofs of which the check refused `bad` (0 < bad < P), proved as a batch of their
+// own.  *ran stays false - and nothing has been touched - when this call is one that runs uncompacted: `_dev` columns
+// below the copy threshold.  The rows the prover reads are moved by ONE launch of k_move_rows, whose table is a per-call
+// value: it is uploaded and the kernel launched here, outside the captured segments, so the segments of the smaller batch
+// depend on the call's signature alone (P = P', an outcome call without verdicts of its own).
+//   * columns in library staging (host-resident input, already copied for the check; gathered columns of the variable
+//     form, whose value vectors are not read again): the plan's moves, in place;
+//   * `_dev` evals / coeffs: the caller's buffer is never written - the survivors' rows are copied into Context::stage_b
+//     (P' moves, dst = i) when cp::copy_route_pays.
+int prove_compacted(Context& c, const ProvingKey& K, uint32_t P, const ProveRequest& rq,
+                    const std::vector<capgpu_witness_fault>& faults, uint32_t bad, bool* ran) {
+  *ran = false;
+  const uint32_t S = P - bad;
+  const size_t n = K.n, row16 = sizeof(fe) * NW * n / sizeof(uint4);
+  const bool in_place = rq.d_wires == (const fe*)c.stage_b.p;
+  if (!in_place && (!cp::copy_route_pays(bad, S) || ((uintptr_t)rq.d_wires & (sizeof(uint4) - 1)))) return CAPGPU_OK;
+  std::vector<uint8_t> refused(P);
+  for (uint32_t p = 0; p < P; p++) refused[p] = faults[p].kind != 0;
+  const cp::Plan plan = cp::compact_plan(refused.data(), P);
+  const std::vector<uint32_t>& orig = plan.orig;
+  int rc;
+  std::vector<uint2> table;
+  fe* cols = const_cast<fe*>(rq.d_wires);
+  if (in_place) {
+    for (const cp::Move& mv : plan.moves) table.push_back(make_uint2(mv.src, mv.dst));
+  } else {
+    if ((rc = scratch_reserve(c.stage_b, wires_stage_bytes(S, n)))) return rc;
+    cols = (fe*)c.stage_b.p;
+    for (uint32_t i = 0; i < S; i++) table.push_back(make_uint2(orig[i], i));
+  }
+  if (!table.empty()) {
+    // (the head of the check's scratch - its key array: the check has been waited for)
+    uint2* d_table = (uint2*)c.stage_a.p;
+    CAP_HIP(hipMemcpyAsync(d_table, table.data(), sizeof(uint2) * table.size(), hipMemcpyHostToDevice, c.stream));
+    launch("k_move_rows", k_move_rows, dim3(cdiv(row16, kThreads), (uint32_t)std::min<size_t>(table.size(), 65535)),
+           dim3(kThreads), 0, c.stream, (const uint4*)rq.d_wires, (uint4*)cols, row16, (const uint2*)d_table,
+           (uint32_t)table.size());
+  }
+  // the compacted request: everything per proof reordered by `orig`, results into temporaries of P'
+  std::vector<const ProvingKey*> keys2;
+  size_t ni2 = rq.num_inputs;
+  if (rq.keys) {
+    ni2 = 0;
+    for (uint32_t i = 0; i < S; i++) {
+      keys2.push_back((*rq.keys)[orig[i]]);
+      ni2 = std::max(ni2, keys2[i]->num_inputs);  // (rows of the survivors' largest count, as prove_batch wants them)
+    }
+  }
+  const ProvingKey& K2 = rq.keys ? *keys2[0] : K;
+  std::vector<uint64_t> pubs2((size_t)4 * ni2 * S + 4, 0), blind2((size_t)4 * 13 * S);
+  std::vector<const uint8_t*> msgs2(S, nullptr);
+  std::vector<size_t> lens2(S, 0);
+  size_t longest = 0;
+  for (uint32_t i = 0; i < S; i++) {
+    const uint32_t p = orig[i];
+    if (ni2) memcpy(&pubs2[(size_t)4 * ni2 * i], rq.pub_inputs + (size_t)4 * rq.num_inputs * p, 32 * ni2);
+    memcpy(&blind2[(size_t)4 * 13 * i], rq.blinders + (size_t)4 * 13 * p, 32 * 13);
+    if (rq.msgs) {
+      msgs2[i] = rq.msgs[p];
+      lens2[i] = rq.msg_lens[p];
+    }
+    const ProvingKey& Kp = rq.keys ? *keys2[i] : K;
+    const size_t ml = rq.msgs ? (rq.msgs[p] ? rq.msg_lens[p] : 0) : (rq.ext_msg ? rq.ext_len : 0);
+    longest = std::max(longest, ml + Kp.vk_bytes.size() + 32 * Kp.num_inputs);
+  }
+  std::vector<capgpu_proof> proofs2(S);
+  std::vector<capgpu_prove_outcome> outcomes2(S);
+  ProveRequest r2 = rq;
+  r2.d_wires = cols;
+  r2.h_wires = nullptr;  // resident since the check
+  r2.pub_inputs = ni2 ? pubs2.data() : nullptr;
+  r2.num_inputs = ni2;
+  r2.blinders = blind2.data();
+  r2.msgs = rq.msgs ? msgs2.data() : nullptr;
+  r2.msg_lens = rq.msgs ? lens2.data() : nullptr;
+  r2.keys = rq.keys ? &keys2 : nullptr;
+  r2.proofs = proofs2.data();
+  r2.outcomes = outcomes2.data();
+  ProvePlan pl2;
+  if ((rc = make_plan(c, K2, S, rq.form, false, longest, false, &pl2))) return rc;
+  pl2.precheck = false;  // these witnesses have been checked
+  ProveRun run2(c, pl2, K2, r2);
+  if ((rc = prove_planned(c, K2, S, r2, pl2, run2))) return rc;
+  for (uint32_t i = 0; i < S; i++) {
+    rq.proofs[orig[i]] = proofs2[i];
+    rq.outcomes[orig[i]] = outcomes2[i];
+  }
+  // a dropped proof was never proved: its fault, an all-ones record, no degree flags - as when every witness is refused
+  for (uint32_t p = 0; p < P; p++)
+    if (refused[p]) oc::finish_outcome(0, &faults[p], &rq.outcomes[p], &rq.proofs[p]);
+  g_compact_calls.fetch_add(1, std::memory_order_relaxed);
+  g_compact_dropped.fetch_add(bad, std::memory_order_relaxed);
+  g_compact_rows.fetch_add(table.size(), std::memory_order_relaxed);
+  *ran = true;
+  return CAPGPU_OK;
+}
+
 // One batch of P proofs under K (mixed keys: K = keys[0]) on the calling thread's context - see ProveRequest for the
 // arguments, ProvePlan for the modes and ProveRun for the schedule.
 int prove_batch(const ProvingKey& K, uint32_t P, const ProveRequest& rq) {
@@ -589,38 +739,14 @@ int prove_batch(const ProvingKey& K, uint32_t P, const ProveRequest& rq) {
         for (uint32_t p = 0; p < P; p++) oc::finish_outcome(0, &faults[p], &rq.outcomes[p], &rq.proofs[p]);
         return CAPGPU_OK;
       }
+      // capgpu_plonk_set_compaction: the refused ones leave the batch here, before the prover reserves its workspace
+      if (bad && compaction_on()) {
+        bool ran = false;
+        if ((rc = prove_compacted(c, K, P, rq, faults, bad, &ran)) || ran) return rc;
+      }
     }
   }
-  // workspace
-  if ((rc = scratch_reserve(c.prove_ws, carve(nullptr, K, P, num_inputs, pl.coeffs, pl.tr_stride).total))) return rc;
-  run.w = carve(c.prove_ws.p, K, P, num_inputs, pl.coeffs, pl.tr_stride);
-  // the check's device-side verdicts, for k_prove_outcomes: out of the check's scratch into the workspace (outside the
-  // segments, like every per-call value; nothing has touched stage_a since the check)
-  if (run.faults && pl.dev_tr)
-    CAP_HIP(hipMemcpy2DAsync(run.w.chk_first, sizeof(unsigned long long), &check_out_at(c.stage_a.p, P)->first,
-                             sizeof(CheckOut), sizeof(unsigned long long), P, hipMemcpyDeviceToDevice, c.stream));
-  if (pl.graphs) {
-    ProveGraphSig sig;
-    sig.key_uid = K.uid;
-    sig.srs = K.srs_handle;
-    sig.P = P;
-    sig.num_inputs = num_inputs;
-    sig.form = rq.form;
-    sig.multi = keys != nullptr;
-    sig.d_wires = rq.d_wires;
-    sig.ws = c.prove_ws.p;
-    sig.msm_ws = c.msm_ws.p;
-    sig.ntt_scratch = c.ntt_scratch.p;
-    sig.bases = pl.B->ext;
-    sig.lagrange = pl.Lag ? pl.Lag->ext : nullptr;
-    sig.stream = c.stream;
-    sig.overlap = pl.overlap;
-    sig.transcript = pl.dev_tr ? CAPGPU_TRANSCRIPT_DEVICE : CAPGPU_TRANSCRIPT_HOST;
-    sig.tr_stride = pl.tr_stride;
-    sig.outcomes = rq.outcomes ? (run.faults ? 2 : 1) : 0;
-    run.gs = graph_set_for(c, sig);
-  }
-  return pl.dev_tr ? run.run_device_transcript() : run.run_host_transcript();
+  return prove_planned(c, K, P, rq, pl, run);
 }
 
 // ---- proving-key construction shared by preprocess and the blob loader -------------------------------------
@@ -842,6 +968,9 @@ void plonk_reset_staging() {
   // (capgpu_shutdown: capgpu_plonk_input_stats counts since capgpu_init)
   g_witness_h2d.store(0);
   g_gather_launches.store(0);
+  g_compact_calls.store(0);  // (capgpu_plonk_compaction_stats likewise)
+  g_compact_dropped.store(0);
+  g_compact_rows.store(0);
 }
 
 // the registry's (home) copy of a key, without replicating it
@@ -2844,6 +2973,27 @@ int capgpu_plonk_check_witness_multi(const uint64_t* pk_handles, int count, cons
 
 int capgpu_plonk_set_precheck(int on) {
   g_precheck.store(on != 0);
+  return CAPGPU_OK;
+}
+
+int capgpu_plonk_set_compaction(int on) {
+  g_compact.store(on != 0);
+  return CAPGPU_OK;
+}
+
+int capgpu_plonk_get_compaction(int* on_out) {
+  if (!on_out) {
+    set_error("capgpu_plonk_get_compaction: bad argument");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  *on_out = compaction_on() ? 1 : 0;
+  return CAPGPU_OK;
+}
+
+int capgpu_plonk_compaction_stats(uint64_t* calls_out, uint64_t* proofs_dropped_out, uint64_t* rows_moved_out) {
+  if (calls_out) *calls_out = g_compact_calls.load();
+  if (proofs_dropped_out) *proofs_dropped_out = g_compact_dropped.load();
+  if (rows_moved_out) *rows_moved_out = g_compact_rows.load();
   return CAPGPU_OK;
 }
 

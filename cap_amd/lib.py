@@ -884,6 +884,25 @@ def plonk_set_precheck(on: bool):
     check(load().capgpu_plonk_set_precheck(ctypes.c_int(1 if on else 0)))
 
 
+def plonk_set_compaction(on: bool):
+    """capgpu_plonk_set_compaction: outcome calls under the witness check prove only the witnesses the check let through
+    (off by default)"""
+    check(load().capgpu_plonk_set_compaction(ctypes.c_int(1 if on else 0)))
+
+
+def plonk_get_compaction() -> bool:
+    m = ctypes.c_int(-1)
+    check(load().capgpu_plonk_get_compaction(ctypes.byref(m)))
+    return bool(m.value)
+
+
+def plonk_compaction_stats():
+    """(calls that ran compacted, proofs they dropped, witness rows handed to k_move_rows) since capgpu_init"""
+    a, b, c = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    check(load().capgpu_plonk_compaction_stats(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+    return a.value, b.value, c.value
+
+
 def plonk_set_coalescing(window_us: int, max_batch: int = 0):
     check(load().capgpu_plonk_set_coalescing(ctypes.c_uint32(window_us), ctypes.c_uint32(max_batch)))
 

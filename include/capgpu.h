@@ -722,9 +722,9 @@ int capgpu_plonk_input_stats(uint64_t* witness_bytes_h2d_out, uint64_t* gather_l
  * written.  Per proof: status is CAPGPU_ERR_PROOF exactly when degree_flags != 0 || fault.kind != 0.  A proof with status
  * CAPGPU_OK is bit for bit what capgpu_plonk_prove_ex makes from the same inputs.  The record of a failed proof is
  * all-ones words - no verifier accepts it (its points and scalars are out of range), so a caller that forgets to look at
- * the status cannot ship it.  Nothing is compacted: a failing witness rides the batch to the end and is blanked (bad
- * witnesses are rare, and the _dev form may not write the caller's buffer).  One exception: with the witness check on and
- * EVERY witness refused the call returns after the check, before the prover reserves anything.
+ * the status cannot ship it.  By default a failing witness rides the batch to the end and is blanked; with the witness
+ * check on and EVERY witness refused the call returns after the check, before the prover reserves anything.  With
+ * capgpu_plonk_set_compaction on as well, the witnesses the check refused leave the batch before round 1 (see there).
  * Both transcript homes, both wire-commit modes, all three input forms, graphs for small batches and capgpu_set_stream
  * are honoured; while capgpu_plonk_shard_msm is on the three calls return CAPGPU_ERR_INVALID_ARG (the ranks' lock step has
  * no per-proof exit). */
@@ -748,6 +748,24 @@ int capgpu_plonk_prove_each_async(const uint64_t* pk_handles, int count, const u
                                   const uint64_t* pub_inputs, size_t num_inputs, const uint8_t* const* ext_msgs,
                                   const size_t* ext_msg_lens, const uint64_t* blinders, int input_form,
                                   capgpu_proof* proofs_out, capgpu_prove_outcome* outcomes_out, uint64_t* ticket_out);
+/* Batch compaction of the outcome calls (off by default; CAPGPU_COMPACT=1 sets the process default).  on != 0: an outcome
+ * call made with capgpu_plonk_set_precheck on, of whose P witnesses the check refused some but not all, proves the P'
+ * survivors as a batch of P' - every launch of the five rounds is that much smaller - and the refused ones cost their
+ * check, not a proof.  A refused proof then has status CAPGPU_ERR_PROOF, its fault, an all-ones record and degree_flags
+ * 0: it was never proved (uncompacted, the degree check sets its flags as well); status is still CAPGPU_ERR_PROOF exactly
+ * when degree_flags != 0 || fault.kind != 0.  Surviving proofs are bit for bit the uncompacted call's.  The witness rows
+ * of the survivors are brought together by one copy kernel ahead of round 1: in library staging (host-resident input,
+ * variable form in either residence) at most min(bad, P') rows move; `_dev` columns and polynomials are the caller's
+ * buffer, which is never written - the survivors' rows are copied into library staging when the proofs saved are worth
+ * the copy (bad * 64 >= P'), and below that the call runs uncompacted.  What stays uncompacted besides: calls with the
+ * witness check off (the degree check's verdict arrives in round 3, too late to be worth it), calls without outcomes,
+ * coalesced calls.  Dealt host batches and tickets compact per part.  Nothing changes while the mode is off.
+ * Process-wide; read when a call - or a ticket - starts.  _get_: the mode in force.  _stats: counters since capgpu_init -
+ * calls (parts of dealt calls) that ran compacted, proofs they dropped, witness rows handed to the copy kernel; any
+ * pointer may be NULL. */
+int capgpu_plonk_set_compaction(int on);
+int capgpu_plonk_get_compaction(int* on_out);
+int capgpu_plonk_compaction_stats(uint64_t* calls_out, uint64_t* proofs_dropped_out, uint64_t* rows_moved_out);
 /* The message capgpu_plonk_prove_ex of that witness ALONE sets in the mode the outcome was made in: with a fault the
  * check's wording ("capgpu_plonk_prove: 1 of 1 witnesses do not satisfy their circuit; first: proof 0: gate 1234 not
  * satisfied" / "... proof 0: copy constraint (2,40) -> (0,7) violated"), otherwise the degree wording with `proof 0` and
