@@ -99,6 +99,37 @@ pub struct capgpu_prove_outcome {
     pub fault: capgpu_witness_fault,
 }
 
+/// `flags` of `capgpu_srs_check`: on a structure fault, find the first bad link by bisection.
+pub const CAPGPU_SRS_CHECK_LOCATE: u32 = 1;
+
+/// `capgpu_srs_report`: the verdict of `capgpu_srs_check` (176 bytes).  `verdict`: 0 consistent, 1 point fault
+/// (`point_fault`: 1 infinity, 2 off the curve, at `first_bad_point`), 2 structure fault (`first_bad_link` with LOCATE).
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct capgpu_srs_report {
+    pub verdict: u32,
+    pub point_fault: u32,
+    pub first_bad_point: u64,
+    pub first_bad_link: u64,
+    pub points_checked: u64,
+    pub links_checked: u64,
+    pub pairing_checks: u32,
+    pub reserved: u32,
+    pub fold_a: [u64; 8],
+    pub fold_b: [u64; 8],
+}
+
+/// `capgpu_key_report`: the verdict of `capgpu_plonk_key_check` (16 bytes).  `verdict`: 0 consistent, 1 shape, 2 a
+/// commitment differs (`column`: 0..12 selector, 13..17 sigma), 3 sigma is no permutation.
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct capgpu_key_report {
+    pub verdict: u32,
+    pub column: u32,
+    pub columns_differing: u32,
+    pub reserved: u32,
+}
+
 #[link(name = "capgpu")]
 extern "C" {
     // ---- lifecycle, devices
@@ -377,6 +408,10 @@ extern "C" {
     pub fn capgpu_plonk_key_deserialize(bytes: *const u8, len: usize, srs_handle_out: *mut u64,
                                         pk_handle_out: *mut u64, vk_out: *mut capgpu_verifying_key, h_out: *mut u64,
                                         beta_h_out: *mut u64, consumed_out: *mut usize) -> c_int;
+    // ---- parameter audit
+    pub fn capgpu_srs_check(srs_handle: u64, g2_h: *const u64, g2_beta_h: *const u64, seed: *const u8, flags: u32,
+                            out: *mut capgpu_srs_report) -> c_int;
+    pub fn capgpu_plonk_key_check(pk_handle: u64, vk: *const capgpu_verifying_key, out: *mut capgpu_key_report) -> c_int;
     // ---- instrumentation
     pub fn capgpu_ubench_mad_rate(lane_ops_per_s_out: *mut f64) -> c_int;
     pub fn capgpu_ubench_issue_rates(rates_out: *mut f64, count: c_int) -> c_int;
@@ -509,6 +544,18 @@ impl Srs {
         })?;
         Ok((Srs { handle }, h, beta_h))
     }
+    /// Is this SRS `[tau^i] g` for the tau of the open key `(h, beta_h)`?  What `load_srs` guards with a SHA-256 over the
+    /// file (src/proof/mod.rs:95-102), asked of the points themselves: once per loaded file, not per proof.  `seed`:
+    /// `None` draws the fold's weights from the OS (the sound choice), `Some` makes the report reproducible; `locate`
+    /// finds the first bad link of an inconsistent SRS.  `Ok` whenever the check ran: the verdict is in the report.
+    pub fn check(&self, h: &[u64; 16], beta_h: &[u64; 16], seed: Option<&[u8; 32]>, locate: bool) -> Result<capgpu_srs_report> {
+        let mut rep = capgpu_srs_report::default();
+        check(unsafe {
+            capgpu_srs_check(self.handle, h.as_ptr(), beta_h.as_ptr(), seed.map_or(std::ptr::null(), |s| s.as_ptr()),
+                             if locate { CAPGPU_SRS_CHECK_LOCATE } else { 0 }, &mut rep)
+        })?;
+        Ok(rep)
+    }
     pub fn handle(&self) -> u64 {
         self.handle
     }
@@ -603,6 +650,15 @@ impl ProvingKey {
                                          wire_vars.as_ptr(), num_vars, &mut handle, &mut vk)
         })?;
         Ok(ProvingKey { handle, vk, domain_size: n, num_inputs })
+    }
+    /// Does this key commit to `vk` (`None`: the key's own - the one a deserialised blob carried, which `load_data`,
+    /// src/parameters.rs:560-577, takes on faith)?  `Ok` whenever the check ran: the verdict is in the report.
+    pub fn check(&self, vk: Option<&capgpu_verifying_key>) -> Result<capgpu_key_report> {
+        let mut rep = capgpu_key_report::default();
+        check(unsafe {
+            capgpu_plonk_key_check(self.handle, vk.map_or(std::ptr::null(), |v| v as *const capgpu_verifying_key), &mut rep)
+        })?;
+        Ok(rep)
     }
     /// Attaches the table to a key made another way (`preprocess`, a deserialised blob); refused when the permutation
     /// it implies is not the key's.

@@ -1470,6 +1470,58 @@ int capgpu_plonk_key_info(uint64_t pk_handle, size_t* domain_size_out, size_t* n
   return CAPGPU_OK;
 }
 
+// Does this proving key produce this verifying key?  The 18 commitments preprocess_impl makes, made again from the key's
+// resident polynomials and compared with vk's (NULL: the key's own - what capgpu_plonk_key_deserialize took from the blob)
+int capgpu_plonk_key_check(uint64_t pk_handle, const capgpu_verifying_key* vk, capgpu_key_report* out) {
+  if (!out) {
+    set_error("capgpu_plonk_key_check: bad argument (no report)");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  memset(out, 0, sizeof *out);
+  CAP_CHECK_INIT();
+  Context& c = ctx();
+  Entry lk(c);
+  std::shared_ptr<ProvingKey> K;
+  int rc = lookup_key(pk_handle, &K);
+  if (rc) return rc;
+  const capgpu_verifying_key& want = vk ? *vk : K->vk;
+  if (want.domain_size != K->n || want.num_inputs != K->num_inputs || memcmp(want.k, K->vk.k, sizeof want.k)) {
+    out->verdict = 1;
+    return CAPGPU_OK;
+  }
+  const MsmBases* B = nullptr;
+  if ((rc = find_srs(K->srs_handle, &B))) return rc;
+  hipStream_t s = c.stream;
+  DevTmp<g1_jac> d_comms;
+  CAP_HIP(d_comms.alloc(18));
+  if ((rc = run_msm(s, *B, K->coef, K->ps, 1, 0, K->n, 18, d_comms))) return rc;
+  std::vector<g1_jac> hj(18);
+  std::vector<g1_affine> ha;
+  CAP_HIP(hipMemcpyAsync(hj.data(), d_comms, sizeof(g1_jac) * 18, hipMemcpyDeviceToHost, s));
+  CAP_HIP(hipStreamSynchronize(s));
+  if ((rc = take_launch_error())) return rc;
+  batch_to_affine(hj, ha);
+  for (int i = 17; i >= 0; i--) {
+    uint64_t w[8];
+    affine_to_words(ha[i], w);
+    if (memcmp(w, i < NS ? want.selector_comms[i] : want.sigma_comms[i - NS], sizeof w)) {
+      out->column = (uint32_t)i;
+      out->columns_differing++;
+    }
+  }
+  if (out->columns_differing) {
+    out->verdict = 2;
+    return CAPGPU_OK;
+  }
+  // the witness check's test of sigma (kept with the key, like the tables that test derives)
+  rc = key_check_tables(*K);
+  if (rc == CAPGPU_ERR_INVALID_ARG && K->chk_rc == CAPGPU_ERR_INVALID_ARG) {
+    out->verdict = 3;
+    return CAPGPU_OK;
+  }
+  return rc;
+}
+
 int capgpu_plonk_key_num_vars(uint64_t pk_handle, size_t* num_vars_out) {
   CAP_CHECK_INIT();
   std::shared_ptr<ProvingKey> K;

@@ -20,6 +20,7 @@
 #define CAP_TD_NO_KERNELS
 #include <stdlib.h>
 #include <string.h>
+#include <unistd.h>
 
 #include <algorithm>
 #include <atomic>
@@ -34,6 +35,7 @@
 #include "pairing29.hpp"
 #include "pairing_wave.hpp"
 #include "proof_codec.hpp"
+#include "srs_check.hpp"
 #include "verify_front.hpp"
 #include "verify_terms.hpp"
 
@@ -705,12 +707,168 @@ int verify_block(const char* who, const uint64_t* vk_handles, const uint64_t g2_
   return CAPGPU_OK;
 }
 
+// ---- capgpu_srs_check (srs_check.hpp: the rule, the point kernel, the soundness argument) -------------------------------
+// r_i = vf::weight_bits(seed, i), one wavefront per weight, written as canonical integers (what the MSM takes); all zero
+// once the point pass has reported a fault: the fold that follows then touches no point (the sort skips zero digits)
+__global__ __launch_bounds__(64) void k_srs_weights(const uint8_t* __restrict__ seed, uint32_t count,
+                                                    const unsigned long long* __restrict__ fault, fe* __restrict__ w) {
+  __shared__ uint8_t idx8[8], dig[32];
+  td::KeccakTabs<td::LaneDev> tabs;
+  tabs.init();
+  const bool clean = fault[0] == sc::kNoIndex;
+  for (uint32_t i = blockIdx.x; i < count; i += gridDim.x) {  // (uniform per block: every lane takes part in the sponge)
+    const fe r = vf::weight_bits<td::LaneDev>(seed, i, tabs, idx8, dig);
+    if (threadIdx.x == 0) w[i] = clean ? r : Fr::zero();
+  }
+}
+// the two folds to affine form: out[0] = A, out[1] = B, out[2] = -B (what the check takes)
+__global__ __launch_bounds__(64) void k_srs_affine(const g1_jac* __restrict__ sums, g1_affine* __restrict__ out) {
+  if (blockIdx.x || threadIdx.x) return;
+  const g1_jac in[2] = {sums[0], sums[1]};
+  g1_affine o[2];
+  td::to_affine(in, 2, o);
+  out[0] = o[0];
+  out[1] = o[1];
+  if (!G1::is_inf(o[1])) o[1].y = Fq::neg(o[1].y);
+  out[2] = o[1];
+}
+
+struct SrsDeviceOut {  // what one fold hands back: the point pass's two words, the check's verdict, A and B
+  unsigned long long fault[2];
+  int ok, pad;
+  g1_affine ab[3];
+};
+
+int srs_check(uint64_t srs_handle, const uint64_t g2_h[16], const uint64_t g2_beta_h[16], const uint8_t* seed,
+              uint32_t flags, capgpu_srs_report* out) {
+  if (!out || !g2_h || !g2_beta_h || (flags & ~CAPGPU_SRS_CHECK_LOCATE)) {
+    set_error("capgpu_srs_check: bad argument (null pointer, or flag bits other than CAPGPU_SRS_CHECK_LOCATE)");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  memset(out, 0, sizeof *out);
+  out->first_bad_point = out->first_bad_link = UINT64_MAX;
+  pairing::g2_affine h, beta_h;
+  int rc = open_key_from_abi(g2_h, g2_beta_h, &h, &beta_h);
+  if (rc) return rc;
+  CAP_CHECK_INIT();
+  SrsRecord rec;
+  if ((rc = srs_record(srs_handle, &rec))) return rc;
+  if (rec.sharded()) {
+    set_error("capgpu_srs_check: SRS %llu is sharded by point range over the devices of this process; the check runs on "
+              "one device's table", (unsigned long long)srs_handle);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  uint8_t seed_bytes[32];
+  if (seed) {
+    memcpy(seed_bytes, seed, 32);
+  } else if (getentropy(seed_bytes, 32) != 0) {
+    set_error("capgpu_srs_check: the operating system gave no random seed (getentropy)");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  Context& c = ctx();
+  Entry lk(c);
+  const MsmBases* B = nullptr;
+  if ((rc = find_srs(srs_handle, &B))) return rc;
+  const size_t n = B->n, links = n ? n - 1 : 0;
+  out->points_checked = n;
+  if (n == 0) return CAPGPU_OK;
+  if (links >= ((size_t)1 << 31)) {
+    set_error("capgpu_srs_check: %zu points (the limit is 2^31)", n);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  const Lines* L = nullptr;
+  if (links && (rc = lines_on_context(c, g2_h, g2_beta_h, h, beta_h, &L))) return rc;
+
+  // workspace: the seed, the device's answer, the two sums, the weights - from the staging scratch; the MSM's own
+  size_t at = 0;
+  auto carve = [&](size_t bytes) {
+    const size_t o = at;
+    at += up256(bytes ? bytes : 1);
+    return o;
+  };
+  const size_t o_seed = carve(32), o_out = carve(sizeof(SrsDeviceOut)), o_sums = carve(sizeof(g1_jac) * 2),
+               o_w = carve(sizeof(fe) * links);
+  if ((rc = scratch_reserve(c.stage_a, at))) return rc;
+  if (links && (rc = scratch_reserve(c.msm_ws, msm_workspace_bytes(*B, links, 1)))) return rc;
+  char* d = (char*)c.stage_a.p;
+  hipStream_t s = c.stream;
+  SrsDeviceOut* d_out = (SrsDeviceOut*)(d + o_out);
+  g1_jac* d_sums = (g1_jac*)(d + o_sums);
+  fe* d_w = (fe*)(d + o_w);
+  SrsDeviceOut init, got;
+  memset(&init, 0, sizeof init);
+  init.fault[0] = init.fault[1] = sc::kNoIndex;
+  CAP_HIP(hipMemcpyAsync(d + o_seed, seed_bytes, 32, hipMemcpyHostToDevice, s));
+  CAP_HIP(hipMemcpyAsync(d_out, &init, sizeof init, hipMemcpyHostToDevice, s));
+  launch("k_srs_points", sc::k_srs_points, dim3((unsigned)((n + sc::kPointThreads - 1) / sc::kPointThreads)),
+         dim3(sc::kPointThreads), 0, s, (const g1_affine*)B->ext, (unsigned long long)n, (unsigned long long*)d_out->fault);
+  if (links)
+    launch("k_srs_weights", k_srs_weights, dim3((unsigned)std::min(links, (size_t)1 << 20)), dim3(64), 0, s,
+           (const uint8_t*)(d + o_seed), (uint32_t)links, (const unsigned long long*)d_out->fault, d_w);
+  if ((rc = take_launch_error())) return rc;
+  // A and B over the first k weights, the check on them, the answer copied back: one wait
+  auto fold = [&](size_t k) -> int {
+    int r = scratch_reserve(c.msm_ws, msm_workspace_bytes(*B, k, 1));
+    if (r) return r;
+    for (int side = 0; side < 2; side++)
+      if ((r = msm_run(*B, (size_t)side, d_w, 0, 1, 0, k, 1, 0, d_sums + side, c.msm_ws.p, c.msm_ws.cap, s)))
+        return hip_fail((hipError_t)r, "msm_run");
+    g1_affine* d_ab = (g1_affine*)d_out->ab;
+    launch("k_srs_affine", k_srs_affine, dim3(1), dim3(64), 0, s, (const g1_jac*)d_sums, d_ab);
+    if ((r = take_launch_error())) return r;
+    if ((r = launch_checks(d_ab, d_ab + 2, 1, L->d1.p, L->d2.p, &d_out->ok, s, CAPGPU_PAIRING_WAVE))) return r;
+    CAP_HIP(hipMemcpyAsync(&got, d_out, sizeof got, hipMemcpyDeviceToHost, s));
+    CAP_HIP(hipStreamSynchronize(s));
+    return CAPGPU_OK;
+  };
+  if (links) {
+    if ((rc = fold(links))) return rc;
+  } else {
+    CAP_HIP(hipMemcpyAsync(&got, d_out, sizeof got, hipMemcpyDeviceToHost, s));
+    CAP_HIP(hipStreamSynchronize(s));
+  }
+  if (got.fault[0] != sc::kNoIndex) {  // (the weights were zeroed: the fold added nothing and its verdict says nothing)
+    out->verdict = 1;
+    out->first_bad_point = got.fault[0];
+    out->point_fault = (uint32_t)(got.fault[1] & 3);
+    return CAPGPU_OK;
+  }
+  out->links_checked = links;
+  if (!links) return CAPGPU_OK;
+  out->pairing_checks = 1;
+  memcpy(out->fold_a, &got.ab[0], 64);
+  memcpy(out->fold_b, &got.ab[1], 64);
+  if (!got.ok) {
+    out->verdict = 2;
+    if (flags & CAPGPU_SRS_CHECK_LOCATE) {
+      // pass(k): the links below k fold to a pair that pairs up.  pass(0) holds, pass(links) has just failed: the lowest
+      // bad link is the largest k with pass(k)
+      size_t lo = 0, hi = links;
+      while (hi - lo > 1) {
+        const size_t mid = lo + (hi - lo) / 2;
+        if ((rc = fold(mid))) return rc;
+        out->pairing_checks++;
+        (got.ok ? lo : hi) = mid;
+      }
+      out->first_bad_link = lo;
+    }
+  }
+  g_wave_checks.fetch_add(out->pairing_checks, std::memory_order_relaxed);
+  return CAPGPU_OK;
+}
+
 }  // namespace
 }  // namespace cap
 
 using namespace cap;
 
 extern "C" {
+
+// Is the resident SRS a power sequence under this open key?  (srs_check.hpp; include/capgpu.h has the contract)
+int capgpu_srs_check(uint64_t srs_handle, const uint64_t g2_h[16], const uint64_t g2_beta_h[16], const uint8_t seed[32],
+                     uint32_t flags, capgpu_srs_report* out) {
+  return srs_check(srs_handle, g2_h, g2_beta_h, seed, flags, out);
+}
 
 // ok_out[i] = (e(p_i, q1) e(r_i, q2) == 1): one lane per check under CAPGPU_PAIRING_LANE, one group of six lanes per
 // check under CAPGPU_PAIRING_WAVE (capgpu_pairing_set_form)

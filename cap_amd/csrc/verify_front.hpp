@@ -182,10 +182,11 @@ CAP_HD void weight_seed(const uint8_t* ub, uint32_t count, const td::KeccakTabs<
   td::store_digest<X>(a, S, 1);
   X::sync();
 }
-// r_i (Montgomery).  idx8: 8 bytes the caller owns, dig: 32; all lanes of X take part and return the same value
+// The first 16 bytes, little-endian, of Keccak-256(S || le64(i)) as a canonical integer below 2^128 - for every i, 0
+// included (srs_check.hpp folds with these).  idx8: 8 bytes the caller owns, dig: 32; all lanes of X take part and return
+// the same value
 template <class X>
-CAP_HD fe weight(const uint8_t* S, uint64_t i, const td::KeccakTabs<X>& tabs, uint8_t* idx8, uint8_t* dig) {
-  if (i == 0) return Fr::one();
+CAP_HD fe weight_bits(const uint8_t* S, uint64_t i, const td::KeccakTabs<X>& tabs, uint8_t* idx8, uint8_t* dig) {
   X::for_each(X::make([](int, int) { return 0ull; }), [idx8, i](int l, int half, uint64_t) {
     if (l < 8 && half == 0) idx8[l] = (uint8_t)(i >> (8 * l));
   });
@@ -198,7 +199,13 @@ CAP_HD fe weight(const uint8_t* S, uint64_t i, const td::KeccakTabs<X>& tabs, ui
   for (int w = 0; w < 4; w++)
     r.v[w] = (uint32_t)dig[4 * w] | ((uint32_t)dig[4 * w + 1] << 8) | ((uint32_t)dig[4 * w + 2] << 16) |
              ((uint32_t)dig[4 * w + 3] << 24);
-  return Fr::to_mont(r);
+  return r;
+}
+// r_i of the block verifier (Montgomery): 1 for i = 0, the hashed weight otherwise
+template <class X>
+CAP_HD fe weight(const uint8_t* S, uint64_t i, const td::KeccakTabs<X>& tabs, uint8_t* idx8, uint8_t* dig) {
+  if (i == 0) return Fr::one();
+  return Fr::to_mont(weight_bits<X>(S, i, tabs, idx8, dig));
 }
 
 }  // namespace vf

@@ -1672,3 +1672,77 @@ def plonk_key_deserialize(data: bytes):
     check(load().capgpu_plonk_key_deserialize(_u8buf(data), ctypes.c_size_t(len(data)), ctypes.byref(srs),
                                               ctypes.byref(pk), ctypes.byref(vk), _p(h), _p(bh), ctypes.byref(used)))
     return srs.value, pk.value, vk, h, bh, used.value
+
+
+# ---- parameter audit (needs init()) ----------------------------------------------------------------------------
+SRS_CHECK_LOCATE = 1
+
+
+class SrsReport(ctypes.Structure):
+    """capgpu_srs_report (include/capgpu.h): the verdict of capgpu_srs_check."""
+    _fields_ = [
+        ("verdict", ctypes.c_uint32),           # 0 consistent, 1 point fault, 2 structure fault
+        ("point_fault", ctypes.c_uint32),       # 0 none, 1 a point at infinity, 2 a point off the curve
+        ("first_bad_point", ctypes.c_uint64),
+        ("first_bad_link", ctypes.c_uint64),
+        ("points_checked", ctypes.c_uint64),
+        ("links_checked", ctypes.c_uint64),
+        ("pairing_checks", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("fold_a", ctypes.c_uint64 * 8),
+        ("fold_b", ctypes.c_uint64 * 8),
+    ]
+
+    def __str__(self):
+        """'' for a consistent SRS, else the fault in words"""
+        if self.verdict == 1:
+            what = "is the point at infinity" if self.point_fault == 1 else "is not on the curve"
+            return f"SRS point {self.first_bad_point} {what}"
+        if self.verdict == 2:
+            where = "" if self.first_bad_link == 2**64 - 1 else \
+                f"; first bad link: point {self.first_bad_link + 1} is not tau times point {self.first_bad_link}"
+            return "SRS is not a power sequence under the open key" + where
+        return ""
+
+
+class KeyReport(ctypes.Structure):
+    """capgpu_key_report (include/capgpu.h): the verdict of capgpu_plonk_key_check."""
+    _fields_ = [
+        ("verdict", ctypes.c_uint32),   # 0 consistent, 1 shape, 2 commitment differs, 3 sigma is no permutation
+        ("column", ctypes.c_uint32),    # verdict 2: 0..12 selector, 13..17 sigma; the lowest differing
+        ("columns_differing", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+    def __str__(self):
+        if self.verdict == 1:
+            return "proving key and verifying key differ in domain_size, num_inputs or k"
+        if self.verdict == 2:
+            col = f"selector {self.column}" if self.column < NUM_SELECTORS else f"sigma {self.column - NUM_SELECTORS}"
+            return (f"the proving key's polynomials do not commit to the verifying key: {self.columns_differing} of 18 "
+                    f"commitments differ, first: {col}")
+        if self.verdict == 3:
+            return "sigma is not a permutation of the extended domain"
+        return ""
+
+
+def srs_check(handle: int, g2_h: np.ndarray, g2_beta_h: np.ndarray, seed: bytes | None = None,
+              locate: bool = False) -> SrsReport:
+    """Is the resident SRS [tau^i] g for the tau of the open key (h, beta_h)?  The report holds the verdict; seed: 32
+    bytes for a reproducible check, None to draw them from the OS.  Call once per loaded file, not per proof."""
+    if seed is not None and len(seed) != 32:
+        raise ValueError("srs_check: the seed is 32 bytes")
+    rep = SrsReport()
+    check(load().capgpu_srs_check(ctypes.c_uint64(handle), _p(np.ascontiguousarray(g2_h, dtype=np.uint64)),
+                                  _p(np.ascontiguousarray(g2_beta_h, dtype=np.uint64)),
+                                  _u8buf(seed) if seed is not None else None,
+                                  ctypes.c_uint32(SRS_CHECK_LOCATE if locate else 0), ctypes.byref(rep)))
+    return rep
+
+
+def plonk_key_check(pk_handle: int, vk: VerifyingKey | None = None) -> KeyReport:
+    """Does the proving key commit to this verifying key (None: the key's own, e.g. the one its blob carried)?"""
+    rep = KeyReport()
+    check(load().capgpu_plonk_key_check(ctypes.c_uint64(pk_handle), ctypes.byref(vk) if vk is not None else None,
+                                        ctypes.byref(rep)))
+    return rep

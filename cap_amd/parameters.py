@@ -182,13 +182,25 @@ def serialize_proving_key(pk: ProvingKey) -> bytes:
         raise TxnApiError.FailedSnark(str(e)) from e
 
 
-def deserialize_proving_key(data: bytes):
-    """-> (ProvingKey, bytes consumed).  The commit key inside the blob becomes the key's own device-resident SRS."""
+def deserialize_proving_key(data: bytes, check: bool = False):
+    """-> (ProvingKey, bytes consumed).  The commit key inside the blob becomes the key's own device-resident SRS.
+    check=True (the reference's load_data checks nothing, src/parameters.rs:560-577): the key's polynomials are committed
+    to again on the device and compared with the verifying key the blob carries (capgpu_plonk_key_check); a key that
+    does not produce its verifying key raises FailedSnark naming the fault, and its handles are freed."""
     try:
         _lib.init()
         srs_h, pk_h, vk, h, beta_h, used = _lib.plonk_key_deserialize(data)
     except _lib.CapGpuError as e:
         raise _de_error(e) from e
+    if check:
+        try:
+            rep = _lib.plonk_key_check(pk_h)
+        except _lib.CapGpuError as e:
+            raise TxnApiError.FailedSnark(str(e)) from e
+        if rep.verdict:
+            _lib.plonk_free_key(pk_h)
+            _lib.srs_free(srs_h)
+            raise TxnApiError.FailedSnark(f"Failed to load proving key: {rep}")
     srs = UniversalSrs(srs_h, _lib.srs_size(srs_h) - 1, h, beta_h)
     return ProvingKey(pk_h, int(vk.domain_size), int(vk.num_inputs), srs), used
 
@@ -217,9 +229,9 @@ def store_transfer_proving_key(key: TransferProvingKey, dest: Path | None = None
 
 
 def load_transfer_proving_key(num_input: int, num_output: int, tree_depth: int,
-                              src: Path | None = None) -> TransferProvingKey:
+                              src: Path | None = None, check: bool = False) -> TransferProvingKey:
     data = load_bytes(src or default_transfer_proving_key_path(num_input, num_output, tree_depth))
-    pk, used = deserialize_proving_key(data)
+    pk, used = deserialize_proving_key(data, check)
     return TransferProvingKey(pk, *_unpack_trailer("<QQB", data, used))
 
 
@@ -241,9 +253,9 @@ def store_mint_proving_key(key: MintProvingKey, dest: Path | None = None) -> Non
                 dest or default_mint_proving_key_path(key.tree_depth))
 
 
-def load_mint_proving_key(tree_depth: int, src: Path | None = None) -> MintProvingKey:
+def load_mint_proving_key(tree_depth: int, src: Path | None = None, check: bool = False) -> MintProvingKey:
     data = load_bytes(src or default_mint_proving_key_path(tree_depth))
-    pk, used = deserialize_proving_key(data)
+    pk, used = deserialize_proving_key(data, check)
     return MintProvingKey(pk, *_unpack_trailer("<B", data, used))
 
 
@@ -263,9 +275,10 @@ def store_freeze_proving_key(key: FreezeProvingKey, dest: Path | None = None) ->
                 dest or default_freeze_proving_key_path(key.num_input, key.tree_depth))
 
 
-def load_freeze_proving_key(num_input: int, tree_depth: int, src: Path | None = None) -> FreezeProvingKey:
+def load_freeze_proving_key(num_input: int, tree_depth: int, src: Path | None = None,
+                            check: bool = False) -> FreezeProvingKey:
     data = load_bytes(src or default_freeze_proving_key_path(num_input, tree_depth))
-    pk, used = deserialize_proving_key(data)
+    pk, used = deserialize_proving_key(data, check)
     return FreezeProvingKey(pk, *_unpack_trailer("<BQ", data, used))
 
 

@@ -121,12 +121,17 @@ def universal_setup(max_degree: int, tau: int, gamma: int | None = None) -> Univ
 AZTEC_CRS_SHA256 = bytes.fromhex("6b81e75fb9c14fd0e58fb2b29e48978cdad5511503685a61f1391dc4a4fc7cbf")
 
 
-def load_srs(max_degree: int, crs_bytes: bytes, expected_sha256: bytes = AZTEC_CRS_SHA256) -> UniversalSrs:
+def load_srs(max_degree: int, crs_bytes: bytes, expected_sha256: bytes = AZTEC_CRS_SHA256,
+             check: bool = False) -> UniversalSrs:
     """src/proof/mod.rs:74-109.  `crs_bytes`: the file the reference embeds with include_bytes! (an ark-serialized
     UniversalSrs; its tree does not ship it, so the caller hands the bytes in).  As there: max_degree > 2^17 is refused
     with the reference's message; the SHA-256 of the bytes must equal the pinned digest (or the one the caller states
     for a test SRS) - a mismatch is the reference's assert_eq! panic, here an AssertionError; the WHOLE file is
-    deserialized, max_degree plays no other role."""
+    deserialized, max_degree plays no other role.
+    check=True (no counterpart in the reference, which stops at the digest): the loaded powers are audited on the device
+    against the blob's own open key (capgpu_srs_check, seed from the OS) - a point off the curve or at infinity, or
+    powers that are no sequence [tau^i] g under beta_h, raise FailedSnark naming the fault and the handle is freed.  The
+    default leaves loading as it was."""
     import hashlib
     if max_degree > 1 << 17:
         raise TxnApiError.FailedSnark("Currently only supports 2^17. Please update Aztec's CRS data file if needed.")
@@ -134,6 +139,11 @@ def load_srs(max_degree: int, crs_bytes: bytes, expected_sha256: bytes = AZTEC_C
     try:
         _lib.init()
         handle, h, beta_h, _used = _lib.srs_deserialize(crs_bytes)
+        if check:
+            rep = _lib.srs_check(handle, h, beta_h, None, locate=True)
+            if rep.verdict:
+                _lib.srs_free(handle)
+                raise TxnApiError.FailedSnark(f"Failed to load SRS: {rep}")
         return UniversalSrs(handle, _lib.srs_size(handle) - 1, h, beta_h)
     except _lib.CapGpuError as e:
         raise TxnApiError.FailedSnark(f"Failed to load SRS: {e}") from e

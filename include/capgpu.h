@@ -985,6 +985,63 @@ int capgpu_plonk_key_deserialize(const uint8_t* bytes, size_t len, uint64_t* srs
                                  capgpu_verifying_key* vk_out, uint64_t h_out[16], uint64_t beta_h_out[16],
                                  size_t* consumed_out);
 
+/* ---- parameter audit: look at an SRS and a proving key before trusting them (needs capgpu_init; no host path) ----------
+ * The reference guards its ceremony file with a SHA-256 over the bytes before it deserialises (load_srs,
+ * src/proof/mod.rs:95-102) and reads its key files with no check at all (load_data, src/parameters.rs:560-577).  A wrong,
+ * truncated or swapped point, a beta_h from another ceremony or a key file whose polynomials do not match its commitments
+ * all give proofs no verifier accepts, and nothing on the proving side says why.  These two calls ask the questions a hash
+ * cannot: call them ONCE per loaded file, not per proof.
+ * Conventions of capgpu_plonk_check_witness*: CAPGPU_OK whenever the check RAN - the verdict is in the report; the same
+ * inputs (and seed) give the same report on every run; negative codes are for malformed arguments only (out == NULL,
+ * unknown flag bits, G2 input off the twist or at infinity - all refused before a device is looked for - and an unknown
+ * handle), CAPGPU_ERR_NOT_INITIALISED before capgpu_init.  Both run on the calling thread's context and stream
+ * (capgpu_set_stream is honoured) and take their workspace from the context's scratch (capgpu_scratch_stats counts it,
+ * capgpu_set_memory_limit caps it: CAPGPU_ERR_OOM naming the bytes).
+ *
+ * capgpu_srs_check: are the resident points P[0 .. n) of the handle a power sequence P[i + 1] = tau P[i] for the tau of the
+ * open key (h, beta_h = [tau] h)?
+ *   a. point pass: every P[i] is on y^2 = x^3 + 3 and not infinity (capgpu_srs_upload does not check this); a fault ends
+ *      the call with verdict 1 - the fold is not run on what is no group element (pairing_checks = 0);
+ *   b. weights r_i, i < n - 1: the first 16 bytes, little-endian, of Keccak-256(seed || le64(i)) (the block verifier's
+ *      byte convention; every i is hashed);
+ *   c. fold: A = sum r_i P[i], B = sum r_i P[i + 1] - two MSMs over the same weights on the resident table;
+ *   d. e(A, beta_h) e(-B, h) == 1 by one wave-form pairing check on the device; failure is verdict 2;
+ *   e. CAPGPU_SRS_CHECK_LOCATE, after a verdict 2 only: bisection on the prefix length k - the prefix [0, k] passes iff
+ *      sum_{i<k} r_i P[i] and sum_{i<k} r_i P[i + 1] pair up - finds the lowest bad link in at most ceil(log2 n) rounds.
+ * The call waits for the device once, and once more per bisection round.  n == 1 has no links: verdict 0, no pairing.
+ * Soundness: a consistent SRS is ALWAYS accepted (B = tau A exactly); an inconsistent one is accepted with probability
+ * about 2^-128 over a seed its author did not know - hence seed == NULL draws 32 bytes from the operating system, and a
+ * caller-given seed is for reproducibility.  Not covered: the hiding powers (powers_of_gamma_g: host-side bytes the prover
+ * never reads), neg_powers_of_h, whether P[0] is any particular generator, and the window tables the library derives
+ * itself from the points.  A sharded SRS is refused (CAPGPU_ERR_INVALID_ARG). */
+#define CAPGPU_SRS_CHECK_LOCATE 1u   /* on a structure fault, find the first bad link (bisection) */
+typedef struct capgpu_srs_report {
+  uint32_t verdict;          /* 0 consistent, 1 point fault, 2 structure fault */
+  uint32_t point_fault;      /* 0 none, 1 a point at infinity, 2 a point off the curve */
+  uint64_t first_bad_point;  /* verdict 1: lowest index with a point fault; else UINT64_MAX */
+  uint64_t first_bad_link;   /* verdict 2 with LOCATE: lowest i with P[i+1] != tau P[i]; else UINT64_MAX */
+  uint64_t points_checked, links_checked;   /* n and n - 1 (0 links when a point fault ended the call) */
+  uint32_t pairing_checks;   /* 1, or 1 + the bisection's rounds; 0 when no fold was made */
+  uint32_t reserved;
+  uint64_t fold_a[8], fold_b[8];  /* A = sum r_i P[i], B = sum r_i P[i+1], i < n-1: affine, Montgomery, (0,0) = infinity */
+} capgpu_srs_report;          /* 176 bytes */
+int capgpu_srs_check(uint64_t srs_handle, const uint64_t g2_h[16], const uint64_t g2_beta_h[16],
+                     const uint8_t seed[32] /* NULL: drawn from the OS */, uint32_t flags, capgpu_srs_report* out);
+/* capgpu_plonk_key_check: does this proving key produce this verifying key?  capgpu_plonk_key_deserialize "rebuilds the
+ * resident tables of the prover without redoing the 18 interpolations and commitments of preprocess": the verifying key
+ * inside a proving-key blob is taken on faith.  This call commits to the key's 18 polynomials again (one batched MSM on
+ * the key's SRS), compares the affine commitments word for word with vk's, compares domain_size, num_inputs and k[], and
+ * runs the witness check's test that sigma's values lie in the five cosets k_i H.  vk == NULL: the key's own verifying
+ * key - the check to run after capgpu_plonk_key_deserialize.  When several faults are present the lowest verdict is
+ * reported. */
+typedef struct capgpu_key_report {
+  uint32_t verdict;      /* 0 consistent, 1 shape (domain_size / num_inputs / k differ), 2 commitment differs, 3 sigma is no permutation */
+  uint32_t column;       /* verdict 2: 0..12 selector (gate order of capgpu_verifying_key), 13..17 sigma; lowest differing */
+  uint32_t columns_differing, reserved;
+} capgpu_key_report;     /* 16 bytes */
+int capgpu_plonk_key_check(uint64_t pk_handle, const capgpu_verifying_key* vk /* NULL: the key's own */,
+                           capgpu_key_report* out);
+
 /* ---- instrumentation ------------------------------------------------------------------------------ */
 /* Measured issue rate of v_mad_u64_u32 on the bound device, in lane-operations per second (8 independent chains per
  * lane, 8 waves per SIMD, ~50 ms).  A lazy Montgomery multiplication is 171 of them (81 + 81 + 9), so rate / 171 is the

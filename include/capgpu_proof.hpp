@@ -245,8 +245,12 @@ inline const std::array<uint8_t, 32>& aztec_crs_sha256() {
 //   - the SHA-256 of the bytes must equal `expected_sha256` - the reference's pinned digest unless the caller states
 //     another one (a test SRS) - or the call PANICS like the reference's assert_eq! (mod.rs:96-102): std::runtime_error;
 //   - the WHOLE file is deserialized and returned; max_degree plays no other role (mod.rs:106).
+// check = true (no counterpart in the reference, which stops at the digest): the loaded powers are audited on the device
+// against the blob's own open key (capgpu_srs_check, seed from the OS); a faulty point or powers that are no sequence
+// [tau^i] g under beta_h give Err(FailedSnark) naming the fault.  The default leaves loading as it was.
 inline Result<UniversalSrs> load_srs(size_t max_degree, const std::vector<uint8_t>& bytes,
-                                     const std::array<uint8_t, 32>& expected_sha256 = aztec_crs_sha256()) {
+                                     const std::array<uint8_t, 32>& expected_sha256 = aztec_crs_sha256(),
+                                     bool check = false) {
   if (max_degree > ((size_t)1 << 17))
     return TxnApiError::failed_snark("Currently only supports 2^17. Please update Aztec's CRS data file if needed.");
   if (sha256(bytes.data(), bytes.size()) != expected_sha256)
@@ -259,6 +263,17 @@ inline Result<UniversalSrs> load_srs(size_t max_degree, const std::vector<uint8_
   rc = capgpu_srs_deserialize(bytes.data(), bytes.size(), 0, &h, s.h.data(), s.beta_h.data(), &used);
   if (rc != CAPGPU_OK) return detail::map_error(rc, "Failed to load SRS");
   s.powers_of_g = std::make_shared<detail::SrsHandle>(h);
+  if (check) {
+    capgpu_srs_report rep;
+    rc = capgpu_srs_check(h, s.h.data(), s.beta_h.data(), nullptr, CAPGPU_SRS_CHECK_LOCATE, &rep);
+    if (rc != CAPGPU_OK) return detail::map_error(rc, "Failed to load SRS");
+    if (rep.verdict == 1)
+      return TxnApiError::failed_snark("Failed to load SRS: point " + std::to_string(rep.first_bad_point) +
+                                       (rep.point_fault == 1 ? " is the point at infinity" : " is not on the curve"));
+    if (rep.verdict == 2)
+      return TxnApiError::failed_snark("Failed to load SRS: not a power sequence under the open key; first bad link: " +
+                                       std::to_string(rep.first_bad_link));
+  }
   capgpu_srs_size(h, &n);
   s.max_degree = n ? n - 1 : 0;
   return s;
