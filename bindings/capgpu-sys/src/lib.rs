@@ -89,6 +89,28 @@ pub struct capgpu_witness_fault {
     pub copies_failed: u64,
 }
 
+/// `capgpu_solver_info`: the figures of a key's witness-solver schedule (48 bytes); all zero: the key has no solver.
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug, PartialEq, Eq)]
+pub struct capgpu_solver_info {
+    pub num_given: u64,
+    pub num_defined: u64,
+    pub levels: u64,
+    pub widest_level: u64,
+    pub inv_rows: u64,
+    pub root_rows: u64,
+}
+
+/// `capgpu_solve_status`: the verdict of the witness solver for one witness (16 bytes).  `kind`: 0 solved, 1 the
+/// denominator of `row` - the lowest such row - is zero (its variable is 0).
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug, PartialEq, Eq)]
+pub struct capgpu_solve_status {
+    pub kind: u32,
+    pub reserved: u32,
+    pub row: u64,
+}
+
 /// `capgpu_prove_outcome`: the verdict of one proof of a `capgpu_plonk_prove_each*` call (56 bytes).  `status` is
 /// `CAPGPU_ERR_PROOF` exactly when `degree_flags != 0 || fault.kind != 0`; the record of such a proof is all-ones words.
 #[repr(C)]
@@ -237,6 +259,13 @@ extern "C" {
                                         pk_handle_out: *mut u64, vk_out: *mut capgpu_verifying_key) -> c_int;
     pub fn capgpu_plonk_key_set_vars(pk_handle: u64, wire_vars: *const u32, num_vars: usize) -> c_int;
     pub fn capgpu_plonk_key_num_vars(pk_handle: u64, num_vars_out: *mut usize) -> c_int;
+    pub fn capgpu_plonk_key_set_given(pk_handle: u64, given_vars: *const u32, num_given: usize,
+                                      info_out: *mut capgpu_solver_info) -> c_int;
+    pub fn capgpu_plonk_key_solver_info(pk_handle: u64, info_out: *mut capgpu_solver_info) -> c_int;
+    pub fn capgpu_plonk_solve_vars(pk_handle: u64, count: c_int, given: *const u64, vars_out: *mut u64,
+                                   status_out: *mut capgpu_solve_status) -> c_int;
+    pub fn capgpu_plonk_solve_vars_dev(pk_handle: u64, count: c_int, d_given: *const c_void, d_vars_out: *mut c_void,
+                                       status_out: *mut capgpu_solve_status) -> c_int;
     pub fn capgpu_plonk_input_stats(witness_bytes_h2d_out: *mut u64, gather_launches_out: *mut u64) -> c_int;
     pub fn capgpu_plonk_free_key(pk_handle: u64) -> c_int;
     pub fn capgpu_plonk_key_info(pk_handle: u64, domain_size_out: *mut usize, num_inputs_out: *mut usize,
@@ -671,6 +700,36 @@ impl ProvingKey {
         let mut nv = 0usize;
         check(unsafe { capgpu_plonk_key_num_vars(self.handle, &mut nv) })?;
         Ok(nv)
+    }
+    /// Names the variables the caller supplies (inputs, the constants 0 and 1, every hinted bit - not fifth roots); the
+    /// key derives the schedule by which `solve` computes all the others.  Refused, naming the lowest offending row, when
+    /// the circuit does not follow from the list by the rule of capgpu.h.
+    pub fn set_given(&self, given_vars: &[u32]) -> Result<capgpu_solver_info> {
+        let mut info = capgpu_solver_info::default();
+        check(unsafe { capgpu_plonk_key_set_given(self.handle, given_vars.as_ptr(), given_vars.len(), &mut info) })?;
+        Ok(info)
+    }
+    /// The schedule's figures; all zero: the key has no solver.
+    pub fn solver_info(&self) -> Result<capgpu_solver_info> {
+        let mut info = capgpu_solver_info::default();
+        check(unsafe { capgpu_plonk_key_solver_info(self.handle, &mut info) })?;
+        Ok(info)
+    }
+    /// Completes `given.len() / num_given` assignments on the device: `given` holds, per witness, the values of the
+    /// given variables in the order of `set_given`'s list.  Returns the assignments (num_vars values each, ready for
+    /// `prove_vars`) and one verdict per witness; `Ok` whenever the solve ran.
+    pub fn solve(&self, given: &[[u64; 4]]) -> Result<(Vec<[u64; 4]>, Vec<capgpu_solve_status>)> {
+        let per = self.solver_info()?.num_given as usize;
+        let nv = self.num_vars()?;
+        assert!(per > 0 && given.len() % per == 0);
+        let count = given.len() / per;
+        let mut vars = vec![[0u64; 4]; count * nv];
+        let mut status = vec![capgpu_solve_status::default(); count];
+        check(unsafe {
+            capgpu_plonk_solve_vars(self.handle, count as c_int, given.as_ptr() as *const u64, vars.as_mut_ptr() as *mut u64,
+                                    status.as_mut_ptr())
+        })?;
+        Ok((vars, status))
     }
     /// The same proof from the circuit's variable assignment (`CAPGPU_INPUT_VARS`): `witness` = `circuit.witness`, one
     /// value per variable - an eighth of the bytes of the five columns for a CAP transfer; the columns are gathered on

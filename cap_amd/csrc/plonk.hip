@@ -41,6 +41,7 @@
 #include "launch.hpp"
 #include "params.hpp"
 #include "plonk_kernels.hpp"
+#include "solve.hpp"
 #include "tickets.hpp"
 #include "transcript_dev.hpp"
 #include "vars_kernels.hpp"
@@ -48,6 +49,15 @@
 namespace cap {
 
 using namespace pk;
+
+// The witness solver's schedule (capgpu_plonk_key_set_given): the host copy, shared by a key and its replicas; every
+// ProvingKey object uploads its own device copy on first use (solve_tables).
+struct SolveSched {
+  uint64_t uid = 0;  // never reused: tells a key's device copy which schedule it holds
+  sp::Plan plan;
+  std::vector<fe> konst;  // per row of plan.rows: 1 / q_o or 1 / q_hash_i, internal form, canonical
+  capgpu_solver_info info{};
+};
 
 struct ProvingKey {
   size_t n = 0, m = 0, ps = 0;  // domain, quotient domain, polynomial stride (n + 8)
@@ -84,12 +94,18 @@ struct ProvingKey {
   // with a table has chk_perm from the start - the permutation's index form is what the table was turned into.
   mutable uint32_t* wire_vars = nullptr;
   mutable size_t num_vars = 0;
+  // The solver's schedule (null: none) and this object's device copy of it, one allocation, made under chk_mu by the first
+  // solve that finds solve_dev_uid != solve->uid.  Set, replaced and dropped like the table (not beside calls that use the key).
+  mutable std::shared_ptr<const SolveSched> solve;
+  mutable void* solve_dev = nullptr;
+  mutable uint64_t solve_dev_uid = 0;
+  mutable SolveTables solve_tab{};
   ProvingKey() = default;
   ProvingKey(const ProvingKey&) = delete;
   ProvingKey& operator=(const ProvingKey&) = delete;
   ~ProvingKey() {
     for (void* p : {(void*)coef, (void*)sig_eval, (void*)pk_coset, (void*)inv_nx1, (void*)chk_sel, (void*)chk_perm,
-                    (void*)wire_vars})
+                    (void*)wire_vars, solve_dev})
       if (p) hipFree(p);
   }
 };
@@ -1023,6 +1039,7 @@ int clone_key_to_current(const ProvingKey& src, int src_device, std::shared_ptr<
       CAP_HIP(copy_between(K->wire_vars, c.device, src.wire_vars, src_device, bytes, c.stream));
       CAP_HIP(copy_between(K->chk_perm, c.device, src.chk_perm, src_device, bytes, c.stream));
       K->num_vars = src.num_vars;
+      K->solve = src.solve;  // the host copy; the replica uploads its own tables on its first solve
     }
   }
   CAP_HIP(hipStreamSynchronize(c.stream));
@@ -1586,6 +1603,7 @@ int capgpu_plonk_key_set_vars(uint64_t pk_handle, const uint32_t* wire_vars, siz
     replaced = K->wire_vars;
     K->wire_vars = table.p;
     K->num_vars = num_vars;
+    K->solve.reset();  // the solver's schedule was derived from the table that leaves
     table.p = nullptr;
   }
   // replicas on other devices were cloned without the table (or with the old one): they are made again on next use
@@ -1603,6 +1621,276 @@ int capgpu_plonk_key_set_vars(uint64_t pk_handle, const uint32_t* wire_vars, siz
     (void)hipFree(replaced);
   }
   return CAPGPU_OK;
+}
+
+// ---- the witness solver (solve_plan.hpp, solve29.hpp, solve_kernels.hpp) ----------------------------------------------
+namespace {
+
+const sv29::Exps* solve_exps() {
+  static const struct Derived {
+    sv29::Exps ex;
+    bool ok;
+    Derived() { ok = sv29::derive_exps(&ex); }
+  } d;
+  return d.ok ? &d.ex : nullptr;
+}
+
+// 1 / x for every x of v (internal form, none zero), in place: one inversion and three products per element
+void solve_batch_inverse(std::vector<fl>& v) {
+  if (v.empty()) return;
+  std::vector<fl> pre(v.size());
+  fl acc = Fr29::one();
+  for (size_t i = 0; i < v.size(); i++) {
+    pre[i] = acc;
+    acc = Fr29::mul(acc, v[i]);
+  }
+  acc = Fr29::inv(acc);
+  for (size_t i = v.size(); i-- > 0;) {
+    const fl x = v[i];
+    v[i] = Fr29::mul(acc, pre[i]);
+    acc = Fr29::mul(acc, x);
+  }
+}
+
+// The device copy of K's schedule on K's device (the current one), uploaded on the first solve after a set_given.
+int solve_tables(const ProvingKey& K, SolveTables* tab, std::shared_ptr<const SolveSched>* hold) {
+  std::lock_guard<std::mutex> lk(K.chk_mu);
+  if (!K.solve || !K.wire_vars) {
+    set_error("capgpu_plonk_solve_vars: the key has no solver (capgpu_plonk_key_set_given gives it one)");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  const SolveSched& S = *K.solve;
+  *hold = K.solve;
+  if (K.solve_dev_uid != S.uid) {
+    if (K.solve_dev) {
+      CAP_HIP(hipFree(K.solve_dev));  // (waits for the device: a launch may still read the tables that leave)
+      K.solve_dev = nullptr;
+      K.solve_dev_uid = 0;
+    }
+    const size_t nrows = S.plan.rows.size();
+    int32_t* slot = nullptr;
+    sp::Row* rows = nullptr;
+    fe* konst = nullptr;
+    uint32_t* off = nullptr;
+    auto carve_tables = [&](void* at) {
+      Carver k(at);
+      slot = k.take<int32_t>(S.plan.slot.size());
+      rows = k.take<sp::Row>(nrows ? nrows : 1);
+      konst = k.take<fe>(nrows ? nrows : 1);
+      off = k.take<uint32_t>(S.plan.level_off.size());
+      return k.off + 256;
+    };
+    DevTmp<char> own;
+    CAP_HIP(own.alloc(carve_tables(nullptr)));
+    (void)carve_tables(own.p);
+    CAP_HIP(hipMemcpy(slot, S.plan.slot.data(), sizeof(int32_t) * S.plan.slot.size(), hipMemcpyHostToDevice));
+    if (nrows) {
+      CAP_HIP(hipMemcpy(rows, S.plan.rows.data(), sizeof(sp::Row) * nrows, hipMemcpyHostToDevice));
+      CAP_HIP(hipMemcpy(konst, S.konst.data(), sizeof(fe) * nrows, hipMemcpyHostToDevice));
+    }
+    CAP_HIP(hipMemcpy(off, S.plan.level_off.data(), sizeof(uint32_t) * S.plan.level_off.size(), hipMemcpyHostToDevice));
+    SolveTables t{};
+    t.slot = slot;
+    t.rows = rows;
+    t.konst = konst;
+    t.level_off = off;
+    t.levels = (uint32_t)S.plan.levels;
+    t.num_given = S.plan.num_given;
+    K.solve_tab = t;
+    K.solve_dev = own.p;
+    K.solve_dev_uid = S.uid;
+    own.p = nullptr;
+  }
+  *tab = K.solve_tab;
+  tab->wire_vars = K.wire_vars;
+  tab->sel = K.chk_sel;
+  tab->n = K.n;
+  tab->num_vars = K.num_vars;
+  return CAPGPU_OK;
+}
+
+// `count` witnesses on the current context: given values and the result in host memory (h_*) or resident (d_*)
+int solve_run(uint64_t pk_handle, uint32_t count, const uint64_t* h_given, uint64_t* h_vars, const void* d_given,
+              void* d_vars, capgpu_solve_status* status_out) {
+  Context& c = ctx();
+  Entry lk(c);
+  std::shared_ptr<ProvingKey> K;
+  int rc = lookup_key(pk_handle, &K);
+  if (rc) return rc;
+  const sv29::Exps* ex = solve_exps();
+  if (!ex) {
+    set_error("capgpu_plonk_solve_vars: (r - 1) mod 5 != 1: the scalar field has no fifth-root exponent");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  {
+    std::lock_guard<std::mutex> klk(K->chk_mu);
+    if (!K->solve || !K->wire_vars) {
+      set_error("capgpu_plonk_solve_vars: the key has no solver (capgpu_plonk_key_set_given gives it one)");
+      return CAPGPU_ERR_INVALID_ARG;
+    }
+  }
+  if ((rc = key_check_tables(*K))) return rc;  // the selector values on the domain (derived once per key)
+  SolveTables tab;
+  std::shared_ptr<const SolveSched> hold;
+  if ((rc = solve_tables(*K, &tab, &hold))) return rc;
+  hipStream_t s = c.stream;
+  const size_t given_elems = (size_t)count * tab.num_given, var_elems = (size_t)count * tab.num_vars;
+  unsigned long long* d_st = nullptr;
+  fe *g = nullptr, *v = nullptr;
+  auto carve_call = [&](void* at) {
+    Carver k(at);
+    d_st = k.take<unsigned long long>(count);
+    if (h_given) g = k.take<fe>(given_elems ? given_elems : 1);
+    if (h_vars) v = k.take<fe>(var_elems);
+    return k.off + 256;
+  };
+  if ((rc = scratch_reserve(c.stage_b, carve_call(nullptr)))) return rc;
+  (void)carve_call(c.stage_b.p);
+  if (h_given) {
+    if (given_elems) CAP_HIP(hipMemcpyAsync(g, h_given, sizeof(fe) * given_elems, hipMemcpyHostToDevice, s));
+    d_given = g;
+  }
+  if (h_vars) d_vars = v;
+  CAP_HIP(hipMemsetAsync(d_st, 0xff, sizeof(unsigned long long) * count, s));
+  solve_launch(s, count, (const fe*)d_given, tab, *ex, (fe*)d_vars, d_st);
+  std::vector<unsigned long long> h_st(count);
+  CAP_HIP(hipMemcpyAsync(h_st.data(), d_st, sizeof(unsigned long long) * count, hipMemcpyDeviceToHost, s));
+  if (h_vars) CAP_HIP(hipMemcpyAsync(h_vars, d_vars, sizeof(fe) * var_elems, hipMemcpyDeviceToHost, s));
+  CAP_HIP(hipStreamSynchronize(s));
+  if ((rc = take_launch_error())) return rc;
+  for (uint32_t p = 0; p < count; p++) {
+    capgpu_solve_status& o = status_out[p];
+    memset(&o, 0, sizeof o);
+    if (h_st[p] != kSolved) {
+      o.kind = 1;
+      o.row = h_st[p];
+    }
+  }
+  return CAPGPU_OK;
+}
+
+}  // namespace
+
+int capgpu_plonk_key_set_given(uint64_t pk_handle, const uint32_t* given_vars, size_t num_given,
+                               capgpu_solver_info* info_out) {
+  if (!given_vars && num_given) {
+    set_error("capgpu_plonk_key_set_given: bad argument (given_vars is NULL)");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  CAP_CHECK_INIT();
+  std::shared_ptr<ProvingKey> K;
+  int rc = home_key(pk_handle, &K);
+  if (rc) return rc;
+  if (!K->wire_vars) {
+    set_error("capgpu_plonk_key_set_given: the key has no wire -> variable table (capgpu_plonk_preprocess_vars makes a key "
+              "with one, capgpu_plonk_key_set_vars gives it one); the key is unchanged");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  if (!solve_exps()) {
+    set_error("capgpu_plonk_key_set_given: (r - 1) mod 5 != 1: the scalar field has no fifth-root exponent");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  Runtime& R = rt();
+  Context* home = nullptr;
+  for (auto& cp : R.ctxs)
+    if (cp->device == K->device) {
+      home = cp.get();
+      break;
+    }
+  if (!home) {
+    set_error("capgpu_plonk_key_set_given: no context on the key's device %d", K->device);
+    return CAPGPU_ERR_BAD_HANDLE;
+  }
+  auto S = std::make_shared<SolveSched>();
+  {
+    ScopedCtx sc(*home);
+    Entry lk(*home);
+    hipStream_t s = home->stream;
+    const size_t n = K->n, cells = (size_t)NW * n, num_vars = K->num_vars;
+    if ((rc = key_check_tables(*K))) return rc;
+    // the table and the selector values, read back once (0.66 MB and 13.6 MB at n = 2^15)
+    std::vector<uint32_t> table(cells);
+    std::vector<fe> sel((size_t)NS * n);
+    CAP_HIP(hipMemcpyAsync(table.data(), K->wire_vars, sizeof(uint32_t) * cells, hipMemcpyDeviceToHost, s));
+    CAP_HIP(hipMemcpyAsync(sel.data(), K->chk_sel, sizeof(fe) * NS * n, hipMemcpyDeviceToHost, s));
+    CAP_HIP(hipStreamSynchronize(s));
+    std::vector<uint8_t> sel_zero((size_t)NS * n);
+    for (size_t i = 0; i < sel.size(); i++) sel_zero[i] = Fr29::is_zero(Fr29::load(sel[i])) ? 1 : 0;
+    if (!sp::solve_plan(n, K->num_inputs, num_vars, table.data(), sel_zero.data(), given_vars, num_given, &S->plan)) {
+      set_error("capgpu_plonk_key_set_given: %s; the key is unchanged", S->plan.error.c_str());
+      return CAPGPU_ERR_INVALID_ARG;
+    }
+    const sp::Plan& P = S->plan;
+    std::vector<fl> inv;
+    std::vector<size_t> where;
+    for (size_t k = 0; k < P.rows.size(); k++) {
+      const uint32_t kind = sp::row_kind(P.rows[k]);
+      if (kind == sp::OUT_INV) continue;
+      const int which = kind == sp::OUT_MUL ? sp::Q_O : sp::Q_HASH + (int)sp::row_wire(P.rows[k]);
+      inv.push_back(Fr29::load(sel[(size_t)which * n + P.rows[k].row]));
+      where.push_back(k);
+    }
+    solve_batch_inverse(inv);
+    S->konst.assign(P.rows.size(), Fr29::pack(Fr29::zero()));
+    for (size_t i = 0; i < inv.size(); i++) S->konst[where[i]] = Fr29::pack(Fr29::canonical(inv[i]));
+    static std::atomic<uint64_t> next_uid{1};
+    S->uid = next_uid.fetch_add(1);
+    S->info = capgpu_solver_info{P.num_given, P.num_defined, P.levels, P.widest_level, P.inv_rows, P.root_rows};
+  }
+  // the key and the replicas other devices hold take the schedule; each uploads its tables on its next solve
+  for (auto& cp : R.ctxs) {
+    Context& c = *cp;
+    ScopedCtx sc(c);
+    Entry lk(c);
+    auto it = c.keys.find(pk_handle);
+    ProvingKey* k = it == c.keys.end() ? (cp.get() == home ? K.get() : nullptr) : it->second.get();
+    if (!k) continue;
+    std::lock_guard<std::mutex> klk(k->chk_mu);
+    k->solve = S;
+  }
+  {
+    std::lock_guard<std::mutex> klk(K->chk_mu);
+    K->solve = S;
+  }
+  if (info_out) *info_out = S->info;
+  return CAPGPU_OK;
+}
+
+int capgpu_plonk_key_solver_info(uint64_t pk_handle, capgpu_solver_info* info_out) {
+  if (!info_out) {
+    set_error("capgpu_plonk_key_solver_info: bad argument (info_out is NULL)");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  CAP_CHECK_INIT();
+  std::shared_ptr<ProvingKey> K;
+  int rc = home_key(pk_handle, &K);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> klk(K->chk_mu);
+  memset(info_out, 0, sizeof *info_out);
+  if (K->solve && K->wire_vars) *info_out = K->solve->info;
+  return CAPGPU_OK;
+}
+
+int capgpu_plonk_solve_vars(uint64_t pk_handle, int count, const uint64_t* given, uint64_t* vars_out,
+                            capgpu_solve_status* status_out) {
+  if (count < 0 || (count && (!given || !vars_out || !status_out))) {
+    set_error("capgpu_plonk_solve_vars: bad argument");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  CAP_CHECK_INIT();
+  if (count == 0) return CAPGPU_OK;
+  return solve_run(pk_handle, (uint32_t)count, given, vars_out, nullptr, nullptr, status_out);
+}
+
+int capgpu_plonk_solve_vars_dev(uint64_t pk_handle, int count, const void* d_given, void* d_vars_out,
+                                capgpu_solve_status* status_out) {
+  if (count < 0 || (count && (!d_given || !d_vars_out || !status_out))) {
+    set_error("capgpu_plonk_solve_vars: bad argument");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  CAP_CHECK_INIT();
+  if (count == 0) return CAPGPU_OK;
+  return solve_run(pk_handle, (uint32_t)count, nullptr, nullptr, d_given, d_vars_out, status_out);
 }
 
 int capgpu_plonk_free_key(uint64_t pk_handle) {

@@ -1,0 +1,33 @@
+// What the witness solver's host code (plonk.hip) and its kernel (solve_kernels.hpp, compiled in solve.hip) share: the
+// schedule as the kernel reads it, and the launch.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "field.hpp"
+#include "solve29.hpp"
+#include "solve_plan.hpp"
+
+namespace cap {
+namespace pk {
+
+constexpr unsigned long long kSolved = ~0ull;
+constexpr int kSolveThreads = 256;  // one workgroup per witness
+
+// the schedule as the kernel reads it (all device pointers, owned by the key)
+struct SolveTables {
+  const int32_t* slot;        // [num_vars]: index into a witness's given values, -1: not given
+  const sp::Row* rows;        // defining rows by (level, kind, row)
+  const fe* konst;            // per row: 1 / q_o or 1 / q_hash_i, internal form, canonical
+  const uint32_t* level_off;  // [levels + 1]
+  const uint32_t* wire_vars;  // [5][n] the key's table
+  const fe* sel;              // [13][n] selector values, internal form, canonical
+  uint32_t levels, pad;
+  size_t n, num_vars, num_given;
+};
+
+// k_solve_vars for `count` witnesses on stream s (through launch(): timed by the profiler, launch errors latched)
+void solve_launch(hipStream_t s, uint32_t count, const fe* d_given, const SolveTables& t, const sv29::Exps& ex, fe* d_vars,
+                  unsigned long long* d_status);
+
+}  // namespace pk
+}  // namespace cap

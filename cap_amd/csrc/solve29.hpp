@@ -1,0 +1,145 @@
+// The witness solver's row rule on the lazy 29-bit field: the value a defining row gives its variable.  Host + device,
+// like gatecheck29.hpp: tests/cpp/solve_plan_check.cpp builds this header for the host with field29.hpp's bound
+// assertions on and checks every solved row with wc29::Check::gate.
+//
+//   rest    = q_c + sum_i q_lc_i w_i + q_mul_0 w0 w1 + q_mul_1 w2 w3 + sum_i q_hash_i w_i^5      (wires 0 .. 3)
+//   OUT     w4  = rest / (q_o - q_ecc w0 w1 w2 w3)     q_ecc = 0: times the row's constant 1 / q_o; else one inversion
+//   ROOT5   w_i = ((q_o w4 - rest|w_i = 0) / q_hash_i)^e,  e = 5^-1 mod (r - 1)   (the plan admits the row only when
+//           q_lc_i, the q_mul of i's pair and q_ecc are zero, so clearing w_i removes exactly the q_hash_i w_i^5 term)
+// Values in the internal Montgomery form (x * 2^261), normalized.  Both exponentiations - r - 2 and e - walk the bits of
+// a PUBLIC exponent: 254 squarings and one product per set bit whatever the base is; a base of 0 comes out as 0.  No
+// step depends on a witness value except the zero test of an inverted denominator (Fl::is_zero), whose outcome is
+// reported anyway.
+#pragma once
+#include "gatecheck29.hpp"
+
+namespace cap {
+namespace sv29 {
+
+constexpr int kExpBits = 254;  // both exponents are below r < 2^254
+
+// the two exponents, 8 x 32-bit words each, little endian
+struct Exps {
+  uint32_t inv[8];    // r - 2
+  uint32_t root5[8];  // 5^-1 mod (r - 1)
+};
+
+// Derived, not copied: r - 2 from the modulus, and e = (4 (r - 1) + 1) / 5 - since r - 1 = 1 (mod 5), 4 (r - 1) + 1 is a
+// multiple of 5 and 5 e = 1 (mod r - 1).  Returns false if (r - 1) mod 5 != 1 or the product check 5 e = 4 (r - 1) + 1 fails.
+inline bool derive_exps(Exps* out) {
+  uint32_t r[8];  // the modulus from its 29-bit limbs
+  {
+    fl m;
+    for (int i = 0; i < 9; i++) m.v[i] = FrP29::MOD[i];
+    const fe p = Fl<FrP29>::pack(m);
+    for (int i = 0; i < 8; i++) r[i] = p.v[i];
+  }
+  uint32_t m1[8];  // r - 1 (r is odd)
+  for (int i = 0; i < 8; i++) m1[i] = r[i];
+  m1[0] -= 1;
+  uint64_t rem = 0;
+  for (int i = 7; i >= 0; i--) rem = ((rem << 32) | m1[i]) % 5;
+  if (rem != 1) return false;
+  for (int i = 0; i < 8; i++) out->inv[i] = r[i];
+  out->inv[0] -= 2;  // the low word of r is 0xf0000001
+  uint32_t t[9];  // 4 (r - 1) + 1
+  uint64_t c = 1;
+  for (int i = 0; i < 8; i++) {
+    c += (uint64_t)m1[i] * 4;
+    t[i] = (uint32_t)c;
+    c >>= 32;
+  }
+  t[8] = (uint32_t)c;
+  rem = 0;
+  uint32_t q[9];
+  for (int i = 8; i >= 0; i--) {
+    const uint64_t cur = (rem << 32) | t[i];
+    q[i] = (uint32_t)(cur / 5);
+    rem = cur % 5;
+  }
+  if (rem != 0 || q[8] != 0) return false;
+  c = 0;
+  for (int i = 0; i < 8; i++) {  // 5 e == 4 (r - 1) + 1
+    c += (uint64_t)q[i] * 5;
+    if ((uint32_t)c != t[i]) return false;
+    c >>= 32;
+  }
+  if ((uint32_t)c != t[8]) return false;
+  for (int i = 0; i < 8; i++) out->root5[i] = q[i];
+  return true;
+}
+
+template <int SCHED = CAP_FL_SCHED>
+struct Solve {
+  using F = Fl<FrP29, SCHED>;
+
+  // a^e for the public exponent e (8 words): left-to-right, every bit of the 254 a squaring, every set bit a product
+  // (word(w): word w of the exponent; the words are walked with a compile-time index so that an exponent held in kernel
+  // arguments stays in scalar registers)
+  static CAP_HD fl pow_fixed(const fl& a, const uint32_t* e) {
+    return pow_words(a, [&](int w) { return e[w]; });
+  }
+  template <class Word>
+  static CAP_HD fl pow_words(const fl& a, Word word) {
+    fl r = F::one();
+#pragma unroll
+    for (int w = 7; w >= 0; w--) {
+      const uint32_t ew = word(w);
+#pragma unroll 1
+      for (int b = (w == 7 ? kExpBits - 1 - 224 : 31); b >= 0; b--) {
+        r = F::sqr(r);
+        if ((ew >> b) & 1) r = F::mul(r, a);
+      }
+    }
+    return r;
+  }
+
+  // rest of the row from wires 0 .. 3 (normalized, below 8 r); *w0123 = w0 w1 w2 w3.  q(s) fetches selector s where it
+  // is used, as in wc29::Check::gate, whose fused pairs these are.
+  template <class Sel>
+  static CAP_HD fl rest(Sel q, const fl* w, fl* w0123) {
+    // every product is < 1.1 r and normalized; the running sum is carried after at most four addends (limbs < 2^31)
+    fl acc = F::add(q(wc29::Q_C), F::mul_add_mul(q(wc29::Q_LC), w[0], q(wc29::Q_LC + 1), w[1]));
+    acc = F::normalize(F::add(acc, F::mul_add_mul(q(wc29::Q_LC + 2), w[2], q(wc29::Q_LC + 3), w[3])));
+    {
+      const fl w01 = F::mul(w[0], w[1]), w23 = F::mul(w[2], w[3]);
+      acc = F::add_norm(acc, F::mul_add_mul(q(wc29::Q_MUL), w01, q(wc29::Q_MUL + 1), w23));
+      *w0123 = F::mul(w01, w23);
+    }
+#pragma unroll 1
+    for (int i = 0; i < 4; i += 2) {
+      // (selected, not indexed: a run-time index would put the wires into scratch memory on the device)
+      const fl wa = i ? w[2] : w[0], wb = i ? w[3] : w[1];
+      const fl a5 = F::mul(F::sqr(F::sqr(wa)), wa), b5 = F::mul(F::sqr(F::sqr(wb)), wb);
+      acc = F::add_norm(acc, F::mul_add_mul(q(wc29::Q_HASH + i), a5, q(wc29::Q_HASH + i + 1), b5));
+    }
+    return acc;
+  }
+
+  // The value of the row's variable.  kind / wire: sp::Kind and the target wire of the plan; w: the five wire values, the
+  // target's cell holding anything; konst: the row's constant (1 / q_o for OUT_MUL, 1 / q_hash_wire for ROOT5; unused for
+  // OUT_INV).  *zero_den: an OUT_INV row whose denominator is 0 mod r - its value is then 0.
+  template <class Sel>
+  static CAP_HD fl row_value(Sel q, uint32_t kind, uint32_t wire, const fl* w_in, const fl& konst, const Exps& ex,
+                             bool* zero_den) {
+    fl w[wc29::kWires];
+#pragma unroll
+    for (int i = 0; i < wc29::kWires; i++) w[i] = (kind == 2 && wire == (uint32_t)i) ? F::zero() : w_in[i];
+    fl w0123;
+    const fl r = rest(q, w, &w0123);
+    *zero_den = false;
+    if (kind == 0) return F::mul(r, konst);
+    fl base;
+    if (kind == 1) {
+      base = F::sub(q(wc29::Q_O), F::mul(q(wc29::Q_ECC), w0123));
+      *zero_den = F::is_zero(base);
+    } else {
+      base = F::mul(F::sub(F::mul(q(wc29::Q_O), w[4]), r), konst);
+    }
+    const fl p = pow_words(base, [&](int w) { return kind == 1 ? ex.inv[w] : ex.root5[w]; });
+    return kind == 1 ? F::mul(r, p) : p;
+  }
+};
+
+}  // namespace sv29
+}  // namespace cap

@@ -1,0 +1,69 @@
+// Kernel of the witness solver (capgpu_plonk_solve_vars*): completes `count` variable assignments from their given values
+// through the schedule a key got from capgpu_plonk_key_set_given (the plan: solve_plan.hpp, the row rule: solve29.hpp).
+//   k_solve_vars   one workgroup of 256 lanes per witness.  The given values are scattered into the witness's row of
+//                  vars_out and every other variable is zeroed; then the levels are walked in order, the lanes striding
+//                  over a level's rows, one __syncthreads() between levels.
+// A value written at level l is read by other wavefronts of the same workgroup at level l + 1 through vars_out in global
+// memory, behind the barrier: vars_out is therefore neither `const` nor `__restrict__` here and never read through a
+// read-only path.  The tables (selector values, wire -> variable ids, rows, constants) are read-only for the launch.
+// A row whose denominator is 0 mod r leaves its variable 0 and enters its row number into the witness's status word by
+// atomicMin (preset to all ones): the smallest such row, whatever order the lanes arrive in.
+// Rows of a level are ordered by kind, so a wavefront pays the fixed exponentiation (254 squarings) only where its 64
+// rows hold an OUT row with q_ecc or a fifth root.
+// Compiled in solve.hip, a translation unit of its own: the prover's kernels in plonk.hip keep the code they had.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "solve.hpp"
+#include "solve29.hpp"
+
+namespace cap {
+namespace pk {
+
+__global__ __launch_bounds__(kSolveThreads) void k_solve_vars(const fe* __restrict__ given /*[count][num_given]*/, SolveTables t,
+                                                         sv29::Exps ex, fe* vars_out /*[count][num_vars]*/,
+                                                         unsigned long long* __restrict__ status /*[count]*/) {
+  using S = sv29::Solve<>;
+  using F = S::F;
+  const size_t p = blockIdx.x;
+  fe* vars = vars_out + p * t.num_vars;
+  const fe* giv = given + p * t.num_given;
+  for (size_t v = threadIdx.x; v < t.num_vars; v += kSolveThreads) {
+    const int32_t s = t.slot[v];
+    fe x;
+#pragma unroll
+    for (int i = 0; i < 8; i++) x.v[i] = 0;
+    if (s >= 0) x = giv[s];
+    vars[v] = x;
+  }
+  __syncthreads();
+#pragma unroll 1
+  for (uint32_t l = 0; l < t.levels; l++) {
+    const uint32_t end = t.level_off[l + 1];
+#pragma unroll 1
+    for (uint32_t k = t.level_off[l] + threadIdx.x; k < end; k += kSolveThreads) {
+      const sp::Row r = t.rows[k];
+      const uint32_t kind = r.kw & 0xffu, wire = r.kw >> 8;
+      const size_t j = r.row;
+      fl w[wc29::kWires];
+      uint32_t target = 0;
+#pragma unroll
+      for (int i = 0; i < wc29::kWires; i++) {
+        const uint32_t id = t.wire_vars[(size_t)i * t.n + j];  // (below num_vars: checked when the key took the table)
+        if (wire == (uint32_t)i) target = id;
+        w[i] = F::from_ext(vars[id]);
+      }
+      const fe* sel = t.sel + j;
+      const size_t n = t.n;
+      bool zero_den;
+      const fl val = S::row_value([&](int s) { return F::load(sel[(size_t)s * n]); }, kind, wire, w, F::load(t.konst[k]), ex,
+                                  &zero_den);
+      if (zero_den) atomicMin(&status[p], (unsigned long long)j);
+      vars[target] = F::to_ext(val);
+    }
+    __syncthreads();
+  }
+}
+
+}  // namespace pk
+}  // namespace cap

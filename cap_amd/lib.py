@@ -711,6 +711,72 @@ def plonk_key_num_vars(pk_handle: int) -> int:
     return nv.value
 
 
+class SolverInfo(ctypes.Structure):
+    """capgpu_solver_info (include/capgpu.h): the figures of a key's solver schedule; all zero: the key has none."""
+    _fields_ = [("num_given", ctypes.c_uint64), ("num_defined", ctypes.c_uint64), ("levels", ctypes.c_uint64),
+                ("widest_level", ctypes.c_uint64), ("inv_rows", ctypes.c_uint64), ("root_rows", ctypes.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class SolveStatus(ctypes.Structure):
+    """capgpu_solve_status: kind 0 solved, 1 the denominator of `row` (the lowest such row) is zero"""
+    _fields_ = [("kind", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("row", ctypes.c_uint64)]
+
+
+def plonk_key_set_given(pk_handle: int, given_vars) -> SolverInfo:
+    """capgpu_plonk_key_set_given: the ids of the variables a caller supplies; the key (one with a wire -> variable
+    table) derives the schedule by which capgpu_plonk_solve_vars computes every other variable.  Refused (-1), naming the
+    lowest offending row, when the circuit does not follow from the list by the rule of include/capgpu.h."""
+    g = np.asarray(given_vars)
+    if g.size and (g.min() < 0 or g.max() > 0xFFFFFFFF):
+        raise CapGpuError(-1, "given_vars ids must fit 32 bits")
+    g = np.ascontiguousarray(g, dtype=np.uint32).reshape(-1)
+    info = SolverInfo()
+    check(load().capgpu_plonk_key_set_given(ctypes.c_uint64(pk_handle), g.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                            ctypes.c_size_t(g.size), ctypes.byref(info)))
+    return info
+
+
+def plonk_key_solver_info(pk_handle: int) -> SolverInfo:
+    info = SolverInfo()
+    check(load().capgpu_plonk_key_solver_info(ctypes.c_uint64(pk_handle), ctypes.byref(info)))
+    return info
+
+
+def plonk_solve_vars(pk_handle: int, given, count: int = 1, out: "DevBuf | None" = None):
+    """capgpu_plonk_solve_vars[_dev]: completes `count` assignments from their given values.  given: (count, num_given, 4)
+    Montgomery words in the order of the key's given list - a numpy array, or a DevBuf of that content.
+    -> (vars, [SolveStatus] * count): vars is a (count, num_vars, 4) array for host input; for a DevBuf it is `out` (a
+    DevBuf of count * num_vars * 32 bytes, allocated here when None), ready for input_form='vars'."""
+    info, nv = plonk_key_solver_info(pk_handle), plonk_key_num_vars(pk_handle)
+    if info.num_given == 0 and info.num_defined == 0 and info.levels == 0:
+        raise CapGpuError(-1, "capgpu_plonk_solve_vars: the key has no solver (plonk_key_set_given gives it one)")
+    if count < 0:
+        raise CapGpuError(-1, f"count must be >= 0, got {count}")
+    status = (SolveStatus * max(count, 1))()
+    L = load()
+    if isinstance(given, DevBuf):
+        if given.nbytes != count * info.num_given * 32:
+            raise CapGpuError(-1, f"given holds {given.nbytes // 32} field elements, need count * {info.num_given}")
+        if out is None:
+            out = DevBuf(max(count * nv * 32, 32))
+        elif out.nbytes < count * nv * 32:
+            raise CapGpuError(-1, f"out holds {out.nbytes} bytes, need count * num_vars * 32 = {count * nv * 32}")
+        check(L.capgpu_plonk_solve_vars_dev(ctypes.c_uint64(pk_handle), count, given.ptr, out.ptr, status))
+        return out, list(status)[:count]
+    given = np.ascontiguousarray(given, dtype=np.uint64).reshape(-1)
+    if given.size != count * info.num_given * 4:
+        raise CapGpuError(-1, f"given holds {given.size / 4:g} field elements, need count * {info.num_given}")
+    if given.size == 0:
+        given = np.zeros(4, np.uint64)
+    vars_out = np.zeros((count, nv, 4), np.uint64)
+    check(L.capgpu_plonk_solve_vars(ctypes.c_uint64(pk_handle), count, _p(given), _p(vars_out.reshape(-1)) if count else None,
+                                    status))
+    return vars_out, list(status)[:count]
+
+
 def _cached_num_vars(pk_handle: int) -> int:
     nv = _num_vars_of.get(pk_handle)
     if nv is None:

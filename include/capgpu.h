@@ -449,6 +449,78 @@ int capgpu_plonk_preprocess_vars(uint64_t srs_handle, size_t n, size_t num_input
 int capgpu_plonk_key_set_vars(uint64_t pk_handle, const uint32_t* wire_vars, size_t num_vars);
 /* num_vars of the key's table: the length of a CAPGPU_INPUT_VARS witness; 0 when the key has no table */
 int capgpu_plonk_key_num_vars(uint64_t pk_handle, size_t* num_vars_out);
+
+/* ---- Completing a witness on the device (the witness solver) -----------------------------------------------------------
+ * A circuit's caller supplies a few thousand values - inputs, constants, hinted bits - and every other variable follows
+ * from a gate row.  A key with a wire -> variable table takes the list of GIVEN variable ids and derives, once, the
+ * schedule by which the rest is computed; capgpu_plonk_solve_vars* then completes whole batches of assignments on the
+ * device.  The result is exactly a CAPGPU_INPUT_VARS witness (canonical Montgomery words, num_vars per witness): it goes
+ * unchanged, and in place, into every entry point that takes that form, capgpu_plonk_check_witness* included.
+ *
+ * THE RULE.  V is the set of valued variables, at first the given ids.  The rows j = 0 .. n-1 are walked in ascending
+ * order; U = the distinct variables in the row's five cells that are not in V.  Selectors are the key's selector VALUES
+ * on the domain (the table the witness check derives); tests against zero are mod r.
+ *   |U| = 0                   the row is a constraint: it defines nothing and is not evaluated (checking stays with
+ *                             capgpu_plonk_check_witness*).
+ *   j < num_inputs, |U| > 0   refused: a public-input variable must be given.
+ *   |U| >= 2                  refused.
+ *   U = {u}:
+ *     OUT    u sits in wire 4 only, and q_o != 0 or q_ecc != 0:   w4 = rest / (q_o - q_ecc w0 w1 w2 w3),
+ *            rest = q_c + sum_i q_lc_i w_i + q_mul0 w0 w1 + q_mul1 w2 w3 + sum_i q_hash_i w_i^5   (i = 0 .. 3).
+ *            A row with q_ecc = 0 multiplies by 1 / q_o, computed once at set-up; a row with q_ecc != 0 inverts per
+ *            witness.
+ *     ROOT5  u sits in exactly one wire i < 4, with q_hash_i != 0, q_lc_i = 0, the q_mul selector of i's pair = 0 and
+ *            q_ecc = 0:   w_i = ((q_o w4 - rest without the q_hash_i term) / q_hash_i)^e,  e = 5^-1 mod (r - 1)
+ *            (it exists because (r - 1) mod 5 = 1; the library derives e and checks this).  This is Rescue's inverse
+ *            S-box gate as jf-relation lays it: the hinted root on an input wire, the known value on wire 4.
+ *     any other shape        refused.
+ *     Then u joins V.
+ * level(given) = 0; level(u) = 1 + the largest level among the other variables of u's row (for ROOT5 that includes wire
+ * 4's variable); the rows of one level are independent of each other.  Variables that occur in no cell and are not given
+ * come out as 0.
+ * Refusals are CAPGPU_ERR_INVALID_ARG at set-up, each naming the lowest offending row and the variable(s); so are a
+ * duplicate id in the list, an id at or beyond num_vars, and a key without a table.  The key then stays as it was.
+ * Per witness, an OUT row whose denominator is 0 mod r sets its variable to 0 and the witness's status becomes
+ * {kind 1, row = the LOWEST such row}; the other witnesses of the call are unaffected.
+ *
+ * TIMING.  Given values are secret.  Both exponentiations of this path - a^(r-2) for the inversion, a^e for the fifth
+ * root - walk the bits of a public exponent: 254 squarings and one product per set bit, whatever the base; no
+ * variable-time inversion is used per witness.  The constants 1 / q_o and 1 / q_hash_i are functions of the circuit
+ * alone.  Which rows run which chain is a property of the circuit, not of the witness.  The one data-dependent step is
+ * the zero test of an inverted denominator, whose outcome the status reports anyway.  (The paragraph at
+ * capgpu_plonk_set_wire_commit describes the prover itself.) */
+typedef struct capgpu_solver_info {
+  uint64_t num_given;    /* ids in the given list */
+  uint64_t num_defined;  /* variables defined by a row */
+  uint64_t levels;       /* dependency depth */
+  uint64_t widest_level; /* rows of the widest level */
+  uint64_t inv_rows;     /* OUT rows with q_ecc != 0: one inversion per witness each */
+  uint64_t root_rows;    /* ROOT5 rows */
+} capgpu_solver_info; /* 48 bytes */
+typedef struct capgpu_solve_status {
+  uint32_t kind; /* 0 solved, 1 zero denominator at `row` */
+  uint32_t reserved;
+  uint64_t row;
+} capgpu_solve_status; /* 16 bytes */
+/* Gives the key its list of given variables and derives the schedule (host pass over the table and the selector values,
+ * read back once; one 32-byte constant per defining row).  The schedule lives with the key: replicated to a context on
+ * first use like the key's table, replaced by a second call, dropped when capgpu_plonk_key_set_vars changes the table,
+ * freed by capgpu_plonk_free_key.  info_out may be NULL.  Not to be called while other calls use the key. */
+int capgpu_plonk_key_set_given(uint64_t pk_handle, const uint32_t* given_vars, size_t num_given,
+                               capgpu_solver_info* info_out);
+/* the schedule's figures; all zero: the key has no solver */
+int capgpu_plonk_key_solver_info(uint64_t pk_handle, capgpu_solver_info* info_out);
+/* Completes `count` assignments.  given: count x num_given field elements (Montgomery), per witness in the order of
+ * given_vars, copied to their variables as they are; vars_out: count x num_vars; status_out: count verdicts.  Returns
+ * CAPGPU_OK whenever the solve ran - verdicts are in status_out; count == 0 returns CAPGPU_OK and writes nothing.  The
+ * solver does not check constraints: a wrong given value yields a completed assignment that capgpu_plonk_check_witness*
+ * refuses.  Runs on the calling thread's context and stream (capgpu_set_stream is honoured); scratch comes from the
+ * context (capgpu_scratch_stats counts it).  The _dev form reads d_given and writes d_vars_out in device memory. */
+int capgpu_plonk_solve_vars(uint64_t pk_handle, int count, const uint64_t* given, uint64_t* vars_out,
+                            capgpu_solve_status* status_out);
+int capgpu_plonk_solve_vars_dev(uint64_t pk_handle, int count, const void* d_given, void* d_vars_out,
+                                capgpu_solve_status* status_out);
+
 int capgpu_plonk_free_key(uint64_t pk_handle);
 /* Shape of a resident proving key: the sizes every prove call's arrays must have (wires: count * 5 * domain_size
  * field elements, pub_inputs: count * num_inputs, blinders: count * 13) and the SRS it commits with.  Any out

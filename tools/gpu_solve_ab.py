@@ -1,0 +1,136 @@
+#!/usr/bin/env python3
+"""Measurements of the witness solver (capgpu_plonk_solve_vars_dev, kernel k_solve_vars) on cap_like_circuit("transfer_2x2"),
+n = 2^15: 2 425 given values per witness, 18 193 defined ones, 584 levels, 5 840 inversions.
+  (a) solve     capgpu_plonk_solve_vars_dev at 1, 256, 1024 and 4096 resident witnesses: wall time per call and the
+                kernel's own time (capgpu_profile_dump);
+  (b) cpu_fill  capwit_fill_many on 16 threads for 256 witnesses - the CPU figure.  The harness inverts on EVERY defining
+                row (18 193 inversions per witness where the solver inverts on 5 840 and multiplies by a constant on the
+                rest), so this arm flatters the device;
+  (c) solve_prove  solve + plonk_prove_batch_dev(vars) of 256 from resident given values, against
+      host_vars    plonk_prove_batch(vars) of 256 host-resident variable-form witnesses (context 0, like the other arm).
+Protocol: per arm 3 warm-up + 10 timed calls, the arms interleaved, three repetitions; the median of the three medians and
+their spread (max - min over the median).  One process, the library loaded first (no torch).  Writes the lines it prints to
+--out (default profiles/solve_vars.txt).   python tools/gpu_solve_ab.py [--out FILE] [--counts 1,256,1024,4096] [--steps 10]"""
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+from cap_amd import bench_utils as bu  # noqa: E402
+from cap_amd import lib as cg  # noqa: E402
+
+P, WARM, DISTINCT = 256, 3, 64
+
+
+def arg(name, default):
+    return sys.argv[sys.argv.index(name) + 1] if name in sys.argv else default
+
+
+def main():
+    steps = int(arg("--steps", 10))
+    counts = [int(c) for c in arg("--counts", "1,256,1024,4096").split(",")]
+    out_path = arg("--out", os.path.join(ROOT, "profiles", "solve_vars.txt"))
+    out = open(out_path, "w")
+
+    def emit(obj):
+        line = json.dumps(obj)
+        print(line, flush=True)
+        out.write(line + "\n")
+        out.flush()
+
+    cg.init(0)
+    cg.set_device(0)
+    sc = bu.cap_like_circuit("transfer_2x2")
+    n, ni, nv = sc.n, sc.num_inputs, sc.num_vars
+    tau = bu.SplitMix64(0xCA9).field()
+    srs = cg.srs_generate(tau, n + 3)
+    wv = np.array(sc.wire_vars, dtype=np.int64)
+    pk, _ = cg.plonk_preprocess_vars(srs, n, ni, sc.selectors_mont(), wv, nv)
+    given = [0, 1] + list(sc.free_vars)
+    t0 = time.perf_counter()
+    info = cg.plonk_key_set_given(pk, given)
+    set_given_s = time.perf_counter() - t0
+    seeds = np.arange(5000, 5000 + DISTINCT, dtype=np.uint64)
+    w, p = sc.witnesses_mont(seeds, threads=16)
+    vals = np.zeros((DISTINCT, nv, 4), np.uint64)
+    vals[:, wv.reshape(-1)] = w.reshape(DISTINCT, 5 * n, 4)
+    vals[:, 0], vals[:, 1] = bu.to_mont_array([0])[0], bu.to_mont_array([1])[0]
+    gv = np.ascontiguousarray(vals[:, given])
+    emit({"circuit": "transfer_2x2", "n": n, "num_vars": nv, "solver_info": info.as_dict(), "set_given_s": round(set_given_s, 3),
+          "bytes_per_witness": {"given": len(given) * 32, "vars": nv * 32, "columns": 5 * n * 32}, "steps": steps, "warmup": WARM})
+
+    top = max(counts + [P])
+    idx = np.arange(top) % DISTINCT
+    d_given = cg.DevBuf.from_numpy(gv[idx])
+    d_vars = cg.DevBuf(top * nv * 32)
+    # the result is the generator's assignment (checked once, outside every timed part)
+    _, st = cg.plonk_solve_vars(pk, d_given.view(0, P * len(given) * 32), P, out=d_vars)
+    got = d_vars.to_numpy(count=P * nv * 4).reshape(P, nv, 4)
+    assert all(s.kind == 0 for s in st) and np.array_equal(got[:, wv.reshape(-1)].reshape(P, 5, n, 4), w[idx[:P]])
+    pubs = np.ascontiguousarray(p[idx[:P]])
+    blind = np.stack([bu.to_mont_array(bu.blinders(7000 + i)) for i in range(P)])
+    host_vars = np.ascontiguousarray(vals[idx[:P]])
+    cg.plonk_reserve(pk, P, "vars", slot=0)
+
+    def solve_arm(count):
+        g = d_given.view(0, count * len(given) * 32)
+
+        def run(k):
+            for _ in range(k):
+                cg.plonk_solve_vars(pk, g, count, out=d_vars)
+        return run
+
+    def cpu_fill(k):
+        for _ in range(k):
+            sc.witnesses_mont(np.arange(9000, 9000 + P, dtype=np.uint64), threads=16)
+
+    def solve_prove(k):
+        g = d_given.view(0, P * len(given) * 32)
+        for _ in range(k):
+            cg.plonk_solve_vars(pk, g, P, out=d_vars)
+            cg.plonk_prove_batch_dev(pk, d_vars.view(0, P * nv * 32), pubs, blind, b"ab", P, input_form="vars")
+
+    def host_vars_arm(k):
+        for _ in range(k):
+            cg.plonk_prove_batch(pk, host_vars, pubs, blind, b"ab", P, input_form="vars")
+
+    arms = [(f"solve_{c}", solve_arm(c), c) for c in counts] + [("cpu_fill_256_16_threads", cpu_fill, P),
+                                                                 ("solve_prove_256", solve_prove, P), ("host_vars_prove_256", host_vars_arm, P)]
+    call_ms = {name: [] for name, _, _ in arms}
+    kern_ms = {name: [] for name, _, _ in arms}
+    cg.profile_enable(True)
+    for rep in range(3):
+        for name, fn, count in arms:
+            fn(WARM)
+            cg.profile_reset()
+            t0 = time.perf_counter()
+            fn(steps)
+            dt = time.perf_counter() - t0
+            k_ms, k_n = cg.profile_stats().get("k_solve_vars", (0.0, 0))
+            call_ms[name].append(1e3 * dt / steps)
+            kern_ms[name].append(k_ms / k_n if k_n else 0.0)
+            emit({"arm": name, "rep": rep, "witnesses": count, "call_ms": round(1e3 * dt / steps, 3),
+                  "witnesses_per_s": round(count * steps / dt, 1), "k_solve_vars_ms": round(k_ms / k_n, 3) if k_n else None})
+    cg.profile_enable(False)
+    med = {k: statistics.median(v) for k, v in call_ms.items()}
+    emit({"median_call_ms": {k: round(v, 3) for k, v in med.items()},
+          "spread_rel": {k: round((max(v) - min(v)) / med[k], 4) for k, v in call_ms.items()},
+          "median_k_solve_vars_ms": {k: round(statistics.median(v), 3) for k, v in kern_ms.items() if any(v)},
+          "witnesses_per_s": {name: round(count / med[name] * 1e3, 1) for name, _, count in arms},
+          "solve_prove_over_host_vars": round(med["solve_prove_256"] / med["host_vars_prove_256"], 4)})
+    for d in (d_given, d_vars):
+        d.free()
+    cg.plonk_free_key(pk)
+    cg.srs_free(srs)
+    cg.shutdown()
+    out.close()
+
+
+if __name__ == "__main__":
+    main()
