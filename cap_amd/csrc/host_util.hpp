@@ -2,6 +2,8 @@
 // conversions, Jacobian -> affine with one batched inversion, ark-serialize 0.3 encodings and the
 // challenge derivation of jf-plonk's SolidityTranscript.  O(1) work per commitment.
 #pragma once
+#include <limits.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <vector>
@@ -21,6 +23,14 @@ static const uint64_t K_CANON[kNumWires][4] = {
     {0x77f010424afeb025ULL, 0xa828a3703b311d0fULL, 0xeaa8fe837060498bULL, 0x1ee678a0470a75a6ULL},
     {0x66905a6895790c0aULL, 0x950b1db26d5c82d6ULL, 0x0a087c03e29c968bULL, 0x2042a587a90c187bULL},
     {0xeb9222db7c81e881ULL, 0x8f739da5d8d40dd3ULL, 0xdf57b799969dea1cULL, 0x2e2b91456103698aULL}};
+
+// An integer knob of the environment: the variable's value when it is set and lies in [lo, hi], else `def`.  Read on every
+// call - a site that wants the value cached keeps it in a static of its own.
+inline int env_int(const char* name, int def, int lo = INT_MIN, int hi = INT_MAX) {
+  const char* e = getenv(name);
+  const int x = e ? atoi(e) : def;
+  return x >= lo && x <= hi ? x : def;
+}
 
 inline fe fe_from_words(const uint64_t v[4]) {
   fe r;

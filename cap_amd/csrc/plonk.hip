@@ -193,8 +193,7 @@ namespace {
 // directly - a few per cent of latency - unless CAPGPU_GRAPH_FORCE=1.
 bool graph_runtime_ok() {
   static const bool ok = [] {
-    const char* f = getenv("CAPGPU_GRAPH_FORCE");
-    if (f && atoi(f) != 0) return true;
+    if (env_int("CAPGPU_GRAPH_FORCE", 0) != 0) return true;
     int v = 0;
     if (hipRuntimeGetVersion(&v) != hipSuccess) {
       (void)hipGetLastError();
@@ -206,8 +205,7 @@ bool graph_runtime_ok() {
 }
 uint32_t graph_max_batch() {
   if (!graph_runtime_ok()) return 0;
-  const char* e = getenv("CAPGPU_GRAPH_MAX_BATCH");
-  const int x = e ? atoi(e) : 16;
+  const int x = env_int("CAPGPU_GRAPH_MAX_BATCH", 16);
   return (uint32_t)(x < 0 ? 0 : (x > 64 ? 64 : x));
 }
 // the graph set of this call's signature, or nullptr when the call launches directly (first sighting, failed capture)
@@ -560,10 +558,7 @@ int prove_planned(Context& c, const ProvingKey& K, uint32_t P, const ProveReques
 std::atomic<int> g_compact{-1};  // -1: the process default (CAPGPU_COMPACT=1 turns it on)
 std::atomic<uint64_t> g_compact_calls{0}, g_compact_dropped{0}, g_compact_rows{0};  // capgpu_plonk_compaction_stats
 bool compaction_on() {
-  static const int env_default = [] {
-    const char* e = getenv("CAPGPU_COMPACT");
-    return (e && atoi(e) != 0) ? 1 : 0;
-  }();
+  static const int env_default = env_int("CAPGPU_COMPACT", 0) != 0 ? 1 : 0;
   const int m = g_compact.load(std::memory_order_relaxed);
   return (m < 0 ? env_default : m) != 0;
 }
@@ -666,6 +661,26 @@ int prove_compacted(Context& c, const ProvingKey& K, uint32_t P, const ProveRequ
   return CAPGPU_OK;
 }
 
+// The rule for the keys of one batch, stated once: they share the domain size and - `same_srs` - the SRS; `no_recompute`
+// refuses a key of the reference-schedule test mode (ProvingKey::recompute) as well.  Reports the common n and the row length
+// of the batch's public inputs, the largest num_inputs among the keys.  `who` opens the message.
+struct KeySet {
+  size_t n = 0, max_inputs = 0;
+};
+int key_set(const char* who, const ProvingKey* const* keys, size_t count, bool same_srs, bool no_recompute, KeySet* out) {
+  *out = KeySet{};
+  for (size_t i = 0; i < count; i++) {
+    const ProvingKey &K = *keys[0], &Kp = *keys[i];
+    if (Kp.n != K.n || (same_srs && Kp.srs_handle != K.srs_handle) || (no_recompute && (Kp.recompute || K.recompute))) {
+      set_error("%s: the keys of one batch must share the domain size and the SRS", who);
+      return CAPGPU_ERR_INVALID_ARG;
+    }
+    out->n = K.n;
+    out->max_inputs = std::max(out->max_inputs, Kp.num_inputs);
+  }
+  return CAPGPU_OK;
+}
+
 // One batch of P proofs under K (mixed keys: K = keys[0]) on the calling thread's context - see ProveRequest for the
 // arguments, ProvePlan for the modes and ProveRun for the schedule.
 int prove_batch(const ProvingKey& K, uint32_t P, const ProveRequest& rq) {
@@ -700,17 +715,10 @@ int prove_batch(const ProvingKey& K, uint32_t P, const ProveRequest& rq) {
     }
   }
   if (keys) {
-    size_t max_ni = 0;
-    for (uint32_t p = 0; p < P; p++) {
-      const ProvingKey& Kp = key_of(p);
-      if (Kp.n != K.n || Kp.srs_handle != K.srs_handle || Kp.recompute || K.recompute) {
-        set_error("capgpu_plonk_prove_multi: the keys of one batch must share the domain size and the SRS");
-        return CAPGPU_ERR_INVALID_ARG;
-      }
-      max_ni = std::max(max_ni, Kp.num_inputs);
-    }
-    if (num_inputs != max_ni) {
-      set_error("capgpu_plonk_prove_multi: rows of %zu public inputs given, the keys need %zu", num_inputs, max_ni);
+    KeySet ks;
+    if (int rc = key_set("capgpu_plonk_prove_multi", keys->data(), P, true, true, &ks)) return rc;
+    if (num_inputs != ks.max_inputs) {
+      set_error("capgpu_plonk_prove_multi: rows of %zu public inputs given, the keys need %zu", num_inputs, ks.max_inputs);
       return CAPGPU_ERR_INVALID_ARG;
     }
   } else if (num_inputs != K.num_inputs) {
@@ -779,8 +787,7 @@ int key_init(ProvingKey& K, size_t n, size_t num_inputs, uint64_t srs_handle) {
   K.num_inputs = num_inputs;
   K.srs_handle = srs_handle;
   K.device = ctx().device;
-  const char* env = getenv("CAPGPU_RECOMPUTE_PK_COSET");
-  K.recompute = env && atoi(env) != 0;
+  K.recompute = env_int("CAPGPU_RECOMPUTE_PK_COSET", 0) != 0;
   CAP_HIP(hipMalloc(&K.coef, sizeof(fe) * 18 * K.ps));
   CAP_HIP(hipMalloc(&K.sig_eval, sizeof(fe) * NW * n));
   CAP_HIP(hipMalloc(&K.inv_nx1, sizeof(fe) * K.m));
@@ -893,8 +900,7 @@ struct StagePool {
   size_t live = 0, made = 0;
   static constexpr size_t kMaxSlots = 320;
   static bool enabled() {  // (read per call: a process may switch it)
-    const char* e = getenv("CAPGPU_COALESCE_PRESTAGE");
-    return e && atoi(e) != 0;
+    return env_int("CAPGPU_COALESCE_PRESTAGE", 0) != 0;
   }
   // a slot of `bytes` on `dev`, or an empty one (the caller's witness then travels with the batch, as before)
   StageSlot acquire(int dev, size_t bytes) {
@@ -1918,69 +1924,20 @@ int capgpu_plonk_free_key(uint64_t pk_handle) {
   return CAPGPU_OK;
 }
 
-int capgpu_plonk_prove_batch_dev_ex(uint64_t pk_handle, int count, const void* d_wires, const uint64_t* pub_inputs,
-                                    size_t num_inputs, const uint8_t* ext_msg, size_t ext_msg_len,
-                                    const uint64_t* blinders, int input_form, capgpu_proof* proofs_out) {
-  CAP_CHECK_INIT();
-  if (bad_form(input_form)) return CAPGPU_ERR_INVALID_ARG;
-  Context& c = ctx();
-  Entry lk(c);
-  if (count < 0 || (count && (!d_wires || !blinders || !proofs_out || (num_inputs && !pub_inputs)))) {
-    set_error("capgpu_plonk_prove: bad argument");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  if (count == 0) return CAPGPU_OK;
-  size_t stride = 0;
-  int rc = input_stride(&pk_handle, 1, input_form, 0, &stride);
-  if (rc) return rc;
-  std::shared_ptr<ProvingKey> K;
-  if ((rc = lookup_key(pk_handle, &K))) return rc;
-  ProveRequest rq;
-  rq.d_wires = (const fe*)d_wires;
-  rq.pub_inputs = pub_inputs;
-  rq.num_inputs = num_inputs;
-  rq.blinders = blinders;
-  rq.proofs = proofs_out;
-  rq.ext_msg = ext_msg;
-  rq.ext_len = ext_msg_len;
-  rq.form = input_form;
-  VarsIn vin{};
-  if (input_form == CAPGPU_INPUT_VARS) {
-    // the caller's buffer holds count * num_vars values and is only read: the columns are gathered into staging
-    if ((rc = scratch_reserve(c.stage_b, vars_stage_bytes((size_t)count, K->n, 0, false)))) return rc;
-    vin = VarsIn{(const fe*)d_wires, stride};
-    rq.d_wires = (const fe*)c.stage_b.p;
-    rq.vin = &vin;
-  }
-  return prove_batch(*K, (uint32_t)count, rq);
-}
-int capgpu_plonk_prove_batch_dev(uint64_t pk_handle, int count, const void* d_wires, const uint64_t* pub_inputs,
-                                 size_t num_inputs, const uint8_t* ext_msg, size_t ext_msg_len,
-                                 const uint64_t* blinders, capgpu_proof* proofs_out) {
-  return capgpu_plonk_prove_batch_dev_ex(pk_handle, count, d_wires, pub_inputs, num_inputs, ext_msg, ext_msg_len,
-                                         blinders, CAPGPU_INPUT_EVALS, proofs_out);
-}
-
 // ---- dealing host-buffer batches over the device contexts -------------------------------------------------------
 // A batch that arrives with its witnesses in host memory names no device, so a process that drives several (capgpu_init
 // with more than one id, or CAPGPU_CONTEXTS_PER_DEVICE) cuts it into contiguous parts, one per context, each proved
 // from a thread of its own: proofs are independent, so the parts' proofs are bit for bit those of the undivided batch.
 // A thread that bound itself to a device (capgpu_set_device) keeps its batches there.
 static int deal_min() {  // proofs a part must hold at least (smaller batches stay on one context)
-  const char* e = getenv("CAPGPU_DEAL_MIN");
-  const int x = e ? atoi(e) : 8;
-  return x >= 1 ? x : 8;
+  return env_int("CAPGPU_DEAL_MIN", 8, 1);
 }
 // ... and at most two parts per DEVICE (CAPGPU_DEAL_PARTS_PER_DEVICE): two halves of a batch overlap on a GPU - one's
 // copies, latency-bound launches and transcript steps under the other's issue-bound kernels - but four quarters are smaller
 // launches for nothing (256 host-resident proofs on a device with four contexts: 1274 proofs/s as two parts, 1200 as four).
 // The contexts beyond two are there for the coalescer's gathered batches (capgpu_init).
 static size_t deal_max_parts(size_t contexts) {
-  static const size_t per_device = [] {
-    const char* e = getenv("CAPGPU_DEAL_PARTS_PER_DEVICE");
-    const int x = e ? atoi(e) : 2;
-    return (size_t)(x >= 1 ? x : 2);
-  }();
+  static const size_t per_device = (size_t)env_int("CAPGPU_DEAL_PARTS_PER_DEVICE", 2, 1);
   std::vector<int> seen;
   for (size_t i = 0; i < contexts; i++) {
     const int d = rt().ctxs[i]->device;
@@ -2026,11 +1983,7 @@ static int deal(int count, const std::function<int(int first, int cnt)>& part) {
   // witnesses arrive, stays ahead through every round and would end well before it, leaving the second part's last rounds
   // alone on the device (its host steps uncovered).  The first part is therefore the larger: CAPGPU_DEAL_FIRST_SIXTEENTHS
   // (default 9: 144 + 112 of 256; 8 = equal halves).
-  static const uint64_t first16 = [] {
-    const char* e = getenv("CAPGPU_DEAL_FIRST_SIXTEENTHS");
-    const int x = e ? atoi(e) : 9;
-    return (uint64_t)(x >= 4 && x <= 12 ? x : 9);
-  }();
+  static const uint64_t first16 = (uint64_t)env_int("CAPGPU_DEAL_FIRST_SIXTEENTHS", 9, 4, 12);
   auto cut = [&](size_t i) -> int {  // first proof of part i
     if (i == 0) return 0;
     if (i >= parts) return count;
@@ -2073,79 +2026,187 @@ static int part_key(uint64_t h, const std::shared_ptr<ProvingKey>* home, std::sh
   return clone_key_to_current(**home, (*home)->device, out);
 }
 
-// Proofs [first, first + cnt) of a host-resident batch under one key, on the calling thread's context: the part
-// capgpu_plonk_prove_batch_ex deals to a context, and - whole - the body of a ticket.
-struct HostBatch {
-  uint64_t pk;
-  const uint64_t *wires, *pub_inputs;
-  size_t num_inputs;
-  const uint8_t* ext_msg;
-  size_t ext_msg_len;
-  const uint64_t* blinders;
-  int input_form;
-  capgpu_proof* proofs_out;
-  size_t n;
-  const std::shared_ptr<ProvingKey>* home;  // tickets: see part_key
-  size_t stride;  // elements per proof of `wires`: 5 n, or the key's num_vars (input_stride)
-  // capgpu_plonk_prove_each* of one key: a message per proof in place of ext_msg, and the outcome records
-  const uint8_t* const* msgs = nullptr;
+// ---- the prove entry points ------------------------------------------------------------------------------------------------
+// Every form of the proving call - one key or one per proof, host or device buffers, all-or-nothing or per-proof outcomes,
+// synchronous or by ticket - is described by one ProveCall.  The entry points differ in the ORDER of their checks (part of
+// the ABI: tests/test_gpu_prove_args.py), so each states that order itself, out of the pieces below: bad_front / bad_rest
+// (the pointers), host_part (proofs [first, first + cnt) of a host-resident call on one context - what deal() hands out and,
+// whole, the body of a ticket and of a lone coalesced request), prove_resident (a device-resident call) and fill_job (a ticket).
+struct ProveCall {
+  const uint64_t* handles = nullptr;  // the key of proof i: handles[i], or - one_key - handles[0] for every proof
+  bool one_key = false;               // (then ProveRequest::keys stays null: the single-key launches and graph signatures)
+  int count = 0;
+  const void* wires = nullptr;        // host memory, or - the _dev calls - a device address
+  const uint64_t* pub_inputs = nullptr;
+  size_t num_inputs = 0;
+  const uint8_t* ext_msg = nullptr;   // one message for every proof ...
+  size_t ext_msg_len = 0;
+  const uint8_t* const* msgs = nullptr;  // ... or one per proof
   const size_t* msg_lens = nullptr;
-  capgpu_prove_outcome* outcomes = nullptr;
+  const uint64_t* blinders = nullptr;
+  int form = CAPGPU_INPUT_EVALS;
+  capgpu_proof* proofs = nullptr;
+  capgpu_prove_outcome* outcomes = nullptr;  // capgpu_plonk_prove_each*: one record per proof
+  // host-resident calls, once the first key is known:
+  size_t n = 0;
+  size_t stride = 0;  // elements per proof of `wires`: 5 n, or the largest num_vars among the keys of the WHOLE call
+  const std::shared_ptr<ProvingKey>* homes = nullptr;  // tickets: the home of every handle, see part_key
+  size_t num_keys() const { return one_key ? 1 : (size_t)count; }
 };
-static int host_batch_part(const HostBatch& b, int first, int cnt) {
+static const char kProve[] = "capgpu_plonk_prove", kProveMulti[] = "capgpu_plonk_prove_multi",
+                  kCheckMulti[] = "capgpu_plonk_check_witness_multi";  // the names the refusals open with
+
+// The pointer checks come in two stages: the host-buffer calls look their first key up BETWEEN them (an unknown handle
+// together with a NULL `blinders` is CAPGPU_ERR_BAD_HANDLE there), every other call makes both at once.
+static bool bad_front(const ProveCall& a) { return a.count < 0 || (a.count && (!a.wires || !a.handles)); }
+static bool bad_rest(const ProveCall& a) {
+  return a.count && (!a.blinders || !a.proofs || (a.num_inputs && !a.pub_inputs) || (a.msgs && !a.msg_lens));
+}
+static int bad_args(const char* who) {
+  set_error("%s: bad argument", who);
+  return CAPGPU_ERR_INVALID_ARG;
+}
+
+// The keys of proofs [first, first + cnt) of a call on the current context, held while the part runs.
+struct PartKeys {
+  std::vector<std::shared_ptr<ProvingKey>> hold;
+  std::vector<const ProvingKey*> ptr;
+};
+static int part_keys(const ProveCall& b, int first, int cnt, PartKeys* out) {
+  const size_t nk = b.one_key ? 1 : (size_t)cnt;
+  out->hold.resize(nk);
+  out->ptr.resize(nk);
+  for (size_t i = 0; i < nk; i++) {
+    const size_t at = b.one_key ? 0 : (size_t)first + i;
+    if (int rc = part_key(b.handles[at], b.homes ? b.homes + at : nullptr, &out->hold[i])) return rc;
+    out->ptr[i] = out->hold[i].get();
+  }
+  return CAPGPU_OK;
+}
+// `count` handles through `look` (home_key: the registry's copies, lookup_key: the current context's) and the rule over
+// the keys found (key_set), as a loop over the handles meets the two: a key that breaks the rule is reported before an
+// unknown handle behind it.
+static int keys_in_rule(const char* who, int (*look)(uint64_t, std::shared_ptr<ProvingKey>*), const uint64_t* handles,
+                        size_t count, bool same_srs, bool no_recompute, PartKeys* keys, KeySet* ks) {
+  keys->hold.assign(count, nullptr);
+  keys->ptr.clear();
+  int rc = CAPGPU_OK;
+  for (size_t i = 0; i < count && !(rc = look(handles[i], &keys->hold[i])); i++) keys->ptr.push_back(keys->hold[i].get());
+  if (int rule = key_set(who, keys->ptr.data(), keys->ptr.size(), same_srs, no_recompute, ks)) return rule;
+  return rc;
+}
+// what proofs [first, ...) of a call ask of prove_batch wherever their witnesses are; the caller adds d_wires / h_wires / vin
+static ProveRequest request_of(const ProveCall& b, int first, const PartKeys& keys) {
+  ProveRequest rq;
+  rq.pub_inputs = b.pub_inputs ? b.pub_inputs + (size_t)4 * first * b.num_inputs : nullptr;
+  rq.num_inputs = b.num_inputs;
+  rq.blinders = b.blinders + (size_t)4 * 13 * first;
+  rq.proofs = b.proofs + first;
+  rq.ext_msg = b.ext_msg;
+  rq.ext_len = b.ext_msg_len;
+  rq.msgs = b.msgs ? b.msgs + first : nullptr;
+  rq.msg_lens = b.msgs ? b.msg_lens + first : nullptr;
+  rq.keys = b.one_key ? nullptr : &keys.ptr;
+  rq.outcomes = b.outcomes ? b.outcomes + first : nullptr;
+  rq.form = b.form;
+  return rq;
+}
+
+static int host_part(const ProveCall& b, int first, int cnt) {
   Context& c = ctx();
   Entry lk(c);
   const size_t n = b.n;
-  std::shared_ptr<ProvingKey> K;
-  int rc = part_key(b.pk, b.home, &K);
+  PartKeys keys;
+  int rc = part_keys(b, first, cnt, &keys);
   if (rc) return rc;
-  const bool vars = b.input_form == CAPGPU_INPUT_VARS;
+  ProveRequest rq = request_of(b, first, keys);
+  // several keys: a part's rows carry `num_inputs` = the largest count among the keys of the WHOLE call; prove_batch wants
+  // the largest among its own keys: re-pack when the part's maximum is smaller
+  std::vector<uint64_t> pubs;
+  if (!b.one_key) {
+    size_t ni = 0;
+    for (const ProvingKey* k : keys.ptr) ni = std::max(ni, k->num_inputs);
+    if (ni > b.num_inputs) {
+      set_error("capgpu_plonk_prove_multi: rows of %zu public inputs given, the keys need %zu", b.num_inputs, ni);
+      return CAPGPU_ERR_INVALID_ARG;
+    }
+    if (ni < b.num_inputs) {
+      pubs.assign((size_t)4 * ni * cnt + 4, 0);
+      for (int i = 0; i < cnt; i++)
+        if (ni) memcpy(&pubs[(size_t)4 * ni * i], rq.pub_inputs + (size_t)4 * b.num_inputs * i, 32 * ni);
+      rq.pub_inputs = pubs.data();
+      rq.num_inputs = ni;
+    }
+  }
+  const bool vars = b.form == CAPGPU_INPUT_VARS;
   rc = scratch_reserve(c.stage_b, vars ? vars_stage_bytes((size_t)cnt, n, b.stride, true) : wires_stage_bytes((size_t)cnt, n));
   if (rc) return rc;
   // the columns (variable form: the value vectors) are copied inside round 1, chunk by chunk, behind the commitments of
   // the chunk before
   std::vector<const uint64_t*> rows(cnt);
-  for (int i = 0; i < cnt; i++) rows[i] = b.wires + (size_t)4 * (first + i) * b.stride;
+  for (int i = 0; i < cnt; i++) rows[i] = (const uint64_t*)b.wires + (size_t)4 * (first + i) * b.stride;
   const VarsIn vin{(const fe*)c.stage_b.p + (size_t)cnt * NW * n, b.stride};
-  ProveRequest rq;
   rq.d_wires = (const fe*)c.stage_b.p;
-  rq.pub_inputs = b.pub_inputs ? b.pub_inputs + (size_t)4 * first * b.num_inputs : nullptr;
-  rq.num_inputs = b.num_inputs;
-  rq.blinders = b.blinders + (size_t)4 * 13 * first;
-  rq.proofs = b.proofs_out + first;
-  rq.ext_msg = b.ext_msg;
-  rq.ext_len = b.ext_msg_len;
-  rq.msgs = b.msgs ? b.msgs + first : nullptr;
-  rq.msg_lens = b.msgs ? b.msg_lens + first : nullptr;
-  rq.outcomes = b.outcomes ? b.outcomes + first : nullptr;
   rq.h_wires = rows.data();
-  rq.form = b.input_form;
   rq.vin = vars ? &vin : nullptr;
-  return prove_batch(*K, (uint32_t)cnt, rq);
+  return prove_batch(*keys.ptr[0], (uint32_t)cnt, rq);
+}
+
+// A device-resident call on the calling thread's context, whose lock the caller holds.
+static int prove_resident(const ProveCall& a) {
+  Context& c = ctx();
+  PartKeys keys;
+  int rc = part_keys(a, 0, a.count, &keys);
+  if (rc) return rc;
+  ProveRequest rq = request_of(a, 0, keys);
+  rq.d_wires = (const fe*)a.wires;
+  VarsIn vin{};
+  if (a.form == CAPGPU_INPUT_VARS) {
+    // the caller's buffer holds count * stride values and is only read: the columns are gathered into staging
+    size_t stride = 0;
+    if ((rc = input_stride(a.handles, (int)a.num_keys(), a.form, 0, &stride))) return rc;
+    if ((rc = scratch_reserve(c.stage_b, vars_stage_bytes((size_t)a.count, keys.ptr[0]->n, 0, false)))) return rc;
+    vin = VarsIn{(const fe*)a.wires, stride};
+    rq.d_wires = (const fe*)c.stage_b.p;
+    rq.vin = &vin;
+  }
+  return prove_batch(*keys.ptr[0], (uint32_t)a.count, rq);
+}
+
+// A host-resident call from its first key on: the remaining pointers, the stride, and the parts dealt over the contexts.
+static int prove_dealt(const char* who, ProveCall& a) {
+  std::shared_ptr<ProvingKey> K0;
+  int rc = home_key(a.handles[0], &K0);
+  if (rc) return rc;
+  if (bad_rest(a)) return bad_args(who);
+  if ((rc = input_stride(a.handles, (int)a.num_keys(), a.form, K0->n, &a.stride))) return rc;
+  a.n = K0->n;
+  return deal(a.count, [&](int first, int cnt) -> int { return host_part(a, first, cnt); });
+}
+// capgpu_plonk_prove_batch_ex / _multi_ex
+static int prove_host(const char* who, ProveCall a) {
+  CAP_CHECK_INIT();
+  if (bad_form(a.form)) return CAPGPU_ERR_INVALID_ARG;
+  if (bad_front(a)) return bad_args(who);
+  if (a.count == 0) return CAPGPU_OK;
+  return prove_dealt(who, a);
+}
+// capgpu_plonk_prove_batch_dev_ex / _multi_dev_ex
+static int prove_dev(const char* who, const ProveCall& a) {
+  CAP_CHECK_INIT();
+  if (bad_form(a.form)) return CAPGPU_ERR_INVALID_ARG;
+  Context& c = ctx();
+  Entry lk(c);
+  if (bad_front(a) || bad_rest(a)) return bad_args(who);
+  if (a.count == 0) return CAPGPU_OK;
+  return prove_resident(a);
 }
 
 int capgpu_plonk_prove_batch_ex(uint64_t pk_handle, int count, const uint64_t* wires, const uint64_t* pub_inputs,
                                 size_t num_inputs, const uint8_t* ext_msg, size_t ext_msg_len, const uint64_t* blinders,
                                 int input_form, capgpu_proof* proofs_out) {
-  CAP_CHECK_INIT();
-  if (bad_form(input_form)) return CAPGPU_ERR_INVALID_ARG;
-  if (count < 0 || (count && !wires)) {
-    set_error("capgpu_plonk_prove: bad argument");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  if (count == 0) return CAPGPU_OK;
-  std::shared_ptr<ProvingKey> K0;
-  int rc0 = home_key(pk_handle, &K0);
-  if (rc0) return rc0;
-  if (!blinders || !proofs_out || (num_inputs && !pub_inputs)) {
-    set_error("capgpu_plonk_prove: bad argument");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  size_t stride = 0;
-  if ((rc0 = input_stride(&pk_handle, 1, input_form, K0->n, &stride))) return rc0;
-  const HostBatch b{pk_handle, wires, pub_inputs, num_inputs, ext_msg, ext_msg_len, blinders, input_form, proofs_out, K0->n,
-                    nullptr, stride};
-  return deal(count, [&](int first, int cnt) -> int { return host_batch_part(b, first, cnt); });
+  return prove_host(kProve, ProveCall{&pk_handle, true, count, wires, pub_inputs, num_inputs, ext_msg, ext_msg_len, nullptr,
+                                      nullptr, blinders, input_form, proofs_out});
 }
 int capgpu_plonk_prove_batch(uint64_t pk_handle, int count, const uint64_t* wires, const uint64_t* pub_inputs,
                              size_t num_inputs, const uint8_t* ext_msg, size_t ext_msg_len, const uint64_t* blinders,
@@ -2153,50 +2214,39 @@ int capgpu_plonk_prove_batch(uint64_t pk_handle, int count, const uint64_t* wire
   return capgpu_plonk_prove_batch_ex(pk_handle, count, wires, pub_inputs, num_inputs, ext_msg, ext_msg_len, blinders,
                                      CAPGPU_INPUT_EVALS, proofs_out);
 }
+int capgpu_plonk_prove_batch_dev_ex(uint64_t pk_handle, int count, const void* d_wires, const uint64_t* pub_inputs,
+                                    size_t num_inputs, const uint8_t* ext_msg, size_t ext_msg_len,
+                                    const uint64_t* blinders, int input_form, capgpu_proof* proofs_out) {
+  return prove_dev(kProve, ProveCall{&pk_handle, true, count, d_wires, pub_inputs, num_inputs, ext_msg, ext_msg_len, nullptr,
+                                     nullptr, blinders, input_form, proofs_out});
+}
+int capgpu_plonk_prove_batch_dev(uint64_t pk_handle, int count, const void* d_wires, const uint64_t* pub_inputs,
+                                 size_t num_inputs, const uint8_t* ext_msg, size_t ext_msg_len,
+                                 const uint64_t* blinders, capgpu_proof* proofs_out) {
+  return capgpu_plonk_prove_batch_dev_ex(pk_handle, count, d_wires, pub_inputs, num_inputs, ext_msg, ext_msg_len,
+                                         blinders, CAPGPU_INPUT_EVALS, proofs_out);
+}
 
 // Proofs of several proving keys in one device batch (see prove_batch): pk_handles[i] is the key of proof i.
+int capgpu_plonk_prove_multi_ex(const uint64_t* pk_handles, int count, const uint64_t* wires,
+                                const uint64_t* pub_inputs, size_t num_inputs, const uint8_t* const* ext_msgs,
+                                const size_t* ext_msg_lens, const uint64_t* blinders, int input_form,
+                                capgpu_proof* proofs_out) {
+  return prove_host(kProveMulti, ProveCall{pk_handles, false, count, wires, pub_inputs, num_inputs, nullptr, 0, ext_msgs,
+                                           ext_msg_lens, blinders, input_form, proofs_out});
+}
+int capgpu_plonk_prove_multi(const uint64_t* pk_handles, int count, const uint64_t* wires, const uint64_t* pub_inputs,
+                             size_t num_inputs, const uint8_t* const* ext_msgs, const size_t* ext_msg_lens,
+                             const uint64_t* blinders, capgpu_proof* proofs_out) {
+  return capgpu_plonk_prove_multi_ex(pk_handles, count, wires, pub_inputs, num_inputs, ext_msgs, ext_msg_lens, blinders,
+                                     CAPGPU_INPUT_EVALS, proofs_out);
+}
 int capgpu_plonk_prove_multi_dev_ex(const uint64_t* pk_handles, int count, const void* d_wires,
                                     const uint64_t* pub_inputs, size_t num_inputs, const uint8_t* const* ext_msgs,
                                     const size_t* ext_msg_lens, const uint64_t* blinders, int input_form,
                                     capgpu_proof* proofs_out) {
-  CAP_CHECK_INIT();
-  if (bad_form(input_form)) return CAPGPU_ERR_INVALID_ARG;
-  Context& c = ctx();
-  Entry lk(c);
-  if (count < 0 || (count && (!pk_handles || !d_wires || !blinders || !proofs_out || (num_inputs && !pub_inputs) ||
-                              (ext_msgs && !ext_msg_lens)))) {
-    set_error("capgpu_plonk_prove_multi: bad argument");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  if (count == 0) return CAPGPU_OK;
-  std::vector<std::shared_ptr<ProvingKey>> hold(count);
-  std::vector<const ProvingKey*> keys(count);
-  for (int i = 0; i < count; i++) {
-    int rc = lookup_key(pk_handles[i], &hold[i]);
-    if (rc) return rc;
-    keys[i] = hold[i].get();
-  }
-  ProveRequest rq;
-  rq.d_wires = (const fe*)d_wires;
-  rq.pub_inputs = pub_inputs;
-  rq.num_inputs = num_inputs;
-  rq.blinders = blinders;
-  rq.proofs = proofs_out;
-  rq.msgs = ext_msgs;
-  rq.msg_lens = ext_msg_lens;
-  rq.keys = &keys;
-  rq.form = input_form;
-  VarsIn vin{};
-  if (input_form == CAPGPU_INPUT_VARS) {
-    size_t stride = 0;
-    int rc = input_stride(pk_handles, count, input_form, 0, &stride);
-    if (rc) return rc;
-    if ((rc = scratch_reserve(c.stage_b, vars_stage_bytes((size_t)count, keys[0]->n, 0, false)))) return rc;
-    vin = VarsIn{(const fe*)d_wires, stride};
-    rq.d_wires = (const fe*)c.stage_b.p;
-    rq.vin = &vin;
-  }
-  return prove_batch(*keys[0], (uint32_t)count, rq);
+  return prove_dev(kProveMulti, ProveCall{pk_handles, false, count, d_wires, pub_inputs, num_inputs, nullptr, 0, ext_msgs,
+                                          ext_msg_lens, blinders, input_form, proofs_out});
 }
 int capgpu_plonk_prove_multi_dev(const uint64_t* pk_handles, int count, const void* d_wires, const uint64_t* pub_inputs,
                                  size_t num_inputs, const uint8_t* const* ext_msgs, const size_t* ext_msg_lens,
@@ -2205,121 +2255,24 @@ int capgpu_plonk_prove_multi_dev(const uint64_t* pk_handles, int count, const vo
                                          blinders, CAPGPU_INPUT_EVALS, proofs_out);
 }
 
-// The same for a batch of several keys (capgpu_plonk_prove_multi_ex).
-struct HostMulti {
-  const uint64_t* pk_handles;
-  const uint64_t *wires, *pub_inputs;
-  size_t num_inputs;
-  const uint8_t* const* ext_msgs;
-  const size_t* ext_msg_lens;
-  const uint64_t* blinders;
-  int input_form;
-  capgpu_proof* proofs_out;
-  size_t n;
-  const std::shared_ptr<ProvingKey>* homes;  // tickets: [count], see part_key
-  size_t stride;  // elements per proof of `wires`: 5 n, or the largest num_vars among the keys of the WHOLE call
-  capgpu_prove_outcome* outcomes = nullptr;  // capgpu_plonk_prove_each*
-};
-static int host_multi_part(const HostMulti& b, int first, int cnt) {
-  Context& c = ctx();
-  Entry lk(c);
-  const size_t n = b.n, num_inputs = b.num_inputs;
-  std::vector<std::shared_ptr<ProvingKey>> hold(cnt);
-  std::vector<const ProvingKey*> keys(cnt);
-  int rc;
-  for (int i = 0; i < cnt; i++) {
-    if ((rc = part_key(b.pk_handles[first + i], b.homes ? b.homes + first + i : nullptr, &hold[i]))) return rc;
-    keys[i] = hold[i].get();
-  }
-  // a part's rows carry `num_inputs` = the largest count among the keys of the WHOLE call; prove_batch wants the
-  // largest among its own keys: re-pack when the part's maximum is smaller
-  size_t ni = 0;
-  for (int i = 0; i < cnt; i++) ni = std::max(ni, keys[i]->num_inputs);
-  std::vector<uint64_t> pubs;
-  const uint64_t* pp = b.pub_inputs ? b.pub_inputs + (size_t)4 * first * num_inputs : nullptr;
-  if (ni != num_inputs) {
-    if (ni > num_inputs) {
-      set_error("capgpu_plonk_prove_multi: rows of %zu public inputs given, the keys need %zu", num_inputs, ni);
-      return CAPGPU_ERR_INVALID_ARG;
-    }
-    pubs.assign((size_t)4 * ni * cnt + 4, 0);
-    for (int i = 0; i < cnt; i++)
-      if (ni) memcpy(&pubs[(size_t)4 * ni * i], pp + (size_t)4 * num_inputs * i, 32 * ni);
-    pp = pubs.data();
-  }
-  const bool vars = b.input_form == CAPGPU_INPUT_VARS;
-  if ((rc = scratch_reserve(c.stage_b,
-                            vars ? vars_stage_bytes((size_t)cnt, n, b.stride, true) : wires_stage_bytes((size_t)cnt, n))))
-    return rc;
-  std::vector<const uint64_t*> rows(cnt);
-  for (int i = 0; i < cnt; i++) rows[i] = b.wires + (size_t)4 * (first + i) * b.stride;
-  const VarsIn vin{(const fe*)c.stage_b.p + (size_t)cnt * NW * n, b.stride};
-  ProveRequest rq;
-  rq.d_wires = (const fe*)c.stage_b.p;
-  rq.pub_inputs = pp;
-  rq.num_inputs = ni;
-  rq.blinders = b.blinders + (size_t)4 * 13 * first;
-  rq.proofs = b.proofs_out + first;
-  rq.msgs = b.ext_msgs ? b.ext_msgs + first : nullptr;
-  rq.msg_lens = b.ext_msg_lens ? b.ext_msg_lens + first : nullptr;
-  rq.keys = &keys;
-  rq.outcomes = b.outcomes ? b.outcomes + first : nullptr;
-  rq.h_wires = rows.data();
-  rq.form = b.input_form;
-  rq.vin = vars ? &vin : nullptr;
-  return prove_batch(*keys[0], (uint32_t)cnt, rq);
-}
-
-int capgpu_plonk_prove_multi_ex(const uint64_t* pk_handles, int count, const uint64_t* wires,
-                                const uint64_t* pub_inputs, size_t num_inputs, const uint8_t* const* ext_msgs,
-                                const size_t* ext_msg_lens, const uint64_t* blinders, int input_form,
-                                capgpu_proof* proofs_out) {
-  CAP_CHECK_INIT();
-  if (bad_form(input_form)) return CAPGPU_ERR_INVALID_ARG;
-  if (count < 0 || (count && (!wires || !pk_handles))) {
-    set_error("capgpu_plonk_prove_multi: bad argument");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  if (count == 0) return CAPGPU_OK;
-  std::shared_ptr<ProvingKey> K0;
-  int rc0 = home_key(pk_handles[0], &K0);
-  if (rc0) return rc0;
-  if (!blinders || !proofs_out || (num_inputs && !pub_inputs) || (ext_msgs && !ext_msg_lens)) {
-    set_error("capgpu_plonk_prove_multi: bad argument");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  size_t stride = 0;
-  if ((rc0 = input_stride(pk_handles, count, input_form, K0->n, &stride))) return rc0;
-  const HostMulti b{pk_handles, wires, pub_inputs, num_inputs, ext_msgs, ext_msg_lens, blinders, input_form, proofs_out, K0->n,
-                    nullptr, stride};
-  return deal(count, [&](int first, int cnt) -> int { return host_multi_part(b, first, cnt); });
-}
-int capgpu_plonk_prove_multi(const uint64_t* pk_handles, int count, const uint64_t* wires, const uint64_t* pub_inputs,
-                             size_t num_inputs, const uint8_t* const* ext_msgs, const size_t* ext_msg_lens,
-                             const uint64_t* blinders, capgpu_proof* proofs_out) {
-  return capgpu_plonk_prove_multi_ex(pk_handles, count, wires, pub_inputs, num_inputs, ext_msgs, ext_msg_lens, blinders,
-                                     CAPGPU_INPUT_EVALS, proofs_out);
-}
-
 // ---- per-proof outcomes (capgpu_plonk_prove_each*) ---------------------------------------------------------------------
 // The arguments of capgpu_plonk_prove_multi_ex plus one outcome record per proof; the pointer checks come before the
-// device is looked for.  A call whose handles all name one key takes the single-key path (ProveRequest::keys == nullptr:
-// the launches of capgpu_plonk_prove_batch_ex) with its messages per proof.
-static int each_bad_args(const uint64_t* pk_handles, int count, const void* wires, const uint64_t* pub_inputs,
-                         size_t num_inputs, const uint8_t* const* ext_msgs, const size_t* ext_msg_lens,
-                         const uint64_t* blinders, int input_form, const capgpu_proof* proofs_out,
-                         const capgpu_prove_outcome* outcomes_out) {
-  if (bad_form(input_form)) return CAPGPU_ERR_INVALID_ARG;
-  if (count < 0 || (count && (!pk_handles || !wires || !blinders || !proofs_out || !outcomes_out ||
-                              (num_inputs && !pub_inputs) || (ext_msgs && !ext_msg_lens)))) {
-    set_error("capgpu_plonk_prove_multi: bad argument");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
+// device is looked for.  A call whose handles all name one key takes the single-key path with its messages per proof.
+static ProveCall each_call(const uint64_t* pk_handles, int count, const void* wires, const uint64_t* pub_inputs,
+                           size_t num_inputs, const uint8_t* const* ext_msgs, const size_t* ext_msg_lens,
+                           const uint64_t* blinders, int input_form, capgpu_proof* proofs_out,
+                           capgpu_prove_outcome* outcomes_out) {
+  return ProveCall{pk_handles, false, count, wires, pub_inputs, num_inputs, nullptr, 0, ext_msgs, ext_msg_lens, blinders,
+                   input_form, proofs_out, outcomes_out};
+}
+static int each_bad_args(const ProveCall& a) {
+  if (bad_form(a.form)) return CAPGPU_ERR_INVALID_ARG;
+  if (bad_front(a) || bad_rest(a) || (a.count && !a.outcomes)) return bad_args(kProveMulti);
   return CAPGPU_OK;
 }
-static bool each_one_key(const uint64_t* pk_handles, int count) {
-  for (int i = 1; i < count; i++)
-    if (pk_handles[i] != pk_handles[0]) return false;
+static bool each_one_key(const ProveCall& a) {
+  for (int i = 1; i < a.count; i++)
+    if (a.handles[i] != a.handles[0]) return false;
   return true;
 }
 // the ranks of a communicator prove in lock step (capgpu_plonk_shard_msm): there is no per-proof exit
@@ -2333,74 +2286,32 @@ int capgpu_plonk_prove_each(const uint64_t* pk_handles, int count, const uint64_
                             size_t num_inputs, const uint8_t* const* ext_msgs, const size_t* ext_msg_lens,
                             const uint64_t* blinders, int input_form, capgpu_proof* proofs_out,
                             capgpu_prove_outcome* outcomes_out) {
-  if (int rc = each_bad_args(pk_handles, count, wires, pub_inputs, num_inputs, ext_msgs, ext_msg_lens, blinders, input_form,
-                             proofs_out, outcomes_out))
-    return rc;
+  ProveCall a = each_call(pk_handles, count, wires, pub_inputs, num_inputs, ext_msgs, ext_msg_lens, blinders, input_form,
+                          proofs_out, outcomes_out);
+  if (int rc = each_bad_args(a)) return rc;
   CAP_CHECK_INIT();
   if (count == 0) return CAPGPU_OK;
   if (each_refused_by_sharding()) return CAPGPU_ERR_INVALID_ARG;
-  std::shared_ptr<ProvingKey> K0;
-  int rc0 = home_key(pk_handles[0], &K0);
-  if (rc0) return rc0;
-  size_t stride = 0;
-  if ((rc0 = input_stride(pk_handles, count, input_form, K0->n, &stride))) return rc0;
-  if (each_one_key(pk_handles, count)) {
-    HostBatch b{pk_handles[0], wires, pub_inputs, num_inputs, nullptr, 0, blinders, input_form, proofs_out, K0->n, nullptr,
-                stride};
-    b.msgs = ext_msgs;
-    b.msg_lens = ext_msg_lens;
-    b.outcomes = outcomes_out;
-    return deal(count, [&](int first, int cnt) -> int { return host_batch_part(b, first, cnt); });
-  }
-  HostMulti b{pk_handles, wires, pub_inputs, num_inputs, ext_msgs, ext_msg_lens, blinders, input_form, proofs_out, K0->n,
-              nullptr, stride};
-  b.outcomes = outcomes_out;
-  return deal(count, [&](int first, int cnt) -> int { return host_multi_part(b, first, cnt); });
+  a.one_key = each_one_key(a);
+  return prove_dealt(kProveMulti, a);
 }
 
 int capgpu_plonk_prove_each_dev(const uint64_t* pk_handles, int count, const void* d_wires, const uint64_t* pub_inputs,
                                 size_t num_inputs, const uint8_t* const* ext_msgs, const size_t* ext_msg_lens,
                                 const uint64_t* blinders, int input_form, capgpu_proof* proofs_out,
                                 capgpu_prove_outcome* outcomes_out) {
-  if (int rc = each_bad_args(pk_handles, count, d_wires, pub_inputs, num_inputs, ext_msgs, ext_msg_lens, blinders,
-                             input_form, proofs_out, outcomes_out))
-    return rc;
+  ProveCall a = each_call(pk_handles, count, d_wires, pub_inputs, num_inputs, ext_msgs, ext_msg_lens, blinders, input_form,
+                          proofs_out, outcomes_out);
+  if (int rc = each_bad_args(a)) return rc;
   CAP_CHECK_INIT();
   Context& c = ctx();
   Entry lk(c);
   if (count == 0) return CAPGPU_OK;
   if (each_refused_by_sharding()) return CAPGPU_ERR_INVALID_ARG;
-  const bool one_key = each_one_key(pk_handles, count);
-  std::vector<std::shared_ptr<ProvingKey>> hold(one_key ? 1 : count);
-  std::vector<const ProvingKey*> keys(hold.size());
-  for (size_t i = 0; i < hold.size(); i++) {
-    int rc = lookup_key(pk_handles[i], &hold[i]);
-    if (rc) return rc;
-    keys[i] = hold[i].get();
-  }
-  ProveRequest rq;
-  rq.d_wires = (const fe*)d_wires;
-  rq.pub_inputs = pub_inputs;
-  rq.num_inputs = num_inputs;
-  rq.blinders = blinders;
-  rq.proofs = proofs_out;
-  rq.msgs = ext_msgs;
-  rq.msg_lens = ext_msg_lens;
-  rq.keys = one_key ? nullptr : &keys;
-  rq.form = input_form;
-  rq.outcomes = outcomes_out;
-  VarsIn vin{};
-  if (input_form == CAPGPU_INPUT_VARS) {
-    size_t stride = 0;
-    int rc = input_stride(pk_handles, count, input_form, 0, &stride);
-    if (rc) return rc;
-    if ((rc = scratch_reserve(c.stage_b, vars_stage_bytes((size_t)count, keys[0]->n, 0, false)))) return rc;
-    vin = VarsIn{(const fe*)d_wires, stride};
-    rq.d_wires = (const fe*)c.stage_b.p;
-    rq.vin = &vin;
-  }
-  return prove_batch(*keys[0], (uint32_t)count, rq);
+  a.one_key = each_one_key(a);
+  return prove_resident(a);
 }
+
 
 int capgpu_prove_outcome_text(const capgpu_prove_outcome* outcome, char* buf, size_t cap) {
   if (!outcome || (cap && !buf)) {
@@ -2414,35 +2325,53 @@ int capgpu_prove_outcome_text(const capgpu_prove_outcome* outcome, char* buf, si
 }  // extern "C"
 
 // ---- asynchronous prove tickets ------------------------------------------------------------------------------------------
-// capgpu_plonk_prove_batch_async / _multi_async check their arguments, copy what is small (messages, handles), take a
-// reference to the key(s) and queue a ticket (tickets.hpp); a worker thread of the library then proves the whole batch on
-// ONE context - the body is the part function of the synchronous call with first = 0, cnt = count, not deal(): two tickets
-// in flight are two bound callers (0.995 of the resident rate, profiles/phase_trace_r06.md), four quarter-parts are slower
-// (deal_max_parts above).  Coalescing is not involved.
+// The _async entry points check their arguments, copy what is small (messages, handles), take a reference to the key(s)
+// and queue a ticket (tickets.hpp); a worker thread of the library then proves the whole batch on ONE context - the body is
+// host_part with first = 0, cnt = count, not deal(): two tickets in flight are two bound callers (0.995 of the resident
+// rate, profiles/phase_trace_r06.md), four quarter-parts are slower (deal_max_parts above).  Coalescing is not involved.
 namespace cap {
 namespace {
 struct AsyncJob {
-  bool multi = false;
-  int count = 0;
-  std::vector<uint64_t> pks;                        // one, or one per proof (_multi)
-  std::vector<std::shared_ptr<ProvingKey>> homes;   // shared ownership, as home_key gives it: [pks.size()]
-  const uint64_t *wires = nullptr, *pub_inputs = nullptr, *blinders = nullptr;  // borrowed until the ticket is done
-  capgpu_proof* proofs_out = nullptr;               // borrowed likewise
-  size_t num_inputs = 0, n = 0, stride = 0;          // stride: elements per proof of `wires` (input_stride)
-  int input_form = CAPGPU_INPUT_EVALS;
-  bool has_msgs = false;                            // _multi with ext_msgs != NULL
-  std::vector<std::vector<uint8_t>> msgs;           // copies: one (batch; empty = none) or one per proof
-  int bound_slot = -1;                              // the submitting thread's capgpu_set_device, -1: none
-  capgpu_prove_outcome* outcomes = nullptr;         // capgpu_plonk_prove_each_async: borrowed like proofs_out
+  // the call as it was submitted: wires, public inputs, blinders, proofs and outcomes are borrowed until the ticket is done;
+  // handles, homes and messages are the submitter's no longer - run_ticket points them at the copies below
+  ProveCall call;
+  std::vector<uint64_t> pks;                       // one, or one per proof
+  std::vector<std::shared_ptr<ProvingKey>> homes;  // shared ownership, as home_key gives it: [pks.size()]
+  std::vector<std::vector<uint8_t>> msgs;          // call.msgs != NULL: one per proof, else [1]: the shared message
+  int bound_slot = -1;                             // the submitting thread's capgpu_set_device, -1: none
 };
+// The ticket of a call whose pointers have been checked: every key is known and the set obeys the rule - what the
+// synchronous call finds out on the device (prove_batch) is found out here, before anything is queued.  refuse_recompute:
+// see key_set.
+int fill_job(const ProveCall& a, bool refuse_recompute, AsyncJob* j) {
+  const size_t nk = a.num_keys();
+  PartKeys keys;
+  KeySet ks;
+  int rc = keys_in_rule(kProveMulti, home_key, a.handles, nk, true, refuse_recompute, &keys, &ks);
+  if (rc) return rc;
+  if (a.num_inputs != ks.max_inputs) {
+    if (a.one_key) set_error("capgpu_plonk_prove: %zu public inputs given, key expects %zu", a.num_inputs, ks.max_inputs);
+    else set_error("capgpu_plonk_prove_multi: rows of %zu public inputs given, the keys need %zu", a.num_inputs, ks.max_inputs);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  j->call = a;
+  j->call.n = ks.n;
+  if ((rc = input_stride(a.handles, (int)nk, a.form, ks.n, &j->call.stride))) return rc;
+  j->pks.assign(a.handles, a.handles + nk);
+  j->homes = std::move(keys.hold);
+  j->msgs.resize(a.msgs ? (size_t)a.count : 1);
+  for (size_t i = 0; i < j->msgs.size(); i++) {
+    const uint8_t* m = a.msgs ? a.msgs[i] : a.ext_msg;
+    const size_t len = a.msgs ? a.msg_lens[i] : a.ext_msg_len;
+    if (m && len) j->msgs[i].assign(m, m + len);
+  }
+  j->bound_slot = thread_bound_slot();
+  return CAPGPU_OK;
+}
 using Tickets = TicketTable<AsyncJob>;
 
 uint32_t async_inflight() {  // tickets of one physical device running at once (CAPGPU_ASYNC_INFLIGHT, default 2)
-  static const uint32_t v = [] {
-    const char* e = getenv("CAPGPU_ASYNC_INFLIGHT");
-    const int x = e ? atoi(e) : 2;
-    return (uint32_t)(x >= 1 && x <= 16 ? x : 2);
-  }();
+  static const uint32_t v = (uint32_t)env_int("CAPGPU_ASYNC_INFLIGHT", 2, 1, 16);
   return v;
 }
 // HIP devices behind the contexts, in slot order: a ticket's lane is the index of its device
@@ -2490,7 +2419,7 @@ int run_ticket(AsyncJob& j, int lane, std::string* err) {
       if (cp->device == devs[(size_t)lane]) mine.push_back(cp.get());
     c = mine[R.rr.fetch_add(1, std::memory_order_relaxed) % mine.size()];
   }
-  trace("tk_run", c->slot, j.count);
+  trace("tk_run", c->slot, j.call.count);
   int rc;
   {
     ScopedCtx sc(*c);
@@ -2500,24 +2429,17 @@ int run_ticket(AsyncJob& j, int lane, std::string* err) {
       mp[i] = j.msgs[i].empty() ? nullptr : j.msgs[i].data();
       ml[i] = j.msgs[i].size();
     }
-    if (j.multi) {
-      HostMulti b{j.pks.data(), j.wires, j.pub_inputs, j.num_inputs, j.has_msgs ? mp.data() : nullptr,
-                  j.has_msgs ? ml.data() : nullptr, j.blinders, j.input_form, j.proofs_out, j.n, j.homes.data(), j.stride};
-      b.outcomes = j.outcomes;
-      rc = host_multi_part(b, 0, j.count);
-    } else if (j.outcomes) {  // an outcome call of one key: the single-key path with a message per proof
-      HostBatch b{j.pks[0], j.wires, j.pub_inputs, j.num_inputs, nullptr, 0, j.blinders, j.input_form, j.proofs_out, j.n,
-                  &j.homes[0], j.stride};
-      b.msgs = j.has_msgs ? mp.data() : nullptr;
-      b.msg_lens = j.has_msgs ? ml.data() : nullptr;
-      b.outcomes = j.outcomes;
-      rc = host_batch_part(b, 0, j.count);
+    ProveCall b = j.call;
+    b.handles = j.pks.data();
+    b.homes = j.homes.data();
+    if (b.msgs) {
+      b.msgs = mp.data();
+      b.msg_lens = ml.data();
     } else {
-      const std::vector<uint8_t>& m = j.msgs[0];
-      const HostBatch b{j.pks[0], j.wires, j.pub_inputs, j.num_inputs, m.empty() ? nullptr : m.data(), m.size(),
-                        j.blinders, j.input_form, j.proofs_out, j.n, &j.homes[0], j.stride};
-      rc = host_batch_part(b, 0, j.count);
+      b.ext_msg = mp[0];
+      b.ext_msg_len = ml[0];
     }
+    rc = host_part(b, 0, b.count);
     if (rc) *err = last_error();
   }
   if (locked) c->mu.unlock();
@@ -2577,160 +2499,58 @@ void plonk_async_shutdown() {
 
 extern "C" {
 
+// capgpu_plonk_prove_batch_async / _multi_async: the checks of the synchronous call, in its order, with its codes and
+// messages (prove_host), and those it would meet on the device (fill_job)
+static int prove_async(const char* who, const ProveCall& a, bool refuse_recompute, uint64_t* ticket_out) {
+  CAP_CHECK_INIT();
+  if (bad_form(a.form)) return CAPGPU_ERR_INVALID_ARG;
+  if (bad_front(a) || !ticket_out) return bad_args(who);
+  *ticket_out = 0;
+  if (a.count == 0) return CAPGPU_OK;
+  std::shared_ptr<ProvingKey> K0;
+  int rc = home_key(a.handles[0], &K0);
+  if (rc) return rc;
+  if (bad_rest(a)) return bad_args(who);
+  AsyncJob j;
+  if ((rc = fill_job(a, refuse_recompute, &j))) return rc;
+  if (async_refused_by_sharding()) return CAPGPU_ERR_INVALID_ARG;
+  return submit_ticket(std::move(j), ticket_out);
+}
+
 int capgpu_plonk_prove_batch_async(uint64_t pk_handle, int count, const uint64_t* wires, const uint64_t* pub_inputs,
                                    size_t num_inputs, const uint8_t* ext_msg, size_t ext_msg_len, const uint64_t* blinders,
                                    int input_form, capgpu_proof* proofs_out, uint64_t* ticket_out) {
-  CAP_CHECK_INIT();
-  // the checks of capgpu_plonk_prove_batch_ex, in its order, with its codes and messages
-  if (bad_form(input_form)) return CAPGPU_ERR_INVALID_ARG;
-  if (count < 0 || (count && !wires) || !ticket_out) {
-    set_error("capgpu_plonk_prove: bad argument");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  *ticket_out = 0;
-  if (count == 0) return CAPGPU_OK;
-  AsyncJob j;
-  j.homes.resize(1);
-  int rc = home_key(pk_handle, &j.homes[0]);
-  if (rc) return rc;
-  if (!blinders || !proofs_out || (num_inputs && !pub_inputs)) {
-    set_error("capgpu_plonk_prove: bad argument");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  if (num_inputs != j.homes[0]->num_inputs) {  // (prove_batch's own check, made before anything is queued)
-    set_error("capgpu_plonk_prove: %zu public inputs given, key expects %zu", num_inputs, j.homes[0]->num_inputs);
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  if ((rc = input_stride(&pk_handle, 1, input_form, j.homes[0]->n, &j.stride))) return rc;
-  if (async_refused_by_sharding()) return CAPGPU_ERR_INVALID_ARG;
-  j.count = count;
-  j.pks.assign(1, pk_handle);
-  j.wires = wires;
-  j.pub_inputs = pub_inputs;
-  j.blinders = blinders;
-  j.proofs_out = proofs_out;
-  j.num_inputs = num_inputs;
-  j.n = j.homes[0]->n;
-  j.input_form = input_form;
-  j.msgs.resize(1);
-  if (ext_msg && ext_msg_len) j.msgs[0].assign(ext_msg, ext_msg + ext_msg_len);
-  j.bound_slot = thread_bound_slot();
-  return submit_ticket(std::move(j), ticket_out);
+  return prove_async(kProve, ProveCall{&pk_handle, true, count, wires, pub_inputs, num_inputs, ext_msg, ext_msg_len, nullptr,
+                                       nullptr, blinders, input_form, proofs_out}, false, ticket_out);
 }
 
 int capgpu_plonk_prove_multi_async(const uint64_t* pk_handles, int count, const uint64_t* wires,
                                    const uint64_t* pub_inputs, size_t num_inputs, const uint8_t* const* ext_msgs,
                                    const size_t* ext_msg_lens, const uint64_t* blinders, int input_form,
                                    capgpu_proof* proofs_out, uint64_t* ticket_out) {
-  CAP_CHECK_INIT();
-  if (bad_form(input_form)) return CAPGPU_ERR_INVALID_ARG;
-  if (count < 0 || (count && (!wires || !pk_handles)) || !ticket_out) {
-    set_error("capgpu_plonk_prove_multi: bad argument");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  *ticket_out = 0;
-  if (count == 0) return CAPGPU_OK;
-  AsyncJob j;
-  j.homes.resize((size_t)count);
-  int rc = home_key(pk_handles[0], &j.homes[0]);
-  if (rc) return rc;
-  if (!blinders || !proofs_out || (num_inputs && !pub_inputs) || (ext_msgs && !ext_msg_lens)) {
-    set_error("capgpu_plonk_prove_multi: bad argument");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  // every key is known, and they share the domain size and the SRS: what the synchronous call finds out on the device
-  size_t max_ni = 0;
-  for (int i = 0; i < count; i++) {
-    if (i && (rc = home_key(pk_handles[i], &j.homes[(size_t)i]))) return rc;
-    const ProvingKey &K = *j.homes[0], &Kp = *j.homes[(size_t)i];
-    if (Kp.n != K.n || Kp.srs_handle != K.srs_handle || Kp.recompute || K.recompute) {
-      set_error("capgpu_plonk_prove_multi: the keys of one batch must share the domain size and the SRS");
-      return CAPGPU_ERR_INVALID_ARG;
-    }
-    max_ni = std::max(max_ni, Kp.num_inputs);
-  }
-  if (num_inputs != max_ni) {
-    set_error("capgpu_plonk_prove_multi: rows of %zu public inputs given, the keys need %zu", num_inputs, max_ni);
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  if ((rc = input_stride(pk_handles, count, input_form, j.homes[0]->n, &j.stride))) return rc;
-  if (async_refused_by_sharding()) return CAPGPU_ERR_INVALID_ARG;
-  j.multi = true;
-  j.count = count;
-  j.pks.assign(pk_handles, pk_handles + count);
-  j.wires = wires;
-  j.pub_inputs = pub_inputs;
-  j.blinders = blinders;
-  j.proofs_out = proofs_out;
-  j.num_inputs = num_inputs;
-  j.n = j.homes[0]->n;
-  j.input_form = input_form;
-  j.has_msgs = ext_msgs != nullptr;
-  if (ext_msgs) {
-    j.msgs.resize((size_t)count);
-    for (int i = 0; i < count; i++)
-      if (ext_msgs[i] && ext_msg_lens[i]) j.msgs[(size_t)i].assign(ext_msgs[i], ext_msgs[i] + ext_msg_lens[i]);
-  }
-  j.bound_slot = thread_bound_slot();
-  return submit_ticket(std::move(j), ticket_out);
+  return prove_async(kProveMulti, ProveCall{pk_handles, false, count, wires, pub_inputs, num_inputs, nullptr, 0, ext_msgs,
+                                            ext_msg_lens, blinders, input_form, proofs_out}, true, ticket_out);
 }
 
 int capgpu_plonk_prove_each_async(const uint64_t* pk_handles, int count, const uint64_t* wires,
                                   const uint64_t* pub_inputs, size_t num_inputs, const uint8_t* const* ext_msgs,
                                   const size_t* ext_msg_lens, const uint64_t* blinders, int input_form,
                                   capgpu_proof* proofs_out, capgpu_prove_outcome* outcomes_out, uint64_t* ticket_out) {
-  if (int rc = each_bad_args(pk_handles, count, wires, pub_inputs, num_inputs, ext_msgs, ext_msg_lens, blinders, input_form,
-                             proofs_out, outcomes_out))
-    return rc;
-  if (!ticket_out) {
-    set_error("capgpu_plonk_prove_multi: bad argument");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
+  ProveCall a = each_call(pk_handles, count, wires, pub_inputs, num_inputs, ext_msgs, ext_msg_lens, blinders, input_form,
+                          proofs_out, outcomes_out);
+  if (int rc = each_bad_args(a)) return rc;
+  if (!ticket_out) return bad_args(kProveMulti);
   CAP_CHECK_INIT();
   *ticket_out = 0;
   if (count == 0) return CAPGPU_OK;
   if (each_refused_by_sharding()) return CAPGPU_ERR_INVALID_ARG;
-  const bool one_key = each_one_key(pk_handles, count);
+  a.one_key = each_one_key(a);
   AsyncJob j;
-  j.homes.resize(one_key ? 1 : (size_t)count);
-  int rc;
-  // every key is known, and they share the domain size and the SRS (capgpu_plonk_prove_multi_async's checks)
-  size_t max_ni = 0;
-  for (size_t i = 0; i < j.homes.size(); i++) {
-    if ((rc = home_key(pk_handles[i], &j.homes[i]))) return rc;
-    const ProvingKey &K = *j.homes[0], &Kp = *j.homes[i];
-    if (Kp.n != K.n || Kp.srs_handle != K.srs_handle || (!one_key && (Kp.recompute || K.recompute))) {
-      set_error("capgpu_plonk_prove_multi: the keys of one batch must share the domain size and the SRS");
-      return CAPGPU_ERR_INVALID_ARG;
-    }
-    max_ni = std::max(max_ni, Kp.num_inputs);
-  }
-  if (num_inputs != max_ni) {
-    if (one_key) set_error("capgpu_plonk_prove: %zu public inputs given, key expects %zu", num_inputs, max_ni);
-    else set_error("capgpu_plonk_prove_multi: rows of %zu public inputs given, the keys need %zu", num_inputs, max_ni);
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  if ((rc = input_stride(pk_handles, one_key ? 1 : count, input_form, j.homes[0]->n, &j.stride))) return rc;
-  j.multi = !one_key;
-  j.count = count;
-  j.pks.assign(pk_handles, pk_handles + (one_key ? 1 : count));
-  j.wires = wires;
-  j.pub_inputs = pub_inputs;
-  j.blinders = blinders;
-  j.proofs_out = proofs_out;
-  j.outcomes = outcomes_out;
-  j.num_inputs = num_inputs;
-  j.n = j.homes[0]->n;
-  j.input_form = input_form;
-  j.has_msgs = ext_msgs != nullptr;
-  if (ext_msgs) {
-    j.msgs.resize((size_t)count);
-    for (int i = 0; i < count; i++)
-      if (ext_msgs[i] && ext_msg_lens[i]) j.msgs[(size_t)i].assign(ext_msgs[i], ext_msgs[i] + ext_msg_lens[i]);
-  }
-  j.bound_slot = thread_bound_slot();
+  // (a recompute key is refused only among DIFFERENT keys: one key takes the single-key path)
+  if (int rc = fill_job(a, !a.one_key, &j)) return rc;
   return submit_ticket(std::move(j), ticket_out);
 }
+
 
 int capgpu_wait(uint64_t ticket, uint32_t timeout_ms, int* done_out) {
   CAP_CHECK_INIT();
@@ -2829,23 +2649,12 @@ static void run_coalesced(std::vector<ProveReq*>& reqs) {
     int rc = lookup_key(r->pk, &K);
     const bool rv = r->form == CAPGPU_INPUT_VARS;
     if (rc == CAPGPU_OK && rv && key_lacks_table(*K)) rc = CAPGPU_ERR_INVALID_ARG;
-    if (rc == CAPGPU_OK)
-      rc = scratch_reserve(c.stage_b, rv ? vars_stage_bytes(1, K->n, K->num_vars, true) : wires_stage_bytes(1, K->n));
     if (rc == CAPGPU_OK) {
-      const uint64_t* row = r->wires;
-      const VarsIn vin{(const fe*)c.stage_b.p + (size_t)NW * K->n, K->num_vars};
-      ProveRequest rq;
-      rq.d_wires = (const fe*)c.stage_b.p;
-      rq.pub_inputs = r->pubs;
-      rq.num_inputs = r->num_inputs;
-      rq.blinders = r->blinders;
-      rq.proofs = r->out;
-      rq.ext_msg = r->msg;
-      rq.ext_len = r->msg_len;
-      rq.h_wires = &row;
-      rq.form = r->form;
-      rq.vin = rv ? &vin : nullptr;
-      rc = prove_batch(*K, 1, rq);
+      ProveCall one{&r->pk, true, 1, r->wires, r->pubs, r->num_inputs, r->msg, r->msg_len, nullptr, nullptr, r->blinders,
+                    r->form, r->out};
+      one.n = K->n;
+      one.stride = rv ? K->num_vars : (size_t)NW * K->n;
+      rc = host_part(one, 0, 1);
     }
     r->rc = rc;
     if (rc) r->err = capgpu_last_error();
@@ -3035,15 +2844,12 @@ int capgpu_plonk_prove_ex(uint64_t pk_handle, const uint64_t* wires, const uint6
                           const uint8_t* ext_msg, size_t ext_msg_len, const uint64_t* blinders, int input_form,
                           capgpu_proof* proof_out) {
   Coalescer& co = coalescer();
-  if (co.window_us == 0)
-    return capgpu_plonk_prove_batch_ex(pk_handle, 1, wires, pub_inputs, num_inputs, ext_msg, ext_msg_len, blinders,
-                                       input_form, proof_out);
+  const ProveCall a{&pk_handle, true, 1, wires, pub_inputs, num_inputs, ext_msg, ext_msg_len, nullptr, nullptr, blinders,
+                    input_form, proof_out};
+  if (co.window_us == 0) return prove_host(kProve, a);
   CAP_CHECK_INIT();
   if (bad_form(input_form)) return CAPGPU_ERR_INVALID_ARG;
-  if (!wires || !blinders || !proof_out || (num_inputs && !pub_inputs)) {
-    set_error("capgpu_plonk_prove: bad argument");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
+  if (bad_front(a) || bad_rest(a)) return bad_args(kProve);
   size_t var_elems = 0;  // variable form: the values this call brings (and the refusal of a key without a table)
   if (input_form == CAPGPU_INPUT_VARS) {
     int rc = input_stride(&pk_handle, 1, input_form, 0, &var_elems);
@@ -3140,30 +2946,19 @@ int capgpu_plonk_prove_ex(uint64_t pk_handle, const uint64_t* wires, const uint6
     void release(void* ctx) { static_cast<Context*>(ctx)->mu.unlock(); }
     size_t deal_min() { return (size_t)::deal_min(); }
     size_t split_eighths() {  // CAPGPU_COALESCE_SPLIT = eighths of the first part
-      static const size_t eighths = [] {
-        const char* e = getenv("CAPGPU_COALESCE_SPLIT");
-        const int x = e ? atoi(e) : 3;
-        return (size_t)(x >= 1 && x <= 4 ? x : 3);
-      }();
+      static const size_t eighths = (size_t)env_int("CAPGPU_COALESCE_SPLIT", 3, 1, 4);
       return eighths;
     }
     // batch parts running at once before a leader keeps collecting instead of taking another free context:
     // CAPGPU_COALESCE_INFLIGHT (default 2) per bound DEVICE - two large batches fill a GPU, a third only fragments them
     size_t max_in_flight() {
-      static const size_t per_device = [] {
-        const char* e = getenv("CAPGPU_COALESCE_INFLIGHT");
-        const int x = e ? atoi(e) : 2;
-        return (size_t)(x >= 1 && x <= 64 ? x : 2);
-      }();
+      static const size_t per_device = (size_t)env_int("CAPGPU_COALESCE_INFLIGHT", 2, 1, 64);
       int devices = 1;
       (void)capgpu_physical_device_count(&devices);
       return per_device * (size_t)std::max(devices, 1);
     }
     bool early_release() {  // CAPGPU_COALESCE_EARLY=0: a cut batch's callers return when both parts are done, as before
-      static const bool early = [] {
-        const char* e = getenv("CAPGPU_COALESCE_EARLY");
-        return !e || atoi(e) != 0;
-      }();
+      static const bool early = env_int("CAPGPU_COALESCE_EARLY", 1) != 0;
       return early;
     }
   } hooks;
@@ -3186,18 +2981,13 @@ static int check_part(const uint64_t* pk_handles, uint64_t pk_handle, uint32_t c
                       capgpu_witness_fault* faults, size_t stride) {
   Context& c = ctx();
   Entry lk(c);
-  std::vector<std::shared_ptr<ProvingKey>> hold(pk_handles ? cnt : 1);
-  std::vector<const ProvingKey*> keys(hold.size());
-  int rc;
-  for (size_t i = 0; i < hold.size(); i++) {
-    if ((rc = lookup_key(pk_handles ? pk_handles[i] : pk_handle, &hold[i]))) return rc;
-    keys[i] = hold[i].get();
-    if (keys[i]->n != keys[0]->n || keys[i]->srs_handle != keys[0]->srs_handle) {
-      set_error("capgpu_plonk_check_witness_multi: the keys of one batch must share the domain size and the SRS");
-      return CAPGPU_ERR_INVALID_ARG;
-    }
-  }
-  const size_t n = keys[0]->n;
+  PartKeys held;
+  KeySet ks;
+  int rc = keys_in_rule(kCheckMulti, lookup_key, pk_handles ? pk_handles : &pk_handle, pk_handles ? cnt : 1, true, false,
+                        &held, &ks);
+  if (rc) return rc;
+  const std::vector<const ProvingKey*>& keys = held.ptr;
+  const size_t n = ks.n;
   if (form == CAPGPU_INPUT_VARS) {
     // rows of `stride` values per witness -> the five columns, in staging; then the gate pass alone: gathered columns
     // satisfy every copy constraint
@@ -3224,14 +3014,13 @@ static int check_part(const uint64_t* pk_handles, uint64_t pk_handle, uint32_t c
   return check_resident(*keys[0], pk_handles ? &keys : nullptr, cnt, (const fe*)d_wires, pubs, num_inputs, form, faults);
 }
 
-int capgpu_plonk_check_witness_batch_dev(uint64_t pk_handle, int count, const void* d_wires, const uint64_t* pub_inputs,
-                                         size_t num_inputs, int input_form, capgpu_witness_fault* faults_out) {
+// capgpu_plonk_check_witness_batch (h_wires: dealt over the contexts) and _batch_dev (d_wires: on the caller's context)
+static int check_one_key(uint64_t pk_handle, int count, const uint64_t* h_wires, const void* d_wires,
+                         const uint64_t* pub_inputs, size_t num_inputs, int input_form, capgpu_witness_fault* faults_out) {
   CAP_CHECK_INIT();
   if (bad_form(input_form)) return CAPGPU_ERR_INVALID_ARG;
-  if (count < 0 || (count && (!d_wires || !faults_out || (num_inputs && !pub_inputs)))) {
-    set_error("capgpu_plonk_check_witness: bad argument");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
+  if (count < 0 || (count && ((!h_wires && !d_wires) || !faults_out || (num_inputs && !pub_inputs))))
+    return bad_args("capgpu_plonk_check_witness");
   if (count == 0) return CAPGPU_OK;
   std::shared_ptr<ProvingKey> K0;
   int rc = home_key(pk_handle, &K0);
@@ -3242,33 +3031,22 @@ int capgpu_plonk_check_witness_batch_dev(uint64_t pk_handle, int count, const vo
   }
   size_t stride = 0;
   if ((rc = input_stride(&pk_handle, 1, input_form, K0->n, &stride))) return rc;
-  return check_part(nullptr, pk_handle, (uint32_t)count, nullptr, d_wires, pub_inputs, num_inputs, input_form, faults_out,
-                    stride);
-}
-
-int capgpu_plonk_check_witness_batch(uint64_t pk_handle, int count, const uint64_t* wires, const uint64_t* pub_inputs,
-                                     size_t num_inputs, int input_form, capgpu_witness_fault* faults_out) {
-  CAP_CHECK_INIT();
-  if (bad_form(input_form)) return CAPGPU_ERR_INVALID_ARG;
-  if (count < 0 || (count && (!wires || !faults_out || (num_inputs && !pub_inputs)))) {
-    set_error("capgpu_plonk_check_witness: bad argument");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  if (count == 0) return CAPGPU_OK;
-  std::shared_ptr<ProvingKey> K0;
-  int rc0 = home_key(pk_handle, &K0);
-  if (rc0) return rc0;
-  if (num_inputs != K0->num_inputs) {
-    set_error("capgpu_plonk_check_witness: %zu public inputs given, key expects %zu", num_inputs, K0->num_inputs);
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  size_t stride = 0;
-  if ((rc0 = input_stride(&pk_handle, 1, input_form, K0->n, &stride))) return rc0;
+  if (d_wires)
+    return check_part(nullptr, pk_handle, (uint32_t)count, nullptr, d_wires, pub_inputs, num_inputs, input_form, faults_out,
+                      stride);
   return deal(count, [&](int first, int cnt) -> int {
-    return check_part(nullptr, pk_handle, (uint32_t)cnt, wires + (size_t)4 * first * stride, nullptr,
+    return check_part(nullptr, pk_handle, (uint32_t)cnt, h_wires + (size_t)4 * first * stride, nullptr,
                       pub_inputs ? pub_inputs + (size_t)4 * first * num_inputs : nullptr, num_inputs, input_form,
                       faults_out + first, stride);
   });
+}
+int capgpu_plonk_check_witness_batch_dev(uint64_t pk_handle, int count, const void* d_wires, const uint64_t* pub_inputs,
+                                         size_t num_inputs, int input_form, capgpu_witness_fault* faults_out) {
+  return check_one_key(pk_handle, count, nullptr, d_wires, pub_inputs, num_inputs, input_form, faults_out);
+}
+int capgpu_plonk_check_witness_batch(uint64_t pk_handle, int count, const uint64_t* wires, const uint64_t* pub_inputs,
+                                     size_t num_inputs, int input_form, capgpu_witness_fault* faults_out) {
+  return check_one_key(pk_handle, count, wires, nullptr, pub_inputs, num_inputs, input_form, faults_out);
 }
 
 int capgpu_plonk_check_witness(uint64_t pk_handle, const uint64_t* wires, const uint64_t* pub_inputs, size_t num_inputs,
@@ -3281,35 +3059,27 @@ int capgpu_plonk_check_witness_multi(const uint64_t* pk_handles, int count, cons
                                      capgpu_witness_fault* faults_out) {
   CAP_CHECK_INIT();
   if (bad_form(input_form)) return CAPGPU_ERR_INVALID_ARG;
-  if (count < 0 || (count && (!pk_handles || !wires || !faults_out || (num_inputs && !pub_inputs)))) {
-    set_error("capgpu_plonk_check_witness_multi: bad argument");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
+  if (count < 0 || (count && (!pk_handles || !wires || !faults_out || (num_inputs && !pub_inputs))))
+    return bad_args(kCheckMulti);
   if (count == 0) return CAPGPU_OK;
-  size_t n = 0, max_ni = 0;
-  for (int i = 0; i < count; i++) {
-    std::shared_ptr<ProvingKey> Ki;
-    int rc = home_key(pk_handles[i], &Ki);
-    if (rc) return rc;
-    if (i == 0) n = Ki->n;
-    if (Ki->n != n) {
-      set_error("capgpu_plonk_check_witness_multi: the keys of one batch must share the domain size and the SRS");
-      return CAPGPU_ERR_INVALID_ARG;
-    }
-    max_ni = std::max(max_ni, Ki->num_inputs);
-  }
-  if (num_inputs != max_ni) {
-    set_error("capgpu_plonk_check_witness_multi: rows of %zu public inputs given, the keys need %zu", num_inputs, max_ni);
+  // (the domain size alone: the parts compare the SRS where the keys are resident, check_part)
+  PartKeys homes;
+  KeySet ks;
+  if (int rc = keys_in_rule(kCheckMulti, home_key, pk_handles, (size_t)count, false, false, &homes, &ks)) return rc;
+  if (num_inputs != ks.max_inputs) {
+    set_error("capgpu_plonk_check_witness_multi: rows of %zu public inputs given, the keys need %zu", num_inputs,
+              ks.max_inputs);
     return CAPGPU_ERR_INVALID_ARG;
   }
   size_t stride = 0;
-  if (int rc = input_stride(pk_handles, count, input_form, n, &stride)) return rc;
+  if (int rc = input_stride(pk_handles, count, input_form, ks.n, &stride)) return rc;
   return deal(count, [&](int first, int cnt) -> int {
     return check_part(pk_handles + first, 0, (uint32_t)cnt, wires + (size_t)4 * first * stride, nullptr,
                       pub_inputs ? pub_inputs + (size_t)4 * first * num_inputs : nullptr, num_inputs, input_form,
                       faults_out + first, stride);
   });
 }
+
 
 int capgpu_plonk_set_precheck(int on) {
   g_precheck.store(on != 0);

@@ -254,9 +254,7 @@ int compute_pk_kx(hipStream_t s, const ProvingKey& K, fe* dst) {
 // form for every proof (A/B in one build); 2 - folded, with every proof's 1 / beta zeroed first: all of them take the route
 // of a proof with beta = 0 (the folded launch leaves them out, the direct launch behind it takes them) - for tests.
 int quotient_fold() {
-  const char* e = getenv("CAPGPU_QUOT_FOLD");
-  const int v = e ? atoi(e) : 1;
-  return v >= 0 && v <= 2 ? v : 1;
+  return env_int("CAPGPU_QUOT_FOLD", 1, 0, 2);
 }
 
 // Round 1's wire commitments: from the wire polynomials' coefficients (jf-plonk's way: KZG10::commit under
@@ -288,10 +286,7 @@ int transcript_mode() {
 }
 // the round-2 inversion as a device kernel (the pre-round-4 schedule); the device transcript always does
 bool perm_inv_on_device() {
-  static const bool on = [] {
-    const char* e = getenv("CAPGPU_PERM_INV_ON_DEVICE");
-    return e && atoi(e) != 0;
-  }();
+  static const bool on = env_int("CAPGPU_PERM_INV_ON_DEVICE", 0) != 0;
   return on;
 }
 // The witnesses are checked against their circuits before anything is committed to (the check itself: plonk.hip).
@@ -314,8 +309,7 @@ hipStream_t h2d_stream() {
 // even, batches of 8 and 16 1-2 % SLOWER - there the transforms no longer fit beside the MSMs, they only slow them down.
 uint32_t r1_overlap_max() {
   static const uint32_t v = [] {
-    const char* e = getenv("CAPGPU_R1_OVERLAP_MAX");
-    const int x = e ? atoi(e) : 3;
+    const int x = env_int("CAPGPU_R1_OVERLAP_MAX", 3);
     return (uint32_t)(x < 0 ? 0 : (x > 4096 ? 4096 : x));
   }();
   return v;
@@ -358,20 +352,13 @@ struct H2dTurn {
 thread_local H2dTurn* tl_h2d_turn = nullptr;
 thread_local uint32_t tl_h2d_index = 0;
 static bool h2d_in_part_order() {
-  static const bool on = [] {
-    const char* e = getenv("CAPGPU_H2D_PART_ORDER");
-    return !e || atoi(e) != 0;
-  }();
+  static const bool on = env_int("CAPGPU_H2D_PART_ORDER", 1) != 0;
   return on;
 }
 
 // chunks of proofs the host-resident wire columns of a batch are copied and committed in (round 1 of prove_batch)
 uint32_t h2d_chunks(uint32_t P) {
-  static const int forced = [] {
-    const char* e = getenv("CAPGPU_PROVE_CHUNKS");  // tests: any batch in 1..16 chunks
-    const int x = e ? atoi(e) : 0;
-    return x >= 1 && x <= 16 ? x : 0;
-  }();
+  static const int forced = env_int("CAPGPU_PROVE_CHUNKS", 0, 1, 16);  // tests: any batch in 1..16 chunks
   if (forced) return std::min<uint32_t>((uint32_t)forced, P);
   return P >= 64 ? 4u : (P >= 32 ? 2u : 1u);  // a chunk's commitments should still fill the chip (>= 80 MSMs)
 }
@@ -379,11 +366,7 @@ uint32_t h2d_chunks(uint32_t P) {
 // starts on an idle device is kept short (CAPGPU_PROVE_FIRST_CHUNK proofs, default 16; 0 = equal chunks): nothing runs
 // until it has landed.
 uint32_t h2d_chunk_start(uint32_t P, uint32_t chunks, uint32_t ck, bool short_first) {
-  static const uint32_t first = [] {
-    const char* e = getenv("CAPGPU_PROVE_FIRST_CHUNK");
-    const int x = e ? atoi(e) : 16;
-    return (uint32_t)(x >= 0 && x <= 4096 ? x : 16);
-  }();
+  static const uint32_t first = (uint32_t)env_int("CAPGPU_PROVE_FIRST_CHUNK", 16, 0, 4096);
   if (ck == 0) return 0;
   if (ck >= chunks) return P;
   if (!short_first || first == 0 || chunks < 3 || first * chunks >= P) return (uint32_t)((uint64_t)P * ck / chunks);
