@@ -357,6 +357,27 @@ extern "C" {
                                          rows_moved_out: *mut u64) -> c_int;
     pub fn capgpu_async_stats(submitted_out: *mut u64, completed_out: *mut u64, max_running_out: *mut u32) -> c_int;
     pub fn capgpu_plonk_reserve(pk_handle: u64, count: c_int, input_form: c_int, slot: c_int) -> c_int;
+    // ---- proving from the values a circuit is given: the solver and the variable-form outcome call in one
+    pub fn capgpu_plonk_set_solve_pack(w: c_int) -> c_int;
+    pub fn capgpu_plonk_get_solve_pack(w_out: *mut c_int) -> c_int;
+    pub fn capgpu_plonk_solve_stats(launches_out: *mut u64, witnesses_out: *mut u64,
+                                    packed_launches_out: *mut u64) -> c_int;
+    pub fn capgpu_plonk_prove_given(pk_handles: *const u64, count: c_int, given: *const u64, pub_inputs: *const u64,
+                                    num_inputs: usize, ext_msgs: *const *const u8, ext_msg_lens: *const usize,
+                                    blinders: *const u64, proofs_out: *mut capgpu_proof,
+                                    outcomes_out: *mut capgpu_prove_outcome,
+                                    solved_out: *mut capgpu_solve_status) -> c_int;
+    pub fn capgpu_plonk_prove_given_dev(pk_handles: *const u64, count: c_int, d_given: *const c_void,
+                                        pub_inputs: *const u64, num_inputs: usize, ext_msgs: *const *const u8,
+                                        ext_msg_lens: *const usize, blinders: *const u64,
+                                        proofs_out: *mut capgpu_proof, outcomes_out: *mut capgpu_prove_outcome,
+                                        solved_out: *mut capgpu_solve_status) -> c_int;
+    pub fn capgpu_plonk_prove_given_async(pk_handles: *const u64, count: c_int, given: *const u64,
+                                          pub_inputs: *const u64, num_inputs: usize, ext_msgs: *const *const u8,
+                                          ext_msg_lens: *const usize, blinders: *const u64,
+                                          proofs_out: *mut capgpu_proof, outcomes_out: *mut capgpu_prove_outcome,
+                                          solved_out: *mut capgpu_solve_status, ticket_out: *mut u64) -> c_int;
+    pub fn capgpu_plonk_reserve_given(pk_handle: u64, count: c_int, slot: c_int) -> c_int;
     // ---- verification (host only)
     pub fn capgpu_g2_generator(out: *mut u64) -> c_int;
     pub fn capgpu_g2_mul(q: *const u64, scalar: *const u64, out: *mut u64) -> c_int;

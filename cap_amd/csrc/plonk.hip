@@ -57,6 +57,7 @@ struct SolveSched {
   sp::Plan plan;
   std::vector<fe> konst;  // per row of plan.rows: 1 / q_o or 1 / q_hash_i, internal form, canonical
   capgpu_solver_info info{};
+  int auto_pack = 1;  // the schedule's term of the automatic witnesses-per-workgroup rule (spk::auto_pack)
 };
 
 struct ProvingKey {
@@ -993,6 +994,7 @@ void plonk_reset_staging() {
   g_compact_calls.store(0);  // (capgpu_plonk_compaction_stats likewise)
   g_compact_dropped.store(0);
   g_compact_rows.store(0);
+  solve_stats_reset();  // (capgpu_plonk_solve_stats)
 }
 
 // the registry's (home) copy of a key, without replicating it
@@ -1641,6 +1643,18 @@ const sv29::Exps* solve_exps() {
   return d.ok ? &d.ex : nullptr;
 }
 
+// capgpu_plonk_set_solve_pack: witnesses per workgroup of the solver's launches; 0: the automatic rule (solve_pack.hpp).
+// -1: the process default (CAPGPU_SOLVE_PACK; a value that is no setting counts as 0)
+std::atomic<int> g_solve_pack{-1};
+int solve_pack_setting() {
+  static const int env_default = [] {
+    const int e = env_int("CAPGPU_SOLVE_PACK", 0);
+    return spk::valid_setting(e) ? e : 0;
+  }();
+  const int m = g_solve_pack.load(std::memory_order_relaxed);
+  return m < 0 ? env_default : m;
+}
+
 // 1 / x for every x of v (internal form, none zero), in place: one inversion and three products per element
 void solve_batch_inverse(std::vector<fl>& v) {
   if (v.empty()) return;
@@ -1758,7 +1772,8 @@ int solve_run(uint64_t pk_handle, uint32_t count, const uint64_t* h_given, uint6
   }
   if (h_vars) d_vars = v;
   CAP_HIP(hipMemsetAsync(d_st, 0xff, sizeof(unsigned long long) * count, s));
-  solve_launch(s, count, (const fe*)d_given, tab, *ex, (fe*)d_vars, d_st);
+  solve_launch_packed(s, spk::pack_for(solve_pack_setting(), hold->auto_pack, count),
+                      SolveLaunch{count, (const fe*)d_given, tab.num_given, (fe*)d_vars, tab.num_vars, d_st, nullptr}, tab, *ex);
   std::vector<unsigned long long> h_st(count);
   CAP_HIP(hipMemcpyAsync(h_st.data(), d_st, sizeof(unsigned long long) * count, hipMemcpyDeviceToHost, s));
   if (h_vars) CAP_HIP(hipMemcpyAsync(h_vars, d_vars, sizeof(fe) * var_elems, hipMemcpyDeviceToHost, s));
@@ -1842,6 +1857,7 @@ int capgpu_plonk_key_set_given(uint64_t pk_handle, const uint32_t* given_vars, s
     static std::atomic<uint64_t> next_uid{1};
     S->uid = next_uid.fetch_add(1);
     S->info = capgpu_solver_info{P.num_given, P.num_defined, P.levels, P.widest_level, P.inv_rows, P.root_rows};
+    S->auto_pack = spk::auto_pack(spk::median_level_width(P.level_off.data(), P.levels), kSolveThreads);
   }
   // the key and the replicas other devices hold take the schedule; each uploads its tables on its next solve
   for (auto& cp : R.ctxs) {
@@ -2051,6 +2067,12 @@ struct ProveCall {
   size_t n = 0;
   size_t stride = 0;  // elements per proof of `wires`: 5 n, or the largest num_vars among the keys of the WHOLE call
   const std::shared_ptr<ProvingKey>* homes = nullptr;  // tickets: the home of every handle, see part_key
+  // capgpu_plonk_prove_given*: the input is the values each circuit is GIVEN - `wires` stays null, `form` is
+  // CAPGPU_INPUT_VARS (what the solver's result is) and given_part takes the place of host_part / prove_resident
+  const void* given = nullptr;            // host memory, or - given_dev - a device address
+  bool given_dev = false;
+  capgpu_solve_status* solved = nullptr;  // optional: the solver's verdict per proof
+  size_t given_stride = 0;                // elements per proof of `given`: the largest num_given among the keys of the WHOLE call
   size_t num_keys() const { return one_key ? 1 : (size_t)count; }
 };
 static const char kProve[] = "capgpu_plonk_prove", kProveMulti[] = "capgpu_plonk_prove_multi",
@@ -2112,6 +2134,26 @@ static ProveRequest request_of(const ProveCall& b, int first, const PartKeys& ke
   return rq;
 }
 
+// several keys: a part's rows carry `num_inputs` = the largest count among the keys of the WHOLE call; prove_batch wants
+// the largest among its own keys: re-pack (into *pubs) when the part's maximum is smaller
+static int part_pub_rows(const ProveCall& b, const PartKeys& keys, int cnt, ProveRequest* rq, std::vector<uint64_t>* pubs) {
+  if (b.one_key) return CAPGPU_OK;
+  size_t ni = 0;
+  for (const ProvingKey* k : keys.ptr) ni = std::max(ni, k->num_inputs);
+  if (ni > b.num_inputs) {
+    set_error("capgpu_plonk_prove_multi: rows of %zu public inputs given, the keys need %zu", b.num_inputs, ni);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  if (ni < b.num_inputs) {
+    pubs->assign((size_t)4 * ni * cnt + 4, 0);
+    for (int i = 0; i < cnt; i++)
+      if (ni) memcpy(&(*pubs)[(size_t)4 * ni * i], rq->pub_inputs + (size_t)4 * b.num_inputs * i, 32 * ni);
+    rq->pub_inputs = pubs->data();
+    rq->num_inputs = ni;
+  }
+  return CAPGPU_OK;
+}
+
 static int host_part(const ProveCall& b, int first, int cnt) {
   Context& c = ctx();
   Entry lk(c);
@@ -2120,24 +2162,8 @@ static int host_part(const ProveCall& b, int first, int cnt) {
   int rc = part_keys(b, first, cnt, &keys);
   if (rc) return rc;
   ProveRequest rq = request_of(b, first, keys);
-  // several keys: a part's rows carry `num_inputs` = the largest count among the keys of the WHOLE call; prove_batch wants
-  // the largest among its own keys: re-pack when the part's maximum is smaller
   std::vector<uint64_t> pubs;
-  if (!b.one_key) {
-    size_t ni = 0;
-    for (const ProvingKey* k : keys.ptr) ni = std::max(ni, k->num_inputs);
-    if (ni > b.num_inputs) {
-      set_error("capgpu_plonk_prove_multi: rows of %zu public inputs given, the keys need %zu", b.num_inputs, ni);
-      return CAPGPU_ERR_INVALID_ARG;
-    }
-    if (ni < b.num_inputs) {
-      pubs.assign((size_t)4 * ni * cnt + 4, 0);
-      for (int i = 0; i < cnt; i++)
-        if (ni) memcpy(&pubs[(size_t)4 * ni * i], rq.pub_inputs + (size_t)4 * b.num_inputs * i, 32 * ni);
-      rq.pub_inputs = pubs.data();
-      rq.num_inputs = ni;
-    }
-  }
+  if ((rc = part_pub_rows(b, keys, cnt, &rq, &pubs))) return rc;
   const bool vars = b.form == CAPGPU_INPUT_VARS;
   rc = scratch_reserve(c.stage_b, vars ? vars_stage_bytes((size_t)cnt, n, b.stride, true) : wires_stage_bytes((size_t)cnt, n));
   if (rc) return rc;
@@ -2171,6 +2197,135 @@ static int prove_resident(const ProveCall& a) {
     rq.vin = &vin;
   }
   return prove_batch(*keys.ptr[0], (uint32_t)a.count, rq);
+}
+
+// ---- proving from given values (capgpu_plonk_prove_given*) -------------------------------------------------------------
+static const char kProveGiven[] = "capgpu_plonk_prove_given";
+// Context::stage_b of `cnt` proofs from given values: the columns and, behind them, the value vectors - the layout of the
+// variable form in library staging (vars_stage_bytes), which the solver fills instead of a copy -, then the solver's status
+// words, its witness lists (calls with several keys) and - host-resident values only - the staged given rows.
+struct GivenStage {
+  fe *cols = nullptr, *vars = nullptr, *given = nullptr;
+  unsigned long long* status = nullptr;
+  uint32_t* which = nullptr;
+  size_t bytes = 0;
+};
+static GivenStage given_carve(void* base, size_t cnt, size_t n, size_t var_stride, size_t given_stride, bool host) {
+  GivenStage g;
+  Carver k(base);
+  g.cols = k.take<fe>(cnt * NW * n + cnt * var_stride);  // (one piece: VarsIn of a staged call starts where the columns end)
+  g.vars = base ? g.cols + cnt * NW * n : nullptr;
+  g.status = k.take<unsigned long long>(cnt);
+  g.which = k.take<uint32_t>(cnt);
+  if (host) g.given = k.take<fe>(cnt * given_stride + 1);
+  g.bytes = k.off + 256;
+  return g;
+}
+// The pinned result area of such a part: the prover's own in either transcript home (its carving starts at the base),
+// and behind it the status words, which come back with the proofs - no host wait is added for them.
+static size_t given_pinned_offset(uint32_t P) {
+  return (std::max(prove_pinned_bytes(P, true), prove_pinned_bytes(P, false)) + 255) / 256 * 256;
+}
+static size_t given_pinned_bytes(uint32_t P) { return given_pinned_offset(P) + sizeof(unsigned long long) * P + 256; }
+
+static int no_solver(const char* who) {
+  set_error("%s: the key has no solver (capgpu_plonk_key_set_given gives it one)", who);
+  return CAPGPU_ERR_INVALID_ARG;
+}
+
+// Proofs [first, first + cnt) of a given-value call on the current context: stage the given rows (one copy), solve them
+// on the proving stream into library scratch - one launch per distinct key, over that key's proofs -, and from there the
+// variable-form outcome call on a library-owned buffer (prove_resident's request, columns and values in Context::stage_b).
+static int given_part(const ProveCall& b, int first, int cnt) {
+  Context& c = ctx();
+  Entry lk(c);
+  PartKeys keys;
+  int rc = part_keys(b, first, cnt, &keys);
+  if (rc) return rc;
+  const sv29::Exps* ex = solve_exps();
+  if (!ex) {
+    set_error("%s: (r - 1) mod 5 != 1: the scalar field has no fifth-root exponent", kProveGiven);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  ProveRequest rq = request_of(b, first, keys);
+  std::vector<uint64_t> pubs;
+  if ((rc = part_pub_rows(b, keys, cnt, &rq, &pubs))) return rc;
+  // the distinct keys of the part, in order of first appearance, each with the proofs it proves
+  struct KeyRun {
+    const ProvingKey* K;
+    SolveTables tab;
+    std::shared_ptr<const SolveSched> hold;
+    std::vector<uint32_t> which;
+  };
+  std::vector<KeyRun> runs;
+  for (int i = 0; i < cnt; i++) {
+    const ProvingKey* K = keys.ptr[b.one_key ? 0 : (size_t)i];
+    size_t r = 0;
+    while (r < runs.size() && runs[r].K != K) r++;
+    if (r == runs.size()) {
+      {
+        std::lock_guard<std::mutex> klk(K->chk_mu);
+        if (!K->solve || !K->wire_vars) return no_solver(kProveGiven);
+      }
+      runs.push_back(KeyRun{K, SolveTables{}, nullptr, {}});
+      if ((rc = key_check_tables(*K))) return rc;
+      if ((rc = solve_tables(*K, &runs[r].tab, &runs[r].hold))) return rc;
+      if (runs[r].tab.num_given > b.given_stride || K->num_vars > b.stride) {
+        set_error("%s: rows of %zu given values and %zu variables, the key of proof %d has %zu and %zu", kProveGiven,
+                  b.given_stride, b.stride, first + i, runs[r].tab.num_given, K->num_vars);
+        return CAPGPU_ERR_INVALID_ARG;
+      }
+    }
+    runs[r].which.push_back((uint32_t)i);
+  }
+  const size_t n = keys.ptr[0]->n;
+  const bool host = !b.given_dev;
+  if ((rc = scratch_reserve(c.stage_b, given_carve(nullptr, (size_t)cnt, n, b.stride, b.given_stride, host).bytes))) return rc;
+  if ((rc = pinned_reserve(c, given_pinned_bytes((uint32_t)cnt)))) return rc;
+  const GivenStage g = given_carve(c.stage_b.p, (size_t)cnt, n, b.stride, b.given_stride, host);
+  unsigned long long* const h_st = (unsigned long long*)((char*)c.pin_host + given_pinned_offset((uint32_t)cnt));
+  hipStream_t s = c.stream;
+  const fe* d_given = (const fe*)b.given + (size_t)first * b.given_stride;
+  if (host) {
+    const size_t bytes = sizeof(fe) * (size_t)cnt * b.given_stride;
+    if (bytes) {
+      CAP_HIP(hipMemcpyAsync(g.given, (const uint64_t*)b.given + (size_t)4 * first * b.given_stride, bytes,
+                             hipMemcpyHostToDevice, s));
+      count_witness_h2d(bytes);
+    }
+    d_given = g.given;
+  }
+  CAP_HIP(hipMemsetAsync(g.status, 0xff, sizeof(unsigned long long) * cnt, s));
+  const int setting = solve_pack_setting();
+  size_t listed = 0;
+  for (KeyRun& r : runs) {
+    const uint32_t* d_which = nullptr;
+    if (runs.size() > 1) {  // (one key: its proofs are 0 .. cnt - 1)
+      uint32_t* at = g.which + listed;
+      CAP_HIP(hipMemcpyAsync(at, r.which.data(), sizeof(uint32_t) * r.which.size(), hipMemcpyHostToDevice, s));
+      d_which = at;
+      listed += r.which.size();
+    }
+    const uint32_t k = (uint32_t)r.which.size();
+    solve_launch_packed(s, spk::pack_for(setting, r.hold->auto_pack, k),
+                        SolveLaunch{k, d_given, b.given_stride, g.vars, b.stride, g.status, d_which}, r.tab, *ex);
+  }
+  CAP_HIP(hipMemcpyAsync(h_st, g.status, sizeof(unsigned long long) * cnt, hipMemcpyDeviceToHost, s));
+  const VarsIn vin{g.vars, b.stride};
+  rq.d_wires = g.cols;
+  rq.vin = &vin;
+  if ((rc = prove_batch(*keys.ptr[0], (uint32_t)cnt, rq))) return rc;
+  // (the proofs are here: the stream has been waited for behind the copy above)
+  if (b.solved)
+    for (int i = 0; i < cnt; i++) {
+      capgpu_solve_status& o = b.solved[first + i];
+      memset(&o, 0, sizeof o);
+      if (h_st[i] != kSolved) {
+        o.kind = 1;
+        o.row = h_st[i];
+      }
+    }
+  return CAPGPU_OK;
 }
 
 // A host-resident call from its first key on: the remaining pointers, the stride, and the parts dealt over the contexts.
@@ -2349,6 +2504,13 @@ int fill_job(const ProveCall& a, bool refuse_recompute, AsyncJob* j) {
   KeySet ks;
   int rc = keys_in_rule(kProveMulti, home_key, a.handles, nk, true, refuse_recompute, &keys, &ks);
   if (rc) return rc;
+  size_t given_stride = 0;
+  if (a.given)  // every key needs its solver; the rows of `given` have the largest list's length
+    for (const ProvingKey* K : keys.ptr) {
+      std::lock_guard<std::mutex> klk(K->chk_mu);
+      if (!K->solve || !K->wire_vars) return no_solver(kProveGiven);
+      given_stride = std::max<size_t>(given_stride, K->solve->plan.num_given);
+    }
   if (a.num_inputs != ks.max_inputs) {
     if (a.one_key) set_error("capgpu_plonk_prove: %zu public inputs given, key expects %zu", a.num_inputs, ks.max_inputs);
     else set_error("capgpu_plonk_prove_multi: rows of %zu public inputs given, the keys need %zu", a.num_inputs, ks.max_inputs);
@@ -2356,6 +2518,7 @@ int fill_job(const ProveCall& a, bool refuse_recompute, AsyncJob* j) {
   }
   j->call = a;
   j->call.n = ks.n;
+  j->call.given_stride = given_stride;
   if ((rc = input_stride(a.handles, (int)nk, a.form, ks.n, &j->call.stride))) return rc;
   j->pks.assign(a.handles, a.handles + nk);
   j->homes = std::move(keys.hold);
@@ -2368,6 +2531,27 @@ int fill_job(const ProveCall& a, bool refuse_recompute, AsyncJob* j) {
   j->bound_slot = thread_bound_slot();
   return CAPGPU_OK;
 }
+// the call of a job with its handles, homes and messages pointed at the job's own copies
+struct JobCall {
+  std::vector<const uint8_t*> mp;
+  std::vector<size_t> ml;
+  ProveCall b;
+  explicit JobCall(const AsyncJob& j) : mp(j.msgs.size()), ml(j.msgs.size()), b(j.call) {
+    for (size_t i = 0; i < j.msgs.size(); i++) {
+      mp[i] = j.msgs[i].empty() ? nullptr : j.msgs[i].data();
+      ml[i] = j.msgs[i].size();
+    }
+    b.handles = j.pks.data();
+    b.homes = j.homes.data();
+    if (b.msgs) {
+      b.msgs = mp.data();
+      b.msg_lens = ml.data();
+    } else {
+      b.ext_msg = mp[0];
+      b.ext_msg_len = ml[0];
+    }
+  }
+};
 using Tickets = TicketTable<AsyncJob>;
 
 uint32_t async_inflight() {  // tickets of one physical device running at once (CAPGPU_ASYNC_INFLIGHT, default 2)
@@ -2423,23 +2607,8 @@ int run_ticket(AsyncJob& j, int lane, std::string* err) {
   int rc;
   {
     ScopedCtx sc(*c);
-    std::vector<const uint8_t*> mp(j.msgs.size());
-    std::vector<size_t> ml(j.msgs.size());
-    for (size_t i = 0; i < j.msgs.size(); i++) {
-      mp[i] = j.msgs[i].empty() ? nullptr : j.msgs[i].data();
-      ml[i] = j.msgs[i].size();
-    }
-    ProveCall b = j.call;
-    b.handles = j.pks.data();
-    b.homes = j.homes.data();
-    if (b.msgs) {
-      b.msgs = mp.data();
-      b.msg_lens = ml.data();
-    } else {
-      b.ext_msg = mp[0];
-      b.ext_msg_len = ml[0];
-    }
-    rc = host_part(b, 0, b.count);
+    const JobCall jc(j);
+    rc = jc.b.given ? given_part(jc.b, 0, jc.b.count) : host_part(jc.b, 0, jc.b.count);
     if (rc) *err = last_error();
   }
   if (locked) c->mu.unlock();
@@ -2551,6 +2720,69 @@ int capgpu_plonk_prove_each_async(const uint64_t* pk_handles, int count, const u
   return submit_ticket(std::move(j), ticket_out);
 }
 
+// ---- capgpu_plonk_prove_given*: outcome calls whose input is the values each circuit is given ---------------------------
+// Everything is refused before a device is touched: the pointers, then - through fill_job, the checks a ticket makes at
+// submission - unknown handles, keys that break the batch's rule, a key without a solver, the row length of the public inputs.
+static int given_checked(const uint64_t* pk_handles, int count, const void* given, bool given_dev, const uint64_t* pub_inputs,
+                         size_t num_inputs, const uint8_t* const* ext_msgs, const size_t* ext_msg_lens,
+                         const uint64_t* blinders, capgpu_proof* proofs_out, capgpu_prove_outcome* outcomes_out,
+                         capgpu_solve_status* solved_out, bool ticket, uint64_t* ticket_out, AsyncJob* j) {
+  ProveCall a = each_call(pk_handles, count, nullptr, pub_inputs, num_inputs, ext_msgs, ext_msg_lens, blinders,
+                          CAPGPU_INPUT_VARS, proofs_out, outcomes_out);
+  a.given = given;
+  a.given_dev = given_dev;
+  a.solved = solved_out;
+  if (count < 0 || (count && (!pk_handles || !given || !outcomes_out)) || bad_rest(a) || (ticket && !ticket_out))
+    return bad_args(kProveGiven);
+  CAP_CHECK_INIT();
+  if (ticket) *ticket_out = 0;
+  if (count == 0) return CAPGPU_OK;
+  if (comm_shard_slot() >= 0 || comm_shard_prover()) {
+    set_error("%s: not available while capgpu_plonk_shard_msm is on (the ranks prove in lock step)", kProveGiven);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  a.one_key = each_one_key(a);
+  return fill_job(a, !a.one_key, j);
+}
+
+int capgpu_plonk_prove_given(const uint64_t* pk_handles, int count, const uint64_t* given, const uint64_t* pub_inputs,
+                             size_t num_inputs, const uint8_t* const* ext_msgs, const size_t* ext_msg_lens,
+                             const uint64_t* blinders, capgpu_proof* proofs_out, capgpu_prove_outcome* outcomes_out,
+                             capgpu_solve_status* solved_out) {
+  AsyncJob j;
+  if (int rc = given_checked(pk_handles, count, given, false, pub_inputs, num_inputs, ext_msgs, ext_msg_lens, blinders,
+                             proofs_out, outcomes_out, solved_out, false, nullptr, &j))
+    return rc;
+  if (count == 0) return CAPGPU_OK;
+  const JobCall jc(j);
+  return deal(count, [&](int first, int cnt) -> int { return given_part(jc.b, first, cnt); });
+}
+
+int capgpu_plonk_prove_given_dev(const uint64_t* pk_handles, int count, const void* d_given, const uint64_t* pub_inputs,
+                                 size_t num_inputs, const uint8_t* const* ext_msgs, const size_t* ext_msg_lens,
+                                 const uint64_t* blinders, capgpu_proof* proofs_out, capgpu_prove_outcome* outcomes_out,
+                                 capgpu_solve_status* solved_out) {
+  AsyncJob j;
+  if (int rc = given_checked(pk_handles, count, d_given, true, pub_inputs, num_inputs, ext_msgs, ext_msg_lens, blinders,
+                             proofs_out, outcomes_out, solved_out, false, nullptr, &j))
+    return rc;
+  if (count == 0) return CAPGPU_OK;
+  const JobCall jc(j);
+  return given_part(jc.b, 0, count);  // on the calling thread's context, as every _dev call
+}
+
+int capgpu_plonk_prove_given_async(const uint64_t* pk_handles, int count, const uint64_t* given, const uint64_t* pub_inputs,
+                                   size_t num_inputs, const uint8_t* const* ext_msgs, const size_t* ext_msg_lens,
+                                   const uint64_t* blinders, capgpu_proof* proofs_out, capgpu_prove_outcome* outcomes_out,
+                                   capgpu_solve_status* solved_out, uint64_t* ticket_out) {
+  AsyncJob j;
+  if (int rc = given_checked(pk_handles, count, given, false, pub_inputs, num_inputs, ext_msgs, ext_msg_lens, blinders,
+                             proofs_out, outcomes_out, solved_out, true, ticket_out, &j))
+    return rc;
+  if (count == 0) return CAPGPU_OK;
+  return submit_ticket(std::move(j), ticket_out);
+}
+
 
 int capgpu_wait(uint64_t ticket, uint32_t timeout_ms, int* done_out) {
   CAP_CHECK_INIT();
@@ -2583,16 +2815,31 @@ int capgpu_async_stats(uint64_t* submitted_out, uint64_t* completed_out, uint32_
 
 // Sizes, without proving anything, what a `count`-proof host-resident batch under this key would grow on context `slot`
 // (-1: every context) - see prove_needs - and brings the key, the SRS and the Lagrange-form commit key there.
+static int reserve_impl(uint64_t pk_handle, int count, int input_form, int slot, bool given);
 int capgpu_plonk_reserve(uint64_t pk_handle, int count, int input_form, int slot) {
+  return reserve_impl(pk_handle, count, input_form, slot, false);
+}
+// Everything capgpu_plonk_reserve(pk, count, CAPGPU_INPUT_VARS, slot) sizes, and what a given-value call adds: the staging
+// of the given rows, the solved buffer and the status words (given_carve, given_pinned_bytes - the call's own
+// expressions), the plan of a call whose values are resident (what the prover sees behind the solver), the key's tables.
+int capgpu_plonk_reserve_given(uint64_t pk_handle, int count, int slot) {
+  return reserve_impl(pk_handle, count, CAPGPU_INPUT_VARS, slot, true);
+}
+static int reserve_impl(uint64_t pk_handle, int count, int input_form, int slot, bool given) {
+  const char* const who = given ? "capgpu_plonk_reserve_given" : "capgpu_plonk_reserve";
   CAP_CHECK_INIT();
   if (bad_form(input_form)) return CAPGPU_ERR_INVALID_ARG;
   if (count < 0 || slot < -1 || slot >= (int)num_contexts()) {
-    set_error("capgpu_plonk_reserve: bad argument (count >= 0, slot -1 .. %zu)", num_contexts() - 1);
+    set_error("%s: bad argument (count >= 0, slot -1 .. %zu)", who, num_contexts() - 1);
     return CAPGPU_ERR_INVALID_ARG;
   }
   std::shared_ptr<ProvingKey> K0;
   int rc = home_key(pk_handle, &K0);
   if (rc) return rc;
+  if (given) {
+    std::lock_guard<std::mutex> klk(K0->chk_mu);
+    if (!K0->solve || !K0->wire_vars) return no_solver(who);
+  }
   if (input_form == CAPGPU_INPUT_VARS && key_lacks_table(*K0)) return CAPGPU_ERR_INVALID_ARG;
   if (count == 0) return CAPGPU_OK;
   struct ScaleOne {  // exact sizes: a growth scale the thread carries (gathered batches) does not apply
@@ -2616,7 +2863,22 @@ int capgpu_plonk_reserve(uint64_t pk_handle, int count, int input_form, int slot
     if ((rc = get_domain(K->log_n, &dn)) || (rc = quot_domains(K->log_m, &d3, &dn))) return rc;
     (void)h2d_stream();
     (void)side_stream(c);
-    const ProveNeeds nd = prove_needs(pl, *K);
+    ProveNeeds nd = prove_needs(pl, *K);
+    if (given) {
+      ProvePlan pr;
+      if ((rc = make_plan(c, *K, (uint32_t)count, input_form, false, K->vk_bytes.size() + 32 * K->num_inputs, true, &pr)))
+        return rc;
+      const ProveNeeds nr = prove_needs(pr, *K);
+      nd.prove_ws = std::max(nd.prove_ws, nr.prove_ws);
+      nd.msm_ws = std::max(nd.msm_ws, nr.msm_ws);
+      nd.ntt_scratch = std::max(nd.ntt_scratch, nr.ntt_scratch);
+      nd.stage_a = std::max(nd.stage_a, nr.stage_a);
+      SolveTables tab;
+      std::shared_ptr<const SolveSched> hold;
+      if ((rc = key_check_tables(*K)) || (rc = solve_tables(*K, &tab, &hold))) return rc;
+      nd.stage_b = std::max(nd.stage_b, given_carve(nullptr, (size_t)count, K->n, K->num_vars, tab.num_given, true).bytes);
+      nd.pinned = std::max(nd.pinned, given_pinned_bytes((uint32_t)count));
+    }
     if ((rc = scratch_reserve(c.stage_b, nd.stage_b))) return rc;
     if ((rc = scratch_reserve(c.stage_a, nd.stage_a))) return rc;
     if ((rc = scratch_reserve(c.prove_ws, nd.prove_ws))) return rc;
@@ -3083,6 +3345,28 @@ int capgpu_plonk_check_witness_multi(const uint64_t* pk_handles, int count, cons
 
 int capgpu_plonk_set_precheck(int on) {
   g_precheck.store(on != 0);
+  return CAPGPU_OK;
+}
+
+int capgpu_plonk_set_solve_pack(int w) {
+  if (!spk::valid_setting(w)) {
+    set_error("capgpu_plonk_set_solve_pack: %d is none of 0 (automatic), 1, 2, 4, 8, 16", w);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  g_solve_pack.store(w, std::memory_order_relaxed);
+  return CAPGPU_OK;
+}
+int capgpu_plonk_get_solve_pack(int* w_out) {
+  if (!w_out) {
+    set_error("capgpu_plonk_get_solve_pack: bad argument (w_out is NULL)");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  *w_out = solve_pack_setting();
+  return CAPGPU_OK;
+}
+int capgpu_plonk_solve_stats(uint64_t* launches_out, uint64_t* witnesses_out, uint64_t* packed_launches_out) {
+  CAP_CHECK_INIT();
+  solve_stats(launches_out, witnesses_out, packed_launches_out);
   return CAPGPU_OK;
 }
 

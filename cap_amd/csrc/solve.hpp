@@ -5,13 +5,14 @@
 
 #include "field.hpp"
 #include "solve29.hpp"
+#include "solve_pack.hpp"
 #include "solve_plan.hpp"
 
 namespace cap {
 namespace pk {
 
 constexpr unsigned long long kSolved = ~0ull;
-constexpr int kSolveThreads = 256;  // one workgroup per witness
+constexpr int kSolveThreads = 256;  // one workgroup per witness, or per W witnesses (solve_pack.hpp)
 
 // the schedule as the kernel reads it (all device pointers, owned by the key)
 struct SolveTables {
@@ -28,6 +29,23 @@ struct SolveTables {
 // k_solve_vars for `count` witnesses on stream s (through launch(): timed by the profiler, launch errors latched)
 void solve_launch(hipStream_t s, uint32_t count, const fe* d_given, const SolveTables& t, const sv29::Exps& ex, fe* d_vars,
                   unsigned long long* d_status);
+
+// One launch over a list of witnesses at W per workgroup (W: 1, 2, 4, 8 or 16 - spk::pack_for chooses).  d_which: `count`
+// witness indices, or null for 0 .. count - 1; witness p reads d_given + p given_stride, writes d_vars + p vars_stride and
+// d_status[p].  W = 1 without a list and with the tables' own row lengths is solve_launch.
+struct SolveLaunch {
+  uint32_t count;
+  const fe* d_given;
+  size_t given_stride;
+  fe* d_vars;
+  size_t vars_stride;
+  unsigned long long* d_status;
+  const uint32_t* d_which;
+};
+void solve_launch_packed(hipStream_t s, int W, const SolveLaunch& a, const SolveTables& t, const sv29::Exps& ex);
+// capgpu_plonk_solve_stats: launches, witnesses, launches at W > 1
+void solve_stats(uint64_t* launches, uint64_t* witnesses, uint64_t* packed);
+void solve_stats_reset();
 
 }  // namespace pk
 }  // namespace cap

@@ -777,6 +777,25 @@ def plonk_solve_vars(pk_handle: int, given, count: int = 1, out: "DevBuf | None"
     return vars_out, list(status)[:count]
 
 
+def plonk_set_solve_pack(w: int):
+    """capgpu_plonk_set_solve_pack: witnesses per workgroup of the solver's launches - 1, 2, 4, 8 or 16; 0 (the default)
+    chooses from the key's schedule and the launch's count.  Works before init()."""
+    check(load().capgpu_plonk_set_solve_pack(ctypes.c_int(int(w))))
+
+
+def plonk_get_solve_pack() -> int:
+    w = ctypes.c_int(0)
+    check(load().capgpu_plonk_get_solve_pack(ctypes.byref(w)))
+    return w.value
+
+
+def plonk_solve_stats() -> dict:
+    """counters since init: solver launches, the witnesses they completed, launches at more than one witness per workgroup"""
+    a, b, c = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    check(load().capgpu_plonk_solve_stats(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+    return {"launches": a.value, "witnesses": b.value, "packed_launches": c.value}
+
+
 def _cached_num_vars(pk_handle: int) -> int:
     nv = _num_vars_of.get(pk_handle)
     if nv is None:
@@ -1224,7 +1243,7 @@ def _each_args(who: str, pk_handles, wires_elems, pub_rows, blinders, ext_msgs, 
         max_in = max(sh[1] for sh in shapes)
         if any(sh[0] != n for sh in shapes):
             raise ValueError(f"{who}: the keys of one batch must share the domain size")
-        per = _wires_per_proof(pk_handles, n, input_form)
+        per = None if wires_elems is None else _wires_per_proof(pk_handles, n, input_form)  # (None: no `wires` argument)
         if per is not None and wires_elems != count * per:
             raise ValueError(f"{who}: wires must hold count x 5 x n elements (count x num_vars)")
     if pub_rows.size != count * max_in * 4 or blinders.size != count * 13 * 4:
@@ -1297,6 +1316,78 @@ def plonk_prove_each_async(pk_handles, wires: np.ndarray, pub_rows: np.ndarray, 
                                                _p(blinders), ctypes.c_int(_form(input_form)), proofs, outcomes,
                                                ctypes.byref(t)))
     return EachTicket(t.value, proofs, outcomes, count, (wires, keep))
+
+
+# ---- proving from given values (capgpu_plonk_prove_given*): the solver and the variable-form outcome call in one ---------
+def _given_args(who: str, pk_handles, given_elems, pub_rows, blinders, ext_msgs):
+    count, handles, pub_ptr, max_in, msgs, lens, blinders, proofs, outcomes, keep = _each_args(
+        who, pk_handles, None, pub_rows, blinders, ext_msgs, INPUT_VARS)
+    if count:
+        max_given = max(plonk_key_solver_info(h).num_given for h in set(pk_handles))
+        if given_elems != count * max_given:
+            raise ValueError(f"{who}: given must hold count x {max_given} elements (the largest given list of the keys)")
+    solved = (SolveStatus * max(count, 1))()
+    return count, handles, pub_ptr, max_in, msgs, lens, blinders, proofs, outcomes, solved, keep
+
+
+def plonk_prove_given(pk_handles, given, pub_rows: np.ndarray, blinders: np.ndarray, ext_msgs=None):
+    """capgpu_plonk_prove_given[_dev]: from the values each circuit is given to proofs, in one call ->
+    (proofs, outcomes, solved): one ProveOutcome and one SolveStatus per proof.  given: (count, num_given, 4) Montgomery
+    words in the order of the key's given list (several keys: rows of the largest list) - a numpy array, or a DevBuf of
+    that content, which is only read.  Proofs and outcomes are those of plonk_solve_vars followed by
+    plonk_prove_each_dev(..., input_form='vars')."""
+    pk_handles = list(pk_handles)
+    L = load()
+    if isinstance(given, DevBuf):
+        count, handles, pub_ptr, max_in, msgs, lens, blinders, proofs, outcomes, solved, _keep = _given_args(
+            "plonk_prove_given", pk_handles, given.nbytes // 32, pub_rows, blinders, ext_msgs)
+        check(L.capgpu_plonk_prove_given_dev(handles, count, given.ptr, pub_ptr, ctypes.c_size_t(max_in), msgs, lens,
+                                             _p(blinders), proofs, outcomes, solved))
+    else:
+        given = np.ascontiguousarray(given, dtype=np.uint64).reshape(-1)
+        count, handles, pub_ptr, max_in, msgs, lens, blinders, proofs, outcomes, solved, _keep = _given_args(
+            "plonk_prove_given", pk_handles, given.size // 4, pub_rows, blinders, ext_msgs)
+        if given.size == 0:
+            given = np.zeros(4, np.uint64)
+        check(L.capgpu_plonk_prove_given(handles, count, _p(given), pub_ptr, ctypes.c_size_t(max_in), msgs, lens,
+                                         _p(blinders), proofs, outcomes, solved))
+    return list(proofs)[:count], list(outcomes)[:count], list(solved)[:count]
+
+
+class GivenTicket(EachTicket):
+    """The Ticket of plonk_prove_given_async: wait() -> (proofs, outcomes, solved)."""
+
+    def __init__(self, ticket: int, proofs, outcomes, solved, count: int, keep):
+        super().__init__(ticket, proofs, outcomes, count, keep)
+        self._solved = solved
+
+    def wait(self, timeout_ms: int | None = None):
+        r = super().wait(timeout_ms)
+        if r is None:
+            return None
+        return r[0], r[1], list(self._solved)[:self._count]
+
+
+def plonk_prove_given_async(pk_handles, given: np.ndarray, pub_rows: np.ndarray, blinders: np.ndarray,
+                            ext_msgs=None) -> GivenTicket:
+    """capgpu_plonk_prove_given_async: plonk_prove_given (host values) without the wait.  Two tickets in flight run one
+    batch's solve beside the other's rounds."""
+    pk_handles = list(pk_handles)
+    given = np.ascontiguousarray(given, dtype=np.uint64).reshape(-1)
+    count, handles, pub_ptr, max_in, msgs, lens, blinders, proofs, outcomes, solved, keep = _given_args(
+        "plonk_prove_given_async", pk_handles, given.size // 4, pub_rows, blinders, ext_msgs)
+    if given.size == 0:
+        given = np.zeros(4, np.uint64)
+    t = ctypes.c_uint64(0)
+    check(load().capgpu_plonk_prove_given_async(handles, count, _p(given), pub_ptr, ctypes.c_size_t(max_in), msgs, lens,
+                                                _p(blinders), proofs, outcomes, solved, ctypes.byref(t)))
+    return GivenTicket(t.value, proofs, outcomes, solved, count, (given, keep))
+
+
+def plonk_reserve_given(pk_handle: int, count: int, slot: int = -1):
+    """capgpu_plonk_reserve_given: plonk_reserve(pk, count, 'vars', slot) plus what a plonk_prove_given of `count` proofs
+    adds - the staged given values, the solved buffer, the status words, the key's schedule on the context."""
+    check(load().capgpu_plonk_reserve_given(ctypes.c_uint64(pk_handle), ctypes.c_int(count), ctypes.c_int(slot)))
 
 
 def plonk_reserve(pk_handle: int, count: int, input_form=INPUT_EVALS, slot: int = -1):

@@ -520,6 +520,19 @@ int capgpu_plonk_solve_vars(uint64_t pk_handle, int count, const uint64_t* given
                             capgpu_solve_status* status_out);
 int capgpu_plonk_solve_vars_dev(uint64_t pk_handle, int count, const void* d_given, void* d_vars_out,
                                 capgpu_solve_status* status_out);
+/* Witnesses per workgroup of the solver's launches.  One workgroup per witness leaves most of its 256 lanes idle on a
+ * circuit whose levels are narrow; a packed launch gives a workgroup W witnesses and lets its lanes stride over a level's
+ * (row, witness) items.  The output is word for word the unpacked kernel's, statuses included: a zero denominator in one
+ * witness does not touch its neighbours.  w = 1, 2, 4, 8, 16 forces that W; w = 0 (the default; CAPGPU_SOLVE_PACK sets
+ * the process default) chooses: the largest power of two <= 16 with W * (median rows per level) <= 256 - fixed when
+ * capgpu_plonk_key_set_given derives the schedule - and W <= the largest power of two not above the launch's count.  A
+ * launch of one witness always runs unpacked.  Any other w is CAPGPU_ERR_INVALID_ARG.  Process-wide; read when a solve -
+ * or a capgpu_plonk_prove_given* call, or its ticket - starts; both calls work before capgpu_init.
+ * _stats: counters since capgpu_init - solver launches, the witnesses they completed, launches at W > 1; any pointer may
+ * be NULL. */
+int capgpu_plonk_set_solve_pack(int w);
+int capgpu_plonk_get_solve_pack(int* w_out);
+int capgpu_plonk_solve_stats(uint64_t* launches_out, uint64_t* witnesses_out, uint64_t* packed_launches_out);
 
 int capgpu_plonk_free_key(uint64_t pk_handle);
 /* Shape of a resident proving key: the sizes every prove call's arrays must have (wires: count * 5 * domain_size
@@ -820,6 +833,55 @@ int capgpu_plonk_prove_each_async(const uint64_t* pk_handles, int count, const u
                                   const uint64_t* pub_inputs, size_t num_inputs, const uint8_t* const* ext_msgs,
                                   const size_t* ext_msg_lens, const uint64_t* blinders, int input_form,
                                   capgpu_proof* proofs_out, capgpu_prove_outcome* outcomes_out, uint64_t* ticket_out);
+/* ---- proving from the values a circuit is GIVEN -----------------------------------------------------------------------
+ * One call from given values to proofs: the solver (capgpu_plonk_key_set_given) and the variable-form outcome call, fused.
+ * These are outcome calls: everything capgpu_plonk_prove_each[_dev,_async] says about arguments, layouts, the return value
+ * (CAPGPU_OK whenever the batch ran), the all-ones record of a failed proof and borrowed ticket pointers holds here too.
+ * What differs:
+ *   INPUT.  given holds, per proof, the values of its key's given list in given_vars order (Montgomery), proofs
+ *   consecutive.  With several keys the rows have the largest num_given among the call's keys and a key with fewer uses
+ *   the first of its row - as pub_inputs and variable-form rows do.  The _dev form reads d_given in device memory and
+ *   never writes it.
+ *   SOLVER STATUS.  solved_out may be NULL; otherwise it receives `count` records, exactly what capgpu_plonk_solve_vars
+ *   reports for that witness.  A zero-denominator witness is not treated specially: its variable is 0 and it goes on as
+ *   it is; its outcome is what the witness check or the degree check says about the completed assignment.
+ *   REFUSALS, before a device is touched (tickets: at submission): a key without a solver is CAPGPU_ERR_INVALID_ARG
+ *   ("capgpu_plonk_prove_given: the key has no solver (capgpu_plonk_key_set_given gives it one)"); NULL given, blinders,
+ *   proofs_out or outcomes_out with count > 0; keys of different domain size or SRS, as capgpu_plonk_prove_each refuses
+ *   them; capgpu_plonk_shard_msm on.  count == 0 returns CAPGPU_OK and writes nothing.
+ *   MECHANISM.  The given values are staged in one copy of count * num_given * 32 bytes (capgpu_plonk_input_stats' byte
+ *   counter grows by exactly that; _dev: by nothing).  The solver runs on the proving stream into library scratch, packed
+ *   as capgpu_plonk_set_solve_pack says, one launch per distinct key over that key's proofs.  From there the call IS the
+ *   variable-form outcome call on a library-owned buffer: gather, optional witness check, optional compaction (the rules
+ *   of "variable form in library staging"), five rounds.  The status words come back with the proofs: with the transcript
+ *   on the device, capgpu_plonk_sync_stats' stream_waits moves as for capgpu_plonk_prove_each_dev of the solved buffer.
+ *   Host-resident calls of an unbound thread are dealt over the contexts as capgpu_plonk_prove_each deals them, each part
+ *   solving its slice on its own context.  A ticket runs whole on one context: two tickets in flight are a solve on one
+ *   context beside a prove on the other.
+ *   THE CONTRACT.  For every proof i, proofs_out[i] and outcomes_out[i] are bit for bit what capgpu_plonk_solve_vars_dev
+ *   followed by capgpu_plonk_prove_each_dev(..., CAPGPU_INPUT_VARS, ...) make of the same inputs in the same modes, and
+ *   solved_out[i] is that solve's status.
+ * capgpu_plonk_reserve_given sizes what capgpu_plonk_reserve(pk_handle, count, CAPGPU_INPUT_VARS, slot) sizes and, from the
+ * call's own size expressions, the staging of the given values, the solved buffer and the status words, and brings the
+ * key's schedule to the context: a steady-state call of at most `count` proofs then leaves capgpu_scratch_stats where it
+ * was.
+ * LEFT OUT: coalesced single-proof calls; a given form of the all-or-nothing capgpu_plonk_prove_batch / _multi calls; a
+ * given form of capgpu_plonk_check_witness* (capgpu_plonk_solve_vars, then check); any change to the latency of ONE
+ * witness's chain of dependent inversions (a lane-cooperative field product, another inversion algorithm). */
+int capgpu_plonk_prove_given(const uint64_t* pk_handles, int count, const uint64_t* given, const uint64_t* pub_inputs,
+                             size_t num_inputs, const uint8_t* const* ext_msgs, const size_t* ext_msg_lens,
+                             const uint64_t* blinders, capgpu_proof* proofs_out, capgpu_prove_outcome* outcomes_out,
+                             capgpu_solve_status* solved_out);
+int capgpu_plonk_prove_given_dev(const uint64_t* pk_handles, int count, const void* d_given, const uint64_t* pub_inputs,
+                                 size_t num_inputs, const uint8_t* const* ext_msgs, const size_t* ext_msg_lens,
+                                 const uint64_t* blinders, capgpu_proof* proofs_out, capgpu_prove_outcome* outcomes_out,
+                                 capgpu_solve_status* solved_out);
+int capgpu_plonk_prove_given_async(const uint64_t* pk_handles, int count, const uint64_t* given, const uint64_t* pub_inputs,
+                                   size_t num_inputs, const uint8_t* const* ext_msgs, const size_t* ext_msg_lens,
+                                   const uint64_t* blinders, capgpu_proof* proofs_out, capgpu_prove_outcome* outcomes_out,
+                                   capgpu_solve_status* solved_out, uint64_t* ticket_out);
+int capgpu_plonk_reserve_given(uint64_t pk_handle, int count, int slot);
+
 /* Batch compaction of the outcome calls (off by default; CAPGPU_COMPACT=1 sets the process default).  on != 0: an outcome
  * call made with capgpu_plonk_set_precheck on, of whose P witnesses the check refused some but not all, proves the P'
  * survivors as a batch of P' - every launch of the five rounds is that much smaller - and the refused ones cost their

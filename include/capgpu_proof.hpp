@@ -508,6 +508,68 @@ Result<std::vector<ProveEachEntry>> prove_each(Rng& rng, const std::vector<const
   return out;
 }
 
+// The values one circuit is given, for prove_given: `given` in the order of the key's given list (Montgomery words,
+// capgpu_plonk_key_set_given), pub_inputs as in an Assignment.
+struct GivenValues {
+  const uint64_t* given = nullptr;
+  size_t num_given = 0;
+  const uint64_t* pub_inputs = nullptr;
+};
+// prove_each from the values each circuit is GIVEN (capgpu_plonk_prove_given): the library completes every assignment on
+// the device and proves it in the same call.  Every key needs a solver.  A proof that was made is bit for bit what
+// solving and then prove_each in variable form make of it.
+template <class Rng>
+Result<std::vector<ProveEachEntry>> prove_given(Rng& rng, const std::vector<const ProvingKey*>& pks,
+                                                const std::vector<GivenValues>& gs,
+                                                const std::vector<std::vector<uint8_t>>* ext_msgs = nullptr) {
+  const size_t count = pks.size();
+  if (gs.size() != count || (ext_msgs && ext_msgs->size() != count))
+    return TxnApiError::failed_snark("prove_given: one set of given values (and message) per key");
+  std::vector<ProveEachEntry> out(count);
+  if (!count) return out;
+  size_t ni = 0, per = 0;
+  std::vector<uint64_t> handles(count);
+  for (size_t i = 0; i < count; i++) {
+    if (!pks[i] || (!gs[i].given && gs[i].num_given) || (!gs[i].pub_inputs && pks[i]->num_inputs()))
+      return TxnApiError::failed_snark("prove_given: empty given values or public inputs");
+    handles[i] = pks[i]->handle();
+    ni = std::max(ni, pks[i]->num_inputs());
+    per = std::max(per, gs[i].num_given);
+  }
+  // one array of rows of the largest length, zero-filled
+  std::vector<uint64_t> given(count * per * 4 + 4, 0), pubs(count * ni * 4 + 4, 0), blinders(count * 13 * 4);
+  std::vector<const uint8_t*> mp(count, nullptr);
+  std::vector<size_t> ml(count, 0);
+  for (size_t i = 0; i < count; i++) {
+    if (gs[i].num_given) std::memcpy(&given[i * per * 4], gs[i].given, gs[i].num_given * 32);
+    if (pks[i]->num_inputs()) std::memcpy(&pubs[i * ni * 4], gs[i].pub_inputs, pks[i]->num_inputs() * 32);
+    for (int k = 0; k < 13; k++) {
+      Fr b = rng();
+      std::memcpy(&blinders[(i * 13 + k) * 4], b.data(), 32);
+    }
+    if (ext_msgs && !(*ext_msgs)[i].empty()) {
+      mp[i] = (*ext_msgs)[i].data();
+      ml[i] = (*ext_msgs)[i].size();
+    }
+  }
+  std::vector<Proof> proofs(count);
+  std::vector<capgpu_prove_outcome> oc(count);
+  int rc = capgpu_plonk_prove_given(handles.data(), (int)count, given.data(), ni ? pubs.data() : nullptr, ni,
+                                    ext_msgs ? mp.data() : nullptr, ext_msgs ? ml.data() : nullptr, blinders.data(),
+                                    proofs.data(), oc.data(), nullptr);
+  if (rc != CAPGPU_OK) return detail::map_error(rc, "prove_given");
+  for (size_t i = 0; i < count; i++) {
+    if (oc[i].status == CAPGPU_OK) {
+      out[i].proof = proofs[i];
+      continue;
+    }
+    char text[512];
+    capgpu_prove_outcome_text(&oc[i], text, sizeof text);
+    out[i].error = text;
+  }
+  return out;
+}
+
 }  // namespace proof
 
 // ---- Transfer (src/proof/transfer.rs) ----------------------------------------------------------------------------

@@ -8,6 +8,15 @@ n = 2^15: 2 425 given values per witness, 18 193 defined ones, 584 levels, 5 840
                 rest), so this arm flatters the device;
   (c) solve_prove  solve + plonk_prove_batch_dev(vars) of 256 from resident given values, against
       host_vars    plonk_prove_batch(vars) of 256 host-resident variable-form witnesses (context 0, like the other arm).
+  (d) --packed: the solve arms at every witnesses-per-workgroup setting (capgpu_plonk_set_solve_pack 1, 2, 4, 8, 16 and 0 =
+      automatic; arm solve_<count>_w<setting>, "auto" for 0) instead of (a), and the proving arms from given values:
+      prove_given_256          one synchronous plonk_prove_given of 256 from resident given values, context 0;
+      prove_given_async_2x256  plonk_prove_given_async of 256 host-resident given values, two tickets kept in flight from an
+                               unbound thread (a call = one ticket: wait for the oldest, submit the next);
+      host_vars_async_2x256    the same with plonk_prove_multi_async(vars) of 256 host-resident value vectors - its comparison;
+      beside solve_prove_256 and host_vars_prove_256 as above.  Default --out profiles/solve_packed.txt.
+  --arms a,b runs those arms only (no summary lines), --reps N instead of three repetitions, --no-profile leaves the
+  library's kernel timer off: for a run of one arm under an external profiler.
 Protocol: per arm 3 warm-up + 10 timed calls, the arms interleaved, three repetitions; the median of the three medians and
 their spread (max - min over the median).  One process, the library loaded first (no torch).  Writes the lines it prints to
 --out (default profiles/solve_vars.txt).   python tools/gpu_solve_ab.py [--out FILE] [--counts 1,256,1024,4096] [--steps 10]"""
@@ -35,7 +44,8 @@ def arg(name, default):
 def main():
     steps = int(arg("--steps", 10))
     counts = [int(c) for c in arg("--counts", "1,256,1024,4096").split(",")]
-    out_path = arg("--out", os.path.join(ROOT, "profiles", "solve_vars.txt"))
+    packed = "--packed" in sys.argv
+    out_path = arg("--out", os.path.join(ROOT, "profiles", "solve_packed.txt" if packed else "solve_vars.txt"))
     out = open(out_path, "w")
 
     def emit(obj):
@@ -77,14 +87,45 @@ def main():
     blind = np.stack([bu.to_mont_array(bu.blinders(7000 + i)) for i in range(P)])
     host_vars = np.ascontiguousarray(vals[idx[:P]])
     cg.plonk_reserve(pk, P, "vars", slot=0)
+    if packed:
+        cg.plonk_reserve_given(pk, P, slot=-1)
+    host_given = np.ascontiguousarray(gv[idx[:P]])
+    msgs = [b"ab"] * P
 
-    def solve_arm(count):
+    def solve_arm(count, w=None):
         g = d_given.view(0, count * len(given) * 32)
 
         def run(k):
-            for _ in range(k):
-                cg.plonk_solve_vars(pk, g, count, out=d_vars)
+            if w is not None:
+                cg.plonk_set_solve_pack(w)
+            try:
+                for _ in range(k):
+                    cg.plonk_solve_vars(pk, g, count, out=d_vars)
+            finally:
+                cg.plonk_set_solve_pack(0)
         return run
+
+    def prove_given(k):
+        g = d_given.view(0, P * len(given) * 32)
+        for _ in range(k):
+            cg.plonk_prove_given([pk] * P, g, pubs, blind, msgs)
+
+    def in_flight(submit):
+        """k tickets, two kept in flight, from an unbound thread (a bound thread's tickets all run on its context)"""
+        def run(k):
+            cg.set_device(-1)
+            try:
+                live = [submit()]
+                for i in range(k):
+                    if i + 1 < k:
+                        live.append(submit())
+                    assert live.pop(0).wait() is not None
+            finally:
+                cg.set_device(0)
+        return run
+
+    given_async = in_flight(lambda: cg.plonk_prove_given_async([pk] * P, host_given, pubs, blind, msgs))
+    vars_async = in_flight(lambda: cg.plonk_prove_multi_async([pk] * P, host_vars, pubs, blind, msgs, input_form="vars"))
 
     def cpu_fill(k):
         for _ in range(k):
@@ -100,30 +141,50 @@ def main():
         for _ in range(k):
             cg.plonk_prove_batch(pk, host_vars, pubs, blind, b"ab", P, input_form="vars")
 
-    arms = [(f"solve_{c}", solve_arm(c), c) for c in counts] + [("cpu_fill_256_16_threads", cpu_fill, P),
-                                                                 ("solve_prove_256", solve_prove, P), ("host_vars_prove_256", host_vars_arm, P)]
+    if packed:
+        arms = [(f"solve_{c}_w{w or 'auto'}", solve_arm(c, w), c) for c in counts for w in (1, 2, 4, 8, 16, 0)]
+        arms += [("prove_given_256", prove_given, P), ("prove_given_async_2x256", given_async, P),
+                 ("host_vars_async_2x256", vars_async, P)]
+    else:
+        arms = [(f"solve_{c}", solve_arm(c), c) for c in counts] + [("cpu_fill_256_16_threads", cpu_fill, P)]
+    arms += [("solve_prove_256", solve_prove, P), ("host_vars_prove_256", host_vars_arm, P)]
+    only = arg("--arms", None)
+    if only:
+        arms = [a for a in arms if a[0] in only.split(",")]
+    reps, timer = int(arg("--reps", 3)), "--no-profile" not in sys.argv
     call_ms = {name: [] for name, _, _ in arms}
     kern_ms = {name: [] for name, _, _ in arms}
-    cg.profile_enable(True)
-    for rep in range(3):
+    cg.profile_enable(timer)
+    for rep in range(reps):
         for name, fn, count in arms:
             fn(WARM)
             cg.profile_reset()
             t0 = time.perf_counter()
             fn(steps)
             dt = time.perf_counter() - t0
-            k_ms, k_n = cg.profile_stats().get("k_solve_vars", (0.0, 0))
+            solver = [v for name_, v in cg.profile_stats().items() if name_.startswith("k_solve_vars")]
+            k_ms, k_n = sum(v[0] for v in solver), sum(v[1] for v in solver)
             call_ms[name].append(1e3 * dt / steps)
             kern_ms[name].append(k_ms / k_n if k_n else 0.0)
             emit({"arm": name, "rep": rep, "witnesses": count, "call_ms": round(1e3 * dt / steps, 3),
                   "witnesses_per_s": round(count * steps / dt, 1), "k_solve_vars_ms": round(k_ms / k_n, 3) if k_n else None})
     cg.profile_enable(False)
     med = {k: statistics.median(v) for k, v in call_ms.items()}
-    emit({"median_call_ms": {k: round(v, 3) for k, v in med.items()},
-          "spread_rel": {k: round((max(v) - min(v)) / med[k], 4) for k, v in call_ms.items()},
-          "median_k_solve_vars_ms": {k: round(statistics.median(v), 3) for k, v in kern_ms.items() if any(v)},
-          "witnesses_per_s": {name: round(count / med[name] * 1e3, 1) for name, _, count in arms},
-          "solve_prove_over_host_vars": round(med["solve_prove_256"] / med["host_vars_prove_256"], 4)})
+    if not only:
+        emit({"median_call_ms": {k: round(v, 3) for k, v in med.items()},
+              "spread_rel": {k: round((max(v) - min(v)) / med[k], 4) for k, v in call_ms.items()},
+              "median_k_solve_vars_ms": {k: round(statistics.median(v), 3) for k, v in kern_ms.items() if any(v)},
+              "witnesses_per_s": {name: round(count / med[name] * 1e3, 1) for name, _, count in arms},
+              "solve_prove_over_host_vars": round(med["solve_prove_256"] / med["host_vars_prove_256"], 4)})
+    if packed and not only:
+        top_count = max(counts)
+        emit({"given_tickets_over_vars_tickets_proofs_per_s": round(med["host_vars_async_2x256"] / med["prove_given_async_2x256"], 4),
+              "spread_rel_of_the_two": [round((max(call_ms[a]) - min(call_ms[a])) / med[a], 4)
+                                        for a in ("prove_given_async_2x256", "host_vars_async_2x256")],
+              f"solve_{top_count}_auto_over_w1_call_time": round(med[f"solve_{top_count}_wauto"] / med[f"solve_{top_count}_w1"], 4),
+              "prove_given_over_solve_prove": round(med["prove_given_256"] / med["solve_prove_256"], 4),
+              "prove_given_over_host_vars": round(med["prove_given_256"] / med["host_vars_prove_256"], 4),
+              "solve_stats": cg.plonk_solve_stats()})
     for d in (d_given, d_vars):
         d.free()
     cg.plonk_free_key(pk)
