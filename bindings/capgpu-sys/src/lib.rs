@@ -101,6 +101,31 @@ pub struct capgpu_solver_info {
     pub root_rows: u64,
 }
 
+/// `capgpu_hint`: one solver hint (16 bytes): `count` targets, `targets[first .. first + count)`, valued from `src`.
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug, PartialEq, Eq)]
+pub struct capgpu_hint {
+    pub kind: u32,
+    pub src: u32,
+    pub first: u32,
+    pub count: u32,
+}
+pub const CAPGPU_HINT_BITS: u32 = 0;
+pub const CAPGPU_HINT_INV0: u32 = 1;
+pub const CAPGPU_HINT_ISZERO: u32 = 2;
+
+/// `capgpu_hint_info`: the figures of a key's solver hints (48 bytes); all zero: the key has none.
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug, PartialEq, Eq)]
+pub struct capgpu_hint_info {
+    pub num_hints: u64,
+    pub num_hinted: u64,
+    pub bits_hints: u64,
+    pub inv_hints: u64,
+    pub iszero_hints: u64,
+    pub hint_items: u64,
+}
+
 /// `capgpu_solve_status`: the verdict of the witness solver for one witness (16 bytes).  `kind`: 0 solved, 1 the
 /// denominator of `row` - the lowest such row - is zero (its variable is 0).
 #[repr(C)]
@@ -262,6 +287,11 @@ extern "C" {
     pub fn capgpu_plonk_key_set_given(pk_handle: u64, given_vars: *const u32, num_given: usize,
                                       info_out: *mut capgpu_solver_info) -> c_int;
     pub fn capgpu_plonk_key_solver_info(pk_handle: u64, info_out: *mut capgpu_solver_info) -> c_int;
+    pub fn capgpu_plonk_key_set_given_hints(pk_handle: u64, given_vars: *const u32, num_given: usize,
+                                            hints: *const capgpu_hint, num_hints: usize, targets: *const u32,
+                                            num_targets: usize, info_out: *mut capgpu_solver_info,
+                                            hint_info_out: *mut capgpu_hint_info) -> c_int;
+    pub fn capgpu_plonk_key_hint_info(pk_handle: u64, info_out: *mut capgpu_hint_info) -> c_int;
     pub fn capgpu_plonk_solve_vars(pk_handle: u64, count: c_int, given: *const u64, vars_out: *mut u64,
                                    status_out: *mut capgpu_solve_status) -> c_int;
     pub fn capgpu_plonk_solve_vars_dev(pk_handle: u64, count: c_int, d_given: *const c_void, d_vars_out: *mut c_void,
@@ -728,6 +758,23 @@ impl ProvingKey {
     pub fn set_given(&self, given_vars: &[u32]) -> Result<capgpu_solver_info> {
         let mut info = capgpu_solver_info::default();
         check(unsafe { capgpu_plonk_key_set_given(self.handle, given_vars.as_ptr(), given_vars.len(), &mut info) })?;
+        Ok(info)
+    }
+    /// `set_given` with the hints the circuit's builder recorded (`capgpu_plonk_key_set_given_hints`): `targets` holds every
+    /// hint's target ids, `hints[i].first` and `.count` its slice.  The hinted variables need not be given.
+    pub fn set_given_hints(&self, given_vars: &[u32], hints: &[capgpu_hint], targets: &[u32])
+                           -> Result<(capgpu_solver_info, capgpu_hint_info)> {
+        let (mut info, mut hint_info) = (capgpu_solver_info::default(), capgpu_hint_info::default());
+        check(unsafe {
+            capgpu_plonk_key_set_given_hints(self.handle, given_vars.as_ptr(), given_vars.len(), hints.as_ptr(), hints.len(),
+                                             targets.as_ptr(), targets.len(), &mut info, &mut hint_info)
+        })?;
+        Ok((info, hint_info))
+    }
+    /// The figures of the key's hints; all zero: no hints.
+    pub fn hint_info(&self) -> Result<capgpu_hint_info> {
+        let mut info = capgpu_hint_info::default();
+        check(unsafe { capgpu_plonk_key_hint_info(self.handle, &mut info) })?;
         Ok(info)
     }
     /// The schedule's figures; all zero: the key has no solver.

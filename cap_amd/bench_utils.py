@@ -22,6 +22,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
+from .lib import HINT_BITS, HINT_INV0, HINT_ISZERO  # CAPGPU_HINT_* (include/capgpu.h)
+
 # BN254 scalar field (ark_bn254::Fr; src/config.rs:77-84 fixes the curve)
 R = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001
 MONT = (1 << 256) % R
@@ -356,6 +358,7 @@ class _GadgetBuilder:
         self.j = 0
         self.family = {}
         self._fam = "io"
+        self.hints = []                                  # (kind, src, [targets]) in the order the hinted gadgets made them
         for _ in range(num_inputs):                      # IO gates: q_o = 1, wire 4 = the public input
             v = self.free(VAR_UNIFORM)
             self.pub_vars.append(v)
@@ -410,10 +413,10 @@ class _GadgetBuilder:
         """conditional_select: b x + (1 - b) y"""
         return self.row(b, x, nb, y, mul=(1, 1))
 
-    def lin(self, ws, coeffs, q_c=0):
+    def lin(self, ws, coeffs, q_c=0, out=None):
         ws = list(ws) + [0] * (4 - len(ws))
         coeffs = list(coeffs) + [0] * (4 - len(coeffs))
-        return self.row(*ws, lc=coeffs, q_c=q_c)
+        return self.row(*ws, out=out, lc=coeffs, q_c=q_c)
 
     def decompose(self, bits):
         """the linear-combination chain of a bit decomposition: four bits, then the running sum + three bits per gate
@@ -497,6 +500,81 @@ class _GadgetBuilder:
         right = self.select(b1, nb1, cur, s2)
         return self.rescue_perm([left, mid, right, 0])[0]
 
+    # ---- the same gadgets as jf-relation lays them on a value the circuit already holds: the new variables are HINTS --
+    # (capgpu_plonk_key_set_given_hints) computed from their source; the rows only constrain them.  The row layout is
+    # restated from the crate's published constructions and unpinned - jf-relation is not in this image; the solver's
+    # rule does not depend on it: a hinted variable has its value before the walk reaches any row that holds it.
+    def hinted(self):
+        v = self.num_vars
+        self.num_vars += 1
+        return v
+
+    def unpack(self, v, nbits):
+        """unpack / range gates on an existing variable: nbits hinted bits (bit i of v), a boolean row per bit, and the
+        recomposition chain - four bits, then the running sum + three bits per gate - whose LAST row outputs v itself"""
+        bits = [self.hinted() for _ in range(nbits)]
+        self.hints.append((HINT_BITS, v, list(bits)))
+        for b in bits:
+            self.row(b, b, 0, 0, out=b, mul=(1, 0))
+        acc = self.lin(bits[:4], [1 << i for i in range(len(bits[:4]))], out=v if nbits <= 4 else None)
+        k = 4
+        while k < nbits:
+            grp = bits[k:k + 3]
+            acc = self.lin([acc] + grp, [1] + [1 << (k + i) for i in range(len(grp))], out=v if k + 3 >= nbits else None)
+            k += 3
+        return bits
+
+    def enforce_in_range(self, v, nbits):
+        """v < 2^nbits: the unpack chain closes on v only if it does"""
+        self.unpack(v, nbits)
+
+    def is_zero(self, a):
+        """-> the boolean y = (a == 0): hinted a_inv (1 / a, or 0) and y; y = 1 - a a_inv on (a, a_inv, 0, 0, y) and
+        a y = 0 on (a, y, 0, 0, zero)"""
+        inv, y = self.hinted(), self.hinted()
+        self.hints.append((HINT_INV0, a, [inv]))
+        self.hints.append((HINT_ISZERO, a, [y]))
+        self.row(a, inv, 0, 0, out=y, mul=(1, 0), q_c=-1, q_o=-1)
+        self.row(a, y, 0, 0, out=0, mul=(1, 0))
+        return y
+
+    def is_equal(self, a, b):
+        return self.is_zero(self.lin([a, b], [1, -1]))
+
+    def is_in_range(self, v, nbits):
+        """-> the boolean (v < 2^nbits): a full 254-bit unpack of v, the sum of the bits from nbits up, and is_zero of it
+        (nbits = 254: every canonical value is in range - the constant one)"""
+        high = self.unpack(v, 254)[nbits:]
+        if not high:
+            return 1
+        acc = self.lin(high[:4], [1] * len(high[:4]))
+        for k in range(4, len(high), 3):
+            grp = high[k:k + 3]
+            acc = self.lin([acc] + grp, [1] * (1 + len(grp)))
+        return self.is_zero(acc)
+
+    def scalar_mul_variable_hinted(self, point, scalar):
+        """scalar_mul_variable with the bits unpacked from the scalar variable instead of given"""
+        acc = point
+        for b in self.unpack(scalar, 254):
+            acc = self.ecc_add(acc, acc)
+            sx = self.row(b, point[0], 0, 0, mul=(1, 0))
+            sy = self.row(b, point[1], 0, 0, mul=(1, 0), lc=(-1, 0, 0, 0), q_c=1)
+            acc = self.ecc_add(acc, (sx, sy))
+        return acc
+
+    def scalar_mul_fixed_hinted(self, scalar):
+        """scalar_mul_fixed with the bits unpacked from the scalar variable instead of given"""
+        bits = self.unpack(scalar, 254)
+        acc = None
+        for k in range(0, 254, 2):
+            b0, b1 = bits[k], bits[k + 1]
+            b01 = self.logic_and(b0, b1)
+            sx = self.lin([b0, b1, b01], [self.c(), self.c(), self.c()], q_c=self.c())
+            sy = self.lin([b0, b1, b01], [self.c(), self.c(), self.c()], q_c=self.c())
+            acc = (sx, sy) if acc is None else self.ecc_add(acc, (sx, sy))
+        return acc
+
     def fam(self, name):
         self._fam = name
 
@@ -574,6 +652,94 @@ def cap_like_circuit(kind: str = "transfer_2x2", seed: int = 2, tree_depth: int 
     return SyntheticCircuit(log_n=log_n, num_inputs=num_inputs, selectors=b.sel, wire_vars=b.wv, num_vars=b.num_vars,
                             free_vars=b.free_vars, pub_vars=b.pub_vars, gate_rows=gate_rows, sigma=sigma,
                             free_class=b.free_class, gadget_rows=fam)
+
+
+def cap_like_hinted_circuit(kind: str = "transfer_2x2", seed: int = 2, tree_depth: int = 10):
+    """cap_like_circuit's composition with the hinted gadgets laid the way the reference's circuits call them - on values
+    the circuit computes or is given whole: is_zero(amount) (src/circuit/transfer.rs:82), is_equal(root, public root) on
+    the Merkle path's output (:115), is_in_range(amount_diff) as a 254-bit unpack (:182), unpack of the reveal map (:204),
+    enforce_in_range on the output amounts, and every scalar multiplication's bits unpacked from its scalar.
+    -> (circuit, given ids, hints): the scalars, amounts, roots, siblings and position bits are GIVEN
+    (given = [0, 1] + free_vars, classes in free_class); bits, inverses and flags are hints for
+    capgpu_plonk_key_set_given_hints.  The circuit has no witness generator of its own (SyntheticCircuit.witness draws
+    free variables only): cap_like_given_values draws the given values and the solver completes them.
+    The hinted gadgets' row layout is restated from jf-relation's published constructions and is unpinned (the crate is
+    not in this image); the solver's rule does not depend on it."""
+    log_n, num_inputs = NOTE_SHAPES[kind]
+    n_in, n_out = {"transfer_2x2": (2, 2), "transfer_2x3": (2, 3), "transfer_2x2_d26": (2, 2), "transfer_3x5_d26": (3, 5)}[kind]
+    b = _GadgetBuilder(log_n, num_inputs, seed)
+    root_pub = b.pub_vars[0]
+    amounts_in, amounts_out = [], []
+    for i in range(n_in):
+        b.fam("record commitment")
+        amount = b.free(VAR_U64)
+        amounts_in.append(amount)
+        freeze = b.boolean()
+        fields = [amount] + [b.free(VAR_UNIFORM) for _ in range(10)] + [freeze]
+        rc = b.sponge(fields)
+        b.fam("logic")
+        is_dummy = b.boolean()
+        is_zero_amt = b.is_zero(amount)
+        b.logic_or(b.logic_not(is_dummy), is_zero_amt)
+        b.fam("merkle path")
+        cur = rc
+        for _ in range(tree_depth):
+            cur = b.merkle_level(cur)
+        b.fam("logic")
+        b.logic_or(is_dummy, b.is_equal(cur, root_pub))
+        b.row(freeze, 0, 0, 0, out=0, lc=(0, 0, 0, 0), q_o=1)
+        b.fam("nullifier")
+        b.sponge([b.free(VAR_UNIFORM), rc, cur])
+        b.fam("ownership (fixed-base)")
+        b.scalar_mul_fixed_hinted(b.free(VAR_UNIFORM))
+        b.fam("credential (variable-base x2 + hash)")
+        pk = (b.free(VAR_UNIFORM), b.free(VAR_UNIFORM))
+        r1 = b.scalar_mul_variable_hinted(pk, b.free(VAR_UNIFORM))
+        r2 = b.scalar_mul_variable_hinted((b.free(VAR_UNIFORM), b.free(VAR_UNIFORM)), b.free(VAR_UNIFORM))
+        b.sponge([r1[0], r1[1], r2[0], r2[1], b.free(VAR_UNIFORM), b.free(VAR_UNIFORM)])
+        b.ecc_add(r1, r2)
+    for i in range(n_out):
+        b.fam("range check")
+        amount = b.free(VAR_U64)
+        b.enforce_in_range(amount, 64)
+        amounts_out.append(amount)
+        b.fam("record commitment")
+        b.sponge([amount] + [b.free(VAR_UNIFORM) for _ in range(10)] + [b.boolean()])
+    b.fam("balance")
+    tot_in = b.lin(amounts_in[:4], [1] * len(amounts_in[:4]))
+    tot_out = b.lin(amounts_out[:4], [1] * len(amounts_out[:4]))
+    diff = b.lin([tot_in, tot_out], [1, -1])
+    b.fam("range check")
+    b.is_in_range(diff, 64)                                                          # a flag: the harness draws amounts freely
+    reveal_map = b.free(VAR_U64)
+    b.unpack(reveal_map, 64)
+    b.fam("viewing memo (ElGamal)")
+    b.scalar_mul_fixed_hinted(b.free(VAR_UNIFORM))
+    shared = b.scalar_mul_variable_hinted((b.free(VAR_UNIFORM), b.free(VAR_UNIFORM)), b.free(VAR_UNIFORM))
+    data = [diff] + [b.free(VAR_UNIFORM) for _ in range(24)]
+    key = b.sponge([shared[0], shared[1]])
+    for k in range(0, 25, 3):
+        ks = b.rescue_perm([key, b.lin([1], [k]), 0, 0])
+        for i, d_ in enumerate(data[k:k + 3]):
+            b.row(d_, ks[i], 0, 0, lc=(1, 1, 0, 0))
+    gate_rows = b.j
+    sigma = _permutation(b.wv, b.num_vars, log_n)
+    fam = dict(b.family)
+    fam["padding"] = b.n - gate_rows
+    sc = SyntheticCircuit(log_n=log_n, num_inputs=num_inputs, selectors=b.sel, wire_vars=b.wv, num_vars=b.num_vars,
+                          free_vars=b.free_vars, pub_vars=b.pub_vars, gate_rows=gate_rows, sigma=sigma,
+                          free_class=b.free_class, gadget_rows=fam)
+    return sc, [0, 1] + list(b.free_vars), list(b.hints)
+
+
+def cap_like_given_values(sc: SyntheticCircuit, seed: int):
+    """the values of [0, 1] + free_vars for one witness of a cap_like_hinted_circuit, drawn like SyntheticCircuit.witness
+    draws its free variables (booleans, 64-bit values, field elements by class)"""
+    rng = SplitMix64(seed)
+    vals = [0, 1]
+    for c in sc.free_class:
+        vals.append((rng.next() & 1) if c == VAR_BOOL else rng.next() if c == VAR_U64 else rng.field())
+    return vals
 
 
 def note_circuit(kind: str, seed: int = 2) -> SyntheticCircuit:

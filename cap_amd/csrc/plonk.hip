@@ -57,6 +57,7 @@ struct SolveSched {
   sp::Plan plan;
   std::vector<fe> konst;  // per row of plan.rows: 1 / q_o or 1 / q_hash_i, internal form, canonical
   capgpu_solver_info info{};
+  capgpu_hint_info hint_info{};  // all zero: no hints
   int auto_pack = 1;  // the schedule's term of the automatic witnesses-per-workgroup rule (spk::auto_pack)
 };
 
@@ -1692,12 +1693,19 @@ int solve_tables(const ProvingKey& K, SolveTables* tab, std::shared_ptr<const So
     sp::Row* rows = nullptr;
     fe* konst = nullptr;
     uint32_t* off = nullptr;
+    sp::Hint* hints = nullptr;
+    uint32_t* targets = nullptr;
+    const size_t nhints = S.plan.hints.size(), ntargets = S.plan.targets.size();
     auto carve_tables = [&](void* at) {
       Carver k(at);
       slot = k.take<int32_t>(S.plan.slot.size());
       rows = k.take<sp::Row>(nrows ? nrows : 1);
       konst = k.take<fe>(nrows ? nrows : 1);
       off = k.take<uint32_t>(S.plan.level_off.size());
+      if (nhints) {
+        hints = k.take<sp::Hint>(nhints);
+        targets = k.take<uint32_t>(ntargets);
+      }
       return k.off + 256;
     };
     DevTmp<char> own;
@@ -1709,11 +1717,17 @@ int solve_tables(const ProvingKey& K, SolveTables* tab, std::shared_ptr<const So
       CAP_HIP(hipMemcpy(konst, S.konst.data(), sizeof(fe) * nrows, hipMemcpyHostToDevice));
     }
     CAP_HIP(hipMemcpy(off, S.plan.level_off.data(), sizeof(uint32_t) * S.plan.level_off.size(), hipMemcpyHostToDevice));
+    if (nhints) {
+      CAP_HIP(hipMemcpy(hints, S.plan.hints.data(), sizeof(sp::Hint) * nhints, hipMemcpyHostToDevice));
+      CAP_HIP(hipMemcpy(targets, S.plan.targets.data(), sizeof(uint32_t) * ntargets, hipMemcpyHostToDevice));
+    }
     SolveTables t{};
     t.slot = slot;
     t.rows = rows;
     t.konst = konst;
     t.level_off = off;
+    t.hp.hints = hints;
+    t.hp.targets = targets;
     t.levels = (uint32_t)S.plan.levels;
     t.num_given = S.plan.num_given;
     K.solve_tab = t;
@@ -1790,12 +1804,28 @@ int solve_run(uint64_t pk_handle, uint32_t count, const uint64_t* h_given, uint6
   return CAPGPU_OK;
 }
 
-}  // namespace
+static_assert(sizeof(capgpu_hint) == sizeof(sp::Hint) && sizeof(capgpu_hint) == 16 && sizeof(capgpu_hint_info) == 48 &&
+                  offsetof(capgpu_hint, kind) == offsetof(sp::Hint, kind) && offsetof(capgpu_hint, src) == offsetof(sp::Hint, src) &&
+                  offsetof(capgpu_hint, first) == offsetof(sp::Hint, first) &&
+                  offsetof(capgpu_hint, count) == offsetof(sp::Hint, count),
+              "capgpu_hint is sp::Hint");
+static_assert(CAPGPU_HINT_BITS == sp::HINT_BITS && CAPGPU_HINT_INV0 == sp::HINT_INV0 && CAPGPU_HINT_ISZERO == sp::HINT_ISZERO,
+              "hint kinds");
 
-int capgpu_plonk_key_set_given(uint64_t pk_handle, const uint32_t* given_vars, size_t num_given,
-                               capgpu_solver_info* info_out) {
+// capgpu_plonk_key_set_given (who names it, no hints) and capgpu_plonk_key_set_given_hints
+int key_set_given(const char* who, uint64_t pk_handle, const uint32_t* given_vars, size_t num_given, const capgpu_hint* hints,
+                  size_t num_hints, const uint32_t* targets, size_t num_targets, capgpu_solver_info* info_out,
+                  capgpu_hint_info* hint_info_out) {
   if (!given_vars && num_given) {
-    set_error("capgpu_plonk_key_set_given: bad argument (given_vars is NULL)");
+    set_error("%s: bad argument (given_vars is NULL)", who);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  if ((!hints && num_hints) || (!targets && num_targets)) {
+    set_error("%s: bad argument (%s is NULL)", who, !hints && num_hints ? "hints" : "targets");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  if (num_hints >= (1ull << 32) || num_targets >= (1ull << 32)) {
+    set_error("%s: bad argument (num_hints and num_targets are below 2^32)", who);
     return CAPGPU_ERR_INVALID_ARG;
   }
   CAP_CHECK_INIT();
@@ -1803,12 +1833,13 @@ int capgpu_plonk_key_set_given(uint64_t pk_handle, const uint32_t* given_vars, s
   int rc = home_key(pk_handle, &K);
   if (rc) return rc;
   if (!K->wire_vars) {
-    set_error("capgpu_plonk_key_set_given: the key has no wire -> variable table (capgpu_plonk_preprocess_vars makes a key "
-              "with one, capgpu_plonk_key_set_vars gives it one); the key is unchanged");
+    set_error("%s: the key has no wire -> variable table (capgpu_plonk_preprocess_vars makes a key with one, "
+              "capgpu_plonk_key_set_vars gives it one); the key is unchanged",
+              who);
     return CAPGPU_ERR_INVALID_ARG;
   }
   if (!solve_exps()) {
-    set_error("capgpu_plonk_key_set_given: (r - 1) mod 5 != 1: the scalar field has no fifth-root exponent");
+    set_error("%s: (r - 1) mod 5 != 1: the scalar field has no fifth-root exponent", who);
     return CAPGPU_ERR_INVALID_ARG;
   }
   Runtime& R = rt();
@@ -1819,7 +1850,7 @@ int capgpu_plonk_key_set_given(uint64_t pk_handle, const uint32_t* given_vars, s
       break;
     }
   if (!home) {
-    set_error("capgpu_plonk_key_set_given: no context on the key's device %d", K->device);
+    set_error("%s: no context on the key's device %d", who, K->device);
     return CAPGPU_ERR_BAD_HANDLE;
   }
   auto S = std::make_shared<SolveSched>();
@@ -1837,8 +1868,9 @@ int capgpu_plonk_key_set_given(uint64_t pk_handle, const uint32_t* given_vars, s
     CAP_HIP(hipStreamSynchronize(s));
     std::vector<uint8_t> sel_zero((size_t)NS * n);
     for (size_t i = 0; i < sel.size(); i++) sel_zero[i] = Fr29::is_zero(Fr29::load(sel[i])) ? 1 : 0;
-    if (!sp::solve_plan(n, K->num_inputs, num_vars, table.data(), sel_zero.data(), given_vars, num_given, &S->plan)) {
-      set_error("capgpu_plonk_key_set_given: %s; the key is unchanged", S->plan.error.c_str());
+    if (!sp::solve_plan_hints(n, K->num_inputs, num_vars, table.data(), sel_zero.data(), given_vars, num_given,
+                              (const sp::Hint*)hints, num_hints, targets, num_targets, &S->plan)) {
+      set_error("%s: %s; the key is unchanged", who, S->plan.error.c_str());
       return CAPGPU_ERR_INVALID_ARG;
     }
     const sp::Plan& P = S->plan;
@@ -1846,7 +1878,7 @@ int capgpu_plonk_key_set_given(uint64_t pk_handle, const uint32_t* given_vars, s
     std::vector<size_t> where;
     for (size_t k = 0; k < P.rows.size(); k++) {
       const uint32_t kind = sp::row_kind(P.rows[k]);
-      if (kind == sp::OUT_INV) continue;
+      if (kind == sp::OUT_INV || kind >= sp::kFirstHintKind) continue;
       const int which = kind == sp::OUT_MUL ? sp::Q_O : sp::Q_HASH + (int)sp::row_wire(P.rows[k]);
       inv.push_back(Fr29::load(sel[(size_t)which * n + P.rows[k].row]));
       where.push_back(k);
@@ -1857,6 +1889,7 @@ int capgpu_plonk_key_set_given(uint64_t pk_handle, const uint32_t* given_vars, s
     static std::atomic<uint64_t> next_uid{1};
     S->uid = next_uid.fetch_add(1);
     S->info = capgpu_solver_info{P.num_given, P.num_defined, P.levels, P.widest_level, P.inv_rows, P.root_rows};
+    S->hint_info = capgpu_hint_info{P.hints.size(), P.num_hinted, P.bits_hints, P.inv_hints, P.iszero_hints, P.hint_items};
     S->auto_pack = spk::auto_pack(spk::median_level_width(P.level_off.data(), P.levels), kSolveThreads);
   }
   // the key and the replicas other devices hold take the schedule; each uploads its tables on its next solve
@@ -1875,6 +1908,36 @@ int capgpu_plonk_key_set_given(uint64_t pk_handle, const uint32_t* given_vars, s
     K->solve = S;
   }
   if (info_out) *info_out = S->info;
+  if (hint_info_out) *hint_info_out = S->hint_info;
+  return CAPGPU_OK;
+}
+
+}  // namespace
+
+int capgpu_plonk_key_set_given(uint64_t pk_handle, const uint32_t* given_vars, size_t num_given,
+                               capgpu_solver_info* info_out) {
+  return key_set_given("capgpu_plonk_key_set_given", pk_handle, given_vars, num_given, nullptr, 0, nullptr, 0, info_out, nullptr);
+}
+
+int capgpu_plonk_key_set_given_hints(uint64_t pk_handle, const uint32_t* given_vars, size_t num_given,
+                                     const capgpu_hint* hints, size_t num_hints, const uint32_t* targets,
+                                     size_t num_targets, capgpu_solver_info* info_out, capgpu_hint_info* hint_info_out) {
+  return key_set_given("capgpu_plonk_key_set_given_hints", pk_handle, given_vars, num_given, hints, num_hints, targets,
+                       num_targets, info_out, hint_info_out);
+}
+
+int capgpu_plonk_key_hint_info(uint64_t pk_handle, capgpu_hint_info* info_out) {
+  if (!info_out) {
+    set_error("capgpu_plonk_key_hint_info: bad argument (info_out is NULL)");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  CAP_CHECK_INIT();
+  std::shared_ptr<ProvingKey> K;
+  int rc = home_key(pk_handle, &K);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> klk(K->chk_mu);
+  memset(info_out, 0, sizeof *info_out);
+  if (K->solve && K->wire_vars) *info_out = K->solve->hint_info;
   return CAPGPU_OK;
 }
 

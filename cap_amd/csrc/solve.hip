@@ -16,16 +16,19 @@ void count_launch(uint32_t count, int W) {
   g_witnesses.fetch_add(count, std::memory_order_relaxed);
   if (W > 1) g_packed.fetch_add(1, std::memory_order_relaxed);
 }
+// (a schedule with hint items runs the instantiations that hold the hint code - solve_kernels.hpp says why there are two)
 template <int W>
 void launch_packed(hipStream_t s, const char* name, const SolveLaunch& a, const SolveTables& t, const sv29::Exps& ex) {
-  launch(name, k_solve_vars_packed<W>, dim3(spk::blocks_for(a.count, W)), dim3(kSolveThreads), 0, s, a.d_given, a.given_stride,
-         t, ex, a.d_vars, a.vars_stride, a.d_status, a.d_which, a.count);
+  const auto kernel = t.hp.hints ? k_solve_vars_packed<W, true> : k_solve_vars_packed<W, false>;
+  launch(name, kernel, dim3(spk::blocks_for(a.count, W)), dim3(kSolveThreads), 0, s, a.d_given, a.given_stride,
+         static_cast<const SolveRowTables&>(t), ex, a.d_vars, a.vars_stride, a.d_status, a.d_which, a.count, t.hp);
 }
 }  // namespace
 
 void solve_launch(hipStream_t s, uint32_t count, const fe* d_given, const SolveTables& t, const sv29::Exps& ex, fe* d_vars,
                   unsigned long long* d_status) {
-  launch("k_solve_vars", k_solve_vars, dim3(count), dim3(kSolveThreads), 0, s, d_given, t, ex, d_vars, d_status);
+  launch("k_solve_vars", t.hp.hints ? k_solve_vars<true> : k_solve_vars<false>, dim3(count), dim3(kSolveThreads), 0, s, d_given,
+         static_cast<const SolveRowTables&>(t), ex, d_vars, d_status, t.hp);
   count_launch(count, 1);
 }
 

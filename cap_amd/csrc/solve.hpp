@@ -14,16 +14,27 @@ namespace pk {
 constexpr unsigned long long kSolved = ~0ull;
 constexpr int kSolveThreads = 256;  // one workgroup per witness, or per W witnesses (solve_pack.hpp)
 
-// the schedule as the kernel reads it (all device pointers, owned by the key)
-struct SolveTables {
+// the hint tables of a schedule (device pointers, owned by the key); hints null: no hints - then no item is a hint item
+struct SolveHints {
+  const sp::Hint* hints;
+  const uint32_t* targets;  // the hints' target ids
+};
+
+// the schedule as the kernels read it (all device pointers, owned by the key): the kernels' argument
+struct SolveRowTables {
   const int32_t* slot;        // [num_vars]: index into a witness's given values, -1: not given
-  const sp::Row* rows;        // defining rows by (level, kind, row)
-  const fe* konst;            // per row: 1 / q_o or 1 / q_hash_i, internal form, canonical
+  const sp::Row* rows;        // the items - defining rows and hint items - by (level, kind, row or hint, chunk)
+  const fe* konst;            // per item: 1 / q_o or 1 / q_hash_i, internal form, canonical (a hint item: unused)
   const uint32_t* level_off;  // [levels + 1]
   const uint32_t* wire_vars;  // [5][n] the key's table
   const fe* sel;              // [13][n] selector values, internal form, canonical
   uint32_t levels, pad;
   size_t n, num_vars, num_given;
+};
+// ... and as the host hands it round: with the hint tables, which the kernels take as an argument of their own, the last -
+// the kernels of keys without hints keep the argument layout they had before hints
+struct SolveTables : SolveRowTables {
+  SolveHints hp;
 };
 
 // k_solve_vars for `count` witnesses on stream s (through launch(): timed by the profiler, launch errors latched)

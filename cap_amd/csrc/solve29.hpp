@@ -10,6 +10,8 @@
 // a PUBLIC exponent: 254 squarings and one product per set bit whatever the base is; a base of 0 comes out as 0.  No
 // step depends on a witness value except the zero test of an inverted denominator (Fl::is_zero), whose outcome is
 // reported anyway.
+// The three HINT rules (capgpu_plonk_key_set_given_hints; the plan: solve_plan.hpp) are here too - the bits of a source's
+// canonical value, its inverse or 0, its zero flag - as the same host + device code: tests/cpp/solve_hints_check.cpp.
 #pragma once
 #include "gatecheck29.hpp"
 
@@ -119,7 +121,9 @@ struct Solve {
   // The value of the row's variable.  kind / wire: sp::Kind and the target wire of the plan; w: the five wire values, the
   // target's cell holding anything; konst: the row's constant (1 / q_o for OUT_MUL, 1 / q_hash_wire for ROOT5; unused for
   // OUT_INV).  *zero_den: an OUT_INV row whose denominator is 0 mod r - its value is then 0.
-  template <class Sel>
+  // WITH_INV0: kind 3 (sp::INV0, a hint item riding the rows' path so that one exponentiation serves the three kinds that
+  // need one) is taken too: its value is w_in[0]^(r - 2) - 0 for 0, no zero test - and nothing else of the arguments counts.
+  template <bool WITH_INV0 = false, class Sel>
   static CAP_HD fl row_value(Sel q, uint32_t kind, uint32_t wire, const fl* w_in, const fl& konst, const Exps& ex,
                              bool* zero_den) {
     fl w[wc29::kWires];
@@ -133,11 +137,56 @@ struct Solve {
     if (kind == 1) {
       base = F::sub(q(wc29::Q_O), F::mul(q(wc29::Q_ECC), w0123));
       *zero_den = F::is_zero(base);
-    } else {
+    } else if (!WITH_INV0 || kind == 2) {
       base = F::mul(F::sub(F::mul(q(wc29::Q_O), w[4]), r), konst);
+    } else {
+      base = w_in[0];
     }
-    const fl p = pow_words(base, [&](int w) { return kind == 1 ? ex.inv[w] : ex.root5[w]; });
+    const fl p = pow_words(base, [&](int w) { return (WITH_INV0 ? kind != 2 : kind == 1) ? ex.inv[w] : ex.root5[w]; });
     return kind == 1 ? F::mul(r, p) : p;
+  }
+
+  // ---- hints: a value computed from ONE source variable (the plan: solve_plan.hpp) ----------------------------------------
+  // Sources and results are variables' memory images (external Montgomery form; results canonical).  No branch, loop
+  // bound or address here depends on the source's value: a bit and the zero test select between the images of 0 and 1 by
+  // multiplying the words of 1's image with the bit.
+
+  // the plain integer c of the source, 0 <= c < r
+  static CAP_HD fe hint_plain(const fe& src) { return F::from_mont(F::from_ext(src)); }
+  // word g of a (g < 8) - selected with a compile-time index, like the wires of row_value, and as a sum of word times
+  // (g == i): a chain of selects on g the compiler turns back into an indexed load of a private array
+  static CAP_HD uint32_t word_of(const fe& a, uint32_t g) {
+    uint32_t x = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) x |= a.v[i] * (uint32_t)(g == (uint32_t)i);
+    return x;
+  }
+  // the image of the field element `bit` (0 or 1)
+  static CAP_HD fe bit_image(uint32_t bit) {
+    const fe one = F::to_ext(F::one());
+    fe x;
+#pragma unroll
+    for (int i = 0; i < 8; i++) x.v[i] = one.v[i] * bit;
+    return x;
+  }
+  // BITS: bits 32 g .. 32 g + 31 of c as one word; bit b of the chunk is (word >> b) & 1, its image bit_image of that
+  static CAP_HD uint32_t hint_bits_word(const fe& src, uint32_t g) { return word_of(hint_plain(src), g); }
+  // ISZERO: the image of 1 if c = 0, of 0 otherwise (o + 2^32 - 1 carries into bit 32 exactly when o >= 1)
+  static CAP_HD fe hint_iszero(const fe& src) { return bit_image(zero_bit(hint_plain(src))); }
+  static CAP_HD uint32_t zero_bit(const fe& c) {
+    uint32_t o = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) o |= c.v[i];
+    return 1u ^ (uint32_t)(((uint64_t)o + 0xffffffffull) >> 32);
+  }
+  // INV0: src^(r - 2), the chain of OUT_INV; 0 comes out as 0, without a test (row_value's kind 3: the kernels send an
+  // INV0 item down the rows' path)
+  static CAP_HD fe hint_inv0(const fe& src, const Exps& ex) {
+    fl w[wc29::kWires];
+#pragma unroll
+    for (int i = 0; i < wc29::kWires; i++) w[i] = F::from_ext(src);
+    bool zd;
+    return F::to_ext(row_value<true>([](int) { return F::zero(); }, 3, 0, w, F::zero(), ex, &zd));
   }
 };
 

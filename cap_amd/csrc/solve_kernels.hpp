@@ -13,6 +13,8 @@
 // atomicMin (preset to all ones): the smallest such row, whatever order the lanes arrive in.
 // Rows of a level are ordered by kind, so a wavefront pays the fixed exponentiation (254 squarings) only where its 64
 // rows hold an OUT row with q_ecc or a fifth root.
+// A level's items are its defining rows and its HINT items (kinds INV0, ISZERO, BITS behind the rows' three, INV0 first:
+// next to the other exponentiations): an entry of the level like a row, so the packed decode does not know of them.
 // Compiled in solve.hip, a translation unit of its own: the prover's kernels in plonk.hip keep the code they had.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -24,9 +26,57 @@
 namespace cap {
 namespace pk {
 
-__global__ __launch_bounds__(kSolveThreads) void k_solve_vars(const fe* __restrict__ given /*[count][num_given]*/, SolveTables t,
+// A hint item of kind ISZERO or BITS (the rules: solve29.hpp): the source's image is read from the witness's variables, the
+// targets' images are stored there.  A BITS item stores min(32, count - 32 chunk) images - a bound of the plan, not of the
+// witness - each the image of 1 times its bit; nothing here branches on, or addresses by, a value.  (An INV0 item takes the
+// rows' path: solve_item_ids.)
+__device__ __forceinline__ void solve_hint_item(const SolveHints& t, uint32_t kind, uint32_t hint, uint32_t chunk, fe* vars) {
+  using S = sv29::Solve<>;
+  const sp::Hint h = t.hints[hint];
+  const fe plain = S::hint_plain(vars[h.src]);  // (ids below num_vars: checked when the key took the hints)
+  const uint32_t* tg = t.targets + h.first;
+  const bool bits = kind == sp::BITS;
+  const uint32_t word = bits ? S::word_of(plain, chunk) : S::zero_bit(plain), base = chunk * 32;  // (an ISZERO item: chunk 0)
+  const uint32_t nb = !bits ? 1 : h.count - base < 32 ? h.count - base : 32;
+#pragma unroll 1
+  for (uint32_t b = 0; b < nb; b++) vars[tg[base + b]] = S::bit_image((word >> b) & 1);
+}
+
+// Whether any active lane of the wavefront holds an ISZERO or BITS item: a condition in a scalar register, so that a
+// wavefront of rows alone - every wavefront of a key without hints - branches round that code.
+__device__ __forceinline__ bool solve_any_lane(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0; }
+
+// The variable ids of an item on the rows' path and its target: a row's five cells; an INV0 item's source in every cell
+// (row_value reads cell 0 alone) and the hint's one target.  *j: the row whose selectors the value reads - an INV0 item's
+// value reads none, row 0 stands in.
+__device__ __forceinline__ uint32_t solve_item_ids(const SolveRowTables& t, const SolveHints& hp, const sp::Row& r, uint32_t kind,
+                                                   uint32_t wire, uint32_t* ids, size_t* j) {
+  if (kind == sp::INV0) {
+    const sp::Hint h = hp.hints[r.row];
+#pragma unroll
+    for (int i = 0; i < wc29::kWires; i++) ids[i] = h.src;
+    *j = 0;
+    return hp.targets[h.first];
+  }
+  *j = r.row;
+  uint32_t target = 0;
+#pragma unroll
+  for (int i = 0; i < wc29::kWires; i++) {
+    ids[i] = t.wire_vars[(size_t)i * t.n + r.row];  // (below num_vars: checked when the key took the table)
+    if (wire == (uint32_t)i) target = ids[i];
+  }
+  return target;
+}
+
+// HINTS: whether the key's schedule holds hint items.  A key without hints runs the instantiations without the hint code:
+// with it inlined beside the rows' path the compiler keeps ~190 more scalar values in spill lanes (25 without), which a
+// launch bound by the latency of one dependent chain pays for on every row.  Their item loop is the one from before hints,
+// kept to the letter, and the hint tables travel as the LAST kernel argument (SolveHints; unused there), so that those
+// instantiations are the code they were.
+template <bool HINTS>
+__global__ __launch_bounds__(kSolveThreads) void k_solve_vars(const fe* __restrict__ given /*[count][num_given]*/, SolveRowTables t,
                                                          sv29::Exps ex, fe* vars_out /*[count][num_vars]*/,
-                                                         unsigned long long* __restrict__ status /*[count]*/) {
+                                                         unsigned long long* __restrict__ status /*[count]*/, SolveHints hp) {
   using S = sv29::Solve<>;
   using F = S::F;
   const size_t p = blockIdx.x;
@@ -48,20 +98,41 @@ __global__ __launch_bounds__(kSolveThreads) void k_solve_vars(const fe* __restri
     for (uint32_t k = t.level_off[l] + threadIdx.x; k < end; k += kSolveThreads) {
       const sp::Row r = t.rows[k];
       const uint32_t kind = r.kw & 0xffu, wire = r.kw >> 8;
-      const size_t j = r.row;
-      fl w[wc29::kWires];
-      uint32_t target = 0;
+      if constexpr (!HINTS) {  // the loop as it was before hints, to the letter: the compiler gives it the code it gave it
+        const size_t j = r.row;
+        fl w[wc29::kWires];
+        uint32_t target = 0;
 #pragma unroll
-      for (int i = 0; i < wc29::kWires; i++) {
-        const uint32_t id = t.wire_vars[(size_t)i * t.n + j];  // (below num_vars: checked when the key took the table)
-        if (wire == (uint32_t)i) target = id;
-        w[i] = F::from_ext(vars[id]);
+        for (int i = 0; i < wc29::kWires; i++) {
+          const uint32_t id = t.wire_vars[(size_t)i * t.n + j];  // (below num_vars: checked when the key took the table)
+          if (wire == (uint32_t)i) target = id;
+          w[i] = F::from_ext(vars[id]);
+        }
+        const fe* sel = t.sel + j;
+        const size_t n = t.n;
+        bool zero_den;
+        const fl val = S::row_value([&](int s) { return F::load(sel[(size_t)s * n]); }, kind, wire, w, F::load(t.konst[k]), ex,
+                                    &zero_den);
+        if (zero_den) atomicMin(&status[p], (unsigned long long)j);
+        vars[target] = F::to_ext(val);
+        continue;
       }
+      const bool hint = kind > sp::INV0;
+      if (solve_any_lane(hint)) {
+        if (hint) solve_hint_item(hp, kind, r.row, wire, vars);
+      }
+      if (hint) continue;
+      size_t j;
+      uint32_t ids[wc29::kWires];
+      const uint32_t target = solve_item_ids(t, hp, r, kind, wire, ids, &j);
+      fl w[wc29::kWires];
+#pragma unroll
+      for (int i = 0; i < wc29::kWires; i++) w[i] = F::from_ext(vars[ids[i]]);
       const fe* sel = t.sel + j;
       const size_t n = t.n;
       bool zero_den;
-      const fl val = S::row_value([&](int s) { return F::load(sel[(size_t)s * n]); }, kind, wire, w, F::load(t.konst[k]), ex,
-                                  &zero_den);
+      const fl val = S::template row_value<true>([&](int s) { return F::load(sel[(size_t)s * n]); }, kind, wire, w,
+                                                 F::load(t.konst[k]), ex, &zero_den);
       if (zero_den) atomicMin(&status[p], (unsigned long long)j);
       vars[target] = F::to_ext(val);
     }
@@ -74,12 +145,13 @@ __global__ __launch_bounds__(kSolveThreads) void k_solve_vars(const fe* __restri
 // given + p given_stride and writes vars_out + p vars_stride (the launches of a call with several keys: one per key, over
 // that key's proofs, in rows of the call's largest lengths).  A slot at or beyond `count` loads and stores nothing; its
 // lanes still reach every barrier.  Row by row the arithmetic is k_solve_vars's: the output is the same words.
-template <int W>
+template <int W, bool HINTS>
 __global__ __launch_bounds__(kSolveThreads) void k_solve_vars_packed(const fe* __restrict__ given, size_t given_stride,
-                                                                    SolveTables t, sv29::Exps ex, fe* vars_out,
+                                                                    SolveRowTables t, sv29::Exps ex, fe* vars_out,
                                                                     size_t vars_stride,
                                                                     unsigned long long* __restrict__ status /*per witness*/,
-                                                                    const uint32_t* __restrict__ which, uint32_t count) {
+                                                                    const uint32_t* __restrict__ which, uint32_t count,
+                                                                    SolveHints hp) {
   using S = sv29::Solve<>;
   using F = S::F;
 #pragma unroll 1
@@ -112,22 +184,44 @@ __global__ __launch_bounds__(kSolveThreads) void k_solve_vars_packed(const fe* _
         const uint32_t k = it.k;
         const sp::Row r = t.rows[k];
         const uint32_t kind = r.kw & 0xffu, wire = r.kw >> 8;
-        const size_t j = r.row;
-        fl w[wc29::kWires];
-        uint32_t target = 0;
+        if constexpr (!HINTS) {  // (to the letter what it was before hints, like k_solve_vars's)
+          const size_t j = r.row;
+          fl w[wc29::kWires];
+          uint32_t target = 0;
 #pragma unroll
-        for (int c = 0; c < wc29::kWires; c++) {
-          const uint32_t id = t.wire_vars[(size_t)c * t.n + j];  // (below num_vars: checked when the key took the table)
-          if (wire == (uint32_t)c) target = id;
-          w[c] = F::from_ext(vars[id]);
+          for (int c = 0; c < wc29::kWires; c++) {
+            const uint32_t id = t.wire_vars[(size_t)c * t.n + j];  // (below num_vars: checked when the key took the table)
+            if (wire == (uint32_t)c) target = id;
+            w[c] = F::from_ext(vars[id]);
+          }
+          const fe* sel = t.sel + j;
+          const size_t n = t.n;
+          bool zero_den;
+          const fl val = S::row_value([&](int q) { return F::load(sel[(size_t)q * n]); }, kind, wire, w, F::load(t.konst[k]), ex,
+                                      &zero_den);
+          if (zero_den) atomicMin(&status[p], (unsigned long long)j);
+          vars[target] = F::to_ext(val);
+        } else {
+          const bool hint = kind > sp::INV0;
+          if (solve_any_lane(hint)) {
+            if (hint) solve_hint_item(hp, kind, r.row, wire, vars);
+          }
+          if (!hint) {
+            size_t j;
+            uint32_t ids[wc29::kWires];
+            const uint32_t target = solve_item_ids(t, hp, r, kind, wire, ids, &j);
+            fl w[wc29::kWires];
+#pragma unroll
+            for (int c = 0; c < wc29::kWires; c++) w[c] = F::from_ext(vars[ids[c]]);
+            const fe* sel = t.sel + j;
+            const size_t n = t.n;
+            bool zero_den;
+            const fl val = S::template row_value<true>([&](int q) { return F::load(sel[(size_t)q * n]); }, kind, wire, w,
+                                                       F::load(t.konst[k]), ex, &zero_den);
+            if (zero_den) atomicMin(&status[p], (unsigned long long)j);
+            vars[target] = F::to_ext(val);
+          }
         }
-        const fe* sel = t.sel + j;
-        const size_t n = t.n;
-        bool zero_den;
-        const fl val = S::row_value([&](int q) { return F::load(sel[(size_t)q * n]); }, kind, wire, w, F::load(t.konst[k]), ex,
-                                    &zero_den);
-        if (zero_den) atomicMin(&status[p], (unsigned long long)j);
-        vars[target] = F::to_ext(val);
       }
     }
     __syncthreads();

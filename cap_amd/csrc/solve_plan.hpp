@@ -14,12 +14,22 @@
 // level(given) = 0, level(u) = 1 + the largest level among the other variables of its row: rows of one level are
 // independent, so the kernel walks the levels and spreads a level's rows over its lanes.  Inside a level the rows are
 // ordered by kind, then by row, so that a wavefront meets one kind wherever the level is wide enough.
+//
+// HINTS (solve_plan_hints).  A hint gives `count` target variables a value computed from ONE source variable: the bits of
+// its canonical value (BITS), its inverse or 0 (INV0), whether it is zero (ISZERO).  A hint is READY when its source is in
+// V and it has not fired; firing takes the ready hint of lowest index, its targets join V with level 1 + level(src), and
+// this repeats until no hint is ready - once before row 0 and again after every row that defines a variable.  The row
+// walk itself is unchanged: a row whose variables all have a value is a constraint, so a hinted variable sits on any wire.
+// A level's ITEMS are its defining rows and its hint items: one per INV0 / ISZERO hint, ceil(count / 32) per BITS hint
+// (item g: bits 32 g .. 32 g + 31), ordered by (kind, row or hint index, chunk) with INV0 next to the other two kinds
+// that pay the 254-squaring chain.  Without hints the plan is what it was before hints existed, byte for byte.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 
 #include <algorithm>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -34,34 +44,53 @@ enum Kind : uint32_t {
   OUT_MUL = 0,  // q_ecc = 0: w4 = rest * (1 / q_o), the constant made at set-up
   OUT_INV = 1,  // q_ecc != 0: one inversion per witness
   ROOT5 = 2,    // a fifth root on wire (kw >> 8)
+  // hint items: Row::row is the index into Plan::hints, kw >> 8 the 32-bit chunk (BITS) or 0
+  INV0 = 3,    // src^(r - 2): 0 for 0
+  ISZERO = 4,  // 1 if src = 0 mod r, else 0
+  BITS = 5,    // bits 32 g .. 32 g + 31 of the canonical value of src
+};
+constexpr uint32_t kFirstHintKind = INV0;
+
+// a hint as the caller lists it (capgpu_hint's layout) and as the kernel reads it: targets[first .. first + count)
+constexpr uint32_t HINT_BITS = 0, HINT_INV0 = 1, HINT_ISZERO = 2;
+constexpr uint32_t kMaxBits = 254;
+struct Hint {
+  uint32_t kind, src, first, count;
 };
 
-// one defining row as the kernel reads it
+// one item as the kernel reads it: a defining row, or a hint item
 struct Row {
-  uint32_t row;
-  uint32_t kw;  // kind | target wire << 8
+  uint32_t row;  // the row; a hint item: the hint's index
+  uint32_t kw;   // kind | target wire << 8; a hint item: kind | chunk << 8
 };
 inline uint32_t row_kind(const Row& r) { return r.kw & 0xffu; }
 inline uint32_t row_wire(const Row& r) { return r.kw >> 8; }
 
 struct Plan {
-  std::vector<Row> rows;            // ordered by (level, kind, row)
+  std::vector<Row> rows;            // the items, ordered by (level, kind, row or hint index, chunk)
   std::vector<uint32_t> level_off;  // levels + 1 offsets into rows: level l (1-based l + 1) is rows[level_off[l] .. level_off[l + 1])
   std::vector<int32_t> slot;        // [num_vars]: index in the given list, -1 for a variable that is not given
+  std::vector<Hint> hints;          // the caller's list, checked
+  std::vector<uint32_t> targets;    // the caller's target ids, checked
+  // num_defined, inv_rows and root_rows count rows; levels and widest_level count items
   uint64_t num_given = 0, num_defined = 0, levels = 0, widest_level = 0, inv_rows = 0, root_rows = 0;
+  uint64_t num_hinted = 0, bits_hints = 0, inv_hints = 0, iszero_hints = 0, hint_items = 0;
   std::string error;  // empty: the plan stands
 };
 
-inline std::string fmt(const char* f, unsigned long long a = 0, unsigned long long b = 0, unsigned long long c = 0) {
+inline std::string fmt(const char* f, unsigned long long a = 0, unsigned long long b = 0, unsigned long long c = 0,
+                       unsigned long long d = 0) {
   char buf[256];
-  snprintf(buf, sizeof buf, f, a, b, c);
+  snprintf(buf, sizeof buf, f, a, b, c, d);
   return buf;
 }
 
 // wire_vars: [5][n] ids below num_vars; sel_zero: [13][n], non-zero where the selector's value is 0 mod r.
 // Returns false with Plan::error set when the circuit or the list is refused.
-inline bool solve_plan(size_t n, size_t num_inputs, size_t num_vars, const uint32_t* wire_vars, const uint8_t* sel_zero,
-                       const uint32_t* given, size_t num_given, Plan* out) {
+// hints / targets: the hint list (none: the rule without hints).  Every hint refusal names the hint's index.
+inline bool solve_plan_hints(size_t n, size_t num_inputs, size_t num_vars, const uint32_t* wire_vars, const uint8_t* sel_zero,
+                             const uint32_t* given, size_t num_given, const Hint* hints, size_t num_hints,
+                             const uint32_t* targets, size_t num_targets, Plan* out) {
   Plan& P = *out;
   P = Plan();
   P.slot.assign(num_vars, -1);
@@ -85,6 +114,102 @@ inline bool solve_plan(size_t n, size_t num_inputs, size_t num_vars, const uint3
     uint32_t level, kind, row, wire;
   };
   std::vector<Item> items;
+  // the hints by source (by_src[src_off[v] .. src_off[v + 1]), ascending), the ready ones in a min-heap of indices
+  std::vector<uint32_t> src_off, by_src, def_row, ready;
+  std::vector<uint8_t> fired;
+  if (num_hints) {
+    std::vector<int64_t> owner(num_vars, -1);  // the hint that lists the variable as a target
+    for (size_t h = 0; h < num_hints; h++) {
+      const Hint& H = hints[h];
+      if (H.kind > HINT_ISZERO) {
+        P.error = fmt("hint %llu: unknown kind %llu (source variable %llu)", h, H.kind, H.src);
+        return false;
+      }
+      if (H.count < 1 || H.count > (H.kind == HINT_BITS ? kMaxBits : 1u)) {
+        P.error = fmt("hint %llu: count %llu is out of range for its kind %llu (source variable %llu)", h, H.count, H.kind, H.src);
+        return false;
+      }
+      if ((uint64_t)H.first + H.count > num_targets) {
+        P.error = fmt("hint %llu: first + count = %llu, num_targets is %llu (source variable %llu)", h, (uint64_t)H.first + H.count,
+                      num_targets, H.src);
+        return false;
+      }
+      if (H.src >= num_vars) {
+        P.error = fmt("hint %llu: its source variable %llu is not below num_vars %llu", h, H.src, num_vars);
+        return false;
+      }
+      for (uint32_t i = 0; i < H.count; i++) {
+        const uint32_t t = targets[H.first + i];
+        if (t >= num_vars) {
+          P.error = fmt("hint %llu: its target %llu, variable %llu, is not below num_vars %llu", h, i, t, num_vars);
+          return false;
+        }
+        if (t == H.src) {
+          P.error = fmt("hint %llu: its target %llu is its own source variable %llu", h, i, t);
+          return false;
+        }
+        if (P.slot[t] >= 0) {
+          P.error = fmt("hint %llu: its target variable %llu is given (given_vars[%llu])", h, t, (unsigned long long)P.slot[t]);
+          return false;
+        }
+        if (owner[t] >= 0) {
+          P.error = fmt("hint %llu: its target variable %llu is listed twice (hint %llu has it too)", h, t,
+                        (unsigned long long)owner[t]);
+          return false;
+        }
+        owner[t] = (int64_t)h;
+      }
+    }
+    P.hints.assign(hints, hints + num_hints);
+    P.targets.assign(targets, targets + num_targets);
+    src_off.assign(num_vars + 1, 0);
+    for (size_t h = 0; h < num_hints; h++) src_off[hints[h].src + 1]++;
+    for (size_t v = 0; v < num_vars; v++) src_off[v + 1] += src_off[v];
+    by_src.resize(num_hints);
+    {
+      std::vector<uint32_t> at(src_off.begin(), src_off.end() - 1);
+      for (size_t h = 0; h < num_hints; h++) by_src[at[hints[h].src]++] = (uint32_t)h;
+    }
+    def_row.assign(num_vars, 0);
+    fired.assign(num_hints, 0);
+  }
+  // v got a value: its hints are ready
+  auto valued = [&](uint32_t v) {
+    if (!num_hints) return;
+    for (uint32_t k = src_off[v]; k < src_off[v + 1]; k++) {
+      ready.push_back(by_src[k]);
+      std::push_heap(ready.begin(), ready.end(), std::greater<uint32_t>());
+    }
+  };
+  // fires the ready hint of lowest index until none is ready
+  auto fire = [&]() {
+    while (!ready.empty()) {
+      std::pop_heap(ready.begin(), ready.end(), std::greater<uint32_t>());
+      const uint32_t h = ready.back();
+      ready.pop_back();
+      const Hint& H = hints[h];
+      const uint32_t lvl = (uint32_t)level[H.src] + 1;
+      for (uint32_t i = 0; i < H.count; i++) {
+        const uint32_t t = targets[H.first + i];
+        if (level[t] >= 0) {  // (not given, not another hint's: a row defined it)
+          P.error = fmt("hint %llu: its target variable %llu already has a value when the hint fires (row %llu defines it)", h, t,
+                        def_row[t]);
+          return false;
+        }
+        level[t] = (int32_t)lvl;
+      }
+      fired[h] = 1;
+      const uint32_t kind = H.kind == HINT_BITS ? BITS : H.kind == HINT_INV0 ? INV0 : ISZERO;
+      for (uint32_t g = 0; g < (H.count + 31) / 32; g++) items.push_back(Item{lvl, kind, h, g});
+      P.hint_items += (H.count + 31) / 32;
+      P.num_hinted += H.count;
+      (H.kind == HINT_BITS ? P.bits_hints : H.kind == HINT_INV0 ? P.inv_hints : P.iszero_hints)++;
+      for (uint32_t i = 0; i < H.count; i++) valued(targets[H.first + i]);
+    }
+    return true;
+  };
+  for (size_t k = 0; k < num_given; k++) valued(given[k]);
+  if (!fire()) return false;
   auto zero = [&](int s, size_t j) { return sel_zero[(size_t)s * n + j] != 0; };
   for (size_t j = 0; j < n; j++) {
     uint32_t v[kWires];
@@ -131,11 +256,23 @@ inline bool solve_plan(size_t n, size_t num_inputs, size_t num_vars, const uint3
     }
     level[u[0]] = (int32_t)it.level;
     items.push_back(it);
+    if (num_hints) {
+      def_row[u[0]] = (uint32_t)j;
+      valued(u[0]);
+      if (!fire()) return false;
+    }
   }
+  for (size_t h = 0; h < num_hints; h++)
+    if (!fired[h]) {
+      P.error = fmt("hint %llu: its source variable %llu never gets a value", h, hints[h].src);
+      return false;
+    }
+  const size_t num_rows = items.size() - (size_t)P.hint_items;
   std::sort(items.begin(), items.end(), [](const Item& a, const Item& b) {
     if (a.level != b.level) return a.level < b.level;
     if (a.kind != b.kind) return a.kind < b.kind;
-    return a.row < b.row;
+    if (a.row != b.row) return a.row < b.row;
+    return a.wire < b.wire;  // (a hint's chunks; a row comes once)
   });
   P.level_off.push_back(0);
   for (size_t k = 0; k < items.size(); k++) {
@@ -147,10 +284,15 @@ inline bool solve_plan(size_t n, size_t num_inputs, size_t num_vars, const uint3
   }
   if (!items.empty()) P.level_off.push_back((uint32_t)items.size());
   P.levels = P.level_off.size() - 1;
-  P.num_defined = items.size();
+  P.num_defined = num_rows;
   for (size_t l = 0; l + 1 < P.level_off.size(); l++)
     P.widest_level = std::max<uint64_t>(P.widest_level, P.level_off[l + 1] - P.level_off[l]);
   return true;
+}
+
+inline bool solve_plan(size_t n, size_t num_inputs, size_t num_vars, const uint32_t* wire_vars, const uint8_t* sel_zero,
+                       const uint32_t* given, size_t num_given, Plan* out) {
+  return solve_plan_hints(n, num_inputs, num_vars, wire_vars, sel_zero, given, num_given, nullptr, 0, nullptr, 0, out);
 }
 
 }  // namespace sp

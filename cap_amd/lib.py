@@ -745,6 +745,59 @@ def plonk_key_solver_info(pk_handle: int) -> SolverInfo:
     return info
 
 
+HINT_BITS, HINT_INV0, HINT_ISZERO = 0, 1, 2  # CAPGPU_HINT_*
+
+
+class Hint(ctypes.Structure):
+    """capgpu_hint: `count` targets, targets[first .. first + count), valued from the variable src"""
+    _fields_ = [("kind", ctypes.c_uint32), ("src", ctypes.c_uint32), ("first", ctypes.c_uint32), ("count", ctypes.c_uint32)]
+
+
+class HintInfo(ctypes.Structure):
+    """capgpu_hint_info: the figures of a key's solver hints; all zero: the key has none."""
+    _fields_ = [("num_hints", ctypes.c_uint64), ("num_hinted", ctypes.c_uint64), ("bits_hints", ctypes.c_uint64),
+                ("inv_hints", ctypes.c_uint64), ("iszero_hints", ctypes.c_uint64), ("hint_items", ctypes.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+def plonk_key_set_given_hints(pk_handle: int, given_vars, hints):
+    """capgpu_plonk_key_set_given_hints: plonk_key_set_given with a hint list.  hints: (kind, src, [targets]) entries -
+    HINT_BITS (target i = bit i of the value of src, 1 .. 254 targets), HINT_INV0 (one target: 1 / src, 0 for 0),
+    HINT_ISZERO (one target: 1 if src is 0, else 0) - in the order in which the circuit's builder made them.  The targets
+    need not be given: the solver computes them on the device when their source has its value (the rule: include/capgpu.h).
+    -> (SolverInfo, HintInfo).  Refused (-1), naming the hint's index and the variable, or the lowest offending row."""
+    g = np.asarray(given_vars)
+    if g.size and (g.min() < 0 or g.max() > 0xFFFFFFFF):
+        raise CapGpuError(-1, "given_vars ids must fit 32 bits")
+    g = np.ascontiguousarray(g, dtype=np.uint32).reshape(-1)
+    hints = list(hints)
+    table = (Hint * max(len(hints), 1))()
+    flat = []
+    for i, (kind, src, tg) in enumerate(hints):
+        tg = [int(t) for t in tg]
+        if not (0 <= int(kind) <= 0xFFFFFFFF and 0 <= int(src) <= 0xFFFFFFFF and all(0 <= t <= 0xFFFFFFFF for t in tg)):
+            raise CapGpuError(-1, f"hint {i}: kind, src and targets must fit 32 bits")
+        table[i] = Hint(int(kind), int(src), len(flat), len(tg))
+        flat.extend(tg)
+    if len(flat) > 0xFFFFFFFF:
+        raise CapGpuError(-1, "the hints' targets must number below 2^32")
+    t = np.ascontiguousarray(flat if flat else [0], dtype=np.uint32)
+    info, hinfo = SolverInfo(), HintInfo()
+    check(load().capgpu_plonk_key_set_given_hints(
+        ctypes.c_uint64(pk_handle), g.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.c_size_t(g.size), table,
+        ctypes.c_size_t(len(hints)), t.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.c_size_t(len(flat)),
+        ctypes.byref(info), ctypes.byref(hinfo)))
+    return info, hinfo
+
+
+def plonk_key_hint_info(pk_handle: int) -> HintInfo:
+    info = HintInfo()
+    check(load().capgpu_plonk_key_hint_info(ctypes.c_uint64(pk_handle), ctypes.byref(info)))
+    return info
+
+
 def plonk_solve_vars(pk_handle: int, given, count: int = 1, out: "DevBuf | None" = None):
     """capgpu_plonk_solve_vars[_dev]: completes `count` assignments from their given values.  given: (count, num_given, 4)
     Montgomery words in the order of the key's given list - a numpy array, or a DevBuf of that content.

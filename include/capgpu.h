@@ -483,17 +483,44 @@ int capgpu_plonk_key_num_vars(uint64_t pk_handle, size_t* num_vars_out);
  * Per witness, an OUT row whose denominator is 0 mod r sets its variable to 0 and the witness's status becomes
  * {kind 1, row = the LOWEST such row}; the other witnesses of the call are unaffected.
  *
+ * HINTS (capgpu_plonk_key_set_given_hints).  What a circuit builder computes beside its rows - the bits of a value, an
+ * inverse, a zero flag - need not be given: a hint gives `count` target variables their values from ONE source variable.
+ *   BITS    1 <= count <= 254: c is the canonical integer of src, 0 <= c < r; target i is the field element 0 or 1 equal
+ *           to bit i of c.  Bits beyond `count` are dropped silently: the circuit's recomposition row then fails in
+ *           capgpu_plonk_check_witness*, which is where checking lives.
+ *   INV0    count = 1: src^(r - 2), the chain an OUT row with q_ecc uses; 0 comes out as 0, without a test.
+ *   ISZERO  count = 1: 1 if src = 0 mod r, else 0.
+ * Firing.  A hint is READY when its src is in V and it has not fired.  Firing takes the ready hint of lowest index; its
+ * targets join V with level = 1 + level(src); this repeats until no hint is ready.  Firing runs once before row 0 and
+ * again after every row that defines a variable.  A hint whose source is another hint's target chains by this alone.
+ * The row walk is unchanged: a row whose variables are all valued is a constraint, so a hinted variable may sit on any
+ * wire - jf-relation's unpack / is_zero / is_equal lay theirs on input wires.
+ * Items.  A level's kernel items are its defining rows plus its hint items: INV0 and ISZERO one each, a BITS hint
+ * ceil(count / 32), item g holding bits 32 g .. 32 g + 31.  Inside a level the items are ordered by (kind, row or hint
+ * index, chunk): the rows' three kinds, then INV0 - next to the other exponentiations - then ISZERO, then BITS.
+ * capgpu_solver_info: num_defined, inv_rows and root_rows count rows only; levels, widest_level and the median behind the
+ * automatic pack width count items.  For a key without hints the schedule is byte for byte the one without this rule.
+ * Hint refusals are CAPGPU_ERR_INVALID_ARG at set-up, each naming the hint's index and the variable, the key unchanged:
+ * an unknown kind; src or a target at or beyond num_vars; a count out of range for the kind; first + count > num_targets;
+ * a target listed twice (in one hint or two); a target equal to its src; a target that is given; a target that already
+ * has a value when its hint fires (the defining row is named); a hint whose source never gets a value.  Row refusals are
+ * unchanged and still name their lowest row.  No hint sets a status word.
+ *
  * TIMING.  Given values are secret.  Both exponentiations of this path - a^(r-2) for the inversion, a^e for the fifth
  * root - walk the bits of a public exponent: 254 squarings and one product per set bit, whatever the base; no
  * variable-time inversion is used per witness.  The constants 1 / q_o and 1 / q_hash_i are functions of the circuit
  * alone.  Which rows run which chain is a property of the circuit, not of the witness.  The one data-dependent step is
- * the zero test of an inverted denominator, whose outcome the status reports anyway.  (The paragraph at
- * capgpu_plonk_set_wire_commit describes the prover itself.) */
+ * the zero test of an inverted denominator, whose outcome the status reports anyway.  In a hint item no branch, loop
+ * bound or address depends on a witness value: INV0 is the same public-exponent chain without any zero test; BITS takes
+ * the canonical integer through the field's fixed-sequence conversion, selects its 32-bit word by a chain of selects
+ * over a public chunk number, and stores count-many images (a bound of the circuit), each the words of 1's image times
+ * the bit; ISZERO ors the eight words and turns "non-zero" into a bit by a carry, then selects the same way.  (The
+ * paragraph at capgpu_plonk_set_wire_commit describes the prover itself.) */
 typedef struct capgpu_solver_info {
   uint64_t num_given;    /* ids in the given list */
   uint64_t num_defined;  /* variables defined by a row */
   uint64_t levels;       /* dependency depth */
-  uint64_t widest_level; /* rows of the widest level */
+  uint64_t widest_level; /* items (rows, and hint items if the key has hints) of the widest level */
   uint64_t inv_rows;     /* OUT rows with q_ecc != 0: one inversion per witness each */
   uint64_t root_rows;    /* ROOT5 rows */
 } capgpu_solver_info; /* 48 bytes */
@@ -510,6 +537,34 @@ int capgpu_plonk_key_set_given(uint64_t pk_handle, const uint32_t* given_vars, s
                                capgpu_solver_info* info_out);
 /* the schedule's figures; all zero: the key has no solver */
 int capgpu_plonk_key_solver_info(uint64_t pk_handle, capgpu_solver_info* info_out);
+#define CAPGPU_HINT_BITS 0   /* count targets, 1 <= count <= 254: target i = bit i of the canonical value of src */
+#define CAPGPU_HINT_INV0 1   /* count == 1: src^-1 mod r, and 0 for src = 0 */
+#define CAPGPU_HINT_ISZERO 2 /* count == 1: 1 if src = 0 mod r, else 0 */
+typedef struct capgpu_hint {
+  uint32_t kind;  /* CAPGPU_HINT_* */
+  uint32_t src;   /* the source variable */
+  uint32_t first; /* the hint's targets are targets[first .. first + count) */
+  uint32_t count;
+} capgpu_hint; /* 16 bytes */
+typedef struct capgpu_hint_info {
+  uint64_t num_hints;    /* hints in the list */
+  uint64_t num_hinted;   /* variables that are a hint's target */
+  uint64_t bits_hints;   /* hints of each kind */
+  uint64_t inv_hints;
+  uint64_t iszero_hints;
+  uint64_t hint_items;   /* kernel items the hints add to the levels */
+} capgpu_hint_info; /* 48 bytes */
+/* capgpu_plonk_key_set_given with a hint list (HINTS above); capgpu_plonk_key_set_given is this call with num_hints == 0.
+ * The hint tables are key-resident like the rows: replicated to a context on first use, replaced by a second set-up call
+ * (either one), dropped by capgpu_plonk_key_set_vars, freed by capgpu_plonk_free_key.  Every later entry point -
+ * capgpu_plonk_solve_vars[_dev], capgpu_plonk_prove_given[_dev|_async], capgpu_plonk_reserve_given,
+ * capgpu_plonk_set_solve_pack - uses whatever schedule the key holds; per-call scratch is what it was.  hints may be NULL
+ * when num_hints == 0, targets when num_targets == 0; info_out and hint_info_out may be NULL. */
+int capgpu_plonk_key_set_given_hints(uint64_t pk_handle, const uint32_t* given_vars, size_t num_given,
+                                     const capgpu_hint* hints, size_t num_hints, const uint32_t* targets,
+                                     size_t num_targets, capgpu_solver_info* info_out, capgpu_hint_info* hint_info_out);
+/* the figures of the key's hints; all zero: no hints */
+int capgpu_plonk_key_hint_info(uint64_t pk_handle, capgpu_hint_info* info_out);
 /* Completes `count` assignments.  given: count x num_given field elements (Montgomery), per witness in the order of
  * given_vars, copied to their variables as they are; vars_out: count x num_vars; status_out: count verdicts.  Returns
  * CAPGPU_OK whenever the solve ran - verdicts are in status_out; count == 0 returns CAPGPU_OK and writes nothing.  The

@@ -15,6 +15,15 @@ n = 2^15: 2 425 given values per witness, 18 193 defined ones, 584 levels, 5 840
                                unbound thread (a call = one ticket: wait for the oldest, submit the next);
       host_vars_async_2x256    the same with plonk_prove_multi_async(vars) of 256 host-resident value vectors - its comparison;
       beside solve_prove_256 and host_vars_prove_256 as above.  Default --out profiles/solve_packed.txt.
+  (e) --hinted: cap_like_hinted_circuit("transfer_2x2") - scalars, amounts and roots given; bits, inverses and zero flags
+      hinted (capgpu_plonk_key_set_given_hints) - beside the unhinted model in ONE session, arms interleaved:
+      solve_<count> / solve_<count>_hinted at --counts (default 1,256,4096) and prove_given_256 / prove_given_256_hinted
+      from resident given values.  Prints each key's given count, bytes per proof, capgpu_solver_info and capgpu_hint_info.
+      Default --out profiles/solve_hints.txt.
+  (f) a comparison of two LIBRARIES (CAPGPU_LIBRARY names the one a process loads): one process per library and turn, each
+      with --label NAME --append --out FILE, e.g. for NAME in parent_1 tree_1 parent_2 tree_2
+          python tools/gpu_solve_ab.py --counts 256,4096 --arms solve_256,solve_4096 --label NAME --append --out profiles/solve_hints_ab.txt
+      then  python tools/gpu_solve_ab.py --ab-summary profiles/solve_hints_ab.txt  appends each label's medians and spreads.
   --arms a,b runs those arms only (no summary lines), --reps N instead of three repetitions, --no-profile leaves the
   library's kernel timer off: for a run of one arm under an external profiler.
 Protocol: per arm 3 warm-up + 10 timed calls, the arms interleaved, three repetitions; the median of the three medians and
@@ -41,15 +50,133 @@ def arg(name, default):
     return sys.argv[sys.argv.index(name) + 1] if name in sys.argv else default
 
 
+def hinted_main():
+    steps, reps = int(arg("--steps", 10)), int(arg("--reps", 3))
+    counts = [int(c) for c in arg("--counts", "1,256,4096").split(",")]
+    out = open(arg("--out", os.path.join(ROOT, "profiles", "solve_hints.txt")), "w")
+
+    def emit(obj):
+        line = json.dumps(obj)
+        print(line, flush=True)
+        out.write(line + "\n")
+        out.flush()
+
+    cg.init(0)
+    cg.set_device(0)
+    tau = bu.SplitMix64(0xCA9).field()
+    top = max(counts + [P])
+    idx = np.arange(top) % DISTINCT
+    blind = np.stack([bu.to_mont_array(bu.blinders(7000 + i)) for i in range(P)])
+    msgs = [b"ab"] * P
+    keys = {}
+    srs = None
+    for name in ("", "_hinted"):
+        if name:
+            sc, given, hints = bu.cap_like_hinted_circuit("transfer_2x2")
+            gv = np.stack([bu.to_mont_array(bu.cap_like_given_values(sc, 5000 + i)) for i in range(DISTINCT)])
+        else:
+            sc = bu.cap_like_circuit("transfer_2x2")
+            given, hints = [0, 1] + list(sc.free_vars), []
+            w, _ = sc.witnesses_mont(np.arange(5000, 5000 + DISTINCT, dtype=np.uint64), threads=16)
+            vals = np.zeros((DISTINCT, sc.num_vars, 4), np.uint64)
+            vals[:, np.array(sc.wire_vars).reshape(-1)] = w.reshape(DISTINCT, 5 * sc.n, 4)
+            vals[:, 0], vals[:, 1] = bu.to_mont_array([0])[0], bu.to_mont_array([1])[0]
+            gv = np.ascontiguousarray(vals[:, given])
+        n, nv = sc.n, sc.num_vars
+        srs = srs if srs is not None else cg.srs_generate(tau, n + 3)
+        pk, _ = cg.plonk_preprocess_vars(srs, n, sc.num_inputs, sc.selectors_mont(), np.array(sc.wire_vars, dtype=np.int64), nv)
+        t0 = time.perf_counter()
+        info, hinfo = cg.plonk_key_set_given_hints(pk, given, hints)
+        set_s = time.perf_counter() - t0
+        at = {v: k for k, v in enumerate(given)}
+        pubs = np.ascontiguousarray(gv[idx[:P]][:, [at[v] for v in sc.pub_vars]])
+        d_given = cg.DevBuf.from_numpy(gv[idx])
+        d_vars = cg.DevBuf(top * nv * 32)
+        # every solved witness passes the witness check (once, outside every timed part)
+        _, st = cg.plonk_solve_vars(pk, d_given.view(0, P * len(given) * 32), P, out=d_vars)
+        faults = cg.plonk_check_witness_batch(pk, d_vars.view(0, P * nv * 32), pubs, P, input_form="vars")
+        assert all(s.kind == 0 for s in st) and all(f.kind == 0 for f in faults)
+        cg.plonk_reserve_given(pk, P, slot=-1)
+        keys[name] = (pk, len(given), nv, pubs, d_given, d_vars)
+        emit({"circuit": "transfer_2x2" + name, "n": n, "num_vars": nv, "gate_rows": sc.gate_rows, "num_hints": len(hints),
+              "solver_info": info.as_dict(), "hint_info": hinfo.as_dict(), "set_given_s": round(set_s, 3),
+              "bytes_per_proof": {"given": len(given) * 32, "vars": nv * 32, "columns": 5 * n * 32}, "steps": steps, "warmup": WARM})
+
+    def solve_arm(name, count):
+        pk, ng, _, _, d_given, d_vars = keys[name]
+        g = d_given.view(0, count * ng * 32)
+
+        def run(k):
+            for _ in range(k):
+                cg.plonk_solve_vars(pk, g, count, out=d_vars)
+        return run
+
+    def prove_arm(name):
+        pk, ng, _, pubs, d_given, _ = keys[name]
+        g = d_given.view(0, P * ng * 32)
+
+        def run(k):
+            for _ in range(k):
+                cg.plonk_prove_given([pk] * P, g, pubs, blind, msgs)
+        return run
+
+    arms = [(f"solve_{c}{name}", solve_arm(name, c), c) for c in counts for name in keys]
+    arms += [(f"prove_given_256{name}", prove_arm(name), P) for name in keys]
+    only = arg("--arms", None)
+    if only:
+        arms = [a for a in arms if a[0] in only.split(",")]
+    call_ms = {name: [] for name, _, _ in arms}
+    for rep in range(reps):
+        for name, fn, count in arms:
+            fn(WARM)
+            t0 = time.perf_counter()
+            fn(steps)
+            dt = time.perf_counter() - t0
+            call_ms[name].append(1e3 * dt / steps)
+            emit({"arm": name, "rep": rep, "witnesses": count, "call_ms": round(1e3 * dt / steps, 3)})
+    med = {k: statistics.median(v) for k, v in call_ms.items()}
+    emit({"median_call_ms": {k: round(v, 3) for k, v in med.items()},
+          "spread_rel": {k: round((max(v) - min(v)) / med[k], 4) for k, v in call_ms.items()},
+          "hinted_over_unhinted_call_time": {a: round(med[a + "_hinted"] / med[a], 4) for a in med if a + "_hinted" in med},
+          "solve_stats": cg.plonk_solve_stats()})
+    for pk, _, _, _, d_given, d_vars in keys.values():
+        d_given.free()
+        d_vars.free()
+        cg.plonk_free_key(pk)
+    cg.srs_free(srs)
+    cg.shutdown()
+    out.close()
+
+
+def ab_summary(path):
+    """per label and arm of a file of labelled runs: the median of the repetitions' call times and their spread"""
+    calls = {}
+    for line in open(path):
+        r = json.loads(line)
+        if "label" in r and "arm" in r:
+            calls.setdefault(f"{r['label']}_{r['arm']}", []).append(r["call_ms"])
+    summary = {k: {"median_call_ms": statistics.median(v), "spread_rel": round((max(v) - min(v)) / statistics.median(v), 4)}
+               for k, v in sorted(calls.items())}
+    line = json.dumps({"ab_summary": summary})
+    print(line)
+    with open(path, "a") as out:
+        out.write(line + "\n")
+
+
 def main():
+    if "--ab-summary" in sys.argv:
+        return ab_summary(arg("--ab-summary", None))
+    if "--hinted" in sys.argv:
+        return hinted_main()
     steps = int(arg("--steps", 10))
     counts = [int(c) for c in arg("--counts", "1,256,1024,4096").split(",")]
     packed = "--packed" in sys.argv
     out_path = arg("--out", os.path.join(ROOT, "profiles", "solve_packed.txt" if packed else "solve_vars.txt"))
-    out = open(out_path, "w")
+    out = open(out_path, "a" if "--append" in sys.argv else "w")
+    label = arg("--label", None)
 
     def emit(obj):
-        line = json.dumps(obj)
+        line = json.dumps({"label": label, **obj} if label else obj)
         print(line, flush=True)
         out.write(line + "\n")
         out.flush()
