@@ -392,6 +392,12 @@ extern "C" {
     pub fn capgpu_plonk_get_solve_pack(w_out: *mut c_int) -> c_int;
     pub fn capgpu_plonk_solve_stats(launches_out: *mut u64, witnesses_out: *mut u64,
                                     packed_launches_out: *mut u64) -> c_int;
+    // ---- Fr inversion: the form the solver's launches and the batch calls run (CAPGPU_INVERSE_*), the batch inverse
+    pub fn capgpu_fr_set_inverse_form(form: c_int) -> c_int;
+    pub fn capgpu_fr_get_inverse_form(form_out: *mut c_int) -> c_int;
+    pub fn capgpu_fr_inverse_batch(h_in: *const c_void, h_out: *mut c_void, count: usize) -> c_int;
+    pub fn capgpu_fr_inverse_batch_dev(d_in: *const c_void, d_out: *mut c_void, count: usize) -> c_int;
+    pub fn capgpu_fr_inverse_stats(fermat_launches_out: *mut u64, gcd_launches_out: *mut u64) -> c_int;
     pub fn capgpu_plonk_prove_given(pk_handles: *const u64, count: c_int, given: *const u64, pub_inputs: *const u64,
                                     num_inputs: usize, ext_msgs: *const *const u8, ext_msg_lens: *const usize,
                                     blinders: *const u64, proofs_out: *mut capgpu_proof,
@@ -550,6 +556,8 @@ pub fn set_wire_commit_from_evals(on: bool) -> Result<()> {
 pub const CAPGPU_PAIRING_LANE: c_int = 0;
 pub const CAPGPU_PAIRING_WAVE: c_int = 1;
 
+pub const CAPGPU_INVERSE_FERMAT: c_int = 0;
+pub const CAPGPU_INVERSE_GCD: c_int = 1;
 pub const CAPGPU_TRANSCRIPT_HOST: c_int = 0;
 pub const CAPGPU_TRANSCRIPT_DEVICE: c_int = 1;
 

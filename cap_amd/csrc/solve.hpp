@@ -54,6 +54,11 @@ struct SolveLaunch {
   const uint32_t* d_which;
 };
 void solve_launch_packed(hipStream_t s, int W, const SolveLaunch& a, const SolveTables& t, const sv29::Exps& ex);
+// The process's inverse form (capgpu_fr_set_inverse_form; sv29::kInvFermat or sv29::kInvGcd): both launches above read it
+// and run the instantiation of that form - the caller does not pass it.
+int inverse_form_setting();
+// k_fr_inverse over `count` field images on stream s, in the form set; d_in == d_out is allowed
+void fr_inverse_launch(hipStream_t s, const fe* d_in, fe* d_out, size_t count, const sv29::Exps& ex);
 // capgpu_plonk_solve_stats: launches, witnesses, launches at W > 1
 void solve_stats(uint64_t* launches, uint64_t* witnesses, uint64_t* packed);
 void solve_stats_reset();

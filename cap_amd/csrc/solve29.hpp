@@ -12,13 +12,19 @@
 // reported anyway.
 // The three HINT rules (capgpu_plonk_key_set_given_hints; the plan: solve_plan.hpp) are here too - the bits of a source's
 // canonical value, its inverse or 0, its zero flag - as the same host + device code: tests/cpp/solve_hints_check.cpp.
+// The inversions of kinds OUT_INV and INV0 have two forms, chosen at compile time (INV): Fermat's a^(r - 2) over the public
+// exponent as above - the default - or the constant-time GCD of invgcd29.hpp (a fixed count of divsteps, masks and selects
+// only: the rule above holds for it too).  Both give the same canonical value, 0 for 0; ROOT5 is a 254-bit power by nature
+// and keeps its chain in either form.
 #pragma once
 #include "gatecheck29.hpp"
+#include "invgcd29.hpp"
 
 namespace cap {
 namespace sv29 {
 
 constexpr int kExpBits = 254;  // both exponents are below r < 2^254
+constexpr int kInvFermat = 0, kInvGcd = 1;  // the inverse forms (CAPGPU_INVERSE_FERMAT, CAPGPU_INVERSE_GCD)
 
 // the two exponents, 8 x 32-bit words each, little endian
 struct Exps {
@@ -71,7 +77,7 @@ inline bool derive_exps(Exps* out) {
   return true;
 }
 
-template <int SCHED = CAP_FL_SCHED>
+template <int SCHED = CAP_FL_SCHED, int INV = kInvFermat>
 struct Solve {
   using F = Fl<FrP29, SCHED>;
 
@@ -142,6 +148,10 @@ struct Solve {
     } else {
       base = w_in[0];
     }
+    if constexpr (INV == kInvGcd) {  // kinds 1 and 3 by the GCD; a fifth root keeps its power
+      const fl g = kind == 2 ? pow_words(base, [&](int w) { return ex.root5[w]; }) : inv_gcd<FrP29, SCHED>(base);
+      return kind == 1 ? F::mul(r, g) : g;
+    }
     const fl p = pow_words(base, [&](int w) { return (WITH_INV0 ? kind != 2 : kind == 1) ? ex.inv[w] : ex.root5[w]; });
     return kind == 1 ? F::mul(r, p) : p;
   }
@@ -179,7 +189,7 @@ struct Solve {
     for (int i = 0; i < 8; i++) o |= c.v[i];
     return 1u ^ (uint32_t)(((uint64_t)o + 0xffffffffull) >> 32);
   }
-  // INV0: src^(r - 2), the chain of OUT_INV; 0 comes out as 0, without a test (row_value's kind 3: the kernels send an
+  // INV0: src^(r - 2), the chain of OUT_INV (or its GCD form); 0 comes out as 0, without a test (row_value's kind 3: the kernels send an
   // INV0 item down the rows' path)
   static CAP_HD fe hint_inv0(const fe& src, const Exps& ex) {
     fl w[wc29::kWires];

@@ -15,6 +15,7 @@
 // rows hold an OUT row with q_ecc or a fifth root.
 // A level's items are its defining rows and its HINT items (kinds INV0, ISZERO, BITS behind the rows' three, INV0 first:
 // next to the other exponentiations): an entry of the level like a row, so the packed decode does not know of them.
+// k_fr_inverse: the field inversion alone, one element per lane (capgpu_fr_inverse_batch*).
 // Compiled in solve.hip, a translation unit of its own: the prover's kernels in plonk.hip keep the code they had.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -73,12 +74,14 @@ __device__ __forceinline__ uint32_t solve_item_ids(const SolveRowTables& t, cons
 // launch bound by the latency of one dependent chain pays for on every row.  Their item loop is the one from before hints,
 // kept to the letter, and the hint tables travel as the LAST kernel argument (SolveHints; unused there), so that those
 // instantiations are the code they were.
-template <bool HINTS>
+// INV: the form of the inversions of kinds OUT_INV and INV0 (solve29.hpp) - sv29::kInvFermat, the default, or sv29::kInvGcd
+// (capgpu_fr_set_inverse_form).  The form is a parameter of the row rule's struct alone: the kernels' text is one.
+template <bool HINTS, int INV = sv29::kInvFermat>
 __global__ __launch_bounds__(kSolveThreads) void k_solve_vars(const fe* __restrict__ given /*[count][num_given]*/, SolveRowTables t,
                                                          sv29::Exps ex, fe* vars_out /*[count][num_vars]*/,
                                                          unsigned long long* __restrict__ status /*[count]*/, SolveHints hp) {
-  using S = sv29::Solve<>;
-  using F = S::F;
+  using S = sv29::Solve<CAP_FL_SCHED, INV>;
+  using F = typename S::F;
   const size_t p = blockIdx.x;
   fe* vars = vars_out + p * t.num_vars;
   const fe* giv = given + p * t.num_given;
@@ -145,15 +148,15 @@ __global__ __launch_bounds__(kSolveThreads) void k_solve_vars(const fe* __restri
 // given + p given_stride and writes vars_out + p vars_stride (the launches of a call with several keys: one per key, over
 // that key's proofs, in rows of the call's largest lengths).  A slot at or beyond `count` loads and stores nothing; its
 // lanes still reach every barrier.  Row by row the arithmetic is k_solve_vars's: the output is the same words.
-template <int W, bool HINTS>
+template <int W, bool HINTS, int INV = sv29::kInvFermat>
 __global__ __launch_bounds__(kSolveThreads) void k_solve_vars_packed(const fe* __restrict__ given, size_t given_stride,
                                                                     SolveRowTables t, sv29::Exps ex, fe* vars_out,
                                                                     size_t vars_stride,
                                                                     unsigned long long* __restrict__ status /*per witness*/,
                                                                     const uint32_t* __restrict__ which, uint32_t count,
                                                                     SolveHints hp) {
-  using S = sv29::Solve<>;
-  using F = S::F;
+  using S = sv29::Solve<CAP_FL_SCHED, INV>;
+  using F = typename S::F;
 #pragma unroll 1
   for (uint32_t s = 0; s < (uint32_t)W; s++) {  // (slot by slot: a lane's stores stay next to its neighbours')
     const uint32_t entry = spk::slot_entry(blockIdx.x, s, W);
@@ -226,6 +229,25 @@ __global__ __launch_bounds__(kSolveThreads) void k_solve_vars_packed(const fe* _
     }
     __syncthreads();
   }
+}
+
+// capgpu_fr_inverse_batch*: out[i] = 1 / in[i] (0 for 0) over `count` field images (external Montgomery form; any 256-bit
+// word pattern is taken mod r), canonical results.  One element per lane; in and out may be the same array - a lane reads
+// its element before it writes it and touches no other - so neither is __restrict__.
+template <int INV>
+__global__ __launch_bounds__(kSolveThreads) void k_fr_inverse(const fe* in, fe* out, size_t count, sv29::Exps ex) {
+  using S = sv29::Solve<CAP_FL_SCHED, INV>;
+  using F = typename S::F;
+  const size_t i = (size_t)blockIdx.x * kSolveThreads + threadIdx.x;
+  if (i >= count) return;
+  const fl a = F::from_ext(in[i]);
+  fl y;
+  if constexpr (INV == sv29::kInvGcd) {
+    y = inv_gcd<FrP29, CAP_FL_SCHED>(a);
+  } else {
+    y = S::pow_words(a, [&](int w) { return ex.inv[w]; });
+  }
+  out[i] = F::to_ext(y);
 }
 
 }  // namespace pk

@@ -849,6 +849,51 @@ def plonk_solve_stats() -> dict:
     return {"launches": a.value, "witnesses": b.value, "packed_launches": c.value}
 
 
+INVERSE_FERMAT, INVERSE_GCD = 0, 1
+_INVERSE_FORMS = {"fermat": INVERSE_FERMAT, "gcd": INVERSE_GCD}
+
+
+def fr_set_inverse_form(form):
+    """capgpu_fr_set_inverse_form: the form of the Fr inversions in the solver's launches and the batch inverse calls -
+    'fermat' / INVERSE_FERMAT (x^(r - 2), the default) or 'gcd' / INVERSE_GCD (constant-time GCD in jumps of divsteps).
+    Same results either way.  Works before init()."""
+    check(load().capgpu_fr_set_inverse_form(ctypes.c_int(int(_INVERSE_FORMS.get(form, form)))))
+
+
+def fr_get_inverse_form() -> int:
+    f = ctypes.c_int(0)
+    check(load().capgpu_fr_get_inverse_form(ctypes.byref(f)))
+    return f.value
+
+
+def fr_inverse_batch(x, out: "DevBuf | None" = None, count: "int | None" = None):
+    """capgpu_fr_inverse_batch[_dev]: 1 / x element by element (0 for 0), canonical Montgomery words.  x: an (N, 4) uint64
+    array -> a new (N, 4) array; or a DevBuf of `count` elements (all of it when None) -> `out` (x itself when None: in
+    place), written by a launch on the context's stream - not waited for."""
+    L = load()
+    if isinstance(x, DevBuf):
+        n = x.nbytes // 32 if count is None else int(count)
+        dst = x if out is None else out
+        if n < 0 or x.nbytes < n * 32 or dst.nbytes < n * 32:
+            raise CapGpuError(-1, f"fr_inverse_batch: {n} elements need {n * 32} bytes in both buffers")
+        check(L.capgpu_fr_inverse_batch_dev(x.ptr, dst.ptr, ctypes.c_size_t(n)))
+        return dst
+    a = np.ascontiguousarray(x, dtype=np.uint64)
+    if a.size % 4:
+        raise CapGpuError(-1, "fr_inverse_batch: field elements are 4 uint64 words each")
+    res = np.zeros_like(a)
+    if a.size:
+        check(L.capgpu_fr_inverse_batch(_p(a.reshape(-1)), _p(res.reshape(-1)), ctypes.c_size_t(a.size // 4)))
+    return res
+
+
+def fr_inverse_stats() -> dict:
+    """launches holding an Fr inversion (solver and batch calls) by the form they ran in, since the library was loaded"""
+    a, b = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    check(load().capgpu_fr_inverse_stats(ctypes.byref(a), ctypes.byref(b)))
+    return {"fermat_launches": a.value, "gcd_launches": b.value}
+
+
 def _cached_num_vars(pk_handle: int) -> int:
     nv = _num_vars_of.get(pk_handle)
     if nv is None:

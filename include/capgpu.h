@@ -589,6 +589,39 @@ int capgpu_plonk_set_solve_pack(int w);
 int capgpu_plonk_get_solve_pack(int* w_out);
 int capgpu_plonk_solve_stats(uint64_t* launches_out, uint64_t* witnesses_out, uint64_t* packed_launches_out);
 
+/* ---- inversion in the scalar field Fr ----------------------------------------------------------------------------------
+ * The form of the Fr inversions the solver's launches run (its OUT rows with q_ecc and its INV0 hints) and of the batch
+ * calls below.  CAPGPU_INVERSE_FERMAT: x^(r - 2) bit by bit over the public exponent - what every launch ran before this
+ * setting existed, and the default.  CAPGPU_INVERSE_GCD: a constant-time extended binary GCD in 26 jumps of 29 divsteps
+ * (Bernstein-Yang; the count is the proven bound for 254-bit inputs), the same canonical result for every input, 0 for 0;
+ * like the power it has no branch, loop bound or address that depends on a value.  A fifth-root row is a 254-bit power by
+ * nature and keeps it in either form.  Replaces: nothing - the setting only selects which kernel instantiation
+ * capgpu_plonk_solve_vars[_dev] and capgpu_plonk_prove_given[_dev|_async] launch; the output of either is the same words,
+ * statuses included, and no other entry point changes an inversion with it.
+ * set: any form but the two is CAPGPU_ERR_INVALID_ARG.  get: form_out NULL is CAPGPU_ERR_INVALID_ARG.  The process default
+ * is CAPGPU_INVERSE_FERMAT, or what the environment variable CAPGPU_FR_INVERSE names ("fermat" or "gcd"; any other value
+ * counts as fermat).  Process-wide; read when a launch is issued - a switch between two calls on one key needs no new
+ * set-up; both calls work before capgpu_init. */
+#define CAPGPU_INVERSE_FERMAT 0
+#define CAPGPU_INVERSE_GCD 1
+int capgpu_fr_set_inverse_form(int form);
+int capgpu_fr_get_inverse_form(int* form_out);
+/* out[i] = in[i]^-1 mod r for `count` field elements, and 0 for 0.  Elements are the ABI's field images: 8 x 32-bit words
+ * (4 x uint64_t), Montgomery form as everywhere; an image that is not canonical is taken mod r; results are canonical.
+ * One kernel launch, one element per lane, 256 per workgroup, in the form set above.  in == out is allowed (no other
+ * overlap); count == 0 returns CAPGPU_OK and launches nothing; a NULL array with count > 0 is CAPGPU_ERR_INVALID_ARG.
+ * Replaces: a host loop over a CPU field library for a column of denominators or a caller's own hints - the ABI had no
+ * field inversion of any kind.
+ * capgpu_fr_inverse_batch: host arrays; staged through the context's scratch, returns when h_out is written.
+ * capgpu_fr_inverse_batch_dev: device arrays on the calling thread's context; the launch is enqueued on the context's
+ * stream (capgpu_set_stream is honoured) and the call returns without waiting for it - work enqueued on that stream
+ * afterwards sees d_out. */
+int capgpu_fr_inverse_batch(const void* h_in, void* h_out, size_t count);
+int capgpu_fr_inverse_batch_dev(const void* d_in, void* d_out, size_t count);
+/* Launches that hold an Fr inversion - the solver's and the batch calls' - by the form they ran in, since the library was
+ * loaded.  What shows that the setting selects a kernel.  Either pointer may be NULL; works before capgpu_init. */
+int capgpu_fr_inverse_stats(uint64_t* fermat_launches_out, uint64_t* gcd_launches_out);
+
 int capgpu_plonk_free_key(uint64_t pk_handle);
 /* Shape of a resident proving key: the sizes every prove call's arrays must have (wires: count * 5 * domain_size
  * field elements, pub_inputs: count * num_inputs, blinders: count * 13) and the SRS it commits with.  Any out
