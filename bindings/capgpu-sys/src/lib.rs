@@ -139,6 +139,23 @@ pub struct capgpu_solver_rules_info {
 pub const CAPGPU_SOLVER_LINEAR: u32 = 1;
 pub const CAPGPU_SOLVER_DERIVE_PUBLIC: u32 = 2;
 
+/// `capgpu_solve_form_info`: the form of the schedule a key's solver runs (`capgpu_plonk_key_set_solve_form`) and its
+/// figures (64 bytes); all zero: no solver.
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug, PartialEq, Eq)]
+pub struct capgpu_solve_form_info {
+    pub form: u64,
+    pub deferred_vars: u64,
+    pub frac_rows: u64,
+    pub flush_levels: u64,
+    pub flush_items: u64,
+    pub levels: u64,
+    pub inv_levels_direct: u64,
+    pub inv_levels_deferred: u64,
+}
+pub const CAPGPU_SOLVE_FORM_DIRECT: c_int = 0;
+pub const CAPGPU_SOLVE_FORM_DEFERRED: c_int = 1;
+
 /// `capgpu_solve_status`: the verdict of the witness solver for one witness (16 bytes).  `kind`: 0 solved, 1 the
 /// denominator of `row` - the lowest such row - is zero (its variable is 0).
 #[repr(C)]
@@ -310,6 +327,8 @@ extern "C" {
                                        num_targets: usize, flags: u32, info_out: *mut capgpu_solver_info,
                                        hint_info_out: *mut capgpu_hint_info) -> c_int;
     pub fn capgpu_plonk_key_solver_rules_info(pk_handle: u64, info_out: *mut capgpu_solver_rules_info) -> c_int;
+    pub fn capgpu_plonk_key_set_solve_form(pk_handle: u64, form: c_int, info_out: *mut capgpu_solve_form_info) -> c_int;
+    pub fn capgpu_plonk_key_solve_form_info(pk_handle: u64, info_out: *mut capgpu_solve_form_info) -> c_int;
     pub fn capgpu_plonk_pub_inputs(pk_handle: u64, count: c_int, vars: *const u64, pub_out: *mut u64) -> c_int;
     pub fn capgpu_plonk_pub_inputs_dev(pk_handle: u64, count: c_int, d_vars: *const c_void, d_pub_out: *mut c_void) -> c_int;
     pub fn capgpu_plonk_solve_vars(pk_handle: u64, count: c_int, given: *const u64, vars_out: *mut u64,
@@ -831,6 +850,19 @@ impl ProvingKey {
     pub fn solver_rules_info(&self) -> Result<capgpu_solver_rules_info> {
         let mut info = capgpu_solver_rules_info::default();
         check(unsafe { capgpu_plonk_key_solver_rules_info(self.handle, &mut info) })?;
+        Ok(info)
+    }
+    /// Re-derives the schedule of the solver the key holds in `form` (`CAPGPU_SOLVE_FORM_DIRECT`, what every set-up call
+    /// leaves, or `CAPGPU_SOLVE_FORM_DEFERRED`: a chain's denominators inverted together).  Same values, same statuses.
+    pub fn set_solve_form(&self, form: c_int) -> Result<capgpu_solve_form_info> {
+        let mut info = capgpu_solve_form_info::default();
+        check(unsafe { capgpu_plonk_key_set_solve_form(self.handle, form, &mut info) })?;
+        Ok(info)
+    }
+    /// The form the key's solver runs and its figures; all zero: no solver.
+    pub fn solve_form_info(&self) -> Result<capgpu_solve_form_info> {
+        let mut info = capgpu_solve_form_info::default();
+        check(unsafe { capgpu_plonk_key_solve_form_info(self.handle, &mut info) })?;
         Ok(info)
     }
     /// The public inputs of `vars.len() / num_vars` completed assignments (what `solve` returns, or a `prove_vars` witness

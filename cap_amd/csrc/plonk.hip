@@ -42,6 +42,7 @@
 #include "params.hpp"
 #include "plonk_kernels.hpp"
 #include "solve.hpp"
+#include "solve_defer.hpp"
 #include "tickets.hpp"
 #include "transcript_dev.hpp"
 #include "vars_kernels.hpp"
@@ -60,6 +61,13 @@ struct SolveSched {
   capgpu_hint_info hint_info{};  // all zero: no hints
   capgpu_solver_rules_info rules{};  // capgpu_plonk_key_set_solver's flags and what they admitted
   int auto_pack = 1;  // the schedule's term of the automatic witnesses-per-workgroup rule (spk::auto_pack)
+  // The form the launches run (capgpu_plonk_key_set_solve_form).  Every set-up call makes a DIRECT schedule; the host copies
+  // of the table and of the selectors' zero flags stay with it, so that a change of form is a host pass.
+  int form = CAPGPU_SOLVE_FORM_DIRECT;
+  std::vector<uint32_t> table;    // [5][n]
+  std::vector<uint8_t> sel_zero;  // [13][n]
+  sd::Sched defer;                // form == CAPGPU_SOLVE_FORM_DEFERRED: the schedule the kernels read (solve_defer.hpp)
+  std::vector<fe> defer_konst;    // ... and its items' constants
 };
 
 struct ProvingKey {
@@ -1689,7 +1697,14 @@ int solve_tables(const ProvingKey& K, SolveTables* tab, std::shared_ptr<const So
       K.solve_dev = nullptr;
       K.solve_dev_uid = 0;
     }
-    const size_t nrows = S.plan.rows.size();
+    // (the DEFERRED form: the deferred schedule's items, constants and levels take the direct ones' places)
+    const bool defer = S.form == CAPGPU_SOLVE_FORM_DEFERRED;
+    const std::vector<sp::Row>& h_rows = defer ? S.defer.rows : S.plan.rows;
+    const std::vector<fe>& h_konst = defer ? S.defer_konst : S.konst;
+    const std::vector<uint32_t>& h_off = defer ? S.defer.level_off : S.plan.level_off;
+    const size_t nrows = h_rows.size();
+    int32_t* dslot = nullptr;
+    uint32_t* flush_vars = nullptr;
     int32_t* slot = nullptr;
     sp::Row* rows = nullptr;
     fe* konst = nullptr;
@@ -1702,10 +1717,14 @@ int solve_tables(const ProvingKey& K, SolveTables* tab, std::shared_ptr<const So
       slot = k.take<int32_t>(S.plan.slot.size());
       rows = k.take<sp::Row>(nrows ? nrows : 1);
       konst = k.take<fe>(nrows ? nrows : 1);
-      off = k.take<uint32_t>(S.plan.level_off.size());
+      off = k.take<uint32_t>(h_off.size());
       if (nhints) {
         hints = k.take<sp::Hint>(nhints);
         targets = k.take<uint32_t>(ntargets);
+      }
+      if (defer) {
+        dslot = k.take<int32_t>(S.defer.dslot.size() ? S.defer.dslot.size() : 1);
+        flush_vars = k.take<uint32_t>(S.defer.flush_vars.size() ? S.defer.flush_vars.size() : 1);
       }
       return k.off + 256;
     };
@@ -1714,10 +1733,17 @@ int solve_tables(const ProvingKey& K, SolveTables* tab, std::shared_ptr<const So
     (void)carve_tables(own.p);
     CAP_HIP(hipMemcpy(slot, S.plan.slot.data(), sizeof(int32_t) * S.plan.slot.size(), hipMemcpyHostToDevice));
     if (nrows) {
-      CAP_HIP(hipMemcpy(rows, S.plan.rows.data(), sizeof(sp::Row) * nrows, hipMemcpyHostToDevice));
-      CAP_HIP(hipMemcpy(konst, S.konst.data(), sizeof(fe) * nrows, hipMemcpyHostToDevice));
+      CAP_HIP(hipMemcpy(rows, h_rows.data(), sizeof(sp::Row) * nrows, hipMemcpyHostToDevice));
+      CAP_HIP(hipMemcpy(konst, h_konst.data(), sizeof(fe) * nrows, hipMemcpyHostToDevice));
     }
-    CAP_HIP(hipMemcpy(off, S.plan.level_off.data(), sizeof(uint32_t) * S.plan.level_off.size(), hipMemcpyHostToDevice));
+    CAP_HIP(hipMemcpy(off, h_off.data(), sizeof(uint32_t) * h_off.size(), hipMemcpyHostToDevice));
+    if (defer) {
+      if (!S.defer.dslot.empty())
+        CAP_HIP(hipMemcpy(dslot, S.defer.dslot.data(), sizeof(int32_t) * S.defer.dslot.size(), hipMemcpyHostToDevice));
+      if (!S.defer.flush_vars.empty())
+        CAP_HIP(hipMemcpy(flush_vars, S.defer.flush_vars.data(), sizeof(uint32_t) * S.defer.flush_vars.size(),
+                          hipMemcpyHostToDevice));
+    }
     if (nhints) {
       CAP_HIP(hipMemcpy(hints, S.plan.hints.data(), sizeof(sp::Hint) * nhints, hipMemcpyHostToDevice));
       CAP_HIP(hipMemcpy(targets, S.plan.targets.data(), sizeof(uint32_t) * ntargets, hipMemcpyHostToDevice));
@@ -1729,9 +1755,13 @@ int solve_tables(const ProvingKey& K, SolveTables* tab, std::shared_ptr<const So
     t.level_off = off;
     t.hp.hints = hints;
     t.hp.targets = targets;
-    t.levels = (uint32_t)S.plan.levels;
+    t.levels = (uint32_t)(defer ? S.defer.levels : S.plan.levels);
     t.num_given = S.plan.num_given;
     t.lin = S.plan.lin_rows != 0;
+    t.defer = defer;
+    t.dslot = dslot;
+    t.flush_vars = flush_vars;
+    t.side_slots = defer ? (size_t)S.defer.slots : 0;
     K.solve_tab = t;
     K.solve_dev = own.p;
     K.solve_dev_uid = S.uid;
@@ -1772,12 +1802,13 @@ int solve_run(uint64_t pk_handle, uint32_t count, const uint64_t* h_given, uint6
   hipStream_t s = c.stream;
   const size_t given_elems = (size_t)count * tab.num_given, var_elems = (size_t)count * tab.num_vars;
   unsigned long long* d_st = nullptr;
-  fe *g = nullptr, *v = nullptr;
+  fe *g = nullptr, *v = nullptr, *side = nullptr;
   auto carve_call = [&](void* at) {
     Carver k(at);
     d_st = k.take<unsigned long long>(count);
     if (h_given) g = k.take<fe>(given_elems ? given_elems : 1);
     if (h_vars) v = k.take<fe>(var_elems);
+    if (tab.defer) side = k.take<fe>(tab.side_elems(count) + 1);  // (a key in the DEFERRED form: its denominators)
     return k.off + 256;
   };
   if ((rc = scratch_reserve(c.stage_b, carve_call(nullptr)))) return rc;
@@ -1789,7 +1820,8 @@ int solve_run(uint64_t pk_handle, uint32_t count, const uint64_t* h_given, uint6
   if (h_vars) d_vars = v;
   CAP_HIP(hipMemsetAsync(d_st, 0xff, sizeof(unsigned long long) * count, s));
   solve_launch_packed(s, spk::pack_for(solve_pack_setting(), hold->auto_pack, count),
-                      SolveLaunch{count, (const fe*)d_given, tab.num_given, (fe*)d_vars, tab.num_vars, d_st, nullptr}, tab, *ex);
+                      SolveLaunch{count, (const fe*)d_given, tab.num_given, (fe*)d_vars, tab.num_vars, d_st, nullptr, side}, tab,
+                      *ex);
   std::vector<unsigned long long> h_st(count);
   CAP_HIP(hipMemcpyAsync(h_st.data(), d_st, sizeof(unsigned long long) * count, hipMemcpyDeviceToHost, s));
   if (h_vars) CAP_HIP(hipMemcpyAsync(h_vars, d_vars, sizeof(fe) * var_elems, hipMemcpyDeviceToHost, s));
@@ -1903,6 +1935,8 @@ int key_set_given(const char* who, uint64_t pk_handle, const uint32_t* given_var
     S->hint_info = capgpu_hint_info{P.hints.size(), P.num_hinted, P.bits_hints, P.inv_hints, P.iszero_hints, P.hint_items};
     S->rules = capgpu_solver_rules_info{P.flags, P.lin_rows, P.derived_inputs, 0};
     S->auto_pack = spk::auto_pack(spk::median_level_width(P.level_off.data(), P.levels), kSolveThreads);
+    S->table = std::move(table);
+    S->sel_zero = std::move(sel_zero);
   }
   // the key and the replicas other devices hold take the schedule; each uploads its tables on its next solve
   for (auto& cp : R.ctxs) {
@@ -1958,6 +1992,113 @@ int capgpu_plonk_key_solver_rules_info(uint64_t pk_handle, capgpu_solver_rules_i
   std::lock_guard<std::mutex> klk(K->chk_mu);
   memset(info_out, 0, sizeof *info_out);
   if (K->solve && K->wire_vars) *info_out = K->solve->rules;
+  return CAPGPU_OK;
+}
+
+// ---- the form of the solver's schedule (solve_defer.hpp) ---------------------------------------------------------------
+static_assert(sizeof(capgpu_solve_form_info) == 64, "capgpu_solve_form_info");
+namespace {
+// the figures of S in the form it holds; D: the deferred schedule of S's plan (S.defer, or one derived for the figures)
+capgpu_solve_form_info solve_form_figures(const SolveSched& S, const sd::Sched& D) {
+  if (S.form == CAPGPU_SOLVE_FORM_DEFERRED)
+    return capgpu_solve_form_info{CAPGPU_SOLVE_FORM_DEFERRED, D.deferred_vars, D.frac_rows, D.flush_levels, D.flush_items,
+                                  D.levels, D.inv_levels_direct, D.inv_levels_deferred};
+  return capgpu_solve_form_info{CAPGPU_SOLVE_FORM_DIRECT, 0, 0, 0, 0, S.plan.levels, D.inv_levels_direct, D.inv_levels_deferred};
+}
+}  // namespace
+
+int capgpu_plonk_key_set_solve_form(uint64_t pk_handle, int form, capgpu_solve_form_info* info_out) {
+  static const char who[] = "capgpu_plonk_key_set_solve_form";
+  if (form != CAPGPU_SOLVE_FORM_DIRECT && form != CAPGPU_SOLVE_FORM_DEFERRED) {
+    set_error("%s: bad argument (form %d is neither CAPGPU_SOLVE_FORM_DIRECT (0) nor CAPGPU_SOLVE_FORM_DEFERRED (1)); the key is "
+              "unchanged",
+              who, form);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  if (!pk_handle) {
+    set_error("%s: bad argument (pk_handle is 0)", who);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  CAP_CHECK_INIT();
+  std::shared_ptr<ProvingKey> K;
+  int rc = home_key(pk_handle, &K);
+  if (rc) return rc;
+  std::shared_ptr<const SolveSched> old;
+  {
+    std::lock_guard<std::mutex> klk(K->chk_mu);
+    if (K->solve && K->wire_vars) old = K->solve;
+  }
+  if (!old) {
+    set_error("%s: the key has no solver (capgpu_plonk_key_set_given gives it one); the key is unchanged", who);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  // a new schedule object with a new uid: every holder uploads its tables again on its next solve
+  auto S = std::make_shared<SolveSched>(*old);
+  S->form = form;
+  S->defer = sd::Sched();
+  S->defer_konst.clear();
+  const sp::Plan& P = S->plan;
+  if (form == CAPGPU_SOLVE_FORM_DEFERRED) {
+    sd::defer_plan(P, K->n, S->table.data(), S->sel_zero.data(), &S->defer);
+    const sd::Sched& D = S->defer;
+    S->defer_konst.assign(D.rows.size(), Fr29::pack(Fr29::zero()));
+    for (size_t k = 0; k < D.rows.size(); k++)
+      if (D.src[k] != sd::kNoSrc) S->defer_konst[k] = S->konst[D.src[k]];
+    S->auto_pack = spk::auto_pack(spk::median_level_width(D.level_off.data(), D.levels), kSolveThreads);
+  } else {
+    S->auto_pack = spk::auto_pack(spk::median_level_width(P.level_off.data(), P.levels), kSolveThreads);
+  }
+  static std::atomic<uint64_t> next_uid{1ull << 40};  // (apart from the set-up calls' counter)
+  S->uid = next_uid.fetch_add(1);
+  Runtime& R = rt();
+  for (auto& cp : R.ctxs) {
+    Context& c = *cp;
+    ScopedCtx sc(c);
+    Entry lk(c);
+    auto it = c.keys.find(pk_handle);
+    if (it == c.keys.end()) continue;
+    std::lock_guard<std::mutex> klk(it->second->chk_mu);
+    if (it->second->solve) it->second->solve = S;
+  }
+  {
+    std::lock_guard<std::mutex> klk(K->chk_mu);
+    K->solve = S;
+  }
+  if (info_out) {
+    if (form == CAPGPU_SOLVE_FORM_DEFERRED) {
+      *info_out = solve_form_figures(*S, S->defer);
+    } else {
+      sd::Sched D;
+      sd::defer_plan(P, K->n, S->table.data(), S->sel_zero.data(), &D);
+      *info_out = solve_form_figures(*S, D);
+    }
+  }
+  return CAPGPU_OK;
+}
+
+int capgpu_plonk_key_solve_form_info(uint64_t pk_handle, capgpu_solve_form_info* info_out) {
+  if (!info_out || !pk_handle) {
+    set_error("capgpu_plonk_key_solve_form_info: bad argument (%s)", info_out ? "pk_handle is 0" : "info_out is NULL");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  CAP_CHECK_INIT();
+  std::shared_ptr<ProvingKey> K;
+  int rc = home_key(pk_handle, &K);
+  if (rc) return rc;
+  std::shared_ptr<const SolveSched> S;
+  {
+    std::lock_guard<std::mutex> klk(K->chk_mu);
+    if (K->solve && K->wire_vars) S = K->solve;
+  }
+  memset(info_out, 0, sizeof *info_out);
+  if (!S) return CAPGPU_OK;
+  if (S->form == CAPGPU_SOLVE_FORM_DEFERRED) {
+    *info_out = solve_form_figures(*S, S->defer);
+  } else {
+    sd::Sched D;  // (the figures the other form would have: a host pass over the plan)
+    sd::defer_plan(S->plan, K->n, S->table.data(), S->sel_zero.data(), &D);
+    *info_out = solve_form_figures(*S, D);
+  }
   return CAPGPU_OK;
 }
 
@@ -2357,13 +2498,13 @@ static const char kProveGiven[] = "capgpu_plonk_prove_given";
 // words, its witness lists (calls with several keys), - host-resident values only - the staged given rows and - the _io
 // calls, pub_stride > 0 - the rows of computed public inputs.
 struct GivenStage {
-  fe *cols = nullptr, *vars = nullptr, *given = nullptr, *pub = nullptr;
+  fe *cols = nullptr, *vars = nullptr, *given = nullptr, *pub = nullptr, *side = nullptr;
   unsigned long long* status = nullptr;
   uint32_t* which = nullptr;
   size_t bytes = 0;
 };
 static GivenStage given_carve(void* base, size_t cnt, size_t n, size_t var_stride, size_t given_stride, bool host,
-                              size_t pub_stride = 0) {
+                              size_t pub_stride = 0, size_t side_elems = 0) {
   GivenStage g;
   Carver k(base);
   g.cols = k.take<fe>(cnt * NW * n + cnt * var_stride);  // (one piece: VarsIn of a staged call starts where the columns end)
@@ -2372,6 +2513,7 @@ static GivenStage given_carve(void* base, size_t cnt, size_t n, size_t var_strid
   g.which = k.take<uint32_t>(cnt);
   if (host) g.given = k.take<fe>(cnt * given_stride + 1);
   if (pub_stride) g.pub = k.take<fe>(cnt * pub_stride);
+  if (side_elems) g.side = k.take<fe>(side_elems);  // (keys in the DEFERRED form: the solver's denominators)
   g.bytes = k.off + 256;
   return g;
 }
@@ -2435,10 +2577,14 @@ static int given_part(const ProveCall& b, int first, int cnt) {
   }
   const size_t n = keys.ptr[0]->n;
   const bool host = !b.given_dev;
-  if ((rc = scratch_reserve(c.stage_b, given_carve(nullptr, (size_t)cnt, n, b.stride, b.given_stride, host, io_stride).bytes)))
+  // (the launches of one part run one behind the other on one stream: the side buffer of the largest serves them all)
+  size_t side_elems = 0;
+  for (const KeyRun& r : runs) side_elems = std::max(side_elems, r.tab.side_elems(r.which.size()));
+  if ((rc = scratch_reserve(c.stage_b,
+                            given_carve(nullptr, (size_t)cnt, n, b.stride, b.given_stride, host, io_stride, side_elems).bytes)))
     return rc;
   if ((rc = pinned_reserve(c, given_pinned_bytes((uint32_t)cnt)))) return rc;
-  const GivenStage g = given_carve(c.stage_b.p, (size_t)cnt, n, b.stride, b.given_stride, host, io_stride);
+  const GivenStage g = given_carve(c.stage_b.p, (size_t)cnt, n, b.stride, b.given_stride, host, io_stride, side_elems);
   unsigned long long* const h_st = (unsigned long long*)((char*)c.pin_host + given_pinned_offset((uint32_t)cnt));
   hipStream_t s = c.stream;
   const fe* d_given = (const fe*)b.given + (size_t)first * b.given_stride;
@@ -2464,7 +2610,7 @@ static int given_part(const ProveCall& b, int first, int cnt) {
     }
     const uint32_t k = (uint32_t)r.which.size();
     solve_launch_packed(s, spk::pack_for(setting, r.hold->auto_pack, k),
-                        SolveLaunch{k, d_given, b.given_stride, g.vars, b.stride, g.status, d_which}, r.tab, *ex);
+                        SolveLaunch{k, d_given, b.given_stride, g.vars, b.stride, g.status, d_which, g.side}, r.tab, *ex);
   }
   CAP_HIP(hipMemcpyAsync(h_st, g.status, sizeof(unsigned long long) * cnt, hipMemcpyDeviceToHost, s));
   if (io_stride) {
@@ -3094,7 +3240,8 @@ static int reserve_impl(uint64_t pk_handle, int count, int input_form, int slot,
       if ((rc = key_check_tables(*K)) || (rc = solve_tables(*K, &tab, &hold))) return rc;
       // (a key whose solver derives its public inputs: the rows an _io call gathers them into, too)
       const size_t io_stride = hold->rules.flags & CAPGPU_SOLVER_DERIVE_PUBLIC ? K->num_inputs : 0;
-      nd.stage_b = std::max(nd.stage_b, given_carve(nullptr, (size_t)count, K->n, K->num_vars, tab.num_given, true, io_stride).bytes);
+      nd.stage_b = std::max(nd.stage_b, given_carve(nullptr, (size_t)count, K->n, K->num_vars, tab.num_given, true, io_stride,
+                                                         tab.side_elems((size_t)count)).bytes);
       nd.pinned = std::max(nd.pinned, given_pinned_bytes((uint32_t)count));
     }
     if ((rc = scratch_reserve(c.stage_b, nd.stage_b))) return rc;

@@ -66,6 +66,12 @@ void solve_launch(hipStream_t s, uint32_t count, const fe* d_given, const SolveT
 
 void solve_launch_packed(hipStream_t s, int W, const SolveLaunch& a, const SolveTables& t, const sv29::Exps& ex) {
   if (!a.count) return;
+  if (t.defer) {  // a key in the DEFERRED form: the kernels of solve_defer.hip, counted like any launch
+    const int form = inverse_form_setting();
+    count_launch(a.count, solve_launch_defer(s, W, a, t, ex, form));
+    count_inverse(form);
+    return;
+  }
   if (W <= 1 && !a.d_which && a.given_stride == t.num_given && a.vars_stride == t.num_vars)
     return solve_launch(s, a.count, a.d_given, t, ex, a.d_vars, a.d_status);
   const int form = inverse_form_setting();

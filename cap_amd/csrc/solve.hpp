@@ -36,6 +36,13 @@ struct SolveRowTables {
 struct SolveTables : SolveRowTables {
   SolveHints hp;
   bool lin = false;  // the schedule holds LIN rows: the launches run the kernels that carry that rule (solve_kernels.hpp)
+  // the DEFERRED form (capgpu_plonk_key_set_solve_form; solve_defer.hpp): the tables above are the deferred schedule's, the
+  // launches run solve_defer.hip's kernels and need SolveLaunch::d_side
+  bool defer = false;
+  const int32_t* dslot = nullptr;        // [num_vars]: deferred slot, -1: never deferred
+  const uint32_t* flush_vars = nullptr;  // the flush items' variables
+  size_t side_slots = 0;                 // deferred slots per witness: a launch of `count` needs side_elems(count) images
+  size_t side_elems(size_t count) const { return defer ? count * 2 * side_slots : 0; }
 };
 
 // k_solve_vars for `count` witnesses on stream s (through launch(): timed by the profiler, launch errors latched)
@@ -53,8 +60,12 @@ struct SolveLaunch {
   size_t vars_stride;
   unsigned long long* d_status;
   const uint32_t* d_which;
+  fe* d_side = nullptr;  // a key in the DEFERRED form: SolveTables::side_elems(count) images of scratch, by launch entry
 };
 void solve_launch_packed(hipStream_t s, int W, const SolveLaunch& a, const SolveTables& t, const sv29::Exps& ex);
+// The same launch for a schedule in the DEFERRED form (solve_defer.hip; solve_launch_packed hands it on and counts it):
+// returns the W that ran.  form: the process's inverse form.
+int solve_launch_defer(hipStream_t s, int W, const SolveLaunch& a, const SolveTables& t, const sv29::Exps& ex, int form);
 // The process's inverse form (capgpu_fr_set_inverse_form; sv29::kInvFermat or sv29::kInvGcd): both launches above read it
 // and run the instantiation of that form - the caller does not pass it.
 int inverse_form_setting();

@@ -840,6 +840,34 @@ def plonk_key_solver_rules_info(pk_handle: int) -> SolverRulesInfo:
     return info
 
 
+SOLVE_FORM_DIRECT, SOLVE_FORM_DEFERRED = 0, 1  # CAPGPU_SOLVE_FORM_*
+
+
+class SolveFormInfo(ctypes.Structure):
+    """capgpu_solve_form_info: the form of the schedule a key's solver runs and its figures; all zero: no solver."""
+    _fields_ = [("form", ctypes.c_uint64), ("deferred_vars", ctypes.c_uint64), ("frac_rows", ctypes.c_uint64),
+                ("flush_levels", ctypes.c_uint64), ("flush_items", ctypes.c_uint64), ("levels", ctypes.c_uint64),
+                ("inv_levels_direct", ctypes.c_uint64), ("inv_levels_deferred", ctypes.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+def plonk_key_set_solve_form(pk_handle: int, form: int) -> SolveFormInfo:
+    """capgpu_plonk_key_set_solve_form: re-derives the schedule of the solver the key holds in `form` - SOLVE_FORM_DIRECT,
+    what every set-up call leaves, or SOLVE_FORM_DEFERRED, which carries the variables of OUT rows with q_ecc as pairs
+    (numerator, denominator) and inverts a chain's denominators together.  Same vars_out, same statuses."""
+    info = SolveFormInfo()
+    check(load().capgpu_plonk_key_set_solve_form(ctypes.c_uint64(pk_handle), ctypes.c_int(int(form)), ctypes.byref(info)))
+    return info
+
+
+def plonk_key_solve_form_info(pk_handle: int) -> SolveFormInfo:
+    info = SolveFormInfo()
+    check(load().capgpu_plonk_key_solve_form_info(ctypes.c_uint64(pk_handle), ctypes.byref(info)))
+    return info
+
+
 def plonk_pub_inputs(pk_handle: int, vars_, count: int = 1, out: "DevBuf | None" = None):
     """capgpu_plonk_pub_inputs[_dev]: the public inputs of `count` completed assignments - for every row below num_inputs
     the value that makes the row hold.  vars_: (count, num_vars, 4) Montgomery words -> a (count, num_inputs, 4) array; or a

@@ -604,6 +604,53 @@ int capgpu_plonk_key_set_solver(uint64_t pk_handle, const uint32_t* given_vars, 
                                 capgpu_solver_info* info_out, capgpu_hint_info* hint_info_out);
 /* the figures of the flags; all zero: the key has no solver (or one set with flags == 0 on a circuit that needs none) */
 int capgpu_plonk_key_solver_rules_info(uint64_t pk_handle, capgpu_solver_rules_info* info_out);
+/* THE FORM OF THE SCHEDULE, OPT-IN PER KEY.  Every set-up call above leaves the key in the DIRECT form: the schedule
+ * described so far, in which every OUT row with q_ecc != 0 inverts its own denominator - in a chain of Edwards additions
+ * one inversion behind the other.  The DEFERRED form carries the variable of such a row as a pair (numerator, denominator)
+ * and inverts a whole chain's denominators together when something needs a plain value.  It gives the same words in
+ * vars_out and the same status for every witness.  The rule, over the direct schedule's levels in ascending order with a
+ * set PENDING of deferred variables, empty at first:
+ *   - a row is FRAC-capable if it is an OUT row and every cell i < 4 that holds a pending variable has q_hash_i = 0.  An
+ *     OUT row with q_ecc != 0 that is FRAC-capable defines a deferred variable, whatever its inputs are; so does an OUT row
+ *     without q_ecc that has a pending input.  The variable joins PENDING behind its level.  Any other OUT row without
+ *     q_ecc stays the direct item.
+ *   - ROOT5 and LIN rows, an OUT row with a pending variable on a cell with q_hash_i != 0, and every hint item whose
+ *     source is pending need plain values: if a level holds such an item, a FLUSH LEVEL goes in front of it that resolves
+ *     ALL of PENDING, which is then empty.  Behind the last level a final flush resolves what is left.
+ *   - with cell i holding (N_i, D_i), D_i = 1 for a plain variable, D = D0 D1 D2 D3, E_i = the product of the other three,
+ *     P = N0 N1 N2 N3 and
+ *       R' = q_c D + sum q_lc_i N_i E_i + q_mul0 N0 N1 D2 D3 + q_mul1 N2 N3 D0 D1 + sum over plain i of q_hash_i N_i^5 D
+ *     an OUT row without q_ecc gives (R' / q_o, D) and one with q_ecc (R', q_o D - q_ecc P).  If that denominator is
+ *     0 mod r the row enters its number into the status word as in the direct form and its pair becomes (0, 1).
+ *   - a flush item resolves up to 32 pairs, v = N / D, with ONE inversion (prefix products, one inverse, walk back), in
+ *     the process's inverse form (capgpu_fr_set_inverse_form).
+ * The denominators live in a side buffer of the context's scratch, 64 bytes per witness and deferred slot (the largest
+ * PENDING of the schedule); capgpu_scratch_stats counts it and capgpu_plonk_reserve_given sizes it.  TIMING above holds for
+ * this form: which cells are pending and how many pairs an item resolves are properties of the circuit, a cell's
+ * denominator is selected by the schedule's mask, and the one data-dependent step is still the zero test of a row's own
+ * denominator.
+ * capgpu_solver_info, capgpu_hint_info and capgpu_solver_rules_info keep reporting the direct schedule. */
+#define CAPGPU_SOLVE_FORM_DIRECT 0
+#define CAPGPU_SOLVE_FORM_DEFERRED 1
+typedef struct capgpu_solve_form_info {
+  uint64_t form;                /* CAPGPU_SOLVE_FORM_* */
+  uint64_t deferred_vars;       /* variables carried as a pair (0 in the direct form, like the next three) */
+  uint64_t frac_rows;           /* rows evaluated on pairs */
+  uint64_t flush_levels;
+  uint64_t flush_items;
+  uint64_t levels;              /* levels of the schedule the key runs, flush levels included */
+  uint64_t inv_levels_direct;   /* levels of the direct schedule that hold an OUT row with q_ecc or an INV0 item */
+  uint64_t inv_levels_deferred; /* flush levels + levels that hold an INV0 item */
+} capgpu_solve_form_info; /* 64 bytes */
+/* Re-derives the key's schedule in `form` from the solver the key holds (a host pass; no device work).  A key without a
+ * solver and an unknown form are CAPGPU_ERR_INVALID_ARG, the key unchanged.  capgpu_plonk_key_set_given, _set_given_hints,
+ * _set_solver and capgpu_plonk_key_set_vars leave the key in the DIRECT form.  Everything behind the set-up -
+ * capgpu_plonk_solve_vars[_dev], capgpu_plonk_prove_given[_dev|_async], capgpu_plonk_prove_given_io*,
+ * capgpu_plonk_reserve_given, capgpu_plonk_set_solve_pack, capgpu_plonk_solve_stats - uses the form the key holds.
+ * info_out may be NULL.  Not to be called while other calls use the key. */
+int capgpu_plonk_key_set_solve_form(uint64_t pk_handle, int form, capgpu_solve_form_info* info_out);
+/* the figures of the form the key holds (the last three for either form); all zero: the key has no solver */
+int capgpu_plonk_key_solve_form_info(uint64_t pk_handle, capgpu_solve_form_info* info_out);
 /* The public inputs of `count` completed assignments (CAPGPU_INPUT_VARS witnesses, count x num_vars): pub[p][j] for
  * j < num_inputs is the value that makes row j hold - the negative of the gate at PI = 0,
  *   q_o w4 - q_ecc w0 w1 w2 w3 w4 - rest      (rest as under OUT above)

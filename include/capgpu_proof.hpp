@@ -508,6 +508,22 @@ Result<std::vector<ProveEachEntry>> prove_each(Rng& rng, const std::vector<const
   return out;
 }
 
+// The form of the schedule a key's solver runs (capgpu_plonk_key_set_solve_form): CAPGPU_SOLVE_FORM_DIRECT, what every
+// set-up call leaves, or CAPGPU_SOLVE_FORM_DEFERRED, which inverts the denominators of a chain of additions together.  Either
+// form gives prove_given the same assignments and the same proofs.  The key needs a solver.
+inline Result<capgpu_solve_form_info> set_solve_form(const ProvingKey& pk, int form) {
+  capgpu_solve_form_info info{};
+  int rc = capgpu_plonk_key_set_solve_form(pk.handle(), form, &info);
+  if (rc != CAPGPU_OK) return detail::map_error(rc, "set_solve_form");
+  return info;
+}
+inline Result<capgpu_solve_form_info> solve_form_info(const ProvingKey& pk) {
+  capgpu_solve_form_info info{};
+  int rc = capgpu_plonk_key_solve_form_info(pk.handle(), &info);
+  if (rc != CAPGPU_OK) return detail::map_error(rc, "solve_form_info");
+  return info;
+}
+
 // The values one circuit is given, for prove_given: `given` in the order of the key's given list (Montgomery words,
 // capgpu_plonk_key_set_given), pub_inputs as in an Assignment.
 struct GivenValues {
