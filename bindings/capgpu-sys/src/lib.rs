@@ -274,6 +274,8 @@ extern "C" {
     pub fn capgpu_msm_shard_stats(scalar_bytes_out: *mut u64, partial_bytes_out: *mut u64, calls_out: *mut u64,
                                   replications_out: *mut u64) -> c_int;
     pub fn capgpu_msm_plan(srs_handle: u64, n: usize, count: c_int, buf: *mut c_char, cap: usize) -> c_int;
+    pub fn capgpu_msm_tail_plan(c: c_int, n_sub: usize, sub_msms: c_int, has_parts: c_int, buf: *mut c_char,
+                                cap: usize) -> c_int;
     // ---- one-shot MSM over caller points (no handle, no table)
     pub fn capgpu_msm_g1_var(bases: *const c_void, stride_bytes: usize, coords_montgomery: c_int, scalars: *const u64,
                              n: usize, out_xyz: *mut u64) -> c_int;

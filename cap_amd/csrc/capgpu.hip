@@ -521,6 +521,16 @@ fe fe_from_u64x4(const uint64_t v[4]) {
 }
 
 
+// what a failed msm_precompute / lagrange_build becomes at the boundary: windows the tables cannot hold (CAPGPU_MSM_C
+// below 9) are the caller's argument, everything else is a HIP error
+int msm_table_fail(int rc, const char* what) {
+  if (rc != kMsmErrWindows) return hip_fail((hipError_t)rc, what);
+  const char* e = getenv("CAPGPU_MSM_C");
+  set_error("capgpu: CAPGPU_MSM_C=%s means more than 31 windows per scalar, a table holds 31 at most (window bits 9..16) [%s]",
+            e ? e : "?", what);
+  return CAPGPU_ERR_INVALID_ARG;
+}
+
 // a new SRS entry on the current context: window tables of `n` device-resident bases
 int make_srs_entry(g1_affine* d_bases, size_t n, size_t range_lo, std::shared_ptr<SrsEntry>* out) {
   Context& c = ctx();
@@ -529,7 +539,7 @@ int make_srs_entry(g1_affine* d_bases, size_t n, size_t range_lo, std::shared_pt
   e->range_lo = range_lo;
   uint32_t cw = msm_choose_window(n);
   int rc = msm_precompute(&e->bases, d_bases, n, cw, c.stream);
-  if (rc) return hip_fail((hipError_t)rc, "msm_precompute");
+  if (rc) return msm_table_fail(rc, "msm_precompute");
   CAP_HIP(hipStreamSynchronize(c.stream));
   // msm_precompute latches a failed launch of its table kernels (launch.hpp); a handle whose window tables were never
   // written must not be published: the entry is dropped here (its destructor frees the tables)
@@ -687,9 +697,9 @@ int find_lagrange(uint64_t h, uint32_t log_n, const MsmBases** out) {
     std::unique_ptr<MsmBases> L(new MsmBases);
     rc = lagrange_build(*B, log_n, L.get(), c.stream);
     if (rc) {
-      e->lagrange_failed.insert(log_n);
+      if (rc != kMsmErrWindows) e->lagrange_failed.insert(log_n);  // (a refused window is not remembered: the switch may go)
       msm_free_bases(L.get());
-      return hip_fail((hipError_t)rc, "lagrange_build");
+      return msm_table_fail(rc, "lagrange_build");
     }
     if ((rc = take_launch_error())) {
       e->lagrange_failed.insert(log_n);
@@ -2026,6 +2036,21 @@ int capgpu_msm_var_plan(size_t n, int count, char* buf, size_t cap) {
     return CAPGPU_ERR_INVALID_ARG;
   }
   msm_var_describe(msm_var_plan(n, n, (uint32_t)count), buf, cap);  // host arithmetic only: works without a device
+  return CAPGPU_OK;
+}
+
+int capgpu_msm_tail_plan(int c, size_t n_sub, int sub_msms, int has_parts, char* buf, size_t cap) {
+  if (!buf || cap == 0 || n_sub == 0 || sub_msms < 1 || c < 0) {
+    set_error("capgpu_msm_tail_plan: bad argument (null buffer, no points or no MSMs)");
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  const int rc = msm_tail_describe((uint32_t)c, n_sub, (uint32_t)sub_msms, has_parts != 0, buf, cap);  // no device needed
+  if (rc) {
+    set_error(rc == 2 ? "capgpu_msm_tail_plan: the buffer of %zu bytes is too short"
+                      : "capgpu_msm_tail_plan: no batched launch of this shape (window bits 9..16, sizes within one slice)",
+              cap);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
   return CAPGPU_OK;
 }
 

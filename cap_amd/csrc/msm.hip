@@ -1867,6 +1867,7 @@ size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 struct WsLayout {
   size_t counts, offsets, sorted, buckets, partial, item_off, item_base, totals, item_bucket, item_sub, item_pts, max_items,
       table, off2, tloc, chunks, nblk, seg_tot, part_pts, total;
+  size_t partial_points;  // points reserved at `partial`, all entries
 };
 
 // which table / sort a launch uses
@@ -2201,6 +2202,7 @@ WsLayout ws_layout(uint32_t c, uint32_t windows, size_t n, uint32_t sb, uint32_t
     const size_t npart = reduce_partial_points(c, half, nseg, sb);
     L.buckets = o; o = align_up(o + sizeof(g1_xyzz) * half * sb, 256);
     L.partial = o; o = align_up(o + sizeof(g1_xyzz) * npart * sb, 256);
+    L.partial_points = npart * sb;
   }
   L.max_items = per * sb / choose_item_len(per * sb, half * sb) + half * sb;  // sum ceil(cnt/L) <= entries/L + buckets
   L.item_off = o;    o = align_up(o + sizeof(uint32_t) * half * sb, 256);
@@ -2304,7 +2306,8 @@ int msm_precompute(MsmBases* out, const g1_affine* d_bases, size_t n, uint32_t c
   out->n = n;
   out->c = c;
   out->windows = msm_num_windows(c);
-  if ((size_t)out->windows * n >= ((size_t)1 << 31) || out->windows > 31) return (int)hipErrorInvalidValue;
+  if (out->windows > 31) return kMsmErrWindows;
+  if ((size_t)out->windows * n >= ((size_t)1 << 31)) return (int)hipErrorInvalidValue;
   hipError_t e = hipMalloc(&out->ext, sizeof(g1_affine) * (n ? n : 1) * out->windows);
   if (e != hipSuccess) return (int)e;
   if (n == 0) return 0;
@@ -2437,6 +2440,146 @@ unsigned accumulate_threads() {
   return v;
 }
 
+bool heavy_combine_enabled() {  // CAPGPU_MSM_HEAVY_COMBINE=0: msm_combine walks the many-item buckets itself
+  static const bool on = [] {
+    const char* e = getenv("CAPGPU_MSM_HEAVY_COMBINE");
+    return !e || atoi(e) != 0;
+  }();
+  return on;
+}
+
+// ---- the form of a launch's tail: every choice between kernels, grids and lengths, decided in ONE place ---------------
+// run_tail and msm_run_slice launch what tail_form() returns and decide nothing themselves; capgpu_msm_tail_plan reports
+// the same structure (msm_tail_describe), so that a test can tell which kernels the shape it wrote reaches.
+struct TailShape {
+  uint32_t half, sb, item_len, planes;
+  size_t max_items, entries;
+  uint32_t seg_len = 0, reduce_half = 0;  // as in Tail
+  bool pairs = false;                     // results go to out_pair (the deep plan's entries)
+  bool chained = false;
+  // the sort front of msm_run_slice (scan_rows == 0: the caller has a front of its own)
+  uint32_t c = 0;
+  size_t scan_rows = 0;  // rows of the [bin][tile] table of one sub-MSM
+};
+struct TailForm {
+  // front
+  bool items_chained;
+  enum Scan { kScanNone, kScanBlock, kScanChained, kScanSeg3 } scan;
+  uint32_t scan_nseg;  // segments per sub-MSM of the two long forms
+  uint32_t digits;     // msm_digits_local<11 | 13 | 15>, 0: the window size as an argument
+  // accumulation
+  bool accumulate;
+  enum Acc { kAccOneShot, kAccCounter, kAccStride } acc;
+  unsigned acc_threads, acc_grid;
+  size_t acc_lds;
+  uint32_t item_len;
+  // combine
+  enum Combine { kCombineBucket, kCombineQuad, kCombineWave } combine;
+  uint32_t combine_lanes;  // quads (2, 4, 8) or lanes (8 .. 64) per bucket; per-bucket: 1
+  bool heavy;              // per-bucket: the many-item buckets go to msm_combine_heavy's list
+  // reduction
+  enum Reduce { kReduceSegments, kReduceGridQuad, kReduceGrid, kReduceBits } reduce;
+  uint32_t seg_len, rhalf, rsb, nseg;  // segments
+  bool quad_final;                     // segments: msm_reduce_final_quad, else the one-lane msm_reduce_final
+  uint32_t lo_bits, nsum, slices;      // both grid forms (slices: quads or lanes per row / column sum)
+  uint32_t final_terms;                // grid-quad: 64 or 128; one-lane grid: 0 = final_small, 1 = final
+  uint32_t nplanes, chunks;            // bit planes
+  size_t partial_points;               // points (sizeof(g1_xyzz) each) the reduction writes into `partial`, all entries
+};
+TailForm tail_form(const TailShape& t) {
+  TailForm f{};
+  const uint32_t half = t.half, sb = t.sb, item_len = t.item_len;
+  const uint32_t total_buckets = half * sb;
+  f.item_len = item_len;
+  // front
+  f.items_chained = t.chained;
+  if (t.scan_rows) {
+    const uint32_t nb = (uint32_t)t.scan_rows;
+    f.scan_nseg = (nb + kScanSeg - 1) / kScanSeg;
+    if (nb <= 4 * kScanSeg) f.scan = TailForm::kScanBlock;
+    else if (t.chained && (size_t)f.scan_nseg * sb <= 65535) f.scan = TailForm::kScanChained;
+    else f.scan = TailForm::kScanSeg3;
+    f.digits = t.c == 13 || t.c == 15 || t.c == 11 ? t.c : 0u;
+  }
+  // accumulation
+  f.accumulate = t.max_items > 0;
+  f.acc_threads = accumulate_threads();
+  f.acc_lds = accumulate_lds_bytes();
+  if (f.accumulate) {
+    f.acc_grid = (unsigned)((t.max_items + f.acc_threads - 1) / f.acc_threads);
+    // (256 CUs; + 8: a multiple of 8 that is NOT a whole number of MSMs - an MSM is 64 chunks of length-sorted items, and a
+    // stride of whole MSMs would hand a workgroup the same position, the longest or the shortest items, every time)
+    if (const unsigned per_cu = accumulate_persistent()) {
+      if (f.acc_grid > 256u * per_cu + 8u) {  // (a launch that fits the chip at once stays one-shot: nothing to re-dispatch)
+        f.acc_grid = 256u * per_cu + 8u;
+        f.acc = accumulate_dynamic() ? TailForm::kAccCounter : TailForm::kAccStride;
+      }
+    }
+  }
+  // reduction
+  f.seg_len = t.seg_len ? t.seg_len : reduce_seg_len_for(half, sb);
+  // small and middling launches: the tails run on quads (see msm_combine_quad) - also where the running sums would
+  // otherwise take over with too few segments to fill the chip (CAPGPU_MSM_QUAD_MAX_WIDE beyond 63)
+  const bool quad = !t.pairs && t.seg_len == 0 && use_grid_reduce(half) &&
+                    sb <= (half <= 4096 ? quad_max_batch() : quad_max_batch_wide());
+  const bool segments = t.seg_len != 0 || (use_segment_reduce(half, sb) && !quad);
+  f.heavy = heavy_combine_enabled() && t.max_items > 0;
+  f.combine_lanes = 1;
+  if (segments) {
+    f.combine = TailForm::kCombineBucket;
+    f.reduce = TailForm::kReduceSegments;
+    f.rhalf = t.reduce_half ? t.reduce_half : half;
+    f.rsb = total_buckets / f.rhalf;
+    f.nseg = (f.rhalf + f.seg_len - 1) / f.seg_len;
+    f.quad_final = quad_reduce_final();
+    f.partial_points = 2 * (size_t)f.nseg * f.rsb;
+    return f;
+  }
+  // G lanes per bucket: the smallest power of two that holds a bucket's items with some room for the spread of the
+  // bucket sizes (a bucket with more items than lanes loops), so that the shuffle tree is no deeper than needed
+  const size_t avg_items = (t.entries / total_buckets + item_len - 1) / item_len;
+  const size_t want = avg_items * 3 / 2;
+  if (avg_items <= 1 && total_buckets >= 65536) {
+    // buckets of (almost always) ONE item - a few dozen MSMs on the wide table: msm_accumulate wrote those buckets
+    // itself, and eight lanes per bucket would be five million idle threads (a 40-MSM launch: 300 us of them); one
+    // thread per bucket walks the rare second item
+    f.combine = TailForm::kCombineBucket;
+  } else if (quad && want <= 32) {
+    // (the same 8, 16 or 32 lanes per bucket as msm_combine_wave would take: two, four or eight quads)
+    f.combine = TailForm::kCombineQuad;
+    f.combine_lanes = want <= 8 ? 2u : (want <= 16 ? 4u : 8u);
+  } else {
+    f.combine = TailForm::kCombineWave;
+    f.combine_lanes = want <= 8 ? 8u : (want <= 16 ? 16u : (want <= 32 ? 32u : 64u));
+  }
+  if (f.combine != TailForm::kCombineBucket) f.heavy = false;
+  if (!t.pairs && use_grid_reduce(half)) {
+    uint32_t k = 0;
+    while ((1u << k) < half) k++;
+    f.lo_bits = k / 2;
+    f.nsum = (half >> f.lo_bits) + (1u << f.lo_bits);
+    const uint32_t dim = std::min(half >> f.lo_bits, 1u << f.lo_bits);
+    if (quad) {
+      f.reduce = TailForm::kReduceGridQuad;
+      f.slices = dim >= 32 ? 16u : 8u;  // 16 quads per sum where the dimension allows it (4 + 4 additions deep), 8 otherwise
+      f.final_terms = half <= 4096 ? 64u : 128u;
+      // behind the sums: the two dimensions' results and a counter (4 bytes) per entry
+      f.partial_points = (size_t)sb * f.nsum + 2 * (size_t)sb + (sizeof(uint32_t) * sb + sizeof(g1_xyzz) - 1) / sizeof(g1_xyzz);
+      return f;
+    }
+    f.reduce = TailForm::kReduceGrid;
+    f.slices = grid_slices(sb, f.nsum, dim);
+    f.final_terms = half > 4096 ? 1u : 0u;
+    f.partial_points = (size_t)sb * f.nsum;
+    return f;
+  }
+  f.reduce = TailForm::kReduceBits;
+  f.nplanes = t.planes + (t.pairs ? 1u : 0u);
+  f.chunks = reduce_chunks(half, f.nplanes, sb);
+  f.partial_points = (size_t)sb * f.nplanes * f.chunks;
+  return f;
+}
+
 // K5 + K6 over `sb` batch entries of `half` buckets each: work items, accumulation, bucket reduction.  One result per
 // entry goes to out (Jacobian), out_part (XYZZ: parts of a longer MSM) or out_pair (XYZZ (sum, weighted sum): entries
 // that are slices of one bucket set).
@@ -2452,16 +2595,25 @@ struct Tail {
   uint32_t reduce_half = 0;
   bool chained = false;  // the item kernels as one chained launch (msm_items); the digits kernel zeroed t.totals[0 .. sb]
 };
-void run_tail(const Tail& t, g1_jac* out, g1_xyzz* out_part, g1_xyzz* out_pair, hipStream_t stream) {
+TailShape tail_shape(const Tail& t, bool pairs) {
+  TailShape s{};
+  s.half = t.half;
+  s.sb = t.sb;
+  s.item_len = t.item_len;
+  s.planes = t.planes;
+  s.max_items = t.max_items;
+  s.entries = t.entries;
+  s.seg_len = t.seg_len;
+  s.reduce_half = t.reduce_half;
+  s.pairs = pairs;
+  s.chained = t.chained;
+  return s;
+}
+// f: the form of this launch (tail_form; msm_run_slice, which needs it for its sort front, hands over the one it has)
+void run_tail(const Tail& t, const TailForm& f, g1_jac* out, g1_xyzz* out_part, g1_xyzz* out_pair, hipStream_t stream) {
   const uint32_t half = t.half, sb = t.sb, item_len = t.item_len;
-  const uint32_t seg_len = t.seg_len ? t.seg_len : reduce_seg_len_for(half, sb);
-  // small and middling launches: the tails run on quads (see msm_combine_quad) - also where the running sums would
-  // otherwise take over with too few segments to fill the chip (CAPGPU_MSM_QUAD_MAX_WIDE beyond 63)
-  const bool quad = !out_pair && t.seg_len == 0 && use_grid_reduce(half) &&
-                    sb <= (half <= 4096 ? quad_max_batch() : quad_max_batch_wide());
-  const bool segments = t.seg_len != 0 || (use_segment_reduce(half, sb) && !quad);
   const uint32_t total_buckets = half * sb;
-  if (t.chained) {  // (t.totals: the flag words msm_digits_local zeroed)
+  if (f.items_chained) {  // (t.totals: the flag words msm_digits_local zeroed)
     launch("msm_items", msm_items, dim3(sb), dim3(1024), 0, stream, (const uint32_t*)t.counts, half, item_len, sb, t.item_off,
            t.item_base, t.totals, t.item_bucket, t.item_sub);
   } else {
@@ -2471,119 +2623,112 @@ void run_tail(const Tail& t, g1_jac* out, g1_xyzz* out_part, g1_xyzz* out_pair, 
     launch("msm_sort_items", msm_sort_items, dim3(sb), dim3(1024), 0, stream, (const uint32_t*)t.counts,
            (const uint32_t*)t.item_base, half, item_len, t.item_bucket, t.item_sub);
   }
-  if (t.max_items > 0) {
-    const unsigned at = accumulate_threads();
-    unsigned wgs = (unsigned)((t.max_items + at - 1) / at);
-    // (256 CUs; + 8: a multiple of 8 that is NOT a whole number of MSMs - an MSM is 64 chunks of length-sorted items, and a
-    // stride of whole MSMs would hand a workgroup the same position, the longest or the shortest items, every time)
-    bool dynamic = false;
-    if (const unsigned per_cu = accumulate_persistent()) {
-      if (wgs > 256u * per_cu + 8u) {  // (a launch that fits the chip at once stays one-shot: nothing to re-dispatch)
-        wgs = 256u * per_cu + 8u;
-        dynamic = accumulate_dynamic();
-      }
-    }
-    launch("msm_accumulate", msm_accumulate, dim3(wgs), dim3(at),
-           accumulate_lds_bytes(), stream, t.ext, (const uint32_t*)t.sorted, (const uint32_t*)t.counts, (const uint32_t*)t.offsets,
+  if (f.accumulate)
+    launch("msm_accumulate", msm_accumulate, dim3(f.acc_grid), dim3(f.acc_threads), f.acc_lds, stream, t.ext,
+           (const uint32_t*)t.sorted, (const uint32_t*)t.counts, (const uint32_t*)t.offsets,
            (const uint32_t*)t.item_off, (const uint32_t*)t.item_base, (const uint32_t*)t.item_bucket,
-           (const uint32_t*)t.item_sub, t.per, half, sb, item_len, dynamic ? t.item_base + sb + 1 : (uint32_t*)nullptr,
-           t.item_pts, t.buckets);
-  }
-  // bucket = sum of its items, one thread per bucket; the few buckets of many items go to a list (msm_accumulate's item
-  // list, dead by now, holds it; its length sits behind the item bases) and get 32 lanes each
-  auto combine_per_bucket = [&] {
-    static const bool heavy = [] {
-      const char* e = getenv("CAPGPU_MSM_HEAVY_COMBINE");
-      return !e || atoi(e) != 0;
-    }();
-    uint32_t* heavy_list = heavy && t.max_items > 0 ? t.item_bucket : nullptr;
-    uint32_t* heavy_count = t.item_base + sb + 2;
-    launch("msm_combine", msm_combine, dim3((total_buckets + kThreads - 1) / kThreads), dim3(kThreads), 0, stream,
-           (const g1_xyzz*)t.item_pts, (const uint32_t*)t.counts, (const uint32_t*)t.item_off,
-           (const uint32_t*)t.item_base, half, total_buckets, item_len, t.buckets, kHeavyItems, heavy_list, heavy_count);
-    if (heavy_list)
-      launch("msm_combine_heavy", msm_combine_heavy, dim3(512), dim3(kThreads), 0, stream, (const g1_xyzz*)t.item_pts,
-             (const uint32_t*)t.counts, (const uint32_t*)t.item_off, (const uint32_t*)t.item_base, half, item_len,
-             (const uint32_t*)heavy_list, (const uint32_t*)heavy_count, t.buckets);
-  };
-  if (segments) {
-    combine_per_bucket();
-    const uint32_t rhalf = t.reduce_half ? t.reduce_half : half, rsb = total_buckets / rhalf;
-    const uint32_t rnseg = (rhalf + seg_len - 1) / seg_len;
-    launch("msm_reduce_segments", msm_reduce_segments, dim3((rnseg * rsb + kThreads - 1) / kThreads), dim3(kThreads), 0,
-           stream, (const g1_xyzz*)t.buckets, rhalf, seg_len, rnseg, rsb, t.partial);
-    if (quad_reduce_final())
-      launch("msm_reduce_final", msm_reduce_final_quad, dim3(rsb), dim3(256), 0, stream, (const g1_xyzz*)t.partial, seg_len,
-             rnseg, out, out_part, out_pair);
-    else
-      launch("msm_reduce_final", msm_reduce_final, dim3(rsb), dim3(64), 0, stream, (const g1_xyzz*)t.partial, seg_len, rnseg,
-             out, out_part, out_pair);
-  } else {
-    // G lanes per bucket: the smallest power of two that holds a bucket's items with some room for the spread of the
-    // bucket sizes (a bucket with more items than lanes loops), so that the shuffle tree is no deeper than needed
-    const size_t avg_items = (t.entries / total_buckets + item_len - 1) / item_len;
-    const size_t want = avg_items * 3 / 2;
-    if (avg_items <= 1 && total_buckets >= 65536) {
-      // buckets of (almost always) ONE item - a few dozen MSMs on the wide table: msm_accumulate wrote those buckets
-      // itself, and eight lanes per bucket would be five million idle threads (a 40-MSM launch: 300 us of them); one
-      // thread per bucket walks the rare second item
-      combine_per_bucket();
-    } else if (quad && want <= 32) {
-      // (the same 8, 16 or 32 lanes per bucket as msm_combine_wave would take: two, four or eight quads)
-      const uint32_t GQ = want <= 8 ? 2u : (want <= 16 ? 4u : 8u);
+           (const uint32_t*)t.item_sub, t.per, half, sb, item_len,
+           f.acc == TailForm::kAccCounter ? t.item_base + sb + 1 : (uint32_t*)nullptr, t.item_pts, t.buckets);
+  switch (f.combine) {
+    case TailForm::kCombineBucket: {
+      // bucket = sum of its items, one thread per bucket; the few buckets of many items go to a list (msm_accumulate's
+      // item list, dead by now, holds it; its length sits behind the item bases) and get 32 lanes each
+      uint32_t* heavy_list = f.heavy ? t.item_bucket : nullptr;
+      uint32_t* heavy_count = t.item_base + sb + 2;
+      launch("msm_combine", msm_combine, dim3((total_buckets + kThreads - 1) / kThreads), dim3(kThreads), 0, stream,
+             (const g1_xyzz*)t.item_pts, (const uint32_t*)t.counts, (const uint32_t*)t.item_off,
+             (const uint32_t*)t.item_base, half, total_buckets, item_len, t.buckets, kHeavyItems, heavy_list, heavy_count);
+      if (heavy_list)
+        launch("msm_combine_heavy", msm_combine_heavy, dim3(512), dim3(kThreads), 0, stream, (const g1_xyzz*)t.item_pts,
+               (const uint32_t*)t.counts, (const uint32_t*)t.item_off, (const uint32_t*)t.item_base, half, item_len,
+               (const uint32_t*)heavy_list, (const uint32_t*)heavy_count, t.buckets);
+      break;
+    }
+    case TailForm::kCombineQuad: {
+      const uint32_t GQ = f.combine_lanes;
       auto kern = GQ == 2 ? msm_combine_quad<2> : (GQ == 4 ? msm_combine_quad<4> : msm_combine_quad<8>);
       launch("msm_combine", kern, dim3((unsigned)(((size_t)total_buckets * GQ * 4 + kThreads - 1) / kThreads)),
              dim3(kThreads), 0, stream, (const g1_xyzz*)t.item_pts, (const uint32_t*)t.counts,
              (const uint32_t*)t.item_off, (const uint32_t*)t.item_base, half, total_buckets, item_len, t.buckets);
-    } else {
-      const uint32_t G = want <= 8 ? 8u : (want <= 16 ? 16u : (want <= 32 ? 32u : 64u));
+      break;
+    }
+    case TailForm::kCombineWave: {
+      const uint32_t G = f.combine_lanes;
       auto kern = G == 8 ? msm_combine_wave<8>
                          : (G == 16 ? msm_combine_wave<16> : (G == 32 ? msm_combine_wave<32> : msm_combine_wave<64>));
       launch("msm_combine", kern, dim3((unsigned)(((size_t)total_buckets * G + kThreads - 1) / kThreads)),
              dim3(kThreads), 0, stream, (const g1_xyzz*)t.item_pts, (const uint32_t*)t.counts,
              (const uint32_t*)t.item_off, (const uint32_t*)t.item_base, half, total_buckets, item_len, t.buckets);
+      break;
     }
-    if (!out_pair && use_grid_reduce(half)) {
-      uint32_t k = 0;
-      while ((1u << k) < half) k++;
-      const uint32_t lo_bits = k / 2, nsum = (half >> lo_bits) + (1u << lo_bits);
-      if (quad) {
-        // 16 quads per sum where the dimension allows it (4 + 4 additions deep), 8 otherwise
-        const bool s16 = std::min(half >> lo_bits, 1u << lo_bits) >= 32;
-        // behind the sums in `partial` (ws_layout keeps the room): the two dimensions' results and a counter per entry
-        g1_xyzz* fin = t.partial + (size_t)sb * nsum;
-        uint32_t* fin_count = reinterpret_cast<uint32_t*>(fin + 2 * (size_t)sb);
-        const uint32_t qs = s16 ? 16u : 8u;
-        launch("msm_reduce_grid", s16 ? msm_reduce_grid_quad<16> : msm_reduce_grid_quad<8>,
-               dim3((unsigned)(((size_t)sb * nsum * qs * 4 + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream,
-               (const g1_xyzz*)t.buckets, half, lo_bits, sb, t.partial, fin_count);
-        if (half <= 4096)
-          launch("msm_reduce_grid_final", msm_reduce_grid_final_quad<64>, dim3(sb, 2), dim3(256), 0, stream,
-                 (const g1_xyzz*)t.partial, half, lo_bits, fin, fin_count, out, out_part);
-        else
-          launch("msm_reduce_grid_final", msm_reduce_grid_final_quad<128>, dim3(sb, 2), dim3(512), 0, stream,
-                 (const g1_xyzz*)t.partial, half, lo_bits, fin, fin_count, out, out_part);
-        return;
-      }
-      const uint32_t slices = grid_slices(sb, nsum, std::min(half >> lo_bits, 1u << lo_bits));
+  }
+  switch (f.reduce) {
+    case TailForm::kReduceSegments:
+      launch("msm_reduce_segments", msm_reduce_segments, dim3((f.nseg * f.rsb + kThreads - 1) / kThreads), dim3(kThreads), 0,
+             stream, (const g1_xyzz*)t.buckets, f.rhalf, f.seg_len, f.nseg, f.rsb, t.partial);
+      if (f.quad_final)
+        launch("msm_reduce_final", msm_reduce_final_quad, dim3(f.rsb), dim3(256), 0, stream, (const g1_xyzz*)t.partial,
+               f.seg_len, f.nseg, out, out_part, out_pair);
+      else
+        launch("msm_reduce_final", msm_reduce_final, dim3(f.rsb), dim3(64), 0, stream, (const g1_xyzz*)t.partial, f.seg_len,
+               f.nseg, out, out_part, out_pair);
+      break;
+    case TailForm::kReduceGridQuad: {
+      // behind the sums in `partial` (ws_layout keeps the room): the two dimensions' results and a counter per entry
+      g1_xyzz* fin = t.partial + (size_t)sb * f.nsum;
+      uint32_t* fin_count = reinterpret_cast<uint32_t*>(fin + 2 * (size_t)sb);
+      launch("msm_reduce_grid", f.slices == 16 ? msm_reduce_grid_quad<16> : msm_reduce_grid_quad<8>,
+             dim3((unsigned)(((size_t)sb * f.nsum * f.slices * 4 + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream,
+             (const g1_xyzz*)t.buckets, half, f.lo_bits, sb, t.partial, fin_count);
+      if (f.final_terms == 64)
+        launch("msm_reduce_grid_final", msm_reduce_grid_final_quad<64>, dim3(sb, 2), dim3(256), 0, stream,
+               (const g1_xyzz*)t.partial, half, f.lo_bits, fin, fin_count, out, out_part);
+      else
+        launch("msm_reduce_grid_final", msm_reduce_grid_final_quad<128>, dim3(sb, 2), dim3(512), 0, stream,
+               (const g1_xyzz*)t.partial, half, f.lo_bits, fin, fin_count, out, out_part);
+      break;
+    }
+    case TailForm::kReduceGrid: {
+      const uint32_t slices = f.slices;
       auto gk = slices == 64 ? msm_reduce_grid<64> : (slices == 32 ? msm_reduce_grid<32> : (slices == 16 ? msm_reduce_grid<16> : msm_reduce_grid<8>));
-      launch("msm_reduce_grid", gk, dim3((unsigned)(((size_t)sb * nsum * slices + kThreads - 1) / kThreads)),
-             dim3(kThreads), 0, stream, (const g1_xyzz*)t.buckets, half, lo_bits, sb, t.partial);
-      if (half > 4096)
+      launch("msm_reduce_grid", gk, dim3((unsigned)(((size_t)sb * f.nsum * slices + kThreads - 1) / kThreads)),
+             dim3(kThreads), 0, stream, (const g1_xyzz*)t.buckets, half, f.lo_bits, sb, t.partial);
+      if (f.final_terms)
         launch("msm_reduce_grid_final", msm_reduce_grid_final, dim3(sb), dim3(256), 0, stream,
-               (const g1_xyzz*)t.partial, half, lo_bits, out, out_part);
+               (const g1_xyzz*)t.partial, half, f.lo_bits, out, out_part);
       else
         launch("msm_reduce_grid_final", msm_reduce_grid_final_small, dim3(sb), dim3(128), 0, stream,
-               (const g1_xyzz*)t.partial, half, lo_bits, out, out_part);
-      return;
+               (const g1_xyzz*)t.partial, half, f.lo_bits, out, out_part);
+      break;
     }
-    const uint32_t nplanes = t.planes + (out_pair ? 1u : 0u);
-    const uint32_t chunks = reduce_chunks(half, nplanes, sb);
-    launch("msm_reduce_bits", msm_reduce_bits, dim3(chunks, nplanes, sb), dim3(kReduceThreads), 0, stream,
-           (const g1_xyzz*)t.buckets, half, t.planes, nplanes, chunks, t.partial);
-    launch("msm_reduce_bits_final", msm_reduce_bits_final, dim3(sb), dim3(256), 0, stream, (const g1_xyzz*)t.partial,
-           t.planes, nplanes, chunks, out, out_part, out_pair);
+    case TailForm::kReduceBits:
+      launch("msm_reduce_bits", msm_reduce_bits, dim3(f.chunks, f.nplanes, sb), dim3(kReduceThreads), 0, stream,
+             (const g1_xyzz*)t.buckets, half, t.planes, f.nplanes, f.chunks, t.partial);
+      launch("msm_reduce_bits_final", msm_reduce_bits_final, dim3(sb), dim3(256), 0, stream, (const g1_xyzz*)t.partial,
+             t.planes, f.nplanes, f.chunks, out, out_part, out_pair);
+      break;
   }
+}
+
+// callers with a sort front of their own (the deep plan, the one-shot MSM): the form from the tail's fields alone
+void run_tail(const Tail& t, g1_jac* out, g1_xyzz* out_part, g1_xyzz* out_pair, hipStream_t stream) {
+  run_tail(t, tail_form(tail_shape(t, out_pair != nullptr)), out, out_part, out_pair, stream);
+}
+
+// the shape msm_run_slice hands to tail_form: `sb` sub-MSMs of n_sub points on the table (c, W)
+TailShape slice_shape(uint32_t c, uint32_t W, size_t n_sub, uint32_t sb, uint32_t sub_bits, const WsLayout& L) {
+  TailShape s{};
+  const size_t per = (size_t)W * n_sub;
+  s.half = 1u << (c - 1);
+  s.sb = sb;
+  s.item_len = choose_item_len(per * sb, (size_t)s.half * sb);
+  s.planes = c;
+  s.max_items = L.max_items;
+  s.entries = per * sb;
+  s.chained = chained_enabled();
+  s.c = c;
+  s.scan_rows = (size_t)(s.half >> sub_bits) * L.nblk;
+  return s;
 }
 
 // one long MSM on the deep-window table (choose_plan): three-level sort, then the common tail over 2^(K-14) batch
@@ -2705,27 +2850,27 @@ int msm_run_slice(const MsmBases& bases, const Plan& pl, size_t offset, const fe
   // the scalars of MSM `first + b`: the addressing of msm_run with the slice's first MSM folded into the pointer
   // (slices start at multiples of `inner` or the launch has inner == 1 / a single slice)
   const fe* sc0 = d_scalars + (size_t)(first / inner) * outer_stride + (size_t)(first % inner) * inner_stride;
-  // exclusive scan of `nb` counters per sub-MSM: one workgroup per entry, or - for a long table - segments in parallel
+  // exclusive scan of the [bin][tile] table per sub-MSM: one workgroup per entry, or - for a long table - segments in
+  // parallel, as one chained launch (its flag words (seg_tot) and ticket are zeroed by the digits kernel) or as three
   uint32_t* seg_tot = reinterpret_cast<uint32_t*>(base + L.seg_tot);
-  const bool chained = chained_enabled();
-  // the long-table scan as one chained launch: its flag words (seg_tot) and ticket are zeroed by the digits kernel
-  auto scan_is_chained = [&](uint32_t nb) {
-    return chained && nb > 4 * kScanSeg && (size_t)((nb + kScanSeg - 1) / kScanSeg) * sb <= 65535;
-  };
+  const TailShape shape = slice_shape(c, W, n_sub, sb, pl.sub_bits, L);
+  const TailForm f = tail_form(shape);
+  const bool chained = shape.chained;
   auto scan_counts = [&](const uint32_t* in, uint32_t* out, uint32_t nb) {
-    if (nb <= 4 * kScanSeg) {
-      launch("msm_scan", msm_scan<0>, dim3(sb), dim3(1024), 0, stream, in, out, nb, (uint32_t*)nullptr, 0u);
-      return;
+    const uint32_t ns = f.scan_nseg;
+    switch (f.scan) {
+      case TailForm::kScanBlock:
+        launch("msm_scan", msm_scan<0>, dim3(sb), dim3(1024), 0, stream, in, out, nb, (uint32_t*)nullptr, 0u);
+        break;
+      case TailForm::kScanChained:
+        launch("msm_scan_chained", msm_scan_chained, dim3(ns * sb), dim3(1024), 0, stream, in, out, nb, ns, seg_tot,
+               seg_tot + (size_t)ns * sb);
+        break;
+      default:
+        launch("msm_scan_seg", msm_scan_seg, dim3(ns, sb), dim3(1024), 0, stream, in, out, nb, ns, seg_tot);
+        launch("msm_scan_tot", msm_scan_tot, dim3(sb), dim3(1024), 0, stream, seg_tot, ns);
+        launch("msm_scan_add", msm_scan_add, dim3(ns, sb), dim3(1024), 0, stream, out, nb, ns, (const uint32_t*)seg_tot);
     }
-    const uint32_t ns = (nb + kScanSeg - 1) / kScanSeg;
-    if (scan_is_chained(nb)) {
-      launch("msm_scan_chained", msm_scan_chained, dim3(ns * sb), dim3(1024), 0, stream, in, out, nb, ns, seg_tot,
-             seg_tot + (size_t)ns * sb);
-      return;
-    }
-    launch("msm_scan_seg", msm_scan_seg, dim3(ns, sb), dim3(1024), 0, stream, in, out, nb, ns, seg_tot);
-    launch("msm_scan_tot", msm_scan_tot, dim3(sb), dim3(1024), 0, stream, seg_tot, ns);
-    launch("msm_scan_add", msm_scan_add, dim3(ns, sb), dim3(1024), 0, stream, out, nb, ns, (const uint32_t*)seg_tot);
   };
 
   {
@@ -2749,15 +2894,15 @@ int msm_run_slice(const MsmBases& bases, const Plan& pl, size_t offset, const fe
         hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
       attr_set.fetch_or(1ull << (dev & 63));
     }
-    auto digits_kernel = c == 13   ? msm_digits_local<13>
-                         : c == 15 ? msm_digits_local<15>
-                         : c == 11 ? msm_digits_local<11>
-                                   : msm_digits_local<0>;
+    auto digits_kernel = f.digits == 13   ? msm_digits_local<13>
+                         : f.digits == 15 ? msm_digits_local<15>
+                         : f.digits == 11 ? msm_digits_local<11>
+                                          : msm_digits_local<0>;
     launch("msm_digits_local", digits_kernel, dim3(sb == 1 ? nblk : nblk * ((sb + 7) / 8) * 8), dim3(kDigitThreads),
            lds_bytes, stream,
            sc0, outer_stride, inner, inner_stride, n, n_sub, parts, montgomery, c, W, nblk, sb, pl.sub_bits, 0u, table,
            tloc, chunk_buf, seg_tot,
-           scan_is_chained(bins * nblk) ? (uint32_t)(((bins * nblk + kScanSeg - 1) / kScanSeg) * sb + 1) : 0u,
+           f.scan == TailForm::kScanChained ? (uint32_t)(f.scan_nseg * sb + 1) : 0u,
            reinterpret_cast<uint32_t*>(base + L.totals), chained ? sb + 1 : 0u);
     scan_counts(table, off2, bins * nblk);
     if (pl.sub_bits) {
@@ -2787,19 +2932,68 @@ int msm_run_slice(const MsmBases& bases, const Plan& pl, size_t offset, const fe
   t.buckets = reinterpret_cast<g1_xyzz*>(base + L.buckets);
   t.partial = partial;
   t.per = per;
-  t.max_items = L.max_items;
-  t.entries = per * sb;
+  t.max_items = shape.max_items;
+  t.entries = shape.entries;
   t.half = half;
   t.sb = sb;
-  t.item_len = choose_item_len(per * sb, (size_t)half * sb);
-  t.planes = c;
+  t.item_len = shape.item_len;
+  t.planes = shape.planes;
   t.chained = chained;
-  run_tail(t, d_out + first, part_pts, nullptr, stream);
+  run_tail(t, f, d_out + first, part_pts, nullptr, stream);
   if (parts > 1)
     launch("msm_sum_parts", msm_sum_parts, dim3(batch), dim3(64), 0, stream, (const g1_xyzz*)part_pts, parts, d_out + first);
   return 0;  // launch failures are latched by launch() and reported by take_launch_error()
 }
 }  // namespace
+
+int msm_tail_describe(uint32_t c, size_t n_sub, uint32_t sb, bool has_parts, char* buf, size_t cap) {
+  // windows the batched plans can run: 31 at most (a tile entry's 5-bit window field: c >= 9), buckets sets up to 2^15
+  if (c < 9 || c > 16 || n_sub == 0 || sb == 0) return 1;
+  const uint32_t W = msm_num_windows(c);
+  const size_t half = (size_t)1 << (c - 1);
+  // the limits batch_slice keeps a launch within: 32-bit counters, the [key][tile] tables
+  if ((size_t)W * n_sub >= ((size_t)1 << 31) || ((size_t)W * n_sub + half) > ((size_t)3 << 30) / sb) return 1;
+  const uint32_t sub_bits = c >= 14 ? pick_sub_bits(n_sub, c, W) : 0u;  // the wide windows sort in two levels (choose_plan)
+  if ((half >> sub_bits) * ((n_sub + kDigitTile - 1) / kDigitTile) > ((size_t)1 << 28) / sb) return 1;
+  const WsLayout L = ws_layout(c, W, n_sub, sb, sub_bits, has_parts);
+  const TailShape shape = slice_shape(c, W, n_sub, sb, sub_bits, L);
+  const TailForm f = tail_form(shape);
+  static const char* const kScan[] = {"none", "one-block", "chained", "seg-tot-add"};
+  static const char* const kAcc[] = {"one-shot", "persistent-counter", "persistent-stride"};
+  static const char* const kCombine[] = {"bucket", "quad", "wave"};
+  static const char* const kReduce[] = {"segments", "grid-quad", "grid", "bits"};
+  char digits[12];
+  if (f.digits) snprintf(digits, sizeof digits, "%u", f.digits);
+  else snprintf(digits, sizeof digits, "generic");
+  int len = snprintf(buf, cap,
+                     "c=%u windows=%u buckets=%zu sub_msms=%u bin_buckets=%u items=%s scan=%s scan_rows=%zu scan_segments=%u "
+                     "digits=%s acc=%s acc_threads=%u acc_grid=%u acc_lds=%zu max_items=%zu item_len=%u combine=%s "
+                     "combine_lanes=%u heavy=%u reduce=%s",
+                     c, W, half, sb, sub_bits ? 1u << sub_bits : 0u, f.items_chained ? "chained" : "separate", kScan[f.scan],
+                     shape.scan_rows, f.scan == TailForm::kScanBlock ? 0u : f.scan_nseg, digits,
+                     f.accumulate ? kAcc[f.acc] : "none", f.acc_threads, f.acc_grid, f.acc_lds, shape.max_items, f.item_len,
+                     kCombine[f.combine], f.combine_lanes, f.heavy ? 1u : 0u, kReduce[f.reduce]);
+  auto more = [&](const char* fmt, auto... args) {
+    if (len > 0 && (size_t)len < cap) len += snprintf(buf + len, cap - len, fmt, args...);
+  };
+  switch (f.reduce) {
+    case TailForm::kReduceSegments:
+      more(" seg_len=%u segments=%u seg_divides=%u finish=%s", f.seg_len, f.nseg, f.rhalf % f.seg_len == 0 ? 1u : 0u,
+           f.quad_final ? "quad" : "one-lane");
+      break;
+    case TailForm::kReduceGridQuad:
+      more(" grid_sums=%u slices=%u finish=quad-%u", f.nsum, f.slices, f.final_terms);
+      break;
+    case TailForm::kReduceGrid:
+      more(" grid_sums=%u slices=%u finish=%s", f.nsum, f.slices, f.final_terms ? "final" : "final_small");
+      break;
+    case TailForm::kReduceBits:
+      more(" planes=%u chunks=%u", f.nplanes, f.chunks);
+      break;
+  }
+  more(" partial_points=%zu partial_reserved=%zu sums_parts=%u", f.partial_points, L.partial_points, has_parts ? 1u : 0u);
+  return (len > 0 && (size_t)len < cap) ? 0 : 2;
+}
 
 int msm_run(const MsmBases& bases, size_t offset, const fe* d_scalars, size_t outer_stride, uint32_t inner,
             size_t inner_stride, size_t n, uint32_t batch, int montgomery, g1_jac* d_out, void* ws, size_t ws_bytes,

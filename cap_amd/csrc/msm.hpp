@@ -74,12 +74,19 @@ uint32_t msm_choose_window(size_t n);
 uint32_t msm_num_windows(uint32_t c);
 
 // Expand `n` affine bases (device, Montgomery, (0,0) = infinity) into the window table.
+// 0, a hipError_t, or kMsmErrWindows: c means more than the 31 windows a table holds (a tile entry's window field has 5
+// bits) - only CAPGPU_MSM_C below 9 asks for that; nothing is allocated then.
+constexpr int kMsmErrWindows = -31;
 int msm_precompute(MsmBases* out, const g1_affine* d_bases, size_t n, uint32_t c, hipStream_t stream);
 void msm_free_bases(MsmBases* b);
 
 size_t msm_workspace_bytes(const MsmBases& bases, size_t n, uint32_t batch);
 // "c=15 windows=18 sort=two-level parts=256 n_sub=65536 slice=1": which table, sort and split a launch would use
 const char* msm_plan_describe(const MsmBases& bases, size_t n, uint32_t batch, char* buf, size_t cap);
+// What follows the plan: the kernels, grids and lengths one launch of `sub_msms` sub-MSMs of n_sub points on the c-bit
+// table gets (msm.hip: tail_form, which the launch itself consults), as "key=value ..." - host arithmetic only.
+// 0, 1 when the batched plans cannot run such a launch (9 <= c <= 16, sizes within a slice), 2 when buf is too short.
+int msm_tail_describe(uint32_t c, size_t n_sub, uint32_t sub_msms, bool has_parts, char* buf, size_t cap);
 
 // out[b] = sum_{i<n} scalars_b[i] * bases[offset + i]   for b < batch, where
 // scalars_b = d_scalars + (b / inner) * outer_stride + (b % inner) * inner_stride   (elements).

@@ -488,6 +488,24 @@ def msm_var_plan(n: int, count: int = 1) -> dict:
     return out
 
 
+def msm_tail_plan(c: int, n_sub: int, sub_msms: int = 1, has_parts: bool = False) -> dict:
+    """What one launch of `sub_msms` sub-MSMs of n_sub points on the c-bit table runs after its plan is chosen (the inputs
+    are cg.msm_plan's c, n_sub and count * parts): {'items': 'chained', 'scan': 'one-block', 'digits': 13, 'acc':
+    'one-shot', 'acc_grid': ..., 'item_len': ..., 'combine': 'quad', 'combine_lanes': 4, 'reduce': 'grid-quad', ...,
+    'partial_points': ..., 'partial_reserved': ...}; no device needed.  The environment switches are read once per
+    process."""
+    buf = ctypes.create_string_buffer(1024)
+    check(load().capgpu_msm_tail_plan(int(c), ctypes.c_size_t(n_sub), int(sub_msms), int(bool(has_parts)), buf,
+                                      ctypes.c_size_t(1024)))
+    out = {}
+    for kv in buf.value.decode().split():
+        if "=" not in kv:
+            continue
+        k, v = kv.split("=")
+        out[k] = int(v) if v.isdigit() else v
+    return out
+
+
 # ---- multi-GPU (one process per GPU; RCCL inside the library) -----------------------------------------------------
 def comm_unique_id() -> bytes:
     buf = (ctypes.c_uint8 * 128)()

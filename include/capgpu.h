@@ -325,6 +325,14 @@ int capgpu_msm_shard_stats(uint64_t* scalar_bytes_out, uint64_t* partial_bytes_o
  * ("c=15 windows=18 sort=two-level parts=256 n_sub=65536 slice=1").  Tests pin the plan of the BASELINE sizes with
  * it, so that a size limit can never silently move a configuration to a slower path. */
 int capgpu_msm_plan(uint64_t srs_handle, size_t n, int count, char* buf, size_t cap);
+/* Diagnostic: what one launch runs AFTER its plan is chosen - `sub_msms` (count * parts of capgpu_msm_plan) sub-MSMs of
+ * n_sub points on the table of c window bits: item kernels, scan form, digits kernel, msm_accumulate's grid and mode,
+ * item length, combine and reduction kernels with their lengths, and the points the reduction writes next to the points
+ * reserved for it ("... combine=quad combine_lanes=4 reduce=grid-quad grid_sums=128 slices=16 finish=quad-64
+ * partial_points=131 partial_reserved=131").  It is the function the launch itself consults, so the CAPGPU_MSM_* /
+ * CAPGPU_ACC_* switches of the process are in it.  Needs no device and no handle; cap of 1024 bytes is enough.
+ * CAPGPU_ERR_INVALID_ARG for a null buffer, zero sizes, or window bits the batched plans cannot run (outside 9..16). */
+int capgpu_msm_tail_plan(int c, size_t n_sub, int sub_msms, int has_parts, char* buf, size_t cap);
 
 /* out = sum of n Jacobian points (96 B each, host memory): the combine step after the all-gather of a
  * point-range-sharded MSM (replaces the G-1 `GroupProjective::add_assign` a multi-GPU caller would do). */
