@@ -116,6 +116,21 @@ __global__ __launch_bounds__(kThreads) void k_check_copies(const fe* __restrict_
   check_report(key, &out[p].first, &out[p].copies);
 }
 
+// The prover's own test on the rows, where the quotient is interpolated from five n-cosets and carries no redundancy: a
+// numerator that is not divisible by Z_H no longer shows as coefficients above degree 5n + 7 (k_check_degree's bit 1).
+// Divisible means: zero on every row of the domain, where the blinders vanish - the gate constraint holds on every row
+// (k_check_gates: out[p].first), z(omega x) den = z(x) num holds on every row by the way z is made, and z closes:
+// prod num == prod den, from the scans' ends.  flags[p] |= 1 otherwise: the same bit for the same witnesses.
+__global__ void k_rows_verdict(const CheckOut* __restrict__ out, const fe* __restrict__ pre, const fe* __restrict__ num,
+                               const fe* __restrict__ sfx, const fe* __restrict__ den, size_t n,
+                               uint32_t* __restrict__ flags, uint32_t count) {
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= count) return;
+  const size_t o = (size_t)p * n;
+  const fe total_num = Fr::mul(pre[o + n - 1], num[o + n - 1]), total_den = Fr::mul(sfx[o], den[o]);
+  if (out[p].first != kNoFault || !Fr::eq(total_num, total_den)) atomicOr(&flags[p], 1u);
+}
+
 // After both checks: the cell a proof's first violated copy constraint points to (what the message names), one lane per
 // proof - so that the host fetches P words in one copy instead of one word per faulty witness.
 __global__ void k_check_targets(const CheckKey* __restrict__ keys, const CheckOut* __restrict__ out, uint32_t P,

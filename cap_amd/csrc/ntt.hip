@@ -70,6 +70,7 @@ struct PassParams {
   size_t in_outer, in_inner, in_len;
   uint32_t in_group;
   uint32_t in_es;            // element stride of the first-pass input (decimated transforms); 1 = contiguous
+  size_t in_fold;            // folded first-pass input (NttIo::src_fold; contiguous input with a pre-scale table); 0 = none
   // second grouping level of the input (decimated transforms of grouped polynomials): array q = (q2, a) with
   // a = q % in_group the decimation phase and q2 = q / in_group placed at (q2 / in_group2) * in_outer + (q2 % in_group2) * in_inner2
   size_t in_inner2;
@@ -284,6 +285,9 @@ __device__ __forceinline__ void col_tile(const PassParams& p, fl* sh, const uint
       for (int k = 0; k < 8; k++) nz |= raw[u].v[k];
       fl v = Fr29::load(raw[u]);
       if (p.pre_scale && any[u] && nz) v = Fr29::mul(v, Fr29::load(pre[u]));  // zero padding needs no coset scaling
+      if (p.in_fold && sgs[u] + p.in_fold < p.in_len)  // the few coefficients beyond the transform's length, folded in
+        v = Fr29::add_norm(v, Fr29::mul(Fr29::load(in[sgs[u] + p.in_fold]),
+                                        Fr29::load(p.pre_scale[sgs[u] + p.in_fold + (size_t)(by % p.in_group) * p.pre_inner])));
       sh[(bitrev32(j, p.log_len) << p.log_c) + c] = v;
     }
   }
@@ -376,6 +380,9 @@ __device__ __forceinline__ void row_tile(const PassParams& p, fl* sh, const uint
       for (int k = 0; k < 8; k++) nz |= raw[u].v[k];
       fl v = Fr29::load(raw[u]);
       if (p.pre_scale && any[u] && nz) v = Fr29::mul(v, Fr29::load(pre[u]));  // zero padding needs no coset scaling
+      if (p.in_fold && sgs[u] + p.in_fold < p.in_len)  // the few coefficients beyond the transform's length, folded in
+        v = Fr29::add_norm(v, Fr29::mul(Fr29::load(in[sgs[u] + p.in_fold]),
+                                        Fr29::load(p.pre_scale[sgs[u] + p.in_fold + (size_t)(by % p.in_group) * p.pre_inner])));
       sh[(bitrev32(j, p.log_len) << p.log_c) + c] = v;
     }
   }
@@ -486,6 +493,51 @@ __global__ __launch_bounds__(kThreads) void ntt3_combine(const fe* __restrict__ 
     o[m_len + k] = F::store(x1);
     o[2 * m_len + k] = F::store(x2);
   }
+}
+
+// ---- the solve of the five-coset inverse (ntt.hpp: Quot5Const) ----------------------------------------------------
+// y01: [count][2][M] outputs of the inverse M-point transforms of blocks 0 and 1, y2: [count][M / 2] of the inverse
+// M / 2-point transform of the compact block 2 (lazy, internal form).  out: array q at q * 3 M, all 3 M coefficients.
+// One thread per i < n = M / 2 writes coefficients i, n + i, .. 5n + i:  un-scaling (the table changes the form as
+// well: arkworks' from here on), the fixed 2 x 2 and 3 x 5 products, d_j add[q][i], and for i < 8 mt_j top[q][i];
+// coefficient 5n + i is top[q][i] for i < 8 and zero beyond.  Canonical outputs.
+__global__ __launch_bounds__(kThreads) void ntt3_combine5(const fe* __restrict__ y01, const fe* __restrict__ y2,
+                                                          fe* __restrict__ out, size_t n_len,
+                                                          const fe* __restrict__ unscale, Quot5Const qc,
+                                                          const fe* __restrict__ top, const fe* __restrict__ add) {
+  using F = Fr29;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_len) return;
+  const uint32_t q = blockIdx.y;
+  const size_t m_len = 2 * n_len;
+  const fe* ya = y01 + (size_t)q * 2 * m_len;
+  fe* o = out + (size_t)q * 3 * m_len;
+  const fl e0 = F::mul(F::load(ya[i]), F::load(unscale[i]));
+  const fl o0 = F::mul(F::load(ya[n_len + i]), F::load(unscale[n_len + i]));
+  const fl e1 = F::mul(F::load(ya[m_len + i]), F::load(unscale[m_len + i]));
+  const fl o1 = F::mul(F::load(ya[m_len + n_len + i]), F::load(unscale[m_len + n_len + i]));
+  const fl r = F::mul(F::load(y2[(size_t)q * n_len + i]), F::load(unscale[2 * m_len + i]));
+  const bool has_top = i < 8;
+  fl pi = F::zero(), h = F::zero();
+  if (add) pi = F::load(add[(size_t)q * n_len + i]);
+  if (has_top) h = F::load(top[(size_t)q * 8 + i]);
+  // sums of at most four reduced values (< 2p each, normalized): limbs < 2^31, well inside what normalize and canonical take
+  auto finish = [&](fl v, int j) {
+    if (add) v = F::add(v, F::mul(pi, F::load(qc.d[j])));
+    if (has_top) v = F::add(v, F::mul(h, F::load(qc.mt[j])));
+    return F::pack(F::canonical(F::normalize(v)));
+  };
+  for (int jj = 0; jj < 2; jj++)
+    o[(size_t)(2 * jj + 1) * n_len + i] =
+        finish(F::mul_add_mul(o0, F::load(qc.odd[jj][0]), o1, F::load(qc.odd[jj][1])), 2 * jj + 1);
+  for (int jj = 0; jj < 3; jj++) {
+    const fl a = F::mul_add_mul(e0, F::load(qc.even[jj][0]), o0, F::load(qc.even[jj][1]));
+    const fl b = F::mul_add_mul(e1, F::load(qc.even[jj][2]), o1, F::load(qc.even[jj][3]));
+    o[(size_t)(2 * jj) * n_len + i] = finish(F::add(F::add(a, b), F::mul(r, F::load(qc.even[jj][4]))), 2 * jj);
+  }
+  fe t5 = Fr::zero();
+  if (has_top) t5 = top[(size_t)q * 8 + i];
+  o[5 * n_len + i] = t5;
 }
 
 fe host_root_of_unity(uint32_t log_n) {
@@ -750,7 +802,11 @@ int ntt_run(const NttDomain& dom, const NttSmallTables& small, fe* data, fe* scr
   const Addr a_dst = io ? Addr{io->dst_outer, io->dst_inner, io->dst_group ? io->dst_group : 1u} : Addr{stride_elems, 0, 1};
   const Addr a_tmp = Addr{scratch_stride, 0, 1};
   const size_t src_len = io ? io->src_len : ~(size_t)0;
+  const size_t src_fold = io ? io->src_fold : 0;
+  if (src_fold && (!io->pre_scale || (io->src_elem_stride > 1) || src_fold + ((size_t)1 << log_n) < io->src_len))
+    return (int)hipErrorInvalidValue;  // one fold only, of contiguous pre-scaled input
   auto set_in = [&](const Addr& a, size_t len, uint32_t es) {
+    p.in_fold = &a == &a_src ? src_fold : 0;
     p.in_outer = a.outer;
     p.in_inner = a.inner;
     p.in_group = a.group;
@@ -857,6 +913,70 @@ void exponent_third(uint32_t e[8]) {
     rem = cur % 3;
   }
 }
+
+// the tables and constants of the five-coset transforms (ntt.hpp: Ntt3Domain::unscale5, Quot5Const); g = 5, wN = omega_N
+template <class ToInternal>
+int build_quot5(Ntt3Domain* d, const fe& g, const fe& wN, ToInternal to_internal, hipStream_t stream) {
+  const size_t M = (size_t)1 << d->log_m, nh = M / 2;
+  hipError_t e;
+  if ((e = hipMalloc(&d->unscale5, sizeof(fe) * (2 * M + nh))) != hipSuccess) return (int)e;
+  const uint32_t en[8] = {(uint32_t)nh, (uint32_t)((uint64_t)nh >> 32), 0, 0, 0, 0, 0, 0};
+  fe c[5];  // c_k = s_k^n for k < 3, c_(k+3) = -c_k
+  fe s_a = g;
+  int rc;
+  for (int a = 0; a < 3; a++) {
+    c[a] = Fr::pow(s_a, en);
+    if ((rc = build_powers(d->unscale5 + (size_t)a * M, a < 2 ? M : nh, Fr::inv(s_a), nullptr, stream))) return rc;
+    s_a = Fr::mul(s_a, wN);
+  }
+  c[3] = Fr::neg(c[0]);
+  c[4] = Fr::neg(c[1]);
+  // rows E_0, O_0, E_1, O_1, R of the system in (u_0 .. u_4), inverted by Gauss-Jordan elimination
+  fe A[5][10];
+  for (int r = 0; r < 5; r++)
+    for (int j = 0; j < 10; j++) A[r][j] = j == 5 + r ? Fr::one() : Fr::zero();
+  for (int a = 0; a < 2; a++) {
+    const fe c2 = Fr::sqr(c[a]);
+    A[2 * a][0] = Fr::one();
+    A[2 * a][2] = c2;
+    A[2 * a][4] = Fr::sqr(c2);
+    A[2 * a + 1][1] = Fr::one();
+    A[2 * a + 1][3] = c2;
+  }
+  A[4][0] = Fr::one();
+  for (int j = 1; j < 5; j++) A[4][j] = Fr::mul(A[4][j - 1], c[2]);
+  for (int col = 0; col < 5; col++) {
+    int piv = col;
+    while (piv < 5 && Fr::is_zero(A[piv][col])) piv++;
+    if (piv == 5) return (int)hipErrorInvalidValue;  // the c_k are distinct: cannot happen
+    for (int j = 0; j < 10; j++) std::swap(A[piv][j], A[col][j]);
+    const fe inv = Fr::inv(A[col][col]);
+    for (int j = 0; j < 10; j++) A[col][j] = Fr::mul(A[col][j], inv);
+    for (int r = 0; r < 5; r++) {
+      if (r == col) continue;
+      const fe f = A[r][col];
+      for (int j = 0; j < 10; j++) A[r][j] = Fr::sub(A[r][j], Fr::mul(f, A[col][j]));
+    }
+  }
+  Quot5Const& q = d->q5;
+  for (int jj = 0; jj < 2; jj++)
+    for (int a = 0; a < 2; a++) q.odd[jj][a] = to_internal(A[2 * jj + 1][5 + 2 * a + 1]);
+  for (int jj = 0; jj < 3; jj++)
+    for (int r = 0; r < 5; r++) q.even[jj][r] = to_internal(A[2 * jj][5 + r]);
+  // Mt(Y) = prod_k (Y - c_k)
+  fe mt[6];
+  mt[0] = Fr::one();
+  for (int k = 0; k < 5; k++) {
+    mt[k + 1] = mt[k];
+    for (int j = k; j >= 1; j--) mt[j] = Fr::sub(mt[j - 1], Fr::mul(mt[j], c[k]));
+    mt[0] = Fr::neg(Fr::mul(mt[0], c[k]));
+  }
+  for (int j = 0; j < 5; j++) {
+    q.mt[j] = to_internal(mt[j]);
+    q.d[j] = to_internal(Fr::sub(Fr::one(), mt[j]));
+  }
+  return 0;
+}
 }  // namespace
 
 int ntt3_build_domain(Ntt3Domain* d, uint32_t log_m, hipStream_t stream) {
@@ -903,11 +1023,12 @@ int ntt3_build_domain(Ntt3Domain* d, uint32_t log_m, hipStream_t stream) {
   launch("table_to_internal", table_to_internal, dim3(blocks), dim3(256), 0, stream, d->pre3, (const fe*)d->pre3, N);
   launch("table_to_internal", table_to_internal, dim3((unsigned)((2 * M + 255) / 256)), dim3(256), 0, stream,
          d->tw29_inv, (const fe*)d->tw29_inv, 2 * M);
+  if (log_m >= 1 && (rc = build_quot5(d, g, wN, to_internal, stream))) return rc;
   return (int)hipStreamSynchronize(stream);
 }
 
 void ntt3_free_domain(Ntt3Domain* d) {
-  for (fe** t : {&d->xs_ext, &d->xs29, &d->pre3, &d->tw29_inv, &d->coset_inv_ext}) {
+  for (fe** t : {&d->xs_ext, &d->xs29, &d->pre3, &d->tw29_inv, &d->coset_inv_ext, &d->unscale5}) {
     if (*t) hipFree(*t);
     *t = nullptr;
   }
@@ -961,6 +1082,83 @@ int ntt3_inverse(const Ntt3Domain& d3, const NttDomain& dom_m, const NttSmallTab
   if (rc) return rc;
   launch("ntt3_combine", ntt3_combine, dim3((unsigned)((M + kThreads - 1) / kThreads), count), dim3(kThreads), 0, stream,
          (const fe*)y, data, N, (size_t)0, 1u, M, (const fe*)d3.tw29_inv, d3.w3inv_29, (const fe*)d3.coset_inv_ext, add);
+  return 0;  // launch failures are latched by launch() and reported by take_launch_error()
+}
+
+// ---- five of the six n-cosets -----------------------------------------------------------------------------------------
+int ntt3_forward5(const Ntt3Domain& d3, const NttDomain& dom_m, const NttDomain& dom_h, const NttSmallTables& small,
+                  fe* data, NttIo io, uint32_t count, fe* scratch, hipStream_t stream) {
+  if (dom_m.log_n != d3.log_m || d3.log_m < 5 || dom_h.log_n + 1 != d3.log_m) return (int)hipErrorInvalidValue;
+  const size_t M = (size_t)1 << d3.log_m, nh = M / 2;
+  if (io.src_len > M || io.src_len < nh) return (int)hipErrorInvalidValue;
+  // arrays 2 q + a, a = 0, 1: polynomial q pre-scaled by the powers of s_a, to block a
+  NttIo sub{};
+  sub.src = io.src;
+  sub.src_outer = io.src_outer;
+  sub.src_inner = 0;
+  sub.src_group = 2;
+  sub.src_group2 = io.src_group ? io.src_group : 1;
+  sub.src_inner2 = io.src_inner;
+  sub.src_len = io.src_len;
+  sub.pre_scale = d3.pre3;
+  sub.pre_inner = M;
+  sub.lazy_out = 1;
+  sub.dst_outer = io.dst_outer;
+  sub.dst_inner = M;
+  sub.dst_group = 2;
+  sub.dst_group2 = io.dst_group ? io.dst_group : 1;
+  sub.dst_inner2 = io.dst_inner;
+  int rc = ntt_run(dom_m, small, data, scratch, M, count * 2, 0, 0, stream, &sub);
+  if (rc) return rc;
+  // block 2, even elements: the n-point transform of polynomial q modulo X^n - s_2^n, pre-scaled by the powers of s_2
+  NttIo h{};
+  h.src = io.src;
+  h.src_outer = io.src_outer;
+  h.src_inner = io.src_inner;
+  h.src_group = io.src_group ? io.src_group : 1;
+  h.src_len = io.src_len;
+  h.src_fold = io.src_len > nh ? nh : 0;
+  h.pre_scale = d3.pre3 + 2 * M;
+  h.lazy_out = 1;
+  h.dst_outer = io.dst_outer;
+  h.dst_inner = io.dst_inner;
+  h.dst_group = io.dst_group ? io.dst_group : 1;
+  return ntt_run(dom_h, small, data + 2 * M, scratch, nh, count, 0, 0, stream, &h);
+}
+
+int ntt3_inverse5(const Ntt3Domain& d3, const NttDomain& dom_m, const NttDomain& dom_h, const NttSmallTables& small,
+                  fe* data, uint32_t count, fe* scratch, hipStream_t stream, const fe* top, const fe* add) {
+  if (dom_m.log_n != d3.log_m || d3.log_m < 5 || dom_h.log_n + 1 != d3.log_m || !d3.unscale5 || !top)
+    return (int)hipErrorInvalidValue;
+  const size_t M = (size_t)1 << d3.log_m, N = 3 * M, nh = M / 2;
+  fe* y01 = scratch;
+  fe* y2 = y01 + (size_t)count * 2 * M;
+  fe* sub_scratch = y2 + (size_t)count * nh;
+  NttIo sub{};
+  sub.src = data;
+  sub.src_outer = N;
+  sub.src_inner = M;  // block a of array q
+  sub.src_group = 2;
+  sub.src_len = M;
+  sub.lazy_out = 1;
+  sub.dst_outer = M;
+  sub.dst_inner = 0;
+  sub.dst_group = 1;
+  int rc = ntt_run(dom_m, small, y01, sub_scratch, M, count * 2, 1, 0, stream, &sub);
+  if (rc) return rc;
+  NttIo h{};
+  h.src = data + 2 * M;
+  h.src_outer = N;
+  h.src_inner = 0;
+  h.src_group = 1;
+  h.src_len = nh;
+  h.lazy_out = 1;
+  h.dst_outer = nh;
+  h.dst_inner = 0;
+  h.dst_group = 1;
+  if ((rc = ntt_run(dom_h, small, y2, sub_scratch, nh, count, 1, 0, stream, &h))) return rc;
+  launch("ntt3_combine5", ntt3_combine5, dim3((unsigned)((nh + kThreads - 1) / kThreads), count), dim3(kThreads), 0, stream,
+         (const fe*)y01, (const fe*)y2, data, nh, (const fe*)d3.unscale5, d3.q5, top, add);
   return 0;  // launch failures are latched by launch() and reported by take_launch_error()
 }
 

@@ -83,6 +83,10 @@ struct NttIo {
   // domain's n^-1 - a constant factor of the result rides on the multiplication the transform performs anyway
   int has_post_scalar = 0;
   fe post_scalar = {};
+  // folded input (first pass, contiguous input only): element g of the transform is src[g] * pre[g] +
+  // src[g + src_fold] * pre[g + src_fold], the second term only where g + src_fold < src_len - a polynomial a few
+  // coefficients longer than the transform, reduced modulo X^n - s^n on the way in (0: no fold)
+  size_t src_fold = 0;
 };
 int ntt_run(const NttDomain& dom, const NttSmallTables& small, fe* data, fe* scratch, size_t stride_elems,
             uint32_t count, int dir, int coset, hipStream_t stream, const NttIo* io = nullptr);
@@ -111,6 +115,18 @@ int ntt_plan(uint32_t log_n, uint32_t count, NttPlan* out);  // 0, or hipErrorIn
 // M-point coset transforms of the SAME zero-extended input - no radix-3 stage, no strided access.
 // Inverse (the quotient, up to 3M coefficients): three ordinary inverse transforms of the blocks, then one radix-3
 // stage:  t[k + M b] = 5^-(k + M b) / 3 * (Y0[k] + w3^-b omega_N^-k Y1[k] + w3^-2b omega_N^-2k Y2[k]),  w3 = omega_N^M.
+// Constants of the five-coset inverse, internal form.  With Y = X^n and u = sum_j Y^j u_j(X) (deg u_j < n) the two inverse
+// M-point transforms give, per i < n, E_a = u_0 + c_a^2 u_2 + c_a^4 u_4 and O_a = u_1 + c_a^2 u_3 (a = 0, 1) and the inverse
+// n-point transform of block 2 gives R = sum_j c_2^j u_j: a fixed 5 x 5 system whose inverse splits into
+//   (u_1, u_3) = odd (O_0, O_1),   (u_0, u_2, u_4) = even (E_0, O_0, E_1, O_1, R).
+// mt[j]: coefficients of Mt(Y) = prod_{k<5} (Y - c_k) (monic; t = t_lo + Mt(X^n) h);  d[j] = 1 - mt[j]: the public-input
+// addend kappa PI(X) (1 + Y + ... + Y^5) reduced modulo Mt.
+struct Quot5Const {
+  fe odd[2][2];
+  fe even[3][5];
+  fe mt[5];
+  fe d[5];
+};
 struct Ntt3Domain {
   uint32_t log_m = 0;           // M = 2^log_m, N = 3 M
   fe* xs_ext = nullptr;         // the N points in the order above, arkworks form
@@ -128,6 +144,12 @@ struct Ntt3Domain {
   fe kappa;                     // arkworks form (host)
   fe kappa_n_inv29;             // kappa / n, internal form: NttIo::post_scalar of the n-point inverse transform that
                                 // interpolates such an A from its values
+  // ---- five of the six n-cosets (ntt3_forward5 / ntt3_inverse5) ----
+  // Element e of block a lies on the n-coset k = a + 3 (e mod 2), where x^n = c_k = 5^n omega_6^k; the quotient has
+  // 5n + 8 coefficients, so the cosets k = 0 .. 4 - blocks 0 and 1 and the EVEN elements of block 2, kept compactly:
+  // [M][M][M / 2] - carry it once its top 8 coefficients are known.
+  fe* unscale5 = nullptr;       // [M] s_0^-i, [M] s_1^-i, [M / 2] s_2^-i as arkworks-form integers (internal in, arkworks out)
+  Quot5Const q5;                // the fixed solve and the addends' constants, internal form
 };
 int ntt3_build_domain(Ntt3Domain* d, uint32_t log_m, hipStream_t stream);
 void ntt3_free_domain(Ntt3Domain* d);
@@ -142,6 +164,17 @@ int ntt3_forward(const Ntt3Domain& d3, const NttDomain& dom_m, const NttSmallTab
 // six blocks of M / 2, inside the radix-3 stage.  Null: nothing is added.
 int ntt3_inverse(const Ntt3Domain& d3, const NttDomain& dom_m, const NttSmallTables& small, fe* data, uint32_t count,
                  fe* scratch, hipStream_t stream, const fe* add = nullptr);
+
+// The same pair on five of the six n-cosets (M >= 32).  Forward: blocks 0 and 1 as above, block 2 as ONE M / 2-point
+// coset transform of the polynomial folded modulo X^n - s_2^n (NttIo::src_fold), written to the first M / 2 elements of
+// block 2; the rest of the block is not touched.  dom_h: the 2^(log_m - 1) domain.  scratch: 2 M count elements.
+int ntt3_forward5(const Ntt3Domain& d3, const NttDomain& dom_m, const NttDomain& dom_h, const NttSmallTables& small,
+                  fe* data, NttIo io, uint32_t count, fe* scratch, hipStream_t stream);
+// Inverse in place: data[q * N ..) holds [M][M][M / 2] internal-form evaluations -> all N arkworks-form coefficients,
+// canonical: t = t_lo + Mt(X^n) h with t_lo the interpolant on the five cosets, top[q][8] = h (arkworks form) and zeros
+// above 5n + 8.  add as above: coefficient j n + i takes d_j add[q][i].  scratch: 5 M count elements.
+int ntt3_inverse5(const Ntt3Domain& d3, const NttDomain& dom_m, const NttDomain& dom_h, const NttSmallTables& small,
+                  fe* data, uint32_t count, fe* scratch, hipStream_t stream, const fe* top, const fe* add = nullptr);
 
 // out[i] = internal Montgomery form (x * 2^261, canonical) of the arkworks-form value in[i]
 void ntt_table_to_internal(fe* out, const fe* in, size_t n, hipStream_t stream);

@@ -151,11 +151,12 @@ struct ProveGraphSig {
   // capgpu_plonk_prove_each*: 0 a plain call, 1 an outcome call, 2 one whose witnesses were checked first - the device
   // transcript's segment of an outcome call ends in k_prove_outcomes, which reads the check's verdicts or does not
   int outcomes = 0;
+  bool five = false;  // round 3 on five of the six n-cosets (CAPGPU_QUOT_COSETS): other transforms, other launches
   bool operator==(const ProveGraphSig& o) const {
     return key_uid == o.key_uid && srs == o.srs && P == o.P && num_inputs == o.num_inputs && form == o.form &&
            multi == o.multi && d_wires == o.d_wires && ws == o.ws && msm_ws == o.msm_ws && ntt_scratch == o.ntt_scratch &&
            bases == o.bases && lagrange == o.lagrange && stream == o.stream && overlap == o.overlap && transcript == o.transcript &&
-           tr_stride == o.tr_stride && outcomes == o.outcomes;
+           tr_stride == o.tr_stride && outcomes == o.outcomes && five == o.five;
   }
 };
 struct ProveGraphSet {
@@ -327,6 +328,28 @@ namespace {
 // (`check_circuit_satisfiability`, src/proof/transfer.rs:167-177; mint.rs and freeze.rs likewise).  Here: two launches over
 // the resident witnesses (check_kernels.hpp) against two tables a key derives on its first check.
 
+// the selector values alone (K.chk_mu held): what the gate pass reads - the witness check's, and the row test of the
+// five-coset quotient (prove_run.hpp: r3_body), which needs no index form of sigma
+int key_gate_table_locked(const ProvingKey& K) {
+  if (K.chk_sel) return CAPGPU_OK;
+  hipStream_t s = ctx().stream;
+  const size_t n = K.n;
+  DevTmp<fe> sel;
+  CAP_HIP(sel.alloc((size_t)NS * n));
+  int rc = run_ntt_from(s, K.log_n, K.coef, K.ps, n, sel, n, NS, 0, 0);
+  if (rc) return rc;
+  ntt_table_to_internal(sel, sel, (size_t)NS * n, s);
+  CAP_HIP(hipStreamSynchronize(s));
+  if ((rc = take_launch_error())) return rc;
+  K.chk_sel = sel.p;
+  sel.p = nullptr;
+  return CAPGPU_OK;
+}
+int key_gate_table(const ProvingKey& K) {
+  std::lock_guard<std::mutex> lk(K.chk_mu);
+  return key_gate_table_locked(K);
+}
+
 // selector values on the domain and the index form of sigma, on the current context's stream; synchronous
 int key_check_tables(const ProvingKey& K) {
   std::lock_guard<std::mutex> lk(K.chk_mu);
@@ -336,18 +359,11 @@ int key_check_tables(const ProvingKey& K) {
   }
   Context& c = ctx();
   hipStream_t s = c.stream;
-  const size_t n = K.n, cells = (size_t)NW * n;
-  DevTmp<fe> sel;
+  const size_t cells = (size_t)NW * K.n;
   DevTmp<uint32_t> perm, bad;
-  CAP_HIP(sel.alloc((size_t)NS * n));
-  int rc = run_ntt_from(s, K.log_n, K.coef, K.ps, n, sel, n, NS, 0, 0);
+  int rc = key_gate_table_locked(K);
   if (rc) return rc;
-  ntt_table_to_internal(sel, sel, (size_t)NS * n, s);
   if (K.chk_perm) {  // a key that knows its variable table has the index form already: no discrete logarithms
-    CAP_HIP(hipStreamSynchronize(s));
-    if ((rc = take_launch_error())) return rc;
-    K.chk_sel = sel.p;
-    sel.p = nullptr;
     K.chk_rc = CAPGPU_OK;
     return CAPGPU_OK;
   }
@@ -377,9 +393,7 @@ int key_check_tables(const ProvingKey& K) {
     K.chk_rc = CAPGPU_ERR_INVALID_ARG;
     return K.chk_rc;
   }
-  K.chk_sel = sel.p;
   K.chk_perm = perm.p;
-  sel.p = nullptr;
   perm.p = nullptr;
   K.chk_rc = CAPGPU_OK;
   return CAPGPU_OK;
@@ -531,6 +545,9 @@ ProveNeeds prove_needs(const ProvePlan& pl, const ProvingKey& K) {
 int prove_planned(Context& c, const ProvingKey& K, uint32_t P, const ProveRequest& rq, const ProvePlan& pl, ProveRun& run) {
   const size_t num_inputs = rq.num_inputs;
   int rc;
+  if (pl.five)  // the selector values the row test reads, once per key
+    for (uint32_t p = 0; p < P && (rq.keys || p == 0); p++)
+      if ((rc = key_gate_table(rq.keys ? *(*rq.keys)[p] : K))) return rc;
   // workspace
   if ((rc = scratch_reserve(c.prove_ws, carve(nullptr, K, P, num_inputs, pl.coeffs, pl.tr_stride).total))) return rc;
   run.w = carve(c.prove_ws.p, K, P, num_inputs, pl.coeffs, pl.tr_stride);
@@ -558,6 +575,7 @@ int prove_planned(Context& c, const ProvingKey& K, uint32_t P, const ProveReques
     sig.transcript = pl.dev_tr ? CAPGPU_TRANSCRIPT_DEVICE : CAPGPU_TRANSCRIPT_HOST;
     sig.tr_stride = pl.tr_stride;
     sig.outcomes = rq.outcomes ? (run.faults ? 2 : 1) : 0;
+    sig.five = pl.five;
     run.gs = graph_set_for(c, sig);
   }
   return pl.dev_tr ? run.run_device_transcript() : run.run_host_transcript();

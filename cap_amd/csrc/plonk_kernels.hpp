@@ -308,19 +308,24 @@ __global__ __launch_bounds__(kThreads) void k_quotient(const fe* __restrict__ pk
                                                        const fe* __restrict__ cos, const fe* __restrict__ xs,
                                                        const fe* __restrict__ inv_nx1,
                                                        const Chal* __restrict__ chal, QuotConst qc, size_t m,
-                                                       uint32_t only_unfoldable, fe* __restrict__ t_out) {
+                                                       uint32_t only_unfoldable, uint32_t five,
+                                                       fe* __restrict__ t_out) {
   using F = Fr29;
   // grid (proofs, tiles): the proofs of one tile run together, so the 18 shared selector / sigma tiles are read from
   // HBM once per tile and served from L2 to the other proofs of the batch
+  // five: the points are blocks 0 and 1 and the even elements of block 2, kept compactly - [M][M][M / 2] inside the same
+  // strides (ntt.hpp: ntt3_forward5); the tables of the whole domain are read at `it`, the point's index there
   size_t i = (size_t)blockIdx.y * blockDim.x + threadIdx.x;
-  if (i >= m) return;
+  if (i >= (five ? m - m / 6 : m)) return;
   const uint32_t p = blockIdx.x;
   if (FOLD ? !fe_nonzero(chal[p].beta_inv) : (only_unfoldable && fe_nonzero(chal[p].beta_inv))) return;
   if (pkc_of) pkc = pkc_of[p];
   const uint32_t mm = (uint32_t)(m / 3);                                  // block length M (uniform: scalar unit)
   const uint32_t blk = (i >= mm ? 1u : 0u) + (i >= 2 * (size_t)mm ? 1u : 0u);  // which of the three cosets
   const fe* c = cos + (size_t)p * 6 * m;
-  auto sel = [&](int s) { return F::load(pkc[(size_t)s * m + i]); };
+  const bool half = five && blk == 2;
+  const size_t it = half ? 2 * i - 2 * (size_t)mm : i;
+  auto sel = [&](int s) { return F::load(pkc[(size_t)s * m + it]); };
   fl w0 = F::load(c[i]), w1 = F::load(c[m + i]), w2 = F::load(c[2 * m + i]), w3 = F::load(c[3 * m + i]),
      w4 = F::load(c[4 * m + i]);
   // gate constraint (spec eq. (1); selector order q_lc, q_mul, q_hash, q_o, q_c, q_ecc)
@@ -359,7 +364,7 @@ __global__ __launch_bounds__(kThreads) void k_quotient(const fe* __restrict__ pk
   const fl zx = F::load(c[5 * m + i]);
   // index a M + k (ntt.hpp): x * omega_n = x * omega_M^2 is two steps further inside the same block of M = m / 3
   const uint32_t k1 = (uint32_t)i - blk * mm;
-  const size_t inext = (size_t)blk * mm + ((k1 + 2) & (mm - 1));
+  const size_t inext = (size_t)blk * mm + (half ? (k1 + 1) & (mm / 2 - 1) : (k1 + 2) & (mm - 1));
   if constexpr (FOLD) {
     const fl beta_inv = F::load(chal[p].beta_inv);
     // w_j (a stored value: normalized, < 2^256) + gamma (canonical) is a lazy sum of two - limbs < 2^30, what a product
@@ -367,7 +372,7 @@ __global__ __launch_bounds__(kThreads) void k_quotient(const fe* __restrict__ pk
     // < 2^256) again a lazy sum of two that feeds one product: no carry is propagated anywhere in this block
     fl a = zx, b = F::load(c[5 * m + inext]);
     fl u = F::mul(F::add(w0, gamma), beta_inv);
-    a = F::mul(a, F::add(u, F::load(xs[i])));  // the point itself (internal form): s_a * omega_M^k at index a * M + k
+    a = F::mul(a, F::add(u, F::load(xs[it])));  // the point itself (internal form): s_a * omega_M^k at index a * M + k
     b = F::mul(b, F::add(u, sel(NS + 0)));
     u = F::mul(F::add(w1, gamma), beta_inv);
     a = F::mul(a, F::add(u, sel(NS + NW + 0)));
@@ -385,7 +390,7 @@ __global__ __launch_bounds__(kThreads) void k_quotient(const fe* __restrict__ pk
     total = F::normalize(F::add(total, F::mul(F::load(chal[p].alpha_beta5), F::sub(a, b))));
   } else {
     const fl beta = F::load(chal[p].beta);
-    fl x = F::load(xs[i]);  // the point itself (internal form): s_a * omega_M^k at index a * M + k
+    fl x = F::load(xs[it]);  // the point itself (internal form): s_a * omega_M^k at index a * M + k
     fl bx = F::mul(beta, x);
     fl a = zx, b = F::load(c[5 * m + inext]);
     fl wg = F::add(w0, gamma);
@@ -408,8 +413,8 @@ __global__ __launch_bounds__(kThreads) void k_quotient(const fe* __restrict__ pk
   // (gate + alpha * perm) / Z_H  +  alpha^2 (z - 1) / (n (x - 1)) : two products, one reduction
   fl l1a = F::mul(F::load(chal[p].alpha2), F::sub(zx, F::one()));
   // x^n depends on the block and on the parity of k only: (s_a omega_M^k)^n = s_a^n (-1)^k = (5 omega_N^(3k + a))^n
-  const uint32_t zi = 3 * (((uint32_t)i - blk * mm) & 1) + blk;  // < 6
-  fl r = F::mul_add_mul(total, F::load(qc.zh_inv[zi]), l1a, F::load(inv_nx1[i]));
+  const uint32_t zi = 3 * (half ? 0u : ((uint32_t)i - blk * mm) & 1) + blk;  // < 6
+  fl r = F::mul_add_mul(total, F::load(qc.zh_inv[zi]), l1a, F::load(inv_nx1[it]));
   t_out[(size_t)p * m + i] = F::store(r);
 }
 
@@ -432,6 +437,81 @@ __global__ __launch_bounds__(kThreads) void k_check_degree(const fe* __restrict_
     if (zero) atomicOr(&flags[p], 2u);
   } else if (!zero) {
     atomicOr(&flags[p], 1u);
+  }
+}
+
+// ---- five-coset quotient: the top 8 coefficients h = t[5n .. 5n + 8) from the polynomials in hand --------------------
+// t (X^n - 1) = N and t has nothing at or above degree 6n, so h_i = N_(6n+i).  Only two parts of the numerator reach that
+// degree (n >= 16):  alpha [ z prod_j (w_j + beta k_j X + gamma) - z(omega X) prod_j (w_j + beta sigma_j + gamma) ], of
+// degree 6n + 7, and sum_i q_hash_i w_i^5 + q_ecc w_0 w_1 w_2 w_3 w_4, of degree 6n + 4.  Each factor enters through its
+// top coefficients, written as a series from the top down - w_j: n + 1 - k, z: n + 2 - k, sigma_j and the selectors:
+// n - 1 - k - and the products are products of series truncated at 8 terms.  beta k_j X and gamma do not reach.
+// One workgroup of 64 lanes per proof: a series product is 36 field products, one per lane, and a sum per term.
+// Saturated field, arkworks' form in and out.
+__device__ __noinline__ void series_mul8(fe* dst, const fe* x, const fe* y, fe* prod) {
+  const uint32_t t = threadIdx.x, a = t >> 3, b = t & 7;
+  __syncthreads();  // the operands are written, prod is free
+  if (a + b < 8) prod[t] = Fr::mul(x[a], y[b]);
+  __syncthreads();
+  fe s = Fr::zero();
+  if (t < 8) {
+    s = prod[t];
+    for (uint32_t k = 1; k <= t; k++) s = Fr::add(s, prod[k * 8 + t - k]);
+  }
+  __syncthreads();  // (dst may be one of the operands)
+  if (t < 8) dst[t] = s;
+  __syncthreads();
+}
+// coef: the key's 18 polynomials [18][ps] (coef_of: proof p's own key), tw_n: omega_n^e, top: [P][8]
+__global__ __launch_bounds__(64) void k_quotient_top(const fe* __restrict__ wpoly /*[P][5][ps]*/,
+                                                     const fe* __restrict__ zpoly /*[P][ps]*/,
+                                                     const fe* __restrict__ coef, const fe* const* __restrict__ coef_of,
+                                                     const fe* __restrict__ tw_n, const Chal* __restrict__ chal, size_t n,
+                                                     size_t ps, fe* __restrict__ top) {
+  __shared__ fe W[NW][8], B[NW][8], sa[8], sb[8], sc[8], prod[64];
+  const uint32_t p = blockIdx.x, t = threadIdx.x;
+  if (coef_of) coef = coef_of[p];
+  const fe* wp = wpoly + (size_t)p * NW * ps;
+  const fe* zp = zpoly + (size_t)p * ps;
+  if (t < NW * 8) {
+    const uint32_t j = t >> 3, k = t & 7;
+    const fe w = wp[(size_t)j * ps + n + 1 - k];
+    W[j][k] = w;
+    B[j][k] = k >= 2 ? Fr::add(w, Fr::mul(chal[p].beta, coef[(size_t)(NS + j) * ps + n + 1 - k])) : w;
+  }
+  fe h = Fr::zero();  // lane t < 8: h_t
+  // gate terms: series index k <-> degree 6n + 4 - k <-> h_(4-k)
+  auto take_gate = [&](const fe* s) {
+    if (t < 5) h = Fr::add(h, s[4 - t]);
+  };
+  for (int i = 0; i < 4; i++) {  // q_hash_i w_i^5
+    series_mul8(sa, W[i], W[i], prod);
+    series_mul8(sa, sa, sa, prod);
+    series_mul8(sa, sa, W[i], prod);
+    if (t < 8) sb[t] = coef[(size_t)(6 + i) * ps + n - 1 - t];
+    series_mul8(sc, sa, sb, prod);
+    take_gate(sc);
+  }
+  series_mul8(sa, W[0], W[1], prod);
+  for (int j = 2; j < NW; j++) series_mul8(sa, sa, W[j], prod);  // sa = prod_j w_j
+  if (t < 8) sb[t] = coef[(size_t)12 * ps + n - 1 - t];          // q_ecc
+  series_mul8(sc, sa, sb, prod);
+  take_gate(sc);
+  // permutation terms: series index k <-> degree 6n + 7 - k <-> h_(7-k)
+  if (t < 8) sb[t] = zp[n + 2 - t];
+  series_mul8(sc, sa, sb, prod);
+  fe perm = Fr::zero();
+  if (t < 8) perm = sc[7 - t];
+  series_mul8(sa, B[0], B[1], prod);
+  for (int j = 2; j < NW; j++) series_mul8(sa, sa, B[j], prod);
+  if (t < 8) {  // z(omega X): coefficient c times omega^c (omega^n = 1)
+    const size_t c = n + 2 - t;
+    sb[t] = Fr::mul(zp[c], tw_n[c >= n ? c - n : c]);
+  }
+  series_mul8(sc, sa, sb, prod);
+  if (t < 8) {
+    perm = Fr::sub(perm, sc[7 - t]);
+    top[(size_t)p * 8 + t] = Fr::add(h, Fr::mul(chal[p].alpha, perm));
   }
 }
 

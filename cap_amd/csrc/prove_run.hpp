@@ -47,7 +47,11 @@ void scan_exclusive(hipStream_t s, const fe* in, fe* out, size_t len, size_t str
 // (capgpu_plonk_reserve sizes a context ahead from what a proving call WOULD request).
 inline size_t ntt_scratch_inplace(size_t stride, size_t count) { return sizeof(fe) * stride * count; }
 inline size_t ntt_scratch_from(uint32_t log_n, size_t count) { return (sizeof(fe) << log_n) * count; }
-inline size_t ntt3_scratch(uint32_t log_mm, size_t count) { return (sizeof(fe) << log_mm) * 6 * count; }
+// (forward: count * 3 sub-transforms of M elements; inverse: their outputs and as much again for the passes in between.
+// The five-coset forms - `five` - run 2 M + M / 2 per array: forward 2 M for the passes, inverse 2.5 M outputs + 2 M)
+inline size_t ntt3_scratch(uint32_t log_mm, size_t count, bool five = false) {
+  return five ? (sizeof(fe) << log_mm) / 2 * 9 * count : (sizeof(fe) << log_mm) * 6 * count;
+}
 // ... of Context::stage_b for `cnt` host-resident witnesses on a domain of n points
 inline size_t wires_stage_bytes(size_t cnt, size_t n) { return sizeof(fe) * cnt * NW * n; }
 
@@ -108,6 +112,29 @@ int run_ntt3_fwd(hipStream_t s, uint32_t log_mm, fe* data, uint32_t count, const
   if ((rc = scratch_reserve(c.ntt_scratch, ntt3_scratch(log_mm, count)))) return rc;
   rc = ntt3_forward(*d3, *dm, c.small, data, io, count, (fe*)c.ntt_scratch.p, s);
   if (rc) return hip_fail((hipError_t)rc, "ntt3_forward");
+  return CAPGPU_OK;
+}
+// the same on five of the six n-cosets (ntt.hpp: ntt3_forward5 / ntt3_inverse5)
+int run_ntt3_fwd5(hipStream_t s, uint32_t log_mm, fe* data, uint32_t count, const NttIo& io) {
+  Context& c = ctx();
+  const Ntt3Domain* d3 = nullptr;
+  const NttDomain *dm = nullptr, *dh = nullptr;
+  int rc = quot_domains(log_mm, &d3, &dm);
+  if (rc || (rc = get_domain(log_mm - 1, &dh))) return rc;
+  if ((rc = scratch_reserve(c.ntt_scratch, ntt3_scratch(log_mm, count, true)))) return rc;
+  rc = ntt3_forward5(*d3, *dm, *dh, c.small, data, io, count, (fe*)c.ntt_scratch.p, s);
+  if (rc) return hip_fail((hipError_t)rc, "ntt3_forward5");
+  return CAPGPU_OK;
+}
+int run_ntt3_inv5(hipStream_t s, uint32_t log_mm, fe* data, uint32_t count, const fe* top, const fe* add) {
+  Context& c = ctx();
+  const Ntt3Domain* d3 = nullptr;
+  const NttDomain *dm = nullptr, *dh = nullptr;
+  int rc = quot_domains(log_mm, &d3, &dm);
+  if (rc || (rc = get_domain(log_mm - 1, &dh))) return rc;
+  if ((rc = scratch_reserve(c.ntt_scratch, ntt3_scratch(log_mm, count, true)))) return rc;
+  rc = ntt3_inverse5(*d3, *dm, *dh, c.small, data, count, (fe*)c.ntt_scratch.p, s, top, add);
+  if (rc) return hip_fail((hipError_t)rc, "ntt3_inverse5");
   return CAPGPU_OK;
 }
 // add: see ntt3_inverse
@@ -172,7 +199,11 @@ struct BatchWs {
   g1_jac* comms;
   EvalDesc* edesc;
   LinTerm* terms;
-  const fe** key_ptrs;  // [2][P]: sigma evaluations / coset columns of every proof's key (mixed-key batches)
+  const fe** key_ptrs;  // [3][P]: sigma evaluations / coset columns / coefficients of every proof's key (mixed-key batches)
+  // the five-coset quotient: its top coefficients [P][8] (k_quotient_top) and the row test's keys and verdicts (r3_body)
+  fe* top;
+  CheckKey* chk_keys;
+  CheckOut* chk_out;
   // device transcript only (capgpu_plonk_set_transcript): the proofs in ABI layout, zeta, and the transcript's bytes
   uint8_t *d_proofs, *tr_state, *tr_pre, *tr_app;
   uint32_t* tr_pre_len;
@@ -223,7 +254,10 @@ BatchWs carve(void* base, const ProvingKey& K, uint32_t P, size_t num_inputs, bo
   w.comms = c.take<g1_jac>((size_t)P * 5);
   w.edesc = c.take<EvalDesc>((size_t)P * 10);
   w.terms = c.take<LinTerm>((size_t)P * kLinTerms);
-  w.key_ptrs = c.take<const fe*>((size_t)P * 2);
+  w.key_ptrs = c.take<const fe*>((size_t)P * 3);
+  w.top = c.take<fe>((size_t)P * 8);
+  w.chk_keys = c.take<CheckKey>(P);
+  w.chk_out = c.take<CheckOut>(P);
   if (tr_stride) {  // (last: the host mode's layout is a prefix of this one)
     w.d_proofs = c.take<uint8_t>((size_t)P * td::kPrBytes);
     w.zeta = c.take<fe>(P);
@@ -255,6 +289,13 @@ int compute_pk_kx(hipStream_t s, const ProvingKey& K, fe* dst) {
 // of a proof with beta = 0 (the folded launch leaves them out, the direct launch behind it takes them) - for tests.
 int quotient_fold() {
   return env_int("CAPGPU_QUOT_FOLD", 1, 0, 2);
+}
+// CAPGPU_QUOT_COSETS (read per call): 5, the default - round 3 evaluates on five of the six n-cosets of the quotient domain
+// and takes the quotient's top 8 coefficients from the polynomials; 6 - all six, the top coefficients
+// from the interpolation (A/B in one build, tests).  Domains below n = 16 and keys of the reference schedule
+// (ProvingKey::recompute) take six whatever it says.
+int quotient_cosets() {
+  return env_int("CAPGPU_QUOT_COSETS", 5, 5, 6);
 }
 
 // Round 1's wire commitments: from the wire polynomials' coefficients (jf-plonk's way: KZG10::commit under
@@ -446,6 +487,7 @@ struct ProvePlan {
   bool overlap = false;
   hipStream_t s2 = nullptr;
   bool graphs = false;  // small batches replay their kernel segments as hipGraphs (see ProveGraphSet)
+  bool five = false;    // round 3 on five of the six n-cosets (quotient_cosets)
   const MsmBases* B = nullptr;
   const MsmBases* Lag = nullptr;  // the Lagrange-form commit key rounds 1 and 2 commit on (null: from coefficients)
   const MsmBases& wire_key() const { return Lag ? *Lag : *B; }
@@ -481,6 +523,7 @@ int make_plan(Context& c, const ProvingKey& K, uint32_t P, int form, bool host, 
     if (!sizing) trace("pb_lagrange_fallback", c.slot, rc);
   }
   pl.dev_tr = transcript_mode() == CAPGPU_TRANSCRIPT_DEVICE && !comm_shard_prover();
+  pl.five = quotient_cosets() == 5 && K.log_n >= 4 && !K.recompute;
   if (pl.dev_tr) {
     if (longest_prefix > (1u << 30)) {
       set_error("capgpu_plonk_prove: transcript init message of %zu bytes", longest_prefix);
@@ -581,6 +624,8 @@ struct ProveRun {
   std::vector<const fe*> key_ptrs;
   const fe* const* sig_of = nullptr;
   const fe* const* pkc_of = nullptr;
+  const fe* const* coef_of = nullptr;
+  std::vector<CheckKey> chk_keys;
   std::vector<SolidityTranscript> tr;  // host transcript only
   // Results the host needs between the rounds come back into PINNED memory of the context: a device-to-host copy into
   // pageable memory makes the runtime wait for the stream on the host first and copy through a staging buffer of its own
@@ -742,14 +787,22 @@ struct ProveRun {
     if (num_inputs)
       CAP_HIP(hipMemcpyAsync(w.d_pub, pub_inputs, sizeof(fe) * P * num_inputs, hipMemcpyHostToDevice, s));
     if (rq.keys) {
-      key_ptrs.resize((size_t)2 * P);
+      key_ptrs.resize((size_t)3 * P);
       for (uint32_t p = 0; p < P; p++) {
         key_ptrs[p] = key_of(p).sig_eval;
         key_ptrs[P + p] = key_of(p).pk_coset;
+        key_ptrs[2 * P + p] = key_of(p).coef;
       }
       CAP_HIP(hipMemcpyAsync(w.key_ptrs, key_ptrs.data(), sizeof(const fe*) * key_ptrs.size(), hipMemcpyHostToDevice, s));
       sig_of = w.key_ptrs;
       pkc_of = w.key_ptrs + P;
+      coef_of = w.key_ptrs + 2 * P;
+    }
+    if (pl.five) {  // the row test's keys (prove_planned has built the selector values of every key)
+      chk_keys.resize(P);
+      for (uint32_t p = 0; p < P; p++) chk_keys[p] = CheckKey{key_of(p).chk_sel, nullptr, (uint32_t)key_of(p).num_inputs, 0};
+      CAP_HIP(hipMemcpyAsync(w.chk_keys, chk_keys.data(), sizeof(CheckKey) * P, hipMemcpyHostToDevice, s));
+      CAP_HIP(hipMemsetAsync(w.chk_out, 0xff, sizeof(CheckOut) * P, s));  // first = kNoFault
     }
     CAP_HIP(hipMemcpyAsync(w.d_blind, rq.blinders, sizeof(fe) * P * 13, hipMemcpyHostToDevice, s));
     CAP_HIP(hipMemsetAsync(w.flags, 0, sizeof(uint32_t) * P, s));
@@ -873,25 +926,28 @@ struct ProveRun {
   // round 3's coset evaluations of the wire polynomials (on the 6n quotient domain, straight from their coefficient
   // arrays: the transform zero-extends them) depend on nothing the transcript still has to produce.  w.coset: [P][6][m],
   // the wires at 0..4, z at 5.
+  // (five cosets: [M][M][M / 2] at the head of every array of m)
   int r3_wire_cosets(hipStream_t st) {
-    return run_ntt3_fwd(st, K.log_m, w.coset, P * NW, NttIo{w.wpoly, NW * ps, ps, n + 2, NW, 6 * m, m, NW});
+    const NttIo io{w.wpoly, NW * ps, ps, n + 2, NW, 6 * m, m, NW};
+    return pl.five ? run_ntt3_fwd5(st, K.log_m, w.coset, P * NW, io) : run_ntt3_fwd(st, K.log_m, w.coset, P * NW, io);
   }
   // the commitment to z and - independent of it - z's coset evaluations for round 3: one after the other (the second while
   // the host hashes), or, for the small batches of `overlap`, side by side on the two streams
   int z_cosets(hipStream_t st) {
-    return run_ntt3_fwd(st, K.log_m, w.coset + 5 * m, P, NttIo{w.zpoly, ps, 0, n + 3, 1, 6 * m, 0, 1});
+    const NttIo io{w.zpoly, ps, 0, n + 3, 1, 6 * m, 0, 1};
+    return pl.five ? run_ntt3_fwd5(st, K.log_m, w.coset + 5 * m, P, io) : run_ntt3_fwd(st, K.log_m, w.coset + 5 * m, P, io);
   }
   // (r3_wire_cosets and z_cosets)
-  static void cosets_needs(const ProvePlan&, const ProvingKey& K, uint32_t cnt, ProveNeeds& nd) {
-    nd.ntt(ntt3_scratch(K.log_m, (size_t)cnt * NW));
-    nd.ntt(ntt3_scratch(K.log_m, cnt));
+  static void cosets_needs(const ProvePlan& pl, const ProvingKey& K, uint32_t cnt, ProveNeeds& nd) {
+    nd.ntt(ntt3_scratch(K.log_m, (size_t)cnt * NW, pl.five));
+    nd.ntt(ntt3_scratch(K.log_m, cnt, pl.five));
   }
   int r1_overlapped() {
     int r;
     const hipStream_t s2 = pl.s2;
     // every transform below shares c.ntt_scratch: those of the side stream run in its order, the one in front of the
     // fork before them.  The largest size is reserved now - a growth later would free a buffer still in use.
-    if ((r = scratch_reserve(c.ntt_scratch, ntt3_scratch(K.log_m, (size_t)P * NW)))) return r;
+    if ((r = scratch_reserve(c.ntt_scratch, ntt3_scratch(K.log_m, (size_t)P * NW, pl.five)))) return r;
     auto interpolate_and_blind = [&](hipStream_t st) -> int {
       int q = CAPGPU_OK;
       if (pl.coeffs) pad_copy(st, w.wpoly, ps, 0, d_wires, n, 0, 1, P * NW, n, n);
@@ -917,7 +973,7 @@ struct ProveRun {
     return CAPGPU_OK;
   }
   static void r1_overlapped_needs(const ProvePlan& pl, const ProvingKey& K, uint32_t cnt, ProveNeeds& nd) {
-    if (pl.overlap) nd.ntt(ntt3_scratch(K.log_m, (size_t)cnt * NW));  // reserved first, the largest
+    if (pl.overlap) nd.ntt(ntt3_scratch(K.log_m, (size_t)cnt * NW, pl.five));  // reserved first, the largest
   }
   int r1_body() {
     if (pl.overlap) return r1_overlapped();
@@ -998,18 +1054,35 @@ struct ProveRun {
     const int fold = quotient_fold();
     if (fold == 2)
       CAP_HIP(hipMemset2DAsync(&w.chal29[0].beta_inv, sizeof(Chal), 0, sizeof(fe), P, s));
+    // five cosets: 5n points per proof; the key's columns and the domain's tables are those of the whole domain, read at
+    // every other element of block 2 (k_quotient: `it`)
+    const uint32_t five = pl.five ? 1u : 0u;
+    const size_t pts = pl.five ? 5 * n : m;
     if (fold)
-      launch("k_quotient", k_quotient<true>, dim3(P, cdiv(m, kThreads)), dim3(kThreads), 0, s, pkc, pkc_of,
-             (const fe*)w.coset, (const fe*)dom_q->xs29, (const fe*)K.inv_nx1, (const Chal*)w.chal29, K.qc29, m, 1u, w.t);
+      launch("k_quotient", k_quotient<true>, dim3(P, cdiv(pts, kThreads)), dim3(kThreads), 0, s, pkc, pkc_of,
+             (const fe*)w.coset, (const fe*)dom_q->xs29, (const fe*)K.inv_nx1, (const Chal*)w.chal29, K.qc29, m, 1u, five,
+             w.t);
     // the direct form: for every proof (fold = 0), or behind the folded launch for the proofs it left out - beta = 0.
     // The host transcript knows whether there is one; the device transcript does not, and its launch is P x m / 256
     // workgroups that load one word and leave.
     if (!fold || fold == 2 || beta_zero_possible)
-      launch("k_quotient_direct", k_quotient<false>, dim3(P, cdiv(m, kThreads)), dim3(kThreads), 0, s,
+      launch("k_quotient_direct", k_quotient<false>, dim3(P, cdiv(pts, kThreads)), dim3(kThreads), 0, s,
              pkc, pkc_of, (const fe*)w.coset, (const fe*)dom_q->xs29, (const fe*)K.inv_nx1, (const Chal*)w.chal29, K.qc29, m,
-             fold ? 1u : 0u, w.t);
+             fold ? 1u : 0u, five, w.t);
     // k_quotient leaves the public-input term out; it arrives here as coefficients (pi_fold), before the degree check
-    if ((r = run_ntt3_inv(s, K.log_m, w.t, P, w.pi))) return r;
+    if (pl.five) {
+      // the top 8 coefficients from the polynomials; then what the sixth coset used to witness - that the numerator is
+      // divisible by Z_H at all - is tested on the rows themselves (k_rows_verdict): bit 1 of the flags, as before
+      launch("k_quotient_top", k_quotient_top, dim3(P), dim3(64), 0, s, (const fe*)w.wpoly, (const fe*)w.zpoly,
+             (const fe*)K.coef, coef_of, (const fe*)dom_n->tw_fwd, (const Chal*)w.chal, n, ps, w.top);
+      launch("k_check_gates", k_check_gates, dim3(cdiv(n, kThreads), P), dim3(kThreads), 0, s,
+             pl.coeffs ? (const fe*)w.wev : d_wires, (const fe*)w.d_pub, num_inputs, (const CheckKey*)w.chk_keys, n, w.chk_out);
+      launch("k_rows_verdict", k_rows_verdict, dim3(cdiv(P, 64)), dim3(64), 0, s, (const CheckOut*)w.chk_out,
+             (const fe*)w.pre, (const fe*)w.num, (const fe*)w.sfx, (const fe*)w.den, n, w.flags, P);
+      if ((r = run_ntt3_inv5(s, K.log_m, w.t, P, w.top, w.pi))) return r;
+    } else if ((r = run_ntt3_inv(s, K.log_m, w.t, P, w.pi))) {
+      return r;
+    }
     {
       size_t lo = NW * (n + 1) + 3;  // first index that must be zero: degree is exactly 5(n+1)+2
       launch("k_check_degree", k_check_degree, dim3(cdiv(m - (lo - 1), kThreads), P), dim3(kThreads), 0, s,
@@ -1019,7 +1092,7 @@ struct ProveRun {
   }
   static void r3_needs(const ProvePlan& pl, const ProvingKey& K, uint32_t cnt, ProveNeeds& nd) {
     if (K.recompute) nd.ntt(ntt3_scratch(K.log_m, 18));
-    nd.ntt(ntt3_scratch(K.log_m, cnt));
+    nd.ntt(ntt3_scratch(K.log_m, cnt, pl.five));
     nd.msm(*pl.B, K.n + 2, cnt * NW);
   }
 
