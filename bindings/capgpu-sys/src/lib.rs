@@ -176,6 +176,32 @@ pub struct capgpu_prove_outcome {
     pub fault: capgpu_witness_fault,
 }
 
+/// `capgpu_notes_group`: one group of a `capgpu_plonk_prove_notes*` call - the notes whose keys share domain size and SRS
+/// (32 bytes).  `first`: its lowest note index; `run_order` 0 starts first.
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug, PartialEq, Eq)]
+pub struct capgpu_notes_group {
+    pub srs_handle: u64,
+    pub domain_size: u64,
+    pub count: u32,
+    pub first: u32,
+    pub max_inputs: u32,
+    pub run_order: u32,
+}
+
+/// `capgpu_notes_stats`: process-wide counters of the notes calls since `capgpu_init` (56 bytes).
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug, PartialEq, Eq)]
+pub struct capgpu_notes_stats {
+    pub calls: u64,
+    pub groups: u64,
+    pub groups_dealt: u64,
+    pub contexts_dealt: u64,
+    pub dev_groups_direct: u64,
+    pub dev_groups_gathered: u64,
+    pub rows_gathered: u64,
+}
+
 /// `flags` of `capgpu_srs_check`: on a structure fault, find the first bad link by bisection.
 pub const CAPGPU_SRS_CHECK_LOCATE: u32 = 1;
 
@@ -421,6 +447,25 @@ extern "C" {
                                          proofs_out: *mut capgpu_proof, outcomes_out: *mut capgpu_prove_outcome,
                                          ticket_out: *mut u64) -> c_int;
     pub fn capgpu_prove_outcome_text(outcome: *const capgpu_prove_outcome, buf: *mut c_char, cap: usize) -> c_int;
+    // ---- a Vec of notes whose keys have several domain sizes (or SRS) in one call
+    pub fn capgpu_plonk_prove_notes(pk_handles: *const u64, count: c_int, wires: *const *const u64, pub_inputs: *const u64,
+                                    num_inputs: usize, ext_msgs: *const *const u8, ext_msg_lens: *const usize,
+                                    blinders: *const u64, input_form: c_int, proofs_out: *mut capgpu_proof,
+                                    outcomes_out: *mut capgpu_prove_outcome) -> c_int;
+    pub fn capgpu_plonk_prove_notes_dev(pk_handles: *const u64, count: c_int, d_wires: *const c_void,
+                                        wire_offsets: *const u64, pub_inputs: *const u64, num_inputs: usize,
+                                        ext_msgs: *const *const u8, ext_msg_lens: *const usize, blinders: *const u64,
+                                        input_form: c_int, proofs_out: *mut capgpu_proof,
+                                        outcomes_out: *mut capgpu_prove_outcome) -> c_int;
+    pub fn capgpu_plonk_prove_notes_async(pk_handles: *const u64, count: c_int, wires: *const *const u64,
+                                          pub_inputs: *const u64, num_inputs: usize, ext_msgs: *const *const u8,
+                                          ext_msg_lens: *const usize, blinders: *const u64, input_form: c_int,
+                                          proofs_out: *mut capgpu_proof, outcomes_out: *mut capgpu_prove_outcome,
+                                          ticket_out: *mut u64) -> c_int;
+    pub fn capgpu_plonk_notes_plan(pk_handles: *const u64, count: c_int, groups_out: *mut capgpu_notes_group, cap: usize,
+                                   num_groups_out: *mut usize, group_of_out: *mut u32) -> c_int;
+    pub fn capgpu_plonk_reserve_notes(pk_handles: *const u64, count: c_int, input_form: c_int, slot: c_int) -> c_int;
+    pub fn capgpu_plonk_notes_stats(out: *mut capgpu_notes_stats) -> c_int;
     // ---- batch compaction of the outcome calls: witnesses the check refused leave the batch before round 1
     pub fn capgpu_plonk_set_compaction(on: c_int) -> c_int;
     pub fn capgpu_plonk_get_compaction(on_out: *mut c_int) -> c_int;
@@ -1006,6 +1051,42 @@ impl ProvingKey {
     pub fn handle(&self) -> u64 {
         self.handle
     }
+}
+/// One note of `prove_notes`: its key, its own witness block (5 n elements, or - `CAPGPU_INPUT_VARS` - the key's num_vars
+/// values), the public inputs of ITS key, its transcript message and its blinders.
+pub struct Note<'a> {
+    pub key: &'a ProvingKey,
+    pub wires: &'a [[u64; 4]],
+    pub pub_inputs: &'a [[u64; 4]],
+    pub ext_msg: &'a [u8],
+    pub blinders: &'a [[u64; 4]; 13],
+}
+/// The reference's `Vec<TransactionNote>` of transfers, mints and freezes - keys of SEVERAL domain sizes - proved in ONE
+/// call (`capgpu_plonk_prove_notes`): every note gets a `Result` of its own, bit for bit what `ProvingKey::prove_each`
+/// makes of the notes of its group (same domain size and SRS) alone.  The witness blocks are read where they are.
+pub fn prove_notes(notes: &[Note<'_>], input_form: c_int) -> Result<Vec<std::result::Result<capgpu_proof, ProveError>>> {
+    let count = notes.len();
+    let num_inputs = notes.iter().map(|n| n.key.num_inputs).max().unwrap_or(0);
+    let handles: Vec<u64> = notes.iter().map(|n| n.key.handle).collect();
+    let rows: Vec<*const u64> = notes.iter().map(|n| n.wires.as_ptr() as *const u64).collect();
+    let mut pubs = vec![[0u64; 4]; count * num_inputs];
+    let mut blinders = Vec::with_capacity(count * 13);
+    for (i, n) in notes.iter().enumerate() {
+        assert_eq!(n.pub_inputs.len(), n.key.num_inputs);
+        pubs[i * num_inputs..i * num_inputs + n.pub_inputs.len()].copy_from_slice(n.pub_inputs);
+        blinders.extend_from_slice(&n.blinders[..]);
+    }
+    let msgs: Vec<*const u8> = notes.iter().map(|n| if n.ext_msg.is_empty() { std::ptr::null() } else { n.ext_msg.as_ptr() }).collect();
+    let lens: Vec<usize> = notes.iter().map(|n| n.ext_msg.len()).collect();
+    let mut proofs: Vec<capgpu_proof> = (0..count).map(|_| unsafe { std::mem::zeroed() }).collect();
+    let mut outcomes = vec![capgpu_prove_outcome::default(); count];
+    check(unsafe {
+        capgpu_plonk_prove_notes(handles.as_ptr(), count as c_int, rows.as_ptr(), pubs.as_ptr() as *const u64, num_inputs,
+                                 msgs.as_ptr(), lens.as_ptr(), blinders.as_ptr() as *const u64, input_form,
+                                 proofs.as_mut_ptr(), outcomes.as_mut_ptr())
+    })?;
+    Ok(proofs.into_iter().zip(outcomes).map(|(p, o)| if o.status == CAPGPU_OK { Ok(p) } else { Err(ProveError::from(o)) })
+        .collect())
 }
 /// Why one note of `ProvingKey::prove_each` has no proof: the outcome record and `capgpu_prove_outcome_text` of it.
 #[derive(Clone)]

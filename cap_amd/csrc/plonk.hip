@@ -39,6 +39,7 @@
 #include "context.hpp"
 #include "host_util.hpp"
 #include "launch.hpp"
+#include "notes.hpp"
 #include "params.hpp"
 #include "plonk_kernels.hpp"
 #include "solve.hpp"
@@ -2269,21 +2270,10 @@ static size_t deal_max_parts(size_t contexts) {
   const size_t devices = std::max<size_t>(seen.size(), 1);
   return devices * std::min<size_t>(per_device, std::max<size_t>(contexts / devices, 1));
 }
-static int deal(int count, const std::function<int(int first, int cnt)>& part) {
+// which contexts `parts` parts run on: the idle ones first, in slot order (a lone caller keeps to the same - warm - contexts
+// call after call; concurrent callers find different ones), the round-robin cursor for the rest
+static std::vector<size_t> deal_pick(size_t parts) {
   const size_t S = num_contexts();
-  const size_t parts = std::min<size_t>(std::min<size_t>(S, deal_max_parts(S)), (size_t)std::max(count / deal_min(), 1));
-  // Mode A (capgpu_plonk_shard_msm): the ranks of the communicator prove the same batch in lock step, so the batch stays
-  // whole and on the communicator's context - cut over contexts, one part would run unsharded and which proofs meet in
-  // an exchange would depend on a cursor the ranks do not share (pick_context sends it there)
-  if (comm_shard_slot() >= 0 || thread_bound_slot() >= 0 || S <= 1 || parts <= 1 || thread_entry_depth() > 0) {
-    Context& c = pick_context();
-    ScopedCtx sc(c);
-    return part(0, count);
-  }
-  std::vector<int> rcs(parts, CAPGPU_OK);
-  std::vector<std::string> errs(parts);
-  // which contexts: the idle ones first, in slot order (a lone caller keeps to the same - warm - contexts call after call;
-  // concurrent callers find different ones), the round-robin cursor for the rest
   const uint32_t start = rt().rr.fetch_add((uint32_t)parts, std::memory_order_relaxed);
   std::vector<size_t> pick;
   for (size_t i = 0; i < S && pick.size() < parts; i++) {
@@ -2297,6 +2287,27 @@ static int deal(int count, const std::function<int(int first, int cnt)>& part) {
     const size_t i = (start + k) % S;
     if (std::find(pick.begin(), pick.end(), i) == pick.end()) pick.push_back(i);
   }
+  return pick;
+}
+// whether a host-resident call stays whole on ONE context (pick_context's): mode A (capgpu_plonk_shard_msm: the ranks of the
+// communicator prove the same batch in lock step), a thread that bound itself, a single context, an entry from inside the library
+static bool deal_stays_whole(size_t S, size_t parts) {
+  return comm_shard_slot() >= 0 || thread_bound_slot() >= 0 || S <= 1 || parts <= 1 || thread_entry_depth() > 0;
+}
+static int deal(int count, const std::function<int(int first, int cnt)>& part) {
+  const size_t S = num_contexts();
+  const size_t parts = std::min<size_t>(std::min<size_t>(S, deal_max_parts(S)), (size_t)std::max(count / deal_min(), 1));
+  // Mode A (capgpu_plonk_shard_msm): the ranks of the communicator prove the same batch in lock step, so the batch stays
+  // whole and on the communicator's context - cut over contexts, one part would run unsharded and which proofs meet in
+  // an exchange would depend on a cursor the ranks do not share (pick_context sends it there)
+  if (deal_stays_whole(S, parts)) {
+    Context& c = pick_context();
+    ScopedCtx sc(c);
+    return part(0, count);
+  }
+  std::vector<int> rcs(parts, CAPGPU_OK);
+  std::vector<std::string> errs(parts);
+  const std::vector<size_t> pick = deal_pick(parts);
   H2dTurn turn;
   // (parts on different devices have a link each: only the parts of ONE device take turns)
   bool one_device = true;
@@ -2383,6 +2394,11 @@ struct ProveCall {
   // capgpu_plonk_prove_given_io*: the public inputs are computed from the solved assignments into pub_out - which
   // pub_inputs then points at too: from the gather on, the call is a given-value call on that host buffer
   uint64_t* pub_out = nullptr;
+  // capgpu_plonk_prove_notes*: host form - rows[i] is proof i's own witness block (`wires` stays null: one pointer per
+  // note, no common stride); device form - dev_stride > 0 is the constant stride the blocks of a variable-form group lie at
+  // in the caller's buffer, which may exceed the largest num_vars
+  const uint64_t* const* rows = nullptr;
+  size_t dev_stride = 0;
   size_t num_keys() const { return one_key ? 1 : (size_t)count; }
 };
 static const char kProve[] = "capgpu_plonk_prove", kProveMulti[] = "capgpu_plonk_prove_multi",
@@ -2480,7 +2496,7 @@ static int host_part(const ProveCall& b, int first, int cnt) {
   // the columns (variable form: the value vectors) are copied inside round 1, chunk by chunk, behind the commitments of
   // the chunk before
   std::vector<const uint64_t*> rows(cnt);
-  for (int i = 0; i < cnt; i++) rows[i] = (const uint64_t*)b.wires + (size_t)4 * (first + i) * b.stride;
+  for (int i = 0; i < cnt; i++) rows[i] = b.rows ? b.rows[first + i] : (const uint64_t*)b.wires + (size_t)4 * (first + i) * b.stride;
   const VarsIn vin{(const fe*)c.stage_b.p + (size_t)cnt * NW * n, b.stride};
   rq.d_wires = (const fe*)c.stage_b.p;
   rq.h_wires = rows.data();
@@ -2501,6 +2517,7 @@ static int prove_resident(const ProveCall& a) {
     // the caller's buffer holds count * stride values and is only read: the columns are gathered into staging
     size_t stride = 0;
     if ((rc = input_stride(a.handles, (int)a.num_keys(), a.form, 0, &stride))) return rc;
+    if (a.dev_stride) stride = a.dev_stride;
     if ((rc = scratch_reserve(c.stage_b, vars_stage_bytes((size_t)a.count, keys.ptr[0]->n, 0, false)))) return rc;
     vin = VarsIn{(const fe*)a.wires, stride};
     rq.d_wires = (const fe*)c.stage_b.p;
@@ -2832,6 +2849,7 @@ struct AsyncJob {
   std::vector<std::shared_ptr<ProvingKey>> homes;  // shared ownership, as home_key gives it: [pks.size()]
   std::vector<std::vector<uint8_t>> msgs;          // call.msgs != NULL: one per proof, else [1]: the shared message
   int bound_slot = -1;                             // the submitting thread's capgpu_set_device, -1: none
+  std::vector<const uint64_t*> rows;               // capgpu_plonk_prove_notes_async: the pointer per note (the blocks are borrowed)
 };
 // The ticket of a call whose pointers have been checked: every key is known and the set obeys the rule - what the
 // synchronous call finds out on the device (prove_batch) is found out here, before anything is queued.  refuse_recompute:
@@ -2881,6 +2899,7 @@ struct JobCall {
     }
     b.handles = j.pks.data();
     b.homes = j.homes.data();
+    if (b.rows) b.rows = j.rows.data();
     if (b.msgs) {
       b.msgs = mp.data();
       b.msg_lens = ml.data();
@@ -2919,6 +2938,8 @@ Context* try_acquire_context_on(int device) {
   return nullptr;
 }
 
+int notes_here(const ProveCall& a);  // capgpu_plonk_prove_notes_async: the groups of the call, one after the other, on this context
+
 int run_ticket(AsyncJob& j, int lane, std::string* err) {
   Runtime& R = rt();
   const std::vector<int> devs = async_devices();
@@ -2946,7 +2967,7 @@ int run_ticket(AsyncJob& j, int lane, std::string* err) {
   {
     ScopedCtx sc(*c);
     const JobCall jc(j);
-    rc = jc.b.given ? given_part(jc.b, 0, jc.b.count) : host_part(jc.b, 0, jc.b.count);
+    rc = jc.b.given ? given_part(jc.b, 0, jc.b.count) : jc.b.rows ? notes_here(jc.b) : host_part(jc.b, 0, jc.b.count);
     if (rc) *err = last_error();
   }
   if (locked) c->mu.unlock();
@@ -3270,6 +3291,439 @@ static int reserve_impl(uint64_t pk_handle, int count, int input_form, int slot,
     if ((rc = pinned_reserve(c, nd.pinned))) return rc;
     CAP_HIP(hipStreamSynchronize(c.stream));
     trace("reserve", c.slot, count);
+  }
+  return CAPGPU_OK;
+}
+
+// ---- capgpu_plonk_prove_notes*: one call over keys of several domain sizes ---------------------------------------------
+// The rule is notes_plan.hpp's: a GROUP is what one device batch may hold.  Every group becomes a ProveCall of its own
+// (GroupCall: the per-proof arrays of its members, in member order) and goes down capgpu_plonk_prove_each's path - host_part
+// or prove_resident - so the contract (group by group, the bytes of that call) holds by construction.
+}  // extern "C"
+
+namespace cap {
+namespace {
+const char kNotes[] = "capgpu_plonk_prove_notes";
+std::atomic<uint64_t> g_notes_calls{0}, g_notes_groups{0}, g_notes_groups_dealt{0}, g_notes_contexts_dealt{0},
+    g_notes_direct{0}, g_notes_gathered{0}, g_notes_rows{0};  // capgpu_plonk_notes_stats
+
+// check (7): the home copy of every note's key
+int notes_keys(const uint64_t* handles, int count, int form, std::vector<std::shared_ptr<ProvingKey>>* home) {
+  home->assign((size_t)count, nullptr);
+  std::map<uint64_t, std::shared_ptr<ProvingKey>> seen;
+  for (int i = 0; i < count; i++) {
+    auto it = seen.find(handles[i]);
+    if (it != seen.end()) {
+      (*home)[i] = it->second;
+      continue;
+    }
+    if (int rc = home_key(handles[i], &(*home)[i])) return rc;
+    const ProvingKey& K = *(*home)[i];
+    if (K.recompute) {
+      set_error("%s: the key of note %d re-transforms its columns for every proof (CAPGPU_RECOMPUTE_PK_COSET): such a key is "
+                "proved alone", kNotes, i);
+      return CAPGPU_ERR_INVALID_ARG;
+    }
+    if (form == CAPGPU_INPUT_VARS && key_lacks_table(K)) return CAPGPU_ERR_INVALID_ARG;
+    seen.emplace(handles[i], (*home)[i]);
+  }
+  return CAPGPU_OK;
+}
+np::Plan notes_plan_of(const std::shared_ptr<ProvingKey>* home, int count, int form) {
+  std::vector<np::Note> notes((size_t)count);
+  for (int i = 0; i < count; i++) {
+    const ProvingKey& K = *home[i];
+    notes[i] = np::Note{K.n, K.srs_handle, K.num_inputs, form == CAPGPU_INPUT_VARS ? K.num_vars : (uint64_t)NW * K.n};
+  }
+  return np::notes_plan(notes.data(), notes.size());
+}
+// check (8)
+int notes_rows_too_short(const ProveCall& a, const np::Plan& pl) {
+  if (a.num_inputs >= pl.max_inputs) return CAPGPU_OK;
+  set_error("%s: rows of %zu public inputs given, the keys need %zu", kNotes, a.num_inputs, (size_t)pl.max_inputs);
+  return CAPGPU_ERR_INVALID_ARG;
+}
+
+// One group of a notes call `a` as a call of its own: everything per proof in member order - the public-input rows
+// re-packed to the group's own largest count, as part_pub_rows re-packs a part's -, results into temporaries that scatter()
+// hands to the caller's slots once the group has run.
+struct GroupCall {
+  const std::vector<uint32_t>& who;
+  std::vector<uint64_t> handles, pubs, blind;
+  std::vector<std::shared_ptr<ProvingKey>> homes;
+  std::vector<const uint64_t*> rows;
+  std::vector<const uint8_t*> msgs;
+  std::vector<size_t> lens;
+  std::vector<capgpu_proof> proofs;
+  std::vector<capgpu_prove_outcome> outcomes;
+  ProveCall b;
+  GroupCall(const ProveCall& a, const std::shared_ptr<ProvingKey>* home, const np::Group& G) : who(G.members), b(a) {
+    const size_t cnt = who.size(), ni = (size_t)G.max_inputs;
+    handles.resize(cnt);
+    homes.resize(cnt);
+    pubs.assign((size_t)4 * ni * cnt + 4, 0);
+    blind.resize((size_t)4 * 13 * cnt);
+    proofs.resize(cnt);
+    outcomes.resize(cnt);
+    if (a.rows) rows.resize(cnt);
+    if (a.msgs) {
+      msgs.resize(cnt);
+      lens.resize(cnt);
+    }
+    for (size_t k = 0; k < cnt; k++) {
+      const size_t i = who[k];
+      handles[k] = a.handles[i];
+      homes[k] = home[i];
+      if (ni) memcpy(&pubs[(size_t)4 * ni * k], a.pub_inputs + (size_t)4 * a.num_inputs * i, 32 * ni);
+      memcpy(&blind[(size_t)4 * 13 * k], a.blinders + (size_t)4 * 13 * i, 32 * 13);
+      if (a.rows) rows[k] = a.rows[i];
+      if (a.msgs) {
+        msgs[k] = a.msgs[i];
+        lens[k] = a.msg_lens[i];
+      }
+    }
+    b.handles = handles.data();
+    b.homes = homes.data();
+    b.count = (int)cnt;
+    b.wires = nullptr;
+    b.rows = a.rows ? rows.data() : nullptr;
+    b.pub_inputs = ni ? pubs.data() : nullptr;
+    b.num_inputs = ni;
+    b.msgs = a.msgs ? msgs.data() : nullptr;
+    b.msg_lens = a.msgs ? lens.data() : nullptr;
+    b.blinders = blind.data();
+    b.proofs = proofs.data();
+    b.outcomes = outcomes.data();
+    b.one_key = each_one_key(b);
+    b.n = (size_t)G.n;
+    b.stride = (size_t)G.max_row;
+  }
+  void scatter(const ProveCall& a) const {
+    for (size_t k = 0; k < who.size(); k++) {
+      a.proofs[who[k]] = proofs[k];
+      a.outcomes[who[k]] = outcomes[k];
+    }
+  }
+};
+
+int notes_host_group(const ProveCall& a, const std::shared_ptr<ProvingKey>* home, const np::Group& G) {
+  GroupCall gc(a, home, G);
+  const int rc = host_part(gc.b, 0, gc.b.count);
+  if (!rc) gc.scatter(a);
+  return rc;
+}
+// the groups in run order, one after the other, on the calling thread's context; stops at the first that fails
+int notes_in_turn(const ProveCall& a, const std::shared_ptr<ProvingKey>* home, const np::Plan& pl) {
+  for (uint32_t g : pl.order)
+    if (int rc = notes_host_group(a, home, pl.groups[g])) return rc;
+  return CAPGPU_OK;
+}
+void notes_count_call(const np::Plan& pl) {
+  g_notes_calls.fetch_add(1, std::memory_order_relaxed);
+  g_notes_groups.fetch_add(pl.groups.size(), std::memory_order_relaxed);
+}
+
+// deal()'s sibling for whole groups: where deal() cuts ONE batch into contiguous parts, this hands out the groups of a
+// notes call, each whole - in run order, a context that finishes taking the next -, on the contexts deal_pick names.  The
+// parts of different groups take no H2D turns: their copies are of different sizes and start when their context is free.
+int deal_groups(const ProveCall& a, const std::shared_ptr<ProvingKey>* home, const np::Plan& pl) {
+  const size_t S = num_contexts(), G = pl.groups.size();
+  const size_t parts = std::min<size_t>(std::min<size_t>(S, deal_max_parts(S)), G);
+  if (deal_stays_whole(S, parts)) {
+    Context& c = pick_context();
+    ScopedCtx sc(c);
+    return notes_in_turn(a, home, pl);
+  }
+  const std::vector<size_t> pick = deal_pick(parts);
+  std::vector<int> rcs(G, CAPGPU_OK);
+  std::vector<std::string> errs(G);
+  std::atomic<size_t> next{0};
+  std::atomic<bool> failed{false};  // (a failed group stops none that runs; it keeps the idle contexts from starting more)
+  auto body = [&](size_t w) {
+    ScopedCtx sc(*rt().ctxs[pick[w]]);
+    for (size_t k; !failed.load(std::memory_order_relaxed) && (k = next.fetch_add(1)) < G;) {
+      rcs[k] = notes_host_group(a, home, pl.groups[pl.order[k]]);
+      if (rcs[k]) {
+        errs[k] = last_error();
+        failed.store(true, std::memory_order_relaxed);
+      }
+    }
+  };
+  std::vector<std::thread> th;
+  for (size_t w = 1; w < parts; w++) th.emplace_back(body, w);
+  body(0);
+  for (auto& t : th) t.join();
+  g_notes_groups_dealt.fetch_add(G, std::memory_order_relaxed);
+  g_notes_contexts_dealt.fetch_add(parts, std::memory_order_relaxed);
+  for (size_t k = 0; k < G; k++)
+    if (rcs[k]) {
+      set_error("%s", errs[k].c_str());
+      return rcs[k];
+    }
+  return CAPGPU_OK;
+}
+
+// A checked host-form call.  One group: capgpu_plonk_prove_each's own path - the caller's arrays as they are, dealt in
+// contiguous cuts - unless the rows of public inputs are longer than the group's (then through GroupCall's re-packed ones).
+int notes_host(ProveCall a, const std::vector<std::shared_ptr<ProvingKey>>& home) {
+  const np::Plan pl = notes_plan_of(home.data(), a.count, a.form);
+  if (int rc = notes_rows_too_short(a, pl)) return rc;
+  notes_count_call(pl);
+  if (pl.groups.size() > 1) return deal_groups(a, home.data(), pl);
+  const np::Group& G = pl.groups[0];
+  a.homes = home.data();
+  if (a.num_inputs == G.max_inputs) {
+    a.one_key = each_one_key(a);
+    a.n = (size_t)G.n;
+    a.stride = (size_t)G.max_row;
+    return deal(a.count, [&](int first, int cnt) -> int { return host_part(a, first, cnt); });
+  }
+  GroupCall gc(a, home.data(), G);
+  const int rc = deal(a.count, [&](int first, int cnt) -> int { return host_part(gc.b, first, cnt); });
+  if (!rc) gc.scatter(a);
+  return rc;
+}
+
+// a ticket's body (run_ticket): the call whole on the worker's context, groups in run order
+int notes_here(const ProveCall& a) {
+  const np::Plan pl = notes_plan_of(a.homes, a.count, a.form);
+  notes_count_call(pl);
+  return notes_in_turn(a, a.homes, pl);
+}
+
+// Context::stage_b of a gathered group of the device form: the layout host-resident input has there (host_part) - the
+// columns, which in the evals / coeffs forms ARE the gathered rows, and in the variable form the value vectors behind them
+// -, then the move table of the gather's one launch.
+size_t notes_stage_table_at(size_t cnt, size_t n, size_t row, bool vars) {
+  return ((vars ? vars_stage_bytes(cnt, n, row, true) : wires_stage_bytes(cnt, n)) + 255) / 256 * 256;
+}
+size_t notes_stage_bytes(size_t cnt, size_t n, size_t row, bool vars) {
+  return notes_stage_table_at(cnt, n, row, vars) + sizeof(np::MoveAt) * cnt + 256;
+}
+
+// One group of a device-form call on the calling thread's context, whose lock the caller holds.
+int notes_dev_group(Context& c, const ProveCall& a, const uint64_t* offsets, const std::shared_ptr<ProvingKey>* home,
+                    const np::Group& G) {
+  GroupCall gc(a, home, G);
+  const bool vars = a.form == CAPGPU_INPUT_VARS;
+  const size_t cnt = G.members.size(), n = (size_t)G.n, cols = (size_t)NW * n, row = (size_t)G.max_row;
+  uint64_t stride = 0;
+  int rc;
+  if (np::constant_stride(offsets, G.members.data(), cnt, vars ? 0 : cols, row, &stride)) {
+    // where it lies: capgpu_plonk_prove_each_dev of the group (a `_dev` column for compaction's rule)
+    gc.b.wires = (const fe*)a.wires + offsets[G.members[0]];
+    gc.b.dev_stride = vars ? (size_t)stride : 0;
+    g_notes_direct.fetch_add(1, std::memory_order_relaxed);
+  } else {
+    if ((rc = scratch_reserve(c.stage_b, notes_stage_bytes(cnt, n, row, vars)))) return rc;
+    fe* const dst = (fe*)c.stage_b.p + (vars ? cnt * cols : 0);
+    np::MoveAt* const d_moves = (np::MoveAt*)((char*)c.stage_b.p + notes_stage_table_at(cnt, n, row, vars));
+    std::vector<np::MoveAt> moves(cnt);
+    for (size_t k = 0; k < cnt; k++)
+      moves[k] = np::MoveAt{offsets[G.members[k]], 2 * (uint64_t)(vars ? home[G.members[k]]->num_vars : cols)};
+    CAP_HIP(hipMemcpyAsync(d_moves, moves.data(), sizeof(np::MoveAt) * cnt, hipMemcpyHostToDevice, c.stream));
+    notes_move_rows(c.stream, a.wires, dst, 2 * (uint64_t)row, d_moves, (uint32_t)cnt);
+    // from here the group is library staging: columns at the head of stage_b, or - variable form - gathered there
+    // from the value vectors behind them (prove_resident's request with the library's buffer for the caller's)
+    gc.b.wires = dst;
+    gc.b.dev_stride = vars ? row : 0;
+    g_notes_gathered.fetch_add(1, std::memory_order_relaxed);
+    g_notes_rows.fetch_add(cnt, std::memory_order_relaxed);
+  }
+  if ((rc = prove_resident(gc.b))) return rc;
+  gc.scatter(a);
+  return CAPGPU_OK;
+}
+}  // namespace
+}  // namespace cap
+
+extern "C" {
+
+static ProveCall notes_call(const uint64_t* pk_handles, int count, const uint64_t* const* wires, const void* d_wires,
+                            const uint64_t* pub_inputs, size_t num_inputs, const uint8_t* const* ext_msgs,
+                            const size_t* ext_msg_lens, const uint64_t* blinders, int input_form, capgpu_proof* proofs_out,
+                            capgpu_prove_outcome* outcomes_out) {
+  ProveCall a = each_call(pk_handles, count, d_wires, pub_inputs, num_inputs, ext_msgs, ext_msg_lens, blinders, input_form,
+                          proofs_out, outcomes_out);
+  a.rows = wires;
+  return a;
+}
+// checks (1) - (3), before a device is looked for
+static int notes_bad_args(const ProveCall& a, bool dev, const uint64_t* offsets, bool ticket, const uint64_t* ticket_out) {
+  if (bad_form(a.form)) return CAPGPU_ERR_INVALID_ARG;
+  if (a.count < 0 || (a.count && (!a.handles || (dev ? !a.wires || !offsets : !a.rows) || !a.outcomes)) || bad_rest(a) ||
+      (ticket && !ticket_out))
+    return bad_args(kNotes);
+  for (int i = 0; !dev && i < a.count; i++)
+    if (!a.rows[i]) {
+      set_error("%s: wires[%d] is NULL", kNotes, i);
+      return CAPGPU_ERR_INVALID_ARG;
+    }
+  if (dev && a.count && ((uintptr_t)a.wires & 15)) {
+    set_error("%s: d_wires %p is not 16-byte aligned", kNotes, a.wires);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  return CAPGPU_OK;
+}
+static bool notes_refused_by_sharding() {
+  if (comm_shard_slot() < 0 && !comm_shard_prover()) return false;
+  set_error("%s: not available while capgpu_plonk_shard_msm is on (the ranks prove in lock step)", kNotes);
+  return true;
+}
+
+int capgpu_plonk_prove_notes(const uint64_t* pk_handles, int count, const uint64_t* const* wires,
+                             const uint64_t* pub_inputs, size_t num_inputs, const uint8_t* const* ext_msgs,
+                             const size_t* ext_msg_lens, const uint64_t* blinders, int input_form,
+                             capgpu_proof* proofs_out, capgpu_prove_outcome* outcomes_out) {
+  const ProveCall a = notes_call(pk_handles, count, wires, nullptr, pub_inputs, num_inputs, ext_msgs, ext_msg_lens, blinders,
+                                 input_form, proofs_out, outcomes_out);
+  if (int rc = notes_bad_args(a, false, nullptr, false, nullptr)) return rc;
+  CAP_CHECK_INIT();
+  if (count == 0) return CAPGPU_OK;
+  if (notes_refused_by_sharding()) return CAPGPU_ERR_INVALID_ARG;
+  std::vector<std::shared_ptr<ProvingKey>> home;
+  if (int rc = notes_keys(pk_handles, count, input_form, &home)) return rc;
+  return notes_host(a, home);
+}
+
+int capgpu_plonk_prove_notes_dev(const uint64_t* pk_handles, int count, const void* d_wires, const uint64_t* wire_offsets,
+                                 const uint64_t* pub_inputs, size_t num_inputs, const uint8_t* const* ext_msgs,
+                                 const size_t* ext_msg_lens, const uint64_t* blinders, int input_form,
+                                 capgpu_proof* proofs_out, capgpu_prove_outcome* outcomes_out) {
+  const ProveCall a = notes_call(pk_handles, count, nullptr, d_wires, pub_inputs, num_inputs, ext_msgs, ext_msg_lens, blinders,
+                                 input_form, proofs_out, outcomes_out);
+  if (int rc = notes_bad_args(a, true, wire_offsets, false, nullptr)) return rc;
+  CAP_CHECK_INIT();
+  Context& c = ctx();
+  Entry lk(c);
+  if (count == 0) return CAPGPU_OK;
+  if (notes_refused_by_sharding()) return CAPGPU_ERR_INVALID_ARG;
+  std::vector<std::shared_ptr<ProvingKey>> home;
+  if (int rc = notes_keys(pk_handles, count, input_form, &home)) return rc;
+  const np::Plan pl = notes_plan_of(home.data(), count, input_form);
+  if (int rc = notes_rows_too_short(a, pl)) return rc;
+  notes_count_call(pl);
+  for (uint32_t g : pl.order)
+    if (int rc = notes_dev_group(c, a, wire_offsets, home.data(), pl.groups[g])) return rc;
+  return CAPGPU_OK;
+}
+
+int capgpu_plonk_prove_notes_async(const uint64_t* pk_handles, int count, const uint64_t* const* wires,
+                                   const uint64_t* pub_inputs, size_t num_inputs, const uint8_t* const* ext_msgs,
+                                   const size_t* ext_msg_lens, const uint64_t* blinders, int input_form,
+                                   capgpu_proof* proofs_out, capgpu_prove_outcome* outcomes_out, uint64_t* ticket_out) {
+  const ProveCall a = notes_call(pk_handles, count, wires, nullptr, pub_inputs, num_inputs, ext_msgs, ext_msg_lens, blinders,
+                                 input_form, proofs_out, outcomes_out);
+  if (int rc = notes_bad_args(a, false, nullptr, true, ticket_out)) return rc;
+  CAP_CHECK_INIT();
+  *ticket_out = 0;
+  if (count == 0) return CAPGPU_OK;
+  if (notes_refused_by_sharding()) return CAPGPU_ERR_INVALID_ARG;
+  AsyncJob j;
+  if (int rc = notes_keys(pk_handles, count, input_form, &j.homes)) return rc;
+  if (int rc = notes_rows_too_short(a, notes_plan_of(j.homes.data(), count, input_form))) return rc;
+  // (fill_job's copies: the handles, the homes above, the messages, the pointer per note)
+  j.call = a;
+  j.pks.assign(pk_handles, pk_handles + count);
+  j.rows.assign(wires, wires + count);
+  j.msgs.resize(a.msgs ? (size_t)count : 1);
+  for (size_t i = 0; a.msgs && i < j.msgs.size(); i++)
+    if (a.msgs[i] && a.msg_lens[i]) j.msgs[i].assign(a.msgs[i], a.msgs[i] + a.msg_lens[i]);
+  j.bound_slot = thread_bound_slot();
+  return submit_ticket(std::move(j), ticket_out);
+}
+
+int capgpu_plonk_notes_plan(const uint64_t* pk_handles, int count, capgpu_notes_group* groups_out, size_t cap,
+                            size_t* num_groups_out, uint32_t* group_of_out) {
+  if (count < 0 || (count && !pk_handles) || (cap && !groups_out) || !num_groups_out) return bad_args("capgpu_plonk_notes_plan");
+  if (!rt().initialised.load(std::memory_order_acquire)) {
+    set_error("capgpu: not initialised (call capgpu_init first)");
+    return CAPGPU_ERR_NOT_INITIALISED;
+  }
+  *num_groups_out = 0;
+  if (count == 0) return CAPGPU_OK;
+  std::vector<std::shared_ptr<ProvingKey>> home;
+  if (int rc = notes_keys(pk_handles, count, CAPGPU_INPUT_EVALS, &home)) return rc;
+  const np::Plan pl = notes_plan_of(home.data(), count, CAPGPU_INPUT_EVALS);
+  *num_groups_out = pl.groups.size();
+  for (size_t g = 0; g < pl.groups.size() && g < cap; g++) {
+    const np::Group& G = pl.groups[g];
+    groups_out[g] = capgpu_notes_group{G.srs, G.n, (uint32_t)G.members.size(), G.members[0], (uint32_t)G.max_inputs, G.run_order};
+  }
+  for (int i = 0; group_of_out && i < count; i++) group_of_out[i] = pl.group_of[i];
+  return CAPGPU_OK;
+}
+
+int capgpu_plonk_notes_stats(capgpu_notes_stats* out) {
+  if (!out) return bad_args("capgpu_plonk_notes_stats");
+  *out = capgpu_notes_stats{g_notes_calls.load(),  g_notes_groups.load(),   g_notes_groups_dealt.load(), g_notes_contexts_dealt.load(),
+                            g_notes_direct.load(), g_notes_gathered.load(), g_notes_rows.load()};
+  return CAPGPU_OK;
+}
+
+// The largest need over the groups of such a call on context `slot` (-1: every one), host and device form: per group the
+// sizes capgpu_plonk_reserve takes for its batch - the plan of host-resident and of resident input, with the group's
+// largest num_vars behind the columns - and the gather's staging (notes_stage_bytes); every key is brought to the context.
+int capgpu_plonk_reserve_notes(const uint64_t* pk_handles, int count, int input_form, int slot) {
+  const char* const who = "capgpu_plonk_reserve_notes";
+  if (bad_form(input_form)) return CAPGPU_ERR_INVALID_ARG;
+  if (count < 0 || (count && !pk_handles)) return bad_args(who);
+  CAP_CHECK_INIT();
+  if (slot < -1 || slot >= (int)num_contexts()) {
+    set_error("%s: bad argument (count >= 0, slot -1 .. %zu)", who, num_contexts() - 1);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  if (count == 0) return CAPGPU_OK;
+  std::vector<std::shared_ptr<ProvingKey>> home;
+  int rc = notes_keys(pk_handles, count, input_form, &home);
+  if (rc) return rc;
+  const np::Plan plan = notes_plan_of(home.data(), count, input_form);
+  const bool vars = input_form == CAPGPU_INPUT_VARS;
+  struct ScaleOne {  // exact sizes, as capgpu_plonk_reserve takes them
+    double saved = scratch_growth_scale();
+    ScaleOne() { scratch_growth_scale() = 1.0; }
+    ~ScaleOne() { scratch_growth_scale() = saved; }
+  } scale_one;
+  for (int sl = slot < 0 ? 0 : slot, end = slot < 0 ? (int)num_contexts() : slot + 1; sl < end; sl++) {
+    Context& c = *rt().ctxs[(size_t)sl];
+    ScopedCtx sc(c);
+    Entry lk(c);
+    ProveNeeds nd;
+    for (const np::Group& G : plan.groups) {
+      const uint32_t cnt = (uint32_t)G.members.size();
+      std::shared_ptr<ProvingKey> K0, K;
+      size_t prefix = 0;
+      for (uint32_t i : G.members) {
+        if ((rc = part_key(pk_handles[i], &home[i], &K))) return rc;
+        if (!K0) K0 = K;
+        prefix = std::max(prefix, K->vk_bytes.size() + 32 * K->num_inputs);
+      }
+      const NttDomain* dn = nullptr;
+      const Ntt3Domain* d3 = nullptr;
+      if ((rc = get_domain(K0->log_n, &dn)) || (rc = quot_domains(K0->log_m, &d3, &dn))) return rc;
+      for (int host = 0; host < 2; host++) {
+        ProvePlan pl;
+        if ((rc = make_plan(c, *K0, cnt, input_form, host != 0, prefix, true, &pl))) return rc;
+        const ProveNeeds g = prove_needs(pl, *K0);
+        nd.prove_ws = std::max(nd.prove_ws, g.prove_ws);
+        nd.msm_ws = std::max(nd.msm_ws, g.msm_ws);
+        nd.ntt_scratch = std::max(nd.ntt_scratch, g.ntt_scratch);
+        nd.stage_a = std::max(nd.stage_a, g.stage_a);
+        nd.stage_b = std::max(nd.stage_b, g.stage_b);
+        nd.pinned = std::max(nd.pinned, g.pinned);
+      }
+      nd.stage_b = std::max(nd.stage_b, notes_stage_bytes(cnt, (size_t)G.n, (size_t)G.max_row, vars));
+    }
+    (void)h2d_stream();
+    (void)side_stream(c);
+    if ((rc = scratch_reserve(c.stage_b, nd.stage_b))) return rc;
+    if ((rc = scratch_reserve(c.stage_a, nd.stage_a))) return rc;
+    if ((rc = scratch_reserve(c.prove_ws, nd.prove_ws))) return rc;
+    if ((rc = scratch_reserve(c.msm_ws, nd.msm_ws))) return rc;
+    if ((rc = scratch_reserve(c.ntt_scratch, nd.ntt_scratch))) return rc;
+    if ((rc = pinned_reserve(c, nd.pinned))) return rc;
+    CAP_HIP(hipStreamSynchronize(c.stream));
+    trace("reserve_notes", c.slot, count);
   }
   return CAPGPU_OK;
 }

@@ -1531,6 +1531,122 @@ def plonk_prove_each_async(pk_handles, wires: np.ndarray, pub_rows: np.ndarray, 
     return EachTicket(t.value, proofs, outcomes, count, (wires, keep))
 
 
+# ---- a Vec of notes over keys of several domain sizes (capgpu_plonk_prove_notes*) ---------------------------------------
+class NotesGroup(ctypes.Structure):
+    """capgpu_notes_group (include/capgpu.h): one group of a notes call - the notes whose keys share domain size and SRS."""
+    _fields_ = [("srs_handle", ctypes.c_uint64), ("domain_size", ctypes.c_uint64), ("count", ctypes.c_uint32),
+                ("first", ctypes.c_uint32), ("max_inputs", ctypes.c_uint32), ("run_order", ctypes.c_uint32)]
+
+
+class NotesStats(ctypes.Structure):
+    """capgpu_notes_stats (include/capgpu.h)"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("calls", "groups", "groups_dealt", "contexts_dealt", "dev_groups_direct",
+                                               "dev_groups_gathered", "rows_gathered")]
+
+
+def _notes_args(who: str, pk_handles, pub_rows, blinders, ext_msgs):
+    """the per-note arrays of a notes call: rows of the largest num_inputs among ALL the keys, 13 blinders per note"""
+    count = len(pk_handles)
+    pub_rows = np.ascontiguousarray(pub_rows, dtype=np.uint64).reshape(-1)
+    blinders = np.ascontiguousarray(blinders, dtype=np.uint64).reshape(-1)
+    if blinders.size != count * 13 * 4 or (count and pub_rows.size % (4 * count)):
+        raise ValueError(f"{who}: pub_rows must hold {count} equal rows and blinders {count} x 13 elements")
+    num_inputs = pub_rows.size // (4 * count) if count else 0
+    handles = (ctypes.c_uint64 * max(count, 1))(*pk_handles)
+    msgs_arg = lens_arg = None
+    keep = [pub_rows, blinders]
+    if ext_msgs is not None:
+        if len(ext_msgs) != count:
+            raise ValueError(f"{who}: one message per note")
+        msgs_arg = (ctypes.c_char_p * max(count, 1))()
+        lens_arg = (ctypes.c_size_t * max(count, 1))()
+        for i, m in enumerate(ext_msgs):
+            keep.append(bytes(m) if m else b"")
+            msgs_arg[i] = keep[-1] if keep[-1] else None
+            lens_arg[i] = len(keep[-1])
+    proofs = (Proof * max(count, 1))()
+    outcomes = (ProveOutcome * max(count, 1))()
+    pub_ptr = _p(pub_rows) if pub_rows.size else None
+    return count, handles, pub_ptr, num_inputs, msgs_arg, lens_arg, blinders, proofs, outcomes, keep
+
+
+def _notes_rows(who: str, wires, count: int):
+    """one pointer per note: every wires[i] is that note's own block (any uint64 array; a view is read where it is when
+    it is contiguous) -> (the pointer array, the arrays to keep alive)"""
+    if len(wires) != count:
+        raise ValueError(f"{who}: one witness block per note")
+    rows = [np.ascontiguousarray(w, dtype=np.uint64).reshape(-1) for w in wires]
+    ptrs = (ctypes.c_void_p * max(count, 1))(*[r.ctypes.data for r in rows])
+    return ptrs, rows
+
+
+def plonk_prove_notes(pk_handles, wires, pub_rows: np.ndarray, blinders: np.ndarray, ext_msgs=None, input_form=INPUT_EVALS):
+    """capgpu_plonk_prove_notes: prove_each over keys of SEVERAL domain sizes (or SRS) -> (proofs, outcomes).  wires: one
+    array per note - 5 n_i elements, or (input_form='vars') the key's num_vars values; pub_rows: count rows of the largest
+    num_inputs among all the keys.  Every note's proof and outcome are what plonk_prove_each makes of its group alone."""
+    count, handles, pub_ptr, ni, msgs, lens, blinders, proofs, outcomes, _keep = _notes_args(
+        "plonk_prove_notes", list(pk_handles), pub_rows, blinders, ext_msgs)
+    ptrs, _rows = _notes_rows("plonk_prove_notes", wires, count)
+    check(load().capgpu_plonk_prove_notes(handles, count, ptrs, pub_ptr, ctypes.c_size_t(ni), msgs, lens, _p(blinders),
+                                          ctypes.c_int(_form(input_form)), proofs, outcomes))
+    return list(proofs)[:count], list(outcomes)[:count]
+
+
+def plonk_prove_notes_dev(pk_handles, d_wires, wire_offsets, pub_rows: np.ndarray, blinders: np.ndarray, ext_msgs=None,
+                          input_form=INPUT_EVALS):
+    """capgpu_plonk_prove_notes_dev: the same from ONE device buffer (a DevBuf, or a device address), note i's block at
+    wire_offsets[i] field elements from its start; on the calling context's stream.  The buffer is never written."""
+    count, handles, pub_ptr, ni, msgs, lens, blinders, proofs, outcomes, _keep = _notes_args(
+        "plonk_prove_notes_dev", list(pk_handles), pub_rows, blinders, ext_msgs)
+    if len(wire_offsets) != count:
+        raise ValueError("plonk_prove_notes_dev: one offset per note")
+    offs = (ctypes.c_uint64 * max(count, 1))(*[int(o) for o in wire_offsets])
+    ptr = d_wires.ptr if isinstance(d_wires, DevBuf) else ctypes.c_void_p(int(d_wires))
+    check(load().capgpu_plonk_prove_notes_dev(handles, count, ptr, offs, pub_ptr, ctypes.c_size_t(ni), msgs, lens,
+                                              _p(blinders), ctypes.c_int(_form(input_form)), proofs, outcomes))
+    return list(proofs)[:count], list(outcomes)[:count]
+
+
+def plonk_prove_notes_async(pk_handles, wires, pub_rows: np.ndarray, blinders: np.ndarray, ext_msgs=None,
+                            input_form=INPUT_EVALS) -> EachTicket:
+    """capgpu_plonk_prove_notes_async: plonk_prove_notes without the wait; EachTicket.wait() -> (proofs, outcomes)."""
+    count, handles, pub_ptr, ni, msgs, lens, blinders, proofs, outcomes, keep = _notes_args(
+        "plonk_prove_notes_async", list(pk_handles), pub_rows, blinders, ext_msgs)
+    ptrs, rows = _notes_rows("plonk_prove_notes_async", wires, count)
+    t = ctypes.c_uint64(0)
+    check(load().capgpu_plonk_prove_notes_async(handles, count, ptrs, pub_ptr, ctypes.c_size_t(ni), msgs, lens, _p(blinders),
+                                                ctypes.c_int(_form(input_form)), proofs, outcomes, ctypes.byref(t)))
+    return EachTicket(t.value, proofs, outcomes, count, (rows, keep))
+
+
+def plonk_notes_plan(pk_handles, cap: int | None = None):
+    """capgpu_plonk_notes_plan -> (groups, group_of, num_groups): the groups a notes call over these keys forms - at most
+    `cap` records (None: all of them) -, every note's group, and the true number of groups."""
+    pk_handles = list(pk_handles)
+    count = len(pk_handles)
+    handles = (ctypes.c_uint64 * max(count, 1))(*pk_handles)
+    group_of = (ctypes.c_uint32 * max(count, 1))()
+    num = ctypes.c_size_t(0)
+    room = count if cap is None else int(cap)
+    groups = (NotesGroup * max(room, 1))()
+    check(load().capgpu_plonk_notes_plan(handles, count, groups, ctypes.c_size_t(room), ctypes.byref(num), group_of))
+    return list(groups)[:min(room, num.value)], list(group_of)[:count], num.value
+
+
+def plonk_reserve_notes(pk_handles, input_form=INPUT_EVALS, slot: int = -1):
+    """capgpu_plonk_reserve_notes: size context `slot` (-1: every one) for a notes call over these keys, host or device form"""
+    pk_handles = list(pk_handles)
+    handles = (ctypes.c_uint64 * max(len(pk_handles), 1))(*pk_handles)
+    check(load().capgpu_plonk_reserve_notes(handles, len(pk_handles), ctypes.c_int(_form(input_form)), ctypes.c_int(slot)))
+
+
+def plonk_notes_stats() -> dict:
+    """capgpu_plonk_notes_stats: process-wide counters of the notes calls since init"""
+    s = NotesStats()
+    check(load().capgpu_plonk_notes_stats(ctypes.byref(s)))
+    return {k: getattr(s, k) for k, _ in NotesStats._fields_}
+
+
 # ---- proving from given values (capgpu_plonk_prove_given*): the solver and the variable-form outcome call in one ---------
 def _given_args(who: str, pk_handles, given_elems, pub_rows, blinders, ext_msgs):
     count, handles, pub_ptr, max_in, msgs, lens, blinders, proofs, outcomes, keep = _each_args(

@@ -227,6 +227,28 @@ def prove_each(proving_keys, wires: np.ndarray, public_input_rows: np.ndarray, b
             for p, o in zip(proofs, outcomes)]
 
 
+def prove_notes(notes, input_form="evals") -> list:
+    """The reference's `Vec<TransactionNote>` of transfers, mints and freezes - keys of SEVERAL domain sizes - proved in ONE
+    call (capgpu_plonk_prove_notes).  notes: (proving_key, wires, public_inputs, blinders, ext_msg) per note - wires the
+    note's own block (5 x n_i elements, or its key's num_vars values for input_form='vars'), public_inputs the inputs of ITS
+    key.  -> per note the proof or the TxnApiError.FailedSnark (RETURNED, not raised) its own prove() would have raised;
+    every entry is what prove_each makes of the notes of its group (same domain size and SRS) alone."""
+    notes = list(notes)
+    nin = max((np.asarray(n[2]).reshape(-1, 4).shape[0] for n in notes), default=0)
+    rows = np.zeros((len(notes), nin, 4), np.uint64)
+    for i, n in enumerate(notes):
+        own = np.asarray(n[2], dtype=np.uint64).reshape(-1, 4)
+        rows[i, :own.shape[0]] = own
+    blinders = np.stack([np.asarray(n[3], dtype=np.uint64).reshape(13, 4) for n in notes]) if notes else np.zeros((0, 13, 4), np.uint64)
+    try:
+        proofs, outcomes = _lib.plonk_prove_notes([n[0].handle for n in notes], [n[1] for n in notes], rows, blinders,
+                                                  [n[4] for n in notes], input_form)
+    except (_lib.CapGpuError, ValueError) as e:
+        raise TxnApiError.FailedSnark(f"Proof Creation failure: {e}") from e
+    return [p if o.status == 0 else TxnApiError.FailedSnark(f"Proof Creation failure: {_lib.prove_outcome_text(o)}")
+            for p, o in zip(proofs, outcomes)]
+
+
 def upload_verifying_key(verifying_key: VerifyingKey) -> int:
     """checks a verifying key once and keeps it for txn_batch_verify -> handle (release with release_verifying_key)"""
     try:

@@ -1029,6 +1029,89 @@ int capgpu_plonk_prove_each_async(const uint64_t* pk_handles, int count, const u
                                   const uint64_t* pub_inputs, size_t num_inputs, const uint8_t* const* ext_msgs,
                                   const size_t* ext_msg_lens, const uint64_t* blinders, int input_form,
                                   capgpu_proof* proofs_out, capgpu_prove_outcome* outcomes_out, uint64_t* ticket_out);
+/* ---- a Vec of notes whose keys have SEVERAL domain sizes (or SRS) in one call --------------------------------------------
+ * The reference proves a Vec<TransactionNote> of transfers, mints and freezes under one into_par_iter()
+ * (src/utils/params_builder.rs:64-241); the mint's domain is half the others'.  One device batch holds keys of one domain
+ * size under one SRS, so capgpu_plonk_prove_each refuses that Vec; these calls take it.  The notes are cut into GROUPS -
+ * all notes whose keys share (domain size, SRS), numbered by first appearance, members in the caller's order - and every
+ * group is proved as ONE batch, exactly as capgpu_plonk_prove_each proves it.
+ * These are outcome calls: everything capgpu_plonk_prove_each[_dev,_async] says about the return value (CAPGPU_OK whenever
+ * the batch ran), the all-ones record of a failed proof, capgpu_prove_outcome[_text], borrowed ticket pointers, the pointer
+ * checks before a device is looked for, capgpu_plonk_shard_msm (CAPGPU_ERR_INVALID_ARG) and count == 0 holds here too.
+ *   WITNESSES, host form.  wires[i] points to note i's own witness as capgpu_plonk_prove_ex takes it for that key:
+ *   5 n_i elements (CAPGPU_INPUT_EVALS / _COEFFS), or the key's num_vars values (CAPGPU_INPUT_VARS) - not padded to the
+ *   call's largest.  The blocks are read where they are: no host copy is made to bring a group together.
+ *   WITNESSES, device form.  wire_offsets[i] is the offset of note i's block, in field elements (32 bytes), from d_wires;
+ *   blocks have the lengths above and may lie in any order.  d_wires must be 16-byte aligned.  The buffer is never written.
+ *   pub_inputs, blinders: capgpu_plonk_verify_block_dev's convention - `count` rows of num_inputs, at least the largest
+ *   count among ALL the call's keys, a key with fewer inputs using the first of its row; blinders is count * 13.  The arrays a
+ *   notes call took and the proofs it wrote go into the block verifier as they are.
+ *   ORDER OF THE CHECKS.  (1) an unknown input_form; (2) the pointers: count < 0, or count > 0 with a NULL pk_handles,
+ *   wires (d_wires, wire_offsets), blinders, proofs_out or outcomes_out, a NULL pub_inputs with num_inputs > 0, ext_msgs
+ *   without ext_msg_lens, a NULL ticket_out: "capgpu_plonk_prove_notes: bad argument"; (3) host form: a NULL wires[i]
+ *   ("capgpu_plonk_prove_notes: wires[i] is NULL"); device form: a d_wires that is not 16-byte aligned - all
+ *   CAPGPU_ERR_INVALID_ARG and made before a device is looked for; (4) CAPGPU_ERR_NOT_INITIALISED; (5) count == 0: CAPGPU_OK,
+ *   nothing written; (6) capgpu_plonk_shard_msm on; (7) the keys, note by note: an unknown handle (CAPGPU_ERR_BAD_HANDLE), a
+ *   key of the reference-schedule test mode (CAPGPU_RECOMPUTE_PK_COSET), CAPGPU_INPUT_VARS with a key that has no table;
+ *   (8) num_inputs smaller than the largest count among the keys ("capgpu_plonk_prove_notes: rows of A public inputs
+ *   given, the keys need B").  Two faults at once give the earlier one.
+ *   THE CONTRACT.  For every note i, proofs_out[i] and outcomes_out[i] are bit for bit what capgpu_plonk_prove_each writes
+ *   for that note when called with the notes of i's group alone, in the same modes; a surviving proof is therefore the lone
+ *   capgpu_plonk_prove_ex's.  A call whose keys form ONE group goes down capgpu_plonk_prove_each's own path: same launches,
+ *   same dealing in contiguous cuts, same graph signatures.
+ *   HOW A CALL RUNS.  Groups START by count * n descending (ties: group number).  Host form, unbound thread, more than one
+ *   context, two or more groups: every group is one part, whole, on a context of its own - at most as many at a time as
+ *   capgpu_plonk_prove_each cuts a batch into, the idle contexts first in slot order; a context that finishes takes the
+ *   next group.  A bound thread, a single context, an entry from inside the library: the groups run one after the other on
+ *   that context.  A ticket runs whole on the context its worker got; keys and messages are copied at submission.  The
+ *   device form runs on the calling thread's context and stream: a group whose members' blocks lie at ONE constant stride
+ *   in member order (evals / coeffs: exactly 5 n; variables: any constant stride of at least the group's largest num_vars)
+ *   is proved where it lies - capgpu_plonk_prove_each_dev's rules, compaction's among them -; any other group is gathered
+ *   into library staging by one copy kernel and is "library staging" from there on.  Precheck, compaction (per group),
+ *   both transcript homes, both wire-commit modes, graphs, capgpu_set_stream and capgpu_set_memory_limit are honoured.
+ *   ERRORS.  A group that fails with a code (CAPGPU_ERR_OOM, HIP) does not stop the groups already running; the call
+ *   returns the code and message of the first failed group in run order, and what proofs_out holds is then unspecified.
+ * capgpu_plonk_notes_plan needs no device: it reports the groups such a call would form (records in group order; cap smaller
+ * than their number fills cap records and still reports the number) and, group_of_out not NULL, every note's group.
+ * capgpu_plonk_reserve_notes sizes context `slot` (-1: every context) for the largest need over the call's groups in the
+ * modes in force, host and device form (the gather's staging included), and brings every key, its SRS and its
+ * Lagrange-form commit key there: a following notes call of the same shape leaves capgpu_scratch_stats where it was.
+ * capgpu_plonk_notes_stats: process-wide counters since capgpu_init; `out` must not be NULL.
+ * LEFT OUT: given-value and all-or-nothing forms over several domain sizes; the device form's groups on sibling contexts;
+ * splitting one heavy group beside a light one; any mixing of domain sizes inside a launch. */
+typedef struct capgpu_notes_group {
+  uint64_t srs_handle;
+  uint64_t domain_size;
+  uint32_t count;      /* notes of the group */
+  uint32_t first;      /* its lowest note index */
+  uint32_t max_inputs; /* the largest num_inputs among its keys */
+  uint32_t run_order;  /* 0: starts first */
+} capgpu_notes_group;  /* 32 bytes */
+typedef struct capgpu_notes_stats {
+  uint64_t calls;               /* notes calls (tickets when they run) that got past their checks */
+  uint64_t groups;              /* groups they proved */
+  uint64_t groups_dealt;        /* ... of which on a context the deal chose, not the caller's own */
+  uint64_t contexts_dealt;      /* contexts those deals used, summed over the calls */
+  uint64_t dev_groups_direct;   /* device form: groups proved where they lay, without a copy */
+  uint64_t dev_groups_gathered; /* device form: groups gathered into library staging ... */
+  uint64_t rows_gathered;       /* ... and the rows that moved */
+} capgpu_notes_stats;           /* 56 bytes */
+int capgpu_plonk_prove_notes(const uint64_t* pk_handles, int count, const uint64_t* const* wires,
+                             const uint64_t* pub_inputs, size_t num_inputs, const uint8_t* const* ext_msgs,
+                             const size_t* ext_msg_lens, const uint64_t* blinders, int input_form,
+                             capgpu_proof* proofs_out, capgpu_prove_outcome* outcomes_out);
+int capgpu_plonk_prove_notes_dev(const uint64_t* pk_handles, int count, const void* d_wires, const uint64_t* wire_offsets,
+                                 const uint64_t* pub_inputs, size_t num_inputs, const uint8_t* const* ext_msgs,
+                                 const size_t* ext_msg_lens, const uint64_t* blinders, int input_form,
+                                 capgpu_proof* proofs_out, capgpu_prove_outcome* outcomes_out);
+int capgpu_plonk_prove_notes_async(const uint64_t* pk_handles, int count, const uint64_t* const* wires,
+                                   const uint64_t* pub_inputs, size_t num_inputs, const uint8_t* const* ext_msgs,
+                                   const size_t* ext_msg_lens, const uint64_t* blinders, int input_form,
+                                   capgpu_proof* proofs_out, capgpu_prove_outcome* outcomes_out, uint64_t* ticket_out);
+int capgpu_plonk_notes_plan(const uint64_t* pk_handles, int count, capgpu_notes_group* groups_out, size_t cap,
+                            size_t* num_groups_out, uint32_t* group_of_out);
+int capgpu_plonk_reserve_notes(const uint64_t* pk_handles, int count, int input_form, int slot);
+int capgpu_plonk_notes_stats(capgpu_notes_stats* out);
 /* ---- proving from the values a circuit is GIVEN -----------------------------------------------------------------------
  * One call from given values to proofs: the solver (capgpu_plonk_key_set_given) and the variable-form outcome call, fused.
  * These are outcome calls: everything capgpu_plonk_prove_each[_dev,_async] says about arguments, layouts, the return value

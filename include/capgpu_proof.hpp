@@ -508,6 +508,61 @@ Result<std::vector<ProveEachEntry>> prove_each(Rng& rng, const std::vector<const
   return out;
 }
 
+// prove_each over keys of SEVERAL domain sizes (or SRS) - the reference's Vec<TransactionNote> of transfers, mints and
+// freezes - in ONE call (capgpu_plonk_prove_notes): assignment i belongs to key i, all in the input form of the first, and
+// is read where it is - no row array is built.  Every entry is bit for bit what prove_each makes of the notes of its
+// group (same domain size and SRS) alone.  Err only when the call could not run.
+template <class Rng>
+Result<std::vector<ProveEachEntry>> prove_notes(Rng& rng, const std::vector<const ProvingKey*>& pks,
+                                                const std::vector<Assignment>& as,
+                                                const std::vector<std::vector<uint8_t>>* ext_msgs = nullptr) {
+  const size_t count = pks.size();
+  if (as.size() != count || (ext_msgs && ext_msgs->size() != count))
+    return TxnApiError::failed_snark("prove_notes: one assignment (and message) per key");
+  std::vector<ProveEachEntry> out(count);
+  if (!count) return out;
+  size_t ni = 0;
+  std::vector<uint64_t> handles(count);
+  std::vector<const uint64_t*> rows(count);
+  for (size_t i = 0; i < count; i++) {
+    if (!pks[i] || !as[i].wires || (!as[i].pub_inputs && pks[i]->num_inputs()) || as[i].input_form != as[0].input_form)
+      return TxnApiError::failed_snark("prove_notes: empty assignment, or assignments of different input forms");
+    handles[i] = pks[i]->handle();
+    rows[i] = as[i].wires;
+    ni = std::max(ni, pks[i]->num_inputs());
+  }
+  std::vector<uint64_t> pubs(count * ni * 4 + 4, 0), blinders(count * 13 * 4);
+  std::vector<const uint8_t*> mp(count, nullptr);
+  std::vector<size_t> ml(count, 0);
+  for (size_t i = 0; i < count; i++) {
+    if (pks[i]->num_inputs()) std::memcpy(&pubs[i * ni * 4], as[i].pub_inputs, pks[i]->num_inputs() * 32);
+    for (int k = 0; k < 13; k++) {  // drawn in note order, as count calls of prove() would draw them
+      Fr b = rng();
+      std::memcpy(&blinders[(i * 13 + k) * 4], b.data(), 32);
+    }
+    if (ext_msgs && !(*ext_msgs)[i].empty()) {
+      mp[i] = (*ext_msgs)[i].data();
+      ml[i] = (*ext_msgs)[i].size();
+    }
+  }
+  std::vector<Proof> proofs(count);
+  std::vector<capgpu_prove_outcome> oc(count);
+  const int rc = capgpu_plonk_prove_notes(handles.data(), (int)count, rows.data(), ni ? pubs.data() : nullptr, ni,
+                                          ext_msgs ? mp.data() : nullptr, ext_msgs ? ml.data() : nullptr, blinders.data(),
+                                          as[0].input_form, proofs.data(), oc.data());
+  if (rc != CAPGPU_OK) return detail::map_error(rc, "prove_notes");
+  for (size_t i = 0; i < count; i++) {
+    if (oc[i].status == CAPGPU_OK) {
+      out[i].proof = proofs[i];
+      continue;
+    }
+    char text[512];
+    capgpu_prove_outcome_text(&oc[i], text, sizeof text);
+    out[i].error = text;
+  }
+  return out;
+}
+
 // The form of the schedule a key's solver runs (capgpu_plonk_key_set_solve_form): CAPGPU_SOLVE_FORM_DIRECT, what every
 // set-up call leaves, or CAPGPU_SOLVE_FORM_DEFERRED, which inverts the denominators of a chain of additions together.  Either
 // form gives prove_given the same assignments and the same proofs.  The key needs a solver.
