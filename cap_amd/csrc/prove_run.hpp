@@ -15,34 +15,14 @@
 #include "outcome.hpp"
 #include "params.hpp"
 #include "plonk_kernels.hpp"
+#include "round_launch.hpp"
 #include "transcript_dev.hpp"
 #include "vars_kernels.hpp"
 
 namespace cap {
 namespace {
 
-// ---- launch helpers -----------------------------------------------------------------------------------------
-inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
-
-void pad_copy(hipStream_t s, fe* dst, size_t dst_outer, size_t dst_inner, const fe* src, size_t src_outer,
-              size_t src_inner, uint32_t inner, uint32_t count, size_t len, size_t total) {
-  if (count == 0 || total == 0) return;
-  launch("k_pad_copy", k_pad_copy, dim3(cdiv(total, kThreads), count), dim3(kThreads), 0, s, dst, dst_outer, dst_inner,
-         src, src_outer, src_inner, inner, len, total);
-}
-
-template <int OP, int REV>
-void scan_exclusive(hipStream_t s, const fe* in, fe* out, size_t len, size_t stride, uint32_t batch, fe* tot) {
-  uint32_t nblocks = cdiv(len, kScanBlock);
-  launch(OP == 0 ? "k_scan_local_mul" : "k_scan_local_add", k_scan_local<OP, REV>, dim3(nblocks, batch), dim3(kThreads),
-         0, s, in, out, len, stride, tot, nblocks);
-  if (nblocks > 1) {
-    launch("k_scan_totals", k_scan_totals<OP>, dim3(batch), dim3(64), 0, s, tot, nblocks);
-    launch("k_scan_apply", k_scan_apply<OP, REV>, dim3(nblocks, batch), dim3(kThreads), 0, s, out, len, stride,
-           (const fe*)tot, nblocks);
-  }
-}
-
+// ---- launch helpers (the round kernels' own: round_launch.hpp) ----------------------------------------------------
 // Bytes of Context::ntt_scratch the transforms below ask for.  One expression each, shared with the `*_needs` of ProveRun
 // (capgpu_plonk_reserve sizes a context ahead from what a proving call WOULD request).
 inline size_t ntt_scratch_inplace(size_t stride, size_t count) { return sizeof(fe) * stride * count; }
@@ -213,7 +193,6 @@ struct BatchWs {
   int32_t* status;
   size_t total;
 };
-constexpr uint32_t kEvalChunks = 16;
 constexpr uint32_t kLinTerms = 29;
 static_assert(oc::kCheckNoFault == pk::kNoFault && sizeof(pk::CheckOut::first) == sizeof(unsigned long long),
               "k_prove_outcomes reads the witness check's verdicts (CheckOut::first)");
@@ -280,8 +259,7 @@ int compute_pk_coset(hipStream_t s, const ProvingKey& K, fe* dst) {
 int compute_pk_kx(hipStream_t s, const ProvingKey& K, fe* dst) {
   const Ntt3Domain* dq = nullptr;
   if (int rc = get_domain3(K.log_m, &dq)) return rc;
-  launch("k_kx_columns", k_kx_columns, dim3(cdiv(K.m, kThreads)), dim3(kThreads), 0, s, dst + (size_t)18 * K.m,
-         (const fe*)dq->xs29, K.qc29, K.m);
+  kx_columns(s, dst + (size_t)18 * K.m, (const fe*)dq->xs29, K.qc29, K.m);
   return CAPGPU_OK;
 }
 // CAPGPU_QUOT_FOLD (read per call): 1, the default - k_quotient's permutation terms with beta folded out; 0 - the direct
@@ -989,8 +967,7 @@ struct ProveRun {
     int r;
     const hipStream_t s2 = pl.s2;
     const MsmBases* const Lag = pl.Lag;
-    launch("k_perm_finish", k_perm_finish, dim3(cdiv(ps, kThreads), P), dim3(kThreads), 0, s, (const fe*)w.pre,
-           (const fe*)w.sfx, (const fe*)w.den, (const fe*)w.inv_total, n, w.zpoly, ps);
+    perm_finish(s, w.pre, w.sfx, w.den, w.inv_total, n, P, w.zpoly, ps);
     auto interpolate_and_blind = [&](hipStream_t st) -> int {
       int q = run_ntt(st, K.log_n, w.zpoly, ps, P, 1, 0);
       if (q) return q;
@@ -1020,9 +997,8 @@ struct ProveRun {
     nd.msm(pl.wire_key(), K.n + 3, cnt);
   }
   int r2_body() {
-    launch("k_perm_numden", k_perm_numden, dim3(cdiv(n, kThreads), P), dim3(kThreads), 0, s,
-           pl.coeffs ? (const fe*)w.wev : d_wires, (const fe*)K.sig_eval, sig_of, (const fe*)dom_n->tw_fwd,
-           (const Chal*)w.chal, K.qc29, n, w.num, w.den);
+    perm_numden(s, pl.coeffs ? (const fe*)w.wev : d_wires, K.sig_eval, sig_of, dom_n->tw_fwd, w.chal, K.qc29, n, P, w.num,
+                w.den);
     {
       uint32_t nb = cdiv(n, kScanBlock);
       scan_exclusive<0, 0>(s, w.num, w.pre, n, n, P, w.scan_tot);
@@ -1030,11 +1006,9 @@ struct ProveRun {
     }
     if (pl.inv_on_device) {
       // (the product is a function of the secret witness: the device kernel runs a fixed-length chain, as the host does)
-      launch("k_perm_inv_total", k_perm_inv_total, dim3(cdiv(P, 64)), dim3(64), 0, s, (const fe*)w.sfx,
-             (const fe*)w.den, n, w.inv_total, P);
+      perm_inv_total(s, w.sfx, w.den, n, w.inv_total, P);
     } else {
-      launch("k_perm_total", k_perm_total, dim3(cdiv(P, 64)), dim3(64), 0, s, (const fe*)w.sfx, (const fe*)w.den, n,
-             w.inv_total, P);
+      perm_total(s, w.sfx, w.den, n, w.inv_total, P);
       return CAPGPU_OK;  // the segment ends here: the host inverts the totals (run_host_transcript)
     }
     return finish_and_commit_z();
@@ -1059,22 +1033,18 @@ struct ProveRun {
     const uint32_t five = pl.five ? 1u : 0u;
     const size_t pts = pl.five ? 5 * n : m;
     if (fold)
-      launch("k_quotient", k_quotient<true>, dim3(P, cdiv(pts, kThreads)), dim3(kThreads), 0, s, pkc, pkc_of,
-             (const fe*)w.coset, (const fe*)dom_q->xs29, (const fe*)K.inv_nx1, (const Chal*)w.chal29, K.qc29, m, 1u, five,
-             w.t);
+      quotient<true>(s, P, pts, pkc, pkc_of, w.coset, dom_q->xs29, K.inv_nx1, w.chal29, K.qc29, m, 1u, five, w.t);
     // the direct form: for every proof (fold = 0), or behind the folded launch for the proofs it left out - beta = 0.
     // The host transcript knows whether there is one; the device transcript does not, and its launch is P x m / 256
     // workgroups that load one word and leave.
     if (!fold || fold == 2 || beta_zero_possible)
-      launch("k_quotient_direct", k_quotient<false>, dim3(P, cdiv(pts, kThreads)), dim3(kThreads), 0, s,
-             pkc, pkc_of, (const fe*)w.coset, (const fe*)dom_q->xs29, (const fe*)K.inv_nx1, (const Chal*)w.chal29, K.qc29, m,
-             fold ? 1u : 0u, five, w.t);
+      quotient<false>(s, P, pts, pkc, pkc_of, w.coset, dom_q->xs29, K.inv_nx1, w.chal29, K.qc29, m, fold ? 1u : 0u, five,
+                      w.t);
     // k_quotient leaves the public-input term out; it arrives here as coefficients (pi_fold), before the degree check
     if (pl.five) {
       // the top 8 coefficients from the polynomials; then what the sixth coset used to witness - that the numerator is
       // divisible by Z_H at all - is tested on the rows themselves (k_rows_verdict): bit 1 of the flags, as before
-      launch("k_quotient_top", k_quotient_top, dim3(P), dim3(64), 0, s, (const fe*)w.wpoly, (const fe*)w.zpoly,
-             (const fe*)K.coef, coef_of, (const fe*)dom_n->tw_fwd, (const Chal*)w.chal, n, ps, w.top);
+      quotient_top(s, P, w.wpoly, w.zpoly, K.coef, coef_of, dom_n->tw_fwd, w.chal, n, ps, w.top);
       launch("k_check_gates", k_check_gates, dim3(cdiv(n, kThreads), P), dim3(kThreads), 0, s,
              pl.coeffs ? (const fe*)w.wev : d_wires, (const fe*)w.d_pub, num_inputs, (const CheckKey*)w.chk_keys, n, w.chk_out);
       launch("k_rows_verdict", k_rows_verdict, dim3(cdiv(P, 64)), dim3(64), 0, s, (const CheckOut*)w.chk_out,
@@ -1085,8 +1055,7 @@ struct ProveRun {
     }
     {
       size_t lo = NW * (n + 1) + 3;  // first index that must be zero: degree is exactly 5(n+1)+2
-      launch("k_check_degree", k_check_degree, dim3(cdiv(m - (lo - 1), kThreads), P), dim3(kThreads), 0, s,
-             (const fe*)w.t, m, lo, w.flags);
+      check_degree(s, P, w.t, m, lo, w.flags);
     }
     return run_msm(s, *pl.B, w.t, m, NW, n + 2, n + 2, P * NW, w.comms);
   }
@@ -1111,16 +1080,8 @@ struct ProveRun {
     return ed;
   }
   int r4_body() {
-    const uint32_t small_len = kPowLow + cdiv(ps, kPowLow);
-    launch("k_powers_small", k_powers_small, dim3(cdiv(small_len, kThreads), P * 4), dim3(kThreads), 0, s,
-           w.pows_small, small_len, (const fe*)w.pw);
-    launch("k_powers", k_powers, dim3(cdiv(ps, kThreads), P * 4), dim3(kThreads), 0, s, w.pows, ps, ps,
-           (const fe*)w.pows_small, small_len);
-    uint32_t per_chunk = cdiv(n + 3, kEvalChunks);
-    launch("k_eval_partial", k_eval_partial, dim3(kEvalChunks, P * 10), dim3(kThreads), 0, s,
-           (const EvalDesc*)w.edesc, w.eval_partial, kEvalChunks, per_chunk);
-    launch("k_eval_final", k_eval_final, dim3(P * 10), dim3(64), 0, s, (const fe*)w.eval_partial, kEvalChunks,
-           w.evals);
+    powers(s, P * 4, w.pw, w.pows_small, w.pows, ps);
+    evaluate(s, P * 10, w.edesc, n + 3, w.eval_partial, w.evals);
     return CAPGPU_OK;
   }
 
@@ -1143,15 +1104,10 @@ struct ProveRun {
   }
   // batchpoly[p][0] = linear combination, batchpoly[p][1] = z polynomial
   int r5_body() {
-    launch("k_lincomb", k_lincomb, dim3(cdiv(ps, kThreads), P), dim3(kThreads), 0, s, (const LinTerm*)w.terms,
-           kLinTerms, w.batchpoly, 2 * ps, ps);
+    lincomb(s, P, w.terms, kLinTerms, w.batchpoly, 2 * ps, ps);
     pad_copy(s, w.batchpoly + ps, 2 * ps, 0, w.zpoly, ps, 0, 1, P, n + 3, ps);
-    launch("k_div_prepare", k_div_prepare, dim3(cdiv(n + 3, kThreads), P * 2), dim3(kThreads), 0, s,
-           (const fe*)w.batchpoly, (const fe*)w.pows, ps, n + 3, w.hbuf);
     // the suffix sums go to batchpoly (its contents are dead once h is formed)
-    scan_exclusive<1, 1>(s, w.hbuf, w.batchpoly, n + 3, ps, P * 2, w.scan_tot);
-    launch("k_div_finish", k_div_finish, dim3(cdiv(ps, kThreads), P * 2), dim3(kThreads), 0, s,
-           (const fe*)w.batchpoly, (const fe*)w.pows, ps, n + 3, w.quot);
+    divide_linear(s, P * 2, w.batchpoly, w.pows, ps, n + 3, w.hbuf, w.scan_tot, w.quot);
     return run_msm(s, *pl.B, w.quot, ps, 1, 0, n + 2, P * 2, w.comms);
   }
   static void r5_needs(const ProvePlan& pl, const ProvingKey& K, uint32_t cnt, ProveNeeds& nd) {

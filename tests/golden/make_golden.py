@@ -83,6 +83,28 @@ def proof_vector():
             "wire_sigma_evals": [hx(v) for v in pr.wire_sigma_evals], "perm_next_eval": hx(pr.perm_next_eval)}
 
 
+def proof_log16_vector():
+    """n = 2^16, the size bench.py reports a rate for and no other test proves: the C oracle's key (about 22 s) and proof
+    (about 26 s) - the Python oracle would take hours - under the test suite's tau.  Same fields as proof_log5.json."""
+    from oracle import capref as cr
+    from tests import helpers as H
+    tau = bn.SplitMix64(0xCA9).field(bn.R)
+    sc = bu.synthetic_circuit(16, 3, seed=16)
+    w, pubs = sc.witness(1600)
+    key = cr.PlonkKey(H.srs_powers(tau, sc.n + 3), sc.n, 3, sc.selectors_mont(), sc.sigma_mont())
+    rc, comms, evals = key.prove(sc.wires_mont(w), bu.to_mont_array(pubs), bu.to_mont_array(bu.blinders(1601)), b"memo-key-16")
+    assert rc == 0
+    pts, ev = H.cref_proof_points(comms, evals)
+    vk = [cr.affine_to_ints(c) for c in key.vk_comms]
+    return {"log_n": 16, "num_inputs": 3, "circuit_seed": 16, "witness_seed": 1600, "blinder_seed": 1601,
+            "tau_seed": 0xCA9, "ext_msg": "memo-key-16",
+            "selector_comms": [pt(p) for p in vk[:13]], "sigma_comms": [pt(p) for p in vk[13:]],
+            "wires_poly_comms": [pt(p) for p in pts[0:5]], "prod_perm_poly_comm": pt(pts[5]),
+            "split_quot_poly_comms": [pt(p) for p in pts[6:11]], "opening_proof": pt(pts[11]),
+            "shifted_opening_proof": pt(pts[12]), "wires_evals": [hx(v) for v in ev[0:5]],
+            "wire_sigma_evals": [hx(v) for v in ev[5:9]], "perm_next_eval": hx(ev[9])}
+
+
 def params_vector():
     """On-disk formats (oracle/params.py) for the log-5 circuit of proof_log5.json under the same tau."""
     tau = bn.SplitMix64(0xCA9).field(bn.R)
@@ -113,8 +135,11 @@ def params_vector():
 
 
 if __name__ == "__main__":
+    # python tests/golden/make_golden.py proof_log16.json ...: only the files named
     for name, fn in (("msm.json", msm_vectors), ("ntt.json", ntt_vectors), ("proof_log5.json", proof_vector),
-                     ("params.json", params_vector)):
+                     ("params.json", params_vector), ("proof_log16.json", proof_log16_vector)):
+        if sys.argv[1:] and name not in sys.argv[1:]:
+            continue
         with open(os.path.join(HERE, name), "w") as f:
             json.dump(fn(), f, indent=0)
         print("wrote", name)
