@@ -36,8 +36,7 @@
 #include "pairing_wave.hpp"
 #include "proof_codec.hpp"
 #include "srs_check.hpp"
-#include "verify_front.hpp"
-#include "verify_terms.hpp"
+#include "verify_launch.hpp"
 
 namespace cap {
 namespace {
@@ -258,171 +257,9 @@ int verify_each(const capgpu_verifying_key* const* vks, const pairing::g2_affine
 
 // ---- the block verifier: front end, weights, fold, two one-shot MSMs, one check (K13) -----------------------------------
 // capgpu_plonk_verify_block_dev / _resident: everything from the proofs' bytes to the verdicts is enqueued on the
-// context's stream and the host waits once.  verify_front.hpp has the term order and the weight rule.
-struct FrontArgs {
-  const uint8_t* proofs;          // count x capgpu_proof
-  const fe* pubs;                 // count rows of pub_stride
-  const vf::DevVk* const* keys;   // the call's keys
-  const uint32_t* meta;           // per proof: key index, message offset, message length, 0
-  const uint8_t* msgs;
-  uint8_t *state, *pre, *app, *ubytes;  // per proof: 64, pre_stride, vf::kAppBytes, 32 bytes
-  int* valid;
-  fe* sc;                         // count x vf::kTerms
-  uint32_t pub_stride, pre_stride, count;
-};
-
-// proof p's point of own term t (< vf::kOwnTerms): the 13 points of a capgpu_proof are contiguous
-__device__ __forceinline__ uint32_t own_point_offset(uint32_t t) {
-  if (t == vf::kTermWzeta || t == vf::kTermBWzeta) return td::kPrOpen;
-  if (t == vf::kTermWzetaW || t == vf::kTermBWzetaW) return td::kPrShifted;
-  return 64 * (t - vf::kTermWires);  // wires, z, quotient parts in the struct's order
-}
-
-// One wavefront per proof: verify.hip's verifier_terms, in its order.  Lanes 0..12 check and compress the proof's points,
-// lanes 13..22 its evaluations, all lanes stride over the public inputs, the message and the key's prefix; the wavefront
-// draws the seven challenges; the lanes stride over PI(zeta); lane 0 derives the scalars.
-__global__ __launch_bounds__(64) void k_verify_front(FrontArgs a) {
-  __shared__ fe sh[64];
-  const uint32_t p = blockIdx.x, t = threadIdx.x;
-  if (p >= a.count) return;
-  const uint8_t* pr = a.proofs + (size_t)p * td::kPrBytes;
-  const uint32_t moff = a.meta[4 * p + 1], mlen = a.meta[4 * p + 2];
-  const vf::DevVk* vk = a.keys[a.meta[4 * p]];
-  const uint32_t nin = vk->num_inputs;
-  const fe* pubs = a.pubs + (size_t)p * a.pub_stride;
-  uint8_t* pre = a.pre + (size_t)p * a.pre_stride;
-  uint8_t* app = a.app + (size_t)p * vf::kAppBytes;
-  uint8_t* st = a.state + (size_t)p * 64;
-  fe* sc = a.sc + (size_t)p * vf::kTerms;
-  bool ok = true;
-  if (t < 13) {
-    const g1_affine pt = *(const g1_affine*)(pr + 64 * t);
-    ok = vf::g1_valid(pt);
-    td::compress_g1(pt, app + (t < 11 ? 32 * t : 32 * (t + 10)));  // the two openings follow the ten evaluations
-  } else if (t < 23) {
-    const fe e = *(const fe*)(pr + td::kPrWireEvals + 32 * (t - 13));
-    ok = !Fr::geq_mod(e);
-    td::serialize_fr(e, app + td::kAppEvals + 32 * (t - 13));
-  }
-  for (uint32_t j = t; j < nin; j += 64) {
-    const fe v = pubs[j];
-    ok = ok && !Fr::geq_mod(v);
-    td::serialize_fr(v, pre + mlen + vf::kPrefixBytes + 32 * j);
-  }
-  for (uint32_t k = t; k < mlen; k += 64) pre[k] = a.msgs[moff + k];
-  for (uint32_t k = t; k < vf::kPrefixBytes; k += 64) pre[mlen + k] = vk->prefix[k];
-  st[t] = 0;
-  bool valid = __syncthreads_and(ok) != 0;
-  fe beta, gamma, alpha, zeta, v, u, zh;
-  if (valid) {
-    td::KeccakTabs<td::LaneDev> tabs;
-    tabs.init();
-    const uint32_t lpre = mlen + vf::kPrefixBytes + 32 * nin;
-    auto draw = [&](uint32_t lapp) {
-      td::transcript_challenge<td::LaneDev>(st, pre, lpre, app, lapp, tabs);
-      return td::reduce48(st);
-    };
-    (void)draw(td::kAppZ);  // plookup's tau
-    beta = draw(td::kAppZ);
-    gamma = draw(td::kAppZ);
-    alpha = draw(td::kAppQuot);
-    zeta = draw(td::kAppEvals);
-    v = draw(vf::kAppOpen);
-    u = draw(vf::kAppBytes);
-    valid = vf::vanishing(zeta, vk->n, &zh);
-  }
-  if (!valid) {  // uniform: every lane saw the same flags and challenges
-    for (uint32_t k = t; k < vf::kTerms; k += 64) sc[k] = Fr::zero();
-    if (t < 32) a.ubytes[(size_t)p * 32 + t] = 0;
-    if (t == 0) a.valid[p] = 0;
-    return;
-  }
-  sh[t] = vf::pi_partial(pubs, nin, t, 64, zeta, zh, vk->omega, vk->n_mont);
-  __syncthreads();
-  if (t == 0) {
-    fe pi = sh[0];
-#pragma unroll 1
-    for (int i = 1; i < 64; i++) pi = Fr::add(pi, sh[i]);
-    const vf::FrontIn in{(const fe*)(pr + td::kPrWireEvals), vk->k, beta, gamma, alpha, zeta, v, u, vk->omega, vk->n_mont,
-                         zh, pi, vk->n};
-    vf::front_scalars(in, sc);
-    td::serialize_fr(u, a.ubytes + (size_t)p * 32);
-    a.valid[p] = 1;
-  }
-}
-
-// S = Keccak-256 of the block's u bytes: one wavefront
-__global__ __launch_bounds__(64) void k_verify_seed(const uint8_t* __restrict__ ubytes, uint32_t count, uint8_t* __restrict__ S) {
-  td::KeccakTabs<td::LaneDev> tabs;
-  tabs.init();
-  vf::weight_seed<td::LaneDev>(ubytes, count, tabs, S);
-}
-// r_i, one wavefront per proof
-__global__ __launch_bounds__(64) void k_verify_weights(const uint8_t* __restrict__ S, uint32_t count, fe* __restrict__ w) {
-  __shared__ uint8_t idx8[8], dig[32];
-  const uint32_t i = blockIdx.x;
-  if (i >= count) return;
-  td::KeccakTabs<td::LaneDev> tabs;
-  tabs.init();
-  const fe r = vf::weight<td::LaneDev>(S, i, tabs, idx8, dig);
-  if (threadIdx.x == 0) w[i] = r;
-}
-
-// The points and weighted scalars of the two MSMs: A over [0, 2 count), B's own terms over the next 13 count.  One thread
-// per (proof, own term).  An invalid proof contributes points at infinity and zero scalars.
-__global__ __launch_bounds__(64) void k_verify_gather(const uint8_t* __restrict__ proofs, const fe* __restrict__ sc,
-                                                      const fe* __restrict__ w, const int* __restrict__ valid,
-                                                      uint32_t count, g1_affine* __restrict__ pts, fe* __restrict__ out) {
-  const uint32_t g = blockIdx.x * 64 + threadIdx.x;
-  if (g >= count * vf::kOwnTerms) return;
-  const uint32_t i = g / vf::kOwnTerms, t = g % vf::kOwnTerms;
-  const uint32_t at = t < vf::kATerms ? vf::kATerms * i + t
-                                      : vf::kATerms * count + (vf::kOwnTerms - vf::kATerms) * i + (t - vf::kATerms);
-  g1_affine pt;
-  fe s = Fr::zero();
-  pt.x = Fq::zero();
-  pt.y = Fq::zero();
-  if (valid[i]) {
-    pt = *(const g1_affine*)(proofs + (size_t)i * td::kPrBytes + own_point_offset(t));
-    s = Fr::mul(w[i], sc[(size_t)i * vf::kTerms + t]);
-  }
-  pts[at] = pt;
-  out[at] = s;
-}
-// Block (k, j): sum over the valid proofs i of key k of r_i s_ij for key term j, lanes striding over the proofs; written
-// with the key's point behind the own terms of B
-__global__ __launch_bounds__(64) void k_verify_fold(const vf::DevVk* const* __restrict__ keys,
-                                                    const uint32_t* __restrict__ meta, const fe* __restrict__ sc,
-                                                    const fe* __restrict__ w, const int* __restrict__ valid,
-                                                    uint32_t count, g1_affine* __restrict__ pts, fe* __restrict__ out) {
-  __shared__ fe sh[64];
-  const uint32_t k = blockIdx.x, j = blockIdx.y, t = threadIdx.x;
-  fe acc = Fr::zero();
-  for (uint32_t i = t; i < count; i += 64)
-    if (meta[4 * i] == k && valid[i]) acc = Fr::add(acc, Fr::mul(w[i], sc[(size_t)i * vf::kTerms + vf::kOwnTerms + j]));
-  sh[t] = acc;
-  __syncthreads();
-  for (uint32_t s = 32; s >= 1; s >>= 1) {
-    if (t < s) sh[t] = Fr::add(sh[t], sh[t + s]);
-    __syncthreads();
-  }
-  if (t == 0) {
-    const uint32_t at = vf::kOwnTerms * count + vf::kKeyTerms * k + j;
-    pts[at] = keys[k]->pts[j];
-    out[at] = sh[0];
-  }
-}
-// the two sums to affine form, B negated: what the check takes
-__global__ __launch_bounds__(64) void k_verify_affine(const g1_jac* __restrict__ sums, g1_affine* __restrict__ a_out,
-                                                      g1_affine* __restrict__ negb_out) {
-  if (blockIdx.x || threadIdx.x) return;
-  const g1_jac in[2] = {sums[0], sums[1]};
-  g1_affine o[2];
-  td::to_affine(in, 2, o);
-  if (!G1::is_inf(o[1])) o[1].y = Fq::neg(o[1].y);
-  a_out[0] = o[0];
-  negb_out[0] = o[1];
-}
+// context's stream and the host waits once.  verify_front.hpp has the term order and the weight rule, verify_kernels.hpp
+// the kernels up to the two sums, verify_launch.hpp their launch sequence (tests/hip/verifycheck.hip runs the same).
+using vk::own_point_offset;
 // The unweighted terms of every proof for k_verify_terms: one thread per (proof, term); scalars as canonical integers
 __global__ __launch_bounds__(64) void k_verify_each_terms(const uint8_t* __restrict__ proofs,
                                                           const vf::DevVk* const* __restrict__ keys,
@@ -660,22 +497,14 @@ int verify_block(const char* who, const uint64_t* vk_handles, const uint64_t g2_
   int* d_valid = (int*)(d + o_valid);
   fe *d_sc = (fe*)(d + o_sc), *d_w = (fe*)(d + o_w), *d_msc = (fe*)(d + o_msc);
   g1_affine *d_mpts = (g1_affine*)(d + o_mpts), *d_ab = (g1_affine*)(d + o_ab);
-  FrontArgs fa{d_proofs, d_pubs, d_keys, d_meta, (const uint8_t*)(d + o_msgs), (uint8_t*)(d + o_state),
-               (uint8_t*)(d + o_pre), (uint8_t*)(d + o_app), (uint8_t*)(d + o_ub), d_valid, d_sc,
-               (uint32_t)num_inputs, (uint32_t)pre_stride, n};
-  launch("k_verify_front", k_verify_front, dim3(n), dim3(64), 0, s, fa);
-  launch("k_verify_seed", k_verify_seed, dim3(1), dim3(64), 0, s, (const uint8_t*)(d + o_ub), n, (uint8_t*)(d + o_seed));
-  launch("k_verify_weights", k_verify_weights, dim3(n), dim3(64), 0, s, (const uint8_t*)(d + o_seed), n, d_w);
-  launch("k_verify_gather", k_verify_gather, dim3((n * vf::kOwnTerms + 63) / 64), dim3(64), 0, s, d_proofs,
-         (const fe*)d_sc, (const fe*)d_w, (const int*)d_valid, n, d_mpts, d_msc);
-  launch("k_verify_fold", k_verify_fold, dim3((unsigned)nkeys, vf::kKeyTerms), dim3(64), 0, s, d_keys, d_meta,
-         (const fe*)d_sc, (const fe*)d_w, (const int*)d_valid, n, d_mpts, d_msc);
+  const vk::FrontArgs fa{d_proofs, d_pubs, d_keys, d_meta, (const uint8_t*)(d + o_msgs), (uint8_t*)(d + o_state),
+                         (uint8_t*)(d + o_pre), (uint8_t*)(d + o_app), (uint8_t*)(d + o_ub), d_valid, d_sc,
+                         (uint32_t)num_inputs, (uint32_t)pre_stride, n};
+  const vk::FoldArgs fold{fa, (uint32_t)nkeys, (uint8_t*)(d + o_seed), d_w, d_mpts, d_msc, (const MsmVarDesc*)(d + o_desc),
+                          (g1_jac*)(d + o_sums), c.msm_ws.p, c.msm_ws.cap, d_ab};
+  const int msm_rc = vk::fold_launch(fold, s);  // k_verify_front .. k_verify_affine (verify_launch.hpp)
   if ((rc = take_launch_error())) return rc;
-  rc = msm_var_run(d_mpts, msm_pts, d_msc, 0, (const MsmVarDesc*)(d + o_desc), desc[1].n, 2, 1, (g1_jac*)(d + o_sums),
-                   c.msm_ws.p, c.msm_ws.cap, s);
-  if (rc) return hip_fail((hipError_t)rc, "msm_var_run");
-  launch("k_verify_affine", k_verify_affine, dim3(1), dim3(64), 0, s, (const g1_jac*)(d + o_sums), d_ab, d_ab + 1);
-  if ((rc = take_launch_error())) return rc;
+  if (msm_rc) return hip_fail((hipError_t)msm_rc, "msm_var_run");
   if ((rc = launch_checks(d_ab, d_ab + 1, 1, L->d1.p, L->d2.p, (int*)(d + o_bok), s, CAPGPU_PAIRING_WAVE))) return rc;
   int form = CAPGPU_PAIRING_WAVE;
   if (each_ok_out) {
@@ -974,34 +803,17 @@ int capgpu_plonk_vk_upload(const capgpu_verifying_key* vk, uint64_t* vk_handle_o
     return CAPGPU_ERR_INVALID_ARG;
   }
   auto rec = std::make_shared<VkRecord>();
-  vf::DevVk& k = rec->host;
-  memset(&k, 0, sizeof k);
-  for (int i = 0; i < 5; i++) {
-    memcpy(&k.k[i], vk->k[i], 32);
-    if (Fr::geq_mod(k.k[i])) {
-      set_error("capgpu_plonk_vk_upload: k[%d] is not canonical", i);
-      return CAPGPU_ERR_INVALID_ARG;
-    }
+  const int bad = vf::dev_vk_fill(vk, &rec->host);
+  if (bad >= 0 && bad < 5) {
+    set_error("capgpu_plonk_vk_upload: k[%d] is not canonical", bad);
+    return CAPGPU_ERR_INVALID_ARG;
   }
-  for (int i = 0; i < 18; i++) {
-    const bool sel = i < 13;
-    k.pts[i] = g1_from_abi(sel ? vk->selector_comms[i] : vk->sigma_comms[i - 13]);
-    if (!g1_abi_on_curve(k.pts[i])) {
-      set_error("capgpu_plonk_vk_upload: %s[%d] is not a canonical point of the curve", sel ? "selector_comms" : "sigma_comms",
-                sel ? i : i - 13);
-      return CAPGPU_ERR_INVALID_ARG;
-    }
+  if (bad >= 5) {
+    const bool sel = bad - 5 < 13;
+    set_error("capgpu_plonk_vk_upload: %s[%d] is not a canonical point of the curve", sel ? "selector_comms" : "sigma_comms",
+              sel ? bad - 5 : bad - 18);
+    return CAPGPU_ERR_INVALID_ARG;
   }
-  k.pts[18].x = Fq::one();
-  k.pts[18].y = Fq::dbl(Fq::one());
-  k.n = n;
-  k.num_inputs = (uint32_t)vk->num_inputs;
-  fe nw = Fr::zero();
-  nw.v[0] = (uint32_t)n;
-  nw.v[1] = (uint32_t)(n >> 32);
-  k.n_mont = Fr::to_mont(nw);
-  k.omega = vf::domain_generator(n);
-  vf::prefix_bytes(k, k.prefix);
   const uint64_t hnd = rt().next_handle.fetch_add(1);
   std::lock_guard<std::mutex> lk(g_vk_mu);
   g_vks[hnd] = rec;
