@@ -7,7 +7,13 @@
 // the product phase - which is 1.2x (saturated) to 1.7x (one wave per SIMD) faster, and because
 // 2^261 >> p no conditional subtraction is ever needed: values stay "lazy" (a few multiples of p).
 //
-// Contract (all bounds are checked by tests/host tools with CAP_FL_CHECK):
+// Contract.  The bounds are asserted under CAP_FL_CHECK, which only host programs define (on the GPU CAP_FL_ASSERT is
+// empty): tests/cpp/field29_check.cpp (the operations one by one), curve29 / madd / quad / gate / pairing29 / inv_gcd /
+// solve_* _check.cpp and tests/hip/devcheck_host.cpp, pairing_wave_host.cpp (the code built on them), and
+// tests/cpp/ntt_elem_check.cpp and round_elem_check.cpp (the NTT kernels' stages and element steps, ntt_elem29.hpp, and
+// the bodies of the lazy-field round kernels with ColAcc, round_elem29.hpp - both also on the bound-tracking field of
+// tests/cpp/bound29.hpp, which checks the preconditions for every input of a class: tests/golden/lazy_envelope.json).
+// Not reached by any of them: transcript_dev.hpp.  (The kernels on the saturated field Fr have no lazy bounds.)
 //   * "normalized": limbs 0..7 < 2^29, limb 8 < 2^29  (value < 2^261).
 //   * mul / sqr:  operands with limbs < 2^30 (a normalized value or one lazy sum of two); returns a
 //     normalized value < p * (1 + A*B/169) for operands < A*p, B*p.
@@ -293,6 +299,13 @@ struct Fl {
   }
 
   // ---- weak reduction: normalized x -> normalized value in [0, 2p) ------------------------------------
+  // In fact below (1 + 2^-10) p, and never above x: with MU > 2^272/p - 1 and x_8 > x/2^232 - 1 the estimate
+  // x_8 MU / 2^40 exceeds x/p - x/2^272 - 2^232/p > x/p - 2^-11 - 2^-21, and flooring costs less than one more.  The
+  // NTT's first stages rely on it: they subtract a weakly reduced value with sub2p, which takes b < 1.9p (the top limb
+  // of a value in the last 2^-22 of [0, 2p) would exceed SUB2P's).  x may also be ONE lazy sum of two normalized
+  // values (limbs < 2^30, value < 2^261; k_perm_numden doubles that way): the limb differences below are carried in
+  // signed 64-bit words, and an x_8 that lacks one carry lowers the estimate by 2^-21 more - the same bound holds.
+  // tests/cpp/bound29.hpp carries both.
   static CAP_HD fl weak_reduce(const fl& x) {
     // q <= floor(x / p) <= q + 1 from the top limb: q = (x_8 * floor(2^272/p)) >> 40
     uint32_t q = (uint32_t)(((uint64_t)x.v[8] * PR::MU) >> 40);

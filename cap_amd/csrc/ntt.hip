@@ -13,6 +13,7 @@
 // per step.  The butterflies keep several independent multiplications in flight; the row-wise schedule stays.)
 #include "ntt.hpp"
 #include "field29.hpp"
+#include "ntt_elem29.hpp"
 #include "launch.hpp"
 
 #include <stdlib.h>
@@ -129,103 +130,33 @@ __device__ __forceinline__ uint32_t bitrev32(uint32_t x, uint32_t bits) { return
 // 147 instead of 216 instructions per element and stage).  The first round of an even-length transform (s = 0) has
 // trivial twiddles - 1, 1 and omega_4 - and, for the prover's zero-padded inputs (a polynomial of n + 2 coefficients on a
 // 2n-point coset: rows len/2.. are zero), two zero operands: ONE multiplication for its four elements instead of four.
-__device__ __forceinline__ uint32_t fl_any(const fl& a) {
-  uint32_t o = 0;
-#pragma unroll
-  for (int k = 0; k < 9; k++) o |= a.v[k];
-  return o;
-}
 // Round 6 (round-5 VERDICT item 4): the butterflies' twiddle products are constant-multiplicand products (Fl::mul_shoup,
 // independent column accumulators: 143 multiply-adds and no serial digit chain against the Montgomery product's 171).
 // tw_small holds PAIRS - entry i at [2i] the plain canonical twiddle, at [2i + 1] its quotient floor(w 2^261 / p) - and a
-// product is below 5p instead of 1.2p: the subtractions add 8p instead of 2p, values grow by at most 13p per radix-4
-// round (5 rounds + the inputs stay far below the 169p the limbs hold).  Everything outside the radix-4 rounds - coset
+// product is below 5p instead of 1.2p: the subtractions add 8p instead of 2p, and values grow by at most 16p per radix-4
+// round (row 3 leaves as a + 8p - t + 8p - t', and zero padding makes both products zero), 10p in the s = 0 round, 2p
+// in the lone radix-2 stage: at most 87.3p behind the last of five rounds for inputs below 2^256, against the 169p the
+// limbs hold (tests/golden/lazy_envelope.json has the bound at every store).  Everything outside the radix-4 rounds - coset
 // pre-scale, inter-pass twiddle, post-scale: factors from 32-byte tables - stays a Montgomery product.  Measured on one
 // box (profiles/ntt_shoup_ab_r06.txt): 768 x 2^16 coset transforms 4.17 -> 4.03 ms, column + row pass per headline step
 // 35.7 -> 34.3 ms, 1373 -> 1387 proofs/s; the microbenchmark behind the decision: profiles/ubench_shoup29_r06.txt.
 // -DCAP_NTT_NO_SHOUP builds the Montgomery rounds of rounds 1-5.
+// The stage bodies are the templates of ntt_elem29.hpp (shared with the host twin and the bound run); the stage loop
+// and the barriers stay here.
 #ifndef CAP_NTT_NO_SHOUP
-constexpr int kTwStride = 2;
-#define NTT_TW_MUL(x, idx) Fr29::mul_shoup((x), tw_small[2 * (idx)], tw_small[2 * (idx) + 1])
-#define NTT_SUB(u, t) Fr29::sub8p((u), (t))
-#define NTT_SUB_LAZY(u, t) Fr29::sub8p_lazy((u), (t))
-#define NTT_SUB_FROM_LAZY(u, t) Fr29::sub8p((u), (t))
+constexpr bool kNttShoup = true;
 #else
-constexpr int kTwStride = 1;
-#define NTT_TW_MUL(x, idx) Fr29::mul((x), tw_small[(idx)])
-#define NTT_SUB(u, t) Fr29::sub2p((u), (t))
-#define NTT_SUB_LAZY(u, t) Fr29::sub2p_lazy((u), (t))
-#define NTT_SUB_FROM_LAZY(u, t) Fr29::sub2p((u), (t))
+constexpr bool kNttShoup = false;
 #endif
+constexpr int kTwStride = NttTw<Fr29, fl, kNttShoup>::kStride;
 __device__ __forceinline__ void lds_ntt(fl* sh, const fl* __restrict__ tw_small, uint32_t log_len, uint32_t log_c) {
-  const uint32_t half_tile = 1u << (log_len + log_c - 1);
-  const uint32_t cmask = (1u << log_c) - 1;
   const uint32_t s0 = log_len & 1;
   if (s0) {
-    // stage 0 alone: every twiddle is omega^0 = 1
-    for (uint32_t b = threadIdx.x; b < half_tile; b += kThreads) {
-      const uint32_t c = b & cmask, bb = b >> log_c;
-      const uint32_t i0 = ((bb << 1) << log_c) + c, i1 = i0 + (1u << log_c);
-      const fl u = sh[i0], v = sh[i1];
-      if (fl_any(v) == 0) {  // zero padding: the butterfly is a copy
-        sh[i1] = u;
-        continue;
-      }
-      const fl t = Fr29::weak_reduce(v);
-      sh[i0] = Fr29::normalize(Fr29::add(u, t));
-      sh[i1] = Fr29::sub2p(u, t);
-    }
+    ntt_stage_radix2<Fr29, fl>(sh, log_len, log_c, threadIdx.x, kThreads);
     __syncthreads();
   }
-  const uint32_t quarter_tile = half_tile >> 1;
   for (uint32_t s = s0; s + 1 < log_len; s += 2) {
-    const uint32_t h = 1u << s;
-    const uint32_t step = h << log_c;
-    for (uint32_t g = threadIdx.x; g < quarter_tile; g += kThreads) {
-      const uint32_t c = g & cmask;
-      const uint32_t gg = g >> log_c;
-      const uint32_t pos = gg & (h - 1);
-      const uint32_t j = ((gg >> s) << (s + 2)) + pos;
-      const uint32_t i0 = (j << log_c) + c, i1 = i0 + step, i2 = i1 + step, i3 = i2 + step;
-      fl a = sh[i0], b = sh[i1], cc = sh[i2], d = sh[i3];
-      // carries are propagated only where a value becomes a multiplicand (limbs < 2^30 needed) or goes back to LDS:
-      // a1, c1 = x + t have limbs < 2^30 as they are; b1 = a - t + 2p is only added to afterwards
-      fl a1, b1, c1, d1, t;
-      if (s == 0) {
-        // w1 = 1: t = b, d themselves (weakly reduced for the subtraction); zero operands make the butterfly a copy
-        if (fl_any(b)) {
-          t = Fr29::weak_reduce(b);
-          a1 = Fr29::add(a, t);
-          b1 = Fr29::sub2p_lazy(a, t);
-        } else {
-          a1 = a;
-          b1 = a;
-        }
-        if (fl_any(d)) {
-          t = Fr29::weak_reduce(d);
-          c1 = Fr29::normalize(Fr29::add(cc, t));
-          d1 = Fr29::sub2p(cc, t);
-        } else {
-          c1 = cc;
-          d1 = cc;
-        }
-        t = Fr29::weak_reduce(c1);  // second-level twiddle of the (a1, c1) pair: omega^0 = 1
-      } else {
-        const uint32_t i_w1 = pos << (log_len - 1 - s);
-        t = NTT_TW_MUL(b, i_w1);
-        a1 = Fr29::add(a, t);
-        b1 = NTT_SUB_LAZY(a, t);
-        t = NTT_TW_MUL(d, i_w1);
-        c1 = Fr29::add(cc, t);
-        d1 = NTT_SUB(cc, t);
-        t = NTT_TW_MUL(c1, pos << (log_len - 2 - s));
-      }
-      sh[i0] = Fr29::normalize(Fr29::add(a1, t));
-      sh[i2] = NTT_SUB(a1, t);
-      t = NTT_TW_MUL(d1, (pos + h) << (log_len - 2 - s));
-      sh[i1] = Fr29::normalize(Fr29::add(b1, t));
-      sh[i3] = NTT_SUB_FROM_LAZY(b1, t);
-    }
+    ntt_stage_radix4<Fr29, fl, kNttShoup>(sh, tw_small, log_len, log_c, s, threadIdx.x, kThreads);
     __syncthreads();
   }
 }
@@ -280,14 +211,10 @@ __device__ __forceinline__ void col_tile(const PassParams& p, fl* sh, const uint
       const uint32_t e = e0 + u * kThreads;
       if (e >= tile) break;
       const uint32_t c = e & cmask, j = e >> p.log_c;
-      uint32_t nz = 0;
-#pragma unroll
-      for (int k = 0; k < 8; k++) nz |= raw[u].v[k];
-      fl v = Fr29::load(raw[u]);
-      if (p.pre_scale && any[u] && nz) v = Fr29::mul(v, Fr29::load(pre[u]));  // zero padding needs no coset scaling
-      if (p.in_fold && sgs[u] + p.in_fold < p.in_len)  // the few coefficients beyond the transform's length, folded in
-        v = Fr29::add_norm(v, Fr29::mul(Fr29::load(in[sgs[u] + p.in_fold]),
-                                        Fr29::load(p.pre_scale[sgs[u] + p.in_fold + (size_t)(by % p.in_group) * p.pre_inner])));
+      // zero padding needs no coset scaling; in_fold: the few coefficients beyond the transform's length, folded in
+      const fl v = ntt_in_elem<Fr29, fl, fe>(raw[u], p.pre_scale && any[u], pre[u],
+                                             p.in_fold && sgs[u] + p.in_fold < p.in_len, in, sgs[u] + p.in_fold, p.pre_scale,
+                                             sgs[u] + p.in_fold + (size_t)(by % p.in_group) * p.pre_inner);
       sh[(bitrev32(j, p.log_len) << p.log_c) + c] = v;
     }
   }
@@ -309,9 +236,7 @@ __device__ __forceinline__ void col_tile(const PassParams& p, fl* sh, const uint
       const uint32_t e = e0 + u * kThreads;
       if (e >= tile) break;
       const uint32_t c = e & cmask, k = e >> p.log_c;
-      fl v = sh[e];
-      v = (exs[u] || p.tw_scaled) ? Fr29::mul(v, Fr29::load(tw[u])) : Fr29::weak_reduce(v);
-      out[base + ((size_t)k << log_s) + c] = Fr29::pack(v);   // < 2p: fits the 32-byte image
+      out[base + ((size_t)k << log_s) + c] = ntt_out_col<Fr29, fl, fe>(sh[e], exs[u] || p.tw_scaled, tw[u]);   // < 2p: fits the 32-byte image
     }
   }
   }
@@ -375,14 +300,10 @@ __device__ __forceinline__ void row_tile(const PassParams& p, fl* sh, const uint
       const uint32_t e = e0 + u * kThreads;
       if (e >= tile) break;
       const uint32_t j = e & lmask, c = e >> p.log_len;
-      uint32_t nz = 0;
-#pragma unroll
-      for (int k = 0; k < 8; k++) nz |= raw[u].v[k];
-      fl v = Fr29::load(raw[u]);
-      if (p.pre_scale && any[u] && nz) v = Fr29::mul(v, Fr29::load(pre[u]));  // zero padding needs no coset scaling
-      if (p.in_fold && sgs[u] + p.in_fold < p.in_len)  // the few coefficients beyond the transform's length, folded in
-        v = Fr29::add_norm(v, Fr29::mul(Fr29::load(in[sgs[u] + p.in_fold]),
-                                        Fr29::load(p.pre_scale[sgs[u] + p.in_fold + (size_t)(by % p.in_group) * p.pre_inner])));
+      // zero padding needs no coset scaling; in_fold: the few coefficients beyond the transform's length, folded in
+      const fl v = ntt_in_elem<Fr29, fl, fe>(raw[u], p.pre_scale && any[u], pre[u],
+                                             p.in_fold && sgs[u] + p.in_fold < p.in_len, in, sgs[u] + p.in_fold, p.pre_scale,
+                                             sgs[u] + p.in_fold + (size_t)(by % p.in_group) * p.pre_inner);
       sh[(bitrev32(j, p.log_len) << p.log_c) + c] = v;
     }
   }
@@ -392,14 +313,14 @@ __device__ __forceinline__ void row_tile(const PassParams& p, fl* sh, const uint
     uint32_t c = e & cmask, k = e >> p.log_c;
     fl v = sh[e];
     size_t g = (size_t)(r0 + c) + ((size_t)k2 << p.log_n1) + ((size_t)k << (p.log_n1 + p.log_n2));
-    if (p.post_scale) v = Fr29::mul(v, Fr29::load(p.post_scale[g]));
-    else if (p.use_post_scalar) v = Fr29::mul(v, Fr29::load(p.post_scalar));
+    if (p.post_scale) v = ntt_scale_elem<Fr29, fl, fe>(v, p.post_scale[g]);
+    else if (p.use_post_scalar) v = ntt_scale_elem<Fr29, fl, fe>(v, p.post_scalar);
     // (a plain inverse transform of two or more passes took its 1/n with the inter-pass twiddles - ntt_run - and, like
     // a forward transform, arrives here straight from the butterflies: normalized limbs, far below the 169p that store
     // and canonical take)
     // results leave the transform canonical (< r), as arkworks stores them - except the internal-form coset
     // evaluations, whose only reader (k_quotient) takes any representative below 2^256
-    out[g] = p.lazy_out ? Fr29::store(v) : Fr29::pack(Fr29::canonical(v));
+    out[g] = ntt_out_row<Fr29, fl, fe>(v, p.lazy_out);
   }
   }
 }
@@ -469,22 +390,13 @@ __global__ __launch_bounds__(kThreads) void ntt3_combine(const fe* __restrict__ 
   const uint32_t q = blockIdx.y;
   const fe* yq = y + (size_t)q * 3 * m_len;
   fe* o = out + (size_t)(q / out_group) * out_outer + (size_t)(q % out_group) * out_inner;
-  const fl y0 = F::load(yq[k]);
-  const fl t1 = F::mul(F::load(yq[m_len + k]), F::load(tw[k]));
-  const fl t2 = F::mul(F::load(yq[2 * m_len + k]), F::load(tw[2 * k]));
-  const fl d = F::mul(F::sub(t1, t2), F::load(w3));
-  fl x0 = F::normalize(F::add(F::add(y0, t1), t2));
-  fl x1 = F::normalize(F::add(F::sub(y0, t2), d));
-  fl x2 = F::sub(F::sub(y0, t1), d);
+  fl x0, x1, x2;
+  ntt3_combine_elem<F, fl, fe>(yq[k], yq[m_len + k], tw[k], yq[2 * m_len + k], tw[2 * k], w3, x0, x1, x2);
   if (post) {
     // products < 2p plus a value < p: normalized and well inside what canonical takes
     const size_t half = m_len >> 1;
     const fl a = add ? F::load(add[(size_t)q * half + (k & (half - 1))]) : F::zero();
-    auto finish = [&](const fl& x, const fe& ps) {
-      fl v = F::mul(x, F::load(ps));
-      if (add) v = F::add_norm(v, a);
-      return F::pack(F::canonical(v));
-    };
+    auto finish = [&](const fl& x, const fe& ps) { return ntt3_finish_elem<F, fl, fe>(x, ps, add != nullptr, a); };
     o[k] = finish(x0, post[k]);
     o[m_len + k] = finish(x1, post[m_len + k]);
     o[2 * m_len + k] = finish(x2, post[2 * m_len + k]);
@@ -512,29 +424,21 @@ __global__ __launch_bounds__(kThreads) void ntt3_combine5(const fe* __restrict__
   const size_t m_len = 2 * n_len;
   const fe* ya = y01 + (size_t)q * 2 * m_len;
   fe* o = out + (size_t)q * 3 * m_len;
-  const fl e0 = F::mul(F::load(ya[i]), F::load(unscale[i]));
-  const fl o0 = F::mul(F::load(ya[n_len + i]), F::load(unscale[n_len + i]));
-  const fl e1 = F::mul(F::load(ya[m_len + i]), F::load(unscale[m_len + i]));
-  const fl o1 = F::mul(F::load(ya[m_len + n_len + i]), F::load(unscale[m_len + n_len + i]));
-  const fl r = F::mul(F::load(y2[(size_t)q * n_len + i]), F::load(unscale[2 * m_len + i]));
+  const fl e0 = ntt_scale_elem<F, fl, fe>(F::load(ya[i]), unscale[i]);
+  const fl o0 = ntt_scale_elem<F, fl, fe>(F::load(ya[n_len + i]), unscale[n_len + i]);
+  const fl e1 = ntt_scale_elem<F, fl, fe>(F::load(ya[m_len + i]), unscale[m_len + i]);
+  const fl o1 = ntt_scale_elem<F, fl, fe>(F::load(ya[m_len + n_len + i]), unscale[m_len + n_len + i]);
+  const fl r = ntt_scale_elem<F, fl, fe>(F::load(y2[(size_t)q * n_len + i]), unscale[2 * m_len + i]);
   const bool has_top = i < 8;
   fl pi = F::zero(), h = F::zero();
   if (add) pi = F::load(add[(size_t)q * n_len + i]);
   if (has_top) h = F::load(top[(size_t)q * 8 + i]);
   // sums of at most four reduced values (< 2p each, normalized): limbs < 2^31, well inside what normalize and canonical take
-  auto finish = [&](fl v, int j) {
-    if (add) v = F::add(v, F::mul(pi, F::load(qc.d[j])));
-    if (has_top) v = F::add(v, F::mul(h, F::load(qc.mt[j])));
-    return F::pack(F::canonical(F::normalize(v)));
-  };
+  using E = Ntt5Elem<F, fl, fe, Quot5Const>;
   for (int jj = 0; jj < 2; jj++)
-    o[(size_t)(2 * jj + 1) * n_len + i] =
-        finish(F::mul_add_mul(o0, F::load(qc.odd[jj][0]), o1, F::load(qc.odd[jj][1])), 2 * jj + 1);
-  for (int jj = 0; jj < 3; jj++) {
-    const fl a = F::mul_add_mul(e0, F::load(qc.even[jj][0]), o0, F::load(qc.even[jj][1]));
-    const fl b = F::mul_add_mul(e1, F::load(qc.even[jj][2]), o1, F::load(qc.even[jj][3]));
-    o[(size_t)(2 * jj) * n_len + i] = finish(F::add(F::add(a, b), F::mul(r, F::load(qc.even[jj][4]))), 2 * jj);
-  }
+    o[(size_t)(2 * jj + 1) * n_len + i] = E::odd(jj, o0, o1, add != nullptr, pi, has_top, h, qc);
+  for (int jj = 0; jj < 3; jj++)
+    o[(size_t)(2 * jj) * n_len + i] = E::even(jj, e0, o0, e1, o1, r, add != nullptr, pi, has_top, h, qc);
   fe t5 = Fr::zero();
   if (has_top) t5 = top[(size_t)q * 8 + i];
   o[5 * n_len + i] = t5;

@@ -11,6 +11,7 @@
 
 #include "field.hpp"
 #include "field29.hpp"
+#include "round_elem29.hpp"
 
 namespace cap {
 namespace pk {
@@ -100,24 +101,11 @@ __global__ __launch_bounds__(kThreads) void k_perm_numden(const fe* __restrict__
   if (j >= n) return;
   uint32_t p = blockIdx.y;
   if (sig_of) sig_eval = sig_of[p];
-  const fl beta = F::from_ext(chal[p].beta);  // internal form
-  const fl gamma = F::load(chal[p].gamma);    // arkworks' form, only ever added
-  const fl bx = F::mul(beta, F::load(tw_n[j]));
-  fl a, b;
-#pragma unroll 1
-  for (int i = 0; i < NW; i++) {
-    const fl wg = F::add(F::load(wires[((size_t)p * NW + i) * n + j]), gamma);
-    const fl t1 = F::normalize(F::add(wg, i == 0 ? bx : F::mul(F::load(qc29.k[i]), bx)));
-    const fl t2 = F::normalize(F::add(wg, F::mul(beta, F::load(sig_eval[(size_t)i * n + j]))));
-    a = i == 0 ? t1 : F::mul(a, t1);
-    b = i == 0 ? t2 : F::mul(b, t2);
-  }
-  // 2^20 in the internal form: 2^281 mod r = (2^261 mod r) * 2^20 mod r, by 20 doublings of ONE
-  fl fix = F::one();
-#pragma unroll 1
-  for (int k = 0; k < 20; k++) fix = F::weak_reduce(F::add(fix, fix));
-  num[(size_t)p * n + j] = F::pack(F::canonical(F::mul(a, fix)));
-  den[(size_t)p * n + j] = F::pack(F::canonical(F::mul(b, fix)));
+  // the row's arithmetic: round_elem29.hpp
+  perm_numden_row<F, fl, fe>(
+      chal[p].beta, chal[p].gamma, tw_n[j], qc29.k,
+      [&](int i) -> const fe& { return wires[((size_t)p * NW + i) * n + j]; },
+      [&](int i) -> const fe& { return sig_eval[(size_t)i * n + j]; }, num[(size_t)p * n + j], den[(size_t)p * n + j]);
 }
 
 // ---- exclusive scans over [batch][len] arrays (stride elements apart) --------------------------------
@@ -263,21 +251,8 @@ __global__ __launch_bounds__(kThreads) void k_perm_finish(const fe* __restrict__
 // cos: [P][6][m] coset evaluations of 5 wires, z;   tw_m: omega_m^i;   inv_nx1: 1 / (n (x_i - 1))
 // The public-input term of the numerator is NOT evaluated here: PI(x) / Z_H(x) is added to the result as coefficients
 // by the inverse transform that follows (ntt.hpp: Ntt3Domain::kappa; prove_run.hpp: pi_fold).
-// Sums of products share one Montgomery reduction (at most 6 products per 64-bit column accumulator).
-struct ColAcc {
-  uint64_t c[18];
-  __device__ __forceinline__ void clear() {
-#pragma unroll
-    for (int k = 0; k < 18; k++) c[k] = 0;
-  }
-  __device__ __forceinline__ void mad(const fl& a, const fl& b) {
-#pragma unroll
-    for (int i = 0; i < 9; i++)
-#pragma unroll
-      for (int j = 0; j < 9; j++) c[i + j] += (uint64_t)a.v[i] * b.v[j];
-  }
-  __device__ __forceinline__ fl reduce() { return Fr29::reduce_cols(c); }
-};
+// Sums of products share one Montgomery reduction (at most 6 products per 64-bit column accumulator): ColAcc,
+// round_elem29.hpp, where the per-point arithmetic of the kernels below lives.
 
 // columns 18 .. 21 of a key's coset table: dst[j][i] = k_(j+1) x_i, internal form, canonical.  A function of the key's
 // separators and the domain only: built once per key (per launch of k_quotient under the reference schedule).
@@ -288,7 +263,7 @@ __global__ __launch_bounds__(kThreads) void k_kx_columns(fe* __restrict__ dst, c
   if (i >= m) return;
   const fl x = F::load(xs[i]);
 #pragma unroll
-  for (int j = 0; j < NKX; j++) dst[(size_t)j * m + i] = F::pack(F::canonical(F::mul(F::load(qc.k[j + 1]), x)));
+  for (int j = 0; j < NKX; j++) dst[(size_t)j * m + i] = kx_elem<F, fl, fe>(qc.k[j + 1], x);
 }
 
 // pkc_of (optional): the key columns of proof p's own key (mixed-key batches), otherwise pkc for all
@@ -325,97 +300,31 @@ __global__ __launch_bounds__(kThreads) void k_quotient(const fe* __restrict__ pk
   const fe* c = cos + (size_t)p * 6 * m;
   const bool half = five && blk == 2;
   const size_t it = half ? 2 * i - 2 * (size_t)mm : i;
-  auto sel = [&](int s) { return F::load(pkc[(size_t)s * m + it]); };
-  fl w0 = F::load(c[i]), w1 = F::load(c[m + i]), w2 = F::load(c[2 * m + i]), w3 = F::load(c[3 * m + i]),
-     w4 = F::load(c[4 * m + i]);
-  // gate constraint (spec eq. (1); selector order q_lc, q_mul, q_hash, q_o, q_c, q_ecc)
-  fl w01 = F::mul(w0, w1), w23 = F::mul(w2, w3);
-  ColAcc acc;
-  acc.clear();
-  acc.mad(sel(0), w0);
-  acc.mad(sel(1), w1);
-  acc.mad(sel(2), w2);
-  acc.mad(sel(3), w3);
-  acc.mad(sel(4), w01);
-  acc.mad(sel(5), w23);
-  fl gate = acc.reduce();
-  acc.clear();
-  {
-    fl t = F::sqr(w0);
-    acc.mad(sel(6), F::mul(F::sqr(t), w0));
-    t = F::sqr(w1);
-    acc.mad(sel(7), F::mul(F::sqr(t), w1));
-    t = F::sqr(w2);
-    acc.mad(sel(8), F::mul(F::sqr(t), w2));
-    t = F::sqr(w3);
-    acc.mad(sel(9), F::mul(F::sqr(t), w3));
-  }
-  acc.mad(sel(12), F::mul(F::mul(w01, w23), w4));
-  acc.mad(F::neg(sel(10)), w4);
-  fl gate2 = acc.reduce();
-  // gate + q_c: three values < 2p each, limbs < 2^31 after the lazy adds
-  fl total = F::normalize(F::add(F::add(gate, gate2), sel(11)));
-  // permutation part:  alpha (z prod_j (w_j + gamma + beta k_j x) - z_omega prod_j (w_j + gamma + beta sigma_j)).
-  // With u_j = (w_j + gamma) / beta every factor is beta (u_j + k_j x) resp. beta (u_j + sigma_j): five products by
-  // 1 / beta take the place of the ten by beta (beta x, four k_j (beta x), five beta sigma_j), k_j x comes from the key's
-  // table (columns 18 .. 21; k_0 = 1: x itself), and the five betas leave with alpha: alpha beta^5 (a' - b').  The same
-  // field element as the direct form (the else branch: k_quotient<false>).
-  const fl gamma = F::load(chal[p].gamma);
-  const fl zx = F::load(c[5 * m + i]);
-  // index a M + k (ntt.hpp): x * omega_n = x * omega_M^2 is two steps further inside the same block of M = m / 3
-  const uint32_t k1 = (uint32_t)i - blk * mm;
-  const size_t inext = (size_t)blk * mm + (half ? (k1 + 1) & (mm / 2 - 1) : (k1 + 2) & (mm - 1));
-  if constexpr (FOLD) {
-    const fl beta_inv = F::load(chal[p].beta_inv);
-    // w_j (a stored value: normalized, < 2^256) + gamma (canonical) is a lazy sum of two - limbs < 2^30, what a product
-    // takes as it is; u_j is a product (normalized, < 1.2p), and u_j + k_j x (canonical) resp. u_j + sigma_j (stored,
-    // < 2^256) again a lazy sum of two that feeds one product: no carry is propagated anywhere in this block
-    fl a = zx, b = F::load(c[5 * m + inext]);
-    fl u = F::mul(F::add(w0, gamma), beta_inv);
-    a = F::mul(a, F::add(u, F::load(xs[it])));  // the point itself (internal form): s_a * omega_M^k at index a * M + k
-    b = F::mul(b, F::add(u, sel(NS + 0)));
-    u = F::mul(F::add(w1, gamma), beta_inv);
-    a = F::mul(a, F::add(u, sel(NS + NW + 0)));
-    b = F::mul(b, F::add(u, sel(NS + 1)));
-    u = F::mul(F::add(w2, gamma), beta_inv);
-    a = F::mul(a, F::add(u, sel(NS + NW + 1)));
-    b = F::mul(b, F::add(u, sel(NS + 2)));
-    u = F::mul(F::add(w3, gamma), beta_inv);
-    a = F::mul(a, F::add(u, sel(NS + NW + 2)));
-    b = F::mul(b, F::add(u, sel(NS + 3)));
-    u = F::mul(F::add(w4, gamma), beta_inv);
-    a = F::mul(a, F::add(u, sel(NS + NW + 3)));
-    b = F::mul(b, F::add(u, sel(NS + 4)));
-    // a, b: products (normalized, < 1.2p), as in the direct form
-    total = F::normalize(F::add(total, F::mul(F::load(chal[p].alpha_beta5), F::sub(a, b))));
-  } else {
-    const fl beta = F::load(chal[p].beta);
-    fl x = F::load(xs[it]);  // the point itself (internal form): s_a * omega_M^k at index a * M + k
-    fl bx = F::mul(beta, x);
-    fl a = zx, b = F::load(c[5 * m + inext]);
-    fl wg = F::add(w0, gamma);
-    a = F::mul(a, F::normalize(F::add(wg, bx)));
-    b = F::mul(b, F::normalize(F::add(wg, F::mul(beta, sel(NS + 0)))));
-    wg = F::add(w1, gamma);
-    a = F::mul(a, F::normalize(F::add(wg, F::mul(F::load(qc.k[1]), bx))));
-    b = F::mul(b, F::normalize(F::add(wg, F::mul(beta, sel(NS + 1)))));
-    wg = F::add(w2, gamma);
-    a = F::mul(a, F::normalize(F::add(wg, F::mul(F::load(qc.k[2]), bx))));
-    b = F::mul(b, F::normalize(F::add(wg, F::mul(beta, sel(NS + 2)))));
-    wg = F::add(w3, gamma);
-    a = F::mul(a, F::normalize(F::add(wg, F::mul(F::load(qc.k[3]), bx))));
-    b = F::mul(b, F::normalize(F::add(wg, F::mul(beta, sel(NS + 3)))));
-    wg = F::add(w4, gamma);
-    a = F::mul(a, F::normalize(F::add(wg, F::mul(F::load(qc.k[4]), bx))));
-    b = F::mul(b, F::normalize(F::add(wg, F::mul(beta, sel(NS + 4)))));
-    total = F::normalize(F::add(total, F::mul(F::load(chal[p].alpha), F::sub(a, b))));
-  }
-  // (gate + alpha * perm) / Z_H  +  alpha^2 (z - 1) / (n (x - 1)) : two products, one reduction
-  fl l1a = F::mul(F::load(chal[p].alpha2), F::sub(zx, F::one()));
-  // x^n depends on the block and on the parity of k only: (s_a omega_M^k)^n = s_a^n (-1)^k = (5 omega_N^(3k + a))^n
-  const uint32_t zi = 3 * (half ? 0u : ((uint32_t)i - blk * mm) & 1) + blk;  // < 6
-  fl r = F::mul_add_mul(total, F::load(qc.zh_inv[zi]), l1a, F::load(inv_nx1[it]));
-  t_out[(size_t)p * m + i] = F::store(r);
+  struct Point {  // what the body reads once, each where it needs it
+    const fe* c;
+    const fe *__restrict__ xs, *__restrict__ inv_nx1;
+    size_t m, i, it;
+    uint32_t blk, mm;
+    bool half;
+    // index a M + k (ntt.hpp): x * omega_n = x * omega_M^2 is two steps further inside the same block of M = m / 3
+    __device__ __forceinline__ const fe& z_next() const {
+      const uint32_t k1 = (uint32_t)i - blk * mm;
+      const size_t inext = (size_t)blk * mm + (half ? (k1 + 1) & (mm / 2 - 1) : (k1 + 2) & (mm - 1));
+      return c[5 * m + inext];
+    }
+    __device__ __forceinline__ const fe& x() const { return xs[it]; }  // the point itself: s_a * omega_M^k at index a * M + k
+    __device__ __forceinline__ const fe& inv() const { return inv_nx1[it]; }
+    // x^n depends on the block and on the parity of k only: (s_a omega_M^k)^n = s_a^n (-1)^k = (5 omega_N^(3k + a))^n
+    __device__ __forceinline__ const fe& zh_inv(const QuotConst& q) const {
+      const uint32_t zi = 3 * (half ? 0u : ((uint32_t)i - blk * mm) & 1) + blk;  // < 6
+      return q.zh_inv[zi];
+    }
+  };
+  const Point at{c, xs, inv_nx1, m, i, it, blk, mm, half};
+  // the point's arithmetic: round_elem29.hpp
+  t_out[(size_t)p * m + i] = quotient_point<FOLD, F, fl, fe>(
+      [&](int s) -> const fe& { return pkc[(size_t)s * m + it]; },
+      [&](int j) -> const fe& { return c[(size_t)j * m + i]; }, at, chal[p], qc);
 }
 
 // out[i] = 1 / (n * (x_i - 1))   (one-time table of the proving key; xs = the points of the quotient domain)
@@ -608,18 +517,15 @@ __global__ __launch_bounds__(kThreads) void k_lincomb(const LinTerm* __restrict_
   if (k >= out_len) return;
   uint32_t p = blockIdx.y;
   const LinTerm* T = terms + (size_t)p * nterms;
-  fl total = F::zero();
-  for (uint32_t t0 = 0; t0 < nterms; t0 += 6) {
-    ColAcc acc;
-    acc.clear();
-#pragma unroll
-    for (uint32_t u = 0; u < 6; u++) {
-      const uint32_t t = t0 + u;
-      if (t < nterms && k < T[t].len) acc.mad(F::load(T[t].scalar), F::load(T[t].poly[k]));
-    }
-    total = F::normalize(F::add(total, acc.reduce()));
-  }
-  out[(size_t)p * out_stride + k] = F::pack(F::canonical(total));
+  struct Terms {
+    const LinTerm* T;
+    uint32_t nterms;
+    size_t k;
+    __device__ __forceinline__ bool active(uint32_t t) const { return t < nterms && k < T[t].len; }
+    __device__ __forceinline__ const fe& scalar(uint32_t t) const { return T[t].scalar; }
+    __device__ __forceinline__ const fe& value(uint32_t t) const { return T[t].poly[k]; }
+  };
+  out[(size_t)p * out_stride + k] = lincomb_elem<F, fl, fe>(nterms, Terms{T, nterms, k});
 }
 
 // h[q][k] = f[q][k] * pows[tab(q)][k];  tab(q) = (q/2)*4 + (q%2)      (q = proof*2 + {zeta, zeta*omega})
