@@ -1,6 +1,6 @@
 // C-ABI entry points of libcapgpu.so (include/capgpu.h): lifecycle, the device contexts and the table of logical
 // handles (context.hpp), device memory plumbing, SRS management, MSM and NTT.  The PLONK entry points live in
-// plonk.hip.  There is no CPU fallback anywhere in this library.
+// plonk.hip and plonk_keys.hip.  There is no CPU fallback anywhere in this library.
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>

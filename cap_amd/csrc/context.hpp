@@ -75,7 +75,7 @@ struct SrsRecord {
   bool sharded() const { return !shards.empty(); }
 };
 
-struct ProvingKey;  // plonk.hip
+struct ProvingKey;  // plonk_key.hpp
 struct ProveGraphCache;  // plonk.hip: instantiated hipGraphs of small-batch prover schedules
 
 // Scalars of MSMs on a (possibly sharded) SRS, resident where their points are ("GPU g holds its bases
@@ -239,7 +239,7 @@ int srs_record(uint64_t h, SrsRecord* out);
 // proving keys: register a key created on the current context / find (replicate) one / drop everywhere
 uint64_t register_key(const std::shared_ptr<ProvingKey>& K);
 int lookup_key(uint64_t h, std::shared_ptr<ProvingKey>* out);
-int clone_key_to_current(const ProvingKey& src, int src_device, std::shared_ptr<ProvingKey>* out);  // plonk.hip
+int clone_key_to_current(const ProvingKey& src, int src_device, std::shared_ptr<ProvingKey>* out);  // plonk_keys.hip
 // a context nobody is using right now (locked; the caller unlocks c->mu), else nullptr
 Context* try_acquire_context();
 // the context a host-buffer call of an unbound thread is dealt to: a free one if there is one, else round-robin

@@ -42,6 +42,8 @@
 #include "notes.hpp"
 #include "params.hpp"
 #include "plonk_kernels.hpp"
+#include "plonk_key.hpp"
+#include "prover.hpp"
 #include "solve.hpp"
 #include "solve_defer.hpp"
 #include "tickets.hpp"
@@ -51,76 +53,6 @@
 namespace cap {
 
 using namespace pk;
-
-// The witness solver's schedule (capgpu_plonk_key_set_given): the host copy, shared by a key and its replicas; every
-// ProvingKey object uploads its own device copy on first use (solve_tables).
-struct SolveSched {
-  uint64_t uid = 0;  // never reused: tells a key's device copy which schedule it holds
-  sp::Plan plan;
-  std::vector<fe> konst;  // per row of plan.rows: 1 / q_o or 1 / q_hash_i, internal form, canonical
-  capgpu_solver_info info{};
-  capgpu_hint_info hint_info{};  // all zero: no hints
-  capgpu_solver_rules_info rules{};  // capgpu_plonk_key_set_solver's flags and what they admitted
-  int auto_pack = 1;  // the schedule's term of the automatic witnesses-per-workgroup rule (spk::auto_pack)
-  // The form the launches run (capgpu_plonk_key_set_solve_form).  Every set-up call makes a DIRECT schedule; the host copies
-  // of the table and of the selectors' zero flags stay with it, so that a change of form is a host pass.
-  int form = CAPGPU_SOLVE_FORM_DIRECT;
-  std::vector<uint32_t> table;    // [5][n]
-  std::vector<uint8_t> sel_zero;  // [13][n]
-  sd::Sched defer;                // form == CAPGPU_SOLVE_FORM_DEFERRED: the schedule the kernels read (solve_defer.hpp)
-  std::vector<fe> defer_konst;    // ... and its items' constants
-};
-
-struct ProvingKey {
-  size_t n = 0, m = 0, ps = 0;  // domain, quotient domain, polynomial stride (n + 8)
-  uint32_t log_n = 0, log_m = 0;
-  size_t num_inputs = 0;
-  uint64_t srs_handle = 0;
-  fe* coef = nullptr;      // [18][ps]: 13 selector + 5 sigma polynomials (coefficients)
-  fe* sig_eval = nullptr;  // [5][n]
-  fe* pk_coset = nullptr;  // [22][m]: 13 selectors, 5 sigmas, k_j x for j = 1 .. 4 (pk::kPkcCols)
-  fe* inv_nx1 = nullptr;   // [m]
-  QuotConst qc;    // arkworks form (host arithmetic, k_perm_numden)
-  QuotConst qc29;  // internal form of the lazy field (k_quotient)
-  capgpu_verifying_key vk;
-  std::vector<uint8_t> vk_bytes;
-  bool recompute = false;
-  int device = 0;  // HIP device the tables live on
-  uint64_t uid = next_uid();  // never reused: identifies the key's tables in the signature of a captured graph
-  static uint64_t next_uid() {
-    static std::atomic<uint64_t> n{1};
-    return n.fetch_add(1);
-  }
-  // Immutable once published: contexts on the same device share the object, other devices get a peer copy
-  // (clone_key_to_current).  The batch workspace lives in the context (Context::prove_ws).
-  // The one exception: the tables of the witness check (key_check_tables), derived on the first check of this key on this
-  // device under chk_mu, read-only afterwards, freed with the key.  A replica on another device derives its own.
-  mutable std::mutex chk_mu;
-  mutable fe* chk_sel = nullptr;         // [13][n] selector VALUES on the domain, internal form (13.6 MB at n = 2^15)
-  mutable uint32_t* chk_perm = nullptr;  // [5 n] index form of the extended permutation: cell i n + j -> i' n + j'
-  mutable int chk_rc = 1;                // 1: not derived yet; CAPGPU_OK: ready; < 0: sigma was refused (chk_err), for good
-  mutable std::string chk_err;
-  // The wire -> variable table of CAPGPU_INPUT_VARS ([5 n] ids below num_vars; null / 0: the key has none).  Set before the
-  // key is published (capgpu_plonk_preprocess_vars, replicas) or attached later by capgpu_plonk_key_set_vars, which must
-  // not run beside calls that use the key; a table it replaces is freed once every context's stream has drained.  A key
-  // with a table has chk_perm from the start - the permutation's index form is what the table was turned into.
-  mutable uint32_t* wire_vars = nullptr;
-  mutable size_t num_vars = 0;
-  // The solver's schedule (null: none) and this object's device copy of it, one allocation, made under chk_mu by the first
-  // solve that finds solve_dev_uid != solve->uid.  Set, replaced and dropped like the table (not beside calls that use the key).
-  mutable std::shared_ptr<const SolveSched> solve;
-  mutable void* solve_dev = nullptr;
-  mutable uint64_t solve_dev_uid = 0;
-  mutable SolveTables solve_tab{};
-  ProvingKey() = default;
-  ProvingKey(const ProvingKey&) = delete;
-  ProvingKey& operator=(const ProvingKey&) = delete;
-  ~ProvingKey() {
-    for (void* p : {(void*)coef, (void*)sig_eval, (void*)pk_coset, (void*)inv_nx1, (void*)chk_sel, (void*)chk_perm,
-                    (void*)wire_vars, solve_dev})
-      if (p) hipFree(p);
-  }
-};
 
 // ---- hipGraph replay of the small-batch schedule -------------------------------------------------------------------
 // One proof is ~100 kernel launches in five Fiat-Shamir rounds, most of them a few microseconds long: at batch 1 .. 16 the
@@ -351,6 +283,8 @@ int key_gate_table(const ProvingKey& K) {
   return key_gate_table_locked(K);
 }
 
+}  // namespace
+
 // selector values on the domain and the index form of sigma, on the current context's stream; synchronous
 int key_check_tables(const ProvingKey& K) {
   std::lock_guard<std::mutex> lk(K.chk_mu);
@@ -399,6 +333,8 @@ int key_check_tables(const ProvingKey& K) {
   K.chk_rc = CAPGPU_OK;
   return CAPGPU_OK;
 }
+
+namespace {
 
 // check_batch's verdicts inside its d_small (the head of check_resident's Context::stage_a): they stay there until the
 // next check, and an outcome call's k_prove_outcomes takes its copy of CheckOut::first from them (prove_batch)
@@ -803,26 +739,7 @@ int prove_batch(const ProvingKey& K, uint32_t P, const ProveRequest& rq) {
   return prove_planned(c, K, P, rq, pl, run);
 }
 
-// ---- proving-key construction shared by preprocess and the blob loader -------------------------------------
-int key_init(ProvingKey& K, size_t n, size_t num_inputs, uint64_t srs_handle) {
-  K.n = n;
-  K.m = 6 * n;  // quotient domain: 3 * 2^(log n + 1) points
-  K.ps = n + 8;
-  while (((size_t)1 << K.log_n) < n) K.log_n++;
-  K.log_m = K.log_n + 1;  // log2 of the power-of-two factor of m
-  if (K.log_m > 25) {
-    set_error("capgpu_plonk_preprocess: domain too large");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  K.num_inputs = num_inputs;
-  K.srs_handle = srs_handle;
-  K.device = ctx().device;
-  K.recompute = env_int("CAPGPU_RECOMPUTE_PK_COSET", 0) != 0;
-  CAP_HIP(hipMalloc(&K.coef, sizeof(fe) * 18 * K.ps));
-  CAP_HIP(hipMalloc(&K.sig_eval, sizeof(fe) * NW * n));
-  CAP_HIP(hipMalloc(&K.inv_nx1, sizeof(fe) * K.m));
-  return CAPGPU_OK;
-}
+}  // namespace
 
 // everything derived from the coefficient table: constants of the quotient kernel, 1 / (n (x - 1)) on the coset,
 // and the cached coset evaluations of the 18 fixed polynomials
@@ -864,23 +781,7 @@ int key_finish_tables(hipStream_t s, ProvingKey& K) {
   return CAPGPU_OK;
 }
 
-// verifying key and transcript prefix from the 18 affine commitments (13 selectors, then 5 sigmas)
-void key_set_vk(ProvingKey& K, const std::vector<g1_affine>& ha) {
-  memset(&K.vk, 0, sizeof(K.vk));
-  K.vk.domain_size = K.n;
-  K.vk.num_inputs = K.num_inputs;
-  for (int i = 0; i < NW; i++) fe_to_words(K.qc.k[i], K.vk.k[i]);
-  for (int i = 0; i < NS; i++) affine_to_words(ha[i], K.vk.selector_comms[i]);
-  for (int i = 0; i < NW; i++) affine_to_words(ha[NS + i], K.vk.sigma_comms[i]);
-  // transcript prefix: field bits, domain size, #inputs, k_i, selector and sigma commitments
-  SolidityTranscript t;
-  t.append_u64_le(254);
-  t.append_u64_le((uint64_t)K.n);
-  t.append_u64_le((uint64_t)K.num_inputs);
-  for (int i = 0; i < NW; i++) append_fr(t, K.qc.k[i]);
-  for (int i = 0; i < 18; i++) append_g1(t, ha[i]);
-  K.vk_bytes = t.buf;
-}
+namespace {
 
 // ---- coalescing of concurrent single-proof calls ----------------------------------------------------------------
 // The reference proves notes under rayon (`into_par_iter()`, src/utils/params_builder.rs:194-226): many host threads
@@ -1026,84 +927,6 @@ void plonk_reset_staging() {
   solve_stats_reset();  // (capgpu_plonk_solve_stats)
 }
 
-// the registry's (home) copy of a key, without replicating it
-static int home_key(uint64_t h, std::shared_ptr<ProvingKey>* out) {
-  Runtime& R = rt();
-  std::lock_guard<std::mutex> lk(R.mu);
-  auto it = R.keys.find(h);
-  if (it == R.keys.end()) {
-    set_error("capgpu: unknown proving key handle %llu", (unsigned long long)h);
-    return CAPGPU_ERR_BAD_HANDLE;
-  }
-  *out = it->second;
-  return CAPGPU_OK;
-}
-
-int clone_key_to_current(const ProvingKey& src, int src_device, std::shared_ptr<ProvingKey>* out) {
-  Context& c = ctx();
-  auto K = std::make_shared<ProvingKey>();
-  K->n = src.n;
-  K->m = src.m;
-  K->ps = src.ps;
-  K->log_n = src.log_n;
-  K->log_m = src.log_m;
-  K->num_inputs = src.num_inputs;
-  K->srs_handle = src.srs_handle;
-  K->qc = src.qc;
-  K->qc29 = src.qc29;
-  K->vk = src.vk;
-  K->vk_bytes = src.vk_bytes;
-  K->recompute = src.recompute;
-  K->device = c.device;
-  auto dup = [&](fe** dst, const fe* from, size_t count) -> int {
-    if (!from) return CAPGPU_OK;
-    CAP_HIP(hipMalloc(dst, sizeof(fe) * count));
-    CAP_HIP(copy_between(*dst, c.device, from, src_device, sizeof(fe) * count, c.stream));
-    return CAPGPU_OK;
-  };
-  int rc;
-  if ((rc = dup(&K->coef, src.coef, 18 * src.ps))) return rc;
-  if ((rc = dup(&K->sig_eval, src.sig_eval, (size_t)NW * src.n))) return rc;
-  if ((rc = dup(&K->pk_coset, src.pk_coset, kPkcCols * src.m))) return rc;
-  if ((rc = dup(&K->inv_nx1, src.inv_nx1, src.m))) return rc;
-  {
-    // the variable table and, with it, the permutation's index form (4 B x 5 n each) travel with the key
-    std::lock_guard<std::mutex> lk(src.chk_mu);
-    if (src.wire_vars && src.chk_perm) {
-      const size_t bytes = sizeof(uint32_t) * NW * src.n;
-      CAP_HIP(hipMalloc(&K->wire_vars, bytes));
-      CAP_HIP(hipMalloc(&K->chk_perm, bytes));
-      CAP_HIP(copy_between(K->wire_vars, c.device, src.wire_vars, src_device, bytes, c.stream));
-      CAP_HIP(copy_between(K->chk_perm, c.device, src.chk_perm, src_device, bytes, c.stream));
-      K->num_vars = src.num_vars;
-      K->solve = src.solve;  // the host copy; the replica uploads its own tables on its first solve
-    }
-  }
-  CAP_HIP(hipStreamSynchronize(c.stream));
-  *out = K;
-  return CAPGPU_OK;
-}
-
-// the key resident on the current context: replicated from its home on first use (same device: the same object)
-int lookup_key(uint64_t h, std::shared_ptr<ProvingKey>* out) {
-  Context& c = ctx();
-  auto it = c.keys.find(h);
-  if (it != c.keys.end()) {
-    *out = it->second;
-    return CAPGPU_OK;
-  }
-  std::shared_ptr<ProvingKey> home, rep;
-  int rc = home_key(h, &home);
-  if (rc) return rc;
-  if (home->device == c.device && !force_replicate()) rep = home;
-  else if ((rc = clone_key_to_current(*home, home->device, &rep))) return rc;
-  else rt().replications++;
-  if ((rc = home_key(h, &home))) return rc;  // freed while it was being copied
-  c.keys[h] = rep;
-  *out = rep;
-  return CAPGPU_OK;
-}
-
 }  // namespace cap
 
 namespace cap {
@@ -1145,18 +968,10 @@ void vars_sigma_values(hipStream_t s, uint32_t log_n, const uint32_t* d_perm, fe
   const size_t cells = (size_t)NW << log_n;
   launch("k_vars_sigma", k_vars_sigma, dim3(cdiv(cells, kThreads)), dim3(kThreads), 0, s, d_perm, sc, cells, d_sigma);
 }
-// first id of the table ([5][n], host) that is not below num_vars: CAPGPU_ERR_INVALID_ARG naming its (wire, row)
-int vars_table_valid(const char* who, const uint32_t* wire_vars, size_t n, size_t num_vars) {
-  if (!wire_vars || num_vars < 1 || num_vars > 0xffffffffull) {
-    set_error("%s: bad argument (wire_vars: 5 columns of n ids, 1 <= num_vars < 2^32)", who);
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  for (size_t c = 0; c < (size_t)NW * n; c++)
-    if (wire_vars[c] >= num_vars) {
-      set_error("%s: wire_vars holds id %u at (wire %zu, row %zu), num_vars is %zu", who, wire_vars[c], c / n, c % n, num_vars);
-      return CAPGPU_ERR_INVALID_ARG;
-    }
-  return CAPGPU_OK;
+// capgpu_plonk_key_set_vars: the table's permutation against the index form of the key's own sigma, cell for cell
+void vars_first_difference(hipStream_t s, const uint32_t* d_perm, const uint32_t* d_key_perm, size_t cells,
+                           unsigned long long* d_first) {
+  launch("k_vars_differ", k_vars_differ, dim3(cdiv(cells, kThreads)), dim3(kThreads), 0, s, d_perm, d_key_perm, cells, d_first);
 }
 }  // namespace cap
 
@@ -1168,12 +983,6 @@ static bool bad_form(int form) {
   if (form == CAPGPU_INPUT_EVALS || form == CAPGPU_INPUT_COEFFS || form == CAPGPU_INPUT_VARS) return false;
   set_error("capgpu_plonk: input_form %d is none of CAPGPU_INPUT_EVALS (0), CAPGPU_INPUT_COEFFS (1), CAPGPU_INPUT_VARS (2)",
             form);
-  return true;
-}
-// the forms a key's COLUMNS (selectors, sigmas) come in
-static bool bad_column_form(int form) {
-  if (form == CAPGPU_INPUT_EVALS || form == CAPGPU_INPUT_COEFFS) return false;
-  set_error("capgpu_plonk_preprocess: form %d is neither CAPGPU_INPUT_EVALS (0) nor CAPGPU_INPUT_COEFFS (1)", form);
   return true;
 }
 // CAPGPU_INPUT_VARS asks for a key with a table: refused before the device is touched.  *stride_out: elements per proof of
@@ -1190,1061 +999,6 @@ static int input_stride(const uint64_t* pks, int count, int form, size_t n, size
     stride = std::max(stride, K->num_vars);
   }
   *stride_out = stride;
-  return CAPGPU_OK;
-}
-
-// capgpu_plonk_preprocess_ex, or - wire_vars != nullptr: capgpu_plonk_preprocess_vars - the same with the extended
-// permutation built on the device from the circuit's wire -> variable table (`sigma_evals` is then unused and
-// `input_form` is the selectors' alone); from the sigma values on, one code path finishes both keys.
-static int preprocess_impl(uint64_t srs_handle, size_t n, size_t num_inputs, const uint64_t* selectors,
-                           const uint64_t* sigma_evals, int input_form, const uint32_t* wire_vars, size_t num_vars,
-                           uint64_t* pk_handle_out, capgpu_verifying_key* vk_out) {
-  Context& c = ctx();
-  Entry lk(c);
-  // n >= 16: the five split-quotient commitments read 5 (n + 2) coefficients of the 6n-point quotient array
-  if (!selectors || (!sigma_evals && !wire_vars) || !pk_handle_out || n < 16 || (n & (n - 1)) || num_inputs >= n) {
-    set_error("capgpu_plonk_preprocess: bad argument (n must be a power of two >= 16, num_inputs < n)");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  const MsmBases* B = nullptr;
-  int rc = find_srs(srs_handle, &B);
-  if (rc) return rc;
-  if (B->n < n + 3) {
-    set_error("capgpu_plonk_preprocess: SRS holds %zu powers, the circuit needs %zu (n + 3)", B->n, n + 3);
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  hipStream_t s = c.stream;
-  auto K = std::make_shared<ProvingKey>();
-  if ((rc = key_init(*K, n, num_inputs, srs_handle))) return rc;
-  const size_t ps = K->ps;
-  // stage the evaluation columns, then interpolate
-  DevTmp<fe> stage;
-  DevTmp<g1_jac> d_comms;
-  CAP_HIP(stage.alloc(18 * n));
-  CAP_HIP(hipMemcpyAsync(stage, selectors, sizeof(fe) * NS * n, hipMemcpyHostToDevice, s));
-  if (wire_vars) {
-    // the permutation comes from the table, on the device: its index form stays with the key (the witness check needs no
-    // discrete logarithm for it), its field form is the sigma VALUES a caller of capgpu_plonk_preprocess would have sent
-    CAP_HIP(hipMalloc(&K->wire_vars, sizeof(uint32_t) * NW * n));
-    CAP_HIP(hipMalloc(&K->chk_perm, sizeof(uint32_t) * NW * n));
-    CAP_HIP(hipMemcpyAsync(K->wire_vars, wire_vars, sizeof(uint32_t) * NW * n, hipMemcpyHostToDevice, s));
-    K->num_vars = num_vars;
-    if ((rc = vars_build_perm(s, K->wire_vars, n, K->chk_perm))) return rc;
-    vars_sigma_values(s, K->log_n, K->chk_perm, stage.p + (size_t)NS * n);
-  } else {
-    CAP_HIP(hipMemcpyAsync(stage.p + (size_t)NS * n, sigma_evals, sizeof(fe) * NW * n, hipMemcpyHostToDevice, s));
-  }
-  CAP_HIP(hipMemcpyAsync(K->sig_eval, stage.p + (size_t)NS * n, sizeof(fe) * NW * n, hipMemcpyDeviceToDevice, s));
-  pad_copy(s, K->coef, ps, 0, stage.p, n, 0, 1, 18, n, ps);
-  if (input_form == CAPGPU_INPUT_COEFFS && wire_vars) {
-    // selector polynomials as they are; the table's sigma is VALUES: interpolate those five columns only
-    if ((rc = run_ntt(s, K->log_n, K->coef + (size_t)NS * ps, ps, NW, 1, 0))) return rc;
-  } else if (input_form == CAPGPU_INPUT_COEFFS) {
-    // the 18 polynomials arrive as jf-relation computes them (compute_selector_polynomials /
-    // compute_extended_permutation_polynomials): nothing to interpolate; round 2 reads sigma's VALUES on the domain
-    if ((rc = run_ntt(s, K->log_n, K->sig_eval, n, NW, 0, 0))) return rc;
-  } else if ((rc = run_ntt(s, K->log_n, K->coef, ps, 18, 1, 0))) {
-    return rc;
-  }
-  if ((rc = key_finish_tables(s, *K))) return rc;
-  // verifying key: commitments of the 18 polynomials
-  CAP_HIP(d_comms.alloc(18));
-  if ((rc = run_msm(s, *B, K->coef, ps, 1, 0, n, 18, d_comms))) return rc;
-  std::vector<g1_jac> hj(18);
-  std::vector<g1_affine> ha;
-  CAP_HIP(hipMemcpyAsync(hj.data(), d_comms, sizeof(g1_jac) * 18, hipMemcpyDeviceToHost, s));
-  CAP_HIP(hipStreamSynchronize(s));
-  batch_to_affine(hj, ha);
-  key_set_vk(*K, ha);
-  if (vk_out) *vk_out = K->vk;
-  // the Lagrange-form commit key of this domain under this SRS (round 1's wire commitments; built once per pair and kept
-  // with the SRS): made here so that the first proof does not pay for it
-  if (wire_commit_from_evals() && !comm_shard_prover()) {
-    const MsmBases* Lag = nullptr;
-    // (an optimisation: a key whose Lagrange-form table cannot be built proves from coefficients - see make_plan)
-    if ((rc = find_lagrange(srs_handle, K->log_n, &Lag)) == CAPGPU_ERR_BAD_HANDLE) return rc;
-    (void)hipGetLastError();
-  }
-  *pk_handle_out = register_key(K);
-  return take_launch_error();
-}
-
-int capgpu_plonk_preprocess_ex(uint64_t srs_handle, size_t n, size_t num_inputs, const uint64_t* selectors,
-                               const uint64_t* sigma_evals, int input_form, uint64_t* pk_handle_out,
-                               capgpu_verifying_key* vk_out) {
-  CAP_CHECK_INIT();
-  if (bad_column_form(input_form)) return CAPGPU_ERR_INVALID_ARG;
-  return preprocess_impl(srs_handle, n, num_inputs, selectors, sigma_evals, input_form, nullptr, 0, pk_handle_out, vk_out);
-}
-
-int capgpu_plonk_preprocess_vars(uint64_t srs_handle, size_t n, size_t num_inputs, const uint64_t* selectors,
-                                 int selector_form, const uint32_t* wire_vars, size_t num_vars, uint64_t* pk_handle_out,
-                                 capgpu_verifying_key* vk_out) {
-  CAP_CHECK_INIT();
-  if (bad_column_form(selector_form)) return CAPGPU_ERR_INVALID_ARG;
-  if (n < 16 || (n & (n - 1))) {
-    set_error("capgpu_plonk_preprocess: bad argument (n must be a power of two >= 16, num_inputs < n)");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  int rc = vars_table_valid("capgpu_plonk_preprocess_vars", wire_vars, n, num_vars);
-  if (rc) return rc;
-  return preprocess_impl(srs_handle, n, num_inputs, selectors, nullptr, selector_form, wire_vars, num_vars, pk_handle_out,
-                         vk_out);
-}
-
-int capgpu_plonk_preprocess(uint64_t srs_handle, size_t n, size_t num_inputs, const uint64_t* selectors,
-                            const uint64_t* sigma_evals, uint64_t* pk_handle_out, capgpu_verifying_key* vk_out) {
-  return capgpu_plonk_preprocess_ex(srs_handle, n, num_inputs, selectors, sigma_evals, CAPGPU_INPUT_EVALS, pk_handle_out,
-                                    vk_out);
-}
-
-// ---- ProvingKey blob (layout in include/capgpu.h) ---------------------------------------------
-int capgpu_plonk_key_serialize(uint64_t pk_handle, const uint64_t gamma_g[8], const uint64_t h[16],
-                               const uint64_t beta_h[16], uint8_t* out, size_t cap, size_t* len_out) {
-  CAP_CHECK_INIT();
-  Context& c = ctx();
-  Entry lk(c);
-  if (!h || !beta_h || !len_out) {
-    set_error("capgpu_plonk_key_serialize: bad argument");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  std::shared_ptr<ProvingKey> K;
-  int rc = lookup_key(pk_handle, &K);
-  if (rc) return rc;
-  const MsmBases* B = nullptr;
-  if ((rc = find_srs(K->srs_handle, &B))) return rc;
-  const size_t n = K->n, ps = K->ps, n_ck = n + 3;
-  // upper bound: every polynomial at full length
-  const SrsEntry* E0 = find_srs_entry(K->srs_handle);
-  const size_t bound = 2 * 8 + 18 * (8 + 32 * n) + 8 + 32 * n_ck + 8 +
-                       (E0 ? std::max(E0->ck_gamma_pts.size(), (size_t)32 * n_ck) : 0) + 1024;
-  if (!out) {
-    *len_out = bound;
-    return CAPGPU_OK;
-  }
-  hipStream_t s = c.stream;
-  std::vector<uint8_t> coef(32 * 18 * ps), ck(32 * n_ck);
-  if ((rc = params::fr_mont_to_bytes(K->coef, 18 * ps, coef.data(), s))) return rc;
-  if ((rc = params::compress_g1(B->ext, 1, n_ck, ck.data(), s))) return rc;
-  params::Writer w;
-  auto poly = [&](int idx) {  // DensePolynomial: no trailing zero coefficients
-    const uint8_t* p = &coef[32 * (size_t)idx * ps];
-    size_t len = n;
-    auto zero = [&](size_t i) {
-      for (int b = 0; b < 32; b++)
-        if (p[32 * i + b]) return false;
-      return true;
-    };
-    while (len && zero(len - 1)) len--;
-    w.u64(len);
-    w.put(p, 32 * len);
-  };
-  w.u64(NW);
-  for (int i = 0; i < NW; i++) poly(NS + i);
-  w.u64(NS);
-  for (int i = 0; i < NS; i++) poly(i);
-  w.u64(n_ck);
-  w.put(ck.data(), ck.size());
-  {
-    // CommitKey::powers_of_gamma_g (Vec<G1>, degrees 0 .. n_ck - 1 - what jf-plonk's trim emits).  A key loaded from a
-    // ProvingKey blob re-emits the blob's vector.  A key preprocessed under a loaded UniversalSrs takes the degrees
-    // 0 .. n_ck - 1 from that SRS's BTreeMap, in order - all of them or, when one is missing, none (a sparse map must
-    // not turn into a shorter vector with the degrees lost).  A synthetic SRS has no hiding powers: empty vector.
-    const SrsEntry* E = find_srs_entry(K->srs_handle);
-    std::vector<uint8_t> gp;
-    if (E && !E->ck_gamma_pts.empty()) {
-      gp = E->ck_gamma_pts;
-    } else if (E && !E->gamma_deg.empty()) {
-      std::map<uint64_t, size_t> at;
-      for (size_t i = 0; i < E->gamma_deg.size(); i++) at[E->gamma_deg[i]] = i;
-      bool all = true;
-      for (uint64_t d = 0; d < n_ck && all; d++) all = at.count(d) != 0;
-      if (all)
-        for (uint64_t d = 0; d < n_ck; d++)
-          gp.insert(gp.end(), E->gamma_pts.begin() + 32 * at[d], E->gamma_pts.begin() + 32 * at[d] + 32);
-    }
-    w.u64(gp.size() / 32);
-    if (!gp.empty()) w.put(gp.data(), gp.size());
-  }
-  params::OpenKey ok;
-  {
-    g1_affine g0;
-    if (!params::g1_decompress_host(ck.data(), &g0)) return CAPGPU_ERR_SERIALIZATION;
-    ok.g = g0;
-  }
-  // open key's gamma_g: the caller's, else what the blob this key (or its SRS) was loaded from held - the key blob's own
-  // value, or degree 0 of a UniversalSrs's hiding powers - else infinity (a synthetic SRS has none)
-  ok.gamma_g.x = ok.gamma_g.y = Fq::zero();
-  if (gamma_g) {
-    ok.gamma_g = params::g1_from_words(gamma_g);
-  } else if (const SrsEntry* Eg = find_srs_entry(K->srs_handle)) {
-    if (Eg->has_ck_gamma_g) {
-      ok.gamma_g = Eg->ck_gamma_g;
-    } else {
-      for (size_t i = 0; i < Eg->gamma_deg.size(); i++)
-        if (Eg->gamma_deg[i] == 0) {
-          g1_affine g0;
-          if (params::g1_decompress_host(&Eg->gamma_pts[32 * i], &g0)) ok.gamma_g = g0;
-          break;
-        }
-    }
-  }
-  ok.h = params::g2_from_words(h);
-  ok.beta_h = params::g2_from_words(beta_h);
-  params::write_vk(w, K->vk, ok);
-  w.u8(0);  // plookup_pk = None
-  *len_out = w.buf.size();
-  if (cap < w.buf.size()) {
-    set_error("capgpu_plonk_key_serialize: buffer of %zu bytes, %zu needed", cap, w.buf.size());
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  memcpy(out, w.buf.data(), w.buf.size());
-  return CAPGPU_OK;
-}
-
-int capgpu_plonk_key_deserialize(const uint8_t* bytes, size_t len, uint64_t* srs_handle_out, uint64_t* pk_handle_out,
-                                 capgpu_verifying_key* vk_out, uint64_t h_out[16], uint64_t beta_h_out[16],
-                                 size_t* consumed_out) {
-  CAP_CHECK_INIT();
-  Context& c = ctx();
-  Entry lk(c);
-  if (!bytes || !srs_handle_out || !pk_handle_out) {
-    set_error("capgpu_plonk_key_deserialize: bad argument");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  params::Reader rd(bytes, len);
-  auto fail = [&](const char* why) {
-    set_error("capgpu_plonk_key_deserialize: %s (byte %zu of %zu)", why, rd.pos, len);
-    return CAPGPU_ERR_SERIALIZATION;
-  };
-  struct Span {
-    const uint8_t* p;
-    uint64_t len;
-  };
-  Span polys[18];  // internal order: 13 selectors, then 5 sigmas
-  uint64_t cnt = 0;
-  if (!rd.count(8, &cnt)) return fail("unexpected end of input");
-  if (cnt != NW) return fail("sigmas: a TurboPlonk key has 5 of them");
-  for (int i = 0; i < NW; i++) {
-    if (!rd.count(32, &polys[NS + i].len)) return fail("unexpected end of input");
-    polys[NS + i].p = rd.take(32 * polys[NS + i].len);
-  }
-  if (!rd.count(8, &cnt)) return fail("unexpected end of input");
-  if (cnt != NS) return fail("selectors: a TurboPlonk key has 13 of them");
-  for (int i = 0; i < NS; i++) {
-    if (!rd.count(32, &polys[i].len)) return fail("unexpected end of input");
-    polys[i].p = rd.take(32 * polys[i].len);
-  }
-  uint64_t n_ck = 0, n_gamma = 0;
-  if (!rd.count(32, &n_ck)) return fail("unexpected end of input");
-  const uint8_t* ck = rd.take(32 * n_ck);
-  if (!rd.count(32, &n_gamma)) return fail("unexpected end of input");
-  const uint8_t* gamma = rd.take(32 * n_gamma);
-  capgpu_verifying_key vk;
-  params::OpenKey ok;
-  if (const char* why = params::read_vk(rd, &vk, &ok)) return fail(why);
-  const uint8_t* tag = rd.take(1);
-  if (!tag) return fail("unexpected end of input");
-  if (*tag) return fail("plookup proving keys are not supported");
-  const size_t n = vk.domain_size;
-  if (n < 16 || (n & (n - 1)) || vk.num_inputs >= n)
-    return fail("domain_size must be a power of two >= 16 above num_inputs");
-  if (n_ck < n + 3) return fail("commit key shorter than domain_size + 3");
-  for (int i = 0; i < 18; i++)
-    if (polys[i].len > n) return fail("polynomial longer than the domain");
-  // the prover's quotient kernel is specialised to the k_i of jf-plonk; refuse anything else
-  for (int i = 0; i < NW; i++) {
-    uint64_t want[4];
-    fe_to_words(Fr::to_mont(fe_from_words(K_CANON[i])), want);
-    if (memcmp(want, vk.k[i], 32) != 0) return fail("coset representatives k_i differ from jf-plonk's");
-  }
-
-  hipStream_t s = c.stream;
-  int rc;
-  // commit key -> device -> window table
-  uint64_t srs_handle = 0;
-  {
-    DevTmp<g1_affine> d_ck;
-    CAP_HIP(d_ck.alloc(std::max<uint64_t>(n_ck, n_gamma)));
-    rc = n_gamma ? params::decompress_g1(gamma, n_gamma, d_ck, s) : CAPGPU_OK;  // validated; bytes kept below
-    if (rc == CAPGPU_OK) rc = params::decompress_g1(ck, n_ck, d_ck, s);
-    if (rc == CAPGPU_OK) rc = register_srs(d_ck, n_ck, &srs_handle);
-    if (rc) return rc;
-    if (SrsEntry* E = find_srs_entry(srs_handle)) {
-      E->ck_gamma_pts.assign(gamma, gamma + 32 * n_gamma);
-      E->ck_gamma_g = ok.gamma_g;
-      E->has_ck_gamma_g = true;
-    }
-  }
-  auto K = std::make_shared<ProvingKey>();
-  auto bail = [&](int code) {
-    // the SRS was registered a moment ago on THIS context and nobody else knows its handle: drop it here (going through
-    // capgpu_srs_free would take the other contexts' locks while this one is held - out of lock order)
-    (void)hipStreamSynchronize(c.stream);
-    c.srs.erase(srs_handle);
-    std::lock_guard<std::mutex> rlk(rt().mu);
-    rt().srs.erase(srs_handle);
-    return code;
-  };
-  if ((rc = key_init(*K, n, vk.num_inputs, srs_handle))) return bail(rc);
-  const size_t ps = K->ps;
-  {
-    std::vector<uint8_t> coef(32 * 18 * ps, 0);
-    for (int i = 0; i < 18; i++)
-      if (polys[i].len) memcpy(&coef[32 * (size_t)i * ps], polys[i].p, 32 * polys[i].len);
-    if ((rc = params::fr_bytes_to_mont(coef.data(), 18 * ps, K->coef, s))) return bail(rc);
-  }
-  // sigma evaluations on the domain (round 2 reads them)
-  pad_copy(s, K->sig_eval, n, 0, K->coef + (size_t)NS * ps, ps, 0, 1, NW, n, n);
-  if ((rc = run_ntt(s, K->log_n, K->sig_eval, n, NW, 0, 0))) return bail(rc);
-  if ((rc = key_finish_tables(s, *K))) return bail(rc);
-  std::vector<g1_affine> ha(18);
-  for (int i = 0; i < NS; i++) ha[i] = params::g1_from_words(vk.selector_comms[i]);
-  for (int i = 0; i < NW; i++) ha[NS + i] = params::g1_from_words(vk.sigma_comms[i]);
-  key_set_vk(*K, ha);
-  CAP_HIP(hipStreamSynchronize(s));
-  if (vk_out) *vk_out = K->vk;
-  if (h_out) params::g2_to_words(ok.h, h_out);
-  if (beta_h_out) params::g2_to_words(ok.beta_h, beta_h_out);
-  if (consumed_out) *consumed_out = rd.pos;
-  *pk_handle_out = register_key(K);
-  *srs_handle_out = srs_handle;
-  return CAPGPU_OK;
-}
-
-int capgpu_plonk_key_info(uint64_t pk_handle, size_t* domain_size_out, size_t* num_inputs_out,
-                          uint64_t* srs_handle_out) {
-  CAP_CHECK_INIT();
-  std::shared_ptr<ProvingKey> K;
-  int rc = home_key(pk_handle, &K);
-  if (rc) return rc;
-  if (domain_size_out) *domain_size_out = K->n;
-  if (num_inputs_out) *num_inputs_out = K->num_inputs;
-  if (srs_handle_out) *srs_handle_out = K->srs_handle;
-  return CAPGPU_OK;
-}
-
-// Does this proving key produce this verifying key?  The 18 commitments preprocess_impl makes, made again from the key's
-// resident polynomials and compared with vk's (NULL: the key's own - what capgpu_plonk_key_deserialize took from the blob)
-int capgpu_plonk_key_check(uint64_t pk_handle, const capgpu_verifying_key* vk, capgpu_key_report* out) {
-  if (!out) {
-    set_error("capgpu_plonk_key_check: bad argument (no report)");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  memset(out, 0, sizeof *out);
-  CAP_CHECK_INIT();
-  Context& c = ctx();
-  Entry lk(c);
-  std::shared_ptr<ProvingKey> K;
-  int rc = lookup_key(pk_handle, &K);
-  if (rc) return rc;
-  const capgpu_verifying_key& want = vk ? *vk : K->vk;
-  if (want.domain_size != K->n || want.num_inputs != K->num_inputs || memcmp(want.k, K->vk.k, sizeof want.k)) {
-    out->verdict = 1;
-    return CAPGPU_OK;
-  }
-  const MsmBases* B = nullptr;
-  if ((rc = find_srs(K->srs_handle, &B))) return rc;
-  hipStream_t s = c.stream;
-  DevTmp<g1_jac> d_comms;
-  CAP_HIP(d_comms.alloc(18));
-  if ((rc = run_msm(s, *B, K->coef, K->ps, 1, 0, K->n, 18, d_comms))) return rc;
-  std::vector<g1_jac> hj(18);
-  std::vector<g1_affine> ha;
-  CAP_HIP(hipMemcpyAsync(hj.data(), d_comms, sizeof(g1_jac) * 18, hipMemcpyDeviceToHost, s));
-  CAP_HIP(hipStreamSynchronize(s));
-  if ((rc = take_launch_error())) return rc;
-  batch_to_affine(hj, ha);
-  for (int i = 17; i >= 0; i--) {
-    uint64_t w[8];
-    affine_to_words(ha[i], w);
-    if (memcmp(w, i < NS ? want.selector_comms[i] : want.sigma_comms[i - NS], sizeof w)) {
-      out->column = (uint32_t)i;
-      out->columns_differing++;
-    }
-  }
-  if (out->columns_differing) {
-    out->verdict = 2;
-    return CAPGPU_OK;
-  }
-  // the witness check's test of sigma (kept with the key, like the tables that test derives)
-  rc = key_check_tables(*K);
-  if (rc == CAPGPU_ERR_INVALID_ARG && K->chk_rc == CAPGPU_ERR_INVALID_ARG) {
-    out->verdict = 3;
-    return CAPGPU_OK;
-  }
-  return rc;
-}
-
-int capgpu_plonk_key_num_vars(uint64_t pk_handle, size_t* num_vars_out) {
-  CAP_CHECK_INIT();
-  std::shared_ptr<ProvingKey> K;
-  int rc = home_key(pk_handle, &K);
-  if (rc) return rc;
-  if (num_vars_out) *num_vars_out = K->wire_vars ? K->num_vars : 0;
-  return CAPGPU_OK;
-}
-
-int capgpu_plonk_input_stats(uint64_t* witness_bytes_h2d_out, uint64_t* gather_launches_out) {
-  if (witness_bytes_h2d_out) *witness_bytes_h2d_out = g_witness_h2d.load();
-  if (gather_launches_out) *gather_launches_out = g_gather_launches.load();
-  return CAPGPU_OK;
-}
-
-// Attaches a wire -> variable table to a key made without one.  Runs on a context of the key's home device: the table's
-// permutation is built there (vars_build_perm) and compared, cell for cell, with the index form of the key's own sigma.
-int capgpu_plonk_key_set_vars(uint64_t pk_handle, const uint32_t* wire_vars, size_t num_vars) {
-  CAP_CHECK_INIT();
-  std::shared_ptr<ProvingKey> K;
-  int rc = home_key(pk_handle, &K);
-  if (rc) return rc;
-  if ((rc = vars_table_valid("capgpu_plonk_key_set_vars", wire_vars, K->n, num_vars))) return rc;
-  Runtime& R = rt();
-  Context* home = nullptr;
-  for (auto& cp : R.ctxs)
-    if (cp->device == K->device) {
-      home = cp.get();
-      break;
-    }
-  if (!home) {
-    set_error("capgpu_plonk_key_set_vars: no context on the key's device %d", K->device);
-    return CAPGPU_ERR_BAD_HANDLE;
-  }
-  uint32_t* replaced = nullptr;  // the table the key had: freed below, behind whatever launch may still read it
-  {
-    ScopedCtx sc(*home);
-    Entry lk(*home);
-    hipStream_t s = home->stream;
-    const size_t n = K->n, cells = (size_t)NW * n;
-    DevTmp<uint32_t> table, perm;
-    DevTmp<unsigned long long> first;
-    CAP_HIP(table.alloc(cells));
-    CAP_HIP(perm.alloc(cells));
-    CAP_HIP(first.alloc(1));
-    CAP_HIP(hipMemcpyAsync(table, wire_vars, sizeof(uint32_t) * cells, hipMemcpyHostToDevice, s));
-    if ((rc = vars_build_perm(s, table, n, perm))) return rc;
-    if ((rc = key_check_tables(*K))) return rc;  // the key's own permutation in index form (derived once per key)
-    unsigned long long h_first = ~0ull;
-    CAP_HIP(hipMemcpyAsync(first, &h_first, sizeof h_first, hipMemcpyHostToDevice, s));
-    launch("k_vars_differ", k_vars_differ, dim3(cdiv(cells, kThreads)), dim3(kThreads), 0, s, (const uint32_t*)perm.p,
-           (const uint32_t*)K->chk_perm, cells, first.p);
-    CAP_HIP(hipMemcpyAsync(&h_first, first, sizeof h_first, hipMemcpyDeviceToHost, s));
-    CAP_HIP(hipStreamSynchronize(s));
-    if ((rc = take_launch_error())) return rc;
-    if (h_first != ~0ull) {
-      set_error("capgpu_plonk_key_set_vars: the table's permutation is not the key's: first difference at (wire %llu, row "
-                "%llu); the key is unchanged", h_first / n, h_first % n);
-      return CAPGPU_ERR_INVALID_ARG;
-    }
-    std::lock_guard<std::mutex> klk(K->chk_mu);
-    replaced = K->wire_vars;
-    K->wire_vars = table.p;
-    K->num_vars = num_vars;
-    K->solve.reset();  // the solver's schedule was derived from the table that leaves
-    table.p = nullptr;
-  }
-  // replicas on other devices were cloned without the table (or with the old one): they are made again on next use
-  for (auto& cp : R.ctxs) {
-    Context& c = *cp;
-    ScopedCtx sc(c);
-    Entry lk(c);
-    auto it = c.keys.find(pk_handle);
-    if (it == c.keys.end()) continue;
-    if (replaced || it->second.get() != K.get()) (void)hipStreamSynchronize(c.stream);
-    if (it->second.get() != K.get()) c.keys.erase(it);
-  }
-  if (replaced) {
-    ScopedCtx sc(*home);
-    (void)hipFree(replaced);
-  }
-  return CAPGPU_OK;
-}
-
-// ---- the witness solver (solve_plan.hpp, solve29.hpp, solve_kernels.hpp) ----------------------------------------------
-namespace {
-
-const sv29::Exps* solve_exps() {
-  static const struct Derived {
-    sv29::Exps ex;
-    bool ok;
-    Derived() { ok = sv29::derive_exps(&ex); }
-  } d;
-  return d.ok ? &d.ex : nullptr;
-}
-
-// capgpu_plonk_set_solve_pack: witnesses per workgroup of the solver's launches; 0: the automatic rule (solve_pack.hpp).
-// -1: the process default (CAPGPU_SOLVE_PACK; a value that is no setting counts as 0)
-std::atomic<int> g_solve_pack{-1};
-int solve_pack_setting() {
-  static const int env_default = [] {
-    const int e = env_int("CAPGPU_SOLVE_PACK", 0);
-    return spk::valid_setting(e) ? e : 0;
-  }();
-  const int m = g_solve_pack.load(std::memory_order_relaxed);
-  return m < 0 ? env_default : m;
-}
-
-// 1 / x for every x of v (internal form, none zero), in place: one inversion and three products per element
-void solve_batch_inverse(std::vector<fl>& v) {
-  if (v.empty()) return;
-  std::vector<fl> pre(v.size());
-  fl acc = Fr29::one();
-  for (size_t i = 0; i < v.size(); i++) {
-    pre[i] = acc;
-    acc = Fr29::mul(acc, v[i]);
-  }
-  acc = Fr29::inv(acc);
-  for (size_t i = v.size(); i-- > 0;) {
-    const fl x = v[i];
-    v[i] = Fr29::mul(acc, pre[i]);
-    acc = Fr29::mul(acc, x);
-  }
-}
-
-// The device copy of K's schedule on K's device (the current one), uploaded on the first solve after a set_given.
-int solve_tables(const ProvingKey& K, SolveTables* tab, std::shared_ptr<const SolveSched>* hold) {
-  std::lock_guard<std::mutex> lk(K.chk_mu);
-  if (!K.solve || !K.wire_vars) {
-    set_error("capgpu_plonk_solve_vars: the key has no solver (capgpu_plonk_key_set_given gives it one)");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  const SolveSched& S = *K.solve;
-  *hold = K.solve;
-  if (K.solve_dev_uid != S.uid) {
-    if (K.solve_dev) {
-      CAP_HIP(hipFree(K.solve_dev));  // (waits for the device: a launch may still read the tables that leave)
-      K.solve_dev = nullptr;
-      K.solve_dev_uid = 0;
-    }
-    // (the DEFERRED form: the deferred schedule's items, constants and levels take the direct ones' places)
-    const bool defer = S.form == CAPGPU_SOLVE_FORM_DEFERRED;
-    const std::vector<sp::Row>& h_rows = defer ? S.defer.rows : S.plan.rows;
-    const std::vector<fe>& h_konst = defer ? S.defer_konst : S.konst;
-    const std::vector<uint32_t>& h_off = defer ? S.defer.level_off : S.plan.level_off;
-    const size_t nrows = h_rows.size();
-    int32_t* dslot = nullptr;
-    uint32_t* flush_vars = nullptr;
-    int32_t* slot = nullptr;
-    sp::Row* rows = nullptr;
-    fe* konst = nullptr;
-    uint32_t* off = nullptr;
-    sp::Hint* hints = nullptr;
-    uint32_t* targets = nullptr;
-    const size_t nhints = S.plan.hints.size(), ntargets = S.plan.targets.size();
-    auto carve_tables = [&](void* at) {
-      Carver k(at);
-      slot = k.take<int32_t>(S.plan.slot.size());
-      rows = k.take<sp::Row>(nrows ? nrows : 1);
-      konst = k.take<fe>(nrows ? nrows : 1);
-      off = k.take<uint32_t>(h_off.size());
-      if (nhints) {
-        hints = k.take<sp::Hint>(nhints);
-        targets = k.take<uint32_t>(ntargets);
-      }
-      if (defer) {
-        dslot = k.take<int32_t>(S.defer.dslot.size() ? S.defer.dslot.size() : 1);
-        flush_vars = k.take<uint32_t>(S.defer.flush_vars.size() ? S.defer.flush_vars.size() : 1);
-      }
-      return k.off + 256;
-    };
-    DevTmp<char> own;
-    CAP_HIP(own.alloc(carve_tables(nullptr)));
-    (void)carve_tables(own.p);
-    CAP_HIP(hipMemcpy(slot, S.plan.slot.data(), sizeof(int32_t) * S.plan.slot.size(), hipMemcpyHostToDevice));
-    if (nrows) {
-      CAP_HIP(hipMemcpy(rows, h_rows.data(), sizeof(sp::Row) * nrows, hipMemcpyHostToDevice));
-      CAP_HIP(hipMemcpy(konst, h_konst.data(), sizeof(fe) * nrows, hipMemcpyHostToDevice));
-    }
-    CAP_HIP(hipMemcpy(off, h_off.data(), sizeof(uint32_t) * h_off.size(), hipMemcpyHostToDevice));
-    if (defer) {
-      if (!S.defer.dslot.empty())
-        CAP_HIP(hipMemcpy(dslot, S.defer.dslot.data(), sizeof(int32_t) * S.defer.dslot.size(), hipMemcpyHostToDevice));
-      if (!S.defer.flush_vars.empty())
-        CAP_HIP(hipMemcpy(flush_vars, S.defer.flush_vars.data(), sizeof(uint32_t) * S.defer.flush_vars.size(),
-                          hipMemcpyHostToDevice));
-    }
-    if (nhints) {
-      CAP_HIP(hipMemcpy(hints, S.plan.hints.data(), sizeof(sp::Hint) * nhints, hipMemcpyHostToDevice));
-      CAP_HIP(hipMemcpy(targets, S.plan.targets.data(), sizeof(uint32_t) * ntargets, hipMemcpyHostToDevice));
-    }
-    SolveTables t{};
-    t.slot = slot;
-    t.rows = rows;
-    t.konst = konst;
-    t.level_off = off;
-    t.hp.hints = hints;
-    t.hp.targets = targets;
-    t.levels = (uint32_t)(defer ? S.defer.levels : S.plan.levels);
-    t.num_given = S.plan.num_given;
-    t.lin = S.plan.lin_rows != 0;
-    t.defer = defer;
-    t.dslot = dslot;
-    t.flush_vars = flush_vars;
-    t.side_slots = defer ? (size_t)S.defer.slots : 0;
-    K.solve_tab = t;
-    K.solve_dev = own.p;
-    K.solve_dev_uid = S.uid;
-    own.p = nullptr;
-  }
-  *tab = K.solve_tab;
-  tab->wire_vars = K.wire_vars;
-  tab->sel = K.chk_sel;
-  tab->n = K.n;
-  tab->num_vars = K.num_vars;
-  return CAPGPU_OK;
-}
-
-// `count` witnesses on the current context: given values and the result in host memory (h_*) or resident (d_*)
-int solve_run(uint64_t pk_handle, uint32_t count, const uint64_t* h_given, uint64_t* h_vars, const void* d_given,
-              void* d_vars, capgpu_solve_status* status_out) {
-  Context& c = ctx();
-  Entry lk(c);
-  std::shared_ptr<ProvingKey> K;
-  int rc = lookup_key(pk_handle, &K);
-  if (rc) return rc;
-  const sv29::Exps* ex = solve_exps();
-  if (!ex) {
-    set_error("capgpu_plonk_solve_vars: (r - 1) mod 5 != 1: the scalar field has no fifth-root exponent");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  {
-    std::lock_guard<std::mutex> klk(K->chk_mu);
-    if (!K->solve || !K->wire_vars) {
-      set_error("capgpu_plonk_solve_vars: the key has no solver (capgpu_plonk_key_set_given gives it one)");
-      return CAPGPU_ERR_INVALID_ARG;
-    }
-  }
-  if ((rc = key_check_tables(*K))) return rc;  // the selector values on the domain (derived once per key)
-  SolveTables tab;
-  std::shared_ptr<const SolveSched> hold;
-  if ((rc = solve_tables(*K, &tab, &hold))) return rc;
-  hipStream_t s = c.stream;
-  const size_t given_elems = (size_t)count * tab.num_given, var_elems = (size_t)count * tab.num_vars;
-  unsigned long long* d_st = nullptr;
-  fe *g = nullptr, *v = nullptr, *side = nullptr;
-  auto carve_call = [&](void* at) {
-    Carver k(at);
-    d_st = k.take<unsigned long long>(count);
-    if (h_given) g = k.take<fe>(given_elems ? given_elems : 1);
-    if (h_vars) v = k.take<fe>(var_elems);
-    if (tab.defer) side = k.take<fe>(tab.side_elems(count) + 1);  // (a key in the DEFERRED form: its denominators)
-    return k.off + 256;
-  };
-  if ((rc = scratch_reserve(c.stage_b, carve_call(nullptr)))) return rc;
-  (void)carve_call(c.stage_b.p);
-  if (h_given) {
-    if (given_elems) CAP_HIP(hipMemcpyAsync(g, h_given, sizeof(fe) * given_elems, hipMemcpyHostToDevice, s));
-    d_given = g;
-  }
-  if (h_vars) d_vars = v;
-  CAP_HIP(hipMemsetAsync(d_st, 0xff, sizeof(unsigned long long) * count, s));
-  solve_launch_packed(s, spk::pack_for(solve_pack_setting(), hold->auto_pack, count),
-                      SolveLaunch{count, (const fe*)d_given, tab.num_given, (fe*)d_vars, tab.num_vars, d_st, nullptr, side}, tab,
-                      *ex);
-  std::vector<unsigned long long> h_st(count);
-  CAP_HIP(hipMemcpyAsync(h_st.data(), d_st, sizeof(unsigned long long) * count, hipMemcpyDeviceToHost, s));
-  if (h_vars) CAP_HIP(hipMemcpyAsync(h_vars, d_vars, sizeof(fe) * var_elems, hipMemcpyDeviceToHost, s));
-  CAP_HIP(hipStreamSynchronize(s));
-  if ((rc = take_launch_error())) return rc;
-  for (uint32_t p = 0; p < count; p++) {
-    capgpu_solve_status& o = status_out[p];
-    memset(&o, 0, sizeof o);
-    if (h_st[p] != kSolved) {
-      o.kind = 1;
-      o.row = h_st[p];
-    }
-  }
-  return CAPGPU_OK;
-}
-
-static_assert(sizeof(capgpu_hint) == sizeof(sp::Hint) && sizeof(capgpu_hint) == 16 && sizeof(capgpu_hint_info) == 48 &&
-                  offsetof(capgpu_hint, kind) == offsetof(sp::Hint, kind) && offsetof(capgpu_hint, src) == offsetof(sp::Hint, src) &&
-                  offsetof(capgpu_hint, first) == offsetof(sp::Hint, first) &&
-                  offsetof(capgpu_hint, count) == offsetof(sp::Hint, count),
-              "capgpu_hint is sp::Hint");
-static_assert(CAPGPU_HINT_BITS == sp::HINT_BITS && CAPGPU_HINT_INV0 == sp::HINT_INV0 && CAPGPU_HINT_ISZERO == sp::HINT_ISZERO,
-              "hint kinds");
-
-static_assert(sizeof(capgpu_solver_rules_info) == 32, "capgpu_solver_rules_info");
-static_assert(CAPGPU_SOLVER_LINEAR == sp::RULE_LINEAR && CAPGPU_SOLVER_DERIVE_PUBLIC == sp::RULE_DERIVE_PUBLIC, "solver flags");
-
-// capgpu_plonk_key_set_given (who names it, no hints), capgpu_plonk_key_set_given_hints (both: flags 0) and
-// capgpu_plonk_key_set_solver
-int key_set_given(const char* who, uint64_t pk_handle, const uint32_t* given_vars, size_t num_given, const capgpu_hint* hints,
-                  size_t num_hints, const uint32_t* targets, size_t num_targets, uint32_t flags, capgpu_solver_info* info_out,
-                  capgpu_hint_info* hint_info_out) {
-  if (flags & ~sp::kRuleFlags) {
-    set_error("%s: bad argument (flags 0x%x: the known bits are CAPGPU_SOLVER_LINEAR (1) and CAPGPU_SOLVER_DERIVE_PUBLIC (2))", who,
-              flags);
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  if (!given_vars && num_given) {
-    set_error("%s: bad argument (given_vars is NULL)", who);
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  if ((!hints && num_hints) || (!targets && num_targets)) {
-    set_error("%s: bad argument (%s is NULL)", who, !hints && num_hints ? "hints" : "targets");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  if (num_hints >= (1ull << 32) || num_targets >= (1ull << 32)) {
-    set_error("%s: bad argument (num_hints and num_targets are below 2^32)", who);
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  CAP_CHECK_INIT();
-  std::shared_ptr<ProvingKey> K;
-  int rc = home_key(pk_handle, &K);
-  if (rc) return rc;
-  if (!K->wire_vars) {
-    set_error("%s: the key has no wire -> variable table (capgpu_plonk_preprocess_vars makes a key with one, "
-              "capgpu_plonk_key_set_vars gives it one); the key is unchanged",
-              who);
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  if (!solve_exps()) {
-    set_error("%s: (r - 1) mod 5 != 1: the scalar field has no fifth-root exponent", who);
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  Runtime& R = rt();
-  Context* home = nullptr;
-  for (auto& cp : R.ctxs)
-    if (cp->device == K->device) {
-      home = cp.get();
-      break;
-    }
-  if (!home) {
-    set_error("%s: no context on the key's device %d", who, K->device);
-    return CAPGPU_ERR_BAD_HANDLE;
-  }
-  auto S = std::make_shared<SolveSched>();
-  {
-    ScopedCtx sc(*home);
-    Entry lk(*home);
-    hipStream_t s = home->stream;
-    const size_t n = K->n, cells = (size_t)NW * n, num_vars = K->num_vars;
-    if ((rc = key_check_tables(*K))) return rc;
-    // the table and the selector values, read back once (0.66 MB and 13.6 MB at n = 2^15)
-    std::vector<uint32_t> table(cells);
-    std::vector<fe> sel((size_t)NS * n);
-    CAP_HIP(hipMemcpyAsync(table.data(), K->wire_vars, sizeof(uint32_t) * cells, hipMemcpyDeviceToHost, s));
-    CAP_HIP(hipMemcpyAsync(sel.data(), K->chk_sel, sizeof(fe) * NS * n, hipMemcpyDeviceToHost, s));
-    CAP_HIP(hipStreamSynchronize(s));
-    std::vector<uint8_t> sel_zero((size_t)NS * n);
-    for (size_t i = 0; i < sel.size(); i++) sel_zero[i] = Fr29::is_zero(Fr29::load(sel[i])) ? 1 : 0;
-    if (!sp::solve_plan_rules(n, K->num_inputs, num_vars, table.data(), sel_zero.data(), given_vars, num_given,
-                              (const sp::Hint*)hints, num_hints, targets, num_targets, flags, &S->plan)) {
-      set_error("%s: %s; the key is unchanged", who, S->plan.error.c_str());
-      return CAPGPU_ERR_INVALID_ARG;
-    }
-    const sp::Plan& P = S->plan;
-    std::vector<fl> inv;
-    std::vector<size_t> where;
-    for (size_t k = 0; k < P.rows.size(); k++) {
-      const uint32_t kind = sp::row_kind(P.rows[k]);
-      if (kind == sp::OUT_INV || sp::is_hint_kind(kind)) continue;
-      const int which = kind == sp::OUT_MUL ? sp::Q_O : (kind == sp::LIN ? sp::Q_LC : sp::Q_HASH) + (int)sp::row_wire(P.rows[k]);
-      inv.push_back(Fr29::load(sel[(size_t)which * n + P.rows[k].row]));
-      where.push_back(k);
-    }
-    solve_batch_inverse(inv);
-    S->konst.assign(P.rows.size(), Fr29::pack(Fr29::zero()));
-    for (size_t i = 0; i < inv.size(); i++) S->konst[where[i]] = Fr29::pack(Fr29::canonical(inv[i]));
-    static std::atomic<uint64_t> next_uid{1};
-    S->uid = next_uid.fetch_add(1);
-    S->info = capgpu_solver_info{P.num_given, P.num_defined, P.levels, P.widest_level, P.inv_rows, P.root_rows};
-    S->hint_info = capgpu_hint_info{P.hints.size(), P.num_hinted, P.bits_hints, P.inv_hints, P.iszero_hints, P.hint_items};
-    S->rules = capgpu_solver_rules_info{P.flags, P.lin_rows, P.derived_inputs, 0};
-    S->auto_pack = spk::auto_pack(spk::median_level_width(P.level_off.data(), P.levels), kSolveThreads);
-    S->table = std::move(table);
-    S->sel_zero = std::move(sel_zero);
-  }
-  // the key and the replicas other devices hold take the schedule; each uploads its tables on its next solve
-  for (auto& cp : R.ctxs) {
-    Context& c = *cp;
-    ScopedCtx sc(c);
-    Entry lk(c);
-    auto it = c.keys.find(pk_handle);
-    ProvingKey* k = it == c.keys.end() ? (cp.get() == home ? K.get() : nullptr) : it->second.get();
-    if (!k) continue;
-    std::lock_guard<std::mutex> klk(k->chk_mu);
-    k->solve = S;
-  }
-  {
-    std::lock_guard<std::mutex> klk(K->chk_mu);
-    K->solve = S;
-  }
-  if (info_out) *info_out = S->info;
-  if (hint_info_out) *hint_info_out = S->hint_info;
-  return CAPGPU_OK;
-}
-
-}  // namespace
-
-int capgpu_plonk_key_set_given(uint64_t pk_handle, const uint32_t* given_vars, size_t num_given,
-                               capgpu_solver_info* info_out) {
-  return key_set_given("capgpu_plonk_key_set_given", pk_handle, given_vars, num_given, nullptr, 0, nullptr, 0, 0, info_out, nullptr);
-}
-
-int capgpu_plonk_key_set_given_hints(uint64_t pk_handle, const uint32_t* given_vars, size_t num_given,
-                                     const capgpu_hint* hints, size_t num_hints, const uint32_t* targets,
-                                     size_t num_targets, capgpu_solver_info* info_out, capgpu_hint_info* hint_info_out) {
-  return key_set_given("capgpu_plonk_key_set_given_hints", pk_handle, given_vars, num_given, hints, num_hints, targets,
-                       num_targets, 0, info_out, hint_info_out);
-}
-
-int capgpu_plonk_key_set_solver(uint64_t pk_handle, const uint32_t* given_vars, size_t num_given, const capgpu_hint* hints,
-                                size_t num_hints, const uint32_t* targets, size_t num_targets, uint32_t flags,
-                                capgpu_solver_info* info_out, capgpu_hint_info* hint_info_out) {
-  // (flags 0: the refusals open with the older call's name - the same texts)
-  return key_set_given(flags ? "capgpu_plonk_key_set_solver" : "capgpu_plonk_key_set_given_hints", pk_handle, given_vars,
-                       num_given, hints, num_hints, targets, num_targets, flags, info_out, hint_info_out);
-}
-
-int capgpu_plonk_key_solver_rules_info(uint64_t pk_handle, capgpu_solver_rules_info* info_out) {
-  if (!info_out) {
-    set_error("capgpu_plonk_key_solver_rules_info: bad argument (info_out is NULL)");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  CAP_CHECK_INIT();
-  std::shared_ptr<ProvingKey> K;
-  int rc = home_key(pk_handle, &K);
-  if (rc) return rc;
-  std::lock_guard<std::mutex> klk(K->chk_mu);
-  memset(info_out, 0, sizeof *info_out);
-  if (K->solve && K->wire_vars) *info_out = K->solve->rules;
-  return CAPGPU_OK;
-}
-
-// ---- the form of the solver's schedule (solve_defer.hpp) ---------------------------------------------------------------
-static_assert(sizeof(capgpu_solve_form_info) == 64, "capgpu_solve_form_info");
-namespace {
-// the figures of S in the form it holds; D: the deferred schedule of S's plan (S.defer, or one derived for the figures)
-capgpu_solve_form_info solve_form_figures(const SolveSched& S, const sd::Sched& D) {
-  if (S.form == CAPGPU_SOLVE_FORM_DEFERRED)
-    return capgpu_solve_form_info{CAPGPU_SOLVE_FORM_DEFERRED, D.deferred_vars, D.frac_rows, D.flush_levels, D.flush_items,
-                                  D.levels, D.inv_levels_direct, D.inv_levels_deferred};
-  return capgpu_solve_form_info{CAPGPU_SOLVE_FORM_DIRECT, 0, 0, 0, 0, S.plan.levels, D.inv_levels_direct, D.inv_levels_deferred};
-}
-}  // namespace
-
-int capgpu_plonk_key_set_solve_form(uint64_t pk_handle, int form, capgpu_solve_form_info* info_out) {
-  static const char who[] = "capgpu_plonk_key_set_solve_form";
-  if (form != CAPGPU_SOLVE_FORM_DIRECT && form != CAPGPU_SOLVE_FORM_DEFERRED) {
-    set_error("%s: bad argument (form %d is neither CAPGPU_SOLVE_FORM_DIRECT (0) nor CAPGPU_SOLVE_FORM_DEFERRED (1)); the key is "
-              "unchanged",
-              who, form);
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  if (!pk_handle) {
-    set_error("%s: bad argument (pk_handle is 0)", who);
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  CAP_CHECK_INIT();
-  std::shared_ptr<ProvingKey> K;
-  int rc = home_key(pk_handle, &K);
-  if (rc) return rc;
-  std::shared_ptr<const SolveSched> old;
-  {
-    std::lock_guard<std::mutex> klk(K->chk_mu);
-    if (K->solve && K->wire_vars) old = K->solve;
-  }
-  if (!old) {
-    set_error("%s: the key has no solver (capgpu_plonk_key_set_given gives it one); the key is unchanged", who);
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  // a new schedule object with a new uid: every holder uploads its tables again on its next solve
-  auto S = std::make_shared<SolveSched>(*old);
-  S->form = form;
-  S->defer = sd::Sched();
-  S->defer_konst.clear();
-  const sp::Plan& P = S->plan;
-  if (form == CAPGPU_SOLVE_FORM_DEFERRED) {
-    sd::defer_plan(P, K->n, S->table.data(), S->sel_zero.data(), &S->defer);
-    const sd::Sched& D = S->defer;
-    S->defer_konst.assign(D.rows.size(), Fr29::pack(Fr29::zero()));
-    for (size_t k = 0; k < D.rows.size(); k++)
-      if (D.src[k] != sd::kNoSrc) S->defer_konst[k] = S->konst[D.src[k]];
-    S->auto_pack = spk::auto_pack(spk::median_level_width(D.level_off.data(), D.levels), kSolveThreads);
-  } else {
-    S->auto_pack = spk::auto_pack(spk::median_level_width(P.level_off.data(), P.levels), kSolveThreads);
-  }
-  static std::atomic<uint64_t> next_uid{1ull << 40};  // (apart from the set-up calls' counter)
-  S->uid = next_uid.fetch_add(1);
-  Runtime& R = rt();
-  for (auto& cp : R.ctxs) {
-    Context& c = *cp;
-    ScopedCtx sc(c);
-    Entry lk(c);
-    auto it = c.keys.find(pk_handle);
-    if (it == c.keys.end()) continue;
-    std::lock_guard<std::mutex> klk(it->second->chk_mu);
-    if (it->second->solve) it->second->solve = S;
-  }
-  {
-    std::lock_guard<std::mutex> klk(K->chk_mu);
-    K->solve = S;
-  }
-  if (info_out) {
-    if (form == CAPGPU_SOLVE_FORM_DEFERRED) {
-      *info_out = solve_form_figures(*S, S->defer);
-    } else {
-      sd::Sched D;
-      sd::defer_plan(P, K->n, S->table.data(), S->sel_zero.data(), &D);
-      *info_out = solve_form_figures(*S, D);
-    }
-  }
-  return CAPGPU_OK;
-}
-
-int capgpu_plonk_key_solve_form_info(uint64_t pk_handle, capgpu_solve_form_info* info_out) {
-  if (!info_out || !pk_handle) {
-    set_error("capgpu_plonk_key_solve_form_info: bad argument (%s)", info_out ? "pk_handle is 0" : "info_out is NULL");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  CAP_CHECK_INIT();
-  std::shared_ptr<ProvingKey> K;
-  int rc = home_key(pk_handle, &K);
-  if (rc) return rc;
-  std::shared_ptr<const SolveSched> S;
-  {
-    std::lock_guard<std::mutex> klk(K->chk_mu);
-    if (K->solve && K->wire_vars) S = K->solve;
-  }
-  memset(info_out, 0, sizeof *info_out);
-  if (!S) return CAPGPU_OK;
-  if (S->form == CAPGPU_SOLVE_FORM_DEFERRED) {
-    *info_out = solve_form_figures(*S, S->defer);
-  } else {
-    sd::Sched D;  // (the figures the other form would have: a host pass over the plan)
-    sd::defer_plan(S->plan, K->n, S->table.data(), S->sel_zero.data(), &D);
-    *info_out = solve_form_figures(*S, D);
-  }
-  return CAPGPU_OK;
-}
-
-// capgpu_plonk_pub_inputs[_dev]: host arrays (h_*) staged through the context's scratch, or resident ones (d_*)
-static int pub_inputs_run(const char* who, uint64_t pk_handle, int count, const uint64_t* h_vars, uint64_t* h_pub,
-                          const void* d_vars, void* d_pub) {
-  if (count < 0 || (count && (!(h_vars || d_vars) || !(h_pub || d_pub)))) {
-    set_error("%s: bad argument (count >= 0; a NULL array with count = %d)", who, count);
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  CAP_CHECK_INIT();
-  Context& c = ctx();
-  Entry lk(c);
-  std::shared_ptr<ProvingKey> K;
-  int rc = lookup_key(pk_handle, &K);
-  if (rc) return rc;
-  if (!K->wire_vars) {
-    set_error("%s: the key has no wire -> variable table (capgpu_plonk_preprocess_vars makes a key with one, "
-              "capgpu_plonk_key_set_vars gives it one)",
-              who);
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  if (count == 0 || K->num_inputs == 0) return CAPGPU_OK;
-  if ((rc = key_check_tables(*K))) return rc;  // the selector values on the domain (derived once per key)
-  hipStream_t s = c.stream;
-  const size_t ni = K->num_inputs, var_elems = (size_t)count * K->num_vars, pub_elems = (size_t)count * ni;
-  if (h_vars) {
-    fe *v = nullptr, *p = nullptr;
-    auto carve_call = [&](void* at) {
-      Carver k(at);
-      v = k.take<fe>(var_elems);
-      p = k.take<fe>(pub_elems);
-      return k.off + 256;
-    };
-    if ((rc = scratch_reserve(c.stage_b, carve_call(nullptr)))) return rc;
-    (void)carve_call(c.stage_b.p);
-    CAP_HIP(hipMemcpyAsync(v, h_vars, sizeof(fe) * var_elems, hipMemcpyHostToDevice, s));
-    pub_inputs_launch(s, (uint32_t)count, v, K->num_vars, K->wire_vars, K->chk_sel, K->n, (uint32_t)ni, nullptr, p, ni);
-    CAP_HIP(hipMemcpyAsync(h_pub, p, sizeof(fe) * pub_elems, hipMemcpyDeviceToHost, s));
-    CAP_HIP(hipStreamSynchronize(s));
-  } else {
-    pub_inputs_launch(s, (uint32_t)count, (const fe*)d_vars, K->num_vars, K->wire_vars, K->chk_sel, K->n, (uint32_t)ni, nullptr,
-                      (fe*)d_pub, ni);
-  }
-  return take_launch_error();
-}
-int capgpu_plonk_pub_inputs(uint64_t pk_handle, int count, const uint64_t* vars, uint64_t* pub_out) {
-  return pub_inputs_run("capgpu_plonk_pub_inputs", pk_handle, count, vars, pub_out, nullptr, nullptr);
-}
-int capgpu_plonk_pub_inputs_dev(uint64_t pk_handle, int count, const void* d_vars, void* d_pub_out) {
-  return pub_inputs_run("capgpu_plonk_pub_inputs_dev", pk_handle, count, nullptr, nullptr, d_vars, d_pub_out);
-}
-
-int capgpu_plonk_key_hint_info(uint64_t pk_handle, capgpu_hint_info* info_out) {
-  if (!info_out) {
-    set_error("capgpu_plonk_key_hint_info: bad argument (info_out is NULL)");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  CAP_CHECK_INIT();
-  std::shared_ptr<ProvingKey> K;
-  int rc = home_key(pk_handle, &K);
-  if (rc) return rc;
-  std::lock_guard<std::mutex> klk(K->chk_mu);
-  memset(info_out, 0, sizeof *info_out);
-  if (K->solve && K->wire_vars) *info_out = K->solve->hint_info;
-  return CAPGPU_OK;
-}
-
-int capgpu_plonk_key_solver_info(uint64_t pk_handle, capgpu_solver_info* info_out) {
-  if (!info_out) {
-    set_error("capgpu_plonk_key_solver_info: bad argument (info_out is NULL)");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  CAP_CHECK_INIT();
-  std::shared_ptr<ProvingKey> K;
-  int rc = home_key(pk_handle, &K);
-  if (rc) return rc;
-  std::lock_guard<std::mutex> klk(K->chk_mu);
-  memset(info_out, 0, sizeof *info_out);
-  if (K->solve && K->wire_vars) *info_out = K->solve->info;
-  return CAPGPU_OK;
-}
-
-int capgpu_plonk_solve_vars(uint64_t pk_handle, int count, const uint64_t* given, uint64_t* vars_out,
-                            capgpu_solve_status* status_out) {
-  if (count < 0 || (count && (!given || !vars_out || !status_out))) {
-    set_error("capgpu_plonk_solve_vars: bad argument");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  CAP_CHECK_INIT();
-  if (count == 0) return CAPGPU_OK;
-  return solve_run(pk_handle, (uint32_t)count, given, vars_out, nullptr, nullptr, status_out);
-}
-
-int capgpu_plonk_solve_vars_dev(uint64_t pk_handle, int count, const void* d_given, void* d_vars_out,
-                                capgpu_solve_status* status_out) {
-  if (count < 0 || (count && (!d_given || !d_vars_out || !status_out))) {
-    set_error("capgpu_plonk_solve_vars: bad argument");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  CAP_CHECK_INIT();
-  if (count == 0) return CAPGPU_OK;
-  return solve_run(pk_handle, (uint32_t)count, nullptr, nullptr, d_given, d_vars_out, status_out);
-}
-
-int capgpu_plonk_free_key(uint64_t pk_handle) {
-  CAP_CHECK_INIT();
-  Runtime& R = rt();
-  {
-    std::lock_guard<std::mutex> lk(R.mu);
-    auto it = R.keys.find(pk_handle);
-    if (it == R.keys.end()) {
-      set_error("capgpu: unknown proving key handle %llu", (unsigned long long)pk_handle);
-      return CAPGPU_ERR_BAD_HANDLE;
-    }
-    R.keys.erase(it);
-  }
-  // every context that holds the key (or a replica) drains its stream before letting go of the tables
-  for (auto& cp : R.ctxs) {
-    Context& c = *cp;
-    ScopedCtx sc(c);
-    Entry lk(c);
-    auto it = c.keys.find(pk_handle);
-    if (it == c.keys.end()) continue;
-    (void)hipStreamSynchronize(c.stream);
-    c.keys.erase(it);
-  }
   return CAPGPU_OK;
 }
 
@@ -2346,18 +1100,6 @@ static int deal(int count, const std::function<int(int first, int cnt)>& part) {
       return rcs[i];
     }
   return CAPGPU_OK;
-}
-
-// The key of a part on the current context.  `home` (tickets only): the reference the ticket took at submission - a key
-// freed since then (capgpu_plonk_free_key with the ticket outstanding) is proved from that reference instead of refused.
-static int part_key(uint64_t h, const std::shared_ptr<ProvingKey>* home, std::shared_ptr<ProvingKey>* out) {
-  const int rc = lookup_key(h, out);
-  if (rc != CAPGPU_ERR_BAD_HANDLE || !home || !*home) return rc;
-  if ((*home)->device == ctx().device) {
-    *out = *home;
-    return CAPGPU_OK;
-  }
-  return clone_key_to_current(**home, (*home)->device, out);
 }
 
 // ---- the prove entry points ------------------------------------------------------------------------------------------------
@@ -4182,28 +2924,6 @@ int capgpu_plonk_check_witness_multi(const uint64_t* pk_handles, int count, cons
 
 int capgpu_plonk_set_precheck(int on) {
   g_precheck.store(on != 0);
-  return CAPGPU_OK;
-}
-
-int capgpu_plonk_set_solve_pack(int w) {
-  if (!spk::valid_setting(w)) {
-    set_error("capgpu_plonk_set_solve_pack: %d is none of 0 (automatic), 1, 2, 4, 8, 16", w);
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  g_solve_pack.store(w, std::memory_order_relaxed);
-  return CAPGPU_OK;
-}
-int capgpu_plonk_get_solve_pack(int* w_out) {
-  if (!w_out) {
-    set_error("capgpu_plonk_get_solve_pack: bad argument (w_out is NULL)");
-    return CAPGPU_ERR_INVALID_ARG;
-  }
-  *w_out = solve_pack_setting();
-  return CAPGPU_OK;
-}
-int capgpu_plonk_solve_stats(uint64_t* launches_out, uint64_t* witnesses_out, uint64_t* packed_launches_out) {
-  CAP_CHECK_INIT();
-  solve_stats(launches_out, witnesses_out, packed_launches_out);
   return CAPGPU_OK;
 }
 

@@ -1,5 +1,5 @@
 // The prover proper of plonk.hip - a component of that translation unit, like tickets.hpp, coalescer.hpp and
-// transcript_dev.hpp, included by it alone (behind ProvingKey, the graph cache and the host pool, which it uses): the
+// transcript_dev.hpp, included by it alone (behind the graph cache and the host pool, which it uses): the
 // launch wrappers and their scratch sizes, the batch workspace, the mode getters, the helpers of host-resident and
 // variable-form input, and the three types a proving call is made of -
 //   ProvePlan  every mode decision of a call, made once (make_plan);
@@ -7,6 +7,9 @@
 //              step with the scratch it asks for (`*_needs`) beside it;
 //   ProveNeeds what a plan asks of a context's buffers (capgpu_plonk_reserve).
 // prove_batch (plonk.hip) validates, plans, checks the witnesses, carves, picks the graph set and calls a driver.
+// What plonk_keys.hip and plonk_solver.hip - units without device code - call of this file is declared in prover.hpp and stands outside the
+// anonymous namespace: run_ntt, run_msm, pad_columns, wire_commit_from_evals and the two input counters.  Carver, which
+// plonk_solver.hip lays its scratch out with too, is prover.hpp's.
 #pragma once
 #include "check_kernels.hpp"
 #include "context.hpp"
@@ -15,6 +18,8 @@
 #include "outcome.hpp"
 #include "params.hpp"
 #include "plonk_kernels.hpp"
+#include "plonk_key.hpp"
+#include "prover.hpp"
 #include "round_launch.hpp"
 #include "transcript_dev.hpp"
 #include "vars_kernels.hpp"
@@ -35,6 +40,7 @@ inline size_t ntt3_scratch(uint32_t log_mm, size_t count, bool five = false) {
 // ... of Context::stage_b for `cnt` host-resident witnesses on a domain of n points
 inline size_t wires_stage_bytes(size_t cnt, size_t n) { return sizeof(fe) * cnt * NW * n; }
 
+}  // namespace
 int run_ntt(hipStream_t s, uint32_t log_n, fe* data, size_t stride, uint32_t count, int dir, int coset) {
   Context& c = ctx();
   const NttDomain* dom = nullptr;
@@ -46,6 +52,7 @@ int run_ntt(hipStream_t s, uint32_t log_n, fe* data, size_t stride, uint32_t cou
   if (rc) return hip_fail((hipError_t)rc, "ntt_run");
   return CAPGPU_OK;
 }
+namespace {
 
 // out-of-place form: `count` arrays of src_len elements at src (src_stride apart; zero-extended to the transform
 // size inside the kernel) -> transforms at dst (dst_stride apart).  Saves the padded copy an in-place call needs.
@@ -130,6 +137,7 @@ int run_ntt3_inv(hipStream_t s, uint32_t log_mm, fe* data, uint32_t count, const
   return CAPGPU_OK;
 }
 
+}  // namespace
 int run_msm(hipStream_t s, const MsmBases& B, const fe* scalars, size_t outer_stride, uint32_t inner,
             size_t inner_stride, size_t n, uint32_t batch, g1_jac* d_out) {
   Context& c = ctx();
@@ -156,19 +164,24 @@ int run_msm(hipStream_t s, const MsmBases& B, const fe* scalars, size_t outer_st
   }
   return CAPGPU_OK;
 }
+// pk::pad_copy for the key builders of plonk_keys.hip
+void pad_columns(hipStream_t s, fe* dst, size_t dst_outer, size_t dst_inner, const fe* src, size_t src_outer,
+                 size_t src_inner, uint32_t inner, uint32_t count, size_t len, size_t total) {
+  pad_copy(s, dst, dst_outer, dst_inner, src, src_outer, src_inner, inner, count, len, total);
+}
 
-struct Carver {
-  char* base;
-  size_t off = 0;
-  explicit Carver(void* b) : base((char*)b) {}
-  template <class T>
-  T* take(size_t count) {
-    off = (off + 255) / 256 * 256;
-    T* p = base ? (T*)(base + off) : nullptr;
-    off += sizeof(T) * count;
-    return p;
-  }
-};
+// A key's constants as the kernels take them.  ProvingKey keeps them in ks::QuotConst, the definition a unit without
+// device code sees (plonk_key.hpp); this unit sees the kernels' own too and holds the two together.
+static_assert(ks::NW == NW && ks::NS == NS && ks::kPkcCols == kPkcCols && sizeof(ks::QuotConst) == sizeof(QuotConst) &&
+                  offsetof(ks::QuotConst, g) == offsetof(QuotConst, g) && offsetof(ks::QuotConst, k) == offsetof(QuotConst, k) &&
+                  offsetof(ks::QuotConst, zh_inv) == offsetof(QuotConst, zh_inv),
+              "plonk_key.hpp restates the key's shape for the host units");
+static inline QuotConst quot_const(const ks::QuotConst& q) {
+  QuotConst r;
+  memcpy(&r, &q, sizeof r);
+  return r;
+}
+namespace {
 
 struct BatchWs {
   fe *wpoly, *wev, *pi, *num, *den, *pre, *sfx, *scan_tot, *inv_total, *zpoly, *coset, *pkc, *t, *pows, *pows_small, *pw, *batchpoly,
@@ -259,7 +272,7 @@ int compute_pk_coset(hipStream_t s, const ProvingKey& K, fe* dst) {
 int compute_pk_kx(hipStream_t s, const ProvingKey& K, fe* dst) {
   const Ntt3Domain* dq = nullptr;
   if (int rc = get_domain3(K.log_m, &dq)) return rc;
-  kx_columns(s, dst + (size_t)18 * K.m, (const fe*)dq->xs29, K.qc29, K.m);
+  kx_columns(s, dst + (size_t)18 * K.m, (const fe*)dq->xs29, quot_const(K.qc29), K.m);
   return CAPGPU_OK;
 }
 // CAPGPU_QUOT_FOLD (read per call): 1, the default - k_quotient's permutation terms with beta folded out; 0 - the direct
@@ -282,6 +295,7 @@ int quotient_cosets() {
 // have one non-zero digit or none.  capgpu_plonk_set_wire_commit: 0 coefficients, 1 evaluations, -1 the default
 // (evaluations; CAPGPU_WIRE_COMMIT=coeffs turns it off for the process).
 std::atomic<int> g_wire_commit{-1};
+}  // namespace
 bool wire_commit_from_evals() {
   static const int env_default = [] {
     const char* e = getenv("CAPGPU_WIRE_COMMIT");
@@ -290,6 +304,7 @@ bool wire_commit_from_evals() {
   const int m = g_wire_commit.load(std::memory_order_relaxed);
   return (m < 0 ? env_default : m) != 0;
 }
+namespace {
 
 // Where the Fiat-Shamir transcript of a prove call runs (capgpu_plonk_set_transcript; CAPGPU_TRANSCRIPT=device|host sets
 // the process default): on the host - between the rounds the commitments come back, the host hashes them and sends the
@@ -395,7 +410,9 @@ uint32_t h2d_chunk_start(uint32_t P, uint32_t chunks, uint32_t ck, bool short_fi
 // ---- variable-form input (CAPGPU_INPUT_VARS; kernels: vars_kernels.hpp) ------------------------------------------------
 // A witness arrives as one value per variable and becomes the five wire columns on the device, through the table its key
 // keeps: 32 B x num_vars over the link instead of 32 B x 5 n.  Everything behind the gather is the evals path.
+}  // namespace
 std::atomic<uint64_t> g_witness_h2d{0}, g_gather_launches{0};  // capgpu_plonk_input_stats
+namespace {
 inline void count_witness_h2d(size_t bytes) { g_witness_h2d.fetch_add(bytes, std::memory_order_relaxed); }
 
 // Context::stage_b for `cnt` witnesses in variable form: the five columns the gather writes ([cnt][5 n], where the evals
@@ -598,6 +615,7 @@ struct ProveRun {
   const NttDomain* dom_n = nullptr;
   const Ntt3Domain* dom_q = nullptr;
   const fe omega;
+  const QuotConst qc29;  // K.qc29 as the kernels take it
   std::vector<uint64_t> pub_rows;  // mixed keys: the unused tail of a shorter key's row must be zero on the device
   std::vector<const fe*> key_ptrs;
   const fe* const* sig_of = nullptr;
@@ -624,7 +642,7 @@ struct ProveRun {
   ProveRun(Context& c_, const ProvePlan& pl_, const ProvingKey& K_, const ProveRequest& rq_)
       : side_drain{c_, false}, c(c_), s(c_.stream), pl(pl_), K(K_), rq(rq_), P(pl_.P), n(K_.n), m(K_.m), ps(K_.ps),
         num_inputs(rq_.num_inputs), d_wires(rq_.d_wires), pub_inputs(rq_.pub_inputs),
-        h_wires(pl_.r1_copies ? rq_.h_wires : nullptr), omega(ntt_root_of_unity(K_.log_n)),
+        h_wires(pl_.r1_copies ? rq_.h_wires : nullptr), omega(ntt_root_of_unity(K_.log_n)), qc29(quot_const(K_.qc29)),
         proofs_bytes((size_t)pl_.P * td::kPrBytes) {}
   ProveRun(const ProveRun&) = delete;
   ProveRun& operator=(const ProveRun&) = delete;
@@ -997,7 +1015,7 @@ struct ProveRun {
     nd.msm(pl.wire_key(), K.n + 3, cnt);
   }
   int r2_body() {
-    perm_numden(s, pl.coeffs ? (const fe*)w.wev : d_wires, K.sig_eval, sig_of, dom_n->tw_fwd, w.chal, K.qc29, n, P, w.num,
+    perm_numden(s, pl.coeffs ? (const fe*)w.wev : d_wires, K.sig_eval, sig_of, dom_n->tw_fwd, w.chal, qc29, n, P, w.num,
                 w.den);
     {
       uint32_t nb = cdiv(n, kScanBlock);
@@ -1033,12 +1051,12 @@ struct ProveRun {
     const uint32_t five = pl.five ? 1u : 0u;
     const size_t pts = pl.five ? 5 * n : m;
     if (fold)
-      quotient<true>(s, P, pts, pkc, pkc_of, w.coset, dom_q->xs29, K.inv_nx1, w.chal29, K.qc29, m, 1u, five, w.t);
+      quotient<true>(s, P, pts, pkc, pkc_of, w.coset, dom_q->xs29, K.inv_nx1, w.chal29, qc29, m, 1u, five, w.t);
     // the direct form: for every proof (fold = 0), or behind the folded launch for the proofs it left out - beta = 0.
     // The host transcript knows whether there is one; the device transcript does not, and its launch is P x m / 256
     // workgroups that load one word and leave.
     if (!fold || fold == 2 || beta_zero_possible)
-      quotient<false>(s, P, pts, pkc, pkc_of, w.coset, dom_q->xs29, K.inv_nx1, w.chal29, K.qc29, m, fold ? 1u : 0u, five,
+      quotient<false>(s, P, pts, pkc, pkc_of, w.coset, dom_q->xs29, K.inv_nx1, w.chal29, qc29, m, fold ? 1u : 0u, five,
                       w.t);
     // k_quotient leaves the public-input term out; it arrives here as coefficients (pi_fold), before the degree check
     if (pl.five) {

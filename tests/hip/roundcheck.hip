@@ -1,8 +1,8 @@
 // Drives the O(n) kernels of the five prover rounds (cap_amd/csrc/plonk_kernels.hpp) directly, on inputs a proof never
-// presents: chosen challenges, tables the kernels did not make, values at the edges of each input's contract.  The
-// kernels sit in plonk.hip's anonymous namespace and cannot be reached through the library, so this program includes
-// plonk_kernels.hpp itself - built with the product's flags and with CAP_FL_SCHED as plonk.hip sets it - and launches
-// through round_launch.hpp, the geometry the prover uses.  It links libcapgpu.so for what launch.hpp needs.
+// presents: chosen challenges, tables the kernels did not make, values at the edges of each input's contract.  This
+// program compiles the kernels itself: it includes plonk_kernels.hpp - built with the product's flags and with
+// CAP_FL_SCHED as plonk.hip sets it, so it needs no export from the library - and launches through
+// round_launch.hpp, the geometry the prover uses.  It links libcapgpu.so for what launch.hpp needs.
 //
 //   roundcheck <cases.bin> <results.bin>
 //
