@@ -20,46 +20,23 @@
 
 #include <vector>
 
-#include "curve29.hpp"
+#include "lagrange_elem29.hpp"
 #include "launch.hpp"
 #include "ntt.hpp"
 
 namespace cap {
 namespace {
 
-using F = Fq29;
-constexpr uint32_t kLagBlind = 3;  // blinding points behind the n Lagrange points
-
-__device__ __forceinline__ g1x neg_pt(const g1x& p) {
-  g1x r = p;
-  r.y = F::weak_reduce(F::neg(p.y));
-  return r;
-}
-
-// [k] B, k a canonical 256-bit integer: two bits per step from the top (B, 2B, 3B held in registers)
-__device__ __noinline__ g1x scalar_mul(const g1x& b, const fe& k) {
-  int top = -1;
-  for (int i = 7; i >= 0 && top < 0; i--)
-    if (k.v[i]) top = 32 * i + (31 - __clz(k.v[i]));
-  if (top < 0 || G1L::is_inf(b)) return G1L::inf();
-  const g1x b2 = G1L::dbl(b);
-  const g1x b3 = G1L::add(b2, b);
-  g1x acc = G1L::inf();
-  for (int pos = top | 1; pos >= 1; pos -= 2) {  // digit = bits pos, pos - 1
-    acc = G1L::dbl(G1L::dbl(acc));
-    const uint32_t d = (k.v[(pos - 1) >> 5] >> ((pos - 1) & 31)) & 3u;
-    if (d) acc = G1L::add(acc, d == 1 ? b : (d == 2 ? b2 : b3));
-  }
-  return acc;
-}
+// the per-lane arithmetic is lagrange_elem29.hpp's (host+device: tests/cpp/lagrange_check.cpp runs it with the bound
+// assertions on); the kernels keep the indexing, the bounds tests and the memory traffic
 
 // a[bitrev(i)] = P_i (the window-0 rows of the SRS table: internal form, canonical)
 __global__ __launch_bounds__(256) void lag_load(g1_xyzz* __restrict__ a, const g1_affine* __restrict__ srs, uint32_t n,
                                                 uint32_t log_n) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const uint32_t r = log_n ? __brev(i) >> (32 - log_n) : 0;
-  a[r] = G1L::store(G1L::from_affine(G1L::load(srs[i])));
+  const uint32_t r = Lag::bitrev(i, log_n);
+  a[r] = Lag::load_point(srs[i]);
 }
 
 // one decimation-in-time stage on blocks of 2 * half points: (A, B) -> (A + [w] B, A - [w] B), w = omega_n^-(j * step)
@@ -68,11 +45,7 @@ __global__ __launch_bounds__(64) void lag_stage(g1_xyzz* __restrict__ a, uint32_
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n / 2) return;
   const uint32_t j = t & (half - 1), i0 = ((t - j) << 1) + j, i1 = i0 + half;
-  const g1x A = G1L::load(a[i0]);
-  g1x B = G1L::load(a[i1]);
-  if (j) B = scalar_mul(B, tw[(size_t)j * step]);
-  a[i0] = G1L::store(G1L::add(A, B));
-  a[i1] = G1L::store(G1L::add(A, neg_pt(B)));
+  Lag::butterfly(a[i0], a[i1], tw[(size_t)j * step], j != 0, a[i0], a[i1]);
 }
 
 // out[j] = [1/n] a[j] in arkworks' affine form (what msm_precompute takes), j < n; out[n .. n + 2] = the blinding points
@@ -80,22 +53,7 @@ __global__ __launch_bounds__(64) void lag_finish(const g1_xyzz* __restrict__ a, 
                                                  const g1_affine* __restrict__ srs, g1_affine* __restrict__ out) {
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n + kLagBlind) return;
-  g1x p;
-  if (j < n) {
-    p = scalar_mul(G1L::load(a[j]), n_inv);
-  } else {  // [tau^(n + e)] G - [tau^e] G, e = j - n
-    p = G1L::add_mixed(G1L::from_affine(G1L::load(srs[j])), G1L::load(srs[j - n]), true);
-  }
-  g1_affine o;
-  if (G1L::is_inf(p)) {
-    o.x = Fq::zero();
-    o.y = Fq::zero();
-  } else {
-    const g1a q = G1L::to_affine(p);
-    o.x = F::to_ext(q.x);
-    o.y = F::to_ext(q.y);
-  }
-  out[j] = o;
+  Lag::finish(a, n, n_inv, srs, j, out[j]);
 }
 
 }  // namespace
