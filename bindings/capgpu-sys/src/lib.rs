@@ -515,6 +515,15 @@ extern "C" {
                                              proofs_out: *mut capgpu_proof, outcomes_out: *mut capgpu_prove_outcome,
                                              solved_out: *mut capgpu_solve_status, ticket_out: *mut u64) -> c_int;
     pub fn capgpu_plonk_reserve_given(pk_handle: u64, count: c_int, slot: c_int) -> c_int;
+    pub fn capgpu_plonk_prove_given_one(pk_handle: u64, given: *const u64, num_given: usize, pub_inputs: *const u64,
+                                        num_inputs: usize, ext_msg: *const u8, ext_msg_len: usize, blinders: *const u64,
+                                        proof_out: *mut capgpu_proof, outcome_out: *mut capgpu_prove_outcome,
+                                        solved_out: *mut capgpu_solve_status) -> c_int;
+    pub fn capgpu_plonk_prove_given_io_one(pk_handle: u64, given: *const u64, num_given: usize, num_inputs: usize,
+                                           ext_msg: *const u8, ext_msg_len: usize, blinders: *const u64,
+                                           pub_inputs_out: *mut u64, proof_out: *mut capgpu_proof,
+                                           outcome_out: *mut capgpu_prove_outcome,
+                                           solved_out: *mut capgpu_solve_status) -> c_int;
     // ---- verification (host only)
     pub fn capgpu_g2_generator(out: *mut u64) -> c_int;
     pub fn capgpu_g2_mul(q: *const u64, scalar: *const u64, out: *mut u64) -> c_int;
@@ -1042,6 +1051,27 @@ impl ProvingKey {
         })?;
         Ok(proofs.into_iter().zip(outcomes).map(|(p, o)| if o.status == CAPGPU_OK { Ok(p) } else { Err(ProveError::from(o)) })
             .collect())
+    }
+    /// `prove()` for ONE note from the values its circuit is given (`capgpu_plonk_prove_given_one`): the call of a rayon
+    /// map over notes - `notes.par_iter().map(|n| pk.prove_given_one(..)).collect::<Vec<_>>()`.  With `set_coalescing`
+    /// on, the concurrent calls are gathered into one solve and one device batch; every caller's `Ok` proof is bit for bit
+    /// its lone call's.  `Err`: the outcome record and message of a witness that does not satisfy the circuit, or - a
+    /// call that could not run - the library's code in `outcome.status` and its message.
+    pub fn prove_given_one(&self, given: &[[u64; 4]], pub_inputs: &[[u64; 4]], ext_msg: &[u8], blinders: &[[u64; 4]; 13])
+                           -> std::result::Result<capgpu_proof, ProveError> {
+        let mut proof: capgpu_proof = unsafe { std::mem::zeroed() };
+        let mut outcome = capgpu_prove_outcome::default();
+        let rc = unsafe {
+            capgpu_plonk_prove_given_one(self.handle, given.as_ptr() as *const u64, given.len(),
+                                         pub_inputs.as_ptr() as *const u64, pub_inputs.len(),
+                                         if ext_msg.is_empty() { std::ptr::null() } else { ext_msg.as_ptr() }, ext_msg.len(),
+                                         blinders.as_ptr() as *const u64, &mut proof, &mut outcome, std::ptr::null_mut())
+        };
+        if let Err(e) = check(rc) {
+            outcome.status = e.code;
+            return Err(ProveError { outcome, message: e.message });
+        }
+        if outcome.status == CAPGPU_OK { Ok(proof) } else { Err(ProveError::from(outcome)) }
     }
     /// Sizes context `slot` (-1: every context) ahead for batches of `count` host-resident proofs under this key, so that
     /// no allocation lands inside a steady-state call (`scratch_stats` then stays put).

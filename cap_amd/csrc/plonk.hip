@@ -37,6 +37,7 @@
 #include "compact.hpp"
 #include "compact_kernels.hpp"
 #include "context.hpp"
+#include "given_gather.hpp"
 #include "host_util.hpp"
 #include "launch.hpp"
 #include "notes.hpp"
@@ -805,6 +806,15 @@ struct ProveReq {
   // the caller's own copy of its witness on the device, started when the call arrived (StagePool); null: not staged
   const void* d_wires = nullptr;
   hipEvent_t staged = nullptr;  // recorded behind that copy
+  // capgpu_plonk_prove_given_one / _io_one (kind != kWires): `wires` stays null, the values the circuit is given come in
+  // its place; the requests of one gathered batch share the kind too (it is part of the group id)
+  enum Kind { kWires = 0, kGiven, kGivenIo };
+  Kind kind = kWires;
+  const uint64_t* given = nullptr;
+  size_t num_given = 0;
+  capgpu_prove_outcome* outcome = nullptr;
+  capgpu_solve_status* solved = nullptr;  // optional
+  uint64_t* pub_out = nullptr;            // kGivenIo: the caller's row of computed public inputs
 };
 
 // OPTIONAL (CAPGPU_COALESCE_PRESTAGE=1; off by default): witnesses of coalesced single-proof calls copied to the device BY
@@ -1133,6 +1143,8 @@ struct ProveCall {
   bool given_dev = false;
   capgpu_solve_status* solved = nullptr;  // optional: the solver's verdict per proof
   size_t given_stride = 0;                // elements per proof of `given`: the largest num_given among the keys of the WHOLE call
+  size_t given_own_bytes = 0;             // a gathered part (run_coalesced_given): what its callers brought - the rows are padded
+                                          // by the library, capgpu_plonk_input_stats counts the callers' own bytes; 0: the rows'
   // capgpu_plonk_prove_given_io*: the public inputs are computed from the solved assignments into pub_out - which
   // pub_inputs then points at too: from the gather on, the call is a given-value call on that host buffer
   uint64_t* pub_out = nullptr;
@@ -1370,7 +1382,7 @@ static int given_part(const ProveCall& b, int first, int cnt) {
     if (bytes) {
       CAP_HIP(hipMemcpyAsync(g.given, (const uint64_t*)b.given + (size_t)4 * first * b.given_stride, bytes,
                              hipMemcpyHostToDevice, s));
-      count_witness_h2d(bytes);
+      count_witness_h2d(b.given_own_bytes ? b.given_own_bytes : bytes);
     }
     d_given = g.given;
   }
@@ -2470,6 +2482,16 @@ int capgpu_plonk_reserve_notes(const uint64_t* pk_handles, int count, int input_
   return CAPGPU_OK;
 }
 
+// gathered batches differ in size from one to the next: scratch that has to grow for one of `g` proofs grows to the next
+// multiple of 32 proofs (64 at least) at once, while this object lives (see run_coalesced)
+struct GatheredGrowth {
+  double prev;
+  explicit GatheredGrowth(size_t g) : prev(scratch_growth_scale()) {
+    scratch_growth_scale() = (double)std::max<size_t>(64, (g + 31) / 32 * 32) / (double)g;
+  }
+  ~GatheredGrowth() { scratch_growth_scale() = prev; }
+};
+
 // one gathered batch: device staging of every request's wires, per-proof messages and keys.  Without the witness check
 // the batch is proved in outcome mode (ProveRequest::outcomes): a request whose witness does not satisfy its circuit gets
 // its own CAPGPU_ERR_PROOF with the message its lone call would set, the others get their proofs - nothing is proved twice.
@@ -2549,11 +2571,7 @@ static void run_coalesced(std::vector<ProveReq*>& reqs) {
   // gathered batches differ in size from one to the next: scratch that has to grow for one grows to the next multiple of
   // 32 proofs (64 at least) at once - a context otherwise re-allocates gigabytes (0.1 - 0.6 s each time) whenever a batch
   // is a few proofs larger than every batch it has seen (round 6: it cost the bench's coalesced leg a third)
-  struct GrowthScale {
-    double prev;
-    explicit GrowthScale(double f) : prev(scratch_growth_scale()) { scratch_growth_scale() = f; }
-    ~GrowthScale() { scratch_growth_scale() = prev; }
-  } growth((double)std::max<size_t>(64, (g + 31) / 32 * 32) / (double)g);
+  GatheredGrowth growth(g);
   int rc = scratch_reserve(c.stage_b, vars ? vars_stage_bytes(g, n, vstride, true) : per * g);
   if (rc) return fail_all(rc);
   char* const in_base = (char*)c.stage_b.p + (vars ? wires_stage_bytes(g, n) : 0);  // (g: the batch as it arrived)
@@ -2681,6 +2699,216 @@ static void run_coalesced(std::vector<ProveReq*>& reqs) {
   coalescer().proofs += g;
 }
 
+// ---- capgpu_plonk_prove_given_one / _io_one: single given-value calls, gathered ---------------------------------------------
+static const char kProveGivenOne[] = "capgpu_plonk_prove_given_one";
+// what the packing rule (given_gather.hpp) needs to know of one request: its key's home copy - no device is touched - and
+// the two lengths on either side.  An unknown handle leaves home_key's code and message behind.
+static int given_one_ask(uint64_t pk, size_t num_given, size_t num_inputs, std::shared_ptr<ProvingKey>* hold, gg::Ask* ask) {
+  *ask = gg::Ask{};
+  ask->num_given = num_given;
+  ask->num_inputs = num_inputs;
+  const int rc = home_key(pk, hold);
+  if (rc) return rc;
+  const ProvingKey& K = **hold;
+  ask->key_found = true;
+  ask->key_inputs = K.num_inputs;
+  std::lock_guard<std::mutex> klk(K.chk_mu);
+  ask->has_solver = K.solve && K.wire_vars;
+  if (ask->has_solver) ask->key_given = K.solve->plan.num_given;
+  return CAPGPU_OK;
+}
+// the code and message of a request that does not run
+static int given_one_refusal(gg::Aside why, const gg::Ask& a, uint64_t pk) {
+  switch (why) {
+    case gg::kRuns:
+      return CAPGPU_OK;
+    case gg::kKeyGone: {
+      std::shared_ptr<ProvingKey> none;
+      const int rc = home_key(pk, &none);  // (its code and message; handles are never reused)
+      return rc ? rc : CAPGPU_ERR_BAD_HANDLE;
+    }
+    case gg::kNoSolver:
+      return no_solver(kProveGivenOne);
+    default:
+      set_error("%s: %zu given values and %zu public inputs passed, the key has %zu and %zu", kProveGivenOne, a.num_given,
+                a.num_inputs, a.key_given, a.key_inputs);
+      return CAPGPU_ERR_INVALID_ARG;
+  }
+}
+
+// One gathered part of given-value requests (one kind: all plain or all _io) on the calling thread's context, whose lock the
+// leader - or the helper thread of a cut batch - holds.  The requests that cannot run are set aside with their own code and
+// message; the rows of the others are packed by given_gather.hpp's rule into ONE ProveCall with a key per proof, which
+// given_part solves and proves: one staging copy, one solver launch per distinct key, the variable-form outcome call on
+// library staging, witness check and compaction as that call applies them.  Then every caller gets what lies in its slot.
+static void run_coalesced_given(std::vector<ProveReq*>& reqs) {
+  Context& c = ctx();
+  Entry lk(c);
+  const bool io = reqs[0]->kind == ProveReq::kGivenIo;
+  std::vector<gg::Ask> asks(reqs.size());
+  std::vector<std::shared_ptr<ProvingKey>> homes_all(reqs.size());
+  for (size_t i = 0; i < reqs.size(); i++)
+    (void)given_one_ask(reqs[i]->pk, reqs[i]->num_given, reqs[i]->num_inputs, &homes_all[i], &asks[i]);
+  const gg::Plan pl = gg::plan(asks.data(), asks.size());
+  for (size_t i = 0; i < reqs.size(); i++)
+    if (pl.why[i] != gg::kRuns) {
+      reqs[i]->rc = given_one_refusal(pl.why[i], asks[i], reqs[i]->pk);
+      reqs[i]->err = capgpu_last_error();
+    }
+  const size_t g = pl.slots();
+  if (g == 0) return;
+  // the slots [first, first + cnt) as one given-value call
+  auto run = [&](size_t first, size_t cnt) {
+    std::vector<uint64_t> handles(cnt);
+    std::vector<std::shared_ptr<ProvingKey>> homes(cnt);
+    std::vector<gg::Ask> part(cnt);
+    for (size_t s = 0; s < cnt; s++) part[s] = asks[pl.req_of[first + s]];
+    const gg::Plan pp = gg::plan(part.data(), cnt);  // (every one of them runs: the strides of THIS call)
+    std::vector<uint64_t> given(pp.given_words(), 0), pubs(pp.pub_words(), 0), blind(pp.blind_words());
+    std::vector<const uint8_t*> msgs(cnt);
+    std::vector<size_t> lens(cnt);
+    std::vector<capgpu_proof> out(cnt);
+    std::vector<capgpu_prove_outcome> outs(cnt);
+    std::vector<capgpu_solve_status> solved(cnt);
+    size_t stride = 0, own = 0;
+    for (size_t s = 0; s < cnt; s++) {
+      const ProveReq& r = *reqs[pl.req_of[first + s]];
+      handles[s] = r.pk;
+      homes[s] = homes_all[pl.req_of[first + s]];
+      stride = std::max(stride, homes[s]->num_vars);
+      gg::pack_row(&given[pp.given_at(s)], pp.given_stride, r.given, r.num_given);
+      if (!io) gg::pack_row(&pubs[pp.pub_at(s)], pp.pub_stride, r.pubs, r.num_inputs);
+      memcpy(&blind[pp.blind_at(s)], r.blinders, sizeof(uint64_t) * gg::kWords * gg::kBlinders);
+      msgs[s] = r.msg_len ? r.msg : nullptr;
+      lens[s] = r.msg ? r.msg_len : 0;
+      own += sizeof(fe) * r.num_given;
+    }
+    ProveCall b = each_call(handles.data(), (int)cnt, nullptr, pubs.data(), pp.pub_stride, msgs.data(), lens.data(),
+                            blind.data(), CAPGPU_INPUT_VARS, out.data(), outs.data());
+    b.one_key = each_one_key(b);
+    b.homes = homes.data();
+    b.n = homes[0]->n;
+    b.stride = stride;
+    b.given = given.data();
+    b.given_stride = pp.given_stride;
+    b.given_own_bytes = own;
+    b.solved = solved.data();
+    b.pub_out = io ? pubs.data() : nullptr;
+    GatheredGrowth growth(cnt);
+    trace("co_given_packed", (int64_t)cnt, (int64_t)own);
+    int rc = given_part(b, 0, (int)cnt);
+    if (rc == CAPGPU_OK) rc = take_launch_error();
+    const std::string err = rc ? capgpu_last_error() : "";
+    for (size_t s = 0; s < cnt; s++) {
+      ProveReq& r = *reqs[pl.req_of[first + s]];
+      r.rc = rc;
+      if (rc) {  // a failure of the part is every caller's
+        r.err = err;
+        continue;
+      }
+      gg::normalise(&outs[s]);
+      *r.out = out[s];
+      *r.outcome = outs[s];
+      if (r.solved) *r.solved = solved[s];
+      if (io) gg::take_row(r.pub_out, &pubs[pp.pub_at(s)], r.num_inputs);
+    }
+  };
+  bool mixed = false, recompute = false;
+  for (size_t s = 0; s < g; s++) {
+    const ProvingKey* K = homes_all[pl.req_of[s]].get();
+    mixed = mixed || K != homes_all[pl.req_of[0]].get();
+    recompute = recompute || K->recompute;
+  }
+  if (mixed && recompute) {  // the reference-schedule test mode keeps one key per batch: these go one by one
+    for (size_t s = 0; s < g; s++) run(s, 1);
+    coalescer().batches += g;
+  } else {
+    run(0, g);
+    coalescer().batches++;
+  }
+  coalescer().proofs += g;
+}
+
+// what the gathering protocol (coalescer.hpp) needs from the runtime: free device contexts and the prover
+struct CoalesceHooks {
+  // a free device context: any of the process's (several batches are then in flight, one per context), or the one
+  // this thread bound itself to; mode A of config 4: gathered batches go to the communicator's context, whole
+  void* acquire() {
+    const int ss = comm_shard_slot();
+    const int bound = ss >= 0 && (size_t)ss < num_contexts() ? ss : thread_bound_slot();
+    if (bound >= 0) {
+      Context* b = rt().ctxs[(size_t)bound].get();
+      return b->mu.try_lock() ? b : nullptr;
+    }
+    return try_acquire_context();
+  }
+  void* acquire_second() {
+    if (thread_bound_slot() >= 0 || comm_shard_slot() >= 0 || num_contexts() <= 1) return nullptr;
+    Context* c2 = try_acquire_context();
+    if (c2) c2->mu.unlock();  // the helper thread locks it itself (the lock belongs to the thread that takes it)
+    return c2;
+  }
+  // (the requests of one group are of one kind: wire-form, given-value, or given-value with computed public inputs)
+  static void run_kind(std::vector<ProveReq*>& reqs) {
+    if (reqs[0]->kind == ProveReq::kWires) run_coalesced(reqs);
+    else run_coalesced_given(reqs);
+  }
+  void run(void* ctx, std::vector<ProveReq*>& reqs, bool on_helper) {
+    Context& c = *static_cast<Context*>(ctx);
+    ScopedCtx sc(c);
+    if (on_helper) {
+      Entry elk(c);
+      run_kind(reqs);
+    } else {
+      run_kind(reqs);  // re-enters the (recursive) context lock this thread holds
+    }
+  }
+  void release(void* ctx) { static_cast<Context*>(ctx)->mu.unlock(); }
+  size_t deal_min() { return (size_t)::deal_min(); }
+  size_t split_eighths() {  // CAPGPU_COALESCE_SPLIT = eighths of the first part
+    static const size_t eighths = (size_t)env_int("CAPGPU_COALESCE_SPLIT", 3, 1, 4);
+    return eighths;
+  }
+  // batch parts running at once before a leader keeps collecting instead of taking another free context:
+  // CAPGPU_COALESCE_INFLIGHT (default 2) per bound DEVICE - two large batches fill a GPU, a third only fragments them
+  size_t max_in_flight() {
+    static const size_t per_device = (size_t)env_int("CAPGPU_COALESCE_INFLIGHT", 2, 1, 64);
+    int devices = 1;
+    (void)capgpu_physical_device_count(&devices);
+    return per_device * (size_t)std::max(devices, 1);
+  }
+  bool early_release() {  // CAPGPU_COALESCE_EARLY=0: a cut batch's callers return when both parts are done, as before
+    static const bool early = env_int("CAPGPU_COALESCE_EARLY", 1) != 0;
+    return early;
+  }
+};
+
+// The group of a key's requests: keys of one domain size under one SRS may share a device batch.  Bits 0-5 of the id are
+// log2 of the domain size, bits 6-7 the form - the three input forms of the wire-form calls, and the value they leave free
+// (3) for the given-value calls -, bit 63 tells the _io calls among those (a batch proves either against supplied or against
+// computed public inputs), the SRS handle lies from bit 8 up.  *key_n: the key's domain size.  Called with `lk` (on co.mu)
+// held; returns with it held, except with an error - an unknown handle -, which the caller returns at once.
+static int coalesce_group(Coalescer& co, std::unique_lock<std::mutex>& lk, uint64_t pk_handle, unsigned form_bits, bool io,
+                          uint64_t* group, size_t* key_n) {
+  const uint64_t gkey = (pk_handle << 2) | (uint64_t)form_bits;
+  auto it = co.group_of.find(gkey);
+  if (it == co.group_of.end()) {
+    // first call for this key: its domain size and SRS make the group
+    lk.unlock();
+    size_t kn = 0;
+    uint64_t ksrs = 0;
+    int rc = capgpu_plonk_key_info(pk_handle, &kn, nullptr, &ksrs);
+    if (rc) return rc;
+    lk.lock();
+    it = co.group_of.emplace(gkey, std::make_pair((ksrs << 8) ^ (uint64_t)__builtin_ctzll(kn | (1ull << 63)) ^
+                                                      ((uint64_t)form_bits << 6),
+                                                  kn)).first;
+  }
+  *group = it->second.first ^ (io ? 1ull << 63 : 0);
+  *key_n = it->second.second;
+  return CAPGPU_OK;
+}
+
 int capgpu_plonk_prove_ex(uint64_t pk_handle, const uint64_t* wires, const uint64_t* pub_inputs, size_t num_inputs,
                           const uint8_t* ext_msg, size_t ext_msg_len, const uint64_t* blinders, int input_form,
                           capgpu_proof* proof_out) {
@@ -2700,27 +2928,7 @@ int capgpu_plonk_prove_ex(uint64_t pk_handle, const uint64_t* wires, const uint6
   std::unique_lock<std::mutex> lk(co.mu);
   uint64_t group = 0;
   size_t key_n = 0;
-  {
-    // (key, form) -> group: bits 6-7 of the group id are the input form, the bits below them the domain size
-    const uint64_t gkey = (pk_handle << 2) | (uint64_t)input_form;
-    auto it = co.group_of.find(gkey);
-    if (it == co.group_of.end()) {
-      // first call for this key: its domain size and SRS make the group
-      lk.unlock();
-      size_t kn = 0;
-      uint64_t ksrs = 0;
-      int rc = capgpu_plonk_key_info(pk_handle, &kn, nullptr, &ksrs);
-      if (rc) return rc;
-      lk.lock();
-      group = (ksrs << 8) ^ (uint64_t)__builtin_ctzll(kn | (1ull << 63)) ^
-              ((uint64_t)input_form << 6);
-      co.group_of[gkey] = {group, kn};
-      key_n = kn;
-    } else {
-      group = it->second.first;
-      key_n = it->second.second;
-    }
-  }
+  if (int rc = coalesce_group(co, lk, pk_handle, (unsigned)input_form, false, &group, &key_n)) return rc;
   // this caller's witness starts its way to the device now, on the staging pool's stream, while the batch it will be
   // part of is still being gathered (one bound device only: the slot must live where the batch runs)
   StageSlot slot;
@@ -2755,54 +2963,7 @@ int capgpu_plonk_prove_ex(uint64_t pk_handle, const uint64_t* wires, const uint6
     StageSlot& s;
     ~SlotReturn() { stage_pool().release(s); }
   } slot_return{slot};
-  // what the protocol needs from the runtime: free device contexts and the prover
-  struct Hooks {
-    // a free device context: any of the process's (several batches are then in flight, one per context), or the one
-    // this thread bound itself to; mode A of config 4: gathered batches go to the communicator's context, whole
-    void* acquire() {
-      const int ss = comm_shard_slot();
-      const int bound = ss >= 0 && (size_t)ss < num_contexts() ? ss : thread_bound_slot();
-      if (bound >= 0) {
-        Context* b = rt().ctxs[(size_t)bound].get();
-        return b->mu.try_lock() ? b : nullptr;
-      }
-      return try_acquire_context();
-    }
-    void* acquire_second() {
-      if (thread_bound_slot() >= 0 || comm_shard_slot() >= 0 || num_contexts() <= 1) return nullptr;
-      Context* c2 = try_acquire_context();
-      if (c2) c2->mu.unlock();  // the helper thread locks it itself (the lock belongs to the thread that takes it)
-      return c2;
-    }
-    void run(void* ctx, std::vector<ProveReq*>& reqs, bool on_helper) {
-      Context& c = *static_cast<Context*>(ctx);
-      ScopedCtx sc(c);
-      if (on_helper) {
-        Entry elk(c);
-        run_coalesced(reqs);
-      } else {
-        run_coalesced(reqs);  // re-enters the (recursive) context lock this thread holds
-      }
-    }
-    void release(void* ctx) { static_cast<Context*>(ctx)->mu.unlock(); }
-    size_t deal_min() { return (size_t)::deal_min(); }
-    size_t split_eighths() {  // CAPGPU_COALESCE_SPLIT = eighths of the first part
-      static const size_t eighths = (size_t)env_int("CAPGPU_COALESCE_SPLIT", 3, 1, 4);
-      return eighths;
-    }
-    // batch parts running at once before a leader keeps collecting instead of taking another free context:
-    // CAPGPU_COALESCE_INFLIGHT (default 2) per bound DEVICE - two large batches fill a GPU, a third only fragments them
-    size_t max_in_flight() {
-      static const size_t per_device = (size_t)env_int("CAPGPU_COALESCE_INFLIGHT", 2, 1, 64);
-      int devices = 1;
-      (void)capgpu_physical_device_count(&devices);
-      return per_device * (size_t)std::max(devices, 1);
-    }
-    bool early_release() {  // CAPGPU_COALESCE_EARLY=0: a cut batch's callers return when both parts are done, as before
-      static const bool early = env_int("CAPGPU_COALESCE_EARLY", 1) != 0;
-      return early;
-    }
-  } hooks;
+  CoalesceHooks hooks;
   co.submit(lk, req, group, hooks);
   if (req.rc != CAPGPU_OK) set_error("%s", req.err.c_str());
   return req.rc;
@@ -2812,6 +2973,67 @@ int capgpu_plonk_prove(uint64_t pk_handle, const uint64_t* wires, const uint64_t
                        const uint8_t* ext_msg, size_t ext_msg_len, const uint64_t* blinders, capgpu_proof* proof_out) {
   return capgpu_plonk_prove_ex(pk_handle, wires, pub_inputs, num_inputs, ext_msg, ext_msg_len, blinders,
                                CAPGPU_INPUT_EVALS, proof_out);
+}
+
+// capgpu_plonk_prove_given_one / _io_one: ONE proof from the values its circuit is given - what a rayon worker with one
+// note's inputs calls.  Coalescing off: capgpu_plonk_prove_given[_io] with count = 1.  On: the request joins the group of its
+// (domain size, SRS) and kind, and a leader proves the gathered part through run_coalesced_given.
+static int given_one(ProveReq::Kind kind, uint64_t pk_handle, const uint64_t* given, size_t num_given,
+                     const uint64_t* pub_inputs, uint64_t* pub_inputs_out, size_t num_inputs, const uint8_t* ext_msg,
+                     size_t ext_msg_len, const uint64_t* blinders, capgpu_proof* proof_out,
+                     capgpu_prove_outcome* outcome_out, capgpu_solve_status* solved_out) {
+  const bool io = kind == ProveReq::kGivenIo;
+  if (!given || !blinders || !proof_out || !outcome_out || (num_inputs && !(io ? (const void*)pub_inputs_out : pub_inputs)))
+    return bad_args(kProveGivenOne);
+  CAP_CHECK_INIT();
+  if (comm_shard_slot() >= 0 || comm_shard_prover()) {
+    set_error("%s: not available while capgpu_plonk_shard_msm is on (the ranks prove in lock step)", kProveGivenOne);
+    return CAPGPU_ERR_INVALID_ARG;
+  }
+  Coalescer& co = coalescer();
+  if (co.window_us == 0) {
+    std::shared_ptr<ProvingKey> K;
+    gg::Ask ask;
+    (void)given_one_ask(pk_handle, num_given, num_inputs, &K, &ask);
+    if (int rc = given_one_refusal(gg::set_aside(ask), ask, pk_handle)) return rc;
+    const int rc = io ? capgpu_plonk_prove_given_io(&pk_handle, 1, given, num_inputs, &ext_msg, &ext_msg_len, blinders,
+                                                    pub_inputs_out, proof_out, outcome_out, solved_out)
+                      : capgpu_plonk_prove_given(&pk_handle, 1, given, pub_inputs, num_inputs, &ext_msg, &ext_msg_len,
+                                                 blinders, proof_out, outcome_out, solved_out);
+    if (rc == CAPGPU_OK) gg::normalise(outcome_out);
+    return rc;
+  }
+  ProveReq req{pk_handle, nullptr, pub_inputs, num_inputs, ext_msg, ext_msg_len, blinders, proof_out, CAPGPU_INPUT_VARS};
+  req.kind = kind;
+  req.given = given;
+  req.num_given = num_given;
+  req.outcome = outcome_out;
+  req.solved = solved_out;
+  req.pub_out = pub_inputs_out;
+  std::unique_lock<std::mutex> lk(co.mu);
+  uint64_t group = 0;
+  size_t key_n = 0;
+  if (int rc = coalesce_group(co, lk, pk_handle, 3u, io, &group, &key_n)) return rc;
+  // (no pre-staging: a row is a few KB and travels with the part's one copy)
+  CoalesceHooks hooks;
+  co.submit(lk, req, group, hooks);
+  if (req.rc != CAPGPU_OK) set_error("%s", req.err.c_str());
+  return req.rc;
+}
+
+int capgpu_plonk_prove_given_one(uint64_t pk_handle, const uint64_t* given, size_t num_given, const uint64_t* pub_inputs,
+                                 size_t num_inputs, const uint8_t* ext_msg, size_t ext_msg_len, const uint64_t* blinders,
+                                 capgpu_proof* proof_out, capgpu_prove_outcome* outcome_out,
+                                 capgpu_solve_status* solved_out) {
+  return given_one(ProveReq::kGiven, pk_handle, given, num_given, pub_inputs, nullptr, num_inputs, ext_msg, ext_msg_len,
+                   blinders, proof_out, outcome_out, solved_out);
+}
+int capgpu_plonk_prove_given_io_one(uint64_t pk_handle, const uint64_t* given, size_t num_given, size_t num_inputs,
+                                    const uint8_t* ext_msg, size_t ext_msg_len, const uint64_t* blinders,
+                                    uint64_t* pub_inputs_out, capgpu_proof* proof_out, capgpu_prove_outcome* outcome_out,
+                                    capgpu_solve_status* solved_out) {
+  return given_one(ProveReq::kGivenIo, pk_handle, given, num_given, nullptr, pub_inputs_out, num_inputs, ext_msg, ext_msg_len,
+                   blinders, proof_out, outcome_out, solved_out);
 }
 
 // ---- witness check (see check_batch) -------------------------------------------------------------------------------

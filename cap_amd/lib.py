@@ -1781,6 +1781,48 @@ def plonk_reserve_given(pk_handle: int, count: int, slot: int = -1):
     check(load().capgpu_plonk_reserve_given(ctypes.c_uint64(pk_handle), ctypes.c_int(count), ctypes.c_int(slot)))
 
 
+def _given_one_args(given, blinders, ext_msg):
+    given = np.ascontiguousarray(given, dtype=np.uint64).reshape(-1)
+    blinders = np.ascontiguousarray(blinders, dtype=np.uint64).reshape(-1)
+    if given.size % 4 or blinders.size != 13 * 4:
+        raise ValueError("plonk_prove_given_one: given is (num_given, 4), blinders (13, 4) words")
+    mbuf, mlen = _bytes_arg(ext_msg)
+    return given, blinders, mbuf, mlen
+
+
+def plonk_prove_given_one(pk_handle: int, given: np.ndarray, pub_inputs: np.ndarray, blinders: np.ndarray,
+                          ext_msg: bytes | None = None):
+    """capgpu_plonk_prove_given_one: ONE proof from the values its circuit is given -> (proof, outcome, solved) - the call
+    many host threads make at once: with plonk_set_coalescing on, their calls are gathered into one solve and one batch;
+    off, it is plonk_prove_given([pk], ...).  given (num_given, 4), pub_inputs (num_inputs, 4), blinders (13, 4).  The
+    library call runs without the GIL, as every call through ctypes does."""
+    given, blinders, mbuf, mlen = _given_one_args(given, blinders, ext_msg)
+    pub_inputs = np.ascontiguousarray(pub_inputs, dtype=np.uint64).reshape(-1)
+    proof, outcome, solved = Proof(), ProveOutcome(), SolveStatus()
+    check(load().capgpu_plonk_prove_given_one(
+        ctypes.c_uint64(pk_handle), _p(given) if given.size else None, ctypes.c_size_t(given.size // 4),
+        _p(pub_inputs) if pub_inputs.size else None, ctypes.c_size_t(pub_inputs.size // 4), mbuf, ctypes.c_size_t(mlen),
+        _p(blinders), ctypes.byref(proof), ctypes.byref(outcome), ctypes.byref(solved)))
+    return proof, outcome, solved
+
+
+def plonk_prove_given_io_one(pk_handle: int, given: np.ndarray, blinders: np.ndarray, ext_msg: bytes | None = None,
+                             num_inputs: int | None = None):
+    """capgpu_plonk_prove_given_io_one: plonk_prove_given_one without public inputs to pass -> (proof, outcome, solved,
+    pub_inputs), pub_inputs the (num_inputs, 4) Montgomery words the proof verifies against.  num_inputs: the key's
+    (None: asked of the key)."""
+    given, blinders, mbuf, mlen = _given_one_args(given, blinders, ext_msg)
+    if num_inputs is None:
+        num_inputs = plonk_key_info(pk_handle)[1]
+    pub_out = np.zeros((int(num_inputs), 4), np.uint64)
+    proof, outcome, solved = Proof(), ProveOutcome(), SolveStatus()
+    check(load().capgpu_plonk_prove_given_io_one(
+        ctypes.c_uint64(pk_handle), _p(given) if given.size else None, ctypes.c_size_t(given.size // 4),
+        ctypes.c_size_t(int(num_inputs)), mbuf, ctypes.c_size_t(mlen), _p(blinders),
+        _p(pub_out.reshape(-1)) if pub_out.size else None, ctypes.byref(proof), ctypes.byref(outcome), ctypes.byref(solved)))
+    return proof, outcome, solved, pub_out
+
+
 def plonk_reserve(pk_handle: int, count: int, input_form=INPUT_EVALS, slot: int = -1):
     """capgpu_plonk_reserve: size context `slot` (-1: all) ahead for a `count`-proof host-resident batch under this key,
     in the modes in force now, without proving anything."""

@@ -1159,7 +1159,7 @@ int capgpu_plonk_notes_stats(capgpu_notes_stats* out);
  *   capgpu_plonk_prove_given (its stream_waits does not count the extra wait).
  *   capgpu_plonk_reserve_given sizes the staging of these rows too, for a key whose solver was set with
  *   CAPGPU_SOLVER_DERIVE_PUBLIC; other keys keep their figures (their first _io call grows the scratch once).
- * LEFT OUT: coalesced single-proof calls, _io included; a given form of the all-or-nothing capgpu_plonk_prove_batch /
+ * LEFT OUT: a given form of the all-or-nothing capgpu_plonk_prove_batch /
  * _multi calls; a given form of capgpu_plonk_check_witness* (capgpu_plonk_solve_vars, then check); any hint kind beyond
  * the three; a rule that solves a row for two unknowns or inverts a product term; any change to the latency of ONE
  * witness's chain of dependent inversions (a lane-cooperative field product, another inversion algorithm). */
@@ -1189,6 +1189,44 @@ int capgpu_plonk_prove_given_io_async(const uint64_t* pk_handles, int count, con
                                       capgpu_prove_outcome* outcomes_out, capgpu_solve_status* solved_out,
                                       uint64_t* ticket_out);
 int capgpu_plonk_reserve_given(uint64_t pk_handle, int count, int slot);
+/* ONE PROOF PER CALL, GATHERED (capgpu_plonk_prove_given_one / _io_one): what a rayon worker holding one note's inputs
+ * calls.  Outcome calls of one proof: CAPGPU_OK whenever the proof's batch ran, the verdict in outcome_out, an all-ones
+ * record for a failed proof.  given holds the key's num_given values, pub_inputs (pub_inputs_out) its num_inputs; ext_msg
+ * may be NULL with ext_msg_len 0; solved_out may be NULL.
+ *   COALESCING OFF (the default): the call is capgpu_plonk_prove_given (_io) with count = 1.
+ *   COALESCING ON (capgpu_plonk_set_coalescing): calls that arrive together are gathered as concurrent capgpu_plonk_prove
+ *   calls are - same window, max_batch, in-flight limit and uneven cut over two contexts.  One group holds the given-value
+ *   calls of one (domain size, SRS), all keys mixed; _io calls and plain calls form separate groups (a batch proves either
+ *   against supplied or against computed public inputs), and neither ever shares a batch with wire-form capgpu_plonk_prove
+ *   calls.  A gathered part packs its callers' rows in arrival order - given values and public inputs to the largest
+ *   num_given / num_inputs among the part's keys, zeros behind a shorter row - and runs as ONE capgpu_plonk_prove_given
+ *   (_io) call with a key per proof on the context the coalescer took: one staging copy, one solver launch per distinct
+ *   key, witness check and compaction as that call applies them.  capgpu_plonk_coalescing_stats counts these batches and
+ *   proofs with the others, capgpu_plonk_solve_stats the launches, capgpu_plonk_input_stats exactly 32 * num_given bytes
+ *   per caller (the zero fill is the library's).
+ *   THE CONTRACT.  proof_out, outcome_out, solved_out and - _io - pub_inputs_out are bit for bit what
+ *   capgpu_plonk_prove_given (_io) with count = 1 writes for this caller's inputs alone in the same process modes
+ *   (transcript home, wire commit, precheck, inverse form, solve form, solve pack), whichever other callers shared the
+ *   batch and whatever their witnesses were.  One rule makes that so: with the witness check on, a lone refused witness
+ *   returns after the check with degree_flags 0, while in an uncompacted batch it rides to the end and the degree check
+ *   sets its flags as well - these calls report degree_flags = 0 for every outcome whose fault.kind != 0.
+ *   REFUSALS, before a device is looked for: NULL given, blinders, proof_out or outcome_out, NULL pub_inputs
+ *   (pub_inputs_out) with num_inputs > 0: CAPGPU_ERR_INVALID_ARG; then CAPGPU_ERR_NOT_INITIALISED; capgpu_plonk_shard_msm
+ *   on: CAPGPU_ERR_INVALID_ARG.  num_given and num_inputs must be the key's: CAPGPU_ERR_INVALID_ARG
+ *   ("capgpu_plonk_prove_given_one: 3 given values and 1 public inputs passed, the key has 4 and 1").
+ *   FAILURES.  A request whose own key is gone (CAPGPU_ERR_BAD_HANDLE), has no solver or disagrees in num_given /
+ *   num_inputs fails alone with its own code and message; the rest of its batch runs.  A failure of the part itself
+ *   (CAPGPU_ERR_OOM, a HIP error) is returned to every caller of that part with that code and message.
+ * LEFT OUT: a coalesced form over several domain sizes (one group is one domain size); pre-staging of the rows (a row is
+ * a few KB); ticket and device-resident forms of the _one calls. */
+int capgpu_plonk_prove_given_one(uint64_t pk_handle, const uint64_t* given, size_t num_given, const uint64_t* pub_inputs,
+                                 size_t num_inputs, const uint8_t* ext_msg, size_t ext_msg_len, const uint64_t* blinders,
+                                 capgpu_proof* proof_out, capgpu_prove_outcome* outcome_out,
+                                 capgpu_solve_status* solved_out /* may be NULL */);
+int capgpu_plonk_prove_given_io_one(uint64_t pk_handle, const uint64_t* given, size_t num_given, size_t num_inputs,
+                                    const uint8_t* ext_msg, size_t ext_msg_len, const uint64_t* blinders,
+                                    uint64_t* pub_inputs_out, capgpu_proof* proof_out, capgpu_prove_outcome* outcome_out,
+                                    capgpu_solve_status* solved_out);
 
 /* Batch compaction of the outcome calls (off by default; CAPGPU_COMPACT=1 sets the process default).  on != 0: an outcome
  * call made with capgpu_plonk_set_precheck on, of whose P witnesses the check refused some but not all, proves the P'
@@ -1201,7 +1239,7 @@ int capgpu_plonk_reserve_given(uint64_t pk_handle, int count, int slot);
  * buffer, which is never written - the survivors' rows are copied into library staging when the proofs saved are worth
  * the copy (bad * 64 >= P'), and below that the call runs uncompacted.  What stays uncompacted besides: calls with the
  * witness check off (the degree check's verdict arrives in round 3, too late to be worth it), calls without outcomes,
- * coalesced calls.  Dealt host batches and tickets compact per part.  Nothing changes while the mode is off.
+ * coalesced capgpu_plonk_prove calls (gathered capgpu_plonk_prove_given_one parts are outcome calls and compact).  Dealt host batches and tickets compact per part.  Nothing changes while the mode is off.
  * Process-wide; read when a call - or a ticket - starts.  _get_: the mode in force.  _stats: counters since capgpu_init -
  * calls (parts of dealt calls) that ran compacted, proofs they dropped, witness rows handed to the copy kernel; any
  * pointer may be NULL. */

@@ -701,6 +701,67 @@ Result<ProveGivenIo> prove_given_io(Rng& rng, const std::vector<const ProvingKey
   return out;
 }
 
+// prove() for ONE note from the values its circuit is given (capgpu_plonk_prove_given_one): what each thread of a parallel
+// loop over notes calls.  With capgpu_plonk_set_coalescing on, concurrent calls are gathered into one solve and one device
+// batch; the proof is bit for bit the lone call's either way.  The outer error: the call could not run.
+template <class Rng>
+Result<ProveEachEntry> prove_given_one(Rng& rng, const ProvingKey& pk, const GivenValues& g,
+                                       const std::vector<uint8_t>* ext_msg = nullptr) {
+  if ((!g.given && g.num_given) || (!g.pub_inputs && pk.num_inputs()))
+    return TxnApiError::failed_snark("prove_given_one: empty given values or public inputs");
+  uint64_t blinders[13 * 4];
+  for (int k = 0; k < 13; k++) {
+    Fr b = rng();
+    std::memcpy(&blinders[k * 4], b.data(), 32);
+  }
+  const bool msg = ext_msg && !ext_msg->empty();
+  Proof proof;
+  capgpu_prove_outcome oc{};
+  int rc = capgpu_plonk_prove_given_one(pk.handle(), g.given, g.num_given, g.pub_inputs, pk.num_inputs(),
+                                        msg ? ext_msg->data() : nullptr, msg ? ext_msg->size() : 0, blinders, &proof, &oc,
+                                        nullptr);
+  if (rc != CAPGPU_OK) return detail::map_error(rc, "prove_given_one");
+  ProveEachEntry out;
+  if (oc.status == CAPGPU_OK) {
+    out.proof = proof;
+  } else {
+    char text[512];
+    capgpu_prove_outcome_text(&oc, text, sizeof text);
+    out.error = text;
+  }
+  return out;
+}
+// ... without public inputs to pass (capgpu_plonk_prove_given_io_one): pub_inputs receives the key's num_inputs() x 4 words
+// the library proved against, whatever became of the proof.
+template <class Rng>
+Result<ProveEachEntry> prove_given_io_one(Rng& rng, const ProvingKey& pk, const GivenValues& g,
+                                          std::vector<uint64_t>* pub_inputs, const std::vector<uint8_t>* ext_msg = nullptr) {
+  if ((!g.given && g.num_given) || !pub_inputs) return TxnApiError::failed_snark("prove_given_io_one: empty given values");
+  uint64_t blinders[13 * 4];
+  for (int k = 0; k < 13; k++) {
+    Fr b = rng();
+    std::memcpy(&blinders[k * 4], b.data(), 32);
+  }
+  const bool msg = ext_msg && !ext_msg->empty();
+  const size_t ni = pk.num_inputs();
+  pub_inputs->assign(ni * 4, 0);
+  Proof proof;
+  capgpu_prove_outcome oc{};
+  int rc = capgpu_plonk_prove_given_io_one(pk.handle(), g.given, g.num_given, ni, msg ? ext_msg->data() : nullptr,
+                                           msg ? ext_msg->size() : 0, blinders, ni ? pub_inputs->data() : nullptr, &proof, &oc,
+                                           nullptr);
+  if (rc != CAPGPU_OK) return detail::map_error(rc, "prove_given_io_one");
+  ProveEachEntry out;
+  if (oc.status == CAPGPU_OK) {
+    out.proof = proof;
+  } else {
+    char text[512];
+    capgpu_prove_outcome_text(&oc, text, sizeof text);
+    out.error = text;
+  }
+  return out;
+}
+
 }  // namespace proof
 
 // ---- Transfer (src/proof/transfer.rs) ----------------------------------------------------------------------------
