@@ -4,6 +4,11 @@
 //     x, y   normalized, < 2p      (weak_reduce'd: they are differences)
 //     zz,zzz normalized, < 1.1p    (products)
 //     infinity  <=>  zz is the literal 0
+// That is what the general functions (dbl*, add, add_mixed, term_mul) RETURN.  They ACCEPT more: the accumulator class of
+// the lean forms below (x < 2p, y < 3p, zz, zzz < 1.2p - what madd_acc, add_affine_pair and add_acc take and return) and
+// a point loaded from any four 32-byte images.  tests/cpp/curve_envelope_check.cpp runs this law on a field whose values
+// are bounds and shows both classes to close under every chain the kernels build (tests/golden/lazy_envelope.json,
+// section "curve", which also records how much further "y < k p" would still close for each lean form).
 // Affine table entries (`g1_affine` in memory) hold canonical values (< p) in internal Montgomery form
 // (x * 2^261 mod p); (0, 0) encodes infinity.  Bucket points in memory (`g1_xyzz`) hold any value < 2^256.
 #pragma once
@@ -19,16 +24,40 @@ struct g1x {  // XYZZ, registers
   fl x, y, zz, zzz;
 };
 
-template <int SCHED>
-struct G1LT {
-  using F = Fl<FqP29, SCHED>;
-
-  static CAP_HD bool all_zero(const fl& a) {
-    uint32_t o = 0;
+// What goes with a field value type V: the register points, the memory images and the C ABI's constants.  The law below
+// is written once over the field class F and V; tests/cpp/bound_curve29.hpp supplies the set for a field whose values are
+// bounds (tests/cpp/curve_envelope_check.cpp runs the law on it for every input of a class).
+template <class V>
+struct G1Types;
+template <>
+struct G1Types<fl> {
+  using A = g1a;
+  using X = g1x;
+  using MA = g1_affine;
+  using MX = g1_xyzz;
+  using MJ = g1_jac;
+  static CAP_HD fe ext_one() { return Fq::one(); }
+  static CAP_HD fe ext_zero() { return Fq::zero(); }
+};
+// the literal 0: every limb zero
+static CAP_HD bool limbs_all_zero(const fl& a) {
+  uint32_t o = 0;
 #pragma unroll
-    for (int i = 0; i < 9; i++) o |= a.v[i];
-    return o == 0;
-  }
+  for (int i = 0; i < 9; i++) o |= a.v[i];
+  return o == 0;
+}
+
+template <class F_, class V>
+struct G1Law {
+  using F = F_;
+  using fl = V;
+  using g1a = typename G1Types<V>::A;
+  using g1x = typename G1Types<V>::X;
+  using g1_affine = typename G1Types<V>::MA;
+  using g1_xyzz = typename G1Types<V>::MX;
+  using g1_jac = typename G1Types<V>::MJ;
+
+  static CAP_HD bool all_zero(const fl& a) { return limbs_all_zero(a); }
   static CAP_HD bool is_inf(const g1x& p) { return all_zero(p.zz); }
   static CAP_HD bool is_inf(const g1a& p) { return all_zero(p.x) && all_zero(p.y); }
   static CAP_HD g1x inf() {
@@ -320,9 +349,9 @@ struct G1LT {
   static CAP_HD g1_jac to_jac_ext(const g1x& p) {
     g1_jac r;
     if (is_inf(p)) {
-      r.x = Fq::one();
-      r.y = Fq::one();
-      r.z = Fq::zero();
+      r.x = G1Types<V>::ext_one();
+      r.y = G1Types<V>::ext_one();
+      r.z = G1Types<V>::ext_zero();
       return r;
     }
     r.x = F::to_ext(F::mul(p.x, p.zz));
@@ -331,6 +360,9 @@ struct G1LT {
     return r;
   }
 };
+// the law on the lazy field with multiplication schedule SCHED: what every kernel uses
+template <int SCHED>
+struct G1LT : G1Law<Fl<FqP29, SCHED>, fl> {};
 using G1L = G1LT<CAP_FL_SCHED>;  // the translation unit's default multiplication schedule (field29.hpp)
 
 }  // namespace cap

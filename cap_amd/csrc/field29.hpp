@@ -13,6 +13,11 @@
 // tests/cpp/ntt_elem_check.cpp and round_elem_check.cpp (the NTT kernels' stages and element steps, ntt_elem29.hpp, and
 // the bodies of the lazy-field round kernels with ColAcc, round_elem29.hpp - both also on the bound-tracking field of
 // tests/cpp/bound29.hpp, which checks the preconditions for every input of a class: tests/golden/lazy_envelope.json).
+// On that bound field as well: the G1 law of curve29.hpp on every path and the chains the MSM, point-sum and verifier
+// kernels build from it, the quad-lane form (quad29.hpp), the Lagrange key builder (lagrange_elem29.hpp) - all three in
+// tests/cpp/curve_envelope_check.cpp - and the pairing tower with its Miller loop and final exponentiation
+// (pairing29.hpp, tests/cpp/tower_envelope_check.cpp); tests/test_lazy_call_sites.py classifies the operands of every
+// call of the law in the device units.  Not on the bound field: the lane programs of pairing_wave.hpp.
 // Not reached by any of them: transcript_dev.hpp.  (The kernels on the saturated field Fr have no lazy bounds.)
 //   * "normalized": limbs 0..7 < 2^29, limb 8 < 2^29  (value < 2^261).
 //   * mul / sqr:  operands with limbs < 2^30 (a normalized value or one lazy sum of two); returns a
@@ -487,7 +492,10 @@ struct Fl {
     }
     return reduce_cols(c);
   }
-  // a*b + c*d with one reduction (all four operands normalized: 18 products of < 2^58 per column)
+  // a*b + c*d with one reduction.  All four operands normalized: 18 products of < 2^58 per column.  Lazy operands
+  // (limbs < 2^31) are admitted as long as the two products of a column stay within the column limit together:
+  // 9 (limbs(a) limbs(b) + limbs(c) limbs(d)) + 9 * 2^58 + 2^36 < 2^64 - curve29.hpp's lean additions pass b with limbs
+  // < 1.5 * 2^30 and c with limbs < 2^30 next to a normalized a and d (tests/cpp/bound29.hpp checks exactly this sum)
   static CAP_HD fl mul_add_mul(const fl& a, const fl& b, const fl& c2, const fl& d) {
     if constexpr (SCHED == 1) return mul_add_mul_col(a, b, c2, d);
     uint64_t c[18];

@@ -18,10 +18,22 @@ constexpr uint32_t kLagBlind = 3;  // blinding points behind the n Lagrange poin
 #define CAP_LAG_CALL inline
 #endif
 
+// The group law a schedule number selects: 0 and 1 are G1LT on the two multiplication schedules of Fl, what the kernels
+// use; tests/cpp/bound_curve29.hpp adds a number of its own for the law on the field whose values are bounds, so that
+// the same LagT runs on it while LagT<0> and LagT<1> keep their names and their out-of-line scalar_mul.
+template <int SCHED>
+struct LagCurve {
+  using C = G1LT<SCHED>;
+};
+
 template <int SCHED>
 struct LagT {
-  using C = G1LT<SCHED>;
-  using F = Fl<FqP29, SCHED>;
+  using C = typename LagCurve<SCHED>::C;
+  using F = typename C::F;
+  using g1a = typename C::g1a;
+  using g1x = typename C::g1x;
+  using g1_affine = typename C::g1_affine;
+  using g1_xyzz = typename C::g1_xyzz;
 
   static CAP_HD g1x neg_pt(const g1x& p) {
     g1x r = p;
@@ -79,8 +91,8 @@ struct LagT {
     }
     g1_affine o;
     if (C::is_inf(p)) {
-      o.x = Fq::zero();
-      o.y = Fq::zero();
+      o.x = G1Types<typename C::fl>::ext_zero();
+      o.y = G1Types<typename C::fl>::ext_zero();
     } else {
       const g1a q = C::to_affine(p);
       o.x = F::to_ext(q.x);

@@ -63,11 +63,15 @@ struct QuadDev {
 };
 #endif
 
-struct fl4 {  // host simulation: the four lanes of one quad
-  fl l[4];
+template <class E>
+struct lanes4 {  // host simulation: the four lanes of one quad
+  E l[4];
 };
-struct QuadSim {
-  using V = fl4;
+using fl4 = lanes4<fl>;
+// E: the field value type - fl, or a bound (tests/cpp/bound29.hpp) for the envelope check
+template <class E>
+struct QuadSimT {
+  using V = lanes4<E>;
   template <class Fn>
   static V map1(Fn f, const V& a) {
     V r;
@@ -100,19 +104,22 @@ struct QuadSim {
   template <int K, class Pred>
   static bool flag(Pred pr, const V& a) { return pr(a.l[K]); }
   template <int K>
-  static fl lane(const V& a) { return a.l[K]; }
-  static V spread(const fl& x) {
+  static E lane(const V& a) { return a.l[K]; }
+  static V spread(const E& x) {
     V r;
     for (int q = 0; q < 4; q++) r.l[q] = x;
     return r;
   }
 };
+using QuadSim = QuadSimT<fl>;
 
 // ---- the group law on quads --------------------------------------------------------------------------------------------
 template <class G, class P>
 struct QuadG1 {
   using F = typename G::F;
   using V = typename P::V;
+  using fl = typename G::fl;    // the field value type of the law (G1Law)
+  using g1x = typename G::g1x;
 
   static CAP_HD V mul(const V& a, const V& b) {
     return P::map2([](const fl& x, const fl& y) { return F::mul(x, y); }, a, b);

@@ -32,7 +32,9 @@ RANDOM_FLOOR = {"field": 200, "field32": 200, "curve": 64, "quad": 64, "tower": 
 # floor 8: final_exp, miller2, check2, and pairing2, which is nothing but final_exp(miller2(..))
 HEAVY_OPS = {"final_exp", "miller2", "check2", "pairing2"}
 # the fewest edge records an op of the group may have (the generator's own count per op is asserted as well)
-MIN_EDGES = {"field": 6, "field32": 8, "curve": 9, "quad": 1, "tower": 2, "pair": 2}
+MIN_EDGES = {"field": 6, "field32": 8, "curve": 11, "quad": 2, "tower": 3, "pair": 2}
+# the two chains of the curve group run on a handful of top-of-class records only: no random floor, this many edge records
+CHAIN_OPS = {"item_chain": 4, "fold_chain": 4}
 
 
 def _op_tables():
@@ -396,6 +398,25 @@ def xyzz(pt, lam=1, lazy=False):
     return limbs(cx) + limbs(cy) + limbs(mont(zz)) + limbs(mont(zzz))
 
 
+def xyzz_top(rng, pt, ky=2, zmax=(6, 5)):
+    """the top of the accumulator class (curve29.hpp: x < 2p, y < 3p, zz, zzz < 1.2p): pt scaled by lambda, x as its + p
+    and y as its + ky p representative, lambda drawn until zz + p and zzz + p stay below zmax p"""
+    x, y = pt
+    while True:
+        lam = rng.randrange(2, P)
+        zz, zzz = mont(lam * lam % P) + P, mont(pow(lam, 3, P)) + P
+        if zmax[1] * zz < zmax[0] * P and zmax[1] * zzz < zmax[0] * P:
+            break
+    return limbs(mont(x * lam * lam % P) + P) + limbs(mont(y * pow(lam, 3, P) % P) + ky * P) + limbs(zz) + limbs(zzz)
+
+
+def xyzz_image(rng, pt):
+    """a bucket image just below 2^256 (g1_xyzz: "any value < 2^256"): every coordinate its largest representative"""
+    lam = rng.randrange(2, P)
+    c = [mont(pt[0] * lam * lam % P), mont(pt[1] * pow(lam, 3, P) % P), mont(lam * lam % P), mont(pow(lam, 3, P))]
+    return sum((limbs(v + ((1 << 256) - 1 - v) // P * P) for v in c), [])
+
+
 def affine_of(w, ybound=2):
     """36 words of an XYZZ result -> (affine point or None, error or None); checks the invariants of a point in registers"""
     c = [w[0:9], w[9:18], w[18:27], w[27:36]]
@@ -487,13 +508,82 @@ def gen_curve(rng):
             B = xyzz(pt, 1, lazy=(pi == 0 and k % 2 == 1))
             for s in (0, 1):
                 add("term_mul", s, 0, [0] * 36, B, k, (pt, k), kind if pi < 2 else "edge")
+    # edge:top - operands at the top of the classes the envelope closes from (tests/golden/lazy_envelope.json, "curve"):
+    # the accumulator class A (y in [2p, 3p), zz and zzz just below 1.2p) and bucket images just below 2^256
+    top = (1 << 256) - 1
+    for i in range(2):
+        a, b = rand_pt(rng), rand_pt(rng)
+        make = xyzz_top if i == 0 else xyzz_image
+        A, Bx = make(rng, a), make(rng, b)
+        Ba = xyzz(b, 1, True)                                # the table point as its + p representatives (< 2p)
+        Am = xyzz_top(rng, a)                                # madd_acc takes class A only (its 4p - y)
+        mx, my = mont(b[0]) + (top - mont(b[0])) // P * P, mont(b[1]) + (top - mont(b[1])) // P * P
+        for s in (0, 1):
+            add("add", s, 0, A, Bx, 0, (a, b), "edge:top")
+            add("add_acc", s, 0, A, Bx, 0, (a, b), "edge:top")
+            add("dbl", s, 0, A, [0] * 36, 0, (a,), "edge:top")
+            add("to_affine", s, 0, A, [0] * 36, 0, (a,), "edge:top")
+            add("store_load", s, 0, A, [0] * 36, 0, (A,), "edge:top")
+            add("from_affine", s, 0, [0] * 36, Ba, 0, (b, Ba), "edge:top")
+            add("dbl_affine", s, 0, [0] * 36, Ba, 0, (b,), "edge:top")
+            add("term_mul", s, 0, [0] * 36, Ba, top - i, (b, top - i), "edge:top")
+            recs.append(Rec("curve", "load_affine", 0, s, 0, fe_slot(mx) + fe_slot(my) + [0] * (18 + 36 + 9), (mx, my),
+                            "edge:top"))
+            for neg in (0, 1):
+                add("add_mixed", s, neg, A, Ba, 0, (a, b), "edge:top")
+                add("madd_acc", s, neg, Am, Ba, 0, (a, b, Am), "edge:top")
+    # the two chains: an item of msm_accumulate over four table points, and a fold of the reductions on class A
+    for i in range(CHAIN_OPS["item_chain"]):
+        t = [rand_pt(rng) for _ in range(4)]
+        signs = (0x55, 0x66, 0x99, 0xaa, 0x33)[i % 5]        # mixed, a point keeps its sign: no partial sum is +-q
+        words = sum((limbs(mont(q[0])) + limbs(mont(q[1])) for q in t), [])
+        for s in (0, 1):
+            add("item_chain", s, signs, words[:36], words[36:], 0, (t, signs), "edge:top")
+    for i in range(CHAIN_OPS["fold_chain"]):
+        a, b = rand_pt(rng), rand_pt(rng)
+        A, Bx = (xyzz_top(rng, a), xyzz_top(rng, b)) if i < 3 else (xyzz_image(rng, a), xyzz_image(rng, b))
+        for s in (0, 1):
+            add("fold_chain", s, 0, A, Bx, 0, (a, b), "edge:top")
     assert set(r.op for r in recs) == set(C)
     return recs
+
+
+def check_chain(r, out):
+    """item_chain: the item's sum, in the accumulator's class, as it comes back from its memory image; fold_chain:
+    2 (2a + b) as the canonical Jacobian triple of the C ABI"""
+    w, flag = out[:36], out[36]
+    if flag != 1:
+        return "a lean addition refused ordinary operands"
+    if r.op == "item_chain":
+        t, signs = r.meta
+        want = None
+        for i in range(8):
+            q = t[i & 3]
+            want = bn.g1_add(want, neg_pt(q) if (signs >> i) & 1 else q)
+        got, err = affine_of(w, 3)
+        return err or (None if got == want else f"point {got} != {want}")
+    a, b = r.meta
+    s = bn.g1_add(bn.g1_add(a, b), a)
+    want = bn.g1_add(s, s)
+    if any(w[9 * c + 8] for c in range(3)) or any(w[27:36]):
+        return "words beyond the triple are not 0"
+    x, y, z = (fe_val(w[9 * c:9 * c + 8]) for c in range(3))
+    if not max(x, y, z) < P:
+        return "the triple is not canonical"
+    i256 = pow(1 << 256, -1, P)
+    x, y, z = (v * i256 % P for v in (x, y, z))
+    if z == 0:
+        return "infinity"
+    zi = pow(z, -1, P)
+    got = (x * zi * zi % P, y * pow(zi, 3, P) % P)
+    return None if got == want else f"point {got} != {want}"
 
 
 def check_curve(r, out):
     w, flag = out[:36], out[36]
     name, m = r.op, r.meta
+    if name in CHAIN_OPS:
+        return check_chain(r, out)
     if name == "store_load":
         return None if w == m[0] else "load(store(A)) != A"
     if name == "load_affine":
@@ -562,6 +652,12 @@ def gen_quad(rng):
         for i in range(16):
             case = QUAD_CASES[rng.randrange(5)] if rng.randrange(3) == 0 else "ord"
             recs.append(make(case, qops[(w + i) % 4] if rng.randrange(4) else qops[rng.randrange(4)], rng.randrange(2)))
+    # edge:top, one full wave: both operands at the top of the quad class (x, y their + p representatives, zz and zzz
+    # just below 1.2p), every op under both schedules
+    for i in range(16):
+        a, b = rand_pt(rng), rand_pt(rng)
+        recs.append(Rec("quad", qops[i % 4], 0, (i >> 2) & 1, 0, xyzz_top(rng, a, 1) + xyzz_top(rng, b, 1), (a, b),
+                        "edge:top"))
     recs += [make(QUAD_CASES[i % 5], qops[i % 4], i % 2) for i in range(7)]      # the partial last wave
     assert len(recs) % 16 == 7
     return recs
@@ -703,6 +799,8 @@ def gen_tower(rng):
             c[i] = (1, P - 1, rng.randrange(1, P))[i % 3]
             out.append((embed(c, n_f2), (i,) if i % 2 else (), "edge:single"))
         out.append((embed([rng.randrange(P) for _ in range(nc)], n_f2), tuple(range(nc)), "edge:lazy"))
+        # every stored coefficient within 2^64 of the top of class E (2p - 1), all different
+        out.append((embed([unmont(P - 1 - rng.randrange(1 << 64)) for _ in range(nc)], n_f2), tuple(range(nc)), "edge:top"))
         return out
 
     def add(name, aux, a, la, b, lb, kind, wb=None):
@@ -718,6 +816,7 @@ def gen_tower(rng):
                 add(name, 0, cyclo(), tuple(range(12)) if i % 4 == 3 else (), zero, (), "random")
             add(name, 0, list(op.F12_ONE), (), zero, (), "edge:1")
             add(name, 0, conj6(cyc_base[0]), (), zero, (), "edge:conj")
+            add(name, 0, cyclo(), tuple(range(12)), zero, (), "edge:top")      # every coefficient its + p representative
         elif name == "final_exp":
             for a, la, kind in elements(6, 8):
                 add(name, 0, a, la, zero, (), kind)
@@ -959,10 +1058,10 @@ def check_floors(group, recs, counts):
             for name in OPS[group]:
                 key = (group, f, s, name)
                 c = counts.get(key, {"random": 0, "edge": 0})
-                floor = 8 if name in HEAVY_OPS else RANDOM_FLOOR[group]
+                floor = 0 if name in CHAIN_OPS else 8 if name in HEAVY_OPS else RANDOM_FLOOR[group]
                 if c["random"] < floor:
                     msgs.append(f"{group}.{name} field={f} sched={s}: {c['random']} random records checked, floor {floor}")
-                want = max(EDGE_COUNTS.get(key, 0), MIN_EDGES[group])
+                want = max(EDGE_COUNTS.get(key, 0), CHAIN_OPS.get(name, MIN_EDGES[group]))
                 if c["edge"] < want:
                     msgs.append(f"{group}.{name} field={f} sched={s}: {c['edge']} edge records checked, {want} admitted")
     return msgs

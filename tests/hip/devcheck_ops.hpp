@@ -41,7 +41,7 @@ constexpr uint32_t kMagic = 0x4b435644u;  // "DVCK"
 #define DC_FIELD32_OPS(X) X(mul, 0) X(sqr, 1) X(add, 2) X(sub, 3) X(dbl, 4) X(inv, 5) X(pow, 6) X(neg, 7)
 #define DC_CURVE_OPS(X)                                                                                              \
   X(from_affine, 0) X(dbl_affine, 1) X(dbl, 2) X(add_mixed, 3) X(madd_acc, 4) X(add_acc, 5) X(add, 6)                \
-  X(to_affine, 7) X(store_load, 8) X(term_mul, 9) X(load_affine, 10)
+  X(to_affine, 7) X(store_load, 8) X(term_mul, 9) X(load_affine, 10) X(item_chain, 11) X(fold_chain, 12)
 #define DC_QUAD_OPS(X) X(add, 0) X(dbl, 1) X(chain, 2) X(tree, 3)
 #define DC_TOWER_OPS(X)                                                                                              \
   X(f2_mul, 0) X(f2_sqr, 1) X(f2_inv, 2) X(f2_mul_xi, 3) X(f6_mul, 4) X(f6_mul_01, 5) X(f6_inv, 6) X(f6_mul_v, 7)    \
@@ -271,6 +271,34 @@ struct CurveOps {
         r.y = t.y;
         flag = G::is_inf(t) ? 1 : 0;
         break;
+      }
+      case cop::item_chain: {
+        // an item of msm_accumulate: add_affine_pair, six madd_acc with the signs of aux (bit i: entry i), store, load.
+        // The four table points are (A.x, A.y), (A.zz, A.zzz), (B.x, B.y), (B.zz, B.zzz), taken in turn.
+        const g1a t[4] = {{A.x, A.y}, {A.zz, A.zzz}, {B.x, B.y}, {B.zz, B.zzz}};
+        const uint32_t sg = in[3];
+        g1x acc = G::inf();
+        bool ok = G::add_affine_pair(acc, t[0], (sg & 1) != 0, t[1], (sg & 2) != 0);
+        for (int i = 2; i < 8; i++) ok = G::madd_acc(acc, t[i & 3], ((sg >> i) & 1) != 0) && ok;
+        flag = ok ? 1 : 0;
+        r = G::load(G::store(acc));
+        break;
+      }
+      case cop::fold_chain: {
+        // a fold of the reductions: (A + B) + A by add_acc twice, doubled, handed out as the C ABI's Jacobian triple
+        // (x, y, z in the first three slots, 8 words each)
+        g1x acc = A;
+        bool ok = G::add_acc(acc, B);
+        ok = G::add_acc(acc, A) && ok;
+        const g1_jac j = G::to_jac_ext(G::dbl(acc));
+        flag = ok ? 1 : 0;
+        zero_words(out, 36);
+        wr_fe(out, j.x);
+        wr_fe(out + 9, j.y);
+        wr_fe(out + 18, j.z);
+        out[36] = flag;
+        out[37] = kDone + op;
+        return;
       }
       default: return;
     }

@@ -84,19 +84,93 @@ def test_both_schedules_give_the_same_limbs(work):
 
 
 def test_representatives_do_not_depend_on_compiler_flags_or_limb_width(work):
-    """clang++ -O2 with the unsigned-integer-overflow sanitizer (every 64-bit column sum and 32-bit limb sum traps on
-    wrap-around, as in tests/test_field29_host.py) and field.hpp's 32-bit-limb forms (-DCAP_HOST_MUL32, what the device
+    """clang++ -O2 with the unsigned-integer-overflow and undefined-behaviour sanitizers (every 64-bit column sum and
+    32-bit limb sum traps on wrap-around, as in tests/test_field29_host.py; the records include the edge:top operands, the
+    two chains, miller2 and check2) and field.hpp's 32-bit-limb forms (-DCAP_HOST_MUL32, what the device
     runs) against g++ -O1 with the 64-bit-limb forms: the result files are equal limb for limb"""
     if not os.path.exists(CLANG):
         pytest.skip("no clang++ for the sanitizer build")
     d = work["dir"]
     ign = d / "ignore.txt"
     ign.write_text("src:*/field.hpp\nsrc:*/curve.hpp\nsrc:*/pairing.hpp\n")
-    exe = build_host(str(d / "devcheck_host_san"), ["-O2", "-DCAP_HOST_MUL32", "-fsanitize=unsigned-integer-overflow",
+    exe = build_host(str(d / "devcheck_host_san"), ["-O2", "-DCAP_HOST_MUL32", "-fsanitize=unsigned-integer-overflow,undefined",
                                                      f"-fsanitize-ignorelist={ign}", "-fno-sanitize-recover=all"], CLANG)
     other = run_driver(exe, work["vec"], str(d / "san.bin"))
     diff = dv.compare_files(work["res"], other)
     assert not diff, f"{len(diff)} records differ, first {diff[:5]}"
+
+
+def test_chain_records_equal_the_envelope_programs_words(work):
+    """the two chains of the curve group (an item of msm_accumulate, a fold of the reductions) word for word against
+    tests/cpp/curve_envelope_check.cpp, which runs the same operands through the real law for
+    tests/test_curve_envelope_host.py - the device is then held to these words by tests/test_gpu_devcheck.py"""
+    from tests.test_curve_envelope_host import _build
+    exe = _build(work["dir"], False)
+    hexw = lambda w: " ".join(f"{x:x}" for x in w)                   # noqa: E731
+    n = 0
+    for sched in (0, 1):
+        lines, want = [], []
+        for r, out in zip(work["recs"]["curve"], work["res"]["curve"]):
+            if r.sched != sched or r.op not in dv.CHAIN_OPS:
+                continue
+            if r.op == "item_chain":
+                t = [r.words[18 * i:18 * i + 18] for i in range(4)]
+                lines.append("item " + " ".join(f"{hexw(t[i & 3])} {(r.aux >> i) & 1}" for i in range(8)))
+                want.append([f"{out[36]} " + hexw(out[:36])])
+            else:
+                A, B = r.words[:36], r.words[36:72]
+                lines.append(f"fold {hexw(A)} {hexw(B)} {hexw(A)}")
+                want.append([None, " ".join("".join(f"{x:08x}" for x in reversed(out[9 * c:9 * c + 8])) for c in range(3))])
+        res = subprocess.run([exe, "run", str(sched)], input="\n".join(lines) + "\n", capture_output=True, text=True)
+        assert res.returncode == 0, res.stderr[-800:]
+        got = res.stdout.strip().split("\n")
+        pos = 0
+        for line, w in zip(lines, want):
+            for expect in w:
+                if expect is not None:
+                    assert got[pos].strip() == expect, line[:40]
+                    n += 1
+                pos += 1
+        assert pos == len(got)
+    assert n == 2 * sum(dv.CHAIN_OPS.values())
+
+
+def test_results_stay_within_the_envelopes_figures(work):
+    """tests/golden/lazy_envelope.json bounds every result for ALL inputs of a class; the concrete results of the curve
+    and tower groups - random operands, the + p representatives, the edge:top records at the top of the classes - must
+    have a true magnitude no larger than the table's figure for their operation (common path: two ordinary, different
+    points; the special cases return copies and literal zeros)"""
+    import json
+    with open(os.path.join(HERE, "golden", "lazy_envelope.json")) as f:
+        env = json.load(f)
+    U, P = env["unit_per_p"], dv.P
+    ops = env["curve"]["ops"]
+    names = {"add": ["add(A, A)", "add(M any image, M any image)"],
+             "add_acc": ["add_acc(A, A)", "add_acc(M any image, M any image)"],
+             "dbl": ["dbl(A)", "dbl(M any image)"], "dbl_affine": ["dbl_affine(x, y < 2p)"],
+             "madd_acc": ["madd_acc(A, T)", "madd_acc(A, -T)"], "add_mixed": ["add_mixed(A, T)", "add_mixed(A, -T)"],
+             "item_chain": None}
+    n = 0
+    for r, out in zip(work["recs"]["curve"], work["res"]["curve"]):
+        if r.op not in names or not (r.kind in ("random", "edge:top")):
+            continue
+        if r.op == "item_chain":
+            bound = [env["curve"]["chains"]["msm_accumulate: acc"][c][1] for c in ("x", "y", "zz", "zzz")]
+        else:
+            bound = [max(ops[k][c][1] for k in names[r.op]) for c in ("x", "y", "zz", "zzz")]
+        for c in range(4):
+            v = dv.val(out[9 * c:9 * c + 9])
+            assert v * U <= bound[c] * P, f"{r.describe()}: coordinate {c} is {v / P:.4f} p, the table says {bound[c] / U:.4f} p"
+        n += 1
+    assert n > 1000
+    tw, n = env["tower"]["ops"], 0
+    for r, out in zip(work["recs"]["tower"], work["res"]["tower"]):
+        key = f"f12_frob {r.aux}" if r.op == "f12_frob" else r.op
+        for c in range(12):
+            v = dv.val(out[9 * c:9 * c + 9])
+            assert v * U <= tw[key][1] * P, f"{r.describe()}: coefficient {c} is {v / P:.4f} p, the table says {tw[key][1] / U:.4f} p"
+        n += 1
+    assert n > 2000
 
 
 # ---- the checker sees defects ---------------------------------------------------------------------------------------

@@ -294,7 +294,8 @@ def test_envelope_equals_the_committed_table(plain, cases, tmp_path):
     env = full_envelope(plain, cs, path, tmp_path)
     with open(GOLDEN) as f:
         want = json.load(f)
-    want = {k: v for k, v in want.items() if k != "rounds"}         # tests/test_round_elem_host.py owns that section
+    # tests/test_round_elem_host.py, test_curve_envelope_host.py and test_tower_envelope_host.py own these sections
+    want = {k: v for k, v in want.items() if k not in ("rounds", "curve", "quad", "lagrange", "tower")}
     assert sorted(env) == sorted(want)
     for key in env:
         assert env[key] == want[key], f"{key} differs from tests/golden/lazy_envelope.json"
@@ -415,6 +416,10 @@ if __name__ == "__main__":          # rewrite the golden table: python -m tests.
         env = full_envelope(exe, cs, str(dd / "cases.bin"), d)
     from tests.test_round_elem_host import round_envelope
     env["rounds"] = round_envelope()                                # the whole file anew: nothing stale survives
+    from tests.test_curve_envelope_host import curve_envelope
+    from tests.test_tower_envelope_host import tower_envelope
+    env.update(curve_envelope())                                    # "curve", "quad", "lagrange"
+    env["tower"] = tower_envelope()
     with open(GOLDEN, "w") as f:
         json.dump(env, f, indent=1, sort_keys=True)
         f.write("\n")
